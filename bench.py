@@ -9,13 +9,18 @@ loop (<= 30 iterations, each scan stops at its own convergence, MO:1848-1859), a
 back.  Every step registers a DIFFERENT batch (`--batches` distinct batches are cycled); `--handles` (3)
 handles sharing the resident map form a software pipeline: batches k+1 and k+2 are staged, sorted and STARTED
 while batch k still iterates, and only then are the results of batch k collected (two handles leave the GPU
-alone with the tail of one batch while the host prepares the next: 357 k against 416 k registrations/s).  The roofline of the dominant kernel is measured
-in the same run by a separate pass in which the kernel has the GPU to itself (`--roofline-pass-only` makes
-that pass the only timed region, for rocprofv3).  Also reported, never as `value`: the same stream with the records coming from pinned HOST memory
+alone with the tail of one batch while the host prepares the next: 357 k against 416 k registrations/s).
+
+A plain run sets up, warms up, times the steps and prints the result line; `--dump-outputs DIR` also writes what the
+last timed step handed back (poses and per-scan results, .npy).  Everything else is measured with `--full` only: the
+roofline of the dominant kernel, from a separate pass in which the kernel has the GPU to itself (`--roofline-pass-only`
+makes that pass the only timed region, for rocprofv3), the same stream with the records coming from pinned HOST memory
 over PCIe (`streamed_h2d`), the GN loop alone on a pre-sorted resident batch (`gn_loop_only`, round 1's
-definition), and the single-scan sequence a patched node issues per callback (`single_scan_node_path_ms`).
+definition), the single-scan sequence a patched node issues per callback (`single_scan_node_path_ms`), the pose
+errors, and the CPU baseline -- all beside `value`, never as it.
 
   python bench.py --gpus 1 --steps 5 --warmup 2
+  python bench.py --gpus 1 --steps 5 --warmup 2 --full
   python bench.py --gpus N ...            (starts its own N ranks: a child `python -m torch.distributed.run`, before any GPU call)
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...      (the same, started by the caller)
   python bench.py --gpus N --inlib ...    (ONE process, cfg.n_devices = N: the in-library multi-GPU mode a patched node uses)
@@ -37,6 +42,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+T_START = time.perf_counter()
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 BYTES_PER_POINT_ITER = 72  # 12 B scan xyz + 5 x 12 B winning neighbours
@@ -138,6 +144,51 @@ def to_records(scans, stride):
     return rec
 
 
+def device_records(scans, stride, device):
+    """The bytes of to_records(), assembled in device memory (only the x,y,z go over PCIe)."""
+    import torch
+    xyz = torch.from_numpy(np.concatenate(scans)).to(device)
+    rec = torch.zeros((len(xyz), stride // 4), dtype=torch.float32, device=device)
+    rec[:, :3] = xyz
+    if stride >= 32:
+        rec[:, 3] = 1.0
+    return rec
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, poses, results):
+    """What a caller of the timed path receives for one batch: the poses and every field of the per-scan results, one
+    DIR/<name>.npy each (float fields as float32, integer fields as float64: exact).  Past 64 MB in all, a fixed seeded
+    sample of the scans is written, with its indices as scan_index.npy."""
+    arrays = {"poses": np.asarray(poses, np.float32)}
+    for name, _ in results[0]._fields_:
+        a = np.array([np.ctypeslib.as_array(v) if hasattr(v, "_length_") else v for v in (getattr(r, name) for r in results)])
+        arrays[name] = a.astype(np.float32 if a.dtype.kind == "f" else np.float64)
+    n = len(arrays["poses"])
+    per_scan = sum(a.nbytes for a in arrays.values()) / n
+    if per_scan * n > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(n, int(DUMP_LIMIT_BYTES // (per_scan + 8)), replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+        arrays["scan_index"] = keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+GEN_PROCESSES, GEN_THREADS = 4, 2       # query casting: worker processes, threads in each (one casts while one voxel-filters)
+
+
+def cast_queries(sensor, q_range, case_kw):
+    """Worker process: queries q_range[0] .. q_range[1]-1 of the synthetic case (scan, true pose, initial guess)."""
+    import torch
+    torch.set_num_threads(1)                # (the host-side ops are small: more threads only contend with the other workers)
+    synth = importlib.import_module("lio-slam_amd.synth")
+    case = synth.make_case(sensor, q_range=q_range, with_map=False, workers=GEN_THREADS, **case_kw)
+    return [q for q in case["queries"] if q is not None]
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher (the form the driver records): start the N ranks as a child
     `python -m torch.distributed.run` BEFORE this process touches the GPU (nothing is re-exec'ed: the parent never
@@ -177,9 +228,13 @@ def main():
     ap.add_argument("--stride", type=int, default=32, help="bytes per input record (32 = pcl::PointXYZI, 16 = xyzi floats, 12 = packed xyz)")
     ap.add_argument("--sensor", default="hdl64")
     ap.add_argument("--keyframes", type=int, default=200)
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beside `value`: roofline pass, secondary "
+                    "measurements, pose errors, CPU baseline (a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write the poses and per-scan results of "
+                    "the last timed step to DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--cpu-seconds", type=float, default=24.0)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements (streamed H2D, GN loop only, node path, feeders)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary measurements (streamed H2D, GN loop only, node path, feeders)")
     ap.add_argument("--variant", type=int, default=1, help="scan points per thread (1, 2, 4)")
     ap.add_argument("--case-cache", default="", help="npz path: load the synthetic case if present, else generate and save")
     ap.add_argument("--lds", type=int, default=0)
@@ -252,7 +307,7 @@ def main():
 
     def log(msg):
         if rank == 0:
-            print(f"[bench] {msg}", file=sys.stderr, flush=True)
+            print(f"[bench {time.perf_counter() - T_START:6.1f}s] {msg}", file=sys.stderr, flush=True)
 
     pkg = importlib.import_module("lio-slam_amd")
     synth = importlib.import_module("lio-slam_amd.synth")
@@ -277,9 +332,19 @@ def main():
                 del cat
                 return z["map"], sc, z["poses0"], z["poses_true"]
             log("case cache was generated for another workload size: regenerating")
-        case = synth.make_case(args.sensor, n_keyframes=args.keyframes, seed=synth.BASE_SEED, n_queries=NQ,
-                               device=f"cuda:{local_rank}", lawnmower=args.lawnmower, workers=min(8, host_cores()),
-                               progress=lambda k, n: log(f"map keyframe {k}/{n}"), **leafs)
+        # The queries are cast by worker processes while this one builds the map: the host side of a ray cast (some 600
+        # small torch ops, ~3.5 ms) does not go faster with more threads in one process, but it does with more processes.
+        # Every keyframe and every query has its own seed, so the case is the same whatever the schedule.
+        import multiprocessing
+        from concurrent.futures import ProcessPoolExecutor
+        common = dict(n_keyframes=args.keyframes, seed=synth.BASE_SEED, n_queries=NQ, device=f"cuda:{local_rank}",
+                      lawnmower=args.lawnmower, **leafs)
+        n_proc = min(GEN_PROCESSES, max(1, host_cores() // 4))
+        per = -(-NQ // (4 * n_proc))                   # four chunks per process, so that they finish together
+        with ProcessPoolExecutor(n_proc, mp_context=multiprocessing.get_context("spawn")) as ex:
+            jobs = [ex.submit(cast_queries, args.sensor, (a, min(a + per, NQ)), common) for a in range(0, NQ, per)]
+            case = synth.make_case(args.sensor, q_range=(0, 0), progress=lambda k, n: log(f"map keyframe {k}/{n}"), **common)
+            case["queries"] = [q for j in jobs for q in j.result()]
         keyframes.extend(case["keyframes"])
         sc = [q["scan"] for q in case["queries"]]
         p0 = np.stack([q["pose_init"] for q in case["queries"]]).astype(np.float32)
@@ -332,9 +397,9 @@ def main():
     stride = args.stride
     batch_scans = [scans[b * B:(b + 1) * B] for b in range(NB)]
     batch_npts = [[len(s) for s in bs] for bs in batch_scans]
-    batch_rec = [to_records(bs, stride) for bs in batch_scans]
-    dev_rec = [torch.from_numpy(r).cuda() for r in batch_rec]
+    dev_rec = [device_records(bs, stride, "cuda") for bs in batch_scans]
     torch.cuda.synchronize()
+    log("records resident")
 
     # -------------------------------------------------------------- engine
     kcfg = dict(device_id=local_rank, profile=1, max_batch=args.batch, use_graph=1 if args.graph else 0, graph_iters=max(args.graph, 1), lookahead=args.lookahead, kernel_variant=args.variant,
@@ -448,43 +513,47 @@ def main():
     value = B * args.steps / elapsed if not (args.roofline_pass_only and not sharded) else 0.0
     last_b = 0 if (args.roofline_pass_only and not sharded) else (args.warmup + args.steps - 1) % NB   # the batch of the last timed step
 
-    # per-launch accounting of the dominant kernel from the LAST timed step (HIP events on the handle's stream)
+    # the LAST timed step: what the timed path handed back (--dump-outputs writes it) and, with the roofline, the per-launch
+    # accounting of the dominant kernel (HIP events on the handle's stream)
+    with_roofline = args.full or args.roofline_pass_only
     ns_last = n_s[last_b * B:(last_b + 1) * B]
     if runner:
         poses_last, results = runner.results(with_results=True)
         iters = np.array([r.iters for r in results])
-        lms, pts_per_launch = [], []
-        for (a, b_), hh in zip(runner.split, runner.handles):      # every sub-batch has its own launches
-            pr = hh.profile()
-            for i in range(pr.n_launches):
-                lms.append(pr.launch_ms[i])
-                # this rank handles 1/world of the points of the scans still iterating
-                pts_per_launch.append(float(ns_last[a:b_][iters[a:b_] > i].sum()) / world)
-        lms, pts_per_launch = np.array(lms, dtype=np.float64), np.array(pts_per_launch, dtype=np.float64)
-        prof = None
+        if with_roofline:
+            lms, pts_per_launch = [], []
+            for (a, b_), hh in zip(runner.split, runner.handles):      # every sub-batch has its own launches
+                pr = hh.profile()
+                for i in range(pr.n_launches):
+                    lms.append(pr.launch_ms[i])
+                    # this rank handles 1/world of the points of the scans still iterating
+                    pts_per_launch.append(float(ns_last[a:b_][iters[a:b_] > i].sum()) / world)
+            lms, pts_per_launch = np.array(lms, dtype=np.float64), np.array(pts_per_launch, dtype=np.float64)
     else:
         h_last = handles[(args.steps - 1) % len(handles)]
         if args.roofline_pass_only:                   # (profiling run: the streamed region was skipped; one plain batch for the trace)
             h_last = handles[0]
             h_last.batch_upload(batch_scans[0]); h_last.batch_set_poses(poses0[:B]); h_last.batch_run()
         poses_last, results = h_last.batch_results(with_results=True)
-        prof = h_last.profile()
         iters = np.array([r.iters for r in results])
-        # a unit = one launch (eager) or one replay of a captured chunk of unit_iters launches; the
-        # average launch duration and the average algorithmic bytes are both taken over ALL launches
-        # of k_s2m_iterate, like the rocprofv3 kernel-trace average
-        ui = max(prof.unit_iters, 1)
-        n_launch = prof.n_units * ui
-        unit_ms = np.array(prof.launch_ms[:prof.n_units], dtype=np.float64)
-        lms = np.repeat(unit_ms / ui, ui)
-        # (in-library multi-GPU: the launches timed are device 0's, which handles 1/n_dev of the live points)
-        pts_per_launch = np.array([int(ns_last[iters > i].sum()) for i in range(n_launch)], dtype=np.float64) / n_dev
+        if with_roofline:
+            prof = h_last.profile()
+            # a unit = one launch (eager) or one replay of a captured chunk of unit_iters launches; the
+            # average launch duration and the average algorithmic bytes are both taken over ALL launches
+            # of k_s2m_iterate, like the rocprofv3 kernel-trace average
+            ui = max(prof.unit_iters, 1)
+            n_launch = prof.n_units * ui
+            unit_ms = np.array(prof.launch_ms[:prof.n_units], dtype=np.float64)
+            lms = np.repeat(unit_ms / ui, ui)
+            # (in-library multi-GPU: the launches timed are device 0's, which handles 1/n_dev of the live points)
+            pts_per_launch = np.array([int(ns_last[iters > i].sum()) for i in range(n_launch)], dtype=np.float64) / n_dev
+    timed_outputs = (poses_last, results)
     # Roofline pass (single GPU): the dominant kernel ALONE on the GPU.  In the streamed region the launch loops of two
     # batches overlap on purpose (that is what hides the tails), so the duration of a launch there measures how the
     # GPU is shared, not the kernel.  Here one pre-sorted resident batch is re-registered from its initial poses with
     # nothing else in flight, and every launch of every step is bracketed by HIP events on the handle's stream.
     roof = None
-    if not sharded and not inlib:
+    if with_roofline and not sharded and not inlib:
         g = handles[0]
         g.batch_upload(batch_scans[0])
         n_roof = args.steps if args.roofline_pass_only else 32
@@ -514,44 +583,10 @@ def main():
             elapsed = roof["elapsed"]
             value = B * args.steps / elapsed
             keep["poses"] = p_roof
-    live = lms > 0
-    in_stream = None
-    if roof is not None and roof["launches"]:
-        # single GPU: averages over ALL launches of ALL steps of the roofline pass (what rocprofv3's kernel statistics
-        # average too when the same pass is traced: `--roofline-pass-only`)
-        tot_ms = float(np.sum(roof["unit_ms"]))
-        ms_per_launch = tot_ms / roof["launches"]
-        bytes_per_launch = BYTES_PER_POINT_ITER * roof["point_iters"] / roof["launches"]
-        achieved = BYTES_PER_POINT_ITER * roof["point_iters"] / (tot_ms * 1e-3) / 1e9
-        if streamed_acct.get("launches"):
-            in_stream = {"ms_per_launch_while_two_batches_overlap": float(np.sum(streamed_acct["unit_ms"])) / streamed_acct["launches"],
-                         "launches": int(streamed_acct["launches"]),
-                         "algorithmic_GBs_of_the_whole_pipeline": BYTES_PER_POINT_ITER * streamed_acct["point_iters"] / elapsed / 1e9,
-                         "note": "72 B x every live point-iteration of the timed region / its wall time (staging and tile sort included)"}
-    else:
-        bytes_per_launch = BYTES_PER_POINT_ITER * pts_per_launch[live].mean() if live.any() else 0.0
-        ms_per_launch = float(lms[live].mean()) if live.any() else float("nan")
-        achieved = bytes_per_launch / (ms_per_launch * 1e-3) / 1e9 if live.any() else 0.0
-
-    traffic = None
-    tpath = os.path.join(ROOT, "profiles", "r03_traffic.json")
-    if os.path.exists(tpath) and not sharded and not inlib:
-        tj = json.load(open(tpath))
-        if (tj.get("scans_per_step"), tj.get("N_m")) == (B, int(len(map_xyz))):
-            traffic = tj["hbm_bytes_per_launch"]      # rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, see DESIGN.md
-
-    # The roofline of the resource that actually binds the kernel: vector-ALU issue, with the texture addresser next to it.
-    # Counter-derived (SQ_ACTIVE_INST_VALU, GRBM_GUI_ACTIVE, GRBM_TA_BUSY need rocprofv3 --pmc passes), so it is a STORED figure
-    # of the builder's profiling session for this exact workload, like `roofline.traffic`; see tools/issue_roofline.py.
-    issue = None
-    ipath = os.path.join(ROOT, "profiles", "r03_issue_roofline.json")
-    if os.path.exists(ipath) and traffic is not None:
-        issue = json.load(open(ipath))
-        issue["source"] = ("stored figure: separate rocprofv3 --pmc passes of `bench.py --roofline-pass-only` by the builder (profiles/r03_pmc_SQ.txt, "
-                           "r03_pmc_SQ2.txt, tools/issue_roofline.py), same workload as this run (scans_per_step, N_m checked); not a counter of this run")
-        issue["note"] = (f"k_s2m_iterate issues a vector instruction in {100 * issue['frac']:.0f} % of all cycles of every SIMD while its divergent "
-                         f"16-byte candidate gathers keep the texture addresser busy {100 * issue['texture_addresser_busy_frac']:.0f} % of the time: "
-                         "it sits on both limiters (and on the dependent loads five waves per SIMD only partly hide), HBM is at 12 %")
+            timed_outputs = g.batch_results(with_results=True)      # (the timed path of this mode)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *timed_outputs)
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
 
     out = {
         "metric": "scan-to-map registrations/sec, 64x1800 scan vs 200-keyframe map; pose RMSE",
@@ -581,7 +616,52 @@ def main():
             "kernel": {"points_per_thread": int(args.variant), "lds_staging": int(args.lds), "pipeline": "fused",
                        "nn_cache": args.nncache, "tile_sorted_scans": int(args.sort), "cell_div": int(args.celldiv)},
         },
-        "roofline": {
+        "map_build_ms": prof0.map_build_ms, "map_upload_ms": prof0.map_upload_ms,
+        "map_rows": {"x_sub": prof0.map_x_sub, "tight_tables": prof0.map_tight_tables, "first_try": prof0.map_first_try, "points_per_occupied_cell": round(prof0.map_pts_per_cell, 2)},
+        "grid_cells": int(prof0.n_cells),
+    }
+
+    if with_roofline:
+        live = lms > 0
+        in_stream = None
+        if roof is not None and roof["launches"]:
+            # single GPU: averages over ALL launches of ALL steps of the roofline pass (what rocprofv3's kernel statistics
+            # average too when the same pass is traced: `--roofline-pass-only`)
+            tot_ms = float(np.sum(roof["unit_ms"]))
+            ms_per_launch = tot_ms / roof["launches"]
+            bytes_per_launch = BYTES_PER_POINT_ITER * roof["point_iters"] / roof["launches"]
+            achieved = BYTES_PER_POINT_ITER * roof["point_iters"] / (tot_ms * 1e-3) / 1e9
+            if streamed_acct.get("launches"):
+                in_stream = {"ms_per_launch_while_two_batches_overlap": float(np.sum(streamed_acct["unit_ms"])) / streamed_acct["launches"],
+                             "launches": int(streamed_acct["launches"]),
+                             "algorithmic_GBs_of_the_whole_pipeline": BYTES_PER_POINT_ITER * streamed_acct["point_iters"] / elapsed / 1e9,
+                             "note": "72 B x every live point-iteration of the timed region / its wall time (staging and tile sort included)"}
+        else:
+            bytes_per_launch = BYTES_PER_POINT_ITER * pts_per_launch[live].mean() if live.any() else 0.0
+            ms_per_launch = float(lms[live].mean()) if live.any() else float("nan")
+            achieved = bytes_per_launch / (ms_per_launch * 1e-3) / 1e9 if live.any() else 0.0
+
+        traffic = None
+        tpath = os.path.join(ROOT, "profiles", "r03_traffic.json")
+        if os.path.exists(tpath) and not sharded and not inlib:
+            tj = json.load(open(tpath))
+            if (tj.get("scans_per_step"), tj.get("N_m")) == (B, int(len(map_xyz))):
+                traffic = tj["hbm_bytes_per_launch"]      # rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, see DESIGN.md
+
+        # The roofline of the resource that actually binds the kernel: vector-ALU issue, with the texture addresser next to it.
+        # Counter-derived (SQ_ACTIVE_INST_VALU, GRBM_GUI_ACTIVE, GRBM_TA_BUSY need rocprofv3 --pmc passes), so it is a STORED figure
+        # of the builder's profiling session for this exact workload, like `roofline.traffic`; see tools/issue_roofline.py.
+        issue = None
+        ipath = os.path.join(ROOT, "profiles", "r03_issue_roofline.json")
+        if os.path.exists(ipath) and traffic is not None:
+            issue = json.load(open(ipath))
+            issue["source"] = ("stored figure: separate rocprofv3 --pmc passes of `bench.py --roofline-pass-only` by the builder (profiles/r03_pmc_SQ.txt, "
+                               "r03_pmc_SQ2.txt, tools/issue_roofline.py), same workload as this run (scans_per_step, N_m checked); not a counter of this run")
+            issue["note"] = (f"k_s2m_iterate issues a vector instruction in {100 * issue['frac']:.0f} % of all cycles of every SIMD while its divergent "
+                             f"16-byte candidate gathers keep the texture addresser busy {100 * issue['texture_addresser_busy_frac']:.0f} % of the time: "
+                             "it sits on both limiters (and on the dependent loads five waves per SIMD only partly hide), HBM is at 12 %")
+
+        out["roofline"] = {
             "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
             "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
             "traffic_source": None if traffic is None else "stored figure: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command run by the "
@@ -599,23 +679,20 @@ def main():
                         "around every graph replay of every step on the handle's stream; algorithmic bytes = 72 B x live point-iterations "
                         "of the same steps.  (In the streamed region two batches' launch loops overlap on purpose, see in_streamed_region.)"
                         if not (sharded or inlib) else "HIP events around the launches of the last timed step" + (" on device 0" if inlib else ""),
-        },
-        "roofline_issue": issue,
-        "map_build_ms": prof0.map_build_ms, "map_upload_ms": prof0.map_upload_ms,
-        "map_rows": {"x_sub": prof0.map_x_sub, "tight_tables": prof0.map_tight_tables, "first_try": prof0.map_first_try, "points_per_occupied_cell": round(prof0.map_pts_per_cell, 2)},
-        "grid_cells": int(prof0.n_cells),
-    }
+        }
+        out["roofline_issue"] = issue
 
     if inlib:
         pm = handles[0].profile()
         out["inlib_exchange"] = {"form": {0: "peer stores from a kernel", 1: "hipMemcpyPeerAsync", 2: "host memory (round 2)"}.get(int(pm.multi_exchange)),
                                  "gn_iterations_enqueued_last_step": int(pm.multi_iterations), "stream_syncs_in_the_loop_last_step": int(pm.multi_stream_syncs),
                                  "convergence_event_waits_last_step": int(pm.multi_event_waits)}
-    extras = not args.no_extras and not inlib
+    extras = args.full and not args.no_extras and not inlib
     # -------------------------------------------------- secondary measurements (never `value`)
     if extras and not sharded:
         # (1) the same stream with the records in pinned HOST memory: per-scan H2D over PCIe inside the timed region
         pins = []
+        batch_rec = [to_records(bs, stride) for bs in batch_scans]
         for r in batch_rec:
             p = pkg.PinnedBuffer(r.nbytes)
             p.array[:] = r.view(np.uint8).reshape(-1)
@@ -748,10 +825,10 @@ def main():
 
     if rank == 0:
         gpu0 = keep.get("poses")
-        if gpu0 is not None:
+        if gpu0 is not None and args.full:
             rt, rr = rmse_pair(gpu0, poses_true[:B], synth)
             out["pose_rmse_vs_truth"] = {"trans_m": rt, "rot_rad": rr, "scans": B}
-        if not args.no_cpu and world == 1 and not inlib:      # the CPU baseline is timed at N = 1 only (the other ranks would idle)
+        if args.full and not args.no_cpu and world == 1 and not inlib:      # the CPU baseline is timed at N = 1 only (the other ranks would idle)
             cb, cpu_poses, cpu_iters = cpu_baseline(scans[:B], map_xyz, poses0[:B], args.cpu_seconds, log)
             out["cpu_baseline"] = cb
             k = len(cpu_poses)

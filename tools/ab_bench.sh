@@ -8,7 +8,7 @@ mkdir -p "$out"
 for round in 1 2; do
   for v in "$@"; do
     IFS='|' read -r label lib extra envs case <<< "$v"
-    env LIOGPU_LIB=$lib $envs python bench.py --no-cpu --no-extras --case-cache /tmp/ab_case_${case:-default}.npz $extra > "$out/bench_${label}_$round.json" 2> "$out/bench_${label}_$round.err" || exit 1
+    env LIOGPU_LIB=$lib $envs python bench.py --full --no-cpu --no-extras --case-cache /tmp/ab_case_${case:-default}.npz $extra > "$out/bench_${label}_$round.json" 2> "$out/bench_${label}_$round.err" || exit 1
     python - "$out/bench_${label}_$round.json" "$label" <<'PY' | tee -a "$out/ab.txt"
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -21,7 +21,7 @@ SETS=${@:-default jeep livox 6t dense whatif}
 one() { # tag, bench args...
     local tag=$1; shift
     local CASE=/tmp/case_$tag.npz
-    local B="python bench.py --no-cpu --no-extras --case-cache $CASE --label $tag $@"
+    local B="python bench.py --full --no-cpu --no-extras --case-cache $CASE --label $tag $@"
     timeout -k 10 900 $B --steps 8 --warmup 3 > $OUT/bench_$tag.json 2> $OUT/bench_$tag.err
     echo "$tag bench rc=$?"
     local R="$B --steps 6 --warmup 2 --roofline-pass-only"
