@@ -481,6 +481,34 @@ int  lio_kf_store_add_from_handle(lio_kf_store *s, lio_s2m_handle *h, int32_t sc
 int  lio_assemble_map_resident(lio_s2m_handle *h, lio_kf_store *s, int32_t n_selected, const int32_t *ids,
                                const float *poses, float leaf, void *out, size_t out_stride_bytes, size_t *n_out);
 
+/* ------------------------------------------------ surrounding keyframes (extractNearby MO:1519-1551) */
+typedef struct lio_nearby_config {
+    float  search_radius;    /* surroundingKeyframeSearchRadius, UT:316 default 50.0                  */
+    float  pose_density;     /* surroundingKeyframeDensity, UT:314 default 1.0 (the shipped yamls: 2.0) */
+    double recent_window_s;  /* the literal 10.0 of MO:1547                                            */
+} lio_nearby_config;
+void lio_nearby_default_config(lio_nearby_config *cfg);
+
+/* cloudKeyPoses6D[first .. first+n) of keyframes the store already holds: [roll,pitch,yaw,x,y,z] per keyframe (the order
+ * of transformTobeMapped) and its time (PointTypePose.time).  saveKeyFramesAndFactor MO:2107-2120 sets one, correctPoses
+ * MO:2184-2196 rewrites all of them.  times == NULL keeps the stored times (LIO_ERR_ARG for a keyframe that has none yet);
+ * non-finite values -> LIO_ERR_ARG.  Host only: never waits, and work already queued keeps the poses it was given; the
+ * next lio_assemble_map_nearby uploads what changed on its own stream. */
+int  lio_kf_store_set_poses(lio_kf_store *s, int32_t first, int32_t n, const float *poses, const double *times);
+
+/* extractSurroundingKeyFrames MO:1590-1603 + extractCloud MO:1556-1588 in one call: the keyframes are selected on the
+ * device from the stored poses (radius search around the last key pose, VoxelGrid at pose_density, nearest-pose relabel,
+ * the keyframes younger than recent_window_s before time_cur, the radius recheck of MO:1562; DESIGN.md states the tie and
+ * boundary conventions), then the map is assembled exactly as lio_assemble_map_resident does with those ids and their
+ * stored poses, for the same handle kinds (h may be NULL).  ids_out (may be NULL) receives the selected list in order,
+ * duplicates included; *n_ids its length.  `out` (may be NULL) holds out_cap records; a larger map -> LIO_ERR_ARG with the
+ * needed count in *n_out (the handle's map is installed all the same).  An empty store: LIO_OK, *n_ids = 0, the handle's
+ * map untouched (MO:1592-1593).  LIO_ERR_ARG when a keyframe has no pose, when the store and the handle live on different
+ * devices, and when ids_out is given with ids_cap < *n_ids (*n_ids is the needed count; nothing is built). */
+int  lio_assemble_map_nearby(lio_s2m_handle *h, lio_kf_store *s, const lio_nearby_config *cfg, double time_cur, float leaf,
+                             int32_t *ids_out, int32_t ids_cap, int32_t *n_ids, void *out, size_t out_stride_bytes,
+                             size_t out_cap, size_t *n_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -121,4 +121,48 @@ private:
     lio_s2m_handle* h_ = nullptr;
 };
 
+// surfCloudKeyFrames (MO:128) + cloudKeyPoses6D (MO:130) on the device, and extractSurroundingKeyFrames() MO:1590-1603
+// + extractCloud() MO:1556-1588 on them in one call
+class KeyframeStore {
+public:
+    explicit KeyframeStore(int32_t device_id = 0) { check(lio_kf_store_create(device_id, &s_), "lio_kf_store_create"); }
+    ~KeyframeStore() { lio_kf_store_destroy(s_); }
+    KeyframeStore(const KeyframeStore&) = delete;
+    KeyframeStore& operator=(const KeyframeStore&) = delete;
+
+    // saveKeyFramesAndFactor MO:2107-2142: the scan `s2m` has just registered becomes keyframe id, with its pose and time
+    int32_t addFromHandle(ScanToMap& s2m, const float pose6d[6], double time, int32_t scan = 0)
+    {
+        int32_t id = -1;
+        check(lio_kf_store_add_from_handle(s_, s2m.handle(), scan, &id), "lio_kf_store_add_from_handle");
+        check(lio_kf_store_set_poses(s_, id, 1, pose6d, &time), "lio_kf_store_set_poses");
+        return id;
+    }
+    // correctPoses MO:2184-2196: every pose [roll,pitch,yaw,x,y,z] x n, the times kept
+    void setPoses(int32_t first, int32_t n, const float* poses6d, const double* times = nullptr)
+    {
+        check(lio_kf_store_set_poses(s_, first, n, poses6d, times), "lio_kf_store_set_poses");
+    }
+    // extractSurroundingKeyFrames(): the local map of timeLaserInfoCur becomes s2m's resident map; returns its size
+    size_t extractSurroundingKeyFrames(ScanToMap& s2m, double timeLaserInfoCur, float surroundingKeyframeMapLeafSize,
+                                       const lio_nearby_config* cfg = nullptr)
+    {
+        lio_nearby_config c;
+        if (cfg) c = *cfg; else lio_nearby_default_config(&c);
+        int32_t n_ids = 0;
+        size_t n_map = 0;
+        check(lio_assemble_map_nearby(s2m.handle(), s_, &c, timeLaserInfoCur, surroundingKeyframeMapLeafSize, nullptr, 0, &n_ids,
+                                      nullptr, 0, 0, &n_map), "lio_assemble_map_nearby");
+        return n_map;
+    }
+    lio_kf_store* get() { return s_; }
+
+private:
+    static void check(int rc, const char* what)
+    {
+        if (rc < 0) throw Error(rc, std::string(what) + ": " + lio_last_error());
+    }
+    lio_kf_store* s_ = nullptr;
+};
+
 }  // namespace liogpu

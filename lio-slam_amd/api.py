@@ -86,6 +86,11 @@ PC2_UINT8, PC2_UINT16, PC2_INT32 = 2, 4, 5
 PC2_TIME_F32_SECONDS, PC2_TIME_U32_NS, PC2_TIME_U32_RAW, PC2_TIME_F64_STAMP = 0, 1, 2, 3
 
 
+class NearbyConfig(C.Structure):
+    """extractNearby's parameters (include/liogpu.h lio_nearby_config)."""
+    _fields_ = [("search_radius", C.c_float), ("pose_density", C.c_float), ("recent_window_s", C.c_double)]
+
+
 class FeatureConfig(C.Structure):
     _fields_ = [("N_SCAN", C.c_int32), ("edgeThreshold", C.c_float), ("surfThreshold", C.c_float),
                 ("surfLeafSize", C.c_float), ("device_id", C.c_int32)]
@@ -125,6 +130,7 @@ EXPORTS = [
     "lio_s2m_share_map", "lio_s2m_batch_upload_async", "lio_host_alloc", "lio_host_free", "lio_host_register",
     "lio_host_unregister", "lio_s2m_set_shard_plan", "lio_s2m_register_pc2", "lio_deskew_pc2", "lio_kf_store_add_device", "lio_kf_store_add_from_handle",
     "lio_s2m_register_raw", "lio_s2m_debug_persist_spin", "lio_device_alloc", "lio_device_free", "lio_device_upload",
+    "lio_nearby_default_config", "lio_kf_store_set_poses", "lio_assemble_map_nearby",
 ]
 
 
@@ -219,6 +225,11 @@ def load_library():
     L.lio_assemble_map_resident.argtypes = [vp, vp, i32, C.POINTER(i32), C.POINTER(f32), f32, vp, sz, C.POINTER(sz)]
     L.lio_assemble_map.argtypes = [vp, i32, i32, C.POINTER(vp), C.POINTER(sz), sz, C.POINTER(f32), f32, vp, sz,
                                    C.POINTER(sz)]
+    L.lio_nearby_default_config.argtypes = [C.POINTER(NearbyConfig)]
+    L.lio_nearby_default_config.restype = None
+    L.lio_kf_store_set_poses.argtypes = [vp, i32, i32, C.POINTER(f32), C.POINTER(f64)]
+    L.lio_assemble_map_nearby.argtypes = [vp, vp, C.POINTER(NearbyConfig), f64, f32, C.POINTER(i32), i32, C.POINTER(i32), vp, sz, sz,
+                                          C.POINTER(sz)]
     _LIB = L
     return L
 
@@ -696,6 +707,16 @@ def voxel_grid(xyzi, leaf, device_id=0):
     return _from_records(out, n_out.value), rc
 
 
+def nearby_default_config(**overrides):
+    cfg = NearbyConfig()
+    load_library().lio_nearby_default_config(C.byref(cfg))
+    for k, v in overrides.items():
+        if not hasattr(cfg, k):
+            raise AttributeError(k)
+        setattr(cfg, k, v)
+    return cfg
+
+
 # extractCloud, MO:1556-1588
 def assemble_map(clouds_xyzi, poses, leaf, s2m=None, device_id=0, want_output=True):
     recs = [_as_xyzi_records(c) for c in clouds_xyzi]
@@ -750,6 +771,35 @@ class KeyframeStore:
             s2m.h if s2m is not None else None, self.h, len(ids_a), ids_a.ctypes.data_as(C.POINTER(C.c_int32)), _f32p(p),
             leaf, out.ctypes.data if want_output else None, 32, C.byref(n_out)), "lio_assemble_map_resident")
         return (_from_records(out, n_out.value) if want_output else None), n_out.value, rc
+
+    def set_poses(self, first, poses, times=None):   # cloudKeyPoses6D: MO:2107-2120 (one), correctPoses MO:2184-2196 (all)
+        p = np.ascontiguousarray(poses, np.float32).reshape(-1, 6)
+        t = None if times is None else np.ascontiguousarray(times, np.float64).reshape(len(p))
+        _check(self.lib.lio_kf_store_set_poses(self.h, first, len(p), _f32p(p),
+                                               None if t is None else t.ctypes.data_as(C.POINTER(C.c_double))),
+               "lio_kf_store_set_poses")
+
+    def assemble_nearby(self, time_cur, leaf, s2m=None, want_ids=True, want_output=True, **cfg):
+        """extractSurroundingKeyFrames MO:1590-1603 + extractCloud MO:1556-1588 on the device -> (map or None, n_map, ids or
+        None, rc).  cfg: search_radius, pose_density, recent_window_s (lio_nearby_config)."""
+        c = nearby_default_config(**cfg)
+        n = len(self)
+        ids = np.zeros(max(2 * n, 1), np.int32) if want_ids else None   # the list holds at most 2N entries
+        cap = max(sum(int(self.lib.lio_kf_store_points(self.h, i)) for i in range(n)), 1) if want_output else 0
+        while True:
+            out = np.zeros((cap, 8), np.float32) if want_output else None
+            n_ids, n_out = C.c_int32(), C.c_size_t()
+            rc = self.lib.lio_assemble_map_nearby(
+                s2m.h if s2m is not None else None, self.h, C.byref(c), time_cur, leaf,
+                ids.ctypes.data_as(C.POINTER(C.c_int32)) if want_ids else None, len(ids) if want_ids else 0, C.byref(n_ids),
+                out.ctypes.data if want_output else None, 32, cap, C.byref(n_out))
+            if want_output and rc == -1 and n_out.value > cap:    # (more map than one copy of every cloud: room, and again)
+                cap = n_out.value
+                continue
+            _check(rc, "lio_assemble_map_nearby")
+            break
+        return ((_from_records(out, n_out.value) if want_output else None), n_out.value,
+                (ids[:n_ids.value].copy() if want_ids else None), rc)
 
     def close(self):
         if getattr(self, "h", None) and self.h.value:

@@ -6,7 +6,9 @@
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <math.h>
+#include <cmath>
 #include <string.h>
+#include <algorithm>
 #include <vector>
 
 #include "lio_handle.h"
@@ -172,8 +174,6 @@ __global__ __launch_bounds__(256) void k_bbox_reduce(const float* __restrict__ b
     }
 }
 
-struct LioVoxGrid { float inv; int min_b0, min_b1, min_b2, mul1, mul2, n_keys; };
-
 __global__ void k_xyzi4_to_aos(const float4* __restrict__ src, int n, unsigned char* __restrict__ dst, size_t stride)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -221,22 +221,11 @@ float ord2f(unsigned u)
     return f;
 }
 
-// K7 proper (lio_voxsort.h): keys -> stable LSD radix sort of (key, index) pairs -> segment heads -> in-order sums.  g describes
-// the voxel grid, n_keys its size (< 2^31).  (Rounds 1-2 used a counting sort with count / start / rank arrays over the whole
-// key space, atomics for the slots and a per-voxel sort for the order; round 3 first replaced the per-voxel sorts, then measured
-// the sorting form faster on every input -- map assembly 0.37 against 0.43 ms, the raw-sweep chain 0.50 against 0.57 ms at leaf
-// 0.4 m and 0.88 against 1.09 ms at 0.15 m, profiles/r03_k7_forms.txt -- and removed the counting form.)  `out` is allocated for the worst case (n voxels) so that the centroid kernels are
-// enqueued without waiting for the count; the one host wait (*n_out) comes last and overlaps them.
+// Room for sorting n pairs and summing their segments (ws) and for n centroids (out).
 template <class B>
-static int voxel_grid_sorted(const float4* d_in, int n, const LioVoxGrid& g, long long n_keys, B& out, int* n_out, hipStream_t s, LioVoxWs<B>& ws)
+static int vsort_reserve(int n, B& out, LioVoxWs<B>& ws)
 {
-    int bits = 1;
-    while (bits < 31 && (1LL << bits) < n_keys) ++bits;
-    const int passes = (bits + 7) / 8, dbits = (bits + passes - 1) / passes;      // e.g. 25 bits -> 4 passes of 7
-    const unsigned mask = (1u << dbits) - 1u;
-    const int items = n > (1 << 18) ? 8 : 4;
-    const int tile = LIO_VS_THREADS * items, n_blocks = (n + tile - 1) / tile;
-    const int n_hblk = (n + 1023) / 1024;
+    const int n_blocks = (n + LIO_VS_THREADS * 4 - 1) / (LIO_VS_THREADS * 4), n_hblk = (n + 1023) / 1024;
     HIPCHK(ws.pairs_a.alloc(sizeof(uint2) * (size_t)n));
     HIPCHK(ws.pairs_b.alloc(sizeof(uint2) * (size_t)n));
     HIPCHK(ws.hist.alloc(sizeof(int) * (size_t)LIO_VS_BINS * n_blocks));
@@ -246,9 +235,18 @@ static int voxel_grid_sorted(const float4* d_in, int n, const LioVoxGrid& g, lon
     HIPCHK(ws.row_total.alloc(sizeof(int) * LIO_VS_BINS));
     HIPCHK(ws.large.alloc(sizeof(int) * ((size_t)n + 1)));
     HIPCHK(out.alloc(sizeof(float4) * (size_t)n));
-    LioVsGrid vg = { g.inv, g.min_b0, g.min_b1, g.min_b2, g.mul1, g.mul2 };
+    return LIO_OK;
+}
+
+// Stable LSD radix sort of the n pairs in ws.pairs_a by their low `bits` key bits; returns the buffer that holds the result.
+template <class B>
+static uint2* vsort_pairs(int n, int bits, hipStream_t s, LioVoxWs<B>& ws)
+{
+    const int passes = (bits + 7) / 8, dbits = (bits + passes - 1) / passes;      // e.g. 25 bits -> 4 passes of 7
+    const unsigned mask = dbits >= 32 ? 0xffffffffu : (1u << dbits) - 1u;
+    const int items = n > (1 << 18) ? 8 : 4;
+    const int tile = LIO_VS_THREADS * items, n_blocks = (n + tile - 1) / tile;
     uint2 *a = ws.pairs_a.template as<uint2>(), *b = ws.pairs_b.template as<uint2>();
-    hipLaunchKernelGGL(k_vsort_keys, dim3((n + 255) / 256), dim3(256), 0, s, vg, d_in, n, a);
     for (int p = 0; p < passes; ++p) {
         const int shift = p * dbits;
         int* hist = ws.hist.template as<int>();
@@ -260,17 +258,44 @@ static int voxel_grid_sorted(const float4* d_in, int n, const LioVoxGrid& g, lon
         else hipLaunchKernelGGL(k_vsort_scatter<4>, dim3(n_blocks), dim3(LIO_VS_THREADS), 0, s, a, n, shift, mask, hist, row_total, n_blocks, b);
         uint2* t = a; a = b; b = t;
     }
+    return a;
+}
+
+// Segments (voxels) of the sorted pairs `a` and the in-order centroid of each -> out[0 .. ws.d_no[0]); nothing waits.
+template <class B>
+static int vsort_centroids(const float4* d_in, const uint2* a, int n, B& out, hipStream_t s, LioVoxWs<B>& ws)
+{
+    const int n_hblk = (n + 1023) / 1024;
     int* d_no = ws.d_no.template as<int>();
     HIPCHK(hipMemsetAsync(d_no, 0, 2 * sizeof(int), s));                          // [0] voxels, [1] crowded voxels queued
     hipLaunchKernelGGL(k_vsort_head_count, dim3(n_hblk), dim3(256), 0, s, a, n, ws.blk_heads.template as<int>());
     hipLaunchKernelGGL(k_vsort_scan_small, dim3(1), dim3(256), 0, s, ws.blk_heads.template as<int>(), n_hblk, d_no);
     hipLaunchKernelGGL(k_vsort_head_emit, dim3(n_hblk), dim3(256), 0, s, a, n, ws.blk_heads.template as<int>(), d_no, ws.seg_start.template as<int>());
-    int no = 0;
-    HIPCHK(hipMemcpyAsync(&no, d_no, sizeof(int), hipMemcpyDeviceToHost, s));
     hipLaunchKernelGGL(k_vsort_centroid, dim3((n_hblk + 3) / 4), dim3(256), 0, s, d_in, a, n, ws.seg_start.template as<int>(),
                        ws.blk_heads.template as<int>(), n_hblk, d_no, out.template as<float4>(), ws.large.template as<int>(), d_no + 1);
     hipLaunchKernelGGL(k_vsort_centroid_large, dim3(n < 1024 * 64 ? (n + 63) / 64 : 1024), dim3(256), 0, s, d_in, a, ws.seg_start.template as<int>(),
                        out.template as<float4>(), ws.large.template as<int>(), d_no + 1);
+    return LIO_OK;
+}
+
+// K7 proper (lio_voxsort.h): keys -> stable LSD radix sort of (key, index) pairs -> segment heads -> in-order sums.  g describes
+// the voxel grid, n_keys its size (< 2^31).  (Rounds 1-2 used a counting sort with count / start / rank arrays over the whole
+// key space, atomics for the slots and a per-voxel sort for the order; round 3 first replaced the per-voxel sorts, then measured
+// the sorting form faster on every input -- map assembly 0.37 against 0.43 ms, the raw-sweep chain 0.50 against 0.57 ms at leaf
+// 0.4 m and 0.88 against 1.09 ms at 0.15 m, profiles/r03_k7_forms.txt -- and removed the counting form.)  `out` is allocated for the worst case (n voxels) so that the centroid kernels are
+// enqueued without waiting for the count; the one host wait (*n_out) comes last and overlaps them.
+template <class B>
+static int voxel_grid_sorted(const float4* d_in, int n, const LioVsGrid& vg, long long n_keys, B& out, int* n_out, hipStream_t s, LioVoxWs<B>& ws)
+{
+    int bits = 1;
+    while (bits < 31 && (1LL << bits) < n_keys) ++bits;
+    int rc = vsort_reserve<B>(n, out, ws);
+    if (rc != LIO_OK) return rc;
+    hipLaunchKernelGGL(k_vsort_keys, dim3((n + 255) / 256), dim3(256), 0, s, vg, d_in, n, ws.pairs_a.template as<uint2>());
+    const uint2* a = vsort_pairs<B>(n, bits, s, ws);
+    if ((rc = vsort_centroids<B>(d_in, a, n, out, s, ws)) != LIO_OK) return rc;
+    int no = 0;
+    HIPCHK(hipMemcpyAsync(&no, ws.d_no.p, sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));                                              // (`no`; the centroid kernels ran under this wait)
     HIPCHK(hipGetLastError());
     *n_out = no;
@@ -303,28 +328,18 @@ int voxel_grid_device(const float4* d_in, int n, float leaf, B& out, int* n_out,
     float mn[3], mx[3];
     for (int a = 0; a < 3; ++a) { mn[a] = ord2f(hb[a]); mx[a] = ord2f(hb[3 + a]); }
     if (box) for (int a = 0; a < 3; ++a) { box[a] = mn[a]; box[3 + a] = mx[a]; }
-    const float inv = 1.0f / leaf;
-    const long long dx = (long long)((mx[0] - mn[0]) * inv) + 1, dy = (long long)((mx[1] - mn[1]) * inv) + 1,
-                    dz = (long long)((mx[2] - mn[2]) * inv) + 1;
-    // (a box that is not finite -- inf coordinates, or no finite point at all -- is outside what PCL defines: the conversions
-    // above are then meaningless; such a cloud takes the same way out as an overflowing index, deterministically)
-    bool finite_box = true;
-    for (int a = 0; a < 3; ++a) finite_box = finite_box && (mn[a] <= mx[a]) && fabsf(mn[a]) <= 3.0e38f && fabsf(mx[a]) <= 3.0e38f;
-    if (!finite_box || dx <= 0 || dy <= 0 || dz <= 0 || (double)dx * (double)dy * (double)dz > 2147483647.0) {   // "Leaf size is too small": PCL copies the input
+    // (a box that is not finite -- inf coordinates, or no finite point at all -- is outside what PCL defines; such a cloud
+    // takes the same way out as an overflowing index, deterministically)
+    LioVsGrid g;
+    long long n_keys_ll = 0;
+    const int grc = lio_vs_grid_from_box(mn, mx, 1.0f / leaf, &g, &n_keys_ll);
+    if (grc == 1) {                                  // "Leaf size is too small": PCL copies the input
         HIPCHK(out.alloc(sizeof(float4) * (size_t)n));
         HIPCHK(hipMemcpyAsync(out.p, d_in, sizeof(float4) * (size_t)n, hipMemcpyDeviceToDevice, s));
         *n_out = n;
         return 1;
     }
-    LioVoxGrid g;
-    g.inv = inv;
-    g.min_b0 = (int)floorf(mn[0] * inv); g.min_b1 = (int)floorf(mn[1] * inv); g.min_b2 = (int)floorf(mn[2] * inv);
-    const int d0 = (int)floorf(mx[0] * inv) - g.min_b0 + 1, d1 = (int)floorf(mx[1] * inv) - g.min_b1 + 1,
-              d2 = (int)floorf(mx[2] * inv) - g.min_b2 + 1;
-    g.mul1 = d0; g.mul2 = d0 * d1;
-    const long long n_keys_ll = (long long)d0 * d1 * d2;
-    if (n_keys_ll > 2147483647LL) return lio_fail_ext(LIO_ERR_CAPACITY, "voxel grid has more than 2^31 - 1 voxels", hipSuccess);
-    g.n_keys = 0;
+    if (grc == 2) return lio_fail_ext(LIO_ERR_CAPACITY, "voxel grid has more than 2^31 - 1 voxels", hipSuccess);
     (void)wait;                                  // (the sorting form always ends with the wait for the voxel count)
     return voxel_grid_sorted<B>(d_in, n, g, n_keys_ll, out, n_out, s, ws);
 }
@@ -397,6 +412,19 @@ struct lio_kf_store {
     LioKeep world, ds, d_kf, d_poses, d_chunks, blk_box;
     std::vector<LioKfDesc> v_kf;
     std::vector<int2> v_chunks;
+    // key-pose table = cloudKeyPoses6D (x, y, z, roll, pitch, yaw, time): host copy written by lio_kf_store_set_poses (never
+    // blocks), device SoA next to off / cnt uploaded -- the dirty range only -- on the stream of the next selection
+    std::vector<float> px, py, pz, proll, ppitch, pyaw;
+    std::vector<double> ptime;
+    std::vector<unsigned char> has_pose, has_time;
+    size_t n_posed = 0, dirty_lo = SIZE_MAX, dirty_hi = 0, tab_cap = 0;
+    LioKeep d_tab;                                   // [tab_cap] x 6 float, [tab_cap] double, [tab_cap] x 2 int
+    unsigned char* h_stage = nullptr;                // pinned: the dirty range on its way up, then (n_ids, total), then ids
+    size_t stage_cap = 0;
+    // workspace of lio_assemble_map_nearby's selection
+    LioVoxWs<LioKeep> nws;
+    LioKeep nb_pts, nb_cent, nb_cid, nb_ids, nb_meta;
+    hipEvent_t ev_ids = nullptr;
 };
 
 extern "C" int lio_kf_store_create(int32_t device_id, lio_kf_store** out)
@@ -417,8 +445,12 @@ extern "C" void lio_kf_store_destroy(lio_kf_store* s)
     (void)hipDeviceSynchronize();
     if (s->d_pts) (void)hipFree(s->d_pts);
     LioKeep* keep[] = { &s->vws.bbox, &s->vws.large, &s->vws.pairs_a, &s->vws.pairs_b, &s->vws.hist, &s->vws.blk_heads, &s->vws.seg_start, &s->vws.d_no, &s->vws.row_total,
-                        &s->world, &s->ds, &s->d_kf, &s->d_poses, &s->d_chunks, &s->blk_box };
+                        &s->world, &s->ds, &s->d_kf, &s->d_poses, &s->d_chunks, &s->blk_box,
+                        &s->nws.bbox, &s->nws.large, &s->nws.pairs_a, &s->nws.pairs_b, &s->nws.hist, &s->nws.blk_heads, &s->nws.seg_start,
+                        &s->nws.d_no, &s->nws.row_total, &s->d_tab, &s->nb_pts, &s->nb_cent, &s->nb_cid, &s->nb_ids, &s->nb_meta };
     for (LioKeep* k : keep) k->release();
+    if (s->h_stage) (void)hipHostFree(s->h_stage);
+    if (s->ev_ids) (void)hipEventDestroy(s->ev_ids);
     delete s;
 }
 
@@ -444,9 +476,15 @@ static int kf_store_reserve(lio_kf_store* s, size_t n)
 static void kf_store_commit(lio_kf_store* s, size_t n, int32_t* id_out)
 {
     if (id_out) *id_out = (int32_t)s->off.size();
+    s->dirty_lo = std::min(s->dirty_lo, s->off.size());
+    s->dirty_hi = s->off.size() + 1;
     s->off.push_back(s->used);
     s->cnt.push_back(n);
     s->used += n;
+    for (std::vector<float>* v : { &s->px, &s->py, &s->pz, &s->proll, &s->ppitch, &s->pyaw }) v->push_back(0.0f);
+    s->ptime.push_back(0.0);
+    s->has_pose.push_back(0);
+    s->has_time.push_back(0);
 }
 
 // records (x,y,z at xyz_off, FLOAT32 intensity at int_off, < 0 = the record carries none) -> float4 (x,y,z,intensity)
@@ -525,6 +563,14 @@ extern "C" int lio_kf_store_add_from_handle(lio_kf_store* s, lio_s2m_handle* h, 
     return LIO_OK;
 }
 
+// K6 + K7 from selection descriptors already on the device -- src / first / n of every selected keyframe (d_kf, T filled
+// here), its pose (d_poses, [roll,pitch,yaw,x,y,z]) and the 256-point chunks of K6 (d_chunks) -- then the map into `h`:
+// the common tail of lio_assemble_map_resident and lio_assemble_map_nearby.  `s` is h's stream on the node path, else the
+// null stream.
+static int assemble_tail(lio_s2m_handle* h, lio_kf_store* st, int n_sel, size_t total, int n_chunks, LioKfDesc* d_kf,
+                         const float* d_poses, const int2* d_chunks, hipStream_t s, float leaf, void* out, size_t out_stride, size_t out_cap,
+                         size_t* n_out);
+
 extern "C" int lio_assemble_map_resident(lio_s2m_handle* h, lio_kf_store* st, int32_t n_sel, const int32_t* ids,
                                          const float* poses, float leaf, void* out, size_t out_stride, size_t* n_out)
 {
@@ -544,6 +590,7 @@ extern "C" int lio_assemble_map_resident(lio_s2m_handle* h, lio_kf_store* st, in
     }
     if (total > 0x7fffffffull - 1024) return lio_fail_ext(LIO_ERR_CAPACITY, "too many points", hipSuccess);
     if (n_out) *n_out = 0;
+    const int n_chunks = (int)chunks.size();
     if (lio_s2m_takes_device_map(h)) {
         // The node path (MO:1556-1588 straight into the resident map of `h`): everything on the handle's stream, the
         // temporaries kept in the store, the map's grid laid over the bounding box the voxel filter measured anyway, and no
@@ -552,52 +599,63 @@ extern "C" int lio_assemble_map_resident(lio_s2m_handle* h, lio_kf_store* st, in
         hipStream_t s = lio_s2m_stream_of(h);
         st->v_kf.swap(kf);                 // (host arrays of the asynchronous copies live in the store)
         st->v_chunks.swap(chunks);
-        HIPCHK(st->world.alloc(total * sizeof(float4)));
         HIPCHK(st->d_kf.alloc(sizeof(LioKfDesc) * (size_t)(n_sel ? n_sel : 1)));
         HIPCHK(st->d_poses.alloc(sizeof(float) * 6 * (size_t)(n_sel ? n_sel : 1)));
-        HIPCHK(st->d_chunks.alloc(sizeof(int2) * (st->v_chunks.size() ? st->v_chunks.size() : 1)));
+        HIPCHK(st->d_chunks.alloc(sizeof(int2) * (n_chunks ? n_chunks : 1)));
         if (n_sel) {
             HIPCHK(hipMemcpyAsync(st->d_kf.p, st->v_kf.data(), sizeof(LioKfDesc) * (size_t)n_sel, hipMemcpyHostToDevice, s));
             HIPCHK(hipMemcpyAsync(st->d_poses.p, poses, sizeof(float) * 6 * (size_t)n_sel, hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(k_kf_transforms, dim3((n_sel + 63) / 64), dim3(64), 0, s, st->d_kf.as<LioKfDesc>(), st->d_poses.as<float>(), n_sel);
         }
+        if (n_chunks) HIPCHK(hipMemcpyAsync(st->d_chunks.p, st->v_chunks.data(), sizeof(int2) * n_chunks, hipMemcpyHostToDevice, s));
+        // (`poses` is consumed by the voxel filter's first wait, which follows its copy on the same stream)
+        return assemble_tail(h, st, n_sel, total, n_chunks, st->d_kf.as<LioKfDesc>(), st->d_poses.as<float>(), st->d_chunks.as<int2>(),
+                             s, leaf, out, out_stride, SIZE_MAX, n_out);
+    }
+    hipStream_t s = nullptr;
+    Buf d_kf, d_poses, d_chunks;
+    HIPCHK(d_kf.alloc(sizeof(LioKfDesc) * (size_t)(n_sel ? n_sel : 1)));
+    HIPCHK(d_poses.alloc(sizeof(float) * 6 * (size_t)(n_sel ? n_sel : 1)));
+    HIPCHK(d_chunks.alloc(sizeof(int2) * (n_chunks ? n_chunks : 1)));
+    if (n_sel) {
+        HIPCHK(hipMemcpyAsync(d_kf.p, kf.data(), sizeof(LioKfDesc) * (size_t)n_sel, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d_poses.p, poses, sizeof(float) * 6 * (size_t)n_sel, hipMemcpyHostToDevice, s));
+    }
+    if (n_chunks) HIPCHK(hipMemcpyAsync(d_chunks.p, chunks.data(), sizeof(int2) * n_chunks, hipMemcpyHostToDevice, s));
+    return assemble_tail(h, st, n_sel, total, n_chunks, d_kf.as<LioKfDesc>(), d_poses.as<float>(), d_chunks.as<int2>(), s, leaf, out,
+                         out_stride, SIZE_MAX, n_out);
+}
+
+static int assemble_tail(lio_s2m_handle* h, lio_kf_store* st, int n_sel, size_t total, int n_chunks, LioKfDesc* d_kf,
+                         const float* d_poses, const int2* d_chunks, hipStream_t s, float leaf, void* out, size_t out_stride, size_t out_cap,
+                         size_t* n_out)
+{
+    if (n_sel) hipLaunchKernelGGL(k_kf_transforms, dim3((n_sel + 63) / 64), dim3(64), 0, s, d_kf, d_poses, n_sel);
+    int rc;
+    if (lio_s2m_takes_device_map(h)) {
+        HIPCHK(st->world.alloc(total * sizeof(float4)));
         HIPCHK(st->vws.bbox.alloc(6 * sizeof(unsigned)));
-        HIPCHK(st->blk_box.alloc(sizeof(float) * 6 * (st->v_chunks.size() ? st->v_chunks.size() : 1)));
-        if (!st->v_chunks.empty()) {
-            HIPCHK(hipMemcpyAsync(st->d_chunks.p, st->v_chunks.data(), sizeof(int2) * st->v_chunks.size(), hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(k_transform_clouds_bbox, dim3((unsigned)st->v_chunks.size()), dim3(256), 0, s, st->d_pts,
-                               st->d_kf.as<LioKfDesc>(), st->d_chunks.as<int2>(), st->world.as<float4>(), st->blk_box.as<float>());
-        }
-        hipLaunchKernelGGL(k_bbox_reduce, dim3(1), dim3(256), 0, s, st->blk_box.as<float>(), (int)st->v_chunks.size(), st->vws.bbox.as<unsigned>());
+        HIPCHK(st->blk_box.alloc(sizeof(float) * 6 * (n_chunks ? n_chunks : 1)));
+        if (n_chunks)
+            hipLaunchKernelGGL(k_transform_clouds_bbox, dim3((unsigned)n_chunks), dim3(256), 0, s, st->d_pts, d_kf, d_chunks,
+                               st->world.as<float4>(), st->blk_box.as<float>());
+        hipLaunchKernelGGL(k_bbox_reduce, dim3(1), dim3(256), 0, s, st->blk_box.as<float>(), n_chunks, st->vws.bbox.as<unsigned>());
         int no = 0;
         float box[6];
         rc = voxel_grid_device<LioKeep>(st->world.as<float4>(), (int)total, leaf, st->ds, &no, s, st->vws, false, box, true);
         if (rc < 0) return rc;
-        // (`poses` was consumed by the voxel filter's first wait, which follows its copy on the same stream)
         const int rc3 = lio_s2m_set_map_device_bbox(h, st->ds.as<float4>(), (size_t)no, box);
         if (rc3 != LIO_OK) return rc3;
+        if (out && (size_t)no > out_cap) { if (n_out) *n_out = (size_t)no; return lio_fail_ext(LIO_ERR_ARG, "out holds fewer records than the map (*n_out)", hipSuccess); }
         const int rc2 = copy_out(st->ds.as<float4>(), no, out, out_stride, s);
         if (rc2 < 0) return rc2;
         if (n_out) *n_out = (size_t)no;
         return rc;
     }
-    hipStream_t s = nullptr;
-    Buf d_kf, d_poses, d_chunks, world, ds;
+    Buf world, ds;
     HIPCHK(world.alloc(total * sizeof(float4)));
-    HIPCHK(d_kf.alloc(sizeof(LioKfDesc) * (size_t)(n_sel ? n_sel : 1)));
-    HIPCHK(d_poses.alloc(sizeof(float) * 6 * (size_t)(n_sel ? n_sel : 1)));
-    HIPCHK(d_chunks.alloc(sizeof(int2) * (chunks.size() ? chunks.size() : 1)));
-    if (n_sel) {
-        HIPCHK(hipMemcpyAsync(d_kf.p, kf.data(), sizeof(LioKfDesc) * (size_t)n_sel, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(d_poses.p, poses, sizeof(float) * 6 * (size_t)n_sel, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_kf_transforms, dim3((n_sel + 63) / 64), dim3(64), 0, s, d_kf.as<LioKfDesc>(), d_poses.as<float>(), n_sel);
-    }
-    if (!chunks.empty()) {
-        HIPCHK(hipMemcpyAsync(d_chunks.p, chunks.data(), sizeof(int2) * chunks.size(), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_transform_clouds, dim3((unsigned)chunks.size()), dim3(256), 0, s, st->d_pts,
-                           d_kf.as<LioKfDesc>(), d_chunks.as<int2>(), world.as<float4>());
-    }
-    HIPCHK(hipStreamSynchronize(s));       // kf / chunks are stack vectors
+    if (n_chunks)
+        hipLaunchKernelGGL(k_transform_clouds, dim3((unsigned)n_chunks), dim3(256), 0, s, st->d_pts, d_kf, d_chunks, world.as<float4>());
+    HIPCHK(hipStreamSynchronize(s));       // (the descriptors may be pool temporaries or host arrays of the caller)
     int no = 0;
     rc = voxel_grid_device(world.as<float4>(), (int)total, leaf, ds, &no, s);
     if (rc < 0) return rc;
@@ -605,6 +663,7 @@ extern "C" int lio_assemble_map_resident(lio_s2m_handle* h, lio_kf_store* st, in
         const int rc3 = lio_s2m_set_map_device_xyzi(h, ds.as<float4>(), (size_t)no);
         if (rc3 != LIO_OK) return rc3;
     }
+    if (out && (size_t)no > out_cap) { if (n_out) *n_out = (size_t)no; return lio_fail_ext(LIO_ERR_ARG, "out holds fewer records than the map (*n_out)", hipSuccess); }
     const int rc2 = copy_out(ds.as<float4>(), no, out, out_stride, s);
     if (rc2 < 0) return rc2;
     if (n_out) *n_out = (size_t)no;
@@ -627,6 +686,355 @@ extern "C" int lio_assemble_map(lio_s2m_handle* h, int32_t device_id, int32_t n_
     return rc;
 }
 
+
+// ------------------------------------------------ surrounding keyframes on the device (extractNearby MO:1519-1551 + MO:1562)
+// cloudKeyPoses6D lives in the store (lio_kf_store_set_poses); lio_assemble_map_nearby selects the keyframes of the local
+// map from it and hands the selection to the tail of lio_assemble_map_resident without the ids crossing to the host:
+//   k_nb_select    radius test around the last key pose (d2 < r2), the start of the recent suffix, the box of the hits
+//   sort           the hits by (d2, i): the stable radix sort of lio_voxsort.h on (d2 bits, i) pairs, misses keyed last
+//   k_nb_voxkeys   pcl::VoxelGrid at surroundingKeyframeDensity over the sorted hits (lio_voxsort.h: grid, keys, sort,
+//   + centroids    in-order centroids) -> surroundingKeyPosesDS
+//   k_nb_relabel   nearest key pose of every centroid, brute force over all N, ties to the lowest index
+//   k_nb_compact   centroids, then the recent keyframes newest first, minus those beyond the radius (MO:1562); prefix sums
+//                  over cnt[id] and its 256-point chunks -> LioKfDesc records, poses, ids
+// One host wait: (n_ids, total points, chunks), which sizes the world-frame cloud.  DESIGN.md has the conventions.
+struct LioPoseTab { const float *x, *y, *z, *roll, *pitch, *yaw; const double* t; const int *off, *cnt; };
+struct LioNbMeta { int n_sel, recent_fail; unsigned box[6]; int n_ids, n_chunks; unsigned long long total; };
+
+static LioPoseTab pose_tab(lio_kf_store* st)
+{
+    const size_t c = st->tab_cap;
+    const float* f = st->d_tab.as<float>();
+    LioPoseTab t = { f, f + c, f + 2 * c, f + 3 * c, f + 4 * c, f + 5 * c, (const double*)(f + 6 * c), (const int*)(f + 8 * c),
+                     (const int*)(f + 9 * c) };
+    return t;
+}
+
+__device__ __forceinline__ float lio_ord2f_dev(unsigned u)
+{
+    return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
+}
+
+__global__ void k_nb_init(LioNbMeta* m)
+{
+    m->n_sel = 0; m->recent_fail = -1;
+    for (int a = 0; a < 3; ++a) { m->box[a] = 0xffffffffu; m->box[3 + a] = 0u; }
+    m->n_ids = 0; m->n_chunks = 0; m->total = 0ull;
+}
+
+// one thread per key pose: d2 to the last one, the radius flag (strict <, as FLANN's RadiusResultSet), the newest keyframe
+// that fails the recent test (atomic max: the suffix after it is what MO:1544-1551 appends), the box of the hits
+__global__ __launch_bounds__(256) void k_nb_select(LioPoseTab tab, int n, float r2, double time_cur, double window,
+                                                   uint2* __restrict__ pairs, LioNbMeta* __restrict__ m)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const float lx = tab.x[n - 1], ly = tab.y[n - 1], lz = tab.z[n - 1];
+    bool sel = false;
+    int fail = -1;
+    float mn[3] = { INFINITY, INFINITY, INFINITY }, mx[3] = { -INFINITY, -INFINITY, -INFINITY };
+    if (i < n) {
+        const float x = tab.x[i], y = tab.y[i], z = tab.z[i];
+        const float dx = x - lx, dy = y - ly, dz = z - lz;
+        const float d2 = (dx * dx + dy * dy) + dz * dz;
+        sel = d2 < r2;
+        if (!(time_cur - tab.t[i] < window)) fail = i;
+        pairs[i] = make_uint2(sel ? __float_as_uint(d2) : 0xffffffffu, (unsigned)i);
+        if (sel) { mn[0] = mx[0] = x; mn[1] = mx[1] = y; mn[2] = mx[2] = z; }
+    }
+    const int n_hit = __popcll(__ballot(sel));
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        fail = max(fail, __shfl_xor(fail, off));
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { mn[a] = fminf(mn[a], __shfl_xor(mn[a], off)); mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], off)); }
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (n_hit) {
+            atomicAdd(&m->n_sel, n_hit);
+            for (int a = 0; a < 3; ++a) { atomicMin(&m->box[a], lio_f2ord2(mn[a])); atomicMax(&m->box[3 + a], lio_f2ord2(mx[a])); }
+        }
+        if (fail >= 0) atomicMax(&m->recent_fail, fail);
+    }
+}
+
+// sorted hits (d2 bits, i) -> the pose filter's input records (x, y, z, intensity = i) and its (voxel key, position) pairs,
+// in place.  Past the hits: key 2^31 + position (above every voxel key, < 2^31: each miss is a voxel of its own after the
+// hits' voxels, one cheap segment instead of one crowded one), a zero record.  The grid is laid over the box
+// of the hits here, on the device, by the same code as the host's voxel filter; an overflowing index passes the input
+// through (key = position), as pcl::VoxelGrid does.
+__global__ __launch_bounds__(256) void k_nb_voxkeys(LioPoseTab tab, int n, float inv, const LioNbMeta* __restrict__ m,
+                                                    uint2* __restrict__ pairs, float4* __restrict__ pts)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const int n_sel = m->n_sel;
+    if (j >= n_sel) { pairs[j] = make_uint2(0x80000000u | (unsigned)j, (unsigned)j); pts[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); return; }
+    float mn[3], mx[3];
+    for (int a = 0; a < 3; ++a) { mn[a] = lio_ord2f_dev(m->box[a]); mx[a] = lio_ord2f_dev(m->box[3 + a]); }
+    LioVsGrid g;
+    long long n_keys = 0;
+    const bool pass = lio_vs_grid_from_box(mn, mx, inv, &g, &n_keys) != 0;
+    const int i = (int)pairs[j].y;
+    const float x = tab.x[i], y = tab.y[i], z = tab.z[i];
+    pts[j] = make_float4(x, y, z, (float)i);
+    pairs[j] = make_uint2(pass ? (unsigned)j : lio_vs_key(g, x, y, z), (unsigned)j);
+}
+
+// voxels of the pose filter = segments of the sorted pairs minus the trailing one-point segments of the misses
+__device__ __forceinline__ int nb_n_vox(const LioNbMeta* m, const int* d_no, int n) { return d_no[0] - (n - m->n_sel); }
+
+// MO:1537-1541: the nearest key pose of every centroid over ALL N, argmin of (d2 bits, i) in one 64-bit compare (ties go
+// to the lowest index).  One thread per centroid, the poses streamed through LDS 64 at a time; blockIdx.y takes the poses
+// [y * NB_SPLIT, (y + 1) * NB_SPLIT) and the splits meet in a 64-bit atomic min (order-independent: the result is exact).
+#define NB_SPLIT 1024
+__global__ __launch_bounds__(64) void k_nb_relabel(LioPoseTab tab, int n, const float4* __restrict__ cent, const LioNbMeta* __restrict__ m,
+                                                   const int* __restrict__ d_no, unsigned long long* __restrict__ cid)
+{
+    __shared__ float s_x[64], s_y[64], s_z[64];
+    const int n_vox = nb_n_vox(m, d_no, n);
+    if ((int)(blockIdx.x * 64) >= n_vox) return;                 // workgroup-uniform
+    const int o = blockIdx.x * 64 + threadIdx.x;
+    const float4 c = o < n_vox ? cent[o] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    unsigned long long best = ~0ull;
+    const int b_end = min(n, (int)(blockIdx.y + 1) * NB_SPLIT);
+    for (int b = blockIdx.y * NB_SPLIT; b < b_end; b += 64) {
+        const int k = b + threadIdx.x;
+        __syncthreads();
+        if (k < n) { s_x[threadIdx.x] = tab.x[k]; s_y[threadIdx.x] = tab.y[k]; s_z[threadIdx.x] = tab.z[k]; }
+        __syncthreads();
+        const int m_ = min(64, b_end - b);
+        for (int j = 0; j < m_; ++j) {
+            const float dx = c.x - s_x[j], dy = c.y - s_y[j], dz = c.z - s_z[j];
+            const float d2 = (dx * dx + dy * dy) + dz * dz;
+            const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)(b + j);
+            best = key < best ? key : best;
+        }
+    }
+    if (o < n_vox) atomicMin(&cid[o], best);
+}
+
+// exclusive prefix over the workgroup (256 threads); *total receives the sum
+template <typename T>
+__device__ T nb_block_scan(T v, T* s_wave, T* total)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    T incl = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const T t = __shfl_up(incl, off);
+        if (lane >= off) incl += t;
+    }
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    T woff = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) { const T sw = s_wave[w]; if (w < wave) woff += sw; tot += sw; }
+    __syncthreads();
+    *total = tot;
+    return woff + incl - v;
+}
+
+// The list of MO:1535-1551 in order -- centroids (own coordinates, relabelled id), then i = last .. recent_fail + 1 --
+// minus the entries farther than R from the last key pose (MO:1562: sqrtf, strict >), compacted in order by ONE workgroup
+// with running prefix sums of the kept entries, their points and their 256-point chunks.
+__global__ __launch_bounds__(256) void k_nb_compact(LioPoseTab tab, int n, float R, const float4* __restrict__ cent,
+                                                    const unsigned long long* __restrict__ cid, LioNbMeta* __restrict__ m, const int* __restrict__ d_no,
+                                                    int* __restrict__ ids, LioKfDesc* __restrict__ kf, float* __restrict__ poses)
+{
+    __shared__ int s_wi[4];
+    __shared__ unsigned long long s_wl[4];
+    const int n_vox = nb_n_vox(m, d_no, n), n_rec = (n - 1) - m->recent_fail, total_e = n_vox + n_rec;
+    const float lx = tab.x[n - 1], ly = tab.y[n - 1], lz = tab.z[n - 1];
+    int run_ids = 0, run_ch = 0;
+    unsigned long long run_pts = 0;
+    for (int b = 0; b < total_e; b += 256) {
+        const int e = b + threadIdx.x;
+        bool keep = false;
+        int id = 0;
+        if (e < total_e) {
+            float x, y, z;
+            if (e < n_vox) { const float4 c = cent[e]; x = c.x; y = c.y; z = c.z; id = (int)(unsigned)(cid[e] & 0xffffffffull); }
+            else { id = (n - 1) - (e - n_vox); x = tab.x[id]; y = tab.y[id]; z = tab.z[id]; }
+            const float ex = x - lx, ey = y - ly, ez = z - lz;
+            keep = !(sqrtf((ex * ex + ey * ey) + ez * ez) > R);
+        }
+        const int cnt = keep ? tab.cnt[id] : 0;
+        int t_ids, t_ch;
+        unsigned long long t_pts;
+        const int pos = run_ids + nb_block_scan<int>(keep ? 1 : 0, s_wi, &t_ids);
+        const int cb = run_ch + nb_block_scan<int>(keep ? (cnt + 255) / 256 : 0, s_wi, &t_ch);
+        const unsigned long long first = run_pts + nb_block_scan<unsigned long long>((unsigned long long)cnt, s_wl, &t_pts);
+        if (keep) {
+            ids[pos] = id;
+            LioKfDesc d;
+            d.src = tab.off[id]; d.first = (int)first; d.n = cnt; d.pad = cb;     // (pad: the keyframe's first chunk)
+            for (int j = 0; j < 12; ++j) d.T[j] = 0.0f;
+            kf[pos] = d;
+            const float p6[6] = { tab.roll[id], tab.pitch[id], tab.yaw[id], tab.x[id], tab.y[id], tab.z[id] };
+            for (int j = 0; j < 6; ++j) poses[(size_t)pos * 6 + j] = p6[j];
+        }
+        run_ids += t_ids; run_ch += t_ch; run_pts += t_pts;
+    }
+    if (threadIdx.x == 0) { m->n_ids = run_ids; m->n_chunks = run_ch; m->total = run_pts; }
+}
+
+// the 256-point chunks of K6 for the kept list: keyframe k owns chunks [kf[k].pad, kf[k].pad + ceil(n / 256))
+__global__ __launch_bounds__(64) void k_nb_chunks(const LioKfDesc* __restrict__ kf, int2* __restrict__ chunks)
+{
+    const int k = blockIdx.x;
+    const int n = kf[k].n, base = kf[k].pad;
+    for (int c = threadIdx.x; c * 256 < n; c += 64) chunks[base + c] = make_int2(k, c * 256);
+}
+
+extern "C" void lio_nearby_default_config(lio_nearby_config* cfg)
+{
+    if (!cfg) return;
+    cfg->search_radius = 50.0f;      // surroundingKeyframeSearchRadius, UT:316
+    cfg->pose_density = 1.0f;        // surroundingKeyframeDensity, UT:314
+    cfg->recent_window_s = 10.0;     // MO:1547
+}
+
+extern "C" int lio_kf_store_set_poses(lio_kf_store* s, int32_t first, int32_t n, const float* poses, const double* times)
+{
+    if (!s || first < 0 || n < 0 || (n && !poses)) return lio_fail_ext(LIO_ERR_ARG, "null argument", hipSuccess);
+    if ((size_t)first + (size_t)n > s->off.size())
+        return lio_fail_ext(LIO_ERR_ARG, "poses for keyframes the store does not hold (add the cloud first)", hipSuccess);
+    for (int k = 0; k < n; ++k) {
+        for (int j = 0; j < 6; ++j)
+            if (!std::isfinite(poses[(size_t)k * 6 + j])) return lio_fail_ext(LIO_ERR_ARG, "non-finite key pose", hipSuccess);
+        if (times ? !std::isfinite(times[k]) : !s->has_time[(size_t)first + k])
+            return lio_fail_ext(LIO_ERR_ARG, times ? "non-finite key pose time" : "times == NULL for a keyframe that has no time yet", hipSuccess);
+    }
+    for (int k = 0; k < n; ++k) {                    // host only: whatever is in flight keeps the table it was given
+        const size_t i = (size_t)first + k;
+        const float* p = poses + (size_t)k * 6;
+        s->proll[i] = p[0]; s->ppitch[i] = p[1]; s->pyaw[i] = p[2]; s->px[i] = p[3]; s->py[i] = p[4]; s->pz[i] = p[5];
+        if (times) { s->ptime[i] = times[k]; s->has_time[i] = 1; }
+        if (!s->has_pose[i]) { s->has_pose[i] = 1; ++s->n_posed; }
+    }
+    if (n) { s->dirty_lo = std::min(s->dirty_lo, (size_t)first); s->dirty_hi = std::max(s->dirty_hi, (size_t)first + n); }
+    return LIO_OK;
+}
+
+// the dirty range of the key-pose table (and off / cnt) to the device, on stream `s`, through the pinned stage
+static int upload_pose_tab(lio_kf_store* st, hipStream_t s)
+{
+    const size_t N = st->off.size();
+    if (N > st->tab_cap) {                           // (growing waits for the device: the old table may still be read)
+        st->tab_cap = std::max<size_t>(1024, ((2 * N) + 63) / 64 * 64);
+        HIPCHK(st->d_tab.alloc(st->tab_cap * 40));
+        st->dirty_lo = 0; st->dirty_hi = N;
+    }
+    if (!st->h_stage) {                              // (the stage also receives the selection's counts)
+        HIPCHK(hipHostMalloc((void**)&st->h_stage, 4096, hipHostMallocPortable));
+        st->stage_cap = 4096;
+    }
+    if (st->dirty_lo >= st->dirty_hi) return LIO_OK;
+    const size_t lo = st->dirty_lo, L = std::min(st->dirty_hi, N) - lo;
+    if (L * 40 > st->stage_cap) {                    // (the stage is idle: every call ends with a wait behind its copies)
+        if (st->h_stage) HIPCHK(hipHostFree(st->h_stage));
+        st->h_stage = nullptr; st->stage_cap = 0;
+        const size_t want = std::max<size_t>(L * 40 + L * 10, 4096);
+        HIPCHK(hipHostMalloc((void**)&st->h_stage, want, hipHostMallocPortable));
+        st->stage_cap = want;
+    }
+    float* f = (float*)st->h_stage;
+    const std::vector<float>* cols[6] = { &st->px, &st->py, &st->pz, &st->proll, &st->ppitch, &st->pyaw };
+    for (int c = 0; c < 6; ++c) memcpy(f + c * L, cols[c]->data() + lo, L * sizeof(float));
+    memcpy(f + 6 * L, st->ptime.data() + lo, L * sizeof(double));
+    int* o = (int*)(f + 8 * L);
+    for (size_t k = 0; k < L; ++k) { o[k] = (int)st->off[lo + k]; o[L + k] = (int)st->cnt[lo + k]; }
+    float* d = st->d_tab.as<float>();
+    const size_t C = st->tab_cap;
+    for (int c = 0; c < 6; ++c) HIPCHK(hipMemcpyAsync(d + c * C + lo, f + c * L, L * sizeof(float), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync((double*)(d + 6 * C) + lo, f + 6 * L, L * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync((int*)(d + 8 * C) + lo, o, L * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync((int*)(d + 9 * C) + lo, o + L, L * sizeof(int), hipMemcpyHostToDevice, s));
+    st->dirty_lo = SIZE_MAX; st->dirty_hi = 0;
+    return LIO_OK;
+}
+
+extern "C" int lio_assemble_map_nearby(lio_s2m_handle* h, lio_kf_store* st, const lio_nearby_config* cfg, double time_cur,
+                                       float leaf, int32_t* ids_out, int32_t ids_cap, int32_t* n_ids, void* out,
+                                       size_t out_stride, size_t out_cap, size_t* n_out)
+{
+    if (!st || !cfg || ids_cap < 0) return lio_fail_ext(LIO_ERR_ARG, "null argument", hipSuccess);
+    if ((out && (out_stride < 20 || (out_stride & 3))) || !(leaf > 0.0f))
+        return lio_fail_ext(LIO_ERR_ARG, "output stride must be >= 20 and a multiple of 4, leaf > 0", hipSuccess);
+    const float R = cfg->search_radius;
+    if (!(R > 0.0f) || !std::isfinite(R) || !(cfg->pose_density > 0.0f) || !std::isfinite(cfg->pose_density) ||
+        !std::isfinite(cfg->recent_window_s) || !std::isfinite(time_cur))
+        return lio_fail_ext(LIO_ERR_ARG, "search_radius, pose_density > 0 and finite; recent_window_s, time_cur finite", hipSuccess);
+    if (n_ids) *n_ids = 0;
+    if (n_out) *n_out = 0;
+    int rc = check_device(st->device_id);
+    if (rc != LIO_OK) return rc;
+    if (h && h->cfg.device_id != st->device_id)
+        return lio_fail_ext(LIO_ERR_ARG, "the handle and the keyframe store live on different devices", hipSuccess);
+    const int N = (int)st->off.size();
+    if (N == 0) return LIO_OK;                       // MO:1592-1593: nothing to extract, the map stays as it is
+    if (st->n_posed != (size_t)N) return lio_fail_ext(LIO_ERR_ARG, "a keyframe has no pose (lio_kf_store_set_poses)", hipSuccess);
+    const bool node = lio_s2m_takes_device_map(h);
+    hipStream_t s = node ? lio_s2m_stream_of(h) : nullptr;
+    if ((rc = upload_pose_tab(st, s)) != LIO_OK) return rc;
+    if (!st->ev_ids) HIPCHK(hipEventCreateWithFlags(&st->ev_ids, hipEventDisableTiming));
+    if ((rc = vsort_reserve<LioKeep>(N, st->nb_cent, st->nws)) != LIO_OK) return rc;
+    HIPCHK(st->nb_pts.alloc(sizeof(float4) * (size_t)N));
+    HIPCHK(st->nb_cid.alloc(sizeof(unsigned long long) * (size_t)N));
+    HIPCHK(st->nb_ids.alloc(sizeof(int) * 2 * (size_t)N));
+    HIPCHK(st->nb_meta.alloc(sizeof(LioNbMeta)));
+    HIPCHK(st->d_kf.alloc(sizeof(LioKfDesc) * 2 * (size_t)N));    // the list holds at most n_vox + n_recent <= 2N entries
+    HIPCHK(st->d_poses.alloc(sizeof(float) * 6 * 2 * (size_t)N));
+    const LioPoseTab tab = pose_tab(st);
+    LioNbMeta* m = st->nb_meta.as<LioNbMeta>();
+    const unsigned nblk = (unsigned)((N + 255) / 256);
+    hipLaunchKernelGGL(k_nb_init, dim3(1), dim3(1), 0, s, m);
+    const float r2 = (float)((double)R * (double)R);                // what PCL hands FLANN
+    hipLaunchKernelGGL(k_nb_select, dim3(nblk), dim3(256), 0, s, tab, N, r2, time_cur, cfg->recent_window_s,
+                       st->nws.pairs_a.as<uint2>(), m);
+    uint2* hits = vsort_pairs<LioKeep>(N, 32, s, st->nws);          // (d2, i) ascending, the misses last
+    // (an even number of passes ends in pairs_a, where the second sort starts: k_nb_voxkeys rewrites the pairs in place)
+    if (hits != st->nws.pairs_a.as<uint2>()) return lio_fail_ext(LIO_ERR_HIP, "radix sort ended in the wrong buffer", hipSuccess);
+    hipLaunchKernelGGL(k_nb_voxkeys, dim3(nblk), dim3(256), 0, s, tab, N, 1.0f / cfg->pose_density, m, hits, st->nb_pts.as<float4>());
+    const uint2* vox = vsort_pairs<LioKeep>(N, 32, s, st->nws);
+    if ((rc = vsort_centroids<LioKeep>(st->nb_pts.as<float4>(), vox, N, st->nb_cent, s, st->nws)) != LIO_OK) return rc;
+    const int* d_no = st->nws.d_no.as<int>();
+    HIPCHK(hipMemsetAsync(st->nb_cid.p, 0xff, sizeof(unsigned long long) * (size_t)N, s));
+    hipLaunchKernelGGL(k_nb_relabel, dim3((unsigned)((N + 63) / 64), (unsigned)((N + NB_SPLIT - 1) / NB_SPLIT)), dim3(64), 0, s, tab, N,
+                       st->nb_cent.as<float4>(), m, d_no, st->nb_cid.as<unsigned long long>());
+    hipLaunchKernelGGL(k_nb_compact, dim3(1), dim3(256), 0, s, tab, N, R, st->nb_cent.as<float4>(), st->nb_cid.as<unsigned long long>(), m, d_no,
+                       st->nb_ids.as<int>(), st->d_kf.as<LioKfDesc>(), st->d_poses.as<float>());
+    LioNbMeta* hm = (LioNbMeta*)st->h_stage;                        // (the stage exists: the first call uploaded through it)
+    HIPCHK(hipMemcpyAsync(hm, m, sizeof(LioNbMeta), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));                                // THE wait of the selection: (n_ids, total points, chunks)
+    HIPCHK(hipGetLastError());
+    const int n_sel = hm->n_ids, n_chunks = hm->n_chunks;
+    const unsigned long long total = hm->total;
+    if (n_ids) *n_ids = n_sel;
+    if (ids_out && ids_cap < n_sel) return lio_fail_ext(LIO_ERR_ARG, "ids_cap is smaller than the selected list (*n_ids)", hipSuccess);
+    if (total > 0x7fffffffull - 1024) return lio_fail_ext(LIO_ERR_CAPACITY, "too many points", hipSuccess);
+    int* h_ids = (int*)st->h_stage;
+    if (ids_out && n_sel) {
+        if ((size_t)n_sel * sizeof(int) > st->stage_cap) {
+            HIPCHK(hipHostFree(st->h_stage));
+            st->h_stage = nullptr; st->stage_cap = 0;
+            HIPCHK(hipHostMalloc((void**)&st->h_stage, (size_t)n_sel * sizeof(int) * 2, hipHostMallocPortable));
+            st->stage_cap = (size_t)n_sel * sizeof(int) * 2;
+            h_ids = (int*)st->h_stage;
+        }
+        HIPCHK(hipMemcpyAsync(h_ids, st->nb_ids.p, (size_t)n_sel * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipEventRecord(st->ev_ids, s));                      // (complete by the voxel filter's waits further down)
+    }
+    HIPCHK(st->d_chunks.alloc(sizeof(int2) * (n_chunks ? n_chunks : 1)));
+    if (n_sel) hipLaunchKernelGGL(k_nb_chunks, dim3((unsigned)n_sel), dim3(64), 0, s, st->d_kf.as<LioKfDesc>(), st->d_chunks.as<int2>());
+    rc = assemble_tail(h, st, n_sel, (size_t)total, n_chunks, st->d_kf.as<LioKfDesc>(), st->d_poses.as<float>(),
+                       st->d_chunks.as<int2>(), s, leaf, out, out_stride, out_cap, n_out);
+    if (ids_out && n_sel) {
+        HIPCHK(hipEventSynchronize(st->ev_ids));
+        memcpy(ids_out, h_ids, (size_t)n_sel * sizeof(int));
+    }
+    return rc;
+}
 
 // ------------------------------------------------ one callback on the device: downsample + register (SURVEY 8f / verdict r2)
 // Staged cloud and voxel-filter workspace of lio_s2m_register_raw, kept on the handle from one callback to the next.
