@@ -8,7 +8,10 @@
  * crossing is narrowest.  Plain pointers and sizes only; all
  * device memory is owned by the opaque handle.  Nothing here throws or aborts:
  * every entry point returns an int status (0 ok, >0 soft condition that the
- * reference also treats as "skip", <0 hard HIP/argument error).
+ * reference also treats as "skip", <0 hard HIP/argument error).  A C++
+ * exception inside the library (host memory exhausted) is caught at the entry
+ * point and returned as LIO_ERR_CAPACITY; a handle it interrupted is still
+ * safe to destroy, but need not be usable.
  *
  * Point clouds cross the edge in the caller's layout: `stride_bytes` between
  * points, float x,y,z at byte offsets 0,4,8 (pcl::PointXYZI: stride 32, UT:65;

@@ -20,15 +20,6 @@
 #include "../../include/liogpu.h"
 #include "lio_pool.h"
 
-int lio_fail_ext(int code, const char* what, hipError_t e);   // liogpu_api.hip
-
-#define HIPCHK(expr)                                                              \
-    do {                                                                          \
-        hipError_t _e = (expr);                                                   \
-        if (_e != hipSuccess) return lio_fail_ext(LIO_ERR_HIP, #expr, _e);        \
-    } while (0)
-
-typedef LioTemp DevBuf;
 typedef unsigned long long u64;
 
 #define FEAT_BLOCK     256
@@ -427,16 +418,16 @@ extern "C" int lio_extract_features(const lio_feature_config* cfg, const void* c
                                     const int32_t* pointColInd, const float* pointRange,
                                     void* corner_out, size_t* n_corner, void* surface_out, size_t* n_surface,
                                     size_t out_stride, float* curvature, int32_t* neighbor_picked, int32_t* label)
-{
+try {
     if (!cfg || !n_corner || !n_surface || !startRingIndex || !endRingIndex)
-        return lio_fail_ext(LIO_ERR_ARG, "null argument", hipSuccess);
+        return lio_fail(LIO_ERR_ARG, "null argument");
     if (n && (!cloud || !pointColInd || !pointRange || !corner_out || !surface_out))
-        return lio_fail_ext(LIO_ERR_ARG, "null argument", hipSuccess);
+        return lio_fail(LIO_ERR_ARG, "null argument");
     if (stride < 20 || (stride & 3) || out_stride < 20 || (out_stride & 3))
-        return lio_fail_ext(LIO_ERR_ARG, "point strides must be >= 20 and multiples of 4", hipSuccess);
-    if (cfg->N_SCAN < 1 || cfg->N_SCAN > 1024) return lio_fail_ext(LIO_ERR_ARG, "N_SCAN out of range", hipSuccess);
-    if (!(cfg->surfLeafSize > 0.0f)) return lio_fail_ext(LIO_ERR_ARG, "surfLeafSize must be positive", hipSuccess);
-    if (n > 0x7fffffffull - 1024) return lio_fail_ext(LIO_ERR_CAPACITY, "cloud too large", hipSuccess);
+        return lio_fail(LIO_ERR_ARG, "point strides must be >= 20 and multiples of 4");
+    if (cfg->N_SCAN < 1 || cfg->N_SCAN > 1024) return lio_fail(LIO_ERR_ARG, "N_SCAN out of range");
+    if (!(cfg->surfLeafSize > 0.0f)) return lio_fail(LIO_ERR_ARG, "surfLeafSize must be positive");
+    if (n > 0x7fffffffull - 1024) return lio_fail(LIO_ERR_CAPACITY, "cloud too large");
     *n_corner = 0; *n_surface = 0;
     // Rings must own disjoint index windows [start-5, end+4] in ascending order -- what cloudExtraction
     // produces -- or the reference's ring-after-ring order would matter.
@@ -444,23 +435,23 @@ extern "C" int lio_extract_features(const lio_feature_config* cfg, const void* c
     for (int i = 0; i < cfg->N_SCAN; ++i) {
         const long s = startRingIndex[i], e = endRingIndex[i];
         if (e < s) continue;
-        if (s < 0 || e > (long)n - 1) return lio_fail_ext(LIO_ERR_ARG, "ring index range outside the cloud", hipSuccess);
-        if (s - 5 <= prev_hi) return lio_fail_ext(LIO_ERR_ARG, "ring windows overlap or are not ascending", hipSuccess);
+        if (s < 0 || e > (long)n - 1) return lio_fail(LIO_ERR_ARG, "ring index range outside the cloud");
+        if (s - 5 <= prev_hi) return lio_fail(LIO_ERR_ARG, "ring windows overlap or are not ascending");
         prev_hi = e + 4;
-        if (e - s + 11 > FEAT_MAX_RING) return lio_fail_ext(LIO_ERR_CAPACITY, "more than 4086 points in one ring", hipSuccess);
+        if (e - s + 11 > FEAT_MAX_RING) return lio_fail(LIO_ERR_CAPACITY, "more than 4086 points in one ring");
     }
     if (n == 0) return LIO_OK;
     for (size_t i = 0; i < n; ++i)
         if (pointColInd[i] < -32768 || pointColInd[i] > 32767)
-            return lio_fail_ext(LIO_ERR_CAPACITY, "pointColInd does not fit int16", hipSuccess);
+            return lio_fail(LIO_ERR_CAPACITY, "pointColInd does not fit int16");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return lio_fail_ext(LIO_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU fallback)", hipSuccess);
+        return lio_fail(LIO_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU fallback)");
     HIPCHK(hipSetDevice(cfg->device_id));
     (void)hipGetLastError();
 
     const int ns = cfg->N_SCAN;
-    DevBuf d_cloud, d_rings, d_col, d_range, d_curv, d_picked, d_label, d_cidx, d_cnt, d_stage, d_cout, d_sout;
+    LioTemp d_cloud, d_rings, d_col, d_range, d_curv, d_picked, d_label, d_cidx, d_cnt, d_stage, d_cout, d_sout;
     HIPCHK(d_cloud.alloc(n * stride));
     HIPCHK(d_rings.alloc(sizeof(int) * 2 * (size_t)ns));
     HIPCHK(d_col.alloc(n * 4)); HIPCHK(d_range.alloc(n * 4)); HIPCHK(d_curv.alloc(n * 4));
@@ -509,11 +500,11 @@ extern "C" int lio_extract_features(const lio_feature_config* cfg, const void* c
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
     if (h_cnt[4 * (size_t)ns + 2] != 0)
-        return lio_fail_ext(LIO_ERR_CAPACITY, "a ring window (> 4096 points) or a sector (> 1024 points) exceeds the LDS budget", hipSuccess);
+        return lio_fail(LIO_ERR_CAPACITY, "a ring window (> 4096 points) or a sector (> 1024 points) exceeds the LDS budget");
     const size_t nc = (size_t)h_cnt[2 * (size_t)ns + ns], nsf = (size_t)h_cnt[3 * (size_t)ns + 1 + ns];
     if (nc) HIPCHK(hipMemcpy(corner_out, d_cout.p, nc * out_stride, hipMemcpyDeviceToHost));
     if (nsf) HIPCHK(hipMemcpy(surface_out, d_sout.p, nsf * out_stride, hipMemcpyDeviceToHost));
     *n_corner = nc;
     *n_surface = nsf;
     return LIO_OK;
-}
+} LIO_CATCH

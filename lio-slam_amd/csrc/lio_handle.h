@@ -1,5 +1,5 @@
-// lio_handle.h -- the opaque handle behind include/liogpu.h and the small helpers every translation unit of the
-// C-ABI implementation uses (liogpu_api.hip, lio_multi.hip).  Host-side only.
+// lio_handle.h -- the opaque handle behind include/liogpu.h (liogpu_api.hip, lio_multi.hip, lio_mapbuild.hip).  Host-side
+// only; the error plumbing and the buffer types it is built from are in lio_pool.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -9,31 +9,16 @@
 
 #include "../../include/liogpu.h"
 #include "lio_kernels.h"
+#include "lio_pool.h"
 #include "lio_types.h"
 
-int lio_fail(int code, const char* what, hipError_t e = hipSuccess);
 int lio_pc2_check_xyz(const lio_pc2_layout* L);            // liogpu_api.hip
 void lio_raw_ws_free(struct LioRawWs* ws);                 // lio_mapbuild.hip
 
-#define HIPCHK(expr)                                                              \
-    do {                                                                          \
-        hipError_t _e = (expr);                                                   \
-        if (_e != hipSuccess) return lio_fail(LIO_ERR_HIP, #expr, _e);            \
-    } while (0)
-
-template <typename T>
-static hipError_t lio_grow(T** p, size_t* cap, size_t need, double slack = 1.25)
-{
-    if (need <= *cap && *p) return hipSuccess;
-    if (*p) { hipError_t e = hipFree(*p); if (e != hipSuccess) return e; *p = nullptr; }
-    size_t n = (size_t)((double)need * slack) + 64;
-    hipError_t e = hipMalloc((void**)p, n * sizeof(T));
-    if (e == hipSuccess) *cap = n;
-    else *cap = 0;
-    return e;
-}
-
+// Owns everything it points to except `map_src` and a stream installed by lio_s2m_set_stream (own_stream == false); the
+// destructor releases it on the current device, which lio_s2m_destroy sets.
 struct lio_s2m_handle {
+    ~lio_s2m_handle();                // liogpu_api.hip
     lio_s2m_config cfg;
     LioConsts c;
     hipStream_t stream = nullptr;
@@ -42,28 +27,22 @@ struct lio_s2m_handle {
     // ---- resident local map (laserCloudSurfFromMapDS, MO:149) ----
     bool has_map = false;
     size_t n_map = 0;
-    float *d_mx = nullptr, *d_my = nullptr, *d_mz = nullptr; size_t cap_mxyz[3] = {0, 0, 0};
-    float4* d_map4 = nullptr;   size_t cap_map4 = 0;
-    float4* d_sorted = nullptr; size_t cap_sorted = 0;
-    int* d_cell_of = nullptr;   size_t cap_cell_of = 0;
-    int* d_cell_count = nullptr; size_t cap_cell_count = 0;
-    int* d_cell_start = nullptr; size_t cap_cell_start = 0;
-    int* d_tile_sums = nullptr;  size_t cap_tile_sums = 0;
-    int* d_nbr_start = nullptr;  size_t cap_nbr_start = 0;
-    float4* d_nbr_pts = nullptr; size_t cap_nbr_pts = 0;
-    int* d_nbr_slot = nullptr;   size_t cap_nbr_slot = 0;      // [n_map][(2k+1)^2] place of every replica inside its row-cell list
-    unsigned* d_bbox = nullptr;
-    unsigned char* d_stage = nullptr; size_t cap_stage = 0;          // the resident batch's records as uploaded
-    unsigned char* d_map_stage = nullptr; size_t cap_map_stage = 0;  // lio_s2m_set_map's upload (its own buffer: the batch's staged
-                                                                     // records stay valid -- the one-launch loop and
-                                                                     // lio_kf_store_add_from_handle read them after a new map)
+    LioDevBuf<float> d_mx, d_my, d_mz;
+    LioDevBuf<float4> d_map4, d_sorted, d_nbr_pts;
+    LioDevBuf<int> d_cell_of, d_cell_count, d_cell_start, d_tile_sums, d_nbr_start;
+    LioDevBuf<int> d_nbr_slot;                 // [n_map][(2k+1)^2] place of every replica inside its row-cell list
+    LioDevBuf<unsigned> d_bbox;
+    LioDevBuf<unsigned char> d_stage;          // the resident batch's records as uploaded
+    LioDevBuf<unsigned char> d_map_stage;      // lio_s2m_set_map's upload (its own buffer: the batch's staged records stay
+                                               // valid -- the one-launch loop and lio_kf_store_add_from_handle read them
+                                               // after a new map)
     LioGrid grid{};
 
     // ---- resident scan batch (laserCloudSurfLastDS, MO:138) ----
     int n_scans = 0;
     size_t total_pts = 0;
-    float *d_sx = nullptr, *d_sy = nullptr, *d_sz = nullptr; size_t cap_sxyz[3] = {0, 0, 0};
-    LioScanState* d_state = nullptr; size_t cap_state = 0;
+    LioDevBuf<float> d_sx, d_sy, d_sz;
+    LioDevBuf<LioScanState> d_state;
     std::vector<LioScanState> h_state;
     std::vector<LioBlockDesc> v_blocks, v_prep;      // launch descriptors (kept alive for async H2D)
     std::vector<LioScanTiles> v_tiles;
@@ -71,32 +50,27 @@ struct lio_s2m_handle {
     std::vector<int> v_order, v_first, v_first_orig;
     bool defer_sync = false;                         // lio_s2m_register: one sync at the end of the call
     bool async_upload = false;                       // lio_s2m_batch_upload_async: wait for the H2D copy only
-    float* d_poses = nullptr; size_t cap_poses = 0;
+    LioDevBuf<float> d_poses;
     const float* reg_pose = nullptr;  // lio_s2m_register: the initial guess travels inside the state upload
     bool pose_in_state = false;       // ... and is taken from there by the next k_s2m_init_state (which copies it to d_poses)
-    float* d_summary = nullptr; size_t cap_summary = 0;   // [n_scans][10] compact results (lio_s2m_batch_results without `results`)
-    float* h_summary = nullptr; size_t cap_h_summary = 0; // pinned
+    LioDevBuf<float> d_summary;       // [n_scans][10] compact results (lio_s2m_batch_results without `results`)
+    LioPinned<float> h_summary;
     bool host_state_stale = false;    // h_state misses device-side updates (matP ...) since a summary-only read
-    LioBlockDesc* d_blocks = nullptr; size_t cap_blocks = 0;
+    LioDevBuf<LioBlockDesc> d_blocks;
     int n_blocks = 0, ppt = 1, max_blk = 1;
-    double* d_partials = nullptr; size_t cap_partials = 0;
-    unsigned* d_arrive = nullptr; size_t cap_arrive = 0;
+    LioDevBuf<double> d_partials;
+    LioDevBuf<unsigned> d_arrive;
     bool poses_set = false, ran = false;
     // upload-time tile sort of the scans
-    LioScanTiles* d_tiles = nullptr; size_t cap_tiles = 0;
-    LioBlockDesc* d_prep_blocks = nullptr; size_t cap_prep_blocks = 0;
-    int* d_key_of = nullptr; size_t cap_key_of = 0;
-    int* d_key_count = nullptr; size_t cap_key_count = 0;
-    int* d_key_start = nullptr; size_t cap_key_start = 0;
-    int* d_key_tiles = nullptr; size_t cap_key_tiles = 0;
-    int* d_tmp_idx = nullptr; size_t cap_tmp_idx = 0;
-    int* d_perm = nullptr; size_t cap_perm = 0;
-    float* d_block_box = nullptr; size_t cap_block_box = 0;   // map sharding: per-workgroup bounding boxes (cull)
+    LioDevBuf<LioScanTiles> d_tiles;
+    LioDevBuf<LioBlockDesc> d_prep_blocks;
+    LioDevBuf<int> d_key_of, d_key_count, d_key_start, d_key_tiles, d_tmp_idx, d_perm;
+    LioDevBuf<float> d_block_box;     // map sharding: per-workgroup bounding boxes (cull)
     bool has_block_box = false;
-    unsigned char* d_blk_skip = nullptr; size_t cap_blk_skip = 0;
-    int* d_big_list = nullptr; size_t cap_big_list = 0;   // tiles with more than LIO_TILE_CAP points (+ their count in the last slot)
-    unsigned* d_scan_bbox = nullptr; size_t cap_scan_bbox = 0;   // [n_scans][6] ordered-uint bounding boxes
-    unsigned* h_scan_bbox = nullptr; size_t cap_h_scan_bbox = 0; // pinned mirror
+    LioDevBuf<unsigned char> d_blk_skip;
+    LioDevBuf<int> d_big_list;        // tiles with more than LIO_TILE_CAP points (+ their count in the last slot)
+    LioDevBuf<unsigned> d_scan_bbox;  // [n_scans][6] ordered-uint bounding boxes
+    LioPinned<unsigned> h_scan_bbox;  // its host mirror
     bool sorted = false;
     const unsigned char* last_stage = nullptr;   // the records of the resident batch as uploaded (d_stage, or the caller's device buffer)
     size_t last_stride = 0, last_xyz_off = 0;
@@ -111,11 +85,11 @@ struct lio_s2m_handle {
     int persist_withhold = -1;           // test hook (lio_s2m_debug_persist_spin)
     lio_s2m_handle* map_src = nullptr;   // lio_s2m_share_map: the handle whose resident map this one searches
     unsigned long long map_epoch = 0;    // bumped by every set_map
-    float* d_nn_cache = nullptr; size_t cap_nn_cache = 0;   // [total_pts] squared 5th-neighbour distance of the previous GN iteration
-    long long* d_stamps = nullptr; size_t cap_stamps = 0;
+    LioDevBuf<float> d_nn_cache;         // [total_pts] squared 5th-neighbour distance of the previous GN iteration
+    LioDevBuf<long long> d_stamps;
     // one-launch loop (cfg.pipeline = 4, k_s2m_persist): per-scan generation numbers
-    unsigned* d_gen = nullptr; size_t cap_gen = 0;     // [2][cap_gen / 2]: generation numbers, then the speculation states
-    double* d_spec_sums = nullptr; size_t cap_spec_sums = 0;   // sums of the first solve of every scan (roll-back of the speculation)
+    LioDevBuf<unsigned> d_gen;        // [2][d_gen.cap / 2]: generation numbers, then the speculation states
+    LioDevBuf<double> d_spec_sums;    // sums of the first solve of every scan (roll-back of the speculation)
     unsigned gen_epoch = 0;           // grows by 128 per run: generation numbers are never cleared
     int n_cu = 0;                     // compute units of the device: every workgroup of a one-launch loop must be resident
     bool run_persist = false;
@@ -129,9 +103,9 @@ struct lio_s2m_handle {
     int units_this_run = 0, unit_iters = 1;
 
     // correspondence record (debug / parity)
-    unsigned char* d_rec_flag = nullptr; size_t cap_rec_flag = 0;
-    float* d_rec_coeff = nullptr; size_t cap_rec_coeff = 0;
-    int* d_rec_nn = nullptr; size_t cap_rec_nn = 0;
+    LioDevBuf<unsigned char> d_rec_flag;
+    LioDevBuf<float> d_rec_coeff;
+    LioDevBuf<int> d_rec_nn;
 
     // in-library multi-GPU mode (cfg.n_devices > 1): this handle is only a front; see struct LioMulti
     struct LioMulti* multi = nullptr;
@@ -162,9 +136,8 @@ struct lio_s2m_handle {
     hipEvent_t ev_map[2] = {};
     hipEvent_t ev_mapl[2] = {};        // asynchronous map installation (lio_s2m_set_map_device_bbox): build time resolved on demand; [1] = "map ready"
     bool map_timing_pending = false;
-    int* h_active = nullptr;          // pinned: active-scan count after each launch
-    bool ev_ok = false;
+    LioPinned<int> h_active;          // active-scan count after each launch
     lio_s2m_profile prof{};
     int launches_this_run = 0;
-    int* d_active = nullptr;
+    LioDevBuf<int> d_active;
 };

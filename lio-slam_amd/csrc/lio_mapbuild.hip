@@ -17,7 +17,6 @@
 #include "lio_scan2.h"
 #include "lio_voxsort.h"
 
-int lio_fail_ext(int code, const char* what, hipError_t e);                    // liogpu_api.hip
 int lio_s2m_set_map_device_xyzi(lio_s2m_handle* h, const float4* d_xyzi, size_t n);   // liogpu_api.hip
 int lio_s2m_set_map_device_bbox(lio_s2m_handle* h, const float4* d_xyzi, size_t n, const float box[6]);
 hipStream_t lio_s2m_stream_of(lio_s2m_handle* h);
@@ -183,34 +182,10 @@ __global__ void k_xyzi4_to_aos(const float4* __restrict__ src, int n, unsigned c
     o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = 1.0f; o[4] = v.w;
 }
 
-// Grow-only device buffer owned by a keyframe store: the workspace of lio_assemble_map_resident, kept from one call to
-// the next so that nothing has to be waited for before the call returns (a pool temporary is recycled on return).
-struct LioKeep {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t alloc(size_t bytes)
-    {
-        if (!bytes) bytes = 16;
-        if (p && bytes <= cap) return hipSuccess;
-        if (p) {                                          // growing: whoever still reads the old block must be done
-            hipError_t e = hipDeviceSynchronize();
-            if (e != hipSuccess) return e;
-            e = hipFree(p);
-            p = nullptr; cap = 0;
-            if (e != hipSuccess) return e;
-        }
-        const size_t want = bytes + bytes / 4 + 256;
-        const hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    template <typename T> T* as() { return (T*)p; }
-};
-
 namespace {
-typedef LioTemp Buf;         // temporaries come from the recycling pool (lio_pool.h)
 
+// B: LioTemp (pool temporaries, recycled when the call returns) or LioDevBytes (a workspace kept from one call to the next,
+// so that nothing has to be waited for before the call returns)
 template <class B> struct LioVoxWs { B bbox, large, pairs_a, pairs_b, hist, blk_heads, seg_start, d_no, row_total; };
 
 float ord2f(unsigned u)
@@ -339,21 +314,21 @@ int voxel_grid_device(const float4* d_in, int n, float leaf, B& out, int* n_out,
         *n_out = n;
         return 1;
     }
-    if (grc == 2) return lio_fail_ext(LIO_ERR_CAPACITY, "voxel grid has more than 2^31 - 1 voxels", hipSuccess);
+    if (grc == 2) return lio_fail(LIO_ERR_CAPACITY, "voxel grid has more than 2^31 - 1 voxels");
     (void)wait;                                  // (the sorting form always ends with the wait for the voxel count)
     return voxel_grid_sorted<B>(d_in, n, g, n_keys_ll, out, n_out, s, ws);
 }
 
-int voxel_grid_device(const float4* d_in, int n, float leaf, Buf& out, int* n_out, hipStream_t s)
+int voxel_grid_device(const float4* d_in, int n, float leaf, LioTemp& out, int* n_out, hipStream_t s)
 {
-    LioVoxWs<Buf> ws;
-    return voxel_grid_device<Buf>(d_in, n, leaf, out, n_out, s, ws, true, nullptr);
+    LioVoxWs<LioTemp> ws;
+    return voxel_grid_device<LioTemp>(d_in, n, leaf, out, n_out, s, ws, true, nullptr);
 }
 
 int copy_out(const float4* d_pts, int n, void* out, size_t out_stride, hipStream_t s)
 {
     if (!out || n == 0) return LIO_OK;
-    Buf aos;
+    LioTemp aos;
     HIPCHK(aos.alloc((size_t)n * out_stride));
     HIPCHK(hipMemsetAsync(aos.p, 0, (size_t)n * out_stride, s));
     hipLaunchKernelGGL(k_xyzi4_to_aos, dim3((n + 255) / 256), dim3(256), 0, s, d_pts, n, aos.as<unsigned char>(), out_stride);
@@ -366,7 +341,7 @@ int check_device(int device_id)
 {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return lio_fail_ext(LIO_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU fallback)", hipSuccess);
+        return lio_fail(LIO_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU fallback)");
     HIPCHK(hipSetDevice(device_id));
     (void)hipGetLastError();
     return LIO_OK;
@@ -375,17 +350,17 @@ int check_device(int device_id)
 
 extern "C" int lio_voxel_grid(int32_t device_id, const void* pts, size_t n, size_t stride, float leaf,
                               void* out, size_t out_stride, size_t* n_out)
-{
-    if (!n_out || (n && (!pts || !out))) return lio_fail_ext(LIO_ERR_ARG, "null argument", hipSuccess);
+try {
+    if (!n_out || (n && (!pts || !out))) return lio_fail(LIO_ERR_ARG, "null argument");
     if (stride < 20 || (stride & 3) || out_stride < 20 || (out_stride & 3) || !(leaf > 0.0f))
-        return lio_fail_ext(LIO_ERR_ARG, "strides must be >= 20 and multiples of 4, leaf > 0", hipSuccess);
-    if (n > 0x7fffffffull - 1024) return lio_fail_ext(LIO_ERR_CAPACITY, "cloud too large", hipSuccess);
+        return lio_fail(LIO_ERR_ARG, "strides must be >= 20 and multiples of 4, leaf > 0");
+    if (n > 0x7fffffffull - 1024) return lio_fail(LIO_ERR_CAPACITY, "cloud too large");
     *n_out = 0;
     if (n == 0) return LIO_OK;
     int rc = check_device(device_id);
     if (rc != LIO_OK) return rc;
     hipStream_t s = nullptr;
-    Buf raw, xyzi, ds;
+    LioTemp raw, xyzi, ds;
     HIPCHK(raw.alloc(n * stride));
     HIPCHK(xyzi.alloc(n * sizeof(float4)));
     HIPCHK(hipMemcpyAsync(raw.p, pts, n * stride, hipMemcpyHostToDevice, s));
@@ -397,19 +372,20 @@ extern "C" int lio_voxel_grid(int32_t device_id, const void* pts, size_t n, size
     if (rc2 < 0) return rc2;
     *n_out = (size_t)no;
     return rc;
-}
+} LIO_CATCH
 
 // ------------------------------------------------------- resident keyframe store
 // surfCloudKeyFrames (MO:128): every keyframe cloud is uploaded ONCE (MO:2138-2142) and stays in
 // HBM; assembling the local map for a scan only needs the selected ids and their current poses.
 struct lio_kf_store {
+    ~lio_kf_store() { if (ev_ids) (void)hipEventDestroy(ev_ids); }   // (the buffers: on the device lio_kf_store_destroy sets)
     int device_id = 0;
-    float4* d_pts = nullptr;
-    size_t cap = 0, used = 0;
+    LioDevBuf<float4> d_pts;
+    size_t used = 0;
     std::vector<size_t> off, cnt;
     // workspace of lio_assemble_map_resident when the map is installed in a handle (kept between calls)
-    LioVoxWs<LioKeep> vws;
-    LioKeep world, ds, d_kf, d_poses, d_chunks, blk_box;
+    LioVoxWs<LioDevBytes> vws;
+    LioDevBytes world, ds, d_kf, d_poses, d_chunks, blk_box;
     std::vector<LioKfDesc> v_kf;
     std::vector<int2> v_chunks;
     // key-pose table = cloudKeyPoses6D (x, y, z, roll, pitch, yaw, time): host copy written by lio_kf_store_set_poses (never
@@ -418,39 +394,30 @@ struct lio_kf_store {
     std::vector<double> ptime;
     std::vector<unsigned char> has_pose, has_time;
     size_t n_posed = 0, dirty_lo = SIZE_MAX, dirty_hi = 0, tab_cap = 0;
-    LioKeep d_tab;                                   // [tab_cap] x 6 float, [tab_cap] double, [tab_cap] x 2 int
-    unsigned char* h_stage = nullptr;                // pinned: the dirty range on its way up, then (n_ids, total), then ids
-    size_t stage_cap = 0;
+    LioDevBytes d_tab;                               // [tab_cap] x 6 float, [tab_cap] double, [tab_cap] x 2 int
+    LioPinned<unsigned char> h_stage;                // the dirty range on its way up, then (n_ids, total), then ids
     // workspace of lio_assemble_map_nearby's selection
-    LioVoxWs<LioKeep> nws;
-    LioKeep nb_pts, nb_cent, nb_cid, nb_ids, nb_meta;
+    LioVoxWs<LioDevBytes> nws;
+    LioDevBytes nb_pts, nb_cent, nb_cid, nb_ids, nb_meta;
     hipEvent_t ev_ids = nullptr;
 };
 
 extern "C" int lio_kf_store_create(int32_t device_id, lio_kf_store** out)
-{
-    if (!out) return lio_fail_ext(LIO_ERR_ARG, "null argument", hipSuccess);
+try {
+    if (!out) return lio_fail(LIO_ERR_ARG, "null argument");
     int rc = check_device(device_id);
     if (rc != LIO_OK) return rc;
     lio_kf_store* s = new lio_kf_store();
     s->device_id = device_id;
     *out = s;
     return LIO_OK;
-}
+} LIO_CATCH
 
 extern "C" void lio_kf_store_destroy(lio_kf_store* s)
 {
     if (!s) return;
     (void)hipSetDevice(s->device_id);
     (void)hipDeviceSynchronize();
-    if (s->d_pts) (void)hipFree(s->d_pts);
-    LioKeep* keep[] = { &s->vws.bbox, &s->vws.large, &s->vws.pairs_a, &s->vws.pairs_b, &s->vws.hist, &s->vws.blk_heads, &s->vws.seg_start, &s->vws.d_no, &s->vws.row_total,
-                        &s->world, &s->ds, &s->d_kf, &s->d_poses, &s->d_chunks, &s->blk_box,
-                        &s->nws.bbox, &s->nws.large, &s->nws.pairs_a, &s->nws.pairs_b, &s->nws.hist, &s->nws.blk_heads, &s->nws.seg_start,
-                        &s->nws.d_no, &s->nws.row_total, &s->d_tab, &s->nb_pts, &s->nb_cent, &s->nb_cid, &s->nb_ids, &s->nb_meta };
-    for (LioKeep* k : keep) k->release();
-    if (s->h_stage) (void)hipHostFree(s->h_stage);
-    if (s->ev_ids) (void)hipEventDestroy(s->ev_ids);
     delete s;
 }
 
@@ -459,16 +426,14 @@ extern "C" size_t lio_kf_store_points(const lio_kf_store* s, int32_t id) { retur
 
 static int kf_store_reserve(lio_kf_store* s, size_t n)
 {
-    if (s->used + n > 0x7fffffffull - 1024) return lio_fail_ext(LIO_ERR_CAPACITY, "keyframe store is full", hipSuccess);
-    if (s->used + n > s->cap) {                         // grow geometrically, keep the resident clouds
-        size_t ncap = (s->cap ? s->cap * 2 : (size_t)1 << 20);
+    if (s->used + n > 0x7fffffffull - 1024) return lio_fail(LIO_ERR_CAPACITY, "keyframe store is full");
+    if (s->used + n > s->d_pts.cap) {                   // grow geometrically, keep the resident clouds
+        size_t ncap = (s->d_pts.cap ? s->d_pts.cap * 2 : (size_t)1 << 20);
         while (ncap < s->used + n) ncap *= 2;
-        float4* np_ = nullptr;
-        HIPCHK(hipMalloc((void**)&np_, ncap * sizeof(float4)));
+        LioDevBuf<float4> np_;
+        HIPCHK(np_.grow(ncap, 1.0, 0));
         if (s->used) HIPCHK(hipMemcpy(np_, s->d_pts, s->used * sizeof(float4), hipMemcpyDeviceToDevice));
-        if (s->d_pts) HIPCHK(hipFree(s->d_pts));
-        s->d_pts = np_;
-        s->cap = ncap;
+        s->d_pts = std::move(np_);                       // (frees the old block)
     }
     return LIO_OK;
 }
@@ -499,14 +464,14 @@ __global__ void k_rec_to_xyzi4(const unsigned char* __restrict__ src, size_t str
 }
 
 extern "C" int lio_kf_store_add(lio_kf_store* s, const void* cloud, size_t n, size_t stride, int32_t* id_out)
-{
-    if (!s || (n && !cloud)) return lio_fail_ext(LIO_ERR_ARG, "null argument", hipSuccess);
-    if (stride < 20 || (stride & 3)) return lio_fail_ext(LIO_ERR_ARG, "stride must be >= 20 and a multiple of 4", hipSuccess);
+try {
+    if (!s || (n && !cloud)) return lio_fail(LIO_ERR_ARG, "null argument");
+    if (stride < 20 || (stride & 3)) return lio_fail(LIO_ERR_ARG, "stride must be >= 20 and a multiple of 4");
     int rc = check_device(s->device_id);
     if (rc != LIO_OK) return rc;
     if ((rc = kf_store_reserve(s, n)) != LIO_OK) return rc;
     if (n) {
-        Buf raw;
+        LioTemp raw;
         HIPCHK(raw.alloc(n * stride));
         HIPCHK(hipMemcpyAsync(raw.p, cloud, n * stride, hipMemcpyDefault, nullptr));
         hipLaunchKernelGGL(k_aos_to_xyzi4, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr,
@@ -516,12 +481,12 @@ extern "C" int lio_kf_store_add(lio_kf_store* s, const void* cloud, size_t n, si
     }
     kf_store_commit(s, n, id_out);
     return LIO_OK;
-}
+} LIO_CATCH
 
 extern "C" int lio_kf_store_add_device(lio_kf_store* s, const void* d_cloud, size_t n, size_t stride, int32_t* id_out)
-{
-    if (!s || (n && !d_cloud)) return lio_fail_ext(LIO_ERR_ARG, "null argument", hipSuccess);
-    if (stride < 12 || (stride & 3)) return lio_fail_ext(LIO_ERR_ARG, "stride must be >= 12 and a multiple of 4", hipSuccess);
+try {
+    if (!s || (n && !d_cloud)) return lio_fail(LIO_ERR_ARG, "null argument");
+    if (stride < 12 || (stride & 3)) return lio_fail(LIO_ERR_ARG, "stride must be >= 12 and a multiple of 4");
     int rc = check_device(s->device_id);
     if (rc != LIO_OK) return rc;
     if ((rc = kf_store_reserve(s, n)) != LIO_OK) return rc;
@@ -534,21 +499,21 @@ extern "C" int lio_kf_store_add_device(lio_kf_store* s, const void* d_cloud, siz
     }
     kf_store_commit(s, n, id_out);
     return LIO_OK;
-}
+} LIO_CATCH
 
 int lio_s2m_staged_scan(lio_s2m_handle* h, int scan, const unsigned char** d_rec, size_t* n, size_t* stride, size_t* xyz_off, int* int_off,
                         int* device_id, hipStream_t* stream);   // liogpu_api.hip
 
 extern "C" int lio_kf_store_add_from_handle(lio_kf_store* s, lio_s2m_handle* h, int32_t scan, int32_t* id_out)
-{
-    if (!s || !h) return lio_fail_ext(LIO_ERR_ARG, "null argument", hipSuccess);
+try {
+    if (!s || !h) return lio_fail(LIO_ERR_ARG, "null argument");
     const unsigned char* rec = nullptr;
     size_t n = 0, stride = 0, xyz_off = 0;
     int dev = 0, int_off = -1;
     hipStream_t st = nullptr;
     int rc = lio_s2m_staged_scan(h, scan, &rec, &n, &stride, &xyz_off, &int_off, &dev, &st);
     if (rc != LIO_OK) return rc;
-    if (dev != s->device_id) return lio_fail_ext(LIO_ERR_ARG, "the handle and the keyframe store live on different devices", hipSuccess);
+    if (dev != s->device_id) return lio_fail(LIO_ERR_ARG, "the handle and the keyframe store live on different devices");
     if ((rc = check_device(s->device_id)) != LIO_OK) return rc;
     if ((rc = kf_store_reserve(s, n)) != LIO_OK) return rc;
     if (n) {
@@ -561,7 +526,7 @@ extern "C" int lio_kf_store_add_from_handle(lio_kf_store* s, lio_s2m_handle* h, 
     }
     kf_store_commit(s, n, id_out);
     return LIO_OK;
-}
+} LIO_CATCH
 
 // K6 + K7 from selection descriptors already on the device -- src / first / n of every selected keyframe (d_kf, T filled
 // here), its pose (d_poses, [roll,pitch,yaw,x,y,z]) and the 256-point chunks of K6 (d_chunks) -- then the map into `h`:
@@ -573,22 +538,22 @@ static int assemble_tail(lio_s2m_handle* h, lio_kf_store* st, int n_sel, size_t 
 
 extern "C" int lio_assemble_map_resident(lio_s2m_handle* h, lio_kf_store* st, int32_t n_sel, const int32_t* ids,
                                          const float* poses, float leaf, void* out, size_t out_stride, size_t* n_out)
-{
-    if (!st || n_sel < 0 || (n_sel && (!ids || !poses))) return lio_fail_ext(LIO_ERR_ARG, "null argument", hipSuccess);
+try {
+    if (!st || n_sel < 0 || (n_sel && (!ids || !poses))) return lio_fail(LIO_ERR_ARG, "null argument");
     if ((out && (out_stride < 20 || (out_stride & 3))) || !(leaf > 0.0f))
-        return lio_fail_ext(LIO_ERR_ARG, "output stride must be >= 20 and a multiple of 4, leaf > 0", hipSuccess);
+        return lio_fail(LIO_ERR_ARG, "output stride must be >= 20 and a multiple of 4, leaf > 0");
     int rc = check_device(st->device_id);
     if (rc != LIO_OK) return rc;
     size_t total = 0;
     std::vector<LioKfDesc> kf((size_t)n_sel);
     std::vector<int2> chunks;
     for (int k = 0; k < n_sel; ++k) {
-        if (ids[k] < 0 || (size_t)ids[k] >= st->off.size()) return lio_fail_ext(LIO_ERR_ARG, "unknown keyframe id", hipSuccess);
+        if (ids[k] < 0 || (size_t)ids[k] >= st->off.size()) return lio_fail(LIO_ERR_ARG, "unknown keyframe id");
         kf[k].src = (int)st->off[ids[k]]; kf[k].first = (int)total; kf[k].n = (int)st->cnt[ids[k]]; kf[k].pad = 0;
         for (size_t b = 0; b < st->cnt[ids[k]]; b += 256) chunks.push_back(make_int2(k, (int)b));
         total += st->cnt[ids[k]];
     }
-    if (total > 0x7fffffffull - 1024) return lio_fail_ext(LIO_ERR_CAPACITY, "too many points", hipSuccess);
+    if (total > 0x7fffffffull - 1024) return lio_fail(LIO_ERR_CAPACITY, "too many points");
     if (n_out) *n_out = 0;
     const int n_chunks = (int)chunks.size();
     if (lio_s2m_takes_device_map(h)) {
@@ -612,7 +577,7 @@ extern "C" int lio_assemble_map_resident(lio_s2m_handle* h, lio_kf_store* st, in
                              s, leaf, out, out_stride, SIZE_MAX, n_out);
     }
     hipStream_t s = nullptr;
-    Buf d_kf, d_poses, d_chunks;
+    LioTemp d_kf, d_poses, d_chunks;
     HIPCHK(d_kf.alloc(sizeof(LioKfDesc) * (size_t)(n_sel ? n_sel : 1)));
     HIPCHK(d_poses.alloc(sizeof(float) * 6 * (size_t)(n_sel ? n_sel : 1)));
     HIPCHK(d_chunks.alloc(sizeof(int2) * (n_chunks ? n_chunks : 1)));
@@ -623,7 +588,7 @@ extern "C" int lio_assemble_map_resident(lio_s2m_handle* h, lio_kf_store* st, in
     if (n_chunks) HIPCHK(hipMemcpyAsync(d_chunks.p, chunks.data(), sizeof(int2) * n_chunks, hipMemcpyHostToDevice, s));
     return assemble_tail(h, st, n_sel, total, n_chunks, d_kf.as<LioKfDesc>(), d_poses.as<float>(), d_chunks.as<int2>(), s, leaf, out,
                          out_stride, SIZE_MAX, n_out);
-}
+} LIO_CATCH
 
 static int assemble_tail(lio_s2m_handle* h, lio_kf_store* st, int n_sel, size_t total, int n_chunks, LioKfDesc* d_kf,
                          const float* d_poses, const int2* d_chunks, hipStream_t s, float leaf, void* out, size_t out_stride, size_t out_cap,
@@ -641,17 +606,17 @@ static int assemble_tail(lio_s2m_handle* h, lio_kf_store* st, int n_sel, size_t 
         hipLaunchKernelGGL(k_bbox_reduce, dim3(1), dim3(256), 0, s, st->blk_box.as<float>(), n_chunks, st->vws.bbox.as<unsigned>());
         int no = 0;
         float box[6];
-        rc = voxel_grid_device<LioKeep>(st->world.as<float4>(), (int)total, leaf, st->ds, &no, s, st->vws, false, box, true);
+        rc = voxel_grid_device<LioDevBytes>(st->world.as<float4>(), (int)total, leaf, st->ds, &no, s, st->vws, false, box, true);
         if (rc < 0) return rc;
         const int rc3 = lio_s2m_set_map_device_bbox(h, st->ds.as<float4>(), (size_t)no, box);
         if (rc3 != LIO_OK) return rc3;
-        if (out && (size_t)no > out_cap) { if (n_out) *n_out = (size_t)no; return lio_fail_ext(LIO_ERR_ARG, "out holds fewer records than the map (*n_out)", hipSuccess); }
+        if (out && (size_t)no > out_cap) { if (n_out) *n_out = (size_t)no; return lio_fail(LIO_ERR_ARG, "out holds fewer records than the map (*n_out)"); }
         const int rc2 = copy_out(st->ds.as<float4>(), no, out, out_stride, s);
         if (rc2 < 0) return rc2;
         if (n_out) *n_out = (size_t)no;
         return rc;
     }
-    Buf world, ds;
+    LioTemp world, ds;
     HIPCHK(world.alloc(total * sizeof(float4)));
     if (n_chunks)
         hipLaunchKernelGGL(k_transform_clouds, dim3((unsigned)n_chunks), dim3(256), 0, s, st->d_pts, d_kf, d_chunks, world.as<float4>());
@@ -663,7 +628,7 @@ static int assemble_tail(lio_s2m_handle* h, lio_kf_store* st, int n_sel, size_t 
         const int rc3 = lio_s2m_set_map_device_xyzi(h, ds.as<float4>(), (size_t)no);
         if (rc3 != LIO_OK) return rc3;
     }
-    if (out && (size_t)no > out_cap) { if (n_out) *n_out = (size_t)no; return lio_fail_ext(LIO_ERR_ARG, "out holds fewer records than the map (*n_out)", hipSuccess); }
+    if (out && (size_t)no > out_cap) { if (n_out) *n_out = (size_t)no; return lio_fail(LIO_ERR_ARG, "out holds fewer records than the map (*n_out)"); }
     const int rc2 = copy_out(ds.as<float4>(), no, out, out_stride, s);
     if (rc2 < 0) return rc2;
     if (n_out) *n_out = (size_t)no;
@@ -674,17 +639,17 @@ static int assemble_tail(lio_s2m_handle* h, lio_kf_store* st, int n_sel, size_t 
 extern "C" int lio_assemble_map(lio_s2m_handle* h, int32_t device_id, int32_t n_kf, const void* const* clouds,
                                 const size_t* n_pts, size_t stride, const float* poses, float leaf,
                                 void* out, size_t out_stride, size_t* n_out)
-{
-    if (!clouds || !n_pts || !poses || n_kf < 0) return lio_fail_ext(LIO_ERR_ARG, "null argument", hipSuccess);
+try {
+    if (!clouds || !n_pts || !poses || n_kf < 0) return lio_fail(LIO_ERR_ARG, "null argument");
+    std::vector<int32_t> ids((size_t)n_kf);
     lio_kf_store* st = nullptr;
     int rc = lio_kf_store_create(device_id, &st);
     if (rc != LIO_OK) return rc;
-    std::vector<int32_t> ids((size_t)n_kf);
     for (int k = 0; k < n_kf && rc == LIO_OK; ++k) rc = lio_kf_store_add(st, clouds[k], n_pts[k], stride, &ids[k]);
     if (rc == LIO_OK) rc = lio_assemble_map_resident(h, st, n_kf, ids.data(), poses, leaf, out, out_stride, n_out);
     lio_kf_store_destroy(st);
     return rc;
-}
+} LIO_CATCH
 
 
 // ------------------------------------------------ surrounding keyframes on the device (extractNearby MO:1519-1551 + MO:1562)
@@ -895,15 +860,15 @@ extern "C" void lio_nearby_default_config(lio_nearby_config* cfg)
 }
 
 extern "C" int lio_kf_store_set_poses(lio_kf_store* s, int32_t first, int32_t n, const float* poses, const double* times)
-{
-    if (!s || first < 0 || n < 0 || (n && !poses)) return lio_fail_ext(LIO_ERR_ARG, "null argument", hipSuccess);
+try {
+    if (!s || first < 0 || n < 0 || (n && !poses)) return lio_fail(LIO_ERR_ARG, "null argument");
     if ((size_t)first + (size_t)n > s->off.size())
-        return lio_fail_ext(LIO_ERR_ARG, "poses for keyframes the store does not hold (add the cloud first)", hipSuccess);
+        return lio_fail(LIO_ERR_ARG, "poses for keyframes the store does not hold (add the cloud first)");
     for (int k = 0; k < n; ++k) {
         for (int j = 0; j < 6; ++j)
-            if (!std::isfinite(poses[(size_t)k * 6 + j])) return lio_fail_ext(LIO_ERR_ARG, "non-finite key pose", hipSuccess);
+            if (!std::isfinite(poses[(size_t)k * 6 + j])) return lio_fail(LIO_ERR_ARG, "non-finite key pose");
         if (times ? !std::isfinite(times[k]) : !s->has_time[(size_t)first + k])
-            return lio_fail_ext(LIO_ERR_ARG, times ? "non-finite key pose time" : "times == NULL for a keyframe that has no time yet", hipSuccess);
+            return lio_fail(LIO_ERR_ARG, times ? "non-finite key pose time" : "times == NULL for a keyframe that has no time yet");
     }
     for (int k = 0; k < n; ++k) {                    // host only: whatever is in flight keeps the table it was given
         const size_t i = (size_t)first + k;
@@ -914,7 +879,7 @@ extern "C" int lio_kf_store_set_poses(lio_kf_store* s, int32_t first, int32_t n,
     }
     if (n) { s->dirty_lo = std::min(s->dirty_lo, (size_t)first); s->dirty_hi = std::max(s->dirty_hi, (size_t)first + n); }
     return LIO_OK;
-}
+} LIO_CATCH
 
 // the dirty range of the key-pose table (and off / cnt) to the device, on stream `s`, through the pinned stage
 static int upload_pose_tab(lio_kf_store* st, hipStream_t s)
@@ -925,20 +890,12 @@ static int upload_pose_tab(lio_kf_store* st, hipStream_t s)
         HIPCHK(st->d_tab.alloc(st->tab_cap * 40));
         st->dirty_lo = 0; st->dirty_hi = N;
     }
-    if (!st->h_stage) {                              // (the stage also receives the selection's counts)
-        HIPCHK(hipHostMalloc((void**)&st->h_stage, 4096, hipHostMallocPortable));
-        st->stage_cap = 4096;
-    }
+    HIPCHK(st->h_stage.grow(0, 4096, hipHostMallocPortable));   // (the stage also receives the selection's counts)
     if (st->dirty_lo >= st->dirty_hi) return LIO_OK;
     const size_t lo = st->dirty_lo, L = std::min(st->dirty_hi, N) - lo;
-    if (L * 40 > st->stage_cap) {                    // (the stage is idle: every call ends with a wait behind its copies)
-        if (st->h_stage) HIPCHK(hipHostFree(st->h_stage));
-        st->h_stage = nullptr; st->stage_cap = 0;
-        const size_t want = std::max<size_t>(L * 40 + L * 10, 4096);
-        HIPCHK(hipHostMalloc((void**)&st->h_stage, want, hipHostMallocPortable));
-        st->stage_cap = want;
-    }
-    float* f = (float*)st->h_stage;
+    // (the stage is idle: every call ends with a wait behind its copies)
+    HIPCHK(st->h_stage.grow(L * 40, std::max<size_t>(L * 40 + L * 10, 4096), hipHostMallocPortable));
+    float* f = (float*)st->h_stage.p;
     const std::vector<float>* cols[6] = { &st->px, &st->py, &st->pz, &st->proll, &st->ppitch, &st->pyaw };
     for (int c = 0; c < 6; ++c) memcpy(f + c * L, cols[c]->data() + lo, L * sizeof(float));
     memcpy(f + 6 * L, st->ptime.data() + lo, L * sizeof(double));
@@ -957,28 +914,28 @@ static int upload_pose_tab(lio_kf_store* st, hipStream_t s)
 extern "C" int lio_assemble_map_nearby(lio_s2m_handle* h, lio_kf_store* st, const lio_nearby_config* cfg, double time_cur,
                                        float leaf, int32_t* ids_out, int32_t ids_cap, int32_t* n_ids, void* out,
                                        size_t out_stride, size_t out_cap, size_t* n_out)
-{
-    if (!st || !cfg || ids_cap < 0) return lio_fail_ext(LIO_ERR_ARG, "null argument", hipSuccess);
+try {
+    if (!st || !cfg || ids_cap < 0) return lio_fail(LIO_ERR_ARG, "null argument");
     if ((out && (out_stride < 20 || (out_stride & 3))) || !(leaf > 0.0f))
-        return lio_fail_ext(LIO_ERR_ARG, "output stride must be >= 20 and a multiple of 4, leaf > 0", hipSuccess);
+        return lio_fail(LIO_ERR_ARG, "output stride must be >= 20 and a multiple of 4, leaf > 0");
     const float R = cfg->search_radius;
     if (!(R > 0.0f) || !std::isfinite(R) || !(cfg->pose_density > 0.0f) || !std::isfinite(cfg->pose_density) ||
         !std::isfinite(cfg->recent_window_s) || !std::isfinite(time_cur))
-        return lio_fail_ext(LIO_ERR_ARG, "search_radius, pose_density > 0 and finite; recent_window_s, time_cur finite", hipSuccess);
+        return lio_fail(LIO_ERR_ARG, "search_radius, pose_density > 0 and finite; recent_window_s, time_cur finite");
     if (n_ids) *n_ids = 0;
     if (n_out) *n_out = 0;
     int rc = check_device(st->device_id);
     if (rc != LIO_OK) return rc;
     if (h && h->cfg.device_id != st->device_id)
-        return lio_fail_ext(LIO_ERR_ARG, "the handle and the keyframe store live on different devices", hipSuccess);
+        return lio_fail(LIO_ERR_ARG, "the handle and the keyframe store live on different devices");
     const int N = (int)st->off.size();
     if (N == 0) return LIO_OK;                       // MO:1592-1593: nothing to extract, the map stays as it is
-    if (st->n_posed != (size_t)N) return lio_fail_ext(LIO_ERR_ARG, "a keyframe has no pose (lio_kf_store_set_poses)", hipSuccess);
+    if (st->n_posed != (size_t)N) return lio_fail(LIO_ERR_ARG, "a keyframe has no pose (lio_kf_store_set_poses)");
     const bool node = lio_s2m_takes_device_map(h);
     hipStream_t s = node ? lio_s2m_stream_of(h) : nullptr;
     if ((rc = upload_pose_tab(st, s)) != LIO_OK) return rc;
     if (!st->ev_ids) HIPCHK(hipEventCreateWithFlags(&st->ev_ids, hipEventDisableTiming));
-    if ((rc = vsort_reserve<LioKeep>(N, st->nb_cent, st->nws)) != LIO_OK) return rc;
+    if ((rc = vsort_reserve<LioDevBytes>(N, st->nb_cent, st->nws)) != LIO_OK) return rc;
     HIPCHK(st->nb_pts.alloc(sizeof(float4) * (size_t)N));
     HIPCHK(st->nb_cid.alloc(sizeof(unsigned long long) * (size_t)N));
     HIPCHK(st->nb_ids.alloc(sizeof(int) * 2 * (size_t)N));
@@ -992,36 +949,31 @@ extern "C" int lio_assemble_map_nearby(lio_s2m_handle* h, lio_kf_store* st, cons
     const float r2 = (float)((double)R * (double)R);                // what PCL hands FLANN
     hipLaunchKernelGGL(k_nb_select, dim3(nblk), dim3(256), 0, s, tab, N, r2, time_cur, cfg->recent_window_s,
                        st->nws.pairs_a.as<uint2>(), m);
-    uint2* hits = vsort_pairs<LioKeep>(N, 32, s, st->nws);          // (d2, i) ascending, the misses last
+    uint2* hits = vsort_pairs<LioDevBytes>(N, 32, s, st->nws);      // (d2, i) ascending, the misses last
     // (an even number of passes ends in pairs_a, where the second sort starts: k_nb_voxkeys rewrites the pairs in place)
-    if (hits != st->nws.pairs_a.as<uint2>()) return lio_fail_ext(LIO_ERR_HIP, "radix sort ended in the wrong buffer", hipSuccess);
+    if (hits != st->nws.pairs_a.as<uint2>()) return lio_fail(LIO_ERR_HIP, "radix sort ended in the wrong buffer");
     hipLaunchKernelGGL(k_nb_voxkeys, dim3(nblk), dim3(256), 0, s, tab, N, 1.0f / cfg->pose_density, m, hits, st->nb_pts.as<float4>());
-    const uint2* vox = vsort_pairs<LioKeep>(N, 32, s, st->nws);
-    if ((rc = vsort_centroids<LioKeep>(st->nb_pts.as<float4>(), vox, N, st->nb_cent, s, st->nws)) != LIO_OK) return rc;
+    const uint2* vox = vsort_pairs<LioDevBytes>(N, 32, s, st->nws);
+    if ((rc = vsort_centroids<LioDevBytes>(st->nb_pts.as<float4>(), vox, N, st->nb_cent, s, st->nws)) != LIO_OK) return rc;
     const int* d_no = st->nws.d_no.as<int>();
     HIPCHK(hipMemsetAsync(st->nb_cid.p, 0xff, sizeof(unsigned long long) * (size_t)N, s));
     hipLaunchKernelGGL(k_nb_relabel, dim3((unsigned)((N + 63) / 64), (unsigned)((N + NB_SPLIT - 1) / NB_SPLIT)), dim3(64), 0, s, tab, N,
                        st->nb_cent.as<float4>(), m, d_no, st->nb_cid.as<unsigned long long>());
     hipLaunchKernelGGL(k_nb_compact, dim3(1), dim3(256), 0, s, tab, N, R, st->nb_cent.as<float4>(), st->nb_cid.as<unsigned long long>(), m, d_no,
                        st->nb_ids.as<int>(), st->d_kf.as<LioKfDesc>(), st->d_poses.as<float>());
-    LioNbMeta* hm = (LioNbMeta*)st->h_stage;                        // (the stage exists: the first call uploaded through it)
+    LioNbMeta* hm = (LioNbMeta*)st->h_stage.p;                        // (the stage exists: the first call uploaded through it)
     HIPCHK(hipMemcpyAsync(hm, m, sizeof(LioNbMeta), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));                                // THE wait of the selection: (n_ids, total points, chunks)
     HIPCHK(hipGetLastError());
     const int n_sel = hm->n_ids, n_chunks = hm->n_chunks;
     const unsigned long long total = hm->total;
     if (n_ids) *n_ids = n_sel;
-    if (ids_out && ids_cap < n_sel) return lio_fail_ext(LIO_ERR_ARG, "ids_cap is smaller than the selected list (*n_ids)", hipSuccess);
-    if (total > 0x7fffffffull - 1024) return lio_fail_ext(LIO_ERR_CAPACITY, "too many points", hipSuccess);
-    int* h_ids = (int*)st->h_stage;
+    if (ids_out && ids_cap < n_sel) return lio_fail(LIO_ERR_ARG, "ids_cap is smaller than the selected list (*n_ids)");
+    if (total > 0x7fffffffull - 1024) return lio_fail(LIO_ERR_CAPACITY, "too many points");
+    int* h_ids = (int*)st->h_stage.p;
     if (ids_out && n_sel) {
-        if ((size_t)n_sel * sizeof(int) > st->stage_cap) {
-            HIPCHK(hipHostFree(st->h_stage));
-            st->h_stage = nullptr; st->stage_cap = 0;
-            HIPCHK(hipHostMalloc((void**)&st->h_stage, (size_t)n_sel * sizeof(int) * 2, hipHostMallocPortable));
-            st->stage_cap = (size_t)n_sel * sizeof(int) * 2;
-            h_ids = (int*)st->h_stage;
-        }
+        HIPCHK(st->h_stage.grow((size_t)n_sel * sizeof(int), (size_t)n_sel * sizeof(int) * 2, hipHostMallocPortable));
+        h_ids = (int*)st->h_stage.p;
         HIPCHK(hipMemcpyAsync(h_ids, st->nb_ids.p, (size_t)n_sel * sizeof(int), hipMemcpyDeviceToHost, s));
         HIPCHK(hipEventRecord(st->ev_ids, s));                      // (complete by the voxel filter's waits further down)
     }
@@ -1034,13 +986,19 @@ extern "C" int lio_assemble_map_nearby(lio_s2m_handle* h, lio_kf_store* st, cons
         memcpy(ids_out, h_ids, (size_t)n_sel * sizeof(int));
     }
     return rc;
-}
+} LIO_CATCH
 
 // ------------------------------------------------ one callback on the device: downsample + register (SURVEY 8f / verdict r2)
 // Staged cloud and voxel-filter workspace of lio_s2m_register_raw, kept on the handle from one callback to the next.
 struct LioRawWs {
-    LioKeep raw, xyzi, ds;
-    LioVoxWs<LioKeep> vws;
+    ~LioRawWs()
+    {
+        if (ev_in) (void)hipEventDestroy(ev_in);
+        if (ev_done) (void)hipEventDestroy(ev_done);
+        if (aux) (void)hipStreamDestroy(aux);
+    }
+    LioDevBytes raw, xyzi, ds;
+    LioVoxWs<LioDevBytes> vws;
     // the upload and the voxel filter of the sweep run on a stream of their own: they do not depend on the local map, whose
     // assembly (lio_assemble_map_resident: K6 + K7 + grid build, ~0.25 ms of small kernels) is usually still in flight on the
     // handle's stream when the node calls lio_s2m_register_raw -- the two chains overlap on the GPU, and the filter's host
@@ -1049,17 +1007,7 @@ struct LioRawWs {
     hipEvent_t ev_in = nullptr, ev_done = nullptr;
 };
 
-void lio_raw_ws_free(LioRawWs* w)
-{
-    if (!w) return;
-    LioKeep* keep[] = { &w->raw, &w->xyzi, &w->ds, &w->vws.bbox, &w->vws.large, &w->vws.pairs_a, &w->vws.pairs_b, &w->vws.hist,
-                        &w->vws.blk_heads, &w->vws.seg_start, &w->vws.d_no, &w->vws.row_total };
-    for (LioKeep* k : keep) k->release();
-    if (w->ev_in) (void)hipEventDestroy(w->ev_in);
-    if (w->ev_done) (void)hipEventDestroy(w->ev_done);
-    if (w->aux) (void)hipStreamDestroy(w->aux);
-    delete w;
-}
+void lio_raw_ws_free(LioRawWs* w) { delete w; }
 
 // downsampleCurrentScan MO:1605-1611 + scan2MapOptimization MO:1839-1865 without a host round trip in between:
 // the deskewed cloud goes up once (or is read in place when it already lives on the device), is voxel-filtered on the
@@ -1069,14 +1017,14 @@ void lio_raw_ws_free(LioRawWs* w)
 // lio_kf_store_add_from_handle turns it into a keyframe (saveKeyFramesAndFactor MO:2136-2142) with its intensities.
 extern "C" int lio_s2m_register_raw(lio_s2m_handle* h, const void* data, size_t n_points, const lio_pc2_layout* layout, float leaf,
                                     float pose[6], lio_s2m_result* res, void* ds_out, size_t ds_out_stride, size_t* n_ds)
-{
-    if (!h || !layout || !pose) return lio_fail_ext(LIO_ERR_ARG, "null argument", hipSuccess);
-    if (h->multi || h->corner_active) return lio_fail_ext(LIO_ERR_ARG, "lio_s2m_register_raw needs a plain single-device handle", hipSuccess);
+try {
+    if (!h || !layout || !pose) return lio_fail(LIO_ERR_ARG, "null argument");
+    if (h->multi || h->corner_active) return lio_fail(LIO_ERR_ARG, "lio_s2m_register_raw needs a plain single-device handle");
     if (lio_pc2_check_xyz(layout) != LIO_OK) return LIO_ERR_ARG;
-    if (!(leaf > 0.0f)) return lio_fail_ext(LIO_ERR_ARG, "leaf must be positive", hipSuccess);
-    if (ds_out && (ds_out_stride < 20 || (ds_out_stride & 3))) return lio_fail_ext(LIO_ERR_ARG, "output stride must be >= 20 and a multiple of 4", hipSuccess);
-    if (n_points && !data) return lio_fail_ext(LIO_ERR_ARG, "null cloud", hipSuccess);
-    if (n_points > 0x7fffffffull - 1024) return lio_fail_ext(LIO_ERR_CAPACITY, "cloud too large", hipSuccess);
+    if (!(leaf > 0.0f)) return lio_fail(LIO_ERR_ARG, "leaf must be positive");
+    if (ds_out && (ds_out_stride < 20 || (ds_out_stride & 3))) return lio_fail(LIO_ERR_ARG, "output stride must be >= 20 and a multiple of 4");
+    if (n_points && !data) return lio_fail(LIO_ERR_ARG, "null cloud");
+    if (n_points > 0x7fffffffull - 1024) return lio_fail(LIO_ERR_CAPACITY, "cloud too large");
     if (n_ds) *n_ds = 0;
     int rc = check_device(h->cfg.device_id);
     if (rc != LIO_OK) return rc;
@@ -1120,7 +1068,7 @@ extern "C" int lio_s2m_register_raw(lio_s2m_handle* h, const void* data, size_t 
     }
     int no = 0;
     // (the filter's first host wait -- the bounding box -- also covers the H2D copy: the caller's blob is free again)
-    rc = voxel_grid_device<LioKeep>(w->xyzi.as<float4>(), (int)n, leaf, w->ds, &no, s, w->vws, false, nullptr);
+    rc = voxel_grid_device<LioDevBytes>(w->xyzi.as<float4>(), (int)n, leaf, w->ds, &no, s, w->vws, false, nullptr);
     if (rc < 0) return rc;                               // (rc == 1: PCL would pass the cloud through -- and so did we)
     if (n == 0) HIPCHK(w->ds.alloc(sizeof(float4)));
     // the filter's last kernels (centroids) may still be in flight: the registration on the handle's stream waits for them
@@ -1133,4 +1081,4 @@ extern "C" int lio_s2m_register_raw(lio_s2m_handle* h, const void* data, size_t 
     if (ds_out) { const int rc2 = copy_out(w->ds.as<float4>(), no, ds_out, ds_out_stride, h->stream); if (rc2 < 0) return rc2; }
     if (n_ds) *n_ds = (size_t)no;
     return rr;
-}
+} LIO_CATCH

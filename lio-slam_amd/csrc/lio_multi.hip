@@ -30,32 +30,13 @@
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
+#include <memory>
 #include <vector>
 
 #include "lio_handle.h"
 #include "lio_multi.h"
 
 #define LIO_MULTI_HALO 16      // cells of map a device holds beyond its slab: workgroups up to ~30 m long stay whole (k_shard_cull)
-
-struct LioMulti {
-    std::vector<lio_s2m_handle*> dev;
-    std::vector<double*> d_part;                      // per child: its partial sums [n_scans][LIO_SUMS]
-    std::vector<double*> d_gather;                    // per child: [2 parities][n_dev slots][cap_scans][LIO_SUMS]
-    std::vector<double*> h_part;                      // (host exchange only) pinned partial sums per child
-    double* h_tot = nullptr;                          // (host exchange only)
-    std::vector<double*> d_tot;                       // (host exchange only)
-    std::vector<hipEvent_t> ev_pub;                   // [n_dev][LIO_MAX_ITERS]
-    hipStream_t join_stream = nullptr;                // four devices and more: ONE stream waits for all publish events of an iteration
-    std::vector<hipEvent_t> ev_all;                   // [LIO_MAX_ITERS] ... and records "everybody has published" for every device to wait on
-    size_t cap_scans = 0;
-    std::vector<std::vector<int>> shard_idx;          // per child: caller's map index of every point of its shard
-    std::vector<unsigned char> gather;                // host staging of one shard's records
-    int n_scans = 0;
-    int exchange = 0;                                 // 0 = peer stores from a kernel, 1 = hipMemcpyPeerAsync, 2 = through the host (round 2)
-    bool peer_ok = true;
-    // diagnostics of the last run (lio_s2m_profile.multi_*)
-    int stream_syncs = 0, event_waits = 0, iterations = 0;
-};
 
 namespace {
 
@@ -76,26 +57,19 @@ __global__ void k_multi_publish(const double* __restrict__ part, int n_val, LioP
 static int lio_multi_reserve(lio_s2m_handle* h, size_t n_scans)
 {
     LioMulti* m = h->multi;
-    if (n_scans <= m->cap_scans) return LIO_OK;
+    if (n_scans <= m->slot_scans) return LIO_OK;
     const size_t nd = m->dev.size();
-    const size_t cap = n_scans + n_scans / 4 + 16, bytes = cap * LIO_SUMS * sizeof(double);
-    for (size_t c = 0; c < nd; ++c) {
-        HIPCHK(hipSetDevice(m->dev[c]->cfg.device_id));
-        HIPCHK(hipStreamSynchronize(m->dev[c]->stream));
-        if (m->d_part[c]) HIPCHK(hipFree(m->d_part[c]));
-        if (m->d_gather[c]) HIPCHK(hipFree(m->d_gather[c]));
-        if (m->d_tot[c]) HIPCHK(hipFree(m->d_tot[c]));
-        if (m->h_part[c]) HIPCHK(hipHostFree(m->h_part[c]));
-        m->d_part[c] = m->d_gather[c] = m->d_tot[c] = m->h_part[c] = nullptr;
-        HIPCHK(hipMalloc((void**)&m->d_part[c], bytes));
-        HIPCHK(hipMalloc((void**)&m->d_gather[c], 2 * nd * bytes));
-        HIPCHK(hipMalloc((void**)&m->d_tot[c], bytes));
-        if (m->exchange == 2) HIPCHK(hipHostMalloc((void**)&m->h_part[c], bytes, hipHostMallocPortable));
+    const size_t cap = n_scans + n_scans / 4 + 16, n_val = cap * LIO_SUMS;
+    for (auto& ch : m->dev) {
+        HIPCHK(hipSetDevice(ch->h->cfg.device_id));
+        HIPCHK(hipStreamSynchronize(ch->h->stream));
+        HIPCHK(ch->d_part.grow(n_val, 1.0, 0));
+        HIPCHK(ch->d_gather.grow(2 * nd * n_val, 1.0, 0));
+        HIPCHK(ch->d_tot.grow(n_val, 1.0, 0));
+        if (m->exchange == 2) HIPCHK(ch->h_part.grow(n_val, n_val, hipHostMallocPortable));
     }
-    if (m->h_tot) HIPCHK(hipHostFree(m->h_tot));
-    m->h_tot = nullptr;
-    if (m->exchange == 2) HIPCHK(hipHostMalloc((void**)&m->h_tot, bytes, hipHostMallocPortable));
-    m->cap_scans = cap;
+    if (m->exchange == 2) HIPCHK(m->h_tot.grow(n_val, n_val, hipHostMallocPortable));
+    m->slot_scans = cap;
     return LIO_OK;
 }
 
@@ -109,10 +83,11 @@ int lio_multi_create(const lio_s2m_config* cfg, lio_s2m_handle** out)
         if (cfg->device_ids[i] < 0 || cfg->device_ids[i] >= ndev) return lio_fail(LIO_ERR_ARG, "device_ids entry out of range");
     if (cfg->use_lds || cfg->kernel_variant > 1)
         return lio_fail(LIO_ERR_ARG, "the multi-device mode runs the default kernel only");
-    lio_s2m_handle* f = new lio_s2m_handle();
+    std::unique_ptr<lio_s2m_handle> f(new lio_s2m_handle());   // (releases whatever had been created if a step fails)
     f->cfg = *cfg;
     f->shard.axis = -1;
     LioMulti* m = f->multi = new LioMulti();
+    m->join_device = cfg->device_ids[0];
     const char* ex = getenv("LIO_MULTI_EXCHANGE");
     m->exchange = (ex && !strcmp(ex, "copy")) ? 1 : ((ex && !strcmp(ex, "host")) ? 2 : 0);
     for (int i = 0; i < cfg->n_devices; ++i) {
@@ -121,13 +96,11 @@ int lio_multi_create(const lio_s2m_config* cfg, lio_s2m_handle** out)
         cc.device_id = cfg->device_ids[i];
         cc.use_graph = 0;                        // the loop is driven iteration by iteration (one exchange each)
         cc.pipeline = 1;
-        lio_s2m_handle* ch = nullptr;
-        const int rc = lio_s2m_create(&cc, &ch);
-        if (rc != LIO_OK) { lio_multi_destroy(f); return rc; }
-        m->dev.push_back(ch);
-        m->d_part.push_back(nullptr); m->d_gather.push_back(nullptr); m->d_tot.push_back(nullptr); m->h_part.push_back(nullptr);
+        std::unique_ptr<LioMultiChild> ch(new LioMultiChild());
+        const int rc = lio_s2m_create(&cc, &ch->h);
+        if (rc != LIO_OK) return rc;
+        m->dev.push_back(std::move(ch));
     }
-    m->shard_idx.resize((size_t)cfg->n_devices);
     // peer access between every pair of DISTINCT devices (a repeated ordinal needs none: its pointers are local)
     for (int a = 0; a < cfg->n_devices && m->exchange == 0; ++a)
         for (int b = 0; b < cfg->n_devices; ++b) {
@@ -141,52 +114,46 @@ int lio_multi_create(const lio_s2m_config* cfg, lio_s2m_handle** out)
             (void)hipGetLastError();
         }
     if (!m->peer_ok && m->exchange == 0) m->exchange = 1;
-    m->ev_pub.assign((size_t)cfg->n_devices * LIO_MAX_ITERS, nullptr);
-    for (int c = 0; c < cfg->n_devices; ++c) {
-        if (hipSetDevice(cfg->device_ids[c]) != hipSuccess) { lio_multi_destroy(f); return lio_fail(LIO_ERR_HIP, "hipSetDevice"); }
-        for (int i = 0; i < LIO_MAX_ITERS; ++i)
-            if (hipEventCreateWithFlags(&m->ev_pub[(size_t)c * LIO_MAX_ITERS + i], hipEventDisableTiming) != hipSuccess) {
-                lio_multi_destroy(f);
-                return lio_fail(LIO_ERR_HIP, "hipEventCreate");
-            }
+    for (auto& ch : m->dev) {
+        if (hipSetDevice(ch->h->cfg.device_id) != hipSuccess) return lio_fail(LIO_ERR_HIP, "hipSetDevice");
+        for (hipEvent_t& e : ch->ev_pub)
+            if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return lio_fail(LIO_ERR_HIP, "hipEventCreate");
     }
     if (cfg->n_devices >= 4) {
         // N devices waiting for N-1 events each is N(N-1) host calls per iteration (56 at N = 8); through one joining stream
         // it is N + 1 + N (17): the host thread that enqueues everything is the scarce resource of this mode
-        bool ok = hipSetDevice(cfg->device_ids[0]) == hipSuccess && hipStreamCreateWithFlags(&m->join_stream, hipStreamNonBlocking) == hipSuccess;
-        m->ev_all.assign(LIO_MAX_ITERS, nullptr);
-        for (int i = 0; i < LIO_MAX_ITERS && ok; ++i) ok = hipEventCreateWithFlags(&m->ev_all[(size_t)i], hipEventDisableTiming) == hipSuccess;
-        if (!ok) { lio_multi_destroy(f); return lio_fail(LIO_ERR_HIP, "hipStreamCreate / hipEventCreate (join stream)"); }
+        bool ok = hipSetDevice(m->join_device) == hipSuccess && hipStreamCreateWithFlags(&m->join_stream, hipStreamNonBlocking) == hipSuccess;
+        for (int i = 0; i < LIO_MAX_ITERS && ok; ++i) ok = hipEventCreateWithFlags(&m->ev_all[i], hipEventDisableTiming) == hipSuccess;
+        if (!ok) return lio_fail(LIO_ERR_HIP, "hipStreamCreate / hipEventCreate (join stream)");
     }
-    *out = f;
+    *out = f.release();
     return LIO_OK;
 }
 
 void lio_multi_destroy(lio_s2m_handle* h)
 {
-    LioMulti* m = h->multi;
-    for (size_t c = 0; c < m->dev.size(); ++c) {
-        (void)hipSetDevice(m->dev[c]->cfg.device_id);
-        (void)hipStreamSynchronize(m->dev[c]->stream);
+    for (auto& ch : h->multi->dev) {
+        (void)hipSetDevice(ch->h->cfg.device_id);
+        (void)hipStreamSynchronize(ch->h->stream);
     }
-    for (size_t c = 0; c < m->dev.size(); ++c) {
-        (void)hipSetDevice(m->dev[c]->cfg.device_id);
-        if (m->d_part[c]) (void)hipFree(m->d_part[c]);
-        if (m->d_gather[c]) (void)hipFree(m->d_gather[c]);
-        if (m->d_tot[c]) (void)hipFree(m->d_tot[c]);
-        if (m->h_part[c]) (void)hipHostFree(m->h_part[c]);
-        for (int i = 0; i < LIO_MAX_ITERS; ++i) {
-            const size_t k = c * LIO_MAX_ITERS + (size_t)i;
-            if (k < m->ev_pub.size() && m->ev_pub[k]) (void)hipEventDestroy(m->ev_pub[k]);
-        }
-        lio_s2m_destroy(m->dev[c]);
-    }
-    if (m->h_tot) (void)hipHostFree(m->h_tot);
-    if (!m->dev.empty()) (void)hipSetDevice(h->cfg.device_ids[0]);
-    for (hipEvent_t e : m->ev_all) if (e) (void)hipEventDestroy(e);
-    if (m->join_stream) (void)hipStreamDestroy(m->join_stream);
-    delete m;
     delete h;
+}
+
+LioMultiChild::~LioMultiChild()
+{
+    for (hipEvent_t e : ev_pub) if (e) (void)hipEventDestroy(e);
+    lio_s2m_destroy(h);
+}
+
+LioMulti::~LioMulti()
+{
+    for (auto& ch : dev) {                        // (a child's buffers are freed with its device current)
+        (void)hipSetDevice(ch->h->cfg.device_id);
+        ch.reset();
+    }
+    if (!dev.empty()) (void)hipSetDevice(join_device);
+    for (hipEvent_t e : ev_all) if (e) (void)hipEventDestroy(e);
+    if (join_stream) (void)hipStreamDestroy(join_stream);
 }
 
 // Multi-device set_map: slab plan on the host (the same arithmetic as lio-slam_amd/multigpu.py plan_shards and as the
@@ -241,13 +208,13 @@ int lio_multi_set_map(lio_s2m_handle* h, const void* pts, size_t n, size_t strid
     }
     for (int r = 0; r < world; ++r) {
         const int lo = bounds[(size_t)r], hi = bounds[(size_t)r + 1];
-        std::vector<int>& idx = m->shard_idx[(size_t)r];
+        std::vector<int>& idx = m->dev[(size_t)r]->shard_idx;
         idx.clear();
         for (size_t i = 0; i < n; ++i)
             if (pc[i] >= lo - LIO_MULTI_HALO && pc[i] < hi + LIO_MULTI_HALO) idx.push_back((int)i);
         m->gather.resize((idx.size() ? idx.size() : 1) * stride);
         for (size_t k = 0; k < idx.size(); ++k) memcpy(m->gather.data() + k * stride, src + (size_t)idx[k] * stride, stride);
-        lio_s2m_handle* ch = m->dev[(size_t)r];
+        lio_s2m_handle* ch = m->dev[(size_t)r]->h;
         int rc = lio_s2m_set_map(ch, m->gather.data(), idx.size(), stride);
         if (rc == LIO_OK) rc = lio_s2m_set_global_grid(ch, origin, dims);
         if (rc == LIO_OK) rc = lio_s2m_set_shard_plan(ch, axis, world, r, bounds.data(), LIO_MULTI_HALO);
@@ -255,7 +222,7 @@ int lio_multi_set_map(lio_s2m_handle* h, const void* pts, size_t n, size_t strid
     }
     h->has_map = true;
     h->n_map = n;
-    h->prof = m->dev[0]->prof;
+    h->prof = m->dev[0]->h->prof;
     h->prof.n_map = (int64_t)n;
     return LIO_OK;
 }
@@ -265,7 +232,8 @@ int lio_multi_upload(lio_s2m_handle* h, int32_t n_scans, const void* const* scan
     // Every device holds every scan: which device owns a point follows the pose, iteration by iteration.  All H2D
     // copies are in flight together (each device has its own PCIe link), one wait per device below.
     LioMulti* m = h->multi;
-    for (lio_s2m_handle* ch : m->dev) {
+    for (auto& c : m->dev) {
+        lio_s2m_handle* ch = c->h;
         ch->defer_sync = true;
         ch->xyz_off = h->xyz_off;
         const int rc = lio_s2m_batch_upload(ch, n_scans, scans, n_pts, stride);
@@ -273,7 +241,7 @@ int lio_multi_upload(lio_s2m_handle* h, int32_t n_scans, const void* const* scan
         if (rc != LIO_OK) return rc;
     }
     h->xyz_off = 0;
-    for (lio_s2m_handle* ch : m->dev) { const int rc = lio_s2m_batch_sync(ch); if (rc != LIO_OK) return rc; }
+    for (auto& c : m->dev) { const int rc = lio_s2m_batch_sync(c->h); if (rc != LIO_OK) return rc; }
     m->n_scans = n_scans;
     h->n_scans = n_scans;
     return lio_multi_reserve(h, (size_t)n_scans);
@@ -281,14 +249,14 @@ int lio_multi_upload(lio_s2m_handle* h, int32_t n_scans, const void* const* scan
 
 int lio_multi_set_poses(lio_s2m_handle* h, const float* poses)
 {
-    for (lio_s2m_handle* ch : h->multi->dev) { const int rc = lio_s2m_batch_set_poses(ch, poses); if (rc != LIO_OK) return rc; }
+    for (auto& c : h->multi->dev) { const int rc = lio_s2m_batch_set_poses(c->h, poses); if (rc != LIO_OK) return rc; }
     h->poses_set = true;
     return LIO_OK;
 }
 
 int lio_multi_set_degeneracy(lio_s2m_handle* h, int32_t scan, const float matP[36], int32_t is_degenerate)
 {
-    for (lio_s2m_handle* ch : h->multi->dev) { const int rc = lio_s2m_set_degeneracy(ch, scan, matP, is_degenerate); if (rc != LIO_OK) return rc; }
+    for (auto& c : h->multi->dev) { const int rc = lio_s2m_set_degeneracy(c->h, scan, matP, is_degenerate); if (rc != LIO_OK) return rc; }
     return LIO_OK;
 }
 
@@ -297,21 +265,21 @@ int lio_multi_set_degeneracy(lio_s2m_handle* h, int32_t scan, const float matP[3
 static int lio_multi_exchange_host(LioMulti* m, size_t n_val)
 {
     const size_t bytes = n_val * sizeof(double);
-    for (size_t c = 0; c < m->dev.size(); ++c)
-        HIPCHK(hipMemcpyAsync(m->h_part[c], m->d_part[c], bytes, hipMemcpyDeviceToHost, m->dev[c]->stream));
-    for (lio_s2m_handle* ch : m->dev) {
-        HIPCHK(hipSetDevice(ch->cfg.device_id));
-        HIPCHK(hipStreamSynchronize(ch->stream));
+    for (auto& c : m->dev)
+        HIPCHK(hipMemcpyAsync(c->h_part, c->d_part, bytes, hipMemcpyDeviceToHost, c->h->stream));
+    for (auto& c : m->dev) {
+        HIPCHK(hipSetDevice(c->h->cfg.device_id));
+        HIPCHK(hipStreamSynchronize(c->h->stream));
         m->stream_syncs++;
     }
     for (size_t k = 0; k < n_val; ++k) {
-        double v = m->h_part[0][k];
-        for (size_t c = 1; c < m->dev.size(); ++c) v += m->h_part[c][k];
+        double v = m->dev[0]->h_part[k];
+        for (size_t c = 1; c < m->dev.size(); ++c) v += m->dev[c]->h_part[k];
         m->h_tot[k] = v;
     }
-    for (size_t c = 0; c < m->dev.size(); ++c) {
-        HIPCHK(hipSetDevice(m->dev[c]->cfg.device_id));
-        HIPCHK(hipMemcpyAsync(m->d_tot[c], m->h_tot, bytes, hipMemcpyHostToDevice, m->dev[c]->stream));
+    for (auto& c : m->dev) {
+        HIPCHK(hipSetDevice(c->h->cfg.device_id));
+        HIPCHK(hipMemcpyAsync(c->d_tot, m->h_tot, bytes, hipMemcpyHostToDevice, c->h->stream));
     }
     return LIO_OK;
 }
@@ -324,9 +292,9 @@ int lio_multi_run(lio_s2m_handle* h)
     if (m->n_scans < 1 || !h->poses_set) return lio_fail(LIO_ERR_ARG, "batch_upload and batch_set_poses first");
     const size_t nd = m->dev.size();
     const int n_val = m->n_scans * LIO_SUMS;
-    const size_t slot = m->cap_scans * LIO_SUMS;                            // doubles per slot
+    const size_t slot = m->slot_scans * LIO_SUMS;                            // doubles per slot
     m->stream_syncs = m->event_waits = m->iterations = 0;
-    for (lio_s2m_handle* ch : m->dev) { const int rc = lio_s2m_batch_begin(ch); if (rc != LIO_OK) return rc; }
+    for (auto& c : m->dev) { const int rc = lio_s2m_batch_begin(c->h); if (rc != LIO_OK) return rc; }
     int look = h->cfg.lookahead;
     if (look < 0) look = 2;
     if (m->exchange == 2) look = 0;
@@ -336,7 +304,7 @@ int lio_multi_run(lio_s2m_handle* h)
         const int chk = it - 1 - look;
         if (chk >= 0) {
             int32_t active = 0;
-            const int rc = lio_s2m_batch_poll_active(m->dev[0], chk, &active);   // (an EVENT wait, not a stream synchronisation)
+            const int rc = lio_s2m_batch_poll_active(m->dev[0]->h, chk, &active);   // (an EVENT wait, not a stream synchronisation)
             m->event_waits++;
             if (rc != LIO_OK) return rc;
             if (active == 0) break;
@@ -344,40 +312,40 @@ int lio_multi_run(lio_s2m_handle* h)
         const size_t par = (size_t)(it & 1) * nd * slot;
         // association + publish on every device
         for (size_t c = 0; c < nd; ++c) {
-            lio_s2m_handle* ch = m->dev[c];
-            const int rc = lio_s2m_batch_iter_partial(ch, m->d_part[c]);    // (sets the device)
+            lio_s2m_handle* ch = m->dev[c]->h;
+            const int rc = lio_s2m_batch_iter_partial(ch, m->dev[c]->d_part);    // (sets the device)
             if (rc != LIO_OK) return rc;
             if (m->exchange == 0) {
                 LioPeerPtrs dst;
-                for (size_t d = 0; d < 8; ++d) dst.p[d] = d < nd ? m->d_gather[d] + par + c * slot : nullptr;
-                hipLaunchKernelGGL(k_multi_publish, dim3((n_val + 255) / 256), dim3(256), 0, ch->stream, m->d_part[c], n_val, dst, (int)nd);
+                for (size_t d = 0; d < 8; ++d) dst.p[d] = d < nd ? m->dev[d]->d_gather + par + c * slot : nullptr;
+                hipLaunchKernelGGL(k_multi_publish, dim3((n_val + 255) / 256), dim3(256), 0, ch->stream, m->dev[c]->d_part, n_val, dst, (int)nd);
             } else if (m->exchange == 1) {
                 for (size_t d = 0; d < nd; ++d)
-                    HIPCHK(hipMemcpyPeerAsync(m->d_gather[d] + par + c * slot, m->dev[d]->cfg.device_id, m->d_part[c], ch->cfg.device_id,
+                    HIPCHK(hipMemcpyPeerAsync(m->dev[d]->d_gather + par + c * slot, m->dev[d]->h->cfg.device_id, m->dev[c]->d_part, ch->cfg.device_id,
                                               (size_t)n_val * sizeof(double), ch->stream));
             }
-            if (m->exchange != 2) HIPCHK(hipEventRecord(m->ev_pub[c * LIO_MAX_ITERS + (size_t)it], ch->stream));
+            if (m->exchange != 2) HIPCHK(hipEventRecord(m->dev[c]->ev_pub[it], ch->stream));
         }
         if (m->exchange == 2) { const int rc = lio_multi_exchange_host(m, (size_t)n_val); if (rc != LIO_OK) return rc; }
         // join + solve on every device
         const bool via_join = m->exchange != 2 && m->join_stream != nullptr;
         if (via_join) {
             HIPCHK(hipSetDevice(h->cfg.device_ids[0]));
-            for (size_t c = 0; c < nd; ++c) HIPCHK(hipStreamWaitEvent(m->join_stream, m->ev_pub[c * LIO_MAX_ITERS + (size_t)it], 0));
+            for (size_t c = 0; c < nd; ++c) HIPCHK(hipStreamWaitEvent(m->join_stream, m->dev[c]->ev_pub[it], 0));
             HIPCHK(hipEventRecord(m->ev_all[(size_t)it], m->join_stream));
         }
         for (size_t p = 0; p < nd; ++p) {
-            lio_s2m_handle* ch = m->dev[p];
+            lio_s2m_handle* ch = m->dev[p]->h;
             HIPCHK(hipSetDevice(ch->cfg.device_id));
             if (via_join) {
                 HIPCHK(hipStreamWaitEvent(ch->stream, m->ev_all[(size_t)it], 0));
             } else if (m->exchange != 2) {
                 for (size_t c = 0; c < nd; ++c)
-                    if (c != p) HIPCHK(hipStreamWaitEvent(ch->stream, m->ev_pub[c * LIO_MAX_ITERS + (size_t)it], 0));
+                    if (c != p) HIPCHK(hipStreamWaitEvent(ch->stream, m->dev[c]->ev_pub[it], 0));
             }
             // the slots are added in device order inside the solving kernel (bitwise reproducible, identical on every device)
-            const int rc = m->exchange != 2 ? lio_s2m_iter_apply_slots(ch, m->d_gather[p] + par, slot, (int)nd)
-                                            : lio_s2m_batch_iter_apply(ch, m->d_tot[p]);
+            const int rc = m->exchange != 2 ? lio_s2m_iter_apply_slots(ch, m->dev[p]->d_gather + par, slot, (int)nd)
+                                            : lio_s2m_batch_iter_apply(ch, m->dev[p]->d_tot);
             if (rc != LIO_OK) return rc;
         }
         m->iterations = it + 1;
@@ -392,7 +360,7 @@ int lio_multi_run(lio_s2m_handle* h)
 
 int lio_multi_sync(lio_s2m_handle* h)
 {
-    for (lio_s2m_handle* ch : h->multi->dev) { const int rc = lio_s2m_batch_sync(ch); if (rc != LIO_OK) return rc; }
+    for (auto& c : h->multi->dev) { const int rc = lio_s2m_batch_sync(c->h); if (rc != LIO_OK) return rc; }
     return LIO_OK;
 }
 
@@ -404,9 +372,9 @@ int lio_multi_results(lio_s2m_handle* h, float* poses, lio_s2m_result* results)
     LioMulti* m = h->multi;
     int rc = LIO_OK;
     for (size_t c = m->dev.size(); c-- > 0 && rc == LIO_OK;)
-        rc = lio_s2m_batch_results(m->dev[c], c == 0 ? poses : nullptr, c == 0 ? results : nullptr);
+        rc = lio_s2m_batch_results(m->dev[c]->h, c == 0 ? poses : nullptr, c == 0 ? results : nullptr);
     const int mi = h->prof.multi_iterations, ms = h->prof.multi_stream_syncs, me = h->prof.multi_event_waits, mx = h->prof.multi_exchange;
-    h->prof = m->dev[0]->prof;
+    h->prof = m->dev[0]->h->prof;
     h->prof.multi_iterations = mi; h->prof.multi_stream_syncs = ms; h->prof.multi_event_waits = me; h->prof.multi_exchange = mx;
     return rc;
 }
@@ -416,7 +384,7 @@ int lio_multi_get_correspondences(lio_s2m_handle* h, int32_t scan, uint8_t* flag
     // a point's record lives on the device that owned it in that iteration; neighbour indices come back in the
     // caller's map order (a shard numbers its points locally)
     LioMulti* m = h->multi;
-    const size_t n = (size_t)m->dev[0]->h_state[scan].n_pts;
+    const size_t n = (size_t)m->dev[0]->h->h_state[scan].n_pts;
     std::vector<uint8_t> f(n);
     std::vector<float> cf(n * 4);
     std::vector<int32_t> nn(n * 5);
@@ -424,9 +392,9 @@ int lio_multi_get_correspondences(lio_s2m_handle* h, int32_t scan, uint8_t* flag
     if (coeff4) memset(coeff4, 0, n * 4 * sizeof(float));
     if (nn_idx5) for (size_t i = 0; i < n * 5; ++i) nn_idx5[i] = -1;
     for (size_t c = 0; c < m->dev.size(); ++c) {
-        const int rc = lio_s2m_get_correspondences(m->dev[c], scan, f.data(), cf.data(), nn.data());
+        const int rc = lio_s2m_get_correspondences(m->dev[c]->h, scan, f.data(), cf.data(), nn.data());
         if (rc != LIO_OK) return rc;
-        const std::vector<int>& idx = m->shard_idx[c];
+        const std::vector<int>& idx = m->dev[c]->shard_idx;
         for (size_t i = 0; i < n; ++i) {
             if (nn[i * 5] < 0) continue;                                // not processed (not owned / gate failed) on this device
             if (flag) flag[i] = f[i];

@@ -14,14 +14,6 @@
 
 #define LIO_DEV __device__ __forceinline__
 
-int lio_fail_ext(int code, const char* what, hipError_t e);   // liogpu_api.hip
-
-#define HIPCHK(expr)                                                              \
-    do {                                                                          \
-        hipError_t _e = (expr);                                                   \
-        if (_e != hipSuccess) return lio_fail_ext(LIO_ERR_HIP, #expr, _e);        \
-    } while (0)
-
 struct LioDeskewParams {
     const unsigned char* pts;   // PointXYZIRT records, IP:4-15
     size_t stride;
@@ -413,28 +405,27 @@ extern "C" void lio_deskew_default_config(lio_deskew_config* c)
     c->device_id = 0;
 }
 
-typedef LioTemp DevBuf;      // temporaries come from the recycling pool (lio_pool.h)
 
 static const lio_pc2_layout kXyzirtLayout = { 32, 0, 16, 20, LIO_PC2_UINT16, 24, LIO_PC2_TIME_F32_SECONDS, 0 };
 
 static int lio_check_layout(const lio_pc2_layout* L, bool need_ring)
 {
-    if (!L) return lio_fail_ext(LIO_ERR_ARG, "null layout", hipSuccess);
+    if (!L) return lio_fail(LIO_ERR_ARG, "null layout");
     // offsets come off the wire: every bound is written without an addition that could wrap in 32 bits
     // (`off_x + 12 > st` passes for off_x = 0xfffffff4 -- round-2 advisor finding)
     const uint32_t st = L->point_step;
     if (st < 12 || (L->off_x & 3) || L->off_x > st - 12)
-        return lio_fail_ext(LIO_ERR_ARG, "x, y, z must be three consecutive FLOAT32 fields inside the record", hipSuccess);
+        return lio_fail(LIO_ERR_ARG, "x, y, z must be three consecutive FLOAT32 fields inside the record");
     if (L->off_intensity >= 0 && ((L->off_intensity & 3) || (uint32_t)L->off_intensity > st - 4))
-        return lio_fail_ext(LIO_ERR_ARG, "intensity must be an aligned FLOAT32 field inside the record", hipSuccess);
+        return lio_fail(LIO_ERR_ARG, "intensity must be an aligned FLOAT32 field inside the record");
     if (need_ring) {
         const uint32_t rs = L->ring_type == LIO_PC2_UINT8 ? 1 : (L->ring_type == LIO_PC2_UINT16 ? 2 : (L->ring_type == LIO_PC2_INT32 ? 4 : 0));
         if (!rs || L->off_ring < 0 || ((uint32_t)L->off_ring % rs) || (uint32_t)L->off_ring > st - rs)
-            return lio_fail_ext(LIO_ERR_ARG, "ring must be an aligned UINT8 / UINT16 / INT32 field inside the record (IP:313-329)", hipSuccess);
+            return lio_fail(LIO_ERR_ARG, "ring must be an aligned UINT8 / UINT16 / INT32 field inside the record (IP:313-329)");
         if (L->off_time >= 0) {
             const uint32_t ts = L->time_type == LIO_PC2_TIME_F64_STAMP ? 8 : 4;
             if (L->time_type < 0 || L->time_type > 3 || (L->off_time & 3) || st < ts || (uint32_t)L->off_time > st - ts)
-                return lio_fail_ext(LIO_ERR_ARG, "time field outside the record or of an unknown type", hipSuccess);
+                return lio_fail(LIO_ERR_ARG, "time field outside the record or of an unknown type");
         }
     }
     return LIO_OK;
@@ -458,13 +449,13 @@ extern "C" int lio_deskew(const lio_deskew_config* cfg, const void* pts, size_t 
                           const double* imuTime, const double* imuRotX, const double* imuRotY,
                           const double* imuRotZ, int32_t imuPointerCur,
                           void* out, size_t out_stride, size_t* n_out)
-{
+try {
     if (stride < 28 || (stride & 3))
-        return lio_fail_ext(LIO_ERR_ARG, "PointXYZIRT stride must be >= 28, output stride >= 20, multiples of 4", hipSuccess);
+        return lio_fail(LIO_ERR_ARG, "PointXYZIRT stride must be >= 28, output stride >= 20, multiples of 4");
     lio_pc2_layout L = kXyzirtLayout;
     L.point_step = (uint32_t)stride;
     return lio_deskew_impl(cfg, pts, n, L, time_scan_cur, imuTime, imuRotX, imuRotY, imuRotZ, imuPointerCur, out, out_stride, n_out);
-}
+} LIO_CATCH
 
 // projectPointCloud IP:577-615 straight from the `data` blob of the incoming sensor_msgs/PointCloud2: replaces
 // pcl::moveFromROSMsg and the per-sensor conversion loops of cachePointCloud IP:226-285 as well.
@@ -473,7 +464,7 @@ extern "C" int lio_deskew_pc2(const lio_deskew_config* cfg, const void* data, si
                               const double* imuTime, const double* imuRotX, const double* imuRotY,
                               const double* imuRotZ, int32_t imuPointerCur,
                               void* out, size_t out_stride, size_t* n_out)
-{
+try {
     const int rc = lio_check_layout(layout, true);
     if (rc != LIO_OK) return rc;
     lio_deskew_config c2;
@@ -486,7 +477,7 @@ extern "C" int lio_deskew_pc2(const lio_deskew_config* cfg, const void* data, si
                                   imuPointerCur, out, out_stride, n_out);
     if (pinned) (void)hipHostUnregister(const_cast<void*>(data));
     return r;
-}
+} LIO_CATCH
 
 static int lio_deskew_impl(const lio_deskew_config* cfg, const void* pts, size_t n, const lio_pc2_layout& L,
                            double time_scan_cur,
@@ -495,27 +486,27 @@ static int lio_deskew_impl(const lio_deskew_config* cfg, const void* pts, size_t
                            void* out, size_t out_stride, size_t* n_out)
 {
     const size_t stride = L.point_step;
-    if (!cfg || !n_out || (n && (!pts || !out))) return lio_fail_ext(LIO_ERR_ARG, "null argument", hipSuccess);
+    if (!cfg || !n_out || (n && (!pts || !out))) return lio_fail(LIO_ERR_ARG, "null argument");
     if (out_stride < 20 || (out_stride & 3))
-        return lio_fail_ext(LIO_ERR_ARG, "PointXYZIRT stride must be >= 28, output stride >= 20, multiples of 4", hipSuccess);
+        return lio_fail(LIO_ERR_ARG, "PointXYZIRT stride must be >= 28, output stride >= 20, multiples of 4");
     if (cfg->downsampleRate < 1 || cfg->point_filter_num < 1)
-        return lio_fail_ext(LIO_ERR_ARG, "downsampleRate and point_filter_num must be >= 1", hipSuccess);
-    if (n > 0x7fffffffull - 1024) return lio_fail_ext(LIO_ERR_CAPACITY, "cloud too large", hipSuccess);
+        return lio_fail(LIO_ERR_ARG, "downsampleRate and point_filter_num must be >= 1");
+    if (n > 0x7fffffffull - 1024) return lio_fail(LIO_ERR_CAPACITY, "cloud too large");
     const bool imu_available = imuPointerCur > 0;                        // IP:414-417
     const bool do_deskew = !(cfg->deskew_flag == -1 || !imu_available);  // IP:547
     if (do_deskew && (!imuTime || !imuRotX || !imuRotY || !imuRotZ || imuPointerCur >= 2000))
-        return lio_fail_ext(LIO_ERR_ARG, "IMU tables missing or imuPointerCur >= 2000 (IP:62)", hipSuccess);
+        return lio_fail(LIO_ERR_ARG, "IMU tables missing or imuPointerCur >= 2000 (IP:62)");
     *n_out = 0;
     if (n == 0) return LIO_OK;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return lio_fail_ext(LIO_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU fallback)", hipSuccess);
+        return lio_fail(LIO_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU fallback)");
     HIPCHK(hipSetDevice(cfg->device_id));
     (void)hipGetLastError();
 
     const int nb = (int)((n + 255) / 256);
     const int nt = do_deskew ? imuPointerCur + 1 : 0;
-    DevBuf d_pts, d_keep, d_cnt, d_misc, d_imu, d_out;
+    LioTemp d_pts, d_keep, d_cnt, d_misc, d_imu, d_out;
     HIPCHK(d_pts.alloc(n * stride));
     HIPCHK(d_keep.alloc(n));
     HIPCHK(d_cnt.alloc(sizeof(int) * (size_t)nb));
@@ -562,16 +553,16 @@ static int lio_deskew_impl(const lio_deskew_config* cfg, const void* pts, size_t
 
 extern "C" int lio_curvature(int32_t device_id, const float* range, size_t n, float* curvature,
                              int32_t* neighbor_picked, int32_t* label)
-{
-    if (n && (!range || !curvature)) return lio_fail_ext(LIO_ERR_ARG, "null argument", hipSuccess);
-    if (n > 0x7fffffffull - 1024) return lio_fail_ext(LIO_ERR_CAPACITY, "array too large", hipSuccess);
+try {
+    if (n && (!range || !curvature)) return lio_fail(LIO_ERR_ARG, "null argument");
+    if (n > 0x7fffffffull - 1024) return lio_fail(LIO_ERR_CAPACITY, "array too large");
     if (n < 11) return LIO_OK;                                           // FE:84: empty loop
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return lio_fail_ext(LIO_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU fallback)", hipSuccess);
+        return lio_fail(LIO_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU fallback)");
     HIPCHK(hipSetDevice(device_id));
     (void)hipGetLastError();
-    DevBuf d_r, d_c, d_p, d_l;
+    LioTemp d_r, d_c, d_p, d_l;
     HIPCHK(d_r.alloc(n * 4)); HIPCHK(d_c.alloc(n * 4));
     if (neighbor_picked) HIPCHK(d_p.alloc(n * 4));
     if (label) HIPCHK(d_l.alloc(n * 4));
@@ -589,7 +580,7 @@ extern "C" int lio_curvature(int32_t device_id, const float* range, size_t n, fl
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
     return LIO_OK;
-}
+} LIO_CATCH
 
 void lio_launch_exclusive_scan(const int* in, int n, int* tile_sums, int* out, hipStream_t s);   // lio_kernels.hip
 int  lio_scan_tiles(int n_cells);
@@ -613,28 +604,28 @@ extern "C" int lio_range_image(const lio_range_image_config* cfg, const void* pt
                                void* out, size_t out_stride, size_t* n_out,
                                int32_t* startRingIndex, int32_t* endRingIndex,
                                int32_t* pointColInd, float* pointRange)
-{
+try {
     if (!cfg || !n_out || !startRingIndex || !endRingIndex || (n && !pts))
-        return lio_fail_ext(LIO_ERR_ARG, "null argument", hipSuccess);
+        return lio_fail(LIO_ERR_ARG, "null argument");
     if (stride < 28 || (stride & 3) || out_stride < 20 || (out_stride & 3))
-        return lio_fail_ext(LIO_ERR_ARG, "PointXYZIRT stride must be >= 28, output stride >= 20, multiples of 4", hipSuccess);
+        return lio_fail(LIO_ERR_ARG, "PointXYZIRT stride must be >= 28, output stride >= 20, multiples of 4");
     if (cfg->N_SCAN < 1 || cfg->N_SCAN > 1024 || cfg->Horizon_SCAN < 1 || cfg->Horizon_SCAN > 32767 || cfg->downsampleRate < 1)
-        return lio_fail_ext(LIO_ERR_ARG, "N_SCAN in 1..1024, Horizon_SCAN in 1..32767, downsampleRate >= 1", hipSuccess);
-    if (n > 0x7fffffffull - 1024) return lio_fail_ext(LIO_ERR_CAPACITY, "cloud too large", hipSuccess);
+        return lio_fail(LIO_ERR_ARG, "N_SCAN in 1..1024, Horizon_SCAN in 1..32767, downsampleRate >= 1");
+    if (n > 0x7fffffffull - 1024) return lio_fail(LIO_ERR_CAPACITY, "cloud too large");
     const bool imu_available = imuPointerCur > 0;
     const bool do_deskew = !(cfg->deskew_flag == -1 || !imu_available);
     if (do_deskew && (!imuTime || !imuRotX || !imuRotY || !imuRotZ || imuPointerCur >= 2000))
-        return lio_fail_ext(LIO_ERR_ARG, "IMU tables missing or imuPointerCur >= 2000 (IP:62)", hipSuccess);
+        return lio_fail(LIO_ERR_ARG, "IMU tables missing or imuPointerCur >= 2000 (IP:62)");
     const int ns = cfg->N_SCAN, H = cfg->Horizon_SCAN, cells = ns * H;
     *n_out = 0;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return lio_fail_ext(LIO_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU fallback)", hipSuccess);
+        return lio_fail(LIO_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU fallback)");
     HIPCHK(hipSetDevice(cfg->device_id));
     (void)hipGetLastError();
 
     const int nt = do_deskew ? imuPointerCur + 1 : 0;
-    DevBuf d_pts, d_first, d_flag, d_rank, d_tiles, d_misc, d_imu, d_out, d_col, d_range, d_rings;
+    LioTemp d_pts, d_first, d_flag, d_rank, d_tiles, d_misc, d_imu, d_out, d_col, d_range, d_rings;
     HIPCHK(d_pts.alloc((n ? n : 1) * stride));
     HIPCHK(d_first.alloc(sizeof(int) * (size_t)cells));
     HIPCHK(d_flag.alloc(sizeof(int) * (size_t)cells));
@@ -693,4 +684,4 @@ extern "C" int lio_range_image(const lio_range_image_config* cfg, const void* pt
         if (pointRange) HIPCHK(hipMemcpy(pointRange, d_range.p, sizeof(float) * (size_t)total, hipMemcpyDeviceToHost));
     }
     return LIO_OK;
-}
+} LIO_CATCH

@@ -5,30 +5,43 @@
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
+#include <algorithm>
 #include <chrono>
-#include <string>
+#include <exception>
+#include <memory>
+#include <mutex>
 #include <vector>
 
 #include "lio_handle.h"
 #include "lio_multi.h"
-#include "lio_pool.h"
-#include <mutex>
-#include <algorithm>
 
 
-static thread_local std::string g_last_error;
+static thread_local char g_last_error[512];   // (a fixed buffer: recording an allocation failure allocates nothing)
 
 int lio_fail(int code, const char* what, hipError_t e)
 {
-    char buf[512];
-    if (e != hipSuccess) snprintf(buf, sizeof(buf), "%s: %s", what, hipGetErrorString(e));
-    else snprintf(buf, sizeof(buf), "%s", what);
-    g_last_error = buf;
+    if (e != hipSuccess) snprintf(g_last_error, sizeof(g_last_error), "%s: %s", what, hipGetErrorString(e));
+    else snprintf(g_last_error, sizeof(g_last_error), "%s", what);
     return code;
 }
 
+// LIO_CATCH: what the library can throw is std::bad_alloc or std::length_error from a container or `new` -- out of
+// host memory or a size beyond it -- hence LIO_ERR_CAPACITY.
+int lio_fail_exception(void)
+{
+    char buf[256];
+    try {
+        throw;
+    } catch (const std::exception& e) {
+        snprintf(buf, sizeof(buf), "C++ exception: %s", e.what());
+    } catch (...) {
+        snprintf(buf, sizeof(buf), "C++ exception of an unknown type");
+    }
+    return lio_fail(LIO_ERR_CAPACITY, buf);
+}
+
 extern "C" int lio_version(void) { return LIO_VERSION; }
-extern "C" const char* lio_last_error(void) { return g_last_error.c_str(); }
+extern "C" const char* lio_last_error(void) { return g_last_error; }
 
 extern "C" void lio_s2m_default_config(lio_s2m_config* c)
 {
@@ -89,14 +102,13 @@ static int lio_s2m_init_resources(lio_s2m_handle* h)
         HIPCHK(hipEventCreate(&h->ev_end[i]));
         HIPCHK(hipEventCreateWithFlags(&h->ev_chk[i], hipEventDisableTiming));
     }
-    HIPCHK(hipHostMalloc((void**)&h->h_active, sizeof(int) * LIO_MAX_ITERS, hipHostMallocDefault));
+    HIPCHK(h->h_active.grow(LIO_MAX_ITERS, LIO_MAX_ITERS));
     HIPCHK(hipEventCreate(&h->ev_map[0]));
     HIPCHK(hipEventCreate(&h->ev_map[1]));
     HIPCHK(hipEventCreate(&h->ev_mapl[0]));
     HIPCHK(hipEventCreate(&h->ev_mapl[1]));
-    h->ev_ok = true;
-    HIPCHK(hipMalloc((void**)&h->d_bbox, 6 * sizeof(unsigned)));
-    HIPCHK(hipMalloc((void**)&h->d_active, sizeof(int)));
+    HIPCHK(h->d_bbox.grow(6, 1.0, 0));
+    HIPCHK(h->d_active.grow(1, 1.0, 0));
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, h->cfg.device_id) == hipSuccess) h->n_cu = prop.multiProcessorCount;
     (void)hipGetLastError();
@@ -104,7 +116,7 @@ static int lio_s2m_init_resources(lio_s2m_handle* h)
 }
 
 extern "C" int lio_s2m_create(const lio_s2m_config* cfg, lio_s2m_handle** out)
-{
+try {
     if (!cfg || !out) return lio_fail(LIO_ERR_ARG, "null argument");
     if (cfg->k != 5) return lio_fail(LIO_ERR_ARG, "only k = 5 is supported (MO:1631)");
     if (cfg->max_iters < 1 || cfg->max_iters > LIO_MAX_ITERS) return lio_fail(LIO_ERR_ARG, "max_iters out of range");
@@ -124,19 +136,17 @@ extern "C" int lio_s2m_create(const lio_s2m_config* cfg, lio_s2m_handle** out)
         return rc;
     }
     HIPCHK(hipSetDevice(cfg->device_id));
-    lio_s2m_handle* h = new lio_s2m_handle();
-    h->cfg = *cfg;
-    if (h->cfg.cell_size > 0.0f && h->cfg.cell_size < sqrtf(h->cfg.max_sq_dist) * 1.001f) {   // (before division by cell_div)
-        delete h;
+    if (cfg->cell_size > 0.0f && cfg->cell_size < sqrtf(cfg->max_sq_dist) * 1.001f)   // (before division by cell_div)
         return lio_fail(LIO_ERR_ARG, "cell_size must be >= sqrt(max_sq_dist)*1.001 for an exact 27-cell search");
-    }
-    lio_fill_consts(h);
+    std::unique_ptr<lio_s2m_handle> h(new lio_s2m_handle());   // (releases whatever had been created if a step fails)
+    h->cfg = *cfg;
+    lio_fill_consts(h.get());
     h->shard.axis = -1;
-    const int rc = lio_s2m_init_resources(h);
-    if (rc != LIO_OK) { lio_s2m_destroy(h); return rc; }    // (releases whatever had been created)
-    *out = h;
+    const int rc = lio_s2m_init_resources(h.get());
+    if (rc != LIO_OK) return rc;
+    *out = h.release();
     return LIO_OK;
-}
+} LIO_CATCH
 
 extern "C" void lio_s2m_destroy(lio_s2m_handle* h)
 {
@@ -144,35 +154,27 @@ extern "C" void lio_s2m_destroy(lio_s2m_handle* h)
     if (h->multi) { lio_multi_destroy(h); return; }
     (void)hipSetDevice(h->cfg.device_id);
     (void)hipStreamSynchronize(h->stream);
-    if (h->corner) { lio_s2m_destroy(h->corner); h->corner = nullptr; }
-    if (h->raw_ws) { lio_raw_ws_free(h->raw_ws); h->raw_ws = nullptr; }
-    void* ptrs[] = { h->d_mx, h->d_my, h->d_mz, h->d_map4, h->d_sorted, h->d_cell_of, h->d_cell_count,
-                     h->d_cell_start, h->d_tile_sums, h->d_bbox, h->d_stage, h->d_map_stage, h->d_sx, h->d_sy, h->d_sz,
-                     h->d_state, h->d_poses, h->d_blocks, h->d_partials, h->d_arrive, h->d_rec_flag,
-                     h->d_rec_coeff, h->d_rec_nn, h->d_active, h->d_tiles, h->d_prep_blocks, h->d_key_of,
-                     h->d_key_count, h->d_key_start, h->d_key_tiles, h->d_tmp_idx, h->d_perm, h->d_stamps, h->d_nbr_start, h->d_nbr_pts,
-                     h->d_nn_cache, h->d_summary, h->d_big_list, h->d_scan_bbox, h->d_block_box, h->d_blk_skip, h->d_gen, h->d_spec_sums, h->d_nbr_slot };
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    for (int i = 0; i < LIO_MAX_ITERS; ++i) {               // (a handle whose creation failed half-way holds nulls)
-        if (h->ev_beg[i]) (void)hipEventDestroy(h->ev_beg[i]);
-        if (h->ev_end[i]) (void)hipEventDestroy(h->ev_end[i]);
-        if (h->ev_chk[i]) (void)hipEventDestroy(h->ev_chk[i]);
-    }
-    if (h->h_active) (void)hipHostFree(h->h_active);
-    if (h->h_summary) (void)hipHostFree(h->h_summary);
-    if (h->h_scan_bbox) (void)hipHostFree(h->h_scan_bbox);
-    if (h->ev_map[0]) (void)hipEventDestroy(h->ev_map[0]);
-    if (h->ev_map[1]) (void)hipEventDestroy(h->ev_map[1]);
-    if (h->ev_mapl[0]) (void)hipEventDestroy(h->ev_mapl[0]);
-    if (h->ev_mapl[1]) (void)hipEventDestroy(h->ev_mapl[1]);
-    if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
-    if (h->graph) (void)hipGraphDestroy(h->graph);
-    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
 
-extern "C" int lio_s2m_set_stream(lio_s2m_handle* h, void* hip_stream)
+lio_s2m_handle::~lio_s2m_handle()
 {
+    delete multi;                                           // (a multi-device front holds nothing else)
+    lio_s2m_destroy(corner);
+    lio_raw_ws_free(raw_ws);
+    for (int i = 0; i < LIO_MAX_ITERS; ++i) {               // (a handle whose creation failed half-way holds nulls)
+        if (ev_beg[i]) (void)hipEventDestroy(ev_beg[i]);
+        if (ev_end[i]) (void)hipEventDestroy(ev_end[i]);
+        if (ev_chk[i]) (void)hipEventDestroy(ev_chk[i]);
+    }
+    for (hipEvent_t e : { ev_map[0], ev_map[1], ev_mapl[0], ev_mapl[1] }) if (e) (void)hipEventDestroy(e);
+    if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
+    if (graph) (void)hipGraphDestroy(graph);
+    if (own_stream && stream) (void)hipStreamDestroy(stream);
+}
+
+extern "C" int lio_s2m_set_stream(lio_s2m_handle* h, void* hip_stream)
+try {
     if (h && h->multi) return lio_fail(LIO_ERR_ARG, "not available on a multi-device handle (cfg.n_devices > 1 shards inside the library)");
     if (!h) return lio_fail(LIO_ERR_ARG, "null handle");
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -182,7 +184,7 @@ extern "C" int lio_s2m_set_stream(lio_s2m_handle* h, void* hip_stream)
     h->graph_dirty = true;
     if (h->corner) return lio_s2m_set_stream(h->corner, hip_stream);
     return LIO_OK;
-}
+} LIO_CATCH
 
 static float lio_ord2f(unsigned u)
 {
@@ -198,12 +200,12 @@ static const lio_s2m_handle* lio_map_of(const lio_s2m_handle* h) { return h->map
 static int lio_map_reserve(lio_s2m_handle* h, size_t n)
 {
     const size_t nn = n ? n : 1;
-    HIPCHK(lio_grow(&h->d_mx, &h->cap_mxyz[0], nn));
-    HIPCHK(lio_grow(&h->d_my, &h->cap_mxyz[1], nn));
-    HIPCHK(lio_grow(&h->d_mz, &h->cap_mxyz[2], nn));
-    HIPCHK(lio_grow(&h->d_map4, &h->cap_map4, nn));
-    HIPCHK(lio_grow(&h->d_sorted, &h->cap_sorted, nn));
-    HIPCHK(lio_grow(&h->d_cell_of, &h->cap_cell_of, nn));
+    HIPCHK(h->d_mx.grow(nn));
+    HIPCHK(h->d_my.grow(nn));
+    HIPCHK(h->d_mz.grow(nn));
+    HIPCHK(h->d_map4.grow(nn));
+    HIPCHK(h->d_sorted.grow(nn));
+    HIPCHK(h->d_cell_of.grow(nn));
     return LIO_OK;
 }
 
@@ -276,7 +278,7 @@ static int lio_map_finish(lio_s2m_handle* h, size_t n, std::chrono::steady_clock
         // read-back here; a map whose bounding box is still on the device (`box`) stays asynchronous and gets one table.
         n_tb = 1;
         if (!box && n > 0) {
-            HIPCHK(lio_grow(&h->d_cell_count, &h->cap_cell_count, (size_t)g.n_cells + 1));
+            HIPCHK(h->d_cell_count.grow((size_t)g.n_cells + 1));
             lio_launch_map_occupancy(g, h->d_mx, h->d_my, h->d_mz, (int)n, h->d_cell_count, h->stream);
             int occ = 0;
             HIPCHK(hipMemcpyAsync(&occ, h->d_cell_count + g.n_cells, sizeof(int), hipMemcpyDeviceToHost, h->stream));
@@ -330,12 +332,12 @@ static int lio_map_finish(lio_s2m_handle* h, size_t n, std::chrono::steady_clock
     }
     h->grid = g;
     const size_t len_a = (size_t)g.n_cells * xsub, reps = (size_t)((2 * g.k + 1) * (2 * g.k + 1)) + 9 * (size_t)n_tb;
-    HIPCHK(lio_grow(&h->d_cell_count, &h->cap_cell_count, (size_t)g.n_cells + len_a + len_b));   // (point counts + row bucket lengths of both tables)
-    HIPCHK(lio_grow(&h->d_cell_start, &h->cap_cell_start, (size_t)g.n_cells + 1));
-    HIPCHK(lio_grow(&h->d_nbr_start, &h->cap_nbr_start, len_a + len_b + 1));
-    HIPCHK(lio_grow(&h->d_nbr_pts, &h->cap_nbr_pts, nn * reps + LIO_ROW_ALIGN * ((size_t)g.ny * g.nz + rows_b) + 4 * LIO_ROW_ALIGN, 1.05));
-    HIPCHK(lio_grow(&h->d_tile_sums, &h->cap_tile_sums, 2 * ((size_t)lio_scan_tiles((int)(len_a + len_b)) + 1)));   // (64-bit pair sums)
-    HIPCHK(lio_grow(&h->d_nbr_slot, &h->cap_nbr_slot, nn * reps, 1.05));
+    HIPCHK(h->d_cell_count.grow((size_t)g.n_cells + len_a + len_b));   // (point counts + row bucket lengths of both tables)
+    HIPCHK(h->d_cell_start.grow((size_t)g.n_cells + 1));
+    HIPCHK(h->d_nbr_start.grow(len_a + len_b + 1));
+    HIPCHK(h->d_nbr_pts.grow(nn * reps + LIO_ROW_ALIGN * ((size_t)g.ny * g.nz + rows_b) + 4 * LIO_ROW_ALIGN, 1.05));
+    HIPCHK(h->d_tile_sums.grow(2 * ((size_t)lio_scan_tiles((int)(len_a + len_b)) + 1)));   // (64-bit pair sums)
+    HIPCHK(h->d_nbr_slot.grow(nn * reps, 1.05));
 
     HIPCHK(hipEventRecord(box ? h->ev_mapl[0] : h->ev_map[0], h->stream));
     if (n) {
@@ -373,7 +375,7 @@ static int lio_map_finish(lio_s2m_handle* h, size_t n, std::chrono::steady_clock
 }
 
 extern "C" int lio_s2m_set_map(lio_s2m_handle* h, const void* pts, size_t n, size_t stride)
-{
+try {
     if (!h) return lio_fail(LIO_ERR_ARG, "null handle");
     if (n > 0 && !pts) return lio_fail(LIO_ERR_ARG, "null map pointer");
     if (stride < 12 || (stride & 3)) return lio_fail(LIO_ERR_ARG, "stride_bytes must be >= 12 and a multiple of 4");
@@ -386,13 +388,13 @@ extern "C" int lio_s2m_set_map(lio_s2m_handle* h, const void* pts, size_t n, siz
     h->has_map = false;
     int rc = lio_map_reserve(h, n);
     if (rc != LIO_OK) return rc;
-    HIPCHK(lio_grow(&h->d_map_stage, &h->cap_map_stage, (n ? n : 1) * stride));
+    HIPCHK(h->d_map_stage.grow((n ? n : 1) * stride));
     if (n) {
         HIPCHK(hipMemcpyAsync(h->d_map_stage, pts, n * stride, hipMemcpyHostToDevice, h->stream));
         lio_launch_aos_to_soa(h->d_map_stage, stride, (int)n, h->d_mx, h->d_my, h->d_mz, h->d_map4, h->stream);
     }
     return lio_map_finish(h, n, t0);
-}
+} LIO_CATCH
 
 // Device-resident form used by lio_assemble_map: d_xyzi = float4 (x,y,z,intensity)[n] on h's device.
 int lio_s2m_set_map_device_xyzi(lio_s2m_handle* h, const float4* d_xyzi, size_t n)
@@ -432,27 +434,27 @@ hipStream_t lio_s2m_stream_of(lio_s2m_handle* h) { return h ? h->stream : nullpt
 bool lio_s2m_takes_device_map(const lio_s2m_handle* h) { return h && !h->multi && !h->map_src; }
 
 extern "C" int lio_s2m_set_global_grid(lio_s2m_handle* h, const float origin[3], const int32_t dims[3])
-{
+try {
     if (!h || !origin || !dims) return lio_fail(LIO_ERR_ARG, "null argument");
     for (int a = 0; a < 3; ++a) { h->gorigin[a] = origin[a]; h->gdims[a] = dims[a]; }
     h->has_global = true;
     return LIO_OK;
-}
+} LIO_CATCH
 
 extern "C" int lio_s2m_set_scan_shard(lio_s2m_handle* h, int32_t rank, int32_t world)
-{
+try {
     if (h && h->multi) return lio_fail(LIO_ERR_ARG, "not available on a multi-device handle (cfg.n_devices > 1 shards inside the library)");
     if (!h || world < 1 || rank < 0 || rank >= world) return lio_fail(LIO_ERR_ARG, "need 0 <= rank < world");
     h->block_rank = rank;
     h->block_world = world;
     return LIO_OK;
-}
+} LIO_CATCH
 
 // Streaming (the metric includes the per-scan H2D): a second handle searches THIS handle's resident
 // map, with its own stream and its own scan buffers, so that batch k+1 can be uploaded and tile-sorted while
 // batch k iterates.  The map owner must outlive the sharer; replacing the map needs both streams idle.
 extern "C" int lio_s2m_share_map(lio_s2m_handle* h, lio_s2m_handle* map_owner)
-{
+try {
     if (!h || h == map_owner) return lio_fail(LIO_ERR_ARG, "need two different handles");
     if (h->multi || (map_owner && map_owner->multi)) return lio_fail(LIO_ERR_ARG, "not available on a multi-device handle");
     if (map_owner && (map_owner->map_src || map_owner->cfg.device_id != h->cfg.device_id))
@@ -463,7 +465,7 @@ extern "C" int lio_s2m_share_map(lio_s2m_handle* h, lio_s2m_handle* map_owner)
     h->map_epoch = map_owner ? map_owner->map_epoch : 0;
     h->graph_dirty = true;
     return LIO_OK;
-}
+} LIO_CATCH
 
 extern "C" void* lio_host_alloc(size_t bytes)
 {
@@ -486,28 +488,28 @@ extern "C" void lio_device_free(int32_t device_id, void* p)
     if (p && hipSetDevice(device_id) == hipSuccess) (void)hipFree(p);
 }
 extern "C" int lio_device_upload(int32_t device_id, void* dst, const void* src, size_t bytes)
-{
+try {
     if (!dst || (!src && bytes)) return lio_fail(LIO_ERR_ARG, "null pointer");
     HIPCHK(hipSetDevice(device_id));
     HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
     return LIO_OK;
-}
+} LIO_CATCH
 extern "C" int lio_host_register(void* p, size_t bytes)
-{
+try {
     if (!p || !bytes) return lio_fail(LIO_ERR_ARG, "null range");
     HIPCHK(hipHostRegister(p, bytes, hipHostRegisterDefault));
     return LIO_OK;
-}
+} LIO_CATCH
 extern "C" int lio_host_unregister(void* p)
-{
+try {
     if (!p) return lio_fail(LIO_ERR_ARG, "null pointer");
     HIPCHK(hipHostUnregister(p));
     return LIO_OK;
-}
+} LIO_CATCH
 
 extern "C" int lio_s2m_batch_upload_async(lio_s2m_handle* h, int32_t n_scans, const void* const* scans,
                                           const size_t* n_pts, size_t stride)
-{
+try {
     if (!h) return lio_fail(LIO_ERR_ARG, "null handle");
     const bool keep = h->defer_sync;
     h->defer_sync = true;
@@ -516,10 +518,10 @@ extern "C" int lio_s2m_batch_upload_async(lio_s2m_handle* h, int32_t n_scans, co
     h->defer_sync = keep;
     h->async_upload = false;
     return rc;
-}
+} LIO_CATCH
 
 extern "C" int lio_s2m_set_shard(lio_s2m_handle* h, int32_t axis, int32_t lo, int32_t hi)
-{
+try {
     if (h && h->multi) return lio_fail(LIO_ERR_ARG, "not available on a multi-device handle (cfg.n_devices > 1 shards inside the library)");
     if (!h) return lio_fail(LIO_ERR_ARG, "null handle");
     if (axis < 0) { h->shard.axis = -1; return LIO_OK; }
@@ -534,7 +536,7 @@ extern "C" int lio_s2m_set_shard(lio_s2m_handle* h, int32_t axis, int32_t lo, in
     h->plan_ranks = 0;                 // (per-point ownership only; lio_s2m_set_shard_plan adds whole-workgroup ownership)
     h->graph_dirty = true;
     return LIO_OK;
-}
+} LIO_CATCH
 
 // The full slab plan: rank `rank` of `n_ranks` owns cells [bounds[rank], bounds[rank+1]) along `axis` and HOLDS the map
 // points of the cells [bounds[rank] - halo_cells, bounds[rank+1] + halo_cells) (what the caller passed to lio_s2m_set_map).
@@ -542,7 +544,7 @@ extern "C" int lio_s2m_set_shard(lio_s2m_handle* h, int32_t axis, int32_t lo, in
 // (k_shard_cull); halo_cells = 1 reduces to lio_s2m_set_shard.  Every rank must be given the same bounds and halo.
 extern "C" int lio_s2m_set_shard_plan(lio_s2m_handle* h, int32_t axis, int32_t n_ranks, int32_t rank, const int32_t* bounds,
                                       int32_t halo_cells)
-{
+try {
     if (!h || !bounds) return lio_fail(LIO_ERR_ARG, "null argument");
     if (h->multi) return lio_fail(LIO_ERR_ARG, "not available on a multi-device handle (cfg.n_devices > 1 shards inside the library)");
     if (n_ranks < 1 || n_ranks > 8 || rank < 0 || rank >= n_ranks || halo_cells < 1)
@@ -556,7 +558,7 @@ extern "C" int lio_s2m_set_shard_plan(lio_s2m_handle* h, int32_t axis, int32_t n
     h->plan_halo = halo_cells;
     for (int r = 0; r <= n_ranks; ++r) h->plan_bounds[r] = bounds[r];
     return LIO_OK;
-}
+} LIO_CATCH
 
 // ------------------------------------------------------------------- batch
 // The whole Gauss-Newton loop as one launch (k_s2m_persist, lio_persist.hip): possible when every workgroup of the batch is
@@ -590,12 +592,12 @@ static unsigned lio_persist_spin_max(const lio_s2m_handle* h)
 // Test hook: bound of the one-launch loop's barrier polls for this handle (0 = default) and the index of an association
 // workgroup that never arrives (-1 = none), which forces the time-out and with it the fall-back to the launch loop.
 extern "C" int lio_s2m_debug_persist_spin(lio_s2m_handle* h, int32_t spin_max, int32_t withhold_wg)
-{
+try {
     if (!h) return lio_fail(LIO_ERR_ARG, "null handle");
     h->persist_spin_max = spin_max > 0 ? (unsigned)spin_max : 0u;
     h->persist_withhold = withhold_wg;
     return LIO_OK;
-}
+} LIO_CATCH
 
 // The SoA copy of the resident batch, for the paths that read it, if the upload skipped it.
 static int lio_ensure_soa(lio_s2m_handle* h)
@@ -609,7 +611,7 @@ static int lio_ensure_soa(lio_s2m_handle* h)
 
 extern "C" int lio_s2m_batch_upload(lio_s2m_handle* h, int32_t n_scans, const void* const* scans,
                                     const size_t* n_pts, size_t stride)
-{
+try {
     if (!h || !scans || !n_pts) return lio_fail(LIO_ERR_ARG, "null argument");
     if (n_scans < 1) return lio_fail(LIO_ERR_ARG, "n_scans must be >= 1");
     if (stride < 12 || (stride & 3)) return lio_fail(LIO_ERR_ARG, "stride_bytes must be >= 12 and a multiple of 4");
@@ -633,21 +635,19 @@ extern "C" int lio_s2m_batch_upload(lio_s2m_handle* h, int32_t n_scans, const vo
     }
     h->host_state_stale = false;
     const size_t tt = total ? total : 1;
-    HIPCHK(lio_grow(&h->d_sx, &h->cap_sxyz[0], tt));
-    HIPCHK(lio_grow(&h->d_sy, &h->cap_sxyz[1], tt));
-    HIPCHK(lio_grow(&h->d_sz, &h->cap_sxyz[2], tt));
-    HIPCHK(lio_grow(&h->d_stage, &h->cap_stage, tt * stride));
-    HIPCHK(lio_grow(&h->d_state, &h->cap_state, (size_t)n_scans));
-    HIPCHK(lio_grow(&h->d_poses, &h->cap_poses, (size_t)n_scans * 6));
+    HIPCHK(h->d_sx.grow(tt));
+    HIPCHK(h->d_sy.grow(tt));
+    HIPCHK(h->d_sz.grow(tt));
+    HIPCHK(h->d_stage.grow(tt * stride));
+    HIPCHK(h->d_state.grow((size_t)n_scans));
+    HIPCHK(h->d_poses.grow((size_t)n_scans * 6));
     {
         // every launch leaves the counters at zero (the last workgroup of a scan re-arms it): clear at allocation only
-        const unsigned* before = h->d_arrive;
-        const size_t cap_before = h->cap_arrive;
-        HIPCHK(lio_grow(&h->d_arrive, &h->cap_arrive, (size_t)n_scans));
-        if (h->d_arrive != before || h->cap_arrive != cap_before)
-            HIPCHK(hipMemsetAsync(h->d_arrive, 0, h->cap_arrive * sizeof(unsigned), h->stream));
+        bool fresh = false;
+        HIPCHK(h->d_arrive.grow((size_t)n_scans, 1.25, 64, false, &fresh));
+        if (fresh) HIPCHK(hipMemsetAsync(h->d_arrive, 0, h->d_arrive.cap * sizeof(unsigned), h->stream));
     }
-    if (h->cfg.nn_cache && !h->cfg.use_lds) HIPCHK(lio_grow(&h->d_nn_cache, &h->cap_nn_cache, tt));
+    if (h->cfg.nn_cache && !h->cfg.use_lds) HIPCHK(h->d_nn_cache.grow(tt));
 
     // launch geometry: one workgroup = LIO_BLOCK * ppt consecutive points of one scan
     int ppt = h->cfg.kernel_variant;
@@ -730,16 +730,16 @@ extern "C" int lio_s2m_batch_upload(lio_s2m_handle* h, int32_t n_scans, const vo
     h->total_pts = total;
     h->n_blocks = (int)blocks.size();
     h->max_blk = max_blk;
-    HIPCHK(lio_grow(&h->d_blocks, &h->cap_blocks, blocks.size() ? blocks.size() : 1));
-    HIPCHK(lio_grow(&h->d_partials, &h->cap_partials, (size_t)n_scans * max_blk * LIO_SUMS));
+    HIPCHK(h->d_blocks.grow(blocks.size() ? blocks.size() : 1));
+    HIPCHK(h->d_partials.grow((size_t)n_scans * max_blk * LIO_SUMS));
     if (h->cfg.profile == 2) {
-        HIPCHK(lio_grow(&h->d_stamps, &h->cap_stamps, blocks.size() * (LIO_BLOCK / 64) * 8 + 8));
+        HIPCHK(h->d_stamps.grow(blocks.size() * (LIO_BLOCK / 64) * 8 + 8));
         HIPCHK(hipMemsetAsync(h->d_stamps, 0, (blocks.size() * (LIO_BLOCK / 64) * 8 + 8) * sizeof(long long), h->stream));
     }
     if (h->cfg.record_corr_iter >= 0) {
-        HIPCHK(lio_grow(&h->d_rec_flag, &h->cap_rec_flag, tt));
-        HIPCHK(lio_grow(&h->d_rec_coeff, &h->cap_rec_coeff, tt * 4));
-        HIPCHK(lio_grow(&h->d_rec_nn, &h->cap_rec_nn, tt * 5));
+        HIPCHK(h->d_rec_flag.grow(tt));
+        HIPCHK(h->d_rec_coeff.grow(tt * 4));
+        HIPCHK(h->d_rec_nn.grow(tt * 5));
         HIPCHK(hipMemsetAsync(h->d_rec_flag, 0, tt, h->stream));
         HIPCHK(hipMemsetAsync(h->d_rec_coeff, 0, tt * 4 * sizeof(float), h->stream));
         HIPCHK(hipMemsetAsync(h->d_rec_nn, 0xff, tt * 5 * sizeof(int), h->stream));
@@ -759,7 +759,7 @@ extern "C" int lio_s2m_batch_upload(lio_s2m_handle* h, int32_t n_scans, const vo
     // an empty slot of k_scan_sort_radix)
     if (want_sort && max_n < 16384 && h->cfg.sort_scan != 3) {
         // every scan fits one workgroup's LDS: bounding box, tile keys, sort and gather in ONE launch, nothing read back
-        HIPCHK(lio_grow(&h->d_perm, &h->cap_perm, tt));
+        HIPCHK(h->d_perm.grow(tt));
         lio_launch_scan_sort_lds(stage, stride, h->d_state, n_scans, (int)max_n, h->cfg.tile_size > 0.0f ? h->cfg.tile_size : 4.0f,
                                  h->shard.axis, h->d_perm, h->d_sx, h->d_sy, h->d_sz, h->stream);
         h->sorted = true;
@@ -770,14 +770,9 @@ extern "C" int lio_s2m_batch_upload(lio_s2m_handle* h, int32_t n_scans, const vo
             const int nb1 = (int)((n_pts[s] + LIO_BLOCK - 1) / LIO_BLOCK);
             for (int b = 0; b < nb1; ++b) prep.push_back({ s, b * LIO_BLOCK, b, nb1 });
         }
-        HIPCHK(lio_grow(&h->d_prep_blocks, &h->cap_prep_blocks, prep.size()));
-        HIPCHK(lio_grow(&h->d_scan_bbox, &h->cap_scan_bbox, (size_t)n_scans * 6));
-        if (h->cap_h_scan_bbox < (size_t)n_scans * 6) {
-            if (h->h_scan_bbox) HIPCHK(hipHostFree(h->h_scan_bbox));
-            h->h_scan_bbox = nullptr; h->cap_h_scan_bbox = 0;
-            HIPCHK(hipHostMalloc((void**)&h->h_scan_bbox, ((size_t)n_scans * 6 + 64) * sizeof(unsigned), hipHostMallocDefault));
-            h->cap_h_scan_bbox = (size_t)n_scans * 6 + 64;
-        }
+        HIPCHK(h->d_prep_blocks.grow(prep.size()));
+        HIPCHK(h->d_scan_bbox.grow((size_t)n_scans * 6));
+        HIPCHK(h->h_scan_bbox.grow((size_t)n_scans * 6, (size_t)n_scans * 6 + 64));
         for (int s = 0; s < n_scans; ++s)
             for (int a = 0; a < 6; ++a) h->h_scan_bbox[s * 6 + a] = a < 3 ? 0xffffffffu : 0u;
         HIPCHK(hipMemcpyAsync(h->d_scan_bbox, h->h_scan_bbox, (size_t)n_scans * 6 * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
@@ -817,18 +812,18 @@ extern "C" int lio_s2m_batch_upload(lio_s2m_handle* h, int32_t n_scans, const vo
             n_keys += (long long)t.ntx * t.nty * t.ntz;
         }
         if (n_keys < 0x7fffffffLL - 1024) {
-            HIPCHK(lio_grow(&h->d_tiles, &h->cap_tiles, (size_t)n_scans));
-            HIPCHK(lio_grow(&h->d_key_of, &h->cap_key_of, tt));
-            HIPCHK(lio_grow(&h->d_big_list, &h->cap_big_list, tt / 1024 + 2));
-            HIPCHK(lio_grow(&h->d_tmp_idx, &h->cap_tmp_idx, tt));
-            HIPCHK(lio_grow(&h->d_perm, &h->cap_perm, tt));
-            HIPCHK(lio_grow(&h->d_key_count, &h->cap_key_count, (size_t)n_keys));
-            HIPCHK(lio_grow(&h->d_key_start, &h->cap_key_start, (size_t)n_keys + 1));
-            HIPCHK(lio_grow(&h->d_key_tiles, &h->cap_key_tiles, (size_t)lio_scan_tiles((int)n_keys) + 1));
+            HIPCHK(h->d_tiles.grow((size_t)n_scans));
+            HIPCHK(h->d_key_of.grow(tt));
+            HIPCHK(h->d_big_list.grow(tt / 1024 + 2));
+            HIPCHK(h->d_tmp_idx.grow(tt));
+            HIPCHK(h->d_perm.grow(tt));
+            HIPCHK(h->d_key_count.grow((size_t)n_keys));
+            HIPCHK(h->d_key_start.grow((size_t)n_keys + 1));
+            HIPCHK(h->d_key_tiles.grow((size_t)lio_scan_tiles((int)n_keys) + 1));
             HIPCHK(hipMemcpyAsync(h->d_tiles, tiles.data(), tiles.size() * sizeof(LioScanTiles), hipMemcpyHostToDevice, h->stream));
             lio_launch_scan_tile_sort(stage, stride, (int)total, h->d_prep_blocks, (int)prep.size(), h->d_state,
                                       h->d_tiles, (int)n_keys, h->d_key_of, h->d_key_count, h->d_key_start,
-                                      h->d_key_tiles, h->d_tmp_idx, h->d_perm, h->d_big_list, h->d_big_list + (h->cap_big_list - 1),
+                                      h->d_key_tiles, h->d_tmp_idx, h->d_perm, h->d_big_list, h->d_big_list + (h->d_big_list.cap - 1),
                                       h->d_sx, h->d_sy, h->d_sz, h->stream);
             h->sorted = true;
         }
@@ -842,8 +837,8 @@ extern "C" int lio_s2m_batch_upload(lio_s2m_handle* h, int32_t n_scans, const vo
     h->has_block_box = false;
     if (h->shard.axis >= 0 && ppt == 1 && !blocks.empty()) {
         // map sharding: the box of every workgroup's points, for the cull at the head of k_s2m_iterate
-        HIPCHK(lio_grow(&h->d_block_box, &h->cap_block_box, (tt / LIO_BLOCK + (size_t)n_scans + 2) * 6));
-        HIPCHK(lio_grow(&h->d_blk_skip, &h->cap_blk_skip, blocks.size()));
+        HIPCHK(h->d_block_box.grow((tt / LIO_BLOCK + (size_t)n_scans + 2) * 6));
+        HIPCHK(h->d_blk_skip.grow(blocks.size()));
         lio_launch_block_boxes(h->d_blocks, (int)blocks.size(), h->d_state, h->d_sx, h->d_sy, h->d_sz, h->d_block_box, h->stream);
         h->has_block_box = true;
     }
@@ -855,11 +850,11 @@ extern "C" int lio_s2m_batch_upload(lio_s2m_handle* h, int32_t n_scans, const vo
     h->graph_dirty = true;
     h->corner_active = false;
     return LIO_OK;
-}
+} LIO_CATCH
 
 // ------------------------------------------------- corner residuals (extension)
 extern "C" int lio_s2m_set_corner_map(lio_s2m_handle* h, const void* pts, size_t n, size_t stride)
-{
+try {
     if (!h) return lio_fail(LIO_ERR_ARG, "null handle");
     if (h->multi) return lio_fail(LIO_ERR_ARG, "the corner extension is not available on a multi-device handle");
     HIPCHK(hipSetDevice(h->cfg.device_id));
@@ -878,11 +873,11 @@ extern "C" int lio_s2m_set_corner_map(lio_s2m_handle* h, const void* pts, size_t
     h->corner_active = false;
     h->graph_dirty = true;
     return lio_s2m_set_map(h->corner, pts, n, stride);
-}
+} LIO_CATCH
 
 extern "C" int lio_s2m_batch_upload_corners(lio_s2m_handle* h, int32_t n_scans, const void* const* scans,
                                             const size_t* n_pts, size_t stride)
-{
+try {
     if (!h || !scans || !n_pts) return lio_fail(LIO_ERR_ARG, "null argument");
     if (!h->corner || !h->corner->has_map) return lio_fail(LIO_ERR_NO_MAP, "set_corner_map has not been called");
     if (h->n_scans < 1 || n_scans != h->n_scans)
@@ -911,7 +906,7 @@ extern "C" int lio_s2m_batch_upload_corners(lio_s2m_handle* h, int32_t n_scans, 
         if (b.n_blk > max_blk) max_blk = b.n_blk;
     }
     h->max_blk = max_blk;
-    HIPCHK(lio_grow(&h->d_partials, &h->cap_partials, (size_t)n_scans * max_blk * LIO_SUMS));
+    HIPCHK(h->d_partials.grow((size_t)n_scans * max_blk * LIO_SUMS));
     if (!h->v_blocks.empty())
         HIPCHK(hipMemcpyAsync(h->d_blocks, h->v_blocks.data(), h->v_blocks.size() * sizeof(LioBlockDesc),
                               hipMemcpyHostToDevice, h->stream));
@@ -929,18 +924,18 @@ extern "C" int lio_s2m_batch_upload_corners(lio_s2m_handle* h, int32_t n_scans, 
     h->poses_set = false;             // (the workgroup list was rewritten: batch_set_poses re-orders it)
     h->graph_dirty = true;
     return LIO_OK;
-}
+} LIO_CATCH
 
 extern "C" int lio_s2m_get_corner_correspondences(lio_s2m_handle* h, int32_t scan, uint8_t* flag,
                                                   float* coeff4, int32_t* nn_idx5)
-{
+try {
     if (!h) return lio_fail(LIO_ERR_ARG, "null handle");
     if (!h->corner || !h->corner_active) return lio_fail(LIO_ERR_ARG, "no corner batch is resident");
     return lio_s2m_get_correspondences(h->corner, scan, flag, coeff4, nn_idx5);
-}
+} LIO_CATCH
 
 extern "C" int lio_s2m_batch_set_poses(lio_s2m_handle* h, const float* poses)
-{
+try {
     if (!h || !poses) return lio_fail(LIO_ERR_ARG, "null argument");
     if (h->n_scans < 1) return lio_fail(LIO_ERR_ARG, "no batch uploaded");
     if (h->multi) return lio_multi_set_poses(h, poses);
@@ -980,10 +975,10 @@ extern "C" int lio_s2m_batch_set_poses(lio_s2m_handle* h, const float* poses)
     if (!h->defer_sync) HIPCHK(hipStreamSynchronize(h->stream));
     h->poses_set = true;
     return LIO_OK;
-}
+} LIO_CATCH
 
 extern "C" int lio_s2m_set_degeneracy(lio_s2m_handle* h, int32_t scan, const float matP[36], int32_t is_degenerate)
-{
+try {
     if (!h || !matP) return lio_fail(LIO_ERR_ARG, "null argument");
     if (scan < 0 || scan >= h->n_scans) return lio_fail(LIO_ERR_ARG, "scan slot out of range");
     if (h->multi) return lio_multi_set_degeneracy(h, scan, matP, is_degenerate);
@@ -997,7 +992,7 @@ extern "C" int lio_s2m_set_degeneracy(lio_s2m_handle* h, int32_t scan, const flo
     HIPCHK(hipMemcpyAsync(base + offsetof(LioScanState, is_degenerate), &st.is_degenerate, sizeof(int), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return LIO_OK;
-}
+} LIO_CATCH
 
 static void lio_fill_params(lio_s2m_handle* h, LioIterParams& P, double* sums_out)
 {
@@ -1057,7 +1052,7 @@ static void lio_launch_gn(lio_s2m_handle* h, const LioIterParams& P, const LioIt
 }
 
 extern "C" int lio_s2m_batch_begin(lio_s2m_handle* h)
-{
+try {
     if (h && h->multi) return lio_fail(LIO_ERR_ARG, "not available on a multi-device handle (cfg.n_devices > 1 shards inside the library)");
     if (!h) return lio_fail(LIO_ERR_ARG, "null handle");
     if (!lio_map_of(h)->has_map) return lio_fail(LIO_ERR_NO_MAP, "set_map has not been called");
@@ -1083,7 +1078,7 @@ extern "C" int lio_s2m_batch_begin(lio_s2m_handle* h)
     h->unit_iters = 1;
     h->ran = true;
     return LIO_OK;
-}
+} LIO_CATCH
 
 // (Re)capture `chunk` consecutive GN-iteration launches into a hipGraph.  Every launch has the
 // same arguments -- all per-iteration state lives in device memory -- so one executable graph
@@ -1154,7 +1149,7 @@ static int lio_run_continue(lio_s2m_handle* h, bool blocking)
 }
 
 extern "C" int lio_s2m_batch_run(lio_s2m_handle* h)
-{
+try {
     if (h && h->multi) return lio_multi_run(h);
     int rc = lio_s2m_batch_begin(h);
     if (rc != LIO_OK) return rc;
@@ -1178,12 +1173,13 @@ extern "C" int lio_s2m_batch_run(lio_s2m_handle* h)
         if (h->cfg.lookahead < 0) look = 0;              // a chunk already is a run-ahead of `chunk` launches
     }
     if (h->run_persist) {
-        if ((size_t)h->n_scans * 2 > h->cap_gen || !h->d_gen) {
-            HIPCHK(lio_grow(&h->d_gen, &h->cap_gen, (size_t)h->n_scans * 2));
-            HIPCHK(hipMemsetAsync(h->d_gen, 0, h->cap_gen * sizeof(unsigned), h->stream));   // (fresh generation numbers / speculation states)
+        bool fresh = false;
+        HIPCHK(h->d_gen.grow((size_t)h->n_scans * 2, 1.25, 64, false, &fresh));
+        if (fresh) {
+            HIPCHK(hipMemsetAsync(h->d_gen, 0, h->d_gen.cap * sizeof(unsigned), h->stream));   // (fresh generation numbers / speculation states)
             h->gen_epoch = 0;
         }
-        HIPCHK(lio_grow(&h->d_spec_sums, &h->cap_spec_sums, (size_t)h->n_scans * LIO_SUMS));
+        HIPCHK(h->d_spec_sums.grow((size_t)h->n_scans * LIO_SUMS));
         h->gen_epoch += 128;
         chunk = h->cfg.max_iters;                        // one unit = the whole loop
     }
@@ -1197,10 +1193,10 @@ extern "C" int lio_s2m_batch_run(lio_s2m_handle* h)
     h->run_pending = true;
     // a lone registration (lio_s2m_register) has nothing to overlap with: drive the loop to the end right away
     return lio_run_continue(h, h->defer_sync);
-}
+} LIO_CATCH
 
 extern "C" int lio_s2m_batch_iter_partial(lio_s2m_handle* h, double* d_sums)
-{
+try {
     if (!h || !d_sums) return lio_fail(LIO_ERR_ARG, "null argument");
     if (!h->ran) return lio_fail(LIO_ERR_ARG, "batch_begin first");
     HIPCHK(hipSetDevice(h->cfg.device_id));
@@ -1239,12 +1235,12 @@ extern "C" int lio_s2m_batch_iter_partial(lio_s2m_handle* h, double* d_sums)
     h->units_this_run = h->launches_this_run;
     HIPCHK(hipGetLastError());
     return LIO_OK;
-}
+} LIO_CATCH
 
 extern "C" int lio_s2m_batch_iter_apply(lio_s2m_handle* h, const double* d_sums)
-{
+try {
     return lio_s2m_iter_apply_slots(h, d_sums, 0, 1);
-}
+} LIO_CATCH
 
 int lio_s2m_iter_apply_slots(lio_s2m_handle* h, const double* d_sums, size_t slot_stride, int n_slots)
 {
@@ -1264,17 +1260,17 @@ int lio_s2m_iter_apply_slots(lio_s2m_handle* h, const double* d_sums, size_t slo
 }
 
 extern "C" int lio_s2m_batch_poll_active(lio_s2m_handle* h, int32_t iteration, int32_t* n_active)
-{
+try {
     if (!h || !n_active) return lio_fail(LIO_ERR_ARG, "null argument");
     if (iteration < 0 || iteration >= h->launches_this_run || iteration >= LIO_MAX_ITERS)
         return lio_fail(LIO_ERR_ARG, "iteration has not been applied");
     HIPCHK(hipEventSynchronize(h->ev_chk[iteration]));
     *n_active = h->h_active[iteration];
     return LIO_OK;
-}
+} LIO_CATCH
 
 extern "C" int lio_s2m_batch_n_active(lio_s2m_handle* h, int32_t* n_active)
-{
+try {
     if (!h || !n_active) return lio_fail(LIO_ERR_ARG, "null argument");
     HIPCHK(hipSetDevice(h->cfg.device_id));
     (void)hipGetLastError();   // drop stale codes left by other HIP users of this thread (e.g. hipErrorNotReady)
@@ -1282,10 +1278,10 @@ extern "C" int lio_s2m_batch_n_active(lio_s2m_handle* h, int32_t* n_active)
     HIPCHK(hipStreamSynchronize(h->stream));
     *n_active = h->h_active[0];
     return LIO_OK;
-}
+} LIO_CATCH
 
 extern "C" int lio_s2m_batch_sync(lio_s2m_handle* h)
-{
+try {
     if (!h) return lio_fail(LIO_ERR_ARG, "null handle");
     if (h->multi) return lio_multi_sync(h);
     HIPCHK(hipSetDevice(h->cfg.device_id));
@@ -1294,10 +1290,10 @@ extern "C" int lio_s2m_batch_sync(lio_s2m_handle* h)
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipGetLastError());
     return LIO_OK;
-}
+} LIO_CATCH
 
 extern "C" int lio_s2m_batch_results(lio_s2m_handle* h, float* poses, lio_s2m_result* results)
-{
+try {
     if (!h) return lio_fail(LIO_ERR_ARG, "null handle");
     if (h->multi) return lio_multi_results(h, poses, results);
     if (!h->ran) return lio_fail(LIO_ERR_ARG, "nothing has been run");
@@ -1312,13 +1308,8 @@ extern "C" int lio_s2m_batch_results(lio_s2m_handle* h, float* poses, lio_s2m_re
     } else {
         // poses only: 40 bytes per scan through a pinned buffer instead of the whole state (1.5 KB per scan)
         const size_t need = (size_t)h->n_scans * 10;
-        HIPCHK(lio_grow(&h->d_summary, &h->cap_summary, need));
-        if (h->cap_h_summary < need) {
-            if (h->h_summary) HIPCHK(hipHostFree(h->h_summary));
-            h->h_summary = nullptr; h->cap_h_summary = 0;
-            HIPCHK(hipHostMalloc((void**)&h->h_summary, (need + 64) * sizeof(float), hipHostMallocDefault));
-            h->cap_h_summary = need + 64;
-        }
+        HIPCHK(h->d_summary.grow(need));
+        HIPCHK(h->h_summary.grow(need, need + 64));
         h->host_state_stale = true;
         lio_launch_pack_summary(h->d_state, h->n_scans, h->d_summary, h->stream);
         HIPCHK(hipMemcpyAsync(h->h_summary, h->d_summary, need * sizeof(float), hipMemcpyDeviceToHost, h->stream));
@@ -1347,7 +1338,7 @@ extern "C" int lio_s2m_batch_results(lio_s2m_handle* h, float* poses, lio_s2m_re
         if (incomplete) {
             h->persist_fallbacks++;
             h->prof.persist_fallbacks = h->persist_fallbacks;
-            HIPCHK(hipMemsetAsync(h->d_arrive, 0, h->cap_arrive * sizeof(unsigned), h->stream));
+            HIPCHK(hipMemsetAsync(h->d_arrive, 0, h->d_arrive.cap * sizeof(unsigned), h->stream));
             const bool keep_defer = h->defer_sync;
             h->no_persist = true; h->defer_sync = true;
             h->poses_set = true; h->pose_in_state = false;           // (k_s2m_init_state left the guesses in d_poses)
@@ -1404,11 +1395,11 @@ extern "C" int lio_s2m_batch_results(lio_s2m_handle* h, float* poses, lio_s2m_re
     h->prof.pipeline = h->run_persist ? 4 : 1;
     h->prof.persist_fallbacks = h->persist_fallbacks;
     return LIO_OK;
-}
+} LIO_CATCH
 
 extern "C" int lio_s2m_register(lio_s2m_handle* h, const void* scan, size_t n, size_t stride,
                                 float pose[6], lio_s2m_result* res)
-{
+try {
     if (!h || !pose) return lio_fail(LIO_ERR_ARG, "null argument");
     if (!lio_map_of(h)->has_map) return lio_fail(LIO_ERR_NO_MAP, "set_map has not been called");
     const void* scans[1] = { scan };
@@ -1429,7 +1420,7 @@ extern "C" int lio_s2m_register(lio_s2m_handle* h, const void* scan, size_t n, s
     lio_s2m_result local;
     if ((rc = lio_s2m_batch_results(h, pose, res ? res : &local)) != LIO_OK) return rc;
     return (res ? res : &local)->status;
-}
+} LIO_CATCH
 
 // Field offsets of a PointCloud2 come off the wire: every comparison is written so that it cannot wrap (off + 12 > step
 // passes for off = 0xfffffff4 in 32-bit arithmetic -- round-2 advisor finding).
@@ -1449,7 +1440,7 @@ int lio_pc2_check_xyz(const lio_pc2_layout* L)
 // into a pcl::PointCloud.  x, y, z are read in place at layout->off_x.
 extern "C" int lio_s2m_register_pc2(lio_s2m_handle* h, const void* data, size_t n_points, const lio_pc2_layout* layout,
                                     float pose[6], lio_s2m_result* res)
-{
+try {
     if (!h || !layout || !pose) return lio_fail(LIO_ERR_ARG, "null argument");
     if (lio_pc2_check_xyz(layout) != LIO_OK) return LIO_ERR_ARG;
     bool pinned = false;
@@ -1465,7 +1456,7 @@ extern "C" int lio_s2m_register_pc2(lio_s2m_handle* h, const void* data, size_t 
     h->int_off = -2;
     if (pinned) (void)hipHostUnregister(const_cast<void*>(data));
     return rc;
-}
+} LIO_CATCH
 
 // Internal (lio_mapbuild.hip): the staged records of batch slot `scan` as they were uploaded.
 int lio_s2m_staged_scan(lio_s2m_handle* h, int scan, const unsigned char** d_rec, size_t* n, size_t* stride, size_t* xyz_off, int* int_off,
@@ -1482,7 +1473,7 @@ int lio_s2m_staged_scan(lio_s2m_handle* h, int scan, const unsigned char** d_rec
 extern "C" int lio_s2m_register_cs(lio_s2m_handle* h, const void* corner_scan, size_t n_corner,
                                    const void* surf_scan, size_t n_surf, size_t stride,
                                    float pose[6], lio_s2m_result* res)
-{
+try {
     if (!h || !pose) return lio_fail(LIO_ERR_ARG, "null argument");
     if (!h->has_map) return lio_fail(LIO_ERR_NO_MAP, "set_map has not been called");
     if (n_corner && (!h->corner || !h->corner->has_map)) return lio_fail(LIO_ERR_NO_MAP, "set_corner_map has not been called");
@@ -1499,11 +1490,11 @@ extern "C" int lio_s2m_register_cs(lio_s2m_handle* h, const void* corner_scan, s
     lio_s2m_result local;
     if ((rc = lio_s2m_batch_results(h, pose, res ? res : &local)) != LIO_OK) return rc;
     return (res ? res : &local)->status;
-}
+} LIO_CATCH
 
 extern "C" int lio_s2m_get_correspondences(lio_s2m_handle* h, int32_t scan, uint8_t* flag,
                                            float* coeff4, int32_t* nn_idx5)
-{
+try {
     if (!h) return lio_fail(LIO_ERR_ARG, "null handle");
     if (h->cfg.record_corr_iter < 0) return lio_fail(LIO_ERR_ARG, "record_corr_iter was not set at create time");
     if (scan < 0 || scan >= h->n_scans) return lio_fail(LIO_ERR_ARG, "scan slot out of range");
@@ -1518,10 +1509,10 @@ extern "C" int lio_s2m_get_correspondences(lio_s2m_handle* h, int32_t scan, uint
     if (nn_idx5) HIPCHK(hipMemcpyAsync(nn_idx5, h->d_rec_nn + off * 5, n * 5 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return LIO_OK;
-}
+} LIO_CATCH
 
 extern "C" int lio_s2m_get_profile(lio_s2m_handle* h, lio_s2m_profile* out)
-{
+try {
     if (!h || !out) return lio_fail(LIO_ERR_ARG, "null argument");
     if (h->multi) h->prof.n_map = (int64_t)h->n_map;
     if (h->map_timing_pending) {
@@ -1534,9 +1525,7 @@ extern "C" int lio_s2m_get_profile(lio_s2m_handle* h, lio_s2m_profile* out)
     }
     *out = h->prof;
     return LIO_OK;
-}
-
-int lio_fail_ext(int code, const char* what, hipError_t e) { return lio_fail(code, what, e); }
+} LIO_CATCH
 
 // ------------------------------------------------------ host-side scalar code
 // transformUpdate, MO:1867-1897: roll/pitch are slerp-blended towards the IMU

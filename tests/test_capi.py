@@ -134,3 +134,51 @@ def test_bench_starts_its_own_ranks_from_the_plain_command():
     assert "starting 2 ranks" in p.stderr and "torch.distributed.run" in p.stderr
     assert "bench.py needs a GPU" in p.stderr
     assert p.stdout.strip() == ""                              # no JSON line without a measurement
+
+
+# Entry points that return a count or a constant and allocate nothing on the C++ side: no exception can leave them.
+_UNGUARDED_INT_ENTRY_POINTS = {"lio_version", "lio_kf_store_count", "lio_imu_deskew_info", "lio_s2m_debug_stamps"}
+
+
+def _matching(src, i, open_ch, close_ch):
+    """Index of the bracket that closes the one at src[i] (brackets inside comments and literals are skipped)."""
+    depth = 0
+    while True:
+        if src.startswith("//", i):
+            i = src.index("\n", i)
+        elif src.startswith("/*", i):
+            i = src.index("*/", i) + 2
+        elif src[i] in "\"'":
+            q, i = src[i], i + 1
+            while src[i] != q:
+                i += 2 if src[i] == "\\" else 1
+            i += 1
+        else:
+            depth += (src[i] == open_ch) - (src[i] == close_ch)
+            if depth == 0:
+                return i
+            i += 1
+
+
+def test_status_entry_points_stop_exceptions():
+    """include/liogpu.h promises that nothing throws: every extern "C" definition returning a status is a
+    function-try-block ending in LIO_CATCH, which turns an exception into LIO_ERR_CAPACITY."""
+    csrc = os.path.join(ROOT, "lio-slam_amd", "csrc")
+    guarded, unguarded = set(), set()
+    for name in sorted(os.listdir(csrc)):
+        if not name.endswith(".hip"):
+            continue
+        src = open(os.path.join(csrc, name)).read()
+        for m in re.finditer(r'extern "C" int (lio_\w+)\s*\(', src):
+            after = src[_matching(src, m.end() - 1, "(", ")") + 1:].lstrip()
+            if after.startswith(";"):
+                continue                                                  # a declaration
+            if after.startswith("try"):
+                body = src.index("{", len(src) - len(after))
+                tail = src[_matching(src, body, "{", "}") + 1:].lstrip()
+                if tail.startswith("LIO_CATCH"):
+                    guarded.add(m.group(1))
+                    continue
+            unguarded.add(m.group(1))
+    assert len(guarded) >= 40, sorted(guarded)
+    assert unguarded == _UNGUARDED_INT_ENTRY_POINTS, unguarded ^ _UNGUARDED_INT_ENTRY_POINTS

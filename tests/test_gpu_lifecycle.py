@@ -62,10 +62,43 @@ def _one_round(pkg, case, flavour):
         st.assemble(list(range(4)), ident, 0.4, s2m=s, want_output=False)
         p, _, _ = s.scan2MapOptimization(scans[0], poses0[0])
         s.close(); st.close()
+    elif flavour == "raw":                        # the raw-sweep workspace of the handle, and a keyframe taken from it
+        lay = pkg.PC2Layout(point_step=32, off_x=0, off_intensity=16, off_ring=-1, off_time=-1, pin_host=0)
+        raw = np.zeros((len(scans[0]), 8), np.float32)
+        raw[:, :3] = scans[0]; raw[:, 4] = 1.0
+        s = pkg.ScanToMap()
+        s.set_map(case["map"])
+        p, _, _, _ = s.downsampleAndScan2MapOptimization(raw, len(raw), lay, 0.4, poses0[0])
+        st = pkg.KeyframeStore()
+        st.add_from_handle(s)
+        s.close(); st.close()
+    elif flavour == "nearby":                     # the store's key-pose table and selection workspace
+        st = pkg.KeyframeStore()
+        rec = np.zeros((len(case["map"]), 4), np.float32)
+        rec[:, :3] = case["map"]
+        for k in range(4):
+            st.add(rec[k::4])
+        st.set_poses(0, np.zeros((4, 6), np.float32), np.arange(4, dtype=np.float64))
+        s = pkg.ScanToMap(sort_scan=2)
+        st.assemble_nearby(3.5, 0.4, s2m=s, want_ids=False, want_output=False)
+        p, _, _ = s.scan2MapOptimization(scans[0], poses0[0])
+        s.close(); st.close()
+    elif flavour == "corner":                     # the corner child handle
+        s = pkg.ScanToMap()
+        s.set_map(case["map"])
+        s.set_corner_map(case["map"][::3])
+        p, _, _ = s.scan2MapOptimizationCS(scans[0][::4], scans[0], poses0[0])
+        s.close()
+    elif flavour == "persist":                    # the one-launch loop's generation numbers and speculation sums
+        s = pkg.ScanToMap(sort_scan=2, pipeline=4)
+        s.set_map(case["map"])
+        s.batch_upload(scans); s.batch_set_poses(poses0); s.batch_run()
+        p, _ = s.batch_results()
+        s.close()
     return p
 
 
-@pytest.mark.parametrize("flavour", ["plain", "sharer", "cert", "multi", "abandoned", "store"])
+@pytest.mark.parametrize("flavour", ["plain", "sharer", "cert", "multi", "abandoned", "store", "raw", "nearby", "corner", "persist"])
 def test_destroy_returns_device_memory(pkg, small_case, flavour):
     first = _one_round(pkg, small_case, flavour)   # warm-up: code objects, HIP's own pools, pinned staging
     _one_round(pkg, small_case, flavour)
