@@ -263,6 +263,11 @@ int  lio_s2m_get_profile(lio_s2m_handle *h, lio_s2m_profile *out);
  * association workgroup that never arrives (-1 = none).  A launch that times out is re-run through the launch loop inside
  * lio_s2m_batch_results / lio_s2m_register and counted in lio_s2m_profile.persist_fallbacks; results are the same. */
 int  lio_s2m_debug_persist_spin(lio_s2m_handle *h, int32_t spin_max, int32_t withhold_wg);
+
+/* Test hook: the device plane fit of the association (MO:1648-1666: 5x3 colPivHouseholderQr solve against -1, unit normal
+ * and offset, plane test against plane_tol) on n neighbour sets, sets[n][5][3] in host memory.  out[n][8]: the raw bits of
+ * X0[0..2], pa, pb, pc, pd, then planeValid (0 / 1). */
+int  lio_debug_plane_fit(int32_t device_id, const float *sets, size_t n, double plane_tol, uint32_t *out);
 /* Diagnostic (cfg.profile == 2): per-wave phase clock of the last GN launch,
  * n_blocks x 4 x 8 cycle counters; returns n_blocks.  Not for production. */
 int  lio_s2m_debug_stamps(lio_s2m_handle *h, long long *out, size_t cap_entries);

@@ -130,7 +130,7 @@ EXPORTS = [
     "lio_s2m_share_map", "lio_s2m_batch_upload_async", "lio_host_alloc", "lio_host_free", "lio_host_register",
     "lio_host_unregister", "lio_s2m_set_shard_plan", "lio_s2m_register_pc2", "lio_deskew_pc2", "lio_kf_store_add_device", "lio_kf_store_add_from_handle",
     "lio_s2m_register_raw", "lio_s2m_debug_persist_spin", "lio_device_alloc", "lio_device_free", "lio_device_upload",
-    "lio_nearby_default_config", "lio_kf_store_set_poses", "lio_assemble_map_nearby",
+    "lio_nearby_default_config", "lio_kf_store_set_poses", "lio_assemble_map_nearby", "lio_debug_plane_fit",
 ]
 
 
@@ -621,6 +621,17 @@ def curvature(rng, device_id=0):
     _check(load_library().lio_curvature(device_id, r.ctypes.data, len(r), curv.ctypes.data,
                                         picked.ctypes.data, label.ctypes.data), "lio_curvature")
     return curv, picked, label
+
+
+# test hook: the device plane fit of the association on (n, 5, 3) neighbour sets -> (n, 8) uint32: the bits of X0[0..2],
+# pa, pb, pc, pd, then planeValid (include/liogpu.h)
+def debug_plane_fit(sets, plane_tol=0.2, device_id=0):
+    a = np.ascontiguousarray(sets, np.float32).reshape(-1, 15)
+    out = np.zeros((len(a), 8), np.uint32)
+    fn = load_library().lio_debug_plane_fit        # bound on first use: A/B runs load older builds through LIOGPU_LIB
+    fn.argtypes = [C.c_int32, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p]
+    _check(fn(device_id, a.ctypes.data, len(a), float(plane_tol), out.ctypes.data), "lio_debug_plane_fit")
+    return out
 
 
 # extension (row A4): projectPointCloud + cloudExtraction of upstream LIO-SAM -> the cloud_info arrays FE consumes

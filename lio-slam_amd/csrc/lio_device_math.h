@@ -14,6 +14,55 @@
 
 #define LIO_DEV __device__ __forceinline__
 
+// ------------------------------------------- divisions that share a denominator
+// n_i / d for several numerators and one denominator, bit-identical to the plain `/`.
+//
+// What the compiler emits for an fp32 `/` on gfx9 (LLVM AMDGPU, LowerFDIV32, fp32 denormals on) is
+//     ds = v_div_scale(d, d, n)   ns = v_div_scale(n, d, n)
+//     r0 = v_rcp_f32(ds)          e  = fma(-ds, r0, 1)      r  = fma(e, r0, r0)
+//     q  = ns * r                 e  = fma(-ds, q, ns)      q  = fma(e, r, q)
+//     e  = fma(-ds, q, ns)        q  = v_div_fmas(e, r, q)  result = v_div_fixup(q, d, n)
+// -- about 11 instructions, the first line and the reciprocal with its refinement among them.  v_div_scale pre-scales an
+// operand only when d, 1/d or n/d would be denormal, when exponent(n) - exponent(d) >= 96 or when the biased exponent of
+// n is <= 23; v_div_fmas is a plain fma unless one of the two scaled; v_div_fixup replaces the value only for zero,
+// infinite or NaN operands and for quotients outside the normal range.  With |d| and every |n_i| in [2^-40, 2^40) none of
+// that happens: exponent differences stay within 80, 1/d and n/d stay within [2^-81, 2^81], nothing is zero, infinite or
+// NaN.  There ds = d, ns = n, and the sequence is r = refine(v_rcp_f32(d)) followed by five operations per numerator
+// that depend on r and d alone.  The fast path below is exactly that, operation for operation, with the reciprocal and
+// its refinement computed once -- the same instructions on the same operands, hence the same (correctly rounded)
+// quotient.  The explicit fma builtins are not subject to -ffp-contract.
+// Outside that range (LioDivisor::mid false, or lio_div_mid false for the numerators) the caller takes the plain `/`;
+// the range test is two comparisons on the smallest and the largest magnitude of the group.
+#ifndef LIO_SHARED_DIV
+#define LIO_SHARED_DIV 1      // 0: every quotient through the plain `/` (A/B and the reference run of tests/test_plane_fit_bits.py)
+#endif
+struct LioDivisor { float d, r; bool mid; };
+
+LIO_DEV bool lio_div_mid(float lo, float hi) { return lo >= 0x1p-40f && hi < 0x1p40f; }   // (false for NaN)
+
+LIO_DEV LioDivisor lio_divisor(float d)
+{
+    LioDivisor v;
+    const float r0 = __builtin_amdgcn_rcpf(d);
+    const float e = __builtin_fmaf(-d, r0, 1.0f);
+    v.d = d; v.r = __builtin_fmaf(e, r0, r0);
+    v.mid = lio_div_mid(fabsf(d), fabsf(d));
+    return v;
+}
+
+// n / v.d; only for v.mid and |n| in [2^-40, 2^40)
+LIO_DEV float lio_div_fast(float n, const LioDivisor& v)
+{
+    float q = n * v.r;
+    float e = __builtin_fmaf(-v.d, q, n);
+    q = __builtin_fmaf(e, v.r, q);
+    e = __builtin_fmaf(-v.d, q, n);
+    return __builtin_fmaf(e, v.r, q);
+}
+
+LIO_DEV float lio_min3_abs(float a, float b, float c) { return fminf(fminf(fabsf(a), fabsf(b)), fabsf(c)); }
+LIO_DEV float lio_max3_abs(float a, float b, float c) { return fmaxf(fmaxf(fabsf(a), fabsf(b)), fabsf(c)); }
+
 // ---------------------------------------------------------------- plane fit
 // matA0.colPivHouseholderQr().solve(matB0) with matB0 = -1, MO:1633-1648
 // (Eigen 3.3 ColPivHouseholderQR: pivot on the largest updated column norm,
@@ -74,9 +123,18 @@ LIO_DEV void lio_plane_qr5x3(float a[5][3], float x[3])
         } else {
             beta = sqrtf(c0 * c0 + tail_sq);
             if (c0 >= 0.0f) beta = -beta;
-            const float den = c0 - beta;
+            // the 4 / 3 / 2 quotients of this column share `den` (lio_div_fast); any operand outside its range: plain `/`
+            const LioDivisor den = lio_divisor(c0 - beta);
+            float lo = fabsf(a[k + 1][k]), hi = lo;
 #pragma unroll
-            for (int i = k + 1; i < 5; ++i) a[i][k] = a[i][k] / den;
+            for (int i = k + 2; i < 5; ++i) { lo = fminf(lo, fabsf(a[i][k])); hi = fmaxf(hi, fabsf(a[i][k])); }
+            if (LIO_SHARED_DIV && den.mid && lio_div_mid(lo, hi)) {
+#pragma unroll
+                for (int i = k + 1; i < 5; ++i) a[i][k] = lio_div_fast(a[i][k], den);
+            } else {
+#pragma unroll
+                for (int i = k + 1; i < 5; ++i) a[i][k] = a[i][k] / den.d;
+            }
             tau = (beta - c0) / beta;
         }
         hc[k] = tau;
@@ -164,6 +222,31 @@ LIO_DEV void lio_plane_qr5x3(float a[5][3], float x[3])
 #pragma unroll
     for (int j = 0; j < 3; ++j)
         x[j] = (p0 == j) ? v0 : (p1 == j) ? v1 : (p2 == j) ? v2 : 0.0f;
+}
+
+// Plane through five map points, MO:1648-1666: the solve above, unit normal and offset (MO:1650-1656), plane test
+// (MO:1658-1666).  m is left alone; X0 receives the raw solution.  Returns planeValid.
+LIO_DEV bool lio_plane_fit5(const float m[5][3], double plane_tol, float X0[3], float& pa, float& pb, float& pc, float& pd)
+{
+    float a[5][3];
+#pragma unroll
+    for (int j = 0; j < 5; ++j) { a[j][0] = m[j][0]; a[j][1] = m[j][1]; a[j][2] = m[j][2]; }
+    lio_plane_qr5x3(a, X0);                                   // MO:1648
+    pa = X0[0]; pb = X0[1]; pc = X0[2]; pd = 1;               // MO:1650-1653
+    const float ps = sqrtf(pa * pa + pb * pb + pc * pc);      // MO:1655
+    const LioDivisor dv = lio_divisor(ps);                    // MO:1656: four quotients by one ps
+    if (LIO_SHARED_DIV && dv.mid && lio_div_mid(lio_min3_abs(pa, pb, pc), lio_max3_abs(pa, pb, pc))) {
+        pa = lio_div_fast(pa, dv); pb = lio_div_fast(pb, dv); pc = lio_div_fast(pc, dv); pd = lio_div_fast(pd, dv);
+    } else {
+        pa /= ps; pb /= ps; pc /= ps; pd /= ps;
+    }
+    bool planeValid = true;                                   // MO:1658-1666
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+        const float v = fabsf(pa * m[j][0] + pb * m[j][1] + pc * m[j][2] + pd);
+        if ((double)v > plane_tol) planeValid = false;
+    }
+    return planeValid;
 }
 
 // --------------------------------------------------------------- Jacobian

@@ -66,3 +66,4 @@ void lio_launch_scan_tile_sort(const void* stage, size_t stride, int total_pts,
                                float* x, float* y, float* z, hipStream_t s);
 void lio_launch_exclusive_scan(const int* in, int n, int* tile_sums, int* out, hipStream_t s);
 void lio_launch_xyzi4_to_soa(const float4* src, int n, float* x, float* y, float* z, float4* xyz4, hipStream_t s);
+void lio_launch_debug_plane_fit(const float* sets, long long n, double plane_tol, unsigned* out, hipStream_t s);

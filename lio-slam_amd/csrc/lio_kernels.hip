@@ -889,24 +889,28 @@ __global__ __launch_bounds__(LIO_BLOCK, (PPT == 1 && !STAGE && !CORNER) ? LIO_MI
     const LioBlockDesc bd = P.blocks[wg];
     LioScanState* st = &P.state[bd.scan];
     if (st->done) return;                                  // workgroup-uniform
-    // diagnostic phase clock (P.stamps is null outside profiling experiments)
-    long long* stamp = P.stamps ? P.stamps + ((size_t)wg * (LIO_BLOCK / 64) + (threadIdx.x >> 6)) * 8 : nullptr;
-#define LIO_STAMP(k) do { if (stamp && (threadIdx.x & 63) == 0) stamp[k] = (long long)__builtin_readcyclecounter(); } while (0)
-    LIO_STAMP(0);
-
-    // wave-uniform per-scan values
+    // wave-uniform per-scan values, read BEFORE the first store of the kernel (the phase clock's stamp below): with no store
+    // between the kernel's entry and these loads they are scalar loads into SGPRs, not 30 vector loads whose results every
+    // lane holds in VGPRs.  (The scan's last workgroup rewrites T / Tp / trig in lio_gn_step after every workgroup of the
+    // scan has arrived, i.e. after all of them have read these.)
     float T[12], tr[6];
 #pragma unroll
     for (int k = 0; k < 12; ++k) T[k] = st->T[k];
 #pragma unroll
     for (int k = 0; k < 6; ++k) tr[k] = st->trig[k];
+    float Tp[12];                                          // the transform of the previous iteration (read only under use_cache)
+#pragma unroll
+    for (int k = 0; k < 12; ++k) Tp[k] = st->Tp[k];
     const int n_pts = CORNER ? st->c_n_pts : st->n_pts;
     const int base = CORNER ? st->c_offset : st->offset;
-    const bool record = (P.rec_flag != nullptr) && (st->iter == P.c.record_iter);
-    const bool use_cache = (P.d5_cache != nullptr) && !STAGE && st->iter > 0;   // iteration 0 has nothing to re-use
-    float Tp[12];                                          // the transform of the previous iteration
-#pragma unroll
-    for (int k = 0; k < 12; ++k) Tp[k] = use_cache ? st->Tp[k] : 0.0f;
+    const int st_iter = st->iter;
+    // diagnostic phase clock (P.stamps is null outside profiling experiments)
+    long long* stamp = P.stamps ? P.stamps + ((size_t)wg * (LIO_BLOCK / 64) + (threadIdx.x >> 6)) * 8 : nullptr;
+#define LIO_STAMP(k) do { if (stamp && (threadIdx.x & 63) == 0) stamp[k] = (long long)__builtin_readcyclecounter(); } while (0)
+    LIO_STAMP(0);
+
+    const bool record = (P.rec_flag != nullptr) && (st_iter == P.c.record_iter);
+    const bool use_cache = (P.d5_cache != nullptr) && !STAGE && st_iter > 0;   // iteration 0 has nothing to re-use
     const LioGrid g = P.grid;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 
@@ -1054,7 +1058,7 @@ __global__ __launch_bounds__(LIO_BLOCK, (PPT == 1 && !STAGE && !CORNER) ? LIO_MI
         // the sentinel.  R is rounded up by 1e-4 (fp32 rounding of the distances is 1e-7).  Typically
         // R ~ 0.5 m against the 1 m gate: half the candidate run.  One float per point is kept.
         float bound2 = P.c.max_sq_dist;
-        float Rx = sqrtf(P.c.max_sq_dist) * 1.0001f + 1e-6f;          // reach along x: the gate, unless the bound below is tighter
+        float Rx = P.c.gate_reach;                                    // reach along x: the gate, unless the bound below is tighter
         bool bounded = false;
         const int ci = base + bd.first + pp * LIO_BLOCK + (int)threadIdx.x;   // slot in the batch SoA
         if (use_cache && act[pp]) {
@@ -1137,6 +1141,31 @@ __global__ __launch_bounds__(LIO_BLOCK, (PPT == 1 && !STAGE && !CORNER) ? LIO_MI
     lio_arrive_and_finish(P, bd, st, lane, s_sum, &s_ws, stamp);
     LIO_STAMP(7);
 #undef LIO_STAMP
+}
+
+// Test hook (lio_debug_plane_fit): the device plane fit on caller-supplied neighbour sets, one set per thread --
+// lio_plane_fit5, the function lio_assoc_point calls.  out[8 i ..] = the bits of X0[0..2], pa, pb, pc, pd, then planeValid.
+__global__ __launch_bounds__(256) void k_debug_plane_fit(const float* __restrict__ sets, long long n, double plane_tol,
+                                                         unsigned* __restrict__ out)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float m[5][3];
+#pragma unroll
+    for (int j = 0; j < 5; ++j)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) m[j][c] = sets[i * 15 + j * 3 + c];
+    float X0[3], pa, pb, pc, pd;
+    const bool valid = lio_plane_fit5(m, plane_tol, X0, pa, pb, pc, pd);
+    uint4* o = reinterpret_cast<uint4*>(out + i * 8);
+    o[0] = make_uint4(__float_as_uint(X0[0]), __float_as_uint(X0[1]), __float_as_uint(X0[2]), __float_as_uint(pa));
+    o[1] = make_uint4(__float_as_uint(pb), __float_as_uint(pc), __float_as_uint(pd), valid ? 1u : 0u);
+}
+
+void lio_launch_debug_plane_fit(const float* sets, long long n, double plane_tol, unsigned* out, hipStream_t s)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_debug_plane_fit, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, sets, n, plane_tol, out);
 }
 
 // Compact per-scan summary for callers that only want the poses: [pose x6 | iter | status | converged | is_degenerate]

@@ -153,7 +153,7 @@ __global__ __launch_bounds__(LIO_BLOCK, 2) void k_s2m_persist(LioIterParams P, u
         LIO_TICK(0);
         // ---- exact 5-NN (MO:1631) inside the search bound of the previous iteration (see k_s2m_iterate)
         float bound2 = P.c.max_sq_dist;
-        float Rx = sqrtf(P.c.max_sq_dist) * 1.0001f + 1e-6f;              // reach along x: the gate, unless the bound below is tighter
+        float Rx = P.c.gate_reach;                                    // reach along x: the gate, unless the bound below is tighter
         bool bounded = false;
         if (use_cache && act) {
             const float d5 = P.d5_cache[ci];

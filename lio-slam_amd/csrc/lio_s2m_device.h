@@ -252,9 +252,28 @@ LIO_DEV void lio_knn_group(const float4& c0, const float4& c1, const float4& c2,
     lio_top5_insert4(top, k0, k1, k2, k3);
 }
 
+// The query's 3x3-cell row in every tight table (LioGrid::tb_*); a query outside a table is clamped into it.  The tables fill
+// tb_reach from 0 up and an absent one has tb_reach <= 0; g is wave-uniform, so the cell arithmetic of a table the map does
+// not have is skipped on a scalar branch (the empty asm keeps the compiler from computing it anyway and selecting afterwards).
+// Evaluated once per query, outside the progressive search's loop.
+LIO_DEV void lio_tb_rows(const LioGrid& g, float qy, float qz, int (&tb_row)[LIO_TB_MAX])
+{
+#pragma unroll
+    for (int l = 0; l < LIO_TB_MAX; ++l) {
+        tb_row[l] = 0;
+        if (g.tb_reach[l] > 0.0f) {
+            const int by = min(max(lio_cell_coord(qy, g.tb_oy[l], g.tb_inv_cell[l], g.tb_ny[l]), 0), g.tb_ny[l] - 1);
+            const int bz = min(max(lio_cell_coord(qz, g.tb_oz[l], g.tb_inv_cell[l], g.tb_nz[l]), 0), g.tb_nz[l] - 1);
+            int row = g.tb_row0[l] + (bz * g.tb_ny[l] + by) * g.nxf;
+            asm volatile("" : "+v"(row));
+            tb_row[l] = row;
+        }
+    }
+}
+
 // The candidate run of one query: [beg, end) records of nbr_pts (beg aligned down to a whole group), empty: beg >= end.
-LIO_DEV void lio_knn_range(const LioIterParams& P, const LioGrid& g, float qx, float qy, float qz,
-                           int cy, int cz, float Rx, unsigned& beg, unsigned& end)
+LIO_DEV void lio_knn_range(const LioIterParams& P, const LioGrid& g, float qx, int cy, int cz, const int (&tb_row)[LIO_TB_MAX],
+                           float Rx, unsigned& beg, unsigned& end)
 {
     // Rx: the current search bound -- the gate radius, or the tighter bound the previous iteration's neighbours gave (see
     // "neighbour cache" in the kernels); [xlo, xhi]: the FINE x cells (LioGrid::xs per cell) that can hold a point within it
@@ -264,16 +283,11 @@ LIO_DEV void lio_knn_range(const LioIterParams& P, const LioGrid& g, float qx, f
     if (x0 > x1) return;
     int row = (min(max(cz, 0), g.nz - 1) * g.ny + min(max(cy, 0), g.ny - 1)) * g.nxf;
     // tight rows (LioGrid::tb_*): every map point within Rx of the query lies in the 3x3 cells around the query's cell of a
-    // table whose cell is at least Rx, i.e. in that cell's row; the tightest such table wins (reach descending); a query
-    // outside the grid is clamped as above
+    // table whose cell is at least Rx, i.e. in that cell's row; the tightest such table wins (reach descending; an absent
+    // table has a negative reach)
 #pragma unroll
-    for (int l = 0; l < LIO_TB_MAX; ++l) {
-        if (Rx <= g.tb_reach[l]) {
-            const int by = min(max(lio_cell_coord(qy, g.tb_oy[l], g.tb_inv_cell[l], g.tb_ny[l]), 0), g.tb_ny[l] - 1);
-            const int bz = min(max(lio_cell_coord(qz, g.tb_oz[l], g.tb_inv_cell[l], g.tb_nz[l]), 0), g.tb_nz[l] - 1);
-            row = g.tb_row0[l] + (bz * g.tb_ny[l] + by) * g.nxf;
-        }
-    }
+    for (int l = 0; l < LIO_TB_MAX; ++l)
+        if (Rx <= g.tb_reach[l]) row = tb_row[l];
 #if LIO_PREFETCH == 3
     beg = (unsigned)P.nbr_start[row + x0] & ~7u;
 #else
@@ -342,6 +356,8 @@ LIO_DEV void lio_knn_global(const LioIterParams& P, const LioGrid& g, float qx, 
                             int cy, int cz, float Rx, float bound2, bool bounded, LioTop5& top)
 {
     int lvl = bounded ? -1 : g.tb_try;
+    int tb_row[LIO_TB_MAX];
+    lio_tb_rows(g, qy, qz, tb_row);
     for (;;) {
         float rx = Rx, b2 = bound2;
         if (lvl >= 0) {
@@ -352,7 +368,7 @@ LIO_DEV void lio_knn_global(const LioIterParams& P, const LioGrid& g, float qx, 
         const double sentinel = lio_make_key(b2, -1);                     // index 0xffffffff: above every real index
         top.k0 = top.k1 = top.k2 = top.k3 = top.k4 = sentinel;
         unsigned beg, end;
-        lio_knn_range(P, g, qx, qy, qz, cy, cz, rx, beg, end);
+        lio_knn_range(P, g, qx, cy, cz, tb_row, rx, beg, end);
         lio_knn_run(P, beg, end, qx, qy, qz, top);
         // five points within the tried radius: every point outside the table's row is farther than that -- done
         if (lvl < 0 || lio_key_idx(top.k4) != -1) break;
@@ -369,28 +385,17 @@ LIO_DEV bool lio_assoc_point(const LioIterParams& P, const int nn[5], float qx, 
 {
     bool accept = false;
     // MO:1642-1646: neighbours in the caller's map order (original xyz)
-    float a[5][3], m[5][3];
+    float m[5][3];
 #pragma unroll
     for (int j = 0; j < 5; ++j) {
         const float4 mp = P.map_xyz4[nn[j]];
-        m[j][0] = a[j][0] = mp.x;
-        m[j][1] = a[j][1] = mp.y;
-        m[j][2] = a[j][2] = mp.z;
+        m[j][0] = mp.x; m[j][1] = mp.y; m[j][2] = mp.z;
     }
     if (CORNER) {
         accept = lio_corner_assoc(m, qx, qy, qz, P.c.weight, P.c.min_s, cxx, cyy, czz, cww);
     } else {
-        float X0[3];
-        lio_plane_qr5x3(a, X0);                                  // MO:1648
-        float pa = X0[0], pb = X0[1], pc = X0[2], pd = 1;         // MO:1650-1653
-        const float ps = sqrtf(pa * pa + pb * pb + pc * pc);      // MO:1655
-        pa /= ps; pb /= ps; pc /= ps; pd /= ps;                   // MO:1656
-        bool planeValid = true;                                   // MO:1658-1666
-#pragma unroll
-        for (int j = 0; j < 5; ++j) {
-            const float v = fabsf(pa * m[j][0] + pb * m[j][1] + pc * m[j][2] + pd);
-            if ((double)v > P.c.plane_tol) planeValid = false;
-        }
+        float X0[3], pa, pb, pc, pd;
+        const bool planeValid = lio_plane_fit5(m, P.c.plane_tol, X0, pa, pb, pc, pd);   // MO:1648-1666
         if (planeValid) {
             const float pd2 = pa * qx + pb * qy + pc * qz + pd;   // MO:1669
             const float r2 = px * px + py * py + pz * pz;

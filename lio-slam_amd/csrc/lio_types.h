@@ -57,6 +57,8 @@ struct LioShard {
 struct LioConsts {
     double plane_tol, weight, min_s, conv_deg, conv_cm;
     float  max_sq_dist, eig_thresh;
+    float  gate_reach;       // sqrtf(max_sq_dist) * 1.0001f + 1e-6f: the search reach of an unbounded query, evaluated once on the
+                             // host (IEEE sqrt, product and sum in fp32, no contraction: the bits the kernels used to compute per lane)
     int32_t min_corr, max_iters, jac_exact, force_all, record_iter, min_scan_pts;
 };
 

@@ -89,6 +89,12 @@ static void lio_fill_consts(lio_s2m_handle* h)
     h->c.plane_tol = g.plane_tol; h->c.weight = g.weight; h->c.min_s = g.min_s;
     h->c.conv_deg = g.conv_deg; h->c.conv_cm = g.conv_cm;
     h->c.max_sq_dist = g.max_sq_dist; h->c.eig_thresh = g.eig_thresh;
+    {   // each step rounded to fp32 on its own, as the device did
+        volatile float r = sqrtf(g.max_sq_dist);
+        r = r * 1.0001f;
+        r = r + 1e-6f;
+        h->c.gate_reach = r;
+    }
     h->c.min_corr = g.min_corr; h->c.max_iters = g.max_iters;
     h->c.jac_exact = g.jacobian_mode ? 1 : 0; h->c.force_all = g.force_all_iters ? 1 : 0;
     h->c.record_iter = g.record_corr_iter; h->c.min_scan_pts = g.min_scan_pts;
@@ -596,6 +602,26 @@ try {
     if (!h) return lio_fail(LIO_ERR_ARG, "null handle");
     h->persist_spin_max = spin_max > 0 ? (unsigned)spin_max : 0u;
     h->persist_withhold = withhold_wg;
+    return LIO_OK;
+} LIO_CATCH
+
+// Test hook: the plane fit of the association kernels (lio_plane_fit5: the 5x3 column-pivoting QR solve, the unit normal and the
+// plane test) on n caller-supplied neighbour sets, sets[n][5][3] in host memory.  out[n][8] receives the raw bits of
+// X0[0..2], pa, pb, pc, pd and planeValid (0 / 1).
+extern "C" int lio_debug_plane_fit(int32_t device_id, const float* sets, size_t n, double plane_tol, uint32_t* out)
+try {
+    if ((!sets || !out) && n) return lio_fail(LIO_ERR_ARG, "null pointer");
+    if (n > ((size_t)1 << 27)) return lio_fail(LIO_ERR_CAPACITY, "at most 2^27 sets per call");
+    if (!n) return LIO_OK;
+    HIPCHK(hipSetDevice(device_id));
+    LioDevBuf<float> d_sets;
+    LioDevBuf<unsigned> d_out;
+    HIPCHK(d_sets.grow(n * 15, 1.0, 0));
+    HIPCHK(d_out.grow(n * 8, 1.0, 0));
+    HIPCHK(hipMemcpy(d_sets, sets, n * 15 * sizeof(float), hipMemcpyHostToDevice));
+    lio_launch_debug_plane_fit(d_sets, (long long)n, plane_tol, d_out, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out, d_out, n * 8 * sizeof(unsigned), hipMemcpyDeviceToHost));
     return LIO_OK;
 } LIO_CATCH
 
