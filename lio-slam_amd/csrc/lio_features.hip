@@ -19,6 +19,7 @@
 
 #include "../../include/liogpu.h"
 #include "lio_pool.h"
+#include "lio_wg.h"
 
 typedef unsigned long long u64;
 
@@ -86,25 +87,6 @@ __device__ static int feat_pow2_at_least(int n)
     int p = 2;
     while (p < n) p <<= 1;
     return p;
-}
-
-// exclusive scan of one int per thread over the workgroup; *total = sum
-__device__ static int feat_block_scan(int v, int* total, int* s_tmp /* [8] */)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(inc, off);
-        if (lane >= off) inc += t;
-    }
-    __syncthreads();
-    if (lane == 63) s_tmp[wave] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int w = 0; w < FEAT_BLOCK / 64; ++w) { if (w < wave) base += s_tmp[w]; tot += s_tmp[w]; }
-    *total = tot;
-    return base + inc - v;
 }
 
 struct FeatParams {
@@ -267,7 +249,7 @@ __global__ __launch_bounds__(FEAT_BLOCK) void k_feat_ring(FeatParams P)
             const int k = b + (int)threadIdx.x;
             const int f = (k <= ep && s_label[k - w0] <= 0) ? 1 : 0;
             int tot;
-            const int off = feat_block_scan(f, &tot, s_tmp);
+            const int off = lio_wg_exclusive_scan<FEAT_BLOCK / 64>(f, &tot, s_tmp);
             const int base = s_n_list;
             if (f) s_list[base + off] = (unsigned short)(k - w0);
             __syncthreads();
@@ -295,25 +277,10 @@ __global__ __launch_bounds__(FEAT_BLOCK) void k_feat_ring(FeatParams P)
 #pragma unroll
         for (int a = 0; a < 3; ++a) { mn[a] = fminf(mn[a], p[a]); mx[a] = fmaxf(mx[a], p[a]); }
     }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            mn[a] = fminf(mn[a], __shfl_xor(mn[a], off));
-            mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], off));
-        }
-    }
-    float* s_red = reinterpret_cast<float*>(s_pool);        // [4 waves][6]
-    if ((threadIdx.x & 63) == 0) {
-        for (int a = 0; a < 3; ++a) { s_red[(threadIdx.x >> 6) * 6 + a] = mn[a]; s_red[(threadIdx.x >> 6) * 6 + 3 + a] = mx[a]; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        float v = s_red[threadIdx.x];
-        for (int w = 1; w < FEAT_BLOCK / 64; ++w)
-            v = threadIdx.x < 3 ? fminf(v, s_red[w * 6 + threadIdx.x]) : fmaxf(v, s_red[w * 6 + threadIdx.x]);
-        s_box[threadIdx.x] = v;
-    }
+    LioWgBoxLds<FEAT_BLOCK / 64>& s_red = *reinterpret_cast<LioWgBoxLds<FEAT_BLOCK / 64>*>(s_pool);
+    float lo, hi;
+    lio_wg_box(mn, mx, s_red, lo, hi);
+    if (threadIdx.x < 3) { s_box[threadIdx.x] = lo; s_box[3 + threadIdx.x] = hi; }
     __syncthreads();
     for (int a = 0; a < 3; ++a) { mn[a] = s_box[a]; mx[a] = s_box[3 + a]; }
     const long long dx = (long long)((mx[0] - mn[0]) * inv) + 1, dy = (long long)((mx[1] - mn[1]) * inv) + 1,
@@ -351,7 +318,7 @@ __global__ __launch_bounds__(FEAT_BLOCK) void k_feat_ring(FeatParams P)
         const int t = b + (int)threadIdx.x;
         const bool head = t < nl && (t == 0 || (unsigned)(s_pool[t] >> 32) != (unsigned)(s_pool[t - 1] >> 32));
         int tot;
-        const int off = feat_block_scan(head ? 1 : 0, &tot, s_tmp);
+        const int off = lio_wg_exclusive_scan<FEAT_BLOCK / 64>(head ? 1 : 0, &tot, s_tmp);
         if (head) {
             const unsigned vox = (unsigned)(s_pool[t] >> 32);
             float sx = 0, sy = 0, sz = 0, si = 0;

@@ -3,6 +3,7 @@
 //
 //   map build : k_map_bbox, k_map_cell_count, k_scan_*, k_map_scatter
 //               (replaces the kd-tree build at MO:1846)
+//   lio_wg.h  : the workgroup scan, the workgroup min / max box and the float-order mapping these and the feeders share
 //   GN iterate: k_s2m_iterate  = surfOptimization MO:1618-1687
 //                              + combineOptimizationCoeffs MO:1689-1700 (as a sum)
 //                              + LMOptimization MO:1702-1837 (last workgroup of a scan)
@@ -15,12 +16,7 @@
 
 #include "lio_s2m_device.h"
 #include "lio_scan2.h"
-
-LIO_DEV unsigned lio_f2ord(float f)   // order-preserving float -> uint
-{
-    unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
+#include "lio_wg.h"
 
 // ------------------------------------------------------------- AoS -> SoA
 // pcl::PointXYZI records (x,y,z at byte 0,4,8; stride given) -> x[],y[],z[]
@@ -61,26 +57,12 @@ __global__ void k_map_bbox(const float* __restrict__ x, const float* __restrict_
             if (fabsf(v[a]) <= LIO_MAX_COORD) { mn[a] = fminf(mn[a], v[a]); mx[a] = fmaxf(mx[a], v[a]); }
         }
     }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            mn[a] = fminf(mn[a], __shfl_xor(mn[a], off));
-            mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], off));
-        }
-    }
     // one set of atomics per workgroup (six hot words: per-wave atomics serialise)
-    __shared__ float s_mn[4][3], s_mx[4][3];
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { s_mn[wave][a] = mn[a]; s_mx[wave][a] = mx[a]; }
-    }
-    __syncthreads();
+    __shared__ LioWgBoxLds<4> s_box;
+    float lo, hi;
+    lio_wg_box(mn, mx, s_box, lo, hi);
     if (threadIdx.x < 3) {
         const int a = threadIdx.x;
-        float lo = s_mn[0][a], hi = s_mx[0][a];
-        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) { lo = fminf(lo, s_mn[w][a]); hi = fmaxf(hi, s_mx[w][a]); }
         atomicMin(&bbox[a], lio_f2ord(lo));
         atomicMax(&bbox[3 + a], lio_f2ord(hi));
     }
@@ -126,25 +108,6 @@ __global__ void k_map_occupancy(LioGrid g, const float* __restrict__ x, const fl
 #define LIO_SCAN_ITEMS 16
 #define LIO_SCAN_TILE (256 * LIO_SCAN_ITEMS)
 
-LIO_DEV int lio_block_exclusive_scan(int v, int* total, int* s_wave /* >= 4 ints */)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(incl, off);
-        if (lane >= off) incl += t;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int wave_off = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) { const int s = s_wave[w]; if (w < wave) wave_off += s; tot += s; }
-    __syncthreads();
-    *total = tot;
-    return wave_off + incl - v;
-}
-
 __global__ __launch_bounds__(256) void k_scan_tile_sums(const int* __restrict__ in, int n, int* __restrict__ tile_sums)
 {
     __shared__ int s_wave[4];
@@ -153,22 +116,14 @@ __global__ __launch_bounds__(256) void k_scan_tile_sums(const int* __restrict__ 
 #pragma unroll
     for (int k = 0; k < LIO_SCAN_ITEMS; ++k) if (base + k < n) s += in[base + k];
     int tot;
-    lio_block_exclusive_scan(s, &tot, s_wave);
+    lio_wg_exclusive_scan<4>(s, &tot, s_wave);
     if (threadIdx.x == 0) tile_sums[blockIdx.x] = tot;
 }
 
 __global__ __launch_bounds__(256) void k_scan_tile_offsets(int* __restrict__ tile_sums, int n_tiles)
 {
     __shared__ int s_wave[4];
-    int carry = 0;
-    for (int b = 0; b < n_tiles; b += 256) {
-        const int i = b + threadIdx.x;
-        const int v = i < n_tiles ? tile_sums[i] : 0;
-        int tot;
-        const int ex = lio_block_exclusive_scan(v, &tot, s_wave);
-        if (i < n_tiles) tile_sums[i] = carry + ex;
-        carry += tot;
-    }
+    lio_wg_scan_in_place<4>(tile_sums, n_tiles, s_wave);
 }
 
 __global__ __launch_bounds__(256) void k_scan_apply(const int* __restrict__ in, int n,
@@ -182,7 +137,7 @@ __global__ __launch_bounds__(256) void k_scan_apply(const int* __restrict__ in, 
 #pragma unroll
     for (int k = 0; k < LIO_SCAN_ITEMS; ++k) { v[k] = (base + k < n) ? in[base + k] : 0; s += v[k]; }
     int tot;
-    int run = tile_offsets[blockIdx.x] + lio_block_exclusive_scan(s, &tot, s_wave);
+    int run = tile_offsets[blockIdx.x] + lio_wg_exclusive_scan<4>(s, &tot, s_wave);
 #pragma unroll
     for (int k = 0; k < LIO_SCAN_ITEMS; ++k) {
         if (base + k < n) out[base + k] = run;
@@ -333,7 +288,7 @@ __global__ __launch_bounds__(LIO_SORT_THREADS) void k_scan_sort_radix(const unsi
     __shared__ volatile int s_cnt[WAVES][256];             // per wave and digit: keys seen so far in this pass
     __shared__ int s_base[WAVES][256];                     // position of the first key of (digit, wave)
     __shared__ int s_dig[256];
-    __shared__ float s_mn[WAVES][3], s_mx[WAVES][3];
+    __shared__ LioWgBoxLds<WAVES> s_box;
     __shared__ float s_o[4];
     __shared__ int s_nt[7];
     const int scan = blockIdx.x;
@@ -352,24 +307,11 @@ __global__ __launch_bounds__(LIO_SORT_THREADS) void k_scan_sort_radix(const unsi
             if (fabsf(v) <= 3.0e38f) { mn[a] = fminf(mn[a], v); mx[a] = fmaxf(mx[a], v); }
         }
     }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            mn[a] = fminf(mn[a], __shfl_xor(mn[a], off));
-            mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], off));
-        }
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { s_mn[wave][a] = mn[a]; s_mx[wave][a] = mx[a]; }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
+    lio_wg_box_stage(mn, mx, s_box);
+    if (threadIdx.x == 0) {                                 // (one thread folds all three axes: it lays out the tile grid)
         float lo[3], hi[3];
         for (int a = 0; a < 3; ++a) {
-            lo[a] = s_mn[0][a]; hi[a] = s_mx[0][a];
-            for (int w = 1; w < WAVES; ++w) { lo[a] = fminf(lo[a], s_mn[w][a]); hi[a] = fmaxf(hi[a], s_mx[w][a]); }
+            lio_wg_box_axis(s_box, a, lo[a], hi[a]);
             if (!(lo[a] <= hi[a])) { lo[a] = 0.0f; hi[a] = 0.0f; }
         }
         float tile = tile0, inv_tile;
@@ -446,9 +388,7 @@ __global__ __launch_bounds__(LIO_SORT_THREADS) void k_scan_sort_radix(const unsi
         if (threadIdx.x < 256) {
 #pragma unroll
             for (int w = 0; w < WAVES; ++w) tot += s_cnt[w][threadIdx.x];
-            incl = tot;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) { const int v = __shfl_up(incl, off); if (lane >= off) incl += v; }
+            incl = lio_wave_inclusive_scan(tot);
             if (lane == 63) s_dig[wave] = incl;
         }
         __syncthreads();
@@ -499,25 +439,11 @@ __global__ __launch_bounds__(256) void k_scan_bbox(const unsigned char* __restri
             if (fabsf(v) <= 3.0e38f) { mn[a] = v; mx[a] = v; }
         }
     }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            mn[a] = fminf(mn[a], __shfl_xor(mn[a], off));
-            mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], off));
-        }
-    }
-    __shared__ float s_mn[4][3], s_mx[4][3];
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { s_mn[wave][a] = mn[a]; s_mx[wave][a] = mx[a]; }
-    }
-    __syncthreads();
+    __shared__ LioWgBoxLds<4> s_box;
+    float lo, hi;
+    lio_wg_box(mn, mx, s_box, lo, hi);
     if (threadIdx.x < 3) {
         const int a = threadIdx.x;
-        float lo = s_mn[0][a], hi = s_mx[0][a];
-        for (int w = 1; w < 4; ++w) { lo = fminf(lo, s_mn[w][a]); hi = fmaxf(hi, s_mx[w][a]); }
         if (lo <= hi) {
             atomicMin(&bbox[bd.scan * 6 + a], lio_f2ord(lo));
             atomicMax(&bbox[bd.scan * 6 + 3 + a], lio_f2ord(hi));
@@ -677,25 +603,11 @@ __global__ __launch_bounds__(LIO_BLOCK) void k_block_boxes(const LioBlockDesc* _
 #pragma unroll
         for (int a = 0; a < 3; ++a) if (fabsf(v[a]) <= 3.0e38f) { mn[a] = v[a]; mx[a] = v[a]; }
     }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            mn[a] = fminf(mn[a], __shfl_xor(mn[a], off));
-            mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], off));
-        }
-    }
-    __shared__ float s_mn[LIO_BLOCK / 64][3], s_mx[LIO_BLOCK / 64][3];
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { s_mn[wave][a] = mn[a]; s_mx[wave][a] = mx[a]; }
-    }
-    __syncthreads();
+    __shared__ LioWgBoxLds<LIO_BLOCK / 64> s_box;
+    float lo, hi;
+    lio_wg_box(mn, mx, s_box, lo, hi);
     if (threadIdx.x < 3) {
         const int a = threadIdx.x;
-        float lo = s_mn[0][a], hi = s_mx[0][a];
-        for (int w = 1; w < LIO_BLOCK / 64; ++w) { lo = fminf(lo, s_mn[w][a]); hi = fmaxf(hi, s_mx[w][a]); }
         float* o = box + (size_t)((base + bd.first) / LIO_BLOCK + bd.scan) * 6;
         o[a] = lo; o[3 + a] = hi;
     }
@@ -1011,7 +923,7 @@ __global__ __launch_bounds__(LIO_BLOCK, (PPT == 1 && !STAGE && !CORNER) ? LIO_MI
                 s_row_beg[threadIdx.x] = b;
             }
             int total;
-            const int off = lio_block_exclusive_scan(cnt, &total, s_scan4);
+            const int off = lio_wg_exclusive_scan<LIO_BLOCK / 64>(cnt, &total, s_scan4);
             if ((int)threadIdx.x < n_rows) s_row_off[threadIdx.x] = off;
             if ((int)threadIdx.x == n_rows) s_row_off[n_rows] = total;
             fits = total <= LIO_LDS_PTS;

@@ -65,12 +65,6 @@ __global__ void k_aos_to_xyzi4(const unsigned char* __restrict__ src, size_t str
     dst[i] = make_float4(p[0], p[1], p[2], p[4]);
 }
 
-__device__ __forceinline__ unsigned lio_f2ord2(float f)
-{
-    const unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 // getMinMax3D (PCL): bbox[0..2] = min, bbox[3..5] = max as order-preserving uints
 __global__ void k_vox_bbox(const float4* __restrict__ p, int n, unsigned* __restrict__ bbox)
 {
@@ -81,25 +75,13 @@ __global__ void k_vox_bbox(const float4* __restrict__ p, int n, unsigned* __rest
         mn[1] = fminf(mn[1], v.y); mx[1] = fmaxf(mx[1], v.y);
         mn[2] = fminf(mn[2], v.z); mx[2] = fmaxf(mx[2], v.z);
     }
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            mn[a] = fminf(mn[a], __shfl_xor(mn[a], off));
-            mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], off));
-        }
-    __shared__ float s_mn[4][3], s_mx[4][3];          // one set of atomics per workgroup
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { s_mn[wave][a] = mn[a]; s_mx[wave][a] = mx[a]; }
-    __syncthreads();
+    __shared__ LioWgBoxLds<4> s_box;                  // one set of atomics per workgroup
+    float lo, hi;
+    lio_wg_box(mn, mx, s_box, lo, hi);
     if (threadIdx.x < 3) {
         const int a = threadIdx.x;
-        float lo = s_mn[0][a], hi = s_mx[0][a];
-        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) { lo = fminf(lo, s_mn[w][a]); hi = fmaxf(hi, s_mx[w][a]); }
-        atomicMin(&bbox[a], lio_f2ord2(lo));
-        atomicMax(&bbox[3 + a], lio_f2ord2(hi));
+        atomicMin(&bbox[a], lio_f2ord(lo));
+        atomicMax(&bbox[3 + a], lio_f2ord(hi));
     }
 }
 
@@ -121,23 +103,11 @@ __global__ __launch_bounds__(256) void k_transform_clouds_bbox(const float4* __r
         dst[d.first + li] = q;
         mn[0] = mx[0] = q.x; mn[1] = mx[1] = q.y; mn[2] = mx[2] = q.z;
     }
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            mn[a] = fminf(mn[a], __shfl_xor(mn[a], off));
-            mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], off));
-        }
-    __shared__ float s_mn[4][3], s_mx[4][3];
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { s_mn[wave][a] = mn[a]; s_mx[wave][a] = mx[a]; }
-    __syncthreads();
+    __shared__ LioWgBoxLds<4> s_box;
+    float lo, hi;
+    lio_wg_box(mn, mx, s_box, lo, hi);
     if (threadIdx.x < 3) {
         const int a = threadIdx.x;
-        float lo = s_mn[0][a], hi = s_mx[0][a];
-        for (int w = 1; w < 4; ++w) { lo = fminf(lo, s_mn[w][a]); hi = fmaxf(hi, s_mx[w][a]); }
         blk_box[(size_t)blockIdx.x * 6 + a] = lo;            // (+inf / -inf for an empty chunk)
         blk_box[(size_t)blockIdx.x * 6 + 3 + a] = hi;
     }
@@ -151,25 +121,13 @@ __global__ __launch_bounds__(256) void k_bbox_reduce(const float* __restrict__ b
     for (int i = threadIdx.x; i < n_blk; i += 256)
 #pragma unroll
         for (int a = 0; a < 3; ++a) { mn[a] = fminf(mn[a], blk_box[(size_t)i * 6 + a]); mx[a] = fmaxf(mx[a], blk_box[(size_t)i * 6 + 3 + a]); }
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            mn[a] = fminf(mn[a], __shfl_xor(mn[a], off));
-            mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], off));
-        }
-    __shared__ float s_mn[4][3], s_mx[4][3];
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { s_mn[wave][a] = mn[a]; s_mx[wave][a] = mx[a]; }
-    __syncthreads();
+    __shared__ LioWgBoxLds<4> s_box;
+    float lo, hi;
+    lio_wg_box(mn, mx, s_box, lo, hi);
     if (threadIdx.x < 3) {
         const int a = threadIdx.x;
-        float lo = s_mn[0][a], hi = s_mx[0][a];
-        for (int w = 1; w < 4; ++w) { lo = fminf(lo, s_mn[w][a]); hi = fmaxf(hi, s_mx[w][a]); }
-        bbox[a] = lo <= hi ? lio_f2ord2(lo) : 0xffffffffu;
-        bbox[3 + a] = lo <= hi ? lio_f2ord2(hi) : 0u;
+        bbox[a] = lo <= hi ? lio_f2ord(lo) : LIO_ORD_NO_MIN;
+        bbox[3 + a] = lo <= hi ? lio_f2ord(hi) : LIO_ORD_NO_MAX;
     }
 }
 
@@ -187,14 +145,6 @@ namespace {
 // B: LioTemp (pool temporaries, recycled when the call returns) or LioDevBytes (a workspace kept from one call to the next,
 // so that nothing has to be waited for before the call returns)
 template <class B> struct LioVoxWs { B bbox, large, pairs_a, pairs_b, hist, blk_heads, seg_start, d_no, row_total; };
-
-float ord2f(unsigned u)
-{
-    const unsigned v = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-    float f;
-    memcpy(&f, &v, 4);
-    return f;
-}
 
 // Room for sorting n pairs and summing their segments (ws) and for n centroids (out).
 template <class B>
@@ -244,7 +194,7 @@ static int vsort_centroids(const float4* d_in, const uint2* a, int n, B& out, hi
     int* d_no = ws.d_no.template as<int>();
     HIPCHK(hipMemsetAsync(d_no, 0, 2 * sizeof(int), s));                          // [0] voxels, [1] crowded voxels queued
     hipLaunchKernelGGL(k_vsort_head_count, dim3(n_hblk), dim3(256), 0, s, a, n, ws.blk_heads.template as<int>());
-    hipLaunchKernelGGL(k_vsort_scan_small, dim3(1), dim3(256), 0, s, ws.blk_heads.template as<int>(), n_hblk, d_no);
+    hipLaunchKernelGGL(k_wg_scan_in_place<4>, dim3(1), dim3(256), 0, s, ws.blk_heads.template as<int>(), n_hblk, d_no);
     hipLaunchKernelGGL(k_vsort_head_emit, dim3(n_hblk), dim3(256), 0, s, a, n, ws.blk_heads.template as<int>(), d_no, ws.seg_start.template as<int>());
     hipLaunchKernelGGL(k_vsort_centroid, dim3((n_hblk + 3) / 4), dim3(256), 0, s, d_in, a, n, ws.seg_start.template as<int>(),
                        ws.blk_heads.template as<int>(), n_hblk, d_no, out.template as<float4>(), ws.large.template as<int>(), d_no + 1);
@@ -292,7 +242,8 @@ int voxel_grid_device(const float4* d_in, int n, float leaf, B& out, int* n_out,
     B& bbox = ws.bbox;
     if (!have_box) {
         HIPCHK(bbox.alloc(6 * sizeof(unsigned)));
-        const unsigned init[6] = { 0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u };
+        unsigned init[6];
+        lio_ord_box_clear(init);
         HIPCHK(hipMemcpyAsync(bbox.p, init, sizeof(init), hipMemcpyHostToDevice, s));
         int nbb = (n + 1023) / 1024; if (nbb > 512) nbb = 512; if (nbb < 1) nbb = 1;
         hipLaunchKernelGGL(k_vox_bbox, dim3(nbb), dim3(256), 0, s, d_in, n, bbox.template as<unsigned>());
@@ -301,7 +252,7 @@ int voxel_grid_device(const float4* d_in, int n, float leaf, B& out, int* n_out,
     HIPCHK(hipMemcpyAsync(hb, bbox.p, sizeof(hb), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     float mn[3], mx[3];
-    for (int a = 0; a < 3; ++a) { mn[a] = ord2f(hb[a]); mx[a] = ord2f(hb[3 + a]); }
+    lio_ord_box_decode(hb, mn, mx);
     if (box) for (int a = 0; a < 3; ++a) { box[a] = mn[a]; box[3 + a] = mx[a]; }
     // (a box that is not finite -- inf coordinates, or no finite point at all -- is outside what PCL defines; such a cloud
     // takes the same way out as an overflowing index, deterministically)
@@ -675,15 +626,10 @@ static LioPoseTab pose_tab(lio_kf_store* st)
     return t;
 }
 
-__device__ __forceinline__ float lio_ord2f_dev(unsigned u)
-{
-    return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-}
-
 __global__ void k_nb_init(LioNbMeta* m)
 {
     m->n_sel = 0; m->recent_fail = -1;
-    for (int a = 0; a < 3; ++a) { m->box[a] = 0xffffffffu; m->box[3 + a] = 0u; }
+    lio_ord_box_clear(m->box);
     m->n_ids = 0; m->n_chunks = 0; m->total = 0ull;
 }
 
@@ -708,15 +654,12 @@ __global__ __launch_bounds__(256) void k_nb_select(LioPoseTab tab, int n, float 
     }
     const int n_hit = __popcll(__ballot(sel));
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        fail = max(fail, __shfl_xor(fail, off));
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { mn[a] = fminf(mn[a], __shfl_xor(mn[a], off)); mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], off)); }
-    }
+    for (int off = 32; off > 0; off >>= 1) fail = max(fail, __shfl_xor(fail, off));
+    lio_wave_box(mn, mx);
     if ((threadIdx.x & 63) == 0) {
         if (n_hit) {
             atomicAdd(&m->n_sel, n_hit);
-            for (int a = 0; a < 3; ++a) { atomicMin(&m->box[a], lio_f2ord2(mn[a])); atomicMax(&m->box[3 + a], lio_f2ord2(mx[a])); }
+            for (int a = 0; a < 3; ++a) { atomicMin(&m->box[a], lio_f2ord(mn[a])); atomicMax(&m->box[3 + a], lio_f2ord(mx[a])); }
         }
         if (fail >= 0) atomicMax(&m->recent_fail, fail);
     }
@@ -735,7 +678,7 @@ __global__ __launch_bounds__(256) void k_nb_voxkeys(LioPoseTab tab, int n, float
     const int n_sel = m->n_sel;
     if (j >= n_sel) { pairs[j] = make_uint2(0x80000000u | (unsigned)j, (unsigned)j); pts[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); return; }
     float mn[3], mx[3];
-    for (int a = 0; a < 3; ++a) { mn[a] = lio_ord2f_dev(m->box[a]); mx[a] = lio_ord2f_dev(m->box[3 + a]); }
+    lio_ord_box_decode(m->box, mn, mx);
     LioVsGrid g;
     long long n_keys = 0;
     const bool pass = lio_vs_grid_from_box(mn, mx, inv, &g, &n_keys) != 0;
@@ -778,27 +721,6 @@ __global__ __launch_bounds__(64) void k_nb_relabel(LioPoseTab tab, int n, const 
     if (o < n_vox) atomicMin(&cid[o], best);
 }
 
-// exclusive prefix over the workgroup (256 threads); *total receives the sum
-template <typename T>
-__device__ T nb_block_scan(T v, T* s_wave, T* total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    T incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const T t = __shfl_up(incl, off);
-        if (lane >= off) incl += t;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    T woff = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) { const T sw = s_wave[w]; if (w < wave) woff += sw; tot += sw; }
-    __syncthreads();
-    *total = tot;
-    return woff + incl - v;
-}
-
 // The list of MO:1535-1551 in order -- centroids (own coordinates, relabelled id), then i = last .. recent_fail + 1 --
 // minus the entries farther than R from the last key pose (MO:1562: sqrtf, strict >), compacted in order by ONE workgroup
 // with running prefix sums of the kept entries, their points and their 256-point chunks.
@@ -826,9 +748,9 @@ __global__ __launch_bounds__(256) void k_nb_compact(LioPoseTab tab, int n, float
         const int cnt = keep ? tab.cnt[id] : 0;
         int t_ids, t_ch;
         unsigned long long t_pts;
-        const int pos = run_ids + nb_block_scan<int>(keep ? 1 : 0, s_wi, &t_ids);
-        const int cb = run_ch + nb_block_scan<int>(keep ? (cnt + 255) / 256 : 0, s_wi, &t_ch);
-        const unsigned long long first = run_pts + nb_block_scan<unsigned long long>((unsigned long long)cnt, s_wl, &t_pts);
+        const int pos = run_ids + lio_wg_exclusive_scan<4>(keep ? 1 : 0, &t_ids, s_wi);
+        const int cb = run_ch + lio_wg_exclusive_scan<4>(keep ? (cnt + 255) / 256 : 0, &t_ch, s_wi);
+        const unsigned long long first = run_pts + lio_wg_exclusive_scan<4>((unsigned long long)cnt, &t_pts, s_wl);
         if (keep) {
             ids[pos] = id;
             LioKfDesc d;

@@ -10,7 +10,9 @@
 #include <string>
 
 #include "../../include/liogpu.h"
+#include "lio_kernels.h"
 #include "lio_pool.h"
+#include "lio_wg.h"
 
 #define LIO_DEV __device__ __forceinline__
 
@@ -152,33 +154,6 @@ __global__ __launch_bounds__(256) void k_deskew_flags(LioDeskewParams P, unsigne
     }
     __syncthreads();
     if (threadIdx.x == 0) blk_count[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-}
-
-// exclusive scan of the workgroup counts by one workgroup (<= a few thousand entries)
-__global__ __launch_bounds__(256) void k_deskew_scan(int* __restrict__ blk_count, int n_blk, int* __restrict__ total)
-{
-    __shared__ int s_wave[4];
-    int carry = 0;
-    for (int b = 0; b < n_blk; b += 256) {
-        const int i = b + threadIdx.x;
-        const int v = i < n_blk ? blk_count[i] : 0;
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        int incl = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int t = __shfl_up(incl, off);
-            if (lane >= off) incl += t;
-        }
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        int woff = 0, tot = 0;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) { const int s = s_wave[w]; if (w < wave) woff += s; tot += s; }
-        __syncthreads();
-        if (i < n_blk) blk_count[i] = carry + woff + incl - v;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) *total = carry;
 }
 
 // pass 2: deskew survivors and write them compacted, input order preserved (IP:611-613)
@@ -538,7 +513,7 @@ static int lio_deskew_impl(const lio_deskew_config* cfg, const void* pts, size_t
 
     int* misc = d_misc.as<int>();
     hipLaunchKernelGGL(k_deskew_flags, dim3(nb), dim3(256), 0, s, P, d_keep.as<unsigned char>(), d_cnt.as<int>(), misc);
-    hipLaunchKernelGGL(k_deskew_scan, dim3(1), dim3(256), 0, s, d_cnt.as<int>(), nb, misc + 1);
+    hipLaunchKernelGGL(k_wg_scan_in_place<4>, dim3(1), dim3(256), 0, s, d_cnt.as<int>(), nb, misc + 1);   // workgroup counts -> offsets
     const size_t lds = 64 + sizeof(double) * 4 * (size_t)(nt ? nt : 1);
     hipLaunchKernelGGL(k_deskew_emit, dim3(nb), dim3(256), lds, s, P, d_keep.as<unsigned char>(), d_cnt.as<int>(),
                        misc, d_out.as<unsigned char>(), out_stride);
@@ -581,9 +556,6 @@ try {
     HIPCHK(hipGetLastError());
     return LIO_OK;
 } LIO_CATCH
-
-void lio_launch_exclusive_scan(const int* in, int n, int* tile_sums, int* out, hipStream_t s);   // lio_kernels.hip
-int  lio_scan_tiles(int n_cells);
 
 extern "C" void lio_range_image_default_config(lio_range_image_config* c)
 {

@@ -6,28 +6,10 @@
 // neighbourhood-row starts).  out_a and out_b have n + 1 entries.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "lio_wg.h"
 
 #define LIO_S2_ITEMS 16
 #define LIO_S2_TILE (256 * LIO_S2_ITEMS)
-
-__device__ __forceinline__ unsigned long long lio_s2_block_exscan(unsigned long long v, unsigned long long* total, unsigned long long* s_wave)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned long long t = __shfl_up(incl, off);
-        if (lane >= off) incl += t;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    unsigned long long wave_off = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) { const unsigned long long q = s_wave[w]; if (w < wave) wave_off += q; tot += q; }
-    __syncthreads();
-    *total = tot;
-    return wave_off + incl - v;
-}
 
 template <bool NZ>
 __device__ __forceinline__ unsigned long long lio_s2_pack(const int* __restrict__ a, const int* __restrict__ b, int i)
@@ -49,22 +31,14 @@ static __global__ __launch_bounds__(256) void k_s2_tile_sums(const int* __restri
         if (i < n) acc += lio_s2_pack<NZ>(a, b, i);
     }
     unsigned long long tot;
-    lio_s2_block_exscan(acc, &tot, s_wave);
+    lio_wg_exclusive_scan<4>(acc, &tot, s_wave);
     if (threadIdx.x == 0) tile_sums[blockIdx.x] = tot;
 }
 
 static __global__ __launch_bounds__(256) void k_s2_tile_offsets(unsigned long long* __restrict__ tile_sums, int n_tiles)
 {
     __shared__ unsigned long long s_wave[4];
-    unsigned long long carry = 0;
-    for (int t = 0; t < n_tiles; t += 256) {
-        const int i = t + (int)threadIdx.x;
-        const unsigned long long v = i < n_tiles ? tile_sums[i] : 0ull;
-        unsigned long long tot;
-        const unsigned long long ex = lio_s2_block_exscan(v, &tot, s_wave);
-        if (i < n_tiles) tile_sums[i] = carry + ex;
-        carry += tot;
-    }
+    lio_wg_scan_in_place<4>(tile_sums, n_tiles, s_wave);
 }
 
 template <bool NZ>
@@ -85,7 +59,7 @@ static __global__ __launch_bounds__(256) void k_s2_apply(const int* __restrict__
 #pragma unroll
     for (int k = 0; k < LIO_S2_ITEMS; ++k) { v[k] = s_v[tid * 17 + k]; acc += v[k]; }
     unsigned long long tot;
-    unsigned long long run = tile_offsets[blockIdx.x] + lio_s2_block_exscan(acc, &tot, s_wave);
+    unsigned long long run = tile_offsets[blockIdx.x] + lio_wg_exclusive_scan<4>(acc, &tot, s_wave);
 #pragma unroll
     for (int k = 0; k < LIO_S2_ITEMS; ++k) {
         s_v[tid * 17 + k] = run;

@@ -19,6 +19,7 @@
 // a prefix over the four waves -- no atomics, no sort inside the tile, deterministic.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "lio_wg.h"
 
 #define LIO_VS_THREADS 256
 #define LIO_VS_BINS 256
@@ -87,56 +88,9 @@ __global__ __launch_bounds__(LIO_VS_THREADS) void k_vsort_hist(const uint2* __re
 // flattened table with one workgroup: 160 k entries, strided reads -- ~50 us per pass for the 1.3 M-point map.)
 __global__ __launch_bounds__(256) void k_vsort_scan_rows(int* __restrict__ hist, int n_blocks, int* __restrict__ row_total)
 {
-    __shared__ int s_wave[4];
-    int* row = hist + (size_t)blockIdx.x * n_blocks;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int carry = 0;
-    for (int b = 0; b < n_blocks; b += 256) {
-        const int i = b + threadIdx.x;
-        const int v = i < n_blocks ? row[i] : 0;
-        int incl = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int t = __shfl_up(incl, off);
-            if (lane >= off) incl += t;
-        }
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        int woff = 0, tot = 0;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) { const int sw = s_wave[w]; if (w < wave) woff += sw; tot += sw; }
-        __syncthreads();
-        if (i < n_blocks) row[i] = carry + woff + incl - v;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) row_total[blockIdx.x] = carry;
-}
-
-// exclusive scan of `n` ints in place by ONE workgroup (the per-workgroup head counts: n / 1024 entries); *total receives the sum
-__global__ __launch_bounds__(256) void k_vsort_scan_small(int* __restrict__ a, int n, int* __restrict__ total)
-{
-    __shared__ int s_wave[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int carry = 0;
-    for (int b = 0; b < n; b += 256) {
-        const int i = b + threadIdx.x;
-        const int v = i < n ? a[i] : 0;
-        int incl = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int t = __shfl_up(incl, off);
-            if (lane >= off) incl += t;
-        }
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        int woff = 0, tot = 0;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) { const int sw = s_wave[w]; if (w < wave) woff += sw; tot += sw; }
-        __syncthreads();
-        if (i < n) a[i] = carry + woff + incl - v;
-        carry += tot;
-    }
-    if (total && threadIdx.x == 0) *total = carry;
+    __shared__ int s_scan[4];
+    const int sum = lio_wg_scan_in_place<4>(hist + (size_t)blockIdx.x * n_blocks, n_blocks, s_scan);
+    if (threadIdx.x == 0) row_total[blockIdx.x] = sum;
 }
 
 // Stable scatter of one pass.  rank of an item = (items of the same digit in earlier workgroups: the scanned table) +

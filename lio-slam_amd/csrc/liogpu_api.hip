@@ -14,6 +14,7 @@
 
 #include "lio_handle.h"
 #include "lio_multi.h"
+#include "lio_wg.h"
 
 
 static thread_local char g_last_error[512];   // (a fixed buffer: recording an allocation failure allocates nothing)
@@ -192,14 +193,6 @@ try {
     return LIO_OK;
 } LIO_CATCH
 
-static float lio_ord2f(unsigned u)
-{
-    unsigned v = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-    float f;
-    memcpy(&f, &v, 4);
-    return f;
-}
-
 static const lio_s2m_handle* lio_map_of(const lio_s2m_handle* h) { return h->map_src ? h->map_src : h; }
 
 // ------------------------------------------------------------------ set_map
@@ -230,16 +223,18 @@ static int lio_map_finish(lio_s2m_handle* h, size_t n, std::chrono::steady_clock
     if (box) {
         for (int a = 0; a < 3; ++a) { mn[a] = n ? box[a] : 0.0f; mx[a] = n ? box[3 + a] : 0.0f; }
     } else {
-        unsigned init[6] = { 0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u };
+        unsigned init[6];
+        lio_ord_box_clear(init);
         HIPCHK(hipMemcpyAsync(h->d_bbox, init, sizeof(init), hipMemcpyHostToDevice, h->stream));
         if (n) lio_launch_map_bbox(h->d_mx, h->d_my, h->d_mz, (int)n, h->d_bbox, h->stream);
         unsigned hb[6];
         HIPCHK(hipMemcpyAsync(hb, h->d_bbox, sizeof(hb), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
-        bool empty = (n == 0) || hb[0] == 0xffffffffu;
+        lio_ord_box_decode(hb, mn, mx);
+        bool empty = (n == 0) || hb[0] == LIO_ORD_NO_MIN;
         // (a map without a single finite point leaves the reduction at its identities, max < min: an empty grid, every point outside it)
-        for (int a = 0; a < 3 && !empty; ++a) empty = !(lio_ord2f(hb[a]) <= lio_ord2f(hb[3 + a]));
-        for (int a = 0; a < 3; ++a) { mn[a] = empty ? 0.0f : lio_ord2f(hb[a]); mx[a] = empty ? 0.0f : lio_ord2f(hb[3 + a]); }
+        for (int a = 0; a < 3 && !empty; ++a) empty = !(mn[a] <= mx[a]);
+        for (int a = 0; a < 3 && empty; ++a) mn[a] = mx[a] = 0.0f;
     }
 
     auto t1 = std::chrono::steady_clock::now();
@@ -800,7 +795,7 @@ try {
         HIPCHK(h->d_scan_bbox.grow((size_t)n_scans * 6));
         HIPCHK(h->h_scan_bbox.grow((size_t)n_scans * 6, (size_t)n_scans * 6 + 64));
         for (int s = 0; s < n_scans; ++s)
-            for (int a = 0; a < 6; ++a) h->h_scan_bbox[s * 6 + a] = a < 3 ? 0xffffffffu : 0u;
+            lio_ord_box_clear(&h->h_scan_bbox[s * 6]);
         HIPCHK(hipMemcpyAsync(h->d_scan_bbox, h->h_scan_bbox, (size_t)n_scans * 6 * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipMemcpyAsync(h->d_prep_blocks, prep.data(), prep.size() * sizeof(LioBlockDesc), hipMemcpyHostToDevice, h->stream));
         lio_launch_scan_bbox(stage, stride, h->d_prep_blocks, (int)prep.size(), h->d_state, h->d_scan_bbox, h->stream);
@@ -812,7 +807,7 @@ try {
             float mn[3], mx[3];
             for (int a = 0; a < 3; ++a) {
                 const unsigned lo = h->h_scan_bbox[s * 6 + a], hi = h->h_scan_bbox[s * 6 + 3 + a];
-                const bool none = lo == 0xffffffffu;
+                const bool none = lo == LIO_ORD_NO_MIN;
                 mn[a] = none ? 0.0f : lio_ord2f(lo);
                 mx[a] = none ? 0.0f : lio_ord2f(hi);
             }
