@@ -81,6 +81,24 @@ int main(int argc, char** argv)
         std::printf("multi iters %d pose %.9g %.9g %.9g %.9g %.9g %.9g\n", multi.last.iters, multi.transformTobeMapped[0],
                     multi.transformTobeMapped[1], multi.transformTobeMapped[2], multi.transformTobeMapped[3],
                     multi.transformTobeMapped[4], multi.transformTobeMapped[5]);
+
+        // ---- performRSLoopClosure MO:1098-1143 from the resident keyframes: the scan registered above becomes keyframe 0 twice
+        //      (two visits of the same place), then the loop-closure ICP between them; with one small keyframe per submap the
+        //      size guards of MO:1104 are what a real node would hit, so they are lowered here
+        liogpu::KeyframeStore store;
+        store.addFromHandle(s2m, s2m.transformTobeMapped, 0.0);
+        store.addFromHandle(s2m, s2m.transformTobeMapped, 100.0);
+        int32_t loopKeyCur = -1, loopKeyPre = -1;
+        if (store.detectLoopClosureDistance(15.0f, 30.0, 100.0, &loopKeyCur, &loopKeyPre)) {                       // MO:1095
+            lio_icp_config icp;
+            lio_icp_default_config(&icp);
+            icp.min_source_points = 1; icp.min_target_points = 1;
+            lio_icp_result loop;
+            const bool ok = store.performLoopClosureICP(loopKeyCur, loopKeyPre, 25, 0.4f, loop, &icp);             // MO:1098-1143
+            std::printf("loop %d -> %d accepted %d iters %d fitness %.6g corrected pose %.9g %.9g %.9g %.9g %.9g %.9g\n", loopKeyCur, loopKeyPre,
+                        (int)ok, loop.iters, loop.fitness, loop.pose_corrected[0], loop.pose_corrected[1], loop.pose_corrected[2],
+                        loop.pose_corrected[3], loop.pose_corrected[4], loop.pose_corrected[5]);
+        }
     } catch (const liogpu::Error& e) {
         // hard errors (<0): the node falls back to its own CPU loop MO:1846-1859
         std::fprintf(stderr, "liogpu: %s (code %d)\n", e.what(), e.code);

@@ -517,6 +517,90 @@ int  lio_assemble_map_nearby(lio_s2m_handle *h, lio_kf_store *s, const lio_nearb
                              int32_t *ids_out, int32_t ids_cap, int32_t *n_ids, void *out, size_t out_stride_bytes,
                              size_t out_cap, size_t *n_out);
 
+/* ------------------------------------------------ loop-closure registration (performRSLoopClosure MO:1098-1143) */
+/* pcl::IterativeClosestPoint<PointType, PointType> as MO:1110-1124 sets it up (no rejectors: setRANSACIterations(0) adds
+ * none; TransformationEstimationSVD; DefaultConvergenceCriteria), its getFitnessScore and the corrected pose MO:1136-1143,
+ * on the device.  DESIGN.md section 2 states what is defined here where PCL is not a function of its inputs (ties, the
+ * order of sums, the thresholds below: parity unpinned, restated from memory).  Out-of-range values are refused with
+ * LIO_ERR_ARG, never clamped. */
+#define LIO_ICP_MAX_ITERS 1000
+enum {                                  /* lio_icp_result.state = DefaultConvergenceCriteria::ConvergenceState */
+    LIO_ICP_NOT_CONVERGED      = 0,
+    LIO_ICP_ITERATIONS         = 1,
+    LIO_ICP_TRANSFORM          = 2,
+    LIO_ICP_ABS_MSE            = 3,
+    LIO_ICP_REL_MSE            = 4,
+    LIO_ICP_NO_CORRESPONDENCES = 5
+};
+typedef struct lio_icp_config {
+    double  max_corr_dist;      /* 30.0     setMaxCorrespondenceDistance: historyKeyframeSearchRadius * 2, MO:1112 (yaml: 15.0) */
+    double  transform_eps;      /* 1e-6     setTransformationEpsilon MO:1114: bound on |t_step|^2                                 */
+    double  fitness_eps;        /* 1e-6     setEuclideanFitnessEpsilon MO:1115: bound on |mse - mse_prev| (ABS_MSE)               */
+    double  rel_mse_eps;        /* 1e-5     bound on |mse - mse_prev| / mse_prev (REL_MSE); PCL 1.10 default                      */
+    double  rotation_threshold; /* 0.99999  bound on cos(angle of the step) = 0.5 (trace R - 1); PCL 1.10 default                 */
+    double  fitness_max;        /* 0.3      historyKeyframeFitnessScore UT:324: accepted = converged && fitness <= fitness_max    */
+    int32_t max_iters;          /* 100      setMaximumIterations MO:1113 (<= LIO_ICP_MAX_ITERS)                                   */
+    int32_t min_corr;           /* 3        fewer correspondences end the loop unconverged; PCL 1.10 default                      */
+    int32_t max_similar;        /* 0        consecutive "similar" iterations before a threshold counts; PCL 1.10 default          */
+    int32_t min_source_points;  /* 300      MO:1104 (lio_kf_store_loop_icp only)                                                  */
+    int32_t min_target_points;  /* 1000     MO:1104                                                                               */
+    int32_t lookahead;          /* iterations enqueued ahead of the look at the done flag; 0 = auto (4)                           */
+} lio_icp_config;
+
+typedef struct lio_icp_result {
+    int32_t status;             /* what the call returned                                                                   */
+    int32_t converged;          /* icp.hasConverged()                                                                       */
+    int32_t state;              /* LIO_ICP_*                                                                                */
+    int32_t iters;              /* nr_iterations_                                                                           */
+    int32_t n_corr_last;        /* correspondences of the last executed iteration                                           */
+    int32_t accepted;           /* converged && fitness <= fitness_max, MO:1124                                             */
+    int32_t n_source, n_target; /* points of the two clouds that were aligned                                               */
+    int32_t n_launches;         /* kernel launches of the loop and the fitness pass (those that exited at once included)    */
+    int32_t pad;
+    double  fitness;            /* icp.getFitnessScore(); DBL_MAX when no source point found a neighbour                    */
+    float   T[16];              /* icp.getFinalTransformation(), row-major                                                  */
+    float   pose_corrected[6];  /* [roll,pitch,yaw,x,y,z] of T * tWrong, MO:1140-1143 (lio_kf_store_loop_icp only, else 0)  */
+} lio_icp_result;
+
+/* Optional clouds of lio_kf_store_loop_icp: the two submaps (cureKeyframeCloud, prevKeyframeCloud) and closed_cloud
+ * (MO:1131), PointXYZI-compatible records of `stride` bytes.  A null pointer skips that cloud; cap_* = records it holds;
+ * n_* = records needed (written always).  A cloud that does not fit: LIO_ERR_ARG with the needed counts, nothing aligned. */
+typedef struct lio_icp_clouds {
+    void  *source, *target, *closed;
+    size_t cap_source, cap_target, cap_closed;
+    size_t n_source, n_target, n_closed;
+    size_t stride;
+} lio_icp_clouds;
+
+void lio_icp_default_config(lio_icp_config *cfg);
+/* icp.setInputSource(source); icp.setInputTarget(target); icp.align(unused, guess); icp.getFitnessScore() on two host
+ * clouds (x,y,z @0,4,8; strides >= 12, multiples of 4).  guess: 16 floats row-major, or NULL for the identity.  Non-finite
+ * points of either cloud are skipped.  An empty cloud: LIO_OK, state NO_CORRESPONDENCES, converged 0, T = guess. */
+int  lio_icp_align(int32_t device_id, const void *source, size_t n_source, size_t source_stride,
+                   const void *target, size_t n_target, size_t target_stride,
+                   const lio_icp_config *cfg, const float *guess, lio_icp_result *result);
+/* MO:1098-1143 in one call, from the resident clouds and the stored poses (lio_kf_store_set_poses): the source submap is
+ * keyframe key_cur, the target submap the keyframes key_pre - search_num .. key_pre + search_num that the store holds
+ * (loopFindNearKeyframes MO:1360-1383: transform, sum, VoxelGrid at `leaf` = loopClosureICPSurfLeafSize; the same K6 + K7
+ * code as lio_assemble_map_resident, bit for bit).  pose_index = -1: every keyframe under its own pose; >= 0: every
+ * keyframe under the pose of that one keyframe.  Fewer than min_source_points / min_target_points (MO:1104): returns
+ * LIO_TOO_FEW_POINTS, nothing aligned.  Then the alignment, the fitness score and pose_corrected.  Neither submap visits
+ * the host unless `clouds` (may be NULL) asks for it. */
+int  lio_kf_store_loop_icp(lio_kf_store *s, int32_t key_cur, int32_t key_pre, int32_t search_num, int32_t pose_index,
+                           float leaf, const lio_icp_config *cfg, lio_icp_result *result, lio_icp_clouds *clouds);
+/* detectLoopClosureDistance MO:1271-1304 over the stored poses (host only): the key poses with d2 < radius^2 around the
+ * last one, ordered by (d2, index); the first whose |time - time_cur| > time_diff is *key_pre, *key_cur = the last key.
+ * Returns 1 when found, 0 when none is or when it is the last key itself (the loopIndexContainer lookup MO:1277 stays with
+ * the caller), LIO_ERR_ARG when a keyframe has no pose or time. */
+int  lio_kf_store_detect_loop(lio_kf_store *s, float radius, double time_diff, double time_cur, int32_t *key_cur, int32_t *key_pre);
+/* Test hook: lio_icp_align that also returns, per executed iteration k < *n_trace, the step transformation (steps[k][16]),
+ * the number of correspondences and their mean squared distance, and the correspondence (target index, -1 = none) of every
+ * source point at iteration rec_iter (-1 = none).  Arrays of cfg->max_iters entries; corr of n_source; any may be NULL. */
+int  lio_icp_debug_trace(int32_t device_id, const void *source, size_t n_source, size_t source_stride,
+                         const void *target, size_t n_target, size_t target_stride,
+                         const lio_icp_config *cfg, const float *guess, int32_t rec_iter, lio_icp_result *result,
+                         float *steps, int32_t *n_corr, double *mse, int32_t *corr, int32_t *n_trace);
+
 #ifdef __cplusplus
 }
 #endif

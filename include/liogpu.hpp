@@ -155,6 +155,26 @@ public:
                                       nullptr, 0, 0, &n_map), "lio_assemble_map_nearby");
         return n_map;
     }
+    // detectLoopClosureDistance MO:1271-1304 over the stored poses; false: no loop candidate
+    bool detectLoopClosureDistance(float historyKeyframeSearchRadius, double historyKeyframeSearchTimeDiff, double timeLaserInfoCur,
+                                   int32_t* latestID, int32_t* closestID)
+    {
+        const int rc = lio_kf_store_detect_loop(s_, historyKeyframeSearchRadius, historyKeyframeSearchTimeDiff, timeLaserInfoCur, latestID,
+                                                closestID);
+        check(rc, "lio_kf_store_detect_loop");
+        return rc == 1;
+    }
+    // performRSLoopClosure MO:1098-1143: both submaps from the resident clouds, ICP, fitness score, corrected pose.
+    // Returns res.accepted (false also for the size guards of MO:1104); cfg == nullptr: the literals of MO:1112-1115.
+    bool performLoopClosureICP(int32_t loopKeyCur, int32_t loopKeyPre, int32_t historyKeyframeSearchNum, float loopClosureICPSurfLeafSize,
+                               lio_icp_result& res, const lio_icp_config* cfg = nullptr, int32_t pose_index = -1)
+    {
+        lio_icp_config c;
+        if (cfg) c = *cfg; else lio_icp_default_config(&c);
+        check(lio_kf_store_loop_icp(s_, loopKeyCur, loopKeyPre, historyKeyframeSearchNum, pose_index, loopClosureICPSurfLeafSize, &c, &res,
+                                    nullptr), "lio_kf_store_loop_icp");
+        return res.accepted != 0;
+    }
     lio_kf_store* get() { return s_; }
 
 private:

@@ -9,10 +9,12 @@ from .api import (LioError, ScanToMap, S2MConfig, S2MResult, S2MProfile, DeskewC
                   lib_path, load_library, build_library, deskew, curvature, imu_deskew_info,
                   transform_update, pack_xyzirt, deskew_default_config, voxel_grid, assemble_map, KeyframeStore, STATUS_NAMES,
                   extract_features, FeatureConfig, range_image, RangeImageConfig, PinnedBuffer, DeviceBuffer, PC2Layout, deskew_pc2,
-                  NearbyConfig, nearby_default_config)
+                  NearbyConfig, nearby_default_config, IcpConfig, IcpResult, IcpClouds, ICP_STATES, icp_default_config, icp_align,
+                  icp_debug_trace)
 
 __all__ = ["LioError", "ScanToMap", "S2MConfig", "S2MResult", "S2MProfile", "DeskewConfig",
            "lib_path", "load_library", "build_library", "deskew", "curvature", "imu_deskew_info",
            "transform_update", "pack_xyzirt", "deskew_default_config", "voxel_grid", "assemble_map", "KeyframeStore", "STATUS_NAMES",
            "extract_features", "FeatureConfig", "range_image", "RangeImageConfig", "PinnedBuffer", "DeviceBuffer", "PC2Layout", "deskew_pc2",
-           "NearbyConfig", "nearby_default_config"]
+           "NearbyConfig", "nearby_default_config", "IcpConfig", "IcpResult", "IcpClouds", "ICP_STATES", "icp_default_config", "icp_align",
+           "icp_debug_trace"]

@@ -96,6 +96,30 @@ class FeatureConfig(C.Structure):
                 ("surfLeafSize", C.c_float), ("device_id", C.c_int32)]
 
 
+class IcpConfig(C.Structure):
+    """pcl::IterativeClosestPoint as MO:1110-1116 sets it up (include/liogpu.h lio_icp_config)."""
+    _fields_ = [("max_corr_dist", C.c_double), ("transform_eps", C.c_double), ("fitness_eps", C.c_double),
+                ("rel_mse_eps", C.c_double), ("rotation_threshold", C.c_double), ("fitness_max", C.c_double),
+                ("max_iters", C.c_int32), ("min_corr", C.c_int32), ("max_similar", C.c_int32),
+                ("min_source_points", C.c_int32), ("min_target_points", C.c_int32), ("lookahead", C.c_int32)]
+
+
+class IcpResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("converged", C.c_int32), ("state", C.c_int32), ("iters", C.c_int32),
+                ("n_corr_last", C.c_int32), ("accepted", C.c_int32), ("n_source", C.c_int32), ("n_target", C.c_int32),
+                ("n_launches", C.c_int32), ("pad", C.c_int32), ("fitness", C.c_double), ("T", C.c_float * 16),
+                ("pose_corrected", C.c_float * 6)]
+
+
+class IcpClouds(C.Structure):
+    _fields_ = [("source", C.c_void_p), ("target", C.c_void_p), ("closed", C.c_void_p),
+                ("cap_source", C.c_size_t), ("cap_target", C.c_size_t), ("cap_closed", C.c_size_t),
+                ("n_source", C.c_size_t), ("n_target", C.c_size_t), ("n_closed", C.c_size_t), ("stride", C.c_size_t)]
+
+
+ICP_STATES = {0: "NOT_CONVERGED", 1: "ITERATIONS", 2: "TRANSFORM", 3: "ABS_MSE", 4: "REL_MSE", 5: "NO_CORRESPONDENCES"}
+
+
 def lib_path():
     # LIOGPU_LIB: A/B-test another build of the same library (kernel experiments); default = the in-tree build
     return os.environ.get("LIOGPU_LIB") or os.path.join(_HERE, "libliogpu.so")
@@ -131,6 +155,7 @@ EXPORTS = [
     "lio_host_unregister", "lio_s2m_set_shard_plan", "lio_s2m_register_pc2", "lio_deskew_pc2", "lio_kf_store_add_device", "lio_kf_store_add_from_handle",
     "lio_s2m_register_raw", "lio_s2m_debug_persist_spin", "lio_device_alloc", "lio_device_free", "lio_device_upload",
     "lio_nearby_default_config", "lio_kf_store_set_poses", "lio_assemble_map_nearby", "lio_debug_plane_fit",
+    "lio_icp_default_config", "lio_icp_align", "lio_kf_store_loop_icp", "lio_kf_store_detect_loop", "lio_icp_debug_trace",
 ]
 
 
@@ -230,6 +255,13 @@ def load_library():
     L.lio_kf_store_set_poses.argtypes = [vp, i32, i32, C.POINTER(f32), C.POINTER(f64)]
     L.lio_assemble_map_nearby.argtypes = [vp, vp, C.POINTER(NearbyConfig), f64, f32, C.POINTER(i32), i32, C.POINTER(i32), vp, sz, sz,
                                           C.POINTER(sz)]
+    L.lio_icp_default_config.argtypes = [C.POINTER(IcpConfig)]
+    L.lio_icp_default_config.restype = None
+    L.lio_icp_align.argtypes = [i32, vp, sz, sz, vp, sz, sz, C.POINTER(IcpConfig), C.POINTER(f32), C.POINTER(IcpResult)]
+    L.lio_kf_store_loop_icp.argtypes = [vp, i32, i32, i32, i32, f32, C.POINTER(IcpConfig), C.POINTER(IcpResult), C.POINTER(IcpClouds)]
+    L.lio_kf_store_detect_loop.argtypes = [vp, f32, f64, f64, C.POINTER(i32), C.POINTER(i32)]
+    L.lio_icp_debug_trace.argtypes = [i32, vp, sz, sz, vp, sz, sz, C.POINTER(IcpConfig), C.POINTER(f32), i32, C.POINTER(IcpResult),
+                                      vp, vp, vp, vp, C.POINTER(i32)]
     _LIB = L
     return L
 
@@ -728,6 +760,55 @@ def nearby_default_config(**overrides):
     return cfg
 
 
+def icp_default_config(**overrides):
+    cfg = IcpConfig()
+    load_library().lio_icp_default_config(C.byref(cfg))
+    for k, v in overrides.items():
+        if not hasattr(cfg, k):
+            raise AttributeError(k)
+        setattr(cfg, k, v)
+    return cfg
+
+
+def _guess_ptr(guess):
+    if guess is None:
+        return None, None
+    g = np.ascontiguousarray(guess, np.float32).reshape(16)
+    return g, _f32p(g)
+
+
+# icp.align + icp.getFitnessScore, MO:1119-1124
+def icp_align(source, target, cfg=None, guess=None, device_id=0):
+    """-> (IcpResult, rc).  source / target: [n, >=3] float32."""
+    src, ss = _as_points(source)
+    tgt, ts = _as_points(target)
+    cfg = cfg or icp_default_config()
+    g, gp = _guess_ptr(guess)
+    res = IcpResult()
+    rc = _check(load_library().lio_icp_align(device_id, src.ctypes.data, len(src), ss, tgt.ctypes.data, len(tgt), ts, C.byref(cfg), gp,
+                                             C.byref(res)), "lio_icp_align")
+    return res, rc
+
+
+def icp_debug_trace(source, target, cfg=None, guess=None, rec_iter=-1, device_id=0):
+    """Test hook -> (IcpResult, steps [k,4,4], n_corr [k], mse [k], corr [n_source] of iteration rec_iter)."""
+    src, ss = _as_points(source)
+    tgt, ts = _as_points(target)
+    cfg = cfg or icp_default_config()
+    g, gp = _guess_ptr(guess)
+    res = IcpResult()
+    steps = np.zeros((cfg.max_iters, 16), np.float32)
+    n_corr = np.zeros(cfg.max_iters, np.int32)
+    mse = np.zeros(cfg.max_iters, np.float64)
+    corr = np.full(max(len(src), 1), -1, np.int32)
+    nt = C.c_int32()
+    _check(load_library().lio_icp_debug_trace(device_id, src.ctypes.data, len(src), ss, tgt.ctypes.data, len(tgt), ts, C.byref(cfg), gp,
+                                              rec_iter, C.byref(res), steps.ctypes.data, n_corr.ctypes.data, mse.ctypes.data,
+                                              corr.ctypes.data, C.byref(nt)), "lio_icp_debug_trace")
+    k = nt.value
+    return res, steps[:k].reshape(k, 4, 4).copy(), n_corr[:k].copy(), mse[:k].copy(), corr[:len(src)].copy()
+
+
 # extractCloud, MO:1556-1588
 def assemble_map(clouds_xyzi, poses, leaf, s2m=None, device_id=0, want_output=True):
     recs = [_as_xyzi_records(c) for c in clouds_xyzi]
@@ -811,6 +892,32 @@ class KeyframeStore:
             break
         return ((_from_records(out, n_out.value) if want_output else None), n_out.value,
                 (ids[:n_ids.value].copy() if want_ids else None), rc)
+
+    def loop_icp(self, key_cur, key_pre, search_num, leaf, cfg=None, pose_index=-1, want_clouds=False):
+        """performRSLoopClosure MO:1098-1143 on the device -> (IcpResult, rc, clouds or None); clouds = (source submap,
+        target submap, closed_cloud) as [n,4] arrays."""
+        cfg = cfg or icp_default_config()
+        res = IcpResult()
+        cl = None
+        if want_clouds:
+            pts = lambda k: int(self.lib.lio_kf_store_points(self.h, k))
+            cap_s = max(pts(key_cur), 1)
+            cap_t = max(sum(pts(k) for k in range(max(key_pre - search_num, 0), min(key_pre + search_num, len(self) - 1) + 1)), 1)
+            bufs = [np.zeros((cap_s, 8), np.float32), np.zeros((cap_t, 8), np.float32), np.zeros((cap_s, 8), np.float32)]
+            cl = IcpClouds(bufs[0].ctypes.data, bufs[1].ctypes.data, bufs[2].ctypes.data, cap_s, cap_t, cap_s, 0, 0, 0, 32)
+        rc = _check(self.lib.lio_kf_store_loop_icp(self.h, key_cur, key_pre, search_num, pose_index, leaf, C.byref(cfg), C.byref(res),
+                                                   C.byref(cl) if cl is not None else None), "lio_kf_store_loop_icp")
+        clouds = None
+        if want_clouds:
+            clouds = (_from_records(bufs[0], cl.n_source), _from_records(bufs[1], cl.n_target), _from_records(bufs[2], cl.n_closed))
+        return res, rc, clouds
+
+    def detect_loop(self, radius, time_diff, time_cur):   # detectLoopClosureDistance, MO:1271-1304
+        """-> (key_cur, key_pre) or None."""
+        kc, kp = C.c_int32(), C.c_int32()
+        rc = _check(self.lib.lio_kf_store_detect_loop(self.h, radius, time_diff, time_cur, C.byref(kc), C.byref(kp)),
+                    "lio_kf_store_detect_loop")
+        return (kc.value, kp.value) if rc == 1 else None
 
     def close(self):
         if getattr(self, "h", None) and self.h.value:

@@ -1,0 +1,23 @@
+// lio_icp.h -- what the entry points of the loop-closure registration (lio_mapbuild.hip) need from lio_icp.hip.
+#pragma once
+#include <hip/hip_runtime.h>
+#include "../../include/liogpu.h"
+
+// Optional per-iteration record of one alignment (lio_icp_debug_trace): host arrays, cfg.max_iters entries each
+// (step: 16 floats per entry), corr: n_src entries for iteration rec_iter.  Any pointer may be null.
+struct LioIcpTrace {
+    float* step = nullptr;
+    int32_t* n_corr = nullptr;
+    double* mse = nullptr;
+    int32_t* corr = nullptr;
+    int rec_iter = -1;
+    int n_trace = 0;          // out: entries written (the executed iterations, the one that found too few pairs included)
+};
+
+int lio_icp_check_config(const lio_icp_config* cfg);       // LIO_OK or LIO_ERR_ARG (lio_last_error says which field)
+
+// pcl::IterativeClosestPoint::align + getFitnessScore on two device-resident clouds (float4 x, y, z, anything), on stream
+// `s`; synchronous.  guess: 16 floats row-major or null.  d_closed (may be null, n_src entries): the source under the
+// final transformation, w kept.  Fills every field of *res but pose_corrected.
+int lio_icp_device(const float4* d_src, int n_src, const float4* d_tgt, int n_tgt, const lio_icp_config& cfg,
+                   const float* guess, lio_icp_result* res, hipStream_t s, LioIcpTrace* trace, float4* d_closed);

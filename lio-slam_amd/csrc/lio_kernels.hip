@@ -1203,6 +1203,19 @@ void lio_launch_map_build(const LioGrid& g, const float* x, const float* y, cons
                            nbr_slot + (size_t)n * (repsA + repsB * l), nbr_pts);
 }
 
+// The cell-sorted copy alone -- counts, starts, scatter -- for a search that walks cells itself (lio_icp.hip).
+// cell_count: n_cells ints; cell_start: n_cells + 1; tile_sums: lio_scan_tiles(n_cells) + 1 ints.
+void lio_launch_map_cell_sort(const LioGrid& g, const float* x, const float* y, const float* z, int n, int* cell_of, int* cell_count,
+                              int* cell_start, int* tile_sums, float4* sorted, hipStream_t s)
+{
+    const int nb = (n + 255) / 256;
+    (void)hipMemsetAsync(cell_count, 0, sizeof(int) * (size_t)g.n_cells, s);
+    hipLaunchKernelGGL(k_map_cell_count, dim3(nb), dim3(256), 0, s, g, x, y, z, n, cell_of, cell_count);
+    lio_launch_exclusive_scan(cell_count, g.n_cells, tile_sums, cell_start, s);
+    (void)hipMemsetAsync(cell_count, 0, sizeof(int) * (size_t)g.n_cells, s);          // reused as the fill cursor
+    hipLaunchKernelGGL(k_map_scatter, dim3(nb), dim3(256), 0, s, x, y, z, n, cell_of, cell_start, cell_count, sorted);
+}
+
 int lio_scan_tiles(int n_cells) { return (n_cells + LIO_SCAN_TILE - 1) / LIO_SCAN_TILE; }
 
 void lio_launch_init_state(LioScanState* st, int n_scans, float* poses, bool from_state, const LioConsts& c,
