@@ -601,6 +601,74 @@ int  lio_icp_debug_trace(int32_t device_id, const void *source, size_t n_source,
                          const lio_icp_config *cfg, const float *guess, int32_t rec_iter, lio_icp_result *result,
                          float *steps, int32_t *n_corr, double *mse, int32_t *corr, int32_t *n_trace);
 
+/* ------------------------------------------------ Scan Context loop detection (performSCLoopClosure MO:1163-1269) */
+/* SCManager (Scancontext.cpp, "SC:") on the device: makeScancontext + the two keys of every keyframe, kept next to the
+ * resident keyframes (descriptor k = keyframe k), and detectLoopClosureID over them.  DESIGN.md section 4c states what is
+ * defined here where Eigen and nanoflann are not functions of their inputs (every sum in ascending index order, an exact
+ * brute-force ring-key search ordered by (distance, index); parity unpinned).  Out-of-range values are refused with
+ * LIO_ERR_ARG, never clamped. */
+#define LIO_SC_MAX_CELLS      4096   /* num_rings * num_sectors: what the kernels' LDS layout holds */
+#define LIO_SC_MAX_DIM        256    /* num_rings and num_sectors, each                              */
+#define LIO_SC_MAX_CANDIDATES 16
+typedef struct lio_sc_config {
+    double  max_radius;          /* 80.0  PC_MAX_RADIUS: points with sqrtf(x^2 + y^2) beyond it are dropped       */
+    double  lidar_height;        /* 2.0   LIDAR_HEIGHT, added to z                                                 */
+    double  search_ratio;        /* 0.1   SEARCH_RATIO: shifts within round(0.5 ratio S) of the sector-key shift, [0, 1] */
+    double  dist_thres;          /* 0.3   SC_DIST_THRES: a loop when min_dist < dist_thres                         */
+    int32_t num_rings;           /* 20    PC_NUM_RING   (<= LIO_SC_MAX_DIM; rings * sectors <= LIO_SC_MAX_CELLS)   */
+    int32_t num_sectors;         /* 60    PC_NUM_SECTOR                                                            */
+    int32_t num_exclude_recent;  /* 30    NUM_EXCLUDE_RECENT                                                       */
+    int32_t num_candidates;      /* 3     NUM_CANDIDATES_FROM_TREE (1 .. LIO_SC_MAX_CANDIDATES)                    */
+    int32_t tree_period;         /* 10    TREE_MAKING_PERIOD_ (>= 1)                                               */
+    int32_t pad;
+} lio_sc_config;
+
+typedef struct lio_sc_result {
+    int32_t status;              /* what the call returned                                                          */
+    int32_t loop_id;             /* detectLoopClosureID().first: the matched descriptor, -1 = no loop               */
+    int32_t align;               /* nn_align: the sector shift of the best candidate                                */
+    int32_t nn_idx;              /* the best candidate whether or not it passed the threshold                       */
+    int32_t n_searched;          /* descriptors [0, n_searched) were searched: the prefix of the last rebuild       */
+    int32_t n_candidates;        /* min(num_candidates, n_searched) entries of the arrays below are set             */
+    float   yaw_diff_rad;        /* detectLoopClosureID().second = deg2rad(align * 360 / num_sectors)               */
+    int32_t pad;
+    double  min_dist;            /* distance of nn_idx; 1e7 when nothing was compared                               */
+    int32_t cand_idx[LIO_SC_MAX_CANDIDATES];      /* candidates in (ring-key distance, index) order                 */
+    float   cand_ring_d2[LIO_SC_MAX_CANDIDATES];  /* their squared ring-key distances (fp32)                        */
+    double  cand_dist[LIO_SC_MAX_CANDIDATES];     /* distanceBtnScanContext().first; 1e7 = no common non-zero column  */
+    int32_t cand_align[LIO_SC_MAX_CANDIDATES];    /* distanceBtnScanContext().second                                */
+} lio_sc_result;
+
+void lio_sc_default_config(lio_sc_config *cfg);
+/* makeScancontext + makeRingkey / makeSectorkeyFromScancontext (SC:151-227) of one host cloud (x,y,z @0,4,8; stride >= 12,
+ * a multiple of 4): desc[num_rings * num_sectors] ring-major, ring_key[num_rings] (the float of polarcontext_invkeys_mat_),
+ * sector_key[num_sectors]; any may be NULL.  Non-finite points and points with x == 0 and y == 0 are skipped.  An empty
+ * cloud: all zeros, LIO_OK. */
+int  lio_sc_make(int32_t device_id, const void *cloud, size_t n, size_t stride_bytes, const lio_sc_config *cfg,
+                 float *desc, float *ring_key, double *sector_key);
+/* makeAndSaveScancontextAndKeys (MO:2149-2156 with SINGLE_SCAN_FULL): appends the descriptor of the next keyframe, from a
+ * host cloud, from device memory (x,y,z @0,4,8; stride >= 12, pointer and stride multiples of 4), or from the whole cloud that h's last lio_s2m_register_raw
+ * staged on the device -- no copy at all.  cfg == NULL: the geometry of the store's first descriptor (the defaults for the
+ * first one); a geometry that differs from the first descriptor's -> LIO_ERR_ARG.  id_out may be NULL. */
+int  lio_kf_store_sc_add(lio_kf_store *s, const void *cloud, size_t n, size_t stride_bytes, const lio_sc_config *cfg, int32_t *id_out);
+int  lio_kf_store_sc_add_device(lio_kf_store *s, const void *d_cloud, size_t n, size_t stride_bytes, const lio_sc_config *cfg,
+                                int32_t *id_out);
+int  lio_kf_store_sc_add_from_handle(lio_kf_store *s, lio_s2m_handle *h, const lio_sc_config *cfg, int32_t *id_out);
+int  lio_kf_store_sc_count(const lio_kf_store *s);
+/* num_rings / num_sectors of the store's descriptors (those of the first one); 0, 0 while it holds none. */
+int  lio_kf_store_sc_geometry(const lio_kf_store *s, int32_t *num_rings, int32_t *num_sectors);
+/* Descriptor `id` and its keys, sized as for lio_sc_make with the store's geometry (lio_kf_store_sc_geometry); any may be NULL. */
+int  lio_kf_store_sc_get(lio_kf_store *s, int32_t id, float *desc, float *ring_key, double *sector_key);
+/* detectLoopClosureID (SC:253-344): the query is the last descriptor.  Fewer than num_exclude_recent + 1 descriptors: LIO_OK,
+ * loop_id -1, yaw 0, nothing searched and the period counter untouched.  Otherwise the searchable prefix is refreshed to
+ * count - num_exclude_recent when the store's counter is a multiple of tree_period (a stale prefix in between is reference
+ * behaviour), the counter is incremented, and the num_candidates nearest ring keys of the prefix are compared.  The result
+ * feeds lio_kf_store_loop_icp(s, count - 1, loop_id, search_num, 0, ...) -- pose_index = 0 is loop_index = 0 of MO:1193-1194.
+ * cfg's num_rings / num_sectors must be the store's. */
+int  lio_kf_store_sc_detect(lio_kf_store *s, const lio_sc_config *cfg, lio_sc_result *result);
+/* Test hook: distanceBtnScanContext (SC:116-148) of two host descriptors (desc_a = _sc1, the query). */
+int  lio_sc_distance(int32_t device_id, const float *desc_a, const float *desc_b, const lio_sc_config *cfg, double *dist, int32_t *align);
+
 #ifdef __cplusplus
 }
 #endif

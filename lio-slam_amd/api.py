@@ -117,6 +117,23 @@ class IcpClouds(C.Structure):
                 ("n_source", C.c_size_t), ("n_target", C.c_size_t), ("n_closed", C.c_size_t), ("stride", C.c_size_t)]
 
 
+SC_MAX_CANDIDATES = 16
+
+
+class ScConfig(C.Structure):
+    """SCManager's constants, Scancontext.h:80-99 (include/liogpu.h lio_sc_config)."""
+    _fields_ = [("max_radius", C.c_double), ("lidar_height", C.c_double), ("search_ratio", C.c_double), ("dist_thres", C.c_double),
+                ("num_rings", C.c_int32), ("num_sectors", C.c_int32), ("num_exclude_recent", C.c_int32),
+                ("num_candidates", C.c_int32), ("tree_period", C.c_int32), ("pad", C.c_int32)]
+
+
+class ScResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("loop_id", C.c_int32), ("align", C.c_int32), ("nn_idx", C.c_int32),
+                ("n_searched", C.c_int32), ("n_candidates", C.c_int32), ("yaw_diff_rad", C.c_float), ("pad", C.c_int32),
+                ("min_dist", C.c_double), ("cand_idx", C.c_int32 * SC_MAX_CANDIDATES), ("cand_ring_d2", C.c_float * SC_MAX_CANDIDATES),
+                ("cand_dist", C.c_double * SC_MAX_CANDIDATES), ("cand_align", C.c_int32 * SC_MAX_CANDIDATES)]
+
+
 ICP_STATES = {0: "NOT_CONVERGED", 1: "ITERATIONS", 2: "TRANSFORM", 3: "ABS_MSE", 4: "REL_MSE", 5: "NO_CORRESPONDENCES"}
 
 
@@ -156,6 +173,8 @@ EXPORTS = [
     "lio_s2m_register_raw", "lio_s2m_debug_persist_spin", "lio_device_alloc", "lio_device_free", "lio_device_upload",
     "lio_nearby_default_config", "lio_kf_store_set_poses", "lio_assemble_map_nearby", "lio_debug_plane_fit",
     "lio_icp_default_config", "lio_icp_align", "lio_kf_store_loop_icp", "lio_kf_store_detect_loop", "lio_icp_debug_trace",
+    "lio_sc_default_config", "lio_sc_make", "lio_sc_distance", "lio_kf_store_sc_add", "lio_kf_store_sc_add_device",
+    "lio_kf_store_sc_add_from_handle", "lio_kf_store_sc_count", "lio_kf_store_sc_geometry", "lio_kf_store_sc_get", "lio_kf_store_sc_detect",
 ]
 
 
@@ -262,6 +281,18 @@ def load_library():
     L.lio_kf_store_detect_loop.argtypes = [vp, f32, f64, f64, C.POINTER(i32), C.POINTER(i32)]
     L.lio_icp_debug_trace.argtypes = [i32, vp, sz, sz, vp, sz, sz, C.POINTER(IcpConfig), C.POINTER(f32), i32, C.POINTER(IcpResult),
                                       vp, vp, vp, vp, C.POINTER(i32)]
+    scp = C.POINTER(ScConfig)
+    L.lio_sc_default_config.argtypes = [scp]
+    L.lio_sc_default_config.restype = None
+    L.lio_sc_make.argtypes = [i32, vp, sz, sz, scp, vp, vp, vp]
+    L.lio_sc_distance.argtypes = [i32, vp, vp, scp, C.POINTER(f64), C.POINTER(i32)]
+    L.lio_kf_store_sc_add.argtypes = [vp, vp, sz, sz, scp, C.POINTER(i32)]
+    L.lio_kf_store_sc_add_device.argtypes = [vp, vp, sz, sz, scp, C.POINTER(i32)]
+    L.lio_kf_store_sc_add_from_handle.argtypes = [vp, vp, scp, C.POINTER(i32)]
+    L.lio_kf_store_sc_count.argtypes = [vp]
+    L.lio_kf_store_sc_geometry.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+    L.lio_kf_store_sc_get.argtypes = [vp, i32, vp, vp, vp]
+    L.lio_kf_store_sc_detect.argtypes = [vp, scp, C.POINTER(ScResult)]
     _LIB = L
     return L
 
@@ -809,6 +840,38 @@ def icp_debug_trace(source, target, cfg=None, guess=None, rec_iter=-1, device_id
     return res, steps[:k].reshape(k, 4, 4).copy(), n_corr[:k].copy(), mse[:k].copy(), corr[:len(src)].copy()
 
 
+def sc_default_config(**overrides):
+    cfg = ScConfig()
+    load_library().lio_sc_default_config(C.byref(cfg))
+    for k, v in overrides.items():
+        if not hasattr(cfg, k):
+            raise AttributeError(k)
+        setattr(cfg, k, v)
+    return cfg
+
+
+# scManager.makeAndSaveScancontextAndKeys without the store, SC:236-246
+def sc_make(cloud, cfg=None, device_id=0):
+    """-> (desc [rings, sectors] float32, ring_key [rings] float32, sector_key [sectors] float64).  cloud: [n, >=3] float32."""
+    pts, stride = _as_points(cloud)
+    cfg = cfg or sc_default_config()
+    R, S = max(cfg.num_rings, 1), max(cfg.num_sectors, 1)
+    desc, rk, sk = np.zeros((R, S), np.float32), np.zeros(R, np.float32), np.zeros(S, np.float64)
+    _check(load_library().lio_sc_make(device_id, pts.ctypes.data, len(pts), stride, C.byref(cfg), desc.ctypes.data, rk.ctypes.data,
+                                      sk.ctypes.data), "lio_sc_make")
+    return desc, rk, sk
+
+
+def sc_distance(desc_a, desc_b, cfg=None, device_id=0):
+    """Test hook: distanceBtnScanContext SC:116-148 -> (dist, align)."""
+    cfg = cfg or sc_default_config()
+    a = np.ascontiguousarray(desc_a, np.float32).reshape(cfg.num_rings, cfg.num_sectors)
+    b = np.ascontiguousarray(desc_b, np.float32).reshape(cfg.num_rings, cfg.num_sectors)
+    d, al = C.c_double(), C.c_int32()
+    _check(load_library().lio_sc_distance(device_id, a.ctypes.data, b.ctypes.data, C.byref(cfg), C.byref(d), C.byref(al)), "lio_sc_distance")
+    return d.value, al.value
+
+
 # extractCloud, MO:1556-1588
 def assemble_map(clouds_xyzi, poses, leaf, s2m=None, device_id=0, want_output=True):
     recs = [_as_xyzi_records(c) for c in clouds_xyzi]
@@ -918,6 +981,51 @@ class KeyframeStore:
         rc = _check(self.lib.lio_kf_store_detect_loop(self.h, radius, time_diff, time_cur, C.byref(kc), C.byref(kp)),
                     "lio_kf_store_detect_loop")
         return (kc.value, kp.value) if rc == 1 else None
+
+    # ---- Scan Context (performSCLoopClosure MO:1163-1269): descriptor k belongs to keyframe k
+    @staticmethod
+    def _sc_cfg(cfg):
+        return C.byref(cfg) if cfg is not None else None
+
+    def sc_add(self, cloud, cfg=None):               # scManager.makeAndSaveScancontextAndKeys, MO:2156
+        pts, stride = _as_points(cloud)
+        kid = C.c_int32()
+        _check(self.lib.lio_kf_store_sc_add(self.h, pts.ctypes.data, len(pts), stride, self._sc_cfg(cfg), C.byref(kid)), "lio_kf_store_sc_add")
+        return kid.value
+
+    def sc_add_device(self, dev_ptr, n, stride, cfg=None):
+        kid = C.c_int32()
+        _check(self.lib.lio_kf_store_sc_add_device(self.h, C.c_void_p(dev_ptr), n, stride, self._sc_cfg(cfg), C.byref(kid)),
+               "lio_kf_store_sc_add_device")
+        return kid.value
+
+    def sc_add_from_handle(self, s2m, cfg=None):     # the cloud s2m's last downsampleAndScan2MapOptimization staged, in place
+        kid = C.c_int32()
+        _check(self.lib.lio_kf_store_sc_add_from_handle(self.h, s2m.h, self._sc_cfg(cfg), C.byref(kid)), "lio_kf_store_sc_add_from_handle")
+        return kid.value
+
+    def sc_count(self):
+        return self.lib.lio_kf_store_sc_count(self.h)
+
+    def sc_geometry(self):
+        """-> (num_rings, num_sectors) of the store's descriptors; (0, 0) while it holds none."""
+        r, s = C.c_int32(), C.c_int32()
+        _check(self.lib.lio_kf_store_sc_geometry(self.h, C.byref(r), C.byref(s)), "lio_kf_store_sc_geometry")
+        return r.value, s.value
+
+    def sc_get(self, kid):
+        """-> (desc [rings, sectors], ring_key, sector_key) of descriptor kid, sized by the store's geometry."""
+        rings, sectors = self.sc_geometry()
+        desc, rk, sk = np.zeros((rings, sectors), np.float32), np.zeros(rings, np.float32), np.zeros(sectors, np.float64)
+        _check(self.lib.lio_kf_store_sc_get(self.h, kid, desc.ctypes.data, rk.ctypes.data, sk.ctypes.data), "lio_kf_store_sc_get")
+        return desc, rk, sk
+
+    def sc_detect(self, cfg=None):                   # scManager.detectLoopClosureID, MO:1175
+        """-> ScResult; loop_id = -1: no loop.  Then loop_icp(len(self) - 1, loop_id, search_num, leaf, pose_index=0)."""
+        cfg = cfg or sc_default_config()
+        res = ScResult()
+        _check(self.lib.lio_kf_store_sc_detect(self.h, C.byref(cfg), C.byref(res)), "lio_kf_store_sc_detect")
+        return res
 
     def close(self):
         if getattr(self, "h", None) and self.h.value:

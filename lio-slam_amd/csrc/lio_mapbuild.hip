@@ -14,6 +14,7 @@
 #include "lio_handle.h"
 #include "lio_icp.h"
 #include "lio_pool.h"
+#include "lio_sc.h"
 #include "lio_device_math.h"
 #include "lio_scan2.h"
 #include "lio_voxsort.h"
@@ -352,6 +353,7 @@ struct lio_kf_store {
     LioVoxWs<LioDevBytes> nws;
     LioDevBytes nb_pts, nb_cent, nb_cid, nb_ids, nb_meta;
     hipEvent_t ev_ids = nullptr;
+    LioScStore sc;                                   // the Scan Context descriptors (lio_sc.hip), descriptor k = keyframe k
 };
 
 extern "C" int lio_kf_store_create(int32_t device_id, lio_kf_store** out)
@@ -928,6 +930,8 @@ struct LioRawWs {
     // waits (bounding box, voxel count) no longer wait for the map as well
     hipStream_t aux = nullptr;
     hipEvent_t ev_in = nullptr, ev_done = nullptr;
+    size_t n_raw = 0;                                // points of the whole cloud in `xyzi` (written on `aux`)
+    bool has_raw = false;
 };
 
 void lio_raw_ws_free(LioRawWs* w) { delete w; }
@@ -959,6 +963,7 @@ try {
         HIPCHK(hipEventCreateWithFlags(&w->ev_done, hipEventDisableTiming));
     }
     hipStream_t s = w->aux;                              // upload + filter here; the registration on h->stream, behind the map
+    w->has_raw = false;
     const size_t step = layout->point_step, n = n_points;
     // the blob: read in place when it is device memory of this device, else one H2D copy (a true DMA when pinned)
     const unsigned char* d_rec = nullptr;
@@ -989,6 +994,7 @@ try {
         hipLaunchKernelGGL(k_rec_to_xyzi4, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_rec, step, (size_t)layout->off_x,
                            layout->off_intensity >= 0 ? layout->off_intensity : -1, (int)n, w->xyzi.as<float4>());
     }
+    w->n_raw = n; w->has_raw = true;                     // (lio_kf_store_sc_add_from_handle reads it on `aux`)
     int no = 0;
     // (the filter's first host wait -- the bounding box -- also covers the H2D copy: the caller's blob is free again)
     rc = voxel_grid_device<LioDevBytes>(w->xyzi.as<float4>(), (int)n, leaf, w->ds, &no, s, w->vws, false, nullptr);
@@ -1195,4 +1201,76 @@ try {
     if (best < 0 || best == last) return 0;               // MO:1297-1298
     *key_cur = last; *key_pre = best;
     return 1;
+} LIO_CATCH
+
+// ------------------------------------------------ Scan Context loop detection (performSCLoopClosure MO:1163-1269)
+// The kernels and the detection are in lio_sc.hip; here are the entry points that need the store and the staged raw cloud.
+extern "C" int lio_kf_store_sc_add(lio_kf_store* s, const void* cloud, size_t n, size_t stride, const lio_sc_config* cfg, int32_t* id_out)
+try {
+    if (!s || (n && !cloud)) return lio_fail(LIO_ERR_ARG, "null argument");
+    if (stride < 12 || (stride & 3)) return lio_fail(LIO_ERR_ARG, "stride must be >= 12 and a multiple of 4");
+    if (n > 0x7fffffffull - 1024) return lio_fail(LIO_ERR_CAPACITY, "cloud too large");
+    int rc = check_device(s->device_id);
+    if (rc != LIO_OK) return rc;
+    LioTemp raw;
+    if (n) {
+        HIPCHK(raw.alloc(n * stride));
+        HIPCHK(hipMemcpyAsync(raw.p, cloud, n * stride, hipMemcpyDefault, nullptr));
+    }
+    return lio_sc_store_append(s->sc, raw.as<unsigned char>(), stride, 0, n, cfg, nullptr, id_out);
+} LIO_CATCH
+
+extern "C" int lio_kf_store_sc_add_device(lio_kf_store* s, const void* d_cloud, size_t n, size_t stride, const lio_sc_config* cfg, int32_t* id_out)
+try {
+    if (!s || (n && !d_cloud)) return lio_fail(LIO_ERR_ARG, "null argument");
+    if (stride < 12 || (stride & 3)) return lio_fail(LIO_ERR_ARG, "stride must be >= 12 and a multiple of 4");
+    if ((uintptr_t)d_cloud & 3) return lio_fail(LIO_ERR_ARG, "d_cloud must be aligned to 4 bytes");      // k_sc_fold reads it as floats
+    int rc = check_device(s->device_id);
+    if (rc != LIO_OK) return rc;
+    if (n) HIPCHK(hipDeviceSynchronize());               // the producer of d_cloud may have used any stream
+    return lio_sc_store_append(s->sc, (const unsigned char*)d_cloud, stride, 0, n, cfg, nullptr, id_out);
+} LIO_CATCH
+
+// thisRawCloudKeyFrame of MO:2149-2156 is cloud_info.cloud_deskewed: the cloud lio_s2m_register_raw has just turned into
+// float4 records on the handle (before the voxel filter).  Read where it lies, on the stream that wrote it.
+extern "C" int lio_kf_store_sc_add_from_handle(lio_kf_store* s, lio_s2m_handle* h, const lio_sc_config* cfg, int32_t* id_out)
+try {
+    if (!s || !h) return lio_fail(LIO_ERR_ARG, "null argument");
+    if (h->cfg.device_id != s->device_id) return lio_fail(LIO_ERR_ARG, "the handle and the keyframe store live on different devices");
+    if (h->multi || !h->raw_ws || !h->raw_ws->has_raw) return lio_fail(LIO_ERR_ARG, "the handle holds no cloud staged by lio_s2m_register_raw");
+    int rc = check_device(s->device_id);
+    if (rc != LIO_OK) return rc;
+    LioRawWs* w = h->raw_ws;
+    return lio_sc_store_append(s->sc, w->xyzi.as<unsigned char>(), sizeof(float4), 0, w->n_raw, cfg, w->aux, id_out);
+} LIO_CATCH
+
+extern "C" int lio_kf_store_sc_count(const lio_kf_store* s)
+try {
+    return s ? (int)s->sc.count : 0;
+} LIO_CATCH
+
+extern "C" int lio_kf_store_sc_geometry(const lio_kf_store* s, int32_t* num_rings, int32_t* num_sectors)
+try {
+    if (!s || !num_rings || !num_sectors) return lio_fail(LIO_ERR_ARG, "null argument");
+    *num_rings = s->sc.count ? s->sc.rings : 0;
+    *num_sectors = s->sc.count ? s->sc.sectors : 0;
+    return LIO_OK;
+} LIO_CATCH
+
+extern "C" int lio_kf_store_sc_get(lio_kf_store* s, int32_t id, float* desc, float* ring_key, double* sector_key)
+try {
+    if (!s) return lio_fail(LIO_ERR_ARG, "null argument");
+    int rc = check_device(s->device_id);
+    if (rc != LIO_OK) return rc;
+    return lio_sc_store_get(s->sc, id, desc, ring_key, sector_key);
+} LIO_CATCH
+
+extern "C" int lio_kf_store_sc_detect(lio_kf_store* s, const lio_sc_config* cfg, lio_sc_result* res)
+try {
+    if (!s || !res) return lio_fail(LIO_ERR_ARG, "null argument");
+    int rc = check_device(s->device_id);
+    if (rc != LIO_OK) return rc;
+    rc = lio_sc_store_detect(s->sc, cfg, res, nullptr);
+    res->status = rc;
+    return rc;
 } LIO_CATCH
