@@ -669,6 +669,49 @@ int  lio_kf_store_sc_detect(lio_kf_store *s, const lio_sc_config *cfg, lio_sc_re
 /* Test hook: distanceBtnScanContext (SC:116-148) of two host descriptors (desc_a = _sc1, the query). */
 int  lio_sc_distance(int32_t device_id, const float *desc_a, const float *desc_b, const lio_sc_config *cfg, double *dist, int32_t *align);
 
+/* ------------------------------------------------ planning local map (publishLocalMap MO:2442-2541) */
+/* pcl::StatisticalOutlierRemoval<PointXYZI> as MO:293-294 sets it up and MO:2513-2514 runs it (sor.setMeanK,
+ * sor.setStddevMulThresh, sor.filter), on the device.  DESIGN.md section 4d states the conventions (parity unpinned,
+ * restated from memory): for every point the mean_k + 1 smallest fp32 squared distances to all points of the cloud, the
+ * point itself included, the smallest dropped; dist_i = the fp64 mean of their square roots, rounded to float; a point
+ * stays iff dist_i <= mean + stddev_mul * stddev of all dist_i.  Input order and intensity are kept.  Records: x,y,z
+ * @0,4,8, intensity @16 when stride >= 20 (else 0); out records are PointXYZI (out_stride >= 20); `out` (may be NULL: count
+ * only) holds n records.  Points with a non-finite coordinate (or one beyond 1e15 m, which the search grid leaves out) are
+ * dropped and not counted.  mean_dist (may be NULL): n floats, dist_i per input point, NaN for a dropped one.  stats (may
+ * be NULL): mean, stddev, threshold.  Returns LIO_OK, or 1 when the cloud has at most mean_k such points and is passed
+ * through (dist_i = 0, stats = 0, 0, +inf).  mean_k outside [1, 32] or a non-finite stddev_mul -> LIO_ERR_ARG. */
+int  lio_sor_filter(int32_t device_id, const void *pts, size_t n, size_t stride_bytes, int32_t mean_k, float stddev_mul,
+                    void *out, size_t out_stride_bytes, size_t *n_out, float *mean_dist, double stats[3]);
+
+typedef struct lio_local_map_config {
+    int32_t n_keyframes;      /* localMapKeyFramesNumber  UT:219  30   */
+    float   front, left, back, right; /* localMapFront .. localMapRight UT:220-223  70, 40, 20, 40 */
+    int32_t remove_outliers;  /* useRemovingOutliers      UT:227  1    */
+    int32_t mean_k;           /* meanK                    UT:228  10   */
+    float   stddev_mul;       /* stddevThreshold          UT:229  1.0  */
+    int32_t downsample;       /* useDownSamplingLocalMap  UT:224  1    */
+    float   leaf;             /* localMappingSurfLeafSize UT:226  0.01 */
+} lio_local_map_config;
+typedef struct lio_local_map_info {
+    int32_t first_keyframe, n_keyframes;            /* startPoseNum MO:2462 and how many keyframes were summed */
+    int32_t n_summed, n_cropped, n_inliers, n_out;  /* points after each stage */
+    int32_t voxel_passthrough;                      /* 1: pcl::VoxelGrid would not filter (voxel index overflow) */
+    int32_t pad;
+    double  sor_mean, sor_stddev, sor_threshold;    /* 0, 0, 0 when remove_outliers is off */
+} lio_local_map_info;
+void lio_local_map_default_config(lio_local_map_config *cfg);
+/* MO:2447-2540 in one call, from the resident store: the keyframes max(0, count - n_keyframes) .. count - 1 summed under
+ * their stored poses (MO:2462-2466, the kernels of lio_assemble_map_resident), moved into the yaw-aligned vehicle frame of
+ * `pose` = transformTobeMapped (MO:2474-2489: yaw, x, y, z are used; roll and pitch are not undone) and cropped to
+ * -left <= x <= right, -back <= y <= front (MO:2502-2506, limits inclusive), filtered as lio_sor_filter when
+ * remove_outliers, voxel-filtered as lio_voxel_grid when downsample.  At the default leaf the voxel index overflows and
+ * PCL passes the cloud through: info->voxel_passthrough says so, it is no error.  `out` (may be NULL: count only) holds
+ * out_cap PointXYZI records; a larger result -> LIO_ERR_ARG with the needed count in *n_out.  An empty store: LIO_OK,
+ * *n_out = 0 (MO:2444).  LIO_ERR_ARG for a summed keyframe without a pose, a non-finite pose and an out-of-range config
+ * (n_keyframes < 1, limits not finite or crossing, flags other than 0 / 1, mean_k, stddev_mul, leaf).  info may be NULL. */
+int  lio_kf_store_local_map(lio_kf_store *s, const lio_local_map_config *cfg, const float pose[6],
+                            void *out, size_t out_stride_bytes, size_t out_cap, size_t *n_out, lio_local_map_info *info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -175,6 +175,18 @@ public:
                                     nullptr), "lio_kf_store_loop_icp");
         return res.accepted != 0;
     }
+    // publishLocalMap MO:2447-2540: the newest keyframes summed, cropped in the vehicle frame of transformTobeMapped,
+    // outliers removed, downsampled; `out` holds out_cap pcl::PointXYZI records.  Returns the points written; what
+    // publishCloud(pubLocalMap, ...) MO:2541 sends.  cfg == nullptr: the defaults of UT:219-229.
+    size_t publishLocalMap(const float transformTobeMapped[6], void* out, size_t out_cap, const lio_local_map_config* cfg = nullptr,
+                           lio_local_map_info* info = nullptr)
+    {
+        lio_local_map_config c;
+        if (cfg) c = *cfg; else lio_local_map_default_config(&c);
+        size_t n = 0;
+        check(lio_kf_store_local_map(s_, &c, transformTobeMapped, out, 32, out_cap, &n, info), "lio_kf_store_local_map");
+        return n;
+    }
     lio_kf_store* get() { return s_; }
 
 private:

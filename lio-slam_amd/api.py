@@ -134,6 +134,19 @@ class ScResult(C.Structure):
                 ("cand_dist", C.c_double * SC_MAX_CANDIDATES), ("cand_align", C.c_int32 * SC_MAX_CANDIDATES)]
 
 
+class LocalMapConfig(C.Structure):
+    """publishLocalMap's parameters, UT:219-229 (include/liogpu.h lio_local_map_config)."""
+    _fields_ = [("n_keyframes", C.c_int32), ("front", C.c_float), ("left", C.c_float), ("back", C.c_float), ("right", C.c_float),
+                ("remove_outliers", C.c_int32), ("mean_k", C.c_int32), ("stddev_mul", C.c_float), ("downsample", C.c_int32),
+                ("leaf", C.c_float)]
+
+
+class LocalMapInfo(C.Structure):
+    _fields_ = [("first_keyframe", C.c_int32), ("n_keyframes", C.c_int32), ("n_summed", C.c_int32), ("n_cropped", C.c_int32),
+                ("n_inliers", C.c_int32), ("n_out", C.c_int32), ("voxel_passthrough", C.c_int32), ("pad", C.c_int32),
+                ("sor_mean", C.c_double), ("sor_stddev", C.c_double), ("sor_threshold", C.c_double)]
+
+
 ICP_STATES = {0: "NOT_CONVERGED", 1: "ITERATIONS", 2: "TRANSFORM", 3: "ABS_MSE", 4: "REL_MSE", 5: "NO_CORRESPONDENCES"}
 
 
@@ -175,6 +188,7 @@ EXPORTS = [
     "lio_icp_default_config", "lio_icp_align", "lio_kf_store_loop_icp", "lio_kf_store_detect_loop", "lio_icp_debug_trace",
     "lio_sc_default_config", "lio_sc_make", "lio_sc_distance", "lio_kf_store_sc_add", "lio_kf_store_sc_add_device",
     "lio_kf_store_sc_add_from_handle", "lio_kf_store_sc_count", "lio_kf_store_sc_geometry", "lio_kf_store_sc_get", "lio_kf_store_sc_detect",
+    "lio_sor_filter", "lio_local_map_default_config", "lio_kf_store_local_map",
 ]
 
 
@@ -293,6 +307,10 @@ def load_library():
     L.lio_kf_store_sc_geometry.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
     L.lio_kf_store_sc_get.argtypes = [vp, i32, vp, vp, vp]
     L.lio_kf_store_sc_detect.argtypes = [vp, scp, C.POINTER(ScResult)]
+    L.lio_sor_filter.argtypes = [i32, vp, sz, sz, i32, f32, vp, sz, C.POINTER(sz), vp, C.POINTER(f64)]
+    L.lio_local_map_default_config.argtypes = [C.POINTER(LocalMapConfig)]
+    L.lio_local_map_default_config.restype = None
+    L.lio_kf_store_local_map.argtypes = [vp, C.POINTER(LocalMapConfig), C.POINTER(f32), vp, sz, sz, C.POINTER(sz), C.POINTER(LocalMapInfo)]
     _LIB = L
     return L
 
@@ -872,6 +890,31 @@ def sc_distance(desc_a, desc_b, cfg=None, device_id=0):
     return d.value, al.value
 
 
+# sor.filter, MO:2513-2514 (pcl::StatisticalOutlierRemoval)
+def sor_filter(xyzi, mean_k=10, stddev_mul=1.0, device_id=0):
+    """-> (inliers [m,4], mean_dist [n] with NaN for a skipped point, stats (mean, stddev, threshold), rc); rc 1 = passed
+    through (at most mean_k finite points).  xyzi: [n,4] float32 (x, y, z, intensity)."""
+    rec = _as_xyzi_records(np.asarray(xyzi, np.float32).reshape(-1, 4))
+    n = len(rec)
+    out = np.zeros((max(n, 1), 8), np.float32)
+    dist = np.zeros(max(n, 1), np.float32)
+    stats = (C.c_double * 3)()
+    n_out = C.c_size_t()
+    rc = _check(load_library().lio_sor_filter(device_id, rec.ctypes.data, n, 32, int(mean_k), float(stddev_mul), out.ctypes.data, 32,
+                                              C.byref(n_out), dist.ctypes.data, stats), "lio_sor_filter")
+    return _from_records(out, n_out.value), dist[:n].copy(), tuple(stats), rc
+
+
+def local_map_default_config(**overrides):
+    cfg = LocalMapConfig()
+    load_library().lio_local_map_default_config(C.byref(cfg))
+    for k, v in overrides.items():
+        if not hasattr(cfg, k):
+            raise AttributeError(k)
+        setattr(cfg, k, v)
+    return cfg
+
+
 # extractCloud, MO:1556-1588
 def assemble_map(clouds_xyzi, poses, leaf, s2m=None, device_id=0, want_output=True):
     recs = [_as_xyzi_records(c) for c in clouds_xyzi]
@@ -974,6 +1017,20 @@ class KeyframeStore:
         if want_clouds:
             clouds = (_from_records(bufs[0], cl.n_source), _from_records(bufs[1], cl.n_target), _from_records(bufs[2], cl.n_closed))
         return res, rc, clouds
+
+    def local_map(self, pose, cfg=None, want_output=True, max_out=None):   # publishLocalMap, MO:2447-2540
+        """-> (cloud [m,4] in the yaw-aligned vehicle frame or None, LocalMapInfo, rc).  pose: transformTobeMapped."""
+        cfg = cfg or local_map_default_config()
+        p = np.ascontiguousarray(pose, np.float32).reshape(6)
+        n = len(self)
+        if want_output and max_out is None:          # room for every summed point: nothing downstream adds any
+            max_out = sum(int(self.lib.lio_kf_store_points(self.h, i)) for i in range(max(n - max(cfg.n_keyframes, 0), 0), n))
+        out = np.zeros((max(max_out or 1, 1), 8), np.float32) if want_output else None
+        n_out, info = C.c_size_t(), LocalMapInfo()
+        rc = _check(self.lib.lio_kf_store_local_map(self.h, C.byref(cfg), _f32p(p), out.ctypes.data if want_output else None, 32,
+                                                    len(out) if want_output else 0, C.byref(n_out), C.byref(info)),
+                    "lio_kf_store_local_map")
+        return (_from_records(out, n_out.value) if want_output else None), info, rc
 
     def detect_loop(self, radius, time_diff, time_cur):   # detectLoopClosureDistance, MO:1271-1304
         """-> (key_cur, key_pre) or None."""

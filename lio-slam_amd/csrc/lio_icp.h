@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/liogpu.h"
+#include "lio_types.h"
 
 // Optional per-iteration record of one alignment (lio_icp_debug_trace): host arrays, cfg.max_iters entries each
 // (step: 16 floats per entry), corr: n_src entries for iteration rec_iter.  Any pointer may be null.
@@ -21,3 +22,8 @@ int lio_icp_check_config(const lio_icp_config* cfg);       // LIO_OK or LIO_ERR_
 // final transformation, w kept.  Fills every field of *res but pose_corrected.
 int lio_icp_device(const float4* d_src, int n_src, const float4* d_tgt, int n_tgt, const lio_icp_config& cfg,
                    const float* guess, lio_icp_result* res, hipStream_t s, LioIcpTrace* trace, float4* d_closed);
+
+// The uniform grid of a cell-walking search over the box mn .. mx of n device points (SoA): the edge (*edge) from their
+// density, about `per_cell` points per occupied cell, at most 2^22 cells.  One host wait (the occupied cells of a trial grid).
+int lio_icp_choose_grid(const float* x, const float* y, const float* z, int n, const float mn[3], const float mx[3], float per_cell,
+                        hipStream_t s, LioGrid* g, float* edge);

@@ -404,9 +404,13 @@ void icp_empty_result(lio_icp_result* res, const float* guess, int n_src, int n_
     for (int i = 0; i < 16; ++i) res->T[i] = guess ? guess[i] : ((i % 5 == 0) ? 1.0f : 0.0f);
 }
 
+}  // namespace
+
 // The grid over the target's box.  Cell edge from the target's density: points per occupied cell of a trial grid (64 cells
-// along the longest side), scaled as for points on surfaces (count ~ edge^2) to about four per occupied cell.
-int icp_choose_grid(const float* x, const float* y, const float* z, int n, const float mn[3], const float mx[3], hipStream_t s, LioGrid* g, float* edge)
+// along the longest side), scaled as for points on surfaces (count ~ edge^2) to about `per_cell` per occupied cell (the
+// alignment asks for four).
+int lio_icp_choose_grid(const float* x, const float* y, const float* z, int n, const float mn[3], const float mx[3], float per_cell,
+                        hipStream_t s, LioGrid* g, float* edge)
 {
     const float ext = fmaxf(fmaxf(mx[0] - mn[0], mx[1] - mn[1]), mx[2] - mn[2]);
     auto lay = [&](float e) {
@@ -433,7 +437,7 @@ int icp_choose_grid(const float* x, const float* y, const float* z, int n, const
         HIPCHK(hipMemcpyAsync(&occ, flags.as<int>() + g->n_cells, sizeof(int), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         const float ppc = occ > 0 ? (float)n / (float)occ : 1.0f;
-        e = e0 * sqrtf(4.0f / ppc);
+        e = e0 * sqrtf(per_cell / ppc);
         e = fminf(fmaxf(e, ext / 500.0f), ext);
         while (lay(e) > (1LL << 22)) e *= 1.26f;
     }
@@ -441,7 +445,6 @@ int icp_choose_grid(const float* x, const float* y, const float* z, int n, const
     *edge = e;
     return LIO_OK;
 }
-}  // namespace
 
 int lio_icp_device(const float4* d_src, int n_src, const float4* d_tgt, int n_tgt, const lio_icp_config& cfg, const float* guess,
                    lio_icp_result* res, hipStream_t s, LioIcpTrace* trace, float4* d_closed)
@@ -477,7 +480,7 @@ int lio_icp_device(const float4* d_src, int n_src, const float4* d_tgt, int n_tg
         HIPCHK(hipStreamSynchronize(s));
         return LIO_OK;
     }
-    int rc = icp_choose_grid(tx.as<float>(), ty.as<float>(), tz.as<float>(), n_tgt, mn, mx, s, &g, &edge);
+    int rc = lio_icp_choose_grid(tx.as<float>(), ty.as<float>(), tz.as<float>(), n_tgt, mn, mx, 4.0f, s, &g, &edge);
     if (rc != LIO_OK) return rc;
     LioTemp cell_of, cell_count, cell_start, tiles, sorted;
     HIPCHK(cell_of.alloc(sizeof(int) * (size_t)n_tgt));

@@ -13,6 +13,7 @@
 
 #include "lio_handle.h"
 #include "lio_icp.h"
+#include "lio_localmap.h"
 #include "lio_pool.h"
 #include "lio_sc.h"
 #include "lio_device_math.h"
@@ -1273,4 +1274,135 @@ try {
     rc = lio_sc_store_detect(s->sc, cfg, res, nullptr);
     res->status = rc;
     return rc;
+} LIO_CATCH
+
+// ------------------------------------------------ planning local map (publishLocalMap MO:2442-2541)
+// The crop and the outlier filter are in lio_localmap.hip; here are the entry points: they need the store, K6 + K7 and the
+// record conversions of this file.
+extern "C" int lio_sor_filter(int32_t device_id, const void* pts, size_t n, size_t stride, int32_t mean_k, float stddev_mul, void* out,
+                              size_t out_stride, size_t* n_out, float* mean_dist, double stats[3])
+try {
+    if (!n_out || (n && !pts)) return lio_fail(LIO_ERR_ARG, "null argument");
+    if (stride < 12 || (stride & 3) || (out && (out_stride < 20 || (out_stride & 3))))
+        return lio_fail(LIO_ERR_ARG, "stride must be >= 12, the output stride >= 20, both multiples of 4");
+    if (n > 0x7fffffffull - 1024) return lio_fail(LIO_ERR_CAPACITY, "cloud too large");
+    int rc = lio_sor_check(mean_k, stddev_mul);
+    if (rc != LIO_OK) return rc;
+    *n_out = 0;
+    if (stats) { stats[0] = 0.0; stats[1] = 0.0; stats[2] = INFINITY; }
+    if (n == 0) return 1;                                  // nothing to filter: the pass-through of at most mean_k points
+    if ((rc = check_device(device_id)) != LIO_OK) return rc;
+    hipStream_t s = nullptr;
+    LioTemp raw, xyzi, inl, dist;
+    HIPCHK(raw.alloc(n * stride));
+    HIPCHK(xyzi.alloc(n * sizeof(float4)));
+    if (mean_dist) HIPCHK(dist.alloc(n * sizeof(float)));
+    HIPCHK(hipMemcpyAsync(raw.p, pts, n * stride, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_rec_to_xyzi4, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, raw.as<unsigned char>(), stride, (size_t)0,
+                       stride >= 20 ? 16 : -1, (int)n, xyzi.as<float4>());
+    int no = 0;
+    LioSorReport rep;
+    rc = lio_sor_device(xyzi.as<float4>(), (int)n, mean_k, stddev_mul, inl, &no, mean_dist ? dist.as<float>() : nullptr, &rep, s);
+    if (rc < 0) return rc;
+    if (mean_dist) HIPCHK(hipMemcpyAsync(mean_dist, dist.p, n * sizeof(float), hipMemcpyDeviceToHost, s));
+    const int rc2 = copy_out(inl.as<float4>(), no, out, out_stride, s);
+    if (rc2 < 0) return rc2;
+    HIPCHK(hipStreamSynchronize(s));
+    if (stats) { stats[0] = rep.mean; stats[1] = rep.stddev; stats[2] = rep.threshold; }
+    *n_out = (size_t)no;
+    return rc;
+} LIO_CATCH
+
+extern "C" void lio_local_map_default_config(lio_local_map_config* cfg)
+{
+    if (!cfg) return;
+    cfg->n_keyframes = 30;                                 // localMapKeyFramesNumber, UT:219
+    cfg->front = 70.0f; cfg->left = 40.0f; cfg->back = 20.0f; cfg->right = 40.0f;        // UT:220-223
+    cfg->remove_outliers = 1;                              // useRemovingOutliers, UT:227
+    cfg->mean_k = 10;                                      // meanK, UT:228
+    cfg->stddev_mul = 1.0f;                                // stddevThreshold, UT:229
+    cfg->downsample = 1;                                   // useDownSamplingLocalMap, UT:224
+    cfg->leaf = 0.01f;                                     // localMappingSurfLeafSize, UT:226
+}
+
+extern "C" int lio_kf_store_local_map(lio_kf_store* st, const lio_local_map_config* cfg, const float* pose, void* out, size_t out_stride,
+                                      size_t out_cap, size_t* n_out, lio_local_map_info* info)
+try {
+    if (!st || !cfg || !pose) return lio_fail(LIO_ERR_ARG, "null argument");
+    if (out && (out_stride < 20 || (out_stride & 3))) return lio_fail(LIO_ERR_ARG, "output stride must be >= 20 and a multiple of 4");
+    if (cfg->n_keyframes < 1) return lio_fail(LIO_ERR_ARG, "n_keyframes must be >= 1");
+    if (!std::isfinite(cfg->front) || !std::isfinite(cfg->left) || !std::isfinite(cfg->back) || !std::isfinite(cfg->right) ||
+        !(-cfg->left <= cfg->right) || !(-cfg->back <= cfg->front))
+        return lio_fail(LIO_ERR_ARG, "front, left, back, right must be finite with -left <= right and -back <= front");
+    if ((cfg->remove_outliers != 0 && cfg->remove_outliers != 1) || (cfg->downsample != 0 && cfg->downsample != 1))
+        return lio_fail(LIO_ERR_ARG, "remove_outliers and downsample are 0 or 1");
+    int rc = lio_sor_check(cfg->mean_k, cfg->stddev_mul);
+    if (rc != LIO_OK) return rc;
+    if (!(cfg->leaf > 0.0f) || !std::isfinite(cfg->leaf)) return lio_fail(LIO_ERR_ARG, "leaf must be positive and finite");
+    for (int j = 0; j < 6; ++j) if (!std::isfinite(pose[j])) return lio_fail(LIO_ERR_ARG, "non-finite pose");
+    if (n_out) *n_out = 0;
+    if (info) memset(info, 0, sizeof(*info));
+    if ((rc = check_device(st->device_id)) != LIO_OK) return rc;
+    const int N = (int)st->off.size();
+    if (N == 0) return LIO_OK;                             // MO:2444-2445
+    const int first = N < cfg->n_keyframes ? 0 : N - cfg->n_keyframes;                     // startPoseNum, MO:2462
+    // ---- K6 over first .. N - 1 under the stored poses: the h == NULL path of lio_assemble_map_resident, kernel for kernel
+    std::vector<LioKfDesc> kf;
+    std::vector<int2> chunks;
+    std::vector<float> poses;
+    size_t total = 0;
+    for (int id = first; id < N; ++id) {
+        if (!st->has_pose[(size_t)id]) return lio_fail(LIO_ERR_ARG, "a keyframe has no pose (lio_kf_store_set_poses)");
+        LioKfDesc d;
+        d.src = (int)st->off[(size_t)id]; d.first = (int)total; d.n = (int)st->cnt[(size_t)id]; d.pad = 0;
+        for (int j = 0; j < 12; ++j) d.T[j] = 0.0f;
+        for (size_t b = 0; b < st->cnt[(size_t)id]; b += 256) chunks.push_back(make_int2((int)kf.size(), (int)b));
+        kf.push_back(d);
+        const float p6[6] = { st->proll[(size_t)id], st->ppitch[(size_t)id], st->pyaw[(size_t)id], st->px[(size_t)id], st->py[(size_t)id], st->pz[(size_t)id] };
+        poses.insert(poses.end(), p6, p6 + 6);
+        total += st->cnt[(size_t)id];
+    }
+    if (total > 0x7fffffffull - 1024) return lio_fail(LIO_ERR_CAPACITY, "too many points");
+    if (info) { info->first_keyframe = first; info->n_keyframes = N - first; info->n_summed = (int)total; }
+    if (total == 0) return LIO_OK;
+    hipStream_t s = nullptr;
+    const int n_sel = (int)kf.size(), n_chunks = (int)chunks.size();
+    LioTemp d_kf, d_poses, d_chunks, world, cropped, inl, ds;
+    HIPCHK(d_kf.alloc(sizeof(LioKfDesc) * (size_t)n_sel));
+    HIPCHK(d_poses.alloc(sizeof(float) * 6 * (size_t)n_sel));
+    HIPCHK(d_chunks.alloc(sizeof(int2) * (size_t)n_chunks));
+    HIPCHK(world.alloc(total * sizeof(float4)));
+    HIPCHK(hipMemcpyAsync(d_kf.p, kf.data(), sizeof(LioKfDesc) * (size_t)n_sel, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_poses.p, poses.data(), sizeof(float) * 6 * (size_t)n_sel, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_chunks.p, chunks.data(), sizeof(int2) * (size_t)n_chunks, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_kf_transforms, dim3((n_sel + 63) / 64), dim3(64), 0, s, d_kf.as<LioKfDesc>(), d_poses.as<float>(), n_sel);
+    hipLaunchKernelGGL(k_transform_clouds, dim3((unsigned)n_chunks), dim3(256), 0, s, st->d_pts, d_kf.as<LioKfDesc>(), d_chunks.as<int2>(),
+                       world.as<float4>());
+    // ---- vehicle frame + the two pass-throughs (the wait for the count also covers the descriptors' copies)
+    float M[12];
+    lio_local_map_vehicle_frame(pose, M);
+    int n_cur = 0;
+    if ((rc = lio_crop_device(world.as<float4>(), (int)total, M, cfg->front, cfg->left, cfg->back, cfg->right, cropped, &n_cur, s)) != LIO_OK)
+        return rc;
+    const float4* cur = cropped.as<float4>();
+    if (info) info->n_cropped = n_cur;
+    if (cfg->remove_outliers) {                            // MO:2510-2516
+        LioSorReport rep;
+        int n_inl = 0;
+        if ((rc = lio_sor_device(cur, n_cur, cfg->mean_k, cfg->stddev_mul, inl, &n_inl, nullptr, &rep, s)) < 0) return rc;
+        cur = inl.as<float4>(); n_cur = n_inl;
+        if (info) { info->sor_mean = rep.mean; info->sor_stddev = rep.stddev; info->sor_threshold = rep.threshold; }
+    }
+    if (info) info->n_inliers = n_cur;
+    if (cfg->downsample) {                                 // MO:2517-2540
+        int n_ds = 0;
+        if ((rc = voxel_grid_device(cur, n_cur, cfg->leaf, ds, &n_ds, s)) < 0) return rc;
+        if (info) info->voxel_passthrough = rc == 1 ? 1 : 0;
+        if (n_cur > 0) { cur = ds.as<float4>(); n_cur = n_ds; }
+    }
+    if (info) info->n_out = n_cur;
+    if (n_out) *n_out = (size_t)n_cur;
+    if (out && (size_t)n_cur > out_cap) return lio_fail(LIO_ERR_ARG, "out holds fewer records than the local map (*n_out)");
+    if ((rc = copy_out(cur, n_cur, out, out_stride, s)) < 0) return rc;
+    return LIO_OK;
 } LIO_CATCH
