@@ -712,6 +712,60 @@ void lio_local_map_default_config(lio_local_map_config *cfg);
 int  lio_kf_store_local_map(lio_kf_store *s, const lio_local_map_config *cfg, const float pose[6],
                             void *out, size_t out_stride_bytes, size_t out_cap, size_t *n_out, lio_local_map_info *info);
 
+/* ------------------------------------------------ planning height map (grid_map_pcl's loader as the fork rewrote it) */
+/* The only subscriber of liorf/mapping/map_4planning, grid_map_pcl_loader_node.cpp:39-76: every local map becomes the
+ * "elevation" layer of /height_map.  DESIGN.md section 4e states the conventions (parity unpinned: PCL, Eigen and grid_map
+ * are restated, not linked).  The defaults are config/parameters.yaml's. */
+typedef struct lio_height_map_config {
+    float   roll, pitch;          /* thisPoseRoll / thisPosePitch, radians, as the node stores them (float) */
+    int32_t level_and_ego_filter; /* 1: GridMapPclLoader.cpp:80-85 (level by R1, ego-vehicle height filter, R2) */
+    int32_t remove_outliers;      /* outlier_removal.is_remove_outliers  1 */
+    int32_t mean_k;               /* outlier_removal.mean_K              10 */
+    float   stddev_mul;           /* outlier_removal.stddev_threshold    1.0 */
+    int32_t downsample;           /* downsampling.is_downsample_cloud    0 */
+    float   voxel[3];             /* downsampling.voxel_size             0.1 0.1 0.1; the three must be equal when downsample */
+    double  resolution;           /* grid_map.resolution                 0.2 */
+    int32_t min_points_per_cell, max_points_per_cell;   /* grid_map.min/max_num_points_per_cell  1, 1000000000 */
+    int32_t use_cluster;          /* cluster_extraction.use_cluster      0 */
+    float   cluster_tolerance;    /* cluster_extraction.cluster_tolerance 1.0 */
+    int32_t cluster_min_points, cluster_max_points;     /* cluster_extraction.min/max_num_points  1, 1000000000 */
+    int32_t use_max_height;       /* cluster_extraction.use_max_height_as_cell_elevation  0 */
+    int32_t fill_holes;           /* 0: the reference as written (its hole-filling pass changes nothing); 1: labelled extension */
+} lio_height_map_config;
+typedef struct lio_height_map_info {
+    int32_t rows, cols;             /* grid_map size(0) (along x), size(1) (along y) */
+    double  length[2], position[2]; /* grid_map length_, position_ */
+    int32_t n_in;                   /* points given */
+    int32_t n_inliers;              /* after the outlier filter (points with a non-finite coordinate are gone from here on) */
+    int32_t n_filtered;             /* after the voxel filter and the ego filter: the points the grid is laid around */
+    int32_t n_binned;               /* of those, the points inside a cell (an index equal to the size is the reference's spare row) */
+    int32_t n_valid_cells;          /* cells with an elevation before the hole filling */
+    int32_t n_filled_cells;         /* cells the hole filling gave one (0 when fill_holes is 0) */
+    int32_t voxel_passthrough, pad; /* 1: pcl::VoxelGrid would not filter (voxel index overflow) */
+} lio_height_map_info;
+void lio_height_map_default_config(lio_height_map_config *cfg);
+/* helpers.cpp:97-105 on n host records (x,y,z @0,4,8; the loader's cloud is PointXYZ), in the reference's order: the outlier
+ * filter of lio_sor_filter when remove_outliers; lio_voxel_grid when downsample; R1 = Rx(-roll) Ry(-pitch), the ego filter
+ * of PointcloudProcessor.cpp:39-55 on the levelled point, R2 = Rx(roll) Ry(pitch) on what it keeps (R2 is not R1's inverse:
+ * reproduced as written); the geometry from the cloud's box; every point to its cell; per cell with min_points_per_cell <=
+ * count <= max_points_per_cell either the fp64 mean of z in input order or, with use_cluster, the min (max) over the
+ * connected components under cluster_tolerance of that mean; the hole filling.  `grid`: column-major rows x cols floats
+ * (grid_map::Matrix), NaN = no elevation; NULL = the geometry only (the counts behind n_filtered stay 0).  More cells than
+ * grid_cap -> LIO_ERR_ARG with rows and cols filled in.  An empty cloud, and a cloud whose box has no extent along x or y
+ * (where the reference asserts): LIO_OK with rows or cols 0.  Points with a non-finite coordinate (or one beyond 1e15 m) are
+ * dropped.  fill_holes = 1: every NaN cell with four valid cells in rows [r-5, r+5) x cols [c-5, c+5) becomes the mean of the
+ * four nearest, found by the cascade of GridMapPclLoader.cpp:225-249 on the layer before the pass.  LIO_ERR_ARG, never a
+ * clamp, for resolution < 1e-4 (the reference throws), flags other than 0 / 1, non-finite angles, mean_k / stddev_mul as
+ * lio_sor_filter, unequal or non-positive voxel sizes when downsample, negative counts, a negative or non-finite tolerance. */
+int  lio_height_map(int32_t device_id, const void *pts, size_t n, size_t stride_bytes, const lio_height_map_config *cfg,
+                    float *grid, size_t grid_cap, lio_height_map_info *info);
+/* lio_kf_store_local_map's stages, then the chain above on the device cloud they leave: nothing goes to the host in between,
+ * only the grid crosses.  lm_info (may be NULL) = what lio_kf_store_local_map reports for the same arguments.  An empty
+ * store or an empty local map: LIO_OK, rows = cols = 0.  Replaces cloudMapInfoHandler, grid_map_pcl_loader_node.cpp:47-54. */
+int  lio_kf_store_height_map(lio_kf_store *s, const lio_local_map_config *lm, const float pose[6],
+                             const lio_height_map_config *cfg, float *grid, size_t grid_cap,
+                             lio_local_map_info *lm_info, lio_height_map_info *info);
+
 #ifdef __cplusplus
 }
 #endif

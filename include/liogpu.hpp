@@ -187,6 +187,20 @@ public:
         check(lio_kf_store_local_map(s_, &c, transformTobeMapped, out, 32, out_cap, &n, info), "lio_kf_store_local_map");
         return n;
     }
+    // publishLocalMap followed by the height-map node's cloudMapInfoHandler (grid_map_pcl_loader_node.cpp:47-54) without the
+    // cloud in between: `grid` holds grid_cap floats, column-major info.rows x info.cols (grid_map::Matrix); grid == nullptr
+    // asks for the geometry only.  Returns the number of cells.  Null configs: the defaults with roll = pitch = 0.
+    size_t heightMap(const float transformTobeMapped[6], float* grid, size_t grid_cap, lio_height_map_info& info,
+                     const lio_height_map_config* cfg = nullptr, const lio_local_map_config* lm_cfg = nullptr,
+                     lio_local_map_info* lm_info = nullptr)
+    {
+        lio_local_map_config lm;
+        if (lm_cfg) lm = *lm_cfg; else lio_local_map_default_config(&lm);
+        lio_height_map_config c;
+        if (cfg) c = *cfg; else lio_height_map_default_config(&c);
+        check(lio_kf_store_height_map(s_, &lm, transformTobeMapped, &c, grid, grid_cap, lm_info, &info), "lio_kf_store_height_map");
+        return (size_t)info.rows * (size_t)info.cols;
+    }
     lio_kf_store* get() { return s_; }
 
 private:

@@ -147,6 +147,21 @@ class LocalMapInfo(C.Structure):
                 ("sor_mean", C.c_double), ("sor_stddev", C.c_double), ("sor_threshold", C.c_double)]
 
 
+class HeightMapConfig(C.Structure):
+    """grid_map_pcl's config/parameters.yaml and the node's roll / pitch (include/liogpu.h lio_height_map_config)."""
+    _fields_ = [("roll", C.c_float), ("pitch", C.c_float), ("level_and_ego_filter", C.c_int32), ("remove_outliers", C.c_int32),
+                ("mean_k", C.c_int32), ("stddev_mul", C.c_float), ("downsample", C.c_int32), ("voxel", C.c_float * 3),
+                ("resolution", C.c_double), ("min_points_per_cell", C.c_int32), ("max_points_per_cell", C.c_int32),
+                ("use_cluster", C.c_int32), ("cluster_tolerance", C.c_float), ("cluster_min_points", C.c_int32),
+                ("cluster_max_points", C.c_int32), ("use_max_height", C.c_int32), ("fill_holes", C.c_int32)]
+
+
+class HeightMapInfo(C.Structure):
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("length", C.c_double * 2), ("position", C.c_double * 2),
+                ("n_in", C.c_int32), ("n_inliers", C.c_int32), ("n_filtered", C.c_int32), ("n_binned", C.c_int32),
+                ("n_valid_cells", C.c_int32), ("n_filled_cells", C.c_int32), ("voxel_passthrough", C.c_int32), ("pad", C.c_int32)]
+
+
 ICP_STATES = {0: "NOT_CONVERGED", 1: "ITERATIONS", 2: "TRANSFORM", 3: "ABS_MSE", 4: "REL_MSE", 5: "NO_CORRESPONDENCES"}
 
 
@@ -189,6 +204,7 @@ EXPORTS = [
     "lio_sc_default_config", "lio_sc_make", "lio_sc_distance", "lio_kf_store_sc_add", "lio_kf_store_sc_add_device",
     "lio_kf_store_sc_add_from_handle", "lio_kf_store_sc_count", "lio_kf_store_sc_geometry", "lio_kf_store_sc_get", "lio_kf_store_sc_detect",
     "lio_sor_filter", "lio_local_map_default_config", "lio_kf_store_local_map",
+    "lio_height_map_default_config", "lio_height_map", "lio_kf_store_height_map",
 ]
 
 
@@ -311,6 +327,11 @@ def load_library():
     L.lio_local_map_default_config.argtypes = [C.POINTER(LocalMapConfig)]
     L.lio_local_map_default_config.restype = None
     L.lio_kf_store_local_map.argtypes = [vp, C.POINTER(LocalMapConfig), C.POINTER(f32), vp, sz, sz, C.POINTER(sz), C.POINTER(LocalMapInfo)]
+    L.lio_height_map_default_config.argtypes = [C.POINTER(HeightMapConfig)]
+    L.lio_height_map_default_config.restype = None
+    L.lio_height_map.argtypes = [i32, vp, sz, sz, C.POINTER(HeightMapConfig), vp, sz, C.POINTER(HeightMapInfo)]
+    L.lio_kf_store_height_map.argtypes = [vp, C.POINTER(LocalMapConfig), C.POINTER(f32), C.POINTER(HeightMapConfig), vp, sz,
+                                          C.POINTER(LocalMapInfo), C.POINTER(HeightMapInfo)]
     _LIB = L
     return L
 
@@ -915,6 +936,48 @@ def local_map_default_config(**overrides):
     return cfg
 
 
+def height_map_default_config(**overrides):
+    cfg = HeightMapConfig()
+    load_library().lio_height_map_default_config(C.byref(cfg))
+    for k, v in overrides.items():
+        if not hasattr(cfg, k):
+            raise AttributeError(k)
+        setattr(cfg, k, (C.c_float * 3)(*v) if k == "voxel" else v)
+    return cfg
+
+
+def _height_map_call(call, what, want_grid):
+    """One call into a grid buffer kept from the last one, as a node keeps it; a second only when the grid has outgrown the
+    buffer (ERR_ARG with rows x cols filled in).  -> (grid [rows, cols] float32 (NaN: no elevation) or None, HeightMapInfo)."""
+    info = HeightMapInfo()
+    if not want_grid:
+        _check(call(None, 0, info), what)
+        return None, info
+    buf = _scratch("height_map", (_SCRATCH_CELLS.get("height_map", 1 << 18),))
+    rc = call(buf.ctypes.data, buf.size, info)
+    if rc == -1 and info.rows * info.cols > buf.size:
+        _SCRATCH_CELLS["height_map"] = info.rows * info.cols
+        buf = _scratch("height_map", (info.rows * info.cols,))
+        rc = call(buf.ctypes.data, buf.size, info)
+    _check(rc, what)
+    n = info.rows * info.cols
+    return buf[:n].reshape((info.rows, info.cols), order="F").copy(order="F"), info     # grid_map::Matrix is column-major
+
+
+_SCRATCH_CELLS = {}
+
+
+# processPointcloud, helpers.cpp:97-105 (grid_map_pcl's loader; DESIGN.md section 4e)
+def height_map(xyz, cfg=None, want_grid=True, device_id=0):
+    """-> (elevation grid [rows, cols] or None, HeightMapInfo).  xyz: [n, >= 3] float32."""
+    cfg = cfg or height_map_default_config()
+    a = np.asarray(xyz, np.float32)
+    p = np.ascontiguousarray((a if a.ndim == 2 else a.reshape(-1, 3))[:, :3])
+    lib = load_library()
+    return _height_map_call(lambda g, cap, info: lib.lio_height_map(device_id, p.ctypes.data, len(p), 12, C.byref(cfg), g, cap, C.byref(info)),
+                            "lio_height_map", want_grid)
+
+
 # extractCloud, MO:1556-1588
 def assemble_map(clouds_xyzi, poses, leaf, s2m=None, device_id=0, want_output=True):
     recs = [_as_xyzi_records(c) for c in clouds_xyzi]
@@ -1031,6 +1094,17 @@ class KeyframeStore:
                                                     len(out) if want_output else 0, C.byref(n_out), C.byref(info)),
                     "lio_kf_store_local_map")
         return (_from_records(out, n_out.value) if want_output else None), info, rc
+
+    def height_map(self, pose, lm_cfg=None, cfg=None, want_grid=True):   # publishLocalMap + cloudMapInfoHandler, without the cloud
+        """-> (elevation grid [rows, cols] or None, HeightMapInfo, LocalMapInfo)."""
+        lm_cfg = lm_cfg or local_map_default_config()
+        cfg = cfg or height_map_default_config()
+        p = np.ascontiguousarray(pose, np.float32).reshape(6)
+        lm_info = LocalMapInfo()
+        grid, info = _height_map_call(
+            lambda g, cap, info: self.lib.lio_kf_store_height_map(self.h, C.byref(lm_cfg), _f32p(p), C.byref(cfg), g, cap, C.byref(lm_info),
+                                                                  C.byref(info)), "lio_kf_store_height_map", want_grid)
+        return grid, info, lm_info
 
     def detect_loop(self, radius, time_diff, time_cur):   # detectLoopClosureDistance, MO:1271-1304
         """-> (key_cur, key_pre) or None."""

@@ -13,6 +13,7 @@
 
 #include "lio_handle.h"
 #include "lio_icp.h"
+#include "lio_heightmap.h"
 #include "lio_localmap.h"
 #include "lio_pool.h"
 #include "lio_sc.h"
@@ -230,6 +231,30 @@ static int voxel_grid_sorted(const float4* d_in, int n, const LioVsGrid& vg, lon
     return LIO_OK;
 }
 
+// getMinMax3D of a device-resident cloud (n > 0) in two halves, so that a caller whose box is already in `bbox`
+// (k_transform_clouds_bbox) takes the second alone: clear + k_vox_bbox, then the copy, the wait and the decoding.
+template <class B>
+int cloud_box_launch(const float4* d_in, int n, B& bbox, hipStream_t s)
+{
+    HIPCHK(bbox.alloc(6 * sizeof(unsigned)));
+    unsigned init[6];
+    lio_ord_box_clear(init);
+    HIPCHK(hipMemcpyAsync(bbox.p, init, sizeof(init), hipMemcpyHostToDevice, s));
+    int nbb = (n + 1023) / 1024; if (nbb > 512) nbb = 512; if (nbb < 1) nbb = 1;
+    hipLaunchKernelGGL(k_vox_bbox, dim3(nbb), dim3(256), 0, s, d_in, n, bbox.template as<unsigned>());
+    return LIO_OK;
+}
+
+template <class B>
+int cloud_box_wait(B& bbox, float mn[3], float mx[3], hipStream_t s)
+{
+    unsigned hb[6];
+    HIPCHK(hipMemcpyAsync(hb, bbox.p, sizeof(hb), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    lio_ord_box_decode(hb, mn, mx);
+    return LIO_OK;
+}
+
 // K7 on a device-resident float4 cloud.  *d_out receives a freshly allocated device array.
 // Returns LIO_OK, or 1 when PCL would pass the cloud through (voxel index overflow).
 // `ws`: the temporaries; `wait`: block until the result is complete (required when ws is made of pool temporaries, which
@@ -244,18 +269,12 @@ int voxel_grid_device(const float4* d_in, int n, float leaf, B& out, int* n_out,
     if (n == 0) return LIO_OK;
     B& bbox = ws.bbox;
     if (!have_box) {
-        HIPCHK(bbox.alloc(6 * sizeof(unsigned)));
-        unsigned init[6];
-        lio_ord_box_clear(init);
-        HIPCHK(hipMemcpyAsync(bbox.p, init, sizeof(init), hipMemcpyHostToDevice, s));
-        int nbb = (n + 1023) / 1024; if (nbb > 512) nbb = 512; if (nbb < 1) nbb = 1;
-        hipLaunchKernelGGL(k_vox_bbox, dim3(nbb), dim3(256), 0, s, d_in, n, bbox.template as<unsigned>());
+        int brc = cloud_box_launch<B>(d_in, n, bbox, s);
+        if (brc != LIO_OK) return brc;
     }
-    unsigned hb[6];
-    HIPCHK(hipMemcpyAsync(hb, bbox.p, sizeof(hb), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
     float mn[3], mx[3];
-    lio_ord_box_decode(hb, mn, mx);
+    int wrc = cloud_box_wait<B>(bbox, mn, mx, s);
+    if (wrc != LIO_OK) return wrc;
     if (box) for (int a = 0; a < 3; ++a) { box[a] = mn[a]; box[3 + a] = mx[a]; }
     // (a box that is not finite -- inf coordinates, or no finite point at all -- is outside what PCL defines; such a cloud
     // takes the same way out as an overflowing index, deterministically)
@@ -1325,11 +1344,16 @@ extern "C" void lio_local_map_default_config(lio_local_map_config* cfg)
     cfg->leaf = 0.01f;                                     // localMappingSurfLeafSize, UT:226
 }
 
-extern "C" int lio_kf_store_local_map(lio_kf_store* st, const lio_local_map_config* cfg, const float* pose, void* out, size_t out_stride,
-                                      size_t out_cap, size_t* n_out, lio_local_map_info* info)
-try {
-    if (!st || !cfg || !pose) return lio_fail(LIO_ERR_ARG, "null argument");
-    if (out && (out_stride < 20 || (out_stride & 3))) return lio_fail(LIO_ERR_ARG, "output stride must be >= 20 and a multiple of 4");
+namespace {
+struct LocalMapBufs { LioTemp d_kf, d_poses, d_chunks, world, cropped, inl, ds; };
+
+// MO:2447-2540 up to the cloud on the device: *cur / *n_cur = the local map in B (null / 0 for an empty store or an empty
+// sum), complete when this returns.  What lio_kf_store_local_map copies out and lio_kf_store_height_map goes on with.
+int local_map_device(lio_kf_store* st, const lio_local_map_config* cfg, const float* pose, LocalMapBufs& B, const float4** cur_out,
+                     int* n_cur_out, size_t* n_out, lio_local_map_info* info, hipStream_t s)
+{
+    LioTemp &d_kf = B.d_kf, &d_poses = B.d_poses, &d_chunks = B.d_chunks, &world = B.world, &cropped = B.cropped, &inl = B.inl, &ds = B.ds;
+    *cur_out = nullptr; *n_cur_out = 0;
     if (cfg->n_keyframes < 1) return lio_fail(LIO_ERR_ARG, "n_keyframes must be >= 1");
     if (!std::isfinite(cfg->front) || !std::isfinite(cfg->left) || !std::isfinite(cfg->back) || !std::isfinite(cfg->right) ||
         !(-cfg->left <= cfg->right) || !(-cfg->back <= cfg->front))
@@ -1365,9 +1389,7 @@ try {
     if (total > 0x7fffffffull - 1024) return lio_fail(LIO_ERR_CAPACITY, "too many points");
     if (info) { info->first_keyframe = first; info->n_keyframes = N - first; info->n_summed = (int)total; }
     if (total == 0) return LIO_OK;
-    hipStream_t s = nullptr;
     const int n_sel = (int)kf.size(), n_chunks = (int)chunks.size();
-    LioTemp d_kf, d_poses, d_chunks, world, cropped, inl, ds;
     HIPCHK(d_kf.alloc(sizeof(LioKfDesc) * (size_t)n_sel));
     HIPCHK(d_poses.alloc(sizeof(float) * 6 * (size_t)n_sel));
     HIPCHK(d_chunks.alloc(sizeof(int2) * (size_t)n_chunks));
@@ -1402,7 +1424,168 @@ try {
     }
     if (info) info->n_out = n_cur;
     if (n_out) *n_out = (size_t)n_cur;
+    *cur_out = cur; *n_cur_out = n_cur;
+    return LIO_OK;
+}
+}  // namespace
+
+extern "C" int lio_kf_store_local_map(lio_kf_store* st, const lio_local_map_config* cfg, const float* pose, void* out, size_t out_stride,
+                                      size_t out_cap, size_t* n_out, lio_local_map_info* info)
+try {
+    if (!st || !cfg || !pose) return lio_fail(LIO_ERR_ARG, "null argument");
+    if (out && (out_stride < 20 || (out_stride & 3))) return lio_fail(LIO_ERR_ARG, "output stride must be >= 20 and a multiple of 4");
+    hipStream_t s = nullptr;
+    LocalMapBufs B;
+    const float4* cur = nullptr;
+    int n_cur = 0;
+    int rc = local_map_device(st, cfg, pose, B, &cur, &n_cur, n_out, info, s);
+    if (rc != LIO_OK) return rc;
     if (out && (size_t)n_cur > out_cap) return lio_fail(LIO_ERR_ARG, "out holds fewer records than the local map (*n_out)");
     if ((rc = copy_out(cur, n_cur, out, out_stride, s)) < 0) return rc;
     return LIO_OK;
+} LIO_CATCH
+
+// ------------------------------------------------ planning height map (grid_map_pcl's loader, helpers.cpp:97-105)
+// The kernels are in lio_heightmap.hip; here is the chain (it needs the outlier filter, K7 and K7's sort) and the entry points.
+extern "C" void lio_height_map_default_config(lio_height_map_config* cfg)
+{
+    if (!cfg) return;
+    memset(cfg, 0, sizeof(*cfg));
+    cfg->roll = 0.0f; cfg->pitch = 0.0f;
+    cfg->level_and_ego_filter = 1;                         // GridMapPclLoader.cpp:80-85
+    cfg->remove_outliers = 1; cfg->mean_k = 10; cfg->stddev_mul = 1.0f;                  // parameters.yaml outlier_removal
+    cfg->downsample = 0; cfg->voxel[0] = cfg->voxel[1] = cfg->voxel[2] = 0.1f;           // downsampling
+    cfg->resolution = 0.2;                                 // grid_map
+    cfg->min_points_per_cell = 1; cfg->max_points_per_cell = 1000000000;
+    cfg->use_cluster = 0; cfg->cluster_tolerance = 1.0f;   // cluster_extraction
+    cfg->cluster_min_points = 1; cfg->cluster_max_points = 1000000000; cfg->use_max_height = 0;
+    cfg->fill_holes = 0;                                   // the reference as written
+}
+
+namespace {
+int height_map_check(const lio_height_map_config* c)
+{
+    const int32_t flags[] = { c->level_and_ego_filter, c->remove_outliers, c->downsample, c->use_cluster, c->use_max_height, c->fill_holes };
+    for (int32_t f : flags)
+        if (f != 0 && f != 1) return lio_fail(LIO_ERR_ARG, "the flags of lio_height_map_config are 0 or 1");
+    if (!std::isfinite(c->roll) || !std::isfinite(c->pitch)) return lio_fail(LIO_ERR_ARG, "roll and pitch must be finite");
+    if (!(c->resolution >= 1e-4) || !std::isfinite(c->resolution)) return lio_fail(LIO_ERR_ARG, "resolution must be at least 1e-4");
+    int rc = lio_sor_check(c->mean_k, c->stddev_mul);
+    if (rc != LIO_OK) return rc;
+    if (c->downsample) {                                   // K7 takes one leaf
+        if (!(c->voxel[0] > 0.0f) || !std::isfinite(c->voxel[0]) || c->voxel[1] != c->voxel[0] || c->voxel[2] != c->voxel[0])
+            return lio_fail(LIO_ERR_ARG, "downsample needs one positive, finite voxel size on all three axes");
+    }
+    if (c->min_points_per_cell < 0 || c->max_points_per_cell < 0 || c->cluster_min_points < 0 || c->cluster_max_points < 0)
+        return lio_fail(LIO_ERR_ARG, "point counts must not be negative");
+    if (c->use_cluster && (!(c->cluster_tolerance >= 0.0f) || !std::isfinite(c->cluster_tolerance)))
+        return lio_fail(LIO_ERR_ARG, "cluster_tolerance must be finite and not negative");
+    return LIO_OK;
+}
+
+// helpers.cpp:97-105 on a device-resident float4 cloud (w is not read): the reference's order, everything on the device, the
+// grid copy last.  Host waits, each for a number that sizes the next launch: outlier filter 3 (box, grid choice, compaction
+// count), voxel filter 2, ego filter 1, the box, and the grid copy with the counters.
+int height_map_device(const float4* d_in, int n, const lio_height_map_config* cfg, float* grid, size_t grid_cap, lio_height_map_info* info,
+                      hipStream_t s)
+{
+    int rc;
+    const float4* cur = d_in;
+    int n_cur = n;
+    LioTemp inl, ds, lev;
+    info->n_in = n;
+    if (cfg->remove_outliers) {                            // PointcloudProcessor.cpp:62-70
+        LioSorReport rep;
+        int n_inl = 0;
+        if ((rc = lio_sor_device(cur, n_cur, cfg->mean_k, cfg->stddev_mul, inl, &n_inl, nullptr, &rep, s)) < 0) return rc;
+        cur = inl.as<float4>(); n_cur = n_inl;
+    }
+    info->n_inliers = n_cur;
+    if (cfg->downsample && n_cur > 0) {                    // PointcloudProcessor.cpp:114-122
+        int n_ds = 0;
+        if ((rc = voxel_grid_device(cur, n_cur, cfg->voxel[0], ds, &n_ds, s)) < 0) return rc;
+        info->voxel_passthrough = rc == 1 ? 1 : 0;
+        cur = ds.as<float4>(); n_cur = n_ds;
+    }
+    float R1[9], R2[9];
+    lio_hm_rotations(cfg->roll, cfg->pitch, R1, R2);
+    int n_lev = 0;
+    if ((rc = lio_hm_level_ego(cur, n_cur, R1, R2, cfg->level_and_ego_filter, lev, &n_lev, s)) != LIO_OK) return rc;
+    cur = lev.as<float4>(); n_cur = n_lev;
+    info->n_filtered = n_cur;
+    if (n_cur == 0) return LIO_OK;                         // no point: no grid
+    float mn[3], mx[3];
+    LioTemp bbox;                                          // K7's box pass (k_vox_bbox)
+    if ((rc = cloud_box_launch(cur, n_cur, bbox, s)) != LIO_OK) return rc;
+    if ((rc = cloud_box_wait(bbox, mn, mx, s)) != LIO_OK) return rc;
+    HIPCHK(hipGetLastError());
+    LioHmGeom g;
+    lio_hm_geometry(mn, mx, cfg->resolution, &g);
+    info->rows = g.rows; info->cols = g.cols;
+    for (int a = 0; a < 2; ++a) { info->length[a] = g.length[a]; info->position[a] = g.position[a]; }
+    if (g.rows == 0 || g.cols == 0) return LIO_OK;         // (the reference asserts in GridMap::setGeometry)
+    if ((long long)g.rows * g.cols > 0x7fffffffLL - 1024) return lio_fail(LIO_ERR_CAPACITY, "the grid has more than 2^31 cells");
+    const size_t n_cells = (size_t)g.rows * (size_t)g.cols;
+    if (!grid) return LIO_OK;                              // the geometry only
+    if (n_cells > grid_cap) return lio_fail(LIO_ERR_ARG, "grid holds fewer cells than rows x cols (info)");
+    // ---- cells: keys, K7's stable sort (the key space: the cells and one key behind them), then lio_hm_grid
+    LioVoxWs<LioTemp> ws;
+    LioTemp counters;
+    const int n_blocks = (n_cur + LIO_VS_THREADS * 4 - 1) / (LIO_VS_THREADS * 4);
+    HIPCHK(ws.pairs_a.alloc(sizeof(uint2) * (size_t)n_cur));
+    HIPCHK(ws.pairs_b.alloc(sizeof(uint2) * (size_t)n_cur));
+    HIPCHK(ws.hist.alloc(sizeof(int) * (size_t)LIO_VS_BINS * n_blocks));
+    HIPCHK(ws.row_total.alloc(sizeof(int) * LIO_VS_BINS));
+    HIPCHK(counters.alloc(4 * sizeof(int)));
+    HIPCHK(hipMemsetAsync(counters.p, 0, 4 * sizeof(int), s));
+    lio_hm_launch_keys(cur, n_cur, g, ws.pairs_a.as<uint2>(), counters.as<int>(), s);
+    int bits = 1;
+    while (bits < 31 && (1LL << bits) < (long long)n_cells + 1) ++bits;
+    const uint2* sorted = vsort_pairs<LioTemp>(n_cur, bits, s, ws);
+    int hc[3] = { 0, 0, 0 };
+    if ((rc = lio_hm_grid(cur, sorted, n_cur, g, cfg, grid, counters.as<int>(), hc, s)) != LIO_OK) return rc;
+    info->n_binned = hc[0]; info->n_valid_cells = hc[1]; info->n_filled_cells = hc[2];
+    return LIO_OK;
+}
+}  // namespace
+
+extern "C" int lio_height_map(int32_t device_id, const void* pts, size_t n, size_t stride, const lio_height_map_config* cfg, float* grid,
+                              size_t grid_cap, lio_height_map_info* info)
+try {
+    if (!cfg || !info || (n && !pts)) return lio_fail(LIO_ERR_ARG, "null argument");
+    if (stride < 12 || (stride & 3)) return lio_fail(LIO_ERR_ARG, "stride must be >= 12 and a multiple of 4");
+    if (n > 0x7fffffffull - 1024) return lio_fail(LIO_ERR_CAPACITY, "cloud too large");
+    int rc = height_map_check(cfg);
+    if (rc != LIO_OK) return rc;
+    memset(info, 0, sizeof(*info));
+    if (n == 0) return LIO_OK;                             // an empty cloud: rows = cols = 0
+    if ((rc = check_device(device_id)) != LIO_OK) return rc;
+    hipStream_t s = nullptr;
+    LioTemp raw, xyzi;
+    HIPCHK(raw.alloc(n * stride));
+    HIPCHK(xyzi.alloc(n * sizeof(float4)));
+    HIPCHK(hipMemcpyAsync(raw.p, pts, n * stride, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_rec_to_xyzi4, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, raw.as<unsigned char>(), stride, (size_t)0, -1, (int)n,
+                       xyzi.as<float4>());
+    rc = height_map_device(xyzi.as<float4>(), (int)n, cfg, grid, grid_cap, info, s);
+    const hipError_t e = hipStreamSynchronize(s);          // (an early return: `raw` goes back to the pool when this returns)
+    if (rc < 0) return rc;                                 // the chain's own error comes first
+    HIPCHK(e);
+    return rc;
+} LIO_CATCH
+
+extern "C" int lio_kf_store_height_map(lio_kf_store* st, const lio_local_map_config* lm, const float* pose, const lio_height_map_config* cfg,
+                                       float* grid, size_t grid_cap, lio_local_map_info* lm_info, lio_height_map_info* info)
+try {
+    if (!st || !lm || !pose || !cfg || !info) return lio_fail(LIO_ERR_ARG, "null argument");
+    int rc = height_map_check(cfg);
+    if (rc != LIO_OK) return rc;
+    memset(info, 0, sizeof(*info));
+    hipStream_t s = nullptr;
+    LocalMapBufs B;
+    const float4* cur = nullptr;
+    int n_cur = 0;
+    if ((rc = local_map_device(st, lm, pose, B, &cur, &n_cur, nullptr, lm_info, s)) != LIO_OK) return rc;
+    if (n_cur == 0) return LIO_OK;                         // an empty store or an empty crop: rows = cols = 0
+    return height_map_device(cur, n_cur, cfg, grid, grid_cap, info, s);
 } LIO_CATCH
