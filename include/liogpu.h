@@ -423,9 +423,13 @@ int  lio_curvature(int32_t device_id, const float *range, size_t n, float *curva
  * cloud_info arrays (MSG:4-8) as the reference does.
  * cloud: extractedCloud records (x,y,z @0,4,8, intensity @16), n points, ring-major.
  * startRingIndex/endRingIndex: cfg->N_SCAN entries.  Rings must own disjoint, ascending index
- * windows [start-5, end+4] (what upstream's cloudExtraction produces); at most 4086 points per
- * ring and 1024 per sector; columns must fit int16.
+ * windows [start-5, end+4] (what upstream's cloudExtraction produces: start = first + 4,
+ * end = last - 5, so a ring's window is the ring and the cell before it); a window holds at most
+ * 4096 cells, i.e. 4096 points per ring (LIO_ERR_CAPACITY beyond); columns must fit int16.
+ * A ring reads and writes neighbor_picked / label inside its own window only.
  * corner_out: room for 120 * N_SCAN records (FE:171: <= 20 per sector); surface_out: room for n.
+ * Records have `stride_bytes` / `out_stride_bytes` (>= 20, multiples of 4); of an output record
+ * only x, y, z and intensity are meaningful: its other bytes are left as they were or set to zero.
  * curvature / neighbor_picked / label (each n entries, may be NULL) receive cloudCurvature,
  * cloudNeighborPicked and cloudLabel as the reference leaves them after the handler.
  * Defined here where the reference is not (see oracle/lio_oracle.c lo_extract_features): the

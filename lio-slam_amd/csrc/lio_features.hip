@@ -25,7 +25,6 @@ typedef unsigned long long u64;
 
 #define FEAT_BLOCK     256
 #define FEAT_MAX_RING  4096     // points of one ring window held in LDS
-#define FEAT_MAX_SECT  1024     // points of one sector (sorted at once)
 #define FEAT_MAX_PICK  120      // 6 sectors x 20 corners, FE:171
 
 // ---- per point: curvature FE:86-93 (0 outside [5, n-5)), flags cleared for the whole scan
@@ -185,7 +184,9 @@ __global__ __launch_bounds__(FEAT_BLOCK) void k_feat_ring(FeatParams P)
     const int start = P.start_ring[ring], end = P.end_ring[ring];
     if (threadIdx.x == 0) { P.corner_cnt[ring] = 0; P.surf_cnt[ring] = 0; }
     if (end < start) return;                                 // every sector has sp >= ep (FE:159)
-    const int w0 = max(start - 5, 0), w1 = min(end + 5, P.n - 1);           // window [w0, w1]
+    // The window the ring owns: picks lie in [start, end-1] and a suppression walk reaches five cells either way, reading the
+    // columns of no cell beyond.  Cell end+5 is the next ring's start-5: it is neither loaded nor written back here.
+    const int w0 = max(start - 5, 0), w1 = min(end + 4, P.n - 1);           // window [w0, w1]
     const int wl = w1 - w0 + 1;
     if (wl > FEAT_MAX_RING) { if (threadIdx.x == 0) atomicExch(P.status, 1); return; }
 
@@ -405,7 +406,8 @@ try {
         if (s < 0 || e > (long)n - 1) return lio_fail(LIO_ERR_ARG, "ring index range outside the cloud");
         if (s - 5 <= prev_hi) return lio_fail(LIO_ERR_ARG, "ring windows overlap or are not ascending");
         prev_hi = e + 4;
-        if (e - s + 11 > FEAT_MAX_RING) return lio_fail(LIO_ERR_CAPACITY, "more than 4086 points in one ring");
+        if (e - s + 10 > FEAT_MAX_RING)                                     // the window [s-5, e+4] is what k_feat_ring holds in LDS
+            return lio_fail(LIO_ERR_CAPACITY, "a ring window [start-5, end+4] holds more than 4096 points");
     }
     if (n == 0) return LIO_OK;
     for (size_t i = 0; i < n; ++i)
@@ -467,7 +469,7 @@ try {
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
     if (h_cnt[4 * (size_t)ns + 2] != 0)
-        return lio_fail(LIO_ERR_CAPACITY, "a ring window (> 4096 points) or a sector (> 1024 points) exceeds the LDS budget");
+        return lio_fail(LIO_ERR_CAPACITY, "a ring window [start-5, end+4] holds more than 4096 points");
     const size_t nc = (size_t)h_cnt[2 * (size_t)ns + ns], nsf = (size_t)h_cnt[3 * (size_t)ns + 1 + ns];
     if (nc) HIPCHK(hipMemcpy(corner_out, d_cout.p, nc * out_stride, hipMemcpyDeviceToHost));
     if (nsf) HIPCHK(hipMemcpy(surface_out, d_sout.p, nsf * out_stride, hipMemcpyDeviceToHost));
