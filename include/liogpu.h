@@ -770,6 +770,72 @@ int  lio_kf_store_height_map(lio_kf_store *s, const lio_local_map_config *lm, co
                              const lio_height_map_config *cfg, float *grid, size_t grid_cap,
                              lio_local_map_info *lm_info, lio_height_map_info *info);
 
+/* ------------------------------------------------ global map, map export, read-back (the last readers of surfCloudKeyFrames) */
+/* With the four calls below the store is the only owner of the keyframe clouds: a node needs no host copy of one to
+ * visualise, save or publish.  Rules that hold for all four:
+ *  - they leave the store and the handle as they found them -- they work in buffers of their own, kept between calls, on
+ *    private non-blocking streams; the map installed in a handle and the buffers of lio_assemble_map_nearby are not touched;
+ *  - they are complete when they return;
+ *  - calls on one store remain non-re-entrant: the node holds `mtx` around them, as MO:1010 does;
+ *  - lio_kf_store_global_map may upload the dirty range of the key-pose table (lio_kf_store_set_poses) on its own stream.
+ * DESIGN.md section 4f states the conventions (parity unpinned). */
+typedef struct lio_global_map_config {
+    float search_radius;   /* globalMapVisualizationSearchRadius  1000.0 */
+    float pose_density;    /* globalMapVisualizationPoseDensity   10.0   */
+    float leaf;            /* globalMapVisualizationLeafSize      1.0    */
+} lio_global_map_config;
+typedef struct lio_global_map_info {
+    int32_t n_keyframes, n_summed, n_out, voxel_passthrough;   /* kept list (duplicates included), its points, the map, 1: the
+                                                                * cloud filter's index overflows and the sum passes through */
+} lio_global_map_info;
+void lio_global_map_default_config(lio_global_map_config *cfg);
+/* publishGlobalMap MO:992-1041: lio_assemble_map_nearby with h == NULL, without the recent-keyframe suffix of MO:1544-1551
+ * and without reading a key-pose time: the radius set around the last key pose (d2 < (float)((double)R * R), ordered by
+ * (d2, i)), VoxelGrid at pose_density over (x, y, z, intensity = i) -- passed through when the voxel index overflows --,
+ * every centroid relabelled to its nearest key pose over all of them (ties to the lowest index), the recheck
+ * pointDistance > R of MO:1030 on the centroid's own coordinates, then the kept keyframes (duplicates included) under their
+ * stored poses, summed and voxel-filtered at `leaf`.  ids_out (may be NULL) receives the kept list, *n_ids its length; `out`
+ * (may be NULL: count only) holds out_cap PointXYZI records.  An empty store (MO:997): LIO_OK, *n_ids = 0, *n_out = 0.
+ * LIO_ERR_ARG for a keyframe without a pose, a non-finite or non-positive radius, density or leaf, ids_cap < *n_ids (the
+ * needed count is returned, nothing is built) and out_cap < *n_out (the needed count is returned).  info may be NULL. */
+int  lio_kf_store_global_map(lio_kf_store *s, const lio_global_map_config *cfg,
+                             int32_t *ids_out, int32_t ids_cap, int32_t *n_ids,
+                             void *out, size_t out_stride_bytes, size_t out_cap,
+                             size_t *n_out, lio_global_map_info *info);
+
+typedef struct lio_export_config {
+    float   resolution;    /* save_map.srv `resolution`; 0 = no filtered copy (MO:943) */
+    int32_t chunk_points;  /* points per transfer chunk of the unfiltered cloud; 0 = default (1 << 22) */
+} lio_export_config;
+/* saveMapService MO:935-962.  out_full receives globalSurfCloud: every keyframe 0 .. count - 1 in store order under its
+ * stored pose, always the sum of the keyframe sizes (GlobalMap.pcd; SurfMap.pcd when resolution is 0).  It is never
+ * materialised on the device: one kernel finds each point's keyframe, transforms it and writes chunk_points records at a
+ * time straight into one of two pinned staging buffers, and the host copies one chunk out while the next is written.  Device
+ * memory of this path: 92 bytes per keyframe (descriptor 64, pose 24, offset 4) plus the allocator's slack, whatever chunk_points is; pinned host memory: two chunks.  out_ds is written
+ * only when resolution != 0: lio_voxel_grid of that cloud at `resolution` (passed through on index overflow, reported in
+ * *voxel_passthrough).  The filtered copy DOES need the whole world-frame cloud on the device (16 bytes per point plus the
+ * sort's workspace): PCL's filter is a global sort.  Either output may be NULL: its count alone is returned.  LIO_ERR_ARG
+ * for a negative or non-finite resolution, chunk_points outside [256, 1 << 26] unless 0, a keyframe without a pose, and
+ * caps that are too small (*n_full and *n_ds hold the needed counts; nothing is written). */
+int  lio_kf_store_export_map(lio_kf_store *s, const lio_export_config *cfg,
+                             void *out_full, size_t full_stride_bytes, size_t full_cap, size_t *n_full,
+                             void *out_ds, size_t ds_stride_bytes, size_t ds_cap, size_t *n_ds,
+                             int32_t *voxel_passthrough);
+
+/* Keyframe `id` back from the store: bit for bit as stored (pose == NULL, lidar frame), or transformPointCloud of it under
+ * pose = [roll,pitch,yaw,x,y,z].  `out` may be NULL (count only).  LIO_ERR_ARG for an unknown id, a non-finite pose and
+ * out_cap < *n_out. */
+int  lio_kf_store_get_keyframe(lio_kf_store *s, int32_t id, const float *pose,
+                               void *out, size_t out_stride_bytes, size_t out_cap, size_t *n_out);
+
+/* publishFrames MO:2330-2345: transformPointCloud of a cloud the handle still has staged, under the final pose.
+ * LIO_STAGED_DS: the scan of batch slot 0 (laserCloudSurfLastDS -> cloud_registered); LIO_STAGED_RAW: the whole cloud of the
+ * last lio_s2m_register_raw (cloud_deskewed -> cloud_registered_raw).  Ordered behind the stream that wrote the staged cloud.
+ * LIO_ERR_ARG when nothing of that kind is staged, for a multi-device handle, a non-finite pose and out_cap < *n_out. */
+enum { LIO_STAGED_DS = 0, LIO_STAGED_RAW = 1 };
+int  lio_s2m_registered_cloud(lio_s2m_handle *h, int32_t which, const float pose[6],
+                              void *out, size_t out_stride_bytes, size_t out_cap, size_t *n_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -111,6 +111,15 @@ public:
                              imuRPYWeight, rotation_tollerance, z_tollerance);
     }
 
+    // publishFrames MO:2330-2345: cloud_registered (LIO_STAGED_DS) / cloud_registered_raw (LIO_STAGED_RAW) under the final
+    // pose, from the clouds still staged on the device; `out` holds out_cap pcl::PointXYZI records.  Returns the points written.
+    size_t registeredCloud(int32_t which, const float pose[6], void* out, size_t out_cap)
+    {
+        size_t n = 0;
+        check(lio_s2m_registered_cloud(h_, which, pose, out, 32, out_cap, &n), "lio_s2m_registered_cloud");
+        return n;
+    }
+
     lio_s2m_handle* handle() { return h_; }
 
 private:
@@ -200,6 +209,33 @@ public:
         if (cfg) c = *cfg; else lio_height_map_default_config(&c);
         check(lio_kf_store_height_map(s_, &lm, transformTobeMapped, &c, grid, grid_cap, lm_info, &info), "lio_kf_store_height_map");
         return (size_t)info.rows * (size_t)info.cols;
+    }
+    // publishGlobalMap MO:992-1041 from the stored poses and clouds; `out` holds out_cap pcl::PointXYZI records.  Returns the
+    // points written: what publishCloud(pubLaserCloudSurround, ...) MO:1040 sends.  cfg == nullptr: the yaml defaults.
+    size_t publishGlobalMap(void* out, size_t out_cap, const lio_global_map_config* cfg = nullptr, lio_global_map_info* info = nullptr)
+    {
+        lio_global_map_config c;
+        if (cfg) c = *cfg; else lio_global_map_default_config(&c);
+        int32_t n_ids = 0;
+        size_t n = 0;
+        check(lio_kf_store_global_map(s_, &c, nullptr, 0, &n_ids, out, 32, out_cap, &n, info), "lio_kf_store_global_map");
+        return n;
+    }
+    // saveMapService MO:935-962: globalSurfCloud into out_full (nullptr: its size only) and, when resolution != 0, its
+    // voxel-filtered copy into out_ds; both pcl::PointXYZI records.  chunk_points = 0: the default transfer chunk.
+    void exportMap(float resolution, void* out_full, size_t full_cap, size_t& n_full, void* out_ds, size_t ds_cap, size_t& n_ds,
+                   int32_t chunk_points = 0, int32_t* voxel_passthrough = nullptr)
+    {
+        const lio_export_config c = { resolution, chunk_points };
+        check(lio_kf_store_export_map(s_, &c, out_full, 32, full_cap, &n_full, out_ds, 32, ds_cap, &n_ds, voxel_passthrough),
+              "lio_kf_store_export_map");
+    }
+    // keyframe `id` as stored (pose6d == nullptr) or under a pose; returns its size (out == nullptr: the size only)
+    size_t getKeyframe(int32_t id, void* out, size_t out_cap, const float* pose6d = nullptr)
+    {
+        size_t n = 0;
+        check(lio_kf_store_get_keyframe(s_, id, pose6d, out, 32, out_cap, &n), "lio_kf_store_get_keyframe");
+        return n;
     }
     lio_kf_store* get() { return s_; }
 

@@ -12,7 +12,8 @@ from .api import (LioError, ScanToMap, S2MConfig, S2MResult, S2MProfile, DeskewC
                   NearbyConfig, nearby_default_config, IcpConfig, IcpResult, IcpClouds, ICP_STATES, icp_default_config, icp_align,
                   icp_debug_trace, ScConfig, ScResult, sc_default_config, sc_make, sc_distance,
                   LocalMapConfig, LocalMapInfo, sor_filter, local_map_default_config,
-                  HeightMapConfig, HeightMapInfo, height_map, height_map_default_config)
+                  HeightMapConfig, HeightMapInfo, height_map, height_map_default_config,
+                  GlobalMapConfig, GlobalMapInfo, ExportConfig, global_map_default_config, STAGED_DS, STAGED_RAW)
 
 __all__ = ["LioError", "ScanToMap", "S2MConfig", "S2MResult", "S2MProfile", "DeskewConfig",
            "lib_path", "load_library", "build_library", "deskew", "curvature", "imu_deskew_info",
@@ -21,4 +22,5 @@ __all__ = ["LioError", "ScanToMap", "S2MConfig", "S2MResult", "S2MProfile", "Des
            "NearbyConfig", "nearby_default_config", "IcpConfig", "IcpResult", "IcpClouds", "ICP_STATES", "icp_default_config", "icp_align",
            "icp_debug_trace", "ScConfig", "ScResult", "sc_default_config", "sc_make", "sc_distance",
            "LocalMapConfig", "LocalMapInfo", "sor_filter", "local_map_default_config",
-           "HeightMapConfig", "HeightMapInfo", "height_map", "height_map_default_config"]
+           "HeightMapConfig", "HeightMapInfo", "height_map", "height_map_default_config",
+           "GlobalMapConfig", "GlobalMapInfo", "ExportConfig", "global_map_default_config", "STAGED_DS", "STAGED_RAW"]

@@ -162,6 +162,22 @@ class HeightMapInfo(C.Structure):
                 ("n_valid_cells", C.c_int32), ("n_filled_cells", C.c_int32), ("voxel_passthrough", C.c_int32), ("pad", C.c_int32)]
 
 
+class GlobalMapConfig(C.Structure):
+    """publishGlobalMap's parameters, globalMapVisualization* of the yaml files (include/liogpu.h lio_global_map_config)."""
+    _fields_ = [("search_radius", C.c_float), ("pose_density", C.c_float), ("leaf", C.c_float)]
+
+
+class GlobalMapInfo(C.Structure):
+    _fields_ = [("n_keyframes", C.c_int32), ("n_summed", C.c_int32), ("n_out", C.c_int32), ("voxel_passthrough", C.c_int32)]
+
+
+class ExportConfig(C.Structure):
+    """saveMapService's resolution and the transfer chunk (include/liogpu.h lio_export_config)."""
+    _fields_ = [("resolution", C.c_float), ("chunk_points", C.c_int32)]
+
+
+STAGED_DS, STAGED_RAW = 0, 1
+
 ICP_STATES = {0: "NOT_CONVERGED", 1: "ITERATIONS", 2: "TRANSFORM", 3: "ABS_MSE", 4: "REL_MSE", 5: "NO_CORRESPONDENCES"}
 
 
@@ -205,6 +221,8 @@ EXPORTS = [
     "lio_kf_store_sc_add_from_handle", "lio_kf_store_sc_count", "lio_kf_store_sc_geometry", "lio_kf_store_sc_get", "lio_kf_store_sc_detect",
     "lio_sor_filter", "lio_local_map_default_config", "lio_kf_store_local_map",
     "lio_height_map_default_config", "lio_height_map", "lio_kf_store_height_map",
+    "lio_global_map_default_config", "lio_kf_store_global_map", "lio_kf_store_export_map", "lio_kf_store_get_keyframe",
+    "lio_s2m_registered_cloud",
 ]
 
 
@@ -332,6 +350,13 @@ def load_library():
     L.lio_height_map.argtypes = [i32, vp, sz, sz, C.POINTER(HeightMapConfig), vp, sz, C.POINTER(HeightMapInfo)]
     L.lio_kf_store_height_map.argtypes = [vp, C.POINTER(LocalMapConfig), C.POINTER(f32), C.POINTER(HeightMapConfig), vp, sz,
                                           C.POINTER(LocalMapInfo), C.POINTER(HeightMapInfo)]
+    L.lio_global_map_default_config.argtypes = [C.POINTER(GlobalMapConfig)]
+    L.lio_global_map_default_config.restype = None
+    L.lio_kf_store_global_map.argtypes = [vp, C.POINTER(GlobalMapConfig), C.POINTER(i32), i32, C.POINTER(i32), vp, sz, sz, C.POINTER(sz),
+                                          C.POINTER(GlobalMapInfo)]
+    L.lio_kf_store_export_map.argtypes = [vp, C.POINTER(ExportConfig), vp, sz, sz, C.POINTER(sz), vp, sz, sz, C.POINTER(sz), C.POINTER(i32)]
+    L.lio_kf_store_get_keyframe.argtypes = [vp, i32, C.POINTER(f32), vp, sz, sz, C.POINTER(sz)]
+    L.lio_s2m_registered_cloud.argtypes = [vp, i32, C.POINTER(f32), vp, sz, sz, C.POINTER(sz)]
     _LIB = L
     return L
 
@@ -430,6 +455,17 @@ class ScanToMap:
             o = out[:n_ds.value]
             return p, res, rc, np.concatenate([o[:, :3], o[:, 4:5]], 1)
         return p, res, rc, int(n_ds.value)
+
+    # publishFrames MO:2330-2345: the staged scan (STAGED_DS) or the whole staged cloud (STAGED_RAW) under the final pose
+    def registered_cloud(self, which, pose):
+        """-> [n,4] (x, y, z, intensity) in the frame of `pose`."""
+        p = np.ascontiguousarray(pose, np.float32).reshape(6)
+        n = C.c_size_t()
+        _check(self.lib.lio_s2m_registered_cloud(self.h, which, _f32p(p), None, 32, 0, C.byref(n)), "lio_s2m_registered_cloud")
+        out = np.zeros((max(n.value, 1), 8), np.float32)
+        _check(self.lib.lio_s2m_registered_cloud(self.h, which, _f32p(p), out.ctypes.data, 32, len(out), C.byref(n)),
+               "lio_s2m_registered_cloud")
+        return _from_records(out, n.value)
 
     # batched form
     def batch_upload(self, scans):
@@ -936,6 +972,22 @@ def local_map_default_config(**overrides):
     return cfg
 
 
+def global_map_default_config(**overrides):
+    cfg = GlobalMapConfig()
+    load_library().lio_global_map_default_config(C.byref(cfg))
+    for k, v in overrides.items():
+        if not hasattr(cfg, k):
+            raise AttributeError(k)
+        setattr(cfg, k, v)
+    return cfg
+
+
+def _from_records_stride(buf, n, stride):
+    """n records of `stride` bytes (x, y, z @0,4,8, intensity @16) in a uint8 buffer -> [n,4] float32."""
+    rec = buf[:n * stride].view(np.float32).reshape(n, stride // 4)
+    return np.concatenate([rec[:, :3], rec[:, 4:5]], axis=1).copy()
+
+
 def height_map_default_config(**overrides):
     cfg = HeightMapConfig()
     load_library().lio_height_map_default_config(C.byref(cfg))
@@ -1105,6 +1157,53 @@ class KeyframeStore:
             lambda g, cap, info: self.lib.lio_kf_store_height_map(self.h, C.byref(lm_cfg), _f32p(p), C.byref(cfg), g, cap, C.byref(lm_info),
                                                                   C.byref(info)), "lio_kf_store_height_map", want_grid)
         return grid, info, lm_info
+
+    def global_map(self, cfg=None, want_ids=True, want_output=True):   # publishGlobalMap, MO:992-1041
+        """-> (cloud [m,4] or None, ids (the kept list, duplicates included) or None, GlobalMapInfo)."""
+        cfg = cfg or global_map_default_config()
+        n = len(self)
+        ids = np.zeros(max(n, 1), np.int32) if want_ids else None        # without the recent suffix: at most one entry per pose
+        cap = max(sum(int(self.lib.lio_kf_store_points(self.h, i)) for i in range(n)), 1) if want_output else 0
+        while True:
+            out = np.zeros((cap, 8), np.float32) if want_output else None
+            n_ids, n_out, info = C.c_int32(), C.c_size_t(), GlobalMapInfo()
+            rc = self.lib.lio_kf_store_global_map(
+                self.h, C.byref(cfg), ids.ctypes.data_as(C.POINTER(C.c_int32)) if want_ids else None, len(ids) if want_ids else 0,
+                C.byref(n_ids), out.ctypes.data if want_output else None, 32, cap, C.byref(n_out), C.byref(info))
+            if want_output and rc == -1 and n_out.value > cap:    # (a keyframe selected twice: more map than one copy of every cloud)
+                cap = n_out.value
+                continue
+            _check(rc, "lio_kf_store_global_map")
+            break
+        return ((_from_records(out, n_out.value) if want_output else None), (ids[:n_ids.value].copy() if want_ids else None), info)
+
+    def export_map(self, resolution=0.0, chunk_points=0, stride=32, want_full=True, want_ds=True):   # saveMapService, MO:935-962
+        """-> (globalSurfCloud [n,4] or None, its filtered copy [m,4] or None (None when resolution == 0), (n_full, n_ds,
+        voxel_passthrough)).  A first call counts, a second fills."""
+        cfg = ExportConfig(float(resolution), int(chunk_points))
+        n_full, n_ds, vpt = C.c_size_t(), C.c_size_t(), C.c_int32()
+        _check(self.lib.lio_kf_store_export_map(self.h, C.byref(cfg), None, stride, 0, C.byref(n_full), None, stride, 0, C.byref(n_ds),
+                                                C.byref(vpt)), "lio_kf_store_export_map")
+        want_ds = want_ds and resolution != 0
+        if not (want_full or want_ds):
+            return None, None, (n_full.value, n_ds.value, vpt.value)
+        full = np.zeros(max(n_full.value, 1) * stride, np.uint8) if want_full else None
+        ds = np.zeros(max(n_ds.value, 1) * stride, np.uint8) if want_ds else None
+        _check(self.lib.lio_kf_store_export_map(self.h, C.byref(cfg), full.ctypes.data if want_full else None, stride, n_full.value,
+                                                C.byref(n_full), ds.ctypes.data if want_ds else None, stride, n_ds.value, C.byref(n_ds),
+                                                C.byref(vpt)), "lio_kf_store_export_map")
+        return ((_from_records_stride(full, n_full.value, stride) if want_full else None),
+                (_from_records_stride(ds, n_ds.value, stride) if want_ds else None), (n_full.value, n_ds.value, vpt.value))
+
+    def get_keyframe(self, kid, pose=None):           # surfCloudKeyFrames[kid], or transformPointCloud of it (MO:849-868)
+        """-> [n,4] (x, y, z, intensity): the stored cloud bit for bit, or under pose = [roll,pitch,yaw,x,y,z]."""
+        p = None if pose is None else np.ascontiguousarray(pose, np.float32).reshape(6)
+        pp = None if p is None else _f32p(p)
+        n = C.c_size_t()
+        _check(self.lib.lio_kf_store_get_keyframe(self.h, kid, pp, None, 32, 0, C.byref(n)), "lio_kf_store_get_keyframe")
+        out = np.zeros((max(n.value, 1), 8), np.float32)
+        _check(self.lib.lio_kf_store_get_keyframe(self.h, kid, pp, out.ctypes.data, 32, len(out), C.byref(n)), "lio_kf_store_get_keyframe")
+        return _from_records(out, n.value)
 
     def detect_loop(self, radius, time_diff, time_cur):   # detectLoopClosureDistance, MO:1271-1304
         """-> (key_cur, key_pre) or None."""

@@ -13,6 +13,7 @@
 
 #include "lio_handle.h"
 #include "lio_icp.h"
+#include "lio_kfstore.h"
 #include "lio_heightmap.h"
 #include "lio_localmap.h"
 #include "lio_pool.h"
@@ -25,14 +26,6 @@ int lio_s2m_set_map_device_xyzi(lio_s2m_handle* h, const float4* d_xyzi, size_t 
 int lio_s2m_set_map_device_bbox(lio_s2m_handle* h, const float4* d_xyzi, size_t n, const float box[6]);
 hipStream_t lio_s2m_stream_of(lio_s2m_handle* h);
 bool lio_s2m_takes_device_map(const lio_s2m_handle* h);
-
-struct LioKfDesc {       // one selected keyframe
-    int src;             // first point of the keyframe in the resident store
-    int first;           // first point in the concatenated world-frame cloud
-    int n;
-    int pad;
-    float T[12];         // pclPointToAffine3f of its pose (MO:856), filled on the device
-};
 
 // pose [roll,pitch,yaw,x,y,z] -> 3x4 transform, same trig definition as the GN loop
 __global__ void k_kf_transforms(LioKfDesc* __restrict__ kf, const float* __restrict__ poses, int n_kf)
@@ -145,10 +138,6 @@ __global__ void k_xyzi4_to_aos(const float4* __restrict__ src, int n, unsigned c
 }
 
 namespace {
-
-// B: LioTemp (pool temporaries, recycled when the call returns) or LioDevBytes (a workspace kept from one call to the next,
-// so that nothing has to be waited for before the call returns)
-template <class B> struct LioVoxWs { B bbox, large, pairs_a, pairs_b, hist, blk_heads, seg_start, d_no, row_total; };
 
 // Room for sorting n pairs and summing their segments (ws) and for n centroids (out).
 template <class B>
@@ -348,33 +337,7 @@ try {
 } LIO_CATCH
 
 // ------------------------------------------------------- resident keyframe store
-// surfCloudKeyFrames (MO:128): every keyframe cloud is uploaded ONCE (MO:2138-2142) and stays in
-// HBM; assembling the local map for a scan only needs the selected ids and their current poses.
-struct lio_kf_store {
-    ~lio_kf_store() { if (ev_ids) (void)hipEventDestroy(ev_ids); }   // (the buffers: on the device lio_kf_store_destroy sets)
-    int device_id = 0;
-    LioDevBuf<float4> d_pts;
-    size_t used = 0;
-    std::vector<size_t> off, cnt;
-    // workspace of lio_assemble_map_resident when the map is installed in a handle (kept between calls)
-    LioVoxWs<LioDevBytes> vws;
-    LioDevBytes world, ds, d_kf, d_poses, d_chunks, blk_box;
-    std::vector<LioKfDesc> v_kf;
-    std::vector<int2> v_chunks;
-    // key-pose table = cloudKeyPoses6D (x, y, z, roll, pitch, yaw, time): host copy written by lio_kf_store_set_poses (never
-    // blocks), device SoA next to off / cnt uploaded -- the dirty range only -- on the stream of the next selection
-    std::vector<float> px, py, pz, proll, ppitch, pyaw;
-    std::vector<double> ptime;
-    std::vector<unsigned char> has_pose, has_time;
-    size_t n_posed = 0, dirty_lo = SIZE_MAX, dirty_hi = 0, tab_cap = 0;
-    LioDevBytes d_tab;                               // [tab_cap] x 6 float, [tab_cap] double, [tab_cap] x 2 int
-    LioPinned<unsigned char> h_stage;                // the dirty range on its way up, then (n_ids, total), then ids
-    // workspace of lio_assemble_map_nearby's selection
-    LioVoxWs<LioDevBytes> nws;
-    LioDevBytes nb_pts, nb_cent, nb_cid, nb_ids, nb_meta;
-    hipEvent_t ev_ids = nullptr;
-    LioScStore sc;                                   // the Scan Context descriptors (lio_sc.hip), descriptor k = keyframe k
-};
+// struct lio_kf_store -- surfCloudKeyFrames (MO:128) in HBM -- is in lio_kfstore.h.
 
 extern "C" int lio_kf_store_create(int32_t device_id, lio_kf_store** out)
 try {
@@ -637,8 +600,6 @@ try {
 //   k_nb_compact   centroids, then the recent keyframes newest first, minus those beyond the radius (MO:1562); prefix sums
 //                  over cnt[id] and its 256-point chunks -> LioKfDesc records, poses, ids
 // One host wait: (n_ids, total points, chunks), which sizes the world-frame cloud.  DESIGN.md has the conventions.
-struct LioPoseTab { const float *x, *y, *z, *roll, *pitch, *yaw; const double* t; const int *off, *cnt; };
-struct LioNbMeta { int n_sel, recent_fail; unsigned box[6]; int n_ids, n_chunks; unsigned long long total; };
 
 static LioPoseTab pose_tab(lio_kf_store* st)
 {
@@ -658,6 +619,9 @@ __global__ void k_nb_init(LioNbMeta* m)
 
 // one thread per key pose: d2 to the last one, the radius flag (strict <, as FLANN's RadiusResultSet), the newest keyframe
 // that fails the recent test (atomic max: the suffix after it is what MO:1544-1551 appends), the box of the hits
+// RECENT = false: no recent suffix (publishGlobalMap MO:992-1041 has none) -- the key-pose times are not read and every
+// keyframe "fails" the recent test, so that the suffix k_nb_compact appends is empty
+template <bool RECENT>
 __global__ __launch_bounds__(256) void k_nb_select(LioPoseTab tab, int n, float r2, double time_cur, double window,
                                                    uint2* __restrict__ pairs, LioNbMeta* __restrict__ m)
 {
@@ -671,7 +635,8 @@ __global__ __launch_bounds__(256) void k_nb_select(LioPoseTab tab, int n, float 
         const float dx = x - lx, dy = y - ly, dz = z - lz;
         const float d2 = (dx * dx + dy * dy) + dz * dz;
         sel = d2 < r2;
-        if (!(time_cur - tab.t[i] < window)) fail = i;
+        if (!RECENT) fail = i;
+        else if (!(time_cur - tab.t[i] < window)) fail = i;
         pairs[i] = make_uint2(sel ? __float_as_uint(d2) : 0xffffffffu, (unsigned)i);
         if (sel) { mn[0] = mx[0] = x; mn[1] = mx[1] = y; mn[2] = mx[2] = z; }
     }
@@ -856,6 +821,44 @@ static int upload_pose_tab(lio_kf_store* st, hipStream_t s)
     return LIO_OK;
 }
 
+// the selection of lio_assemble_map_nearby and of lio_kf_store_global_map (lio_kfstore.h)
+int lio_mb_select(lio_kf_store* st, LioNbBufs& b, float R, float density, bool recent, double time_cur, double window, LioNbMeta* hm,
+                  hipStream_t s)
+{
+    int rc;
+    const int N = (int)st->off.size();
+    if ((rc = vsort_reserve<LioDevBytes>(N, b.cent, b.ws)) != LIO_OK) return rc;
+    HIPCHK(b.pts.alloc(sizeof(float4) * (size_t)N));
+    HIPCHK(b.cid.alloc(sizeof(unsigned long long) * (size_t)N));
+    HIPCHK(b.ids.alloc(sizeof(int) * 2 * (size_t)N));
+    HIPCHK(b.meta.alloc(sizeof(LioNbMeta)));
+    HIPCHK(b.d_kf.alloc(sizeof(LioKfDesc) * 2 * (size_t)N));    // the list holds at most n_vox + n_recent <= 2N entries
+    HIPCHK(b.d_poses.alloc(sizeof(float) * 6 * 2 * (size_t)N));
+    const LioPoseTab tab = pose_tab(st);
+    LioNbMeta* m = b.meta.as<LioNbMeta>();
+    const unsigned nblk = (unsigned)((N + 255) / 256);
+    hipLaunchKernelGGL(k_nb_init, dim3(1), dim3(1), 0, s, m);
+    const float r2 = (float)((double)R * (double)R);                // what PCL hands FLANN
+    if (recent) hipLaunchKernelGGL(k_nb_select<true>, dim3(nblk), dim3(256), 0, s, tab, N, r2, time_cur, window, b.ws.pairs_a.as<uint2>(), m);
+    else hipLaunchKernelGGL(k_nb_select<false>, dim3(nblk), dim3(256), 0, s, tab, N, r2, time_cur, window, b.ws.pairs_a.as<uint2>(), m);
+    uint2* hits = vsort_pairs<LioDevBytes>(N, 32, s, b.ws);      // (d2, i) ascending, the misses last
+    // (an even number of passes ends in pairs_a, where the second sort starts: k_nb_voxkeys rewrites the pairs in place)
+    if (hits != b.ws.pairs_a.as<uint2>()) return lio_fail(LIO_ERR_HIP, "radix sort ended in the wrong buffer");
+    hipLaunchKernelGGL(k_nb_voxkeys, dim3(nblk), dim3(256), 0, s, tab, N, 1.0f / density, m, hits, b.pts.as<float4>());
+    const uint2* vox = vsort_pairs<LioDevBytes>(N, 32, s, b.ws);
+    if ((rc = vsort_centroids<LioDevBytes>(b.pts.as<float4>(), vox, N, b.cent, s, b.ws)) != LIO_OK) return rc;
+    const int* d_no = b.ws.d_no.as<int>();
+    HIPCHK(hipMemsetAsync(b.cid.p, 0xff, sizeof(unsigned long long) * (size_t)N, s));
+    hipLaunchKernelGGL(k_nb_relabel, dim3((unsigned)((N + 63) / 64), (unsigned)((N + NB_SPLIT - 1) / NB_SPLIT)), dim3(64), 0, s, tab, N,
+                       b.cent.as<float4>(), m, d_no, b.cid.as<unsigned long long>());
+    hipLaunchKernelGGL(k_nb_compact, dim3(1), dim3(256), 0, s, tab, N, R, b.cent.as<float4>(), b.cid.as<unsigned long long>(), m, d_no,
+                       b.ids.as<int>(), b.d_kf.as<LioKfDesc>(), b.d_poses.as<float>());
+    HIPCHK(hipMemcpyAsync(hm, m, sizeof(LioNbMeta), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));                                // THE wait of the selection: (n_ids, total points, chunks)
+    HIPCHK(hipGetLastError());
+    return LIO_OK;
+}
+
 extern "C" int lio_assemble_map_nearby(lio_s2m_handle* h, lio_kf_store* st, const lio_nearby_config* cfg, double time_cur,
                                        float leaf, int32_t* ids_out, int32_t ids_cap, int32_t* n_ids, void* out,
                                        size_t out_stride, size_t out_cap, size_t* n_out)
@@ -880,36 +883,9 @@ try {
     hipStream_t s = node ? lio_s2m_stream_of(h) : nullptr;
     if ((rc = upload_pose_tab(st, s)) != LIO_OK) return rc;
     if (!st->ev_ids) HIPCHK(hipEventCreateWithFlags(&st->ev_ids, hipEventDisableTiming));
-    if ((rc = vsort_reserve<LioDevBytes>(N, st->nb_cent, st->nws)) != LIO_OK) return rc;
-    HIPCHK(st->nb_pts.alloc(sizeof(float4) * (size_t)N));
-    HIPCHK(st->nb_cid.alloc(sizeof(unsigned long long) * (size_t)N));
-    HIPCHK(st->nb_ids.alloc(sizeof(int) * 2 * (size_t)N));
-    HIPCHK(st->nb_meta.alloc(sizeof(LioNbMeta)));
-    HIPCHK(st->d_kf.alloc(sizeof(LioKfDesc) * 2 * (size_t)N));    // the list holds at most n_vox + n_recent <= 2N entries
-    HIPCHK(st->d_poses.alloc(sizeof(float) * 6 * 2 * (size_t)N));
-    const LioPoseTab tab = pose_tab(st);
-    LioNbMeta* m = st->nb_meta.as<LioNbMeta>();
-    const unsigned nblk = (unsigned)((N + 255) / 256);
-    hipLaunchKernelGGL(k_nb_init, dim3(1), dim3(1), 0, s, m);
-    const float r2 = (float)((double)R * (double)R);                // what PCL hands FLANN
-    hipLaunchKernelGGL(k_nb_select, dim3(nblk), dim3(256), 0, s, tab, N, r2, time_cur, cfg->recent_window_s,
-                       st->nws.pairs_a.as<uint2>(), m);
-    uint2* hits = vsort_pairs<LioDevBytes>(N, 32, s, st->nws);      // (d2, i) ascending, the misses last
-    // (an even number of passes ends in pairs_a, where the second sort starts: k_nb_voxkeys rewrites the pairs in place)
-    if (hits != st->nws.pairs_a.as<uint2>()) return lio_fail(LIO_ERR_HIP, "radix sort ended in the wrong buffer");
-    hipLaunchKernelGGL(k_nb_voxkeys, dim3(nblk), dim3(256), 0, s, tab, N, 1.0f / cfg->pose_density, m, hits, st->nb_pts.as<float4>());
-    const uint2* vox = vsort_pairs<LioDevBytes>(N, 32, s, st->nws);
-    if ((rc = vsort_centroids<LioDevBytes>(st->nb_pts.as<float4>(), vox, N, st->nb_cent, s, st->nws)) != LIO_OK) return rc;
-    const int* d_no = st->nws.d_no.as<int>();
-    HIPCHK(hipMemsetAsync(st->nb_cid.p, 0xff, sizeof(unsigned long long) * (size_t)N, s));
-    hipLaunchKernelGGL(k_nb_relabel, dim3((unsigned)((N + 63) / 64), (unsigned)((N + NB_SPLIT - 1) / NB_SPLIT)), dim3(64), 0, s, tab, N,
-                       st->nb_cent.as<float4>(), m, d_no, st->nb_cid.as<unsigned long long>());
-    hipLaunchKernelGGL(k_nb_compact, dim3(1), dim3(256), 0, s, tab, N, R, st->nb_cent.as<float4>(), st->nb_cid.as<unsigned long long>(), m, d_no,
-                       st->nb_ids.as<int>(), st->d_kf.as<LioKfDesc>(), st->d_poses.as<float>());
+    LioNbBufs nb = { st->nws, st->nb_pts, st->nb_cent, st->nb_cid, st->nb_ids, st->nb_meta, st->d_kf, st->d_poses };
     LioNbMeta* hm = (LioNbMeta*)st->h_stage.p;                        // (the stage exists: the first call uploaded through it)
-    HIPCHK(hipMemcpyAsync(hm, m, sizeof(LioNbMeta), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));                                // THE wait of the selection: (n_ids, total points, chunks)
-    HIPCHK(hipGetLastError());
+    if ((rc = lio_mb_select(st, nb, R, cfg->pose_density, true, time_cur, cfg->recent_window_s, hm, s)) != LIO_OK) return rc;
     const int n_sel = hm->n_ids, n_chunks = hm->n_chunks;
     const unsigned long long total = hm->total;
     if (n_ids) *n_ids = n_sel;
@@ -934,25 +910,7 @@ try {
 } LIO_CATCH
 
 // ------------------------------------------------ one callback on the device: downsample + register (SURVEY 8f / verdict r2)
-// Staged cloud and voxel-filter workspace of lio_s2m_register_raw, kept on the handle from one callback to the next.
-struct LioRawWs {
-    ~LioRawWs()
-    {
-        if (ev_in) (void)hipEventDestroy(ev_in);
-        if (ev_done) (void)hipEventDestroy(ev_done);
-        if (aux) (void)hipStreamDestroy(aux);
-    }
-    LioDevBytes raw, xyzi, ds;
-    LioVoxWs<LioDevBytes> vws;
-    // the upload and the voxel filter of the sweep run on a stream of their own: they do not depend on the local map, whose
-    // assembly (lio_assemble_map_resident: K6 + K7 + grid build, ~0.25 ms of small kernels) is usually still in flight on the
-    // handle's stream when the node calls lio_s2m_register_raw -- the two chains overlap on the GPU, and the filter's host
-    // waits (bounding box, voxel count) no longer wait for the map as well
-    hipStream_t aux = nullptr;
-    hipEvent_t ev_in = nullptr, ev_done = nullptr;
-    size_t n_raw = 0;                                // points of the whole cloud in `xyzi` (written on `aux`)
-    bool has_raw = false;
-};
+// (struct LioRawWs, the staged cloud and voxel-filter workspace kept on the handle, is in lio_kfstore.h)
 
 void lio_raw_ws_free(LioRawWs* w) { delete w; }
 
@@ -1589,3 +1547,35 @@ try {
     if (n_cur == 0) return LIO_OK;                         // an empty store or an empty crop: rows = cols = 0
     return height_map_device(cur, n_cur, cfg, grid, grid_cap, info, s);
 } LIO_CATCH
+
+// ------------------------------------------------ for lio_globalmap.hip (lio_kfstore.h): the global map, the map export,
+// the keyframe read-back and the registered clouds run this file's kernels through these launches
+int lio_mb_check_device(int device_id) { return check_device(device_id); }
+int lio_mb_upload_pose_tab(lio_kf_store* st, hipStream_t s) { return upload_pose_tab(st, s); }
+
+void lio_mb_launch_nb_chunks(const LioKfDesc* kf, int n_sel, int2* chunks, hipStream_t s)
+{
+    if (n_sel) hipLaunchKernelGGL(k_nb_chunks, dim3((unsigned)n_sel), dim3(64), 0, s, kf, chunks);
+}
+
+void lio_mb_launch_kf_transforms(LioKfDesc* kf, const float* poses, int n_kf, hipStream_t s)
+{
+    if (n_kf) hipLaunchKernelGGL(k_kf_transforms, dim3((unsigned)((n_kf + 63) / 64)), dim3(64), 0, s, kf, poses, n_kf);
+}
+
+void lio_mb_launch_transform_clouds(const float4* store, const LioKfDesc* kf, const int2* chunks, int n_chunks, float4* dst, hipStream_t s)
+{
+    if (n_chunks) hipLaunchKernelGGL(k_transform_clouds, dim3((unsigned)n_chunks), dim3(256), 0, s, store, kf, chunks, dst);
+}
+
+void lio_mb_launch_rec_to_xyzi4(const unsigned char* src, size_t stride, size_t xyz_off, int int_off, int n, float4* dst, hipStream_t s)
+{
+    if (n) hipLaunchKernelGGL(k_rec_to_xyzi4, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, stride, xyz_off, int_off, n, dst);
+}
+
+int lio_mb_voxel_grid(const float4* d_in, int n, float leaf, LioDevBytes& out, int* n_out, hipStream_t s, LioVoxWs<LioDevBytes>& ws)
+{
+    return voxel_grid_device<LioDevBytes>(d_in, n, leaf, out, n_out, s, ws, true, nullptr);
+}
+
+int lio_mb_copy_out(const float4* d_pts, int n, void* out, size_t out_stride, hipStream_t s) { return copy_out(d_pts, n, out, out_stride, s); }
