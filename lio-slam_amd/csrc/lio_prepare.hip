@@ -241,6 +241,7 @@ LIO_DEV int lio_ri_cell(const LioRangeImageParams& P, float x, float y, float z,
     const float at = (float)atan2((double)x, (double)y);
     const float at180 = at * 180;
     const float horizonAngle = (float)((double)at180 / 3.14159265358979323846);
+    if (horizonAngle != horizonAngle) return -1;   // NaN x or y: the (int) below is undefined for it (x86 gives INT_MIN and the point drops, this device 0)
     const float ang_res_x = (float)(360.0 / (double)(float)P.H);
     int col = (int)(-round(((double)horizonAngle - 90.0) / (double)ang_res_x) + (double)(P.H / 2));
     if (col >= P.H) col -= P.H;

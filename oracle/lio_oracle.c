@@ -1191,7 +1191,7 @@ int lo_voxel_grid(const float *in_xyzi, size_t n, float leaf, float *out_xyzi, s
  *   per input point, in order: range = |p|, drop if outside [lidarMinRange, lidarMaxRange]; row = ring,
  *   drop if outside [0, N_SCAN) or row % downsampleRate != 0; column from the azimuth,
  *   horizonAngle = atan2(x, y) * 180 / pi, col = -round((horizonAngle - 90) / (360 / H)) + H / 2,
- *   wrapped once, dropped if outside [0, H); a cell keeps the FIRST point that lands in it; that
+ *   wrapped once, dropped if outside [0, H) or if the azimuth is NaN; a cell keeps the FIRST point that lands in it; that
  *   point is deskewed (the reference transform comes from the first point that gets this far).
  *   cloudExtraction: ring-major, ascending column; startRingIndex = first - 1 + 5, endRingIndex =
  *   last - 5; pointColInd / pointRange per kept point (range of the RAW point).
@@ -1224,6 +1224,7 @@ size_t lo_range_image(const lo_deskew_config *cfg, int horizon_scan, float lidar
         float at = (float)atan2((double)px, (double)py);               /* atan2(float, float) */
         float at180 = at * 180;                                         /* float * int */
         float horizonAngle = (float)((double)at180 / M_PI);             /* ... / M_PI in double, stored as float */
+        if (isnan(horizonAngle)) continue;                              /* NaN x or y: (int)NaN below is undefined; x86's INT_MIN drops the point */
         int columnIdn = (int)(-round(((double)horizonAngle - 90.0) / (double)ang_res_x) + (double)(H / 2));
         if (columnIdn >= H) columnIdn -= H;
         if (columnIdn < 0 || columnIdn >= H) continue;
