@@ -770,6 +770,68 @@ int  lio_kf_store_height_map(lio_kf_store *s, const lio_local_map_config *lm, co
                              const lio_height_map_config *cfg, float *grid, size_t grid_cap,
                              lio_local_map_info *lm_info, lio_height_map_info *info);
 
+/* ------------------------------------------------ terrain layers (grid_map_filters' demo chain behind the height map) */
+/* grid_map_demos/config/filters_demo_filter_chain.yaml on the elevation grid: elevation -> smooth (MeanInRadiusFilter) ->
+ * surface normals (NormalVectorsFilter) -> slope -> roughness (MathExpressionFilter) -> edges
+ * (SlidingWindowMathExpressionFilter) -> traversability -> its two ThresholdFilters.  The input grid stands for the
+ * chain's `elevation_inpainted`: OpenCV's inpaint is not reproduced, fill_holes = 1 of the height map is the labelled
+ * substitute.  DESIGN.md section 4g states the conventions (parity unpinned: Eigen, EigenLab and grid_map are restated, not
+ * linked).  The defaults are the yaml's literal values, which are tuned for a 0.02 m grid: at the loader's 0.2 m resolution
+ * a node scales the three lengths (normal_radius, smooth_radius, edge_window_length) accordingly, by 10. */
+enum { LIO_TERRAIN_SMOOTH = 0, LIO_TERRAIN_NORMAL_X, LIO_TERRAIN_NORMAL_Y, LIO_TERRAIN_NORMAL_Z,
+       LIO_TERRAIN_SLOPE, LIO_TERRAIN_ROUGHNESS, LIO_TERRAIN_EDGES, LIO_TERRAIN_TRAVERSABILITY,
+       LIO_TERRAIN_N_LAYERS };
+typedef struct lio_terrain_config {
+    int32_t  normal_method;       /* 0 area (NormalVectorsFilter.cpp:195-251), 1 raster (:304-394)            */
+    int32_t  normal_axis;         /* normal_vector_positive_axis: 0 x, 1 y, 2 z                    2          */
+    double   normal_radius;       /* surface_normals.radius                                        0.05       */
+    double   smooth_radius;       /* mean_in_radius.radius                                         0.06       */
+    int32_t  edge_window_size;    /* window_size; 0 = derive from edge_window_length               0          */
+    double   edge_window_length;  /* edge_detection.window_length                                  0.05       */
+    float    slope_critical, roughness_critical;   /* the 0.6 and 0.1 of the traversability expression       */
+    float    slope_weight, roughness_weight;       /* 0.5, 0.5                                                */
+    uint32_t layers;              /* bit i set: layer i is copied out; default all                            */
+} lio_terrain_config;
+typedef struct lio_terrain_info {
+    int32_t rows, cols, n_valid_cells;      /* finite cells of the input layer                                */
+    int32_t normal_method_used;             /* 1 when area fell back to raster (radius <= 0, as :39-51 do)    */
+    int32_t n_normal_cells, n_few_points, n_degenerate;   /* normals written; nPoints < 3; eigenvalue(1) <= 1e-8 */
+    int32_t edge_window_size;               /* the odd size used                                              */
+} lio_terrain_info;
+void lio_terrain_default_config(lio_terrain_config *cfg);
+/* The chain on a host grid of rows x cols floats, column-major (grid_map::Matrix), NaN = no elevation; `length` and
+ * `position` are lio_height_map_info's; length[a] must equal size[a] * resolution.  `layers` (may be NULL: the
+ * counts only) receives the layers whose bit is set in cfg->layers, in enum order, each rows x cols floats, column-major,
+ * NaN = no value; layers_cap counts floats.  Fewer than (set bits) x rows x cols -> LIO_ERR_ARG with rows and cols
+ * filled in.  rows or cols 0: LIO_OK, nothing written.  Stage by stage:
+ *  - smooth, every cell: (float)(fp64 sum of the finite input values in the circle of smooth_radius / their count), NaN for
+ *    none.  A cell belongs to a circle iff dx dx + dy dy <= radius radius on the fp64 cell centres of GridMapMath.cpp:130-145,
+ *    visited in SubmapIterator order over the window of CircleIterator::findSubmapParameters;
+ *  - normals, area: from the fp64 sums of (x, y, z) and their products over the circle of normal_radius, the eigenvector of
+ *    the smallest eigenvalue of the covariance by SelfAdjointEigenSolver::computeDirect; UnitZ for fewer than 3 points or
+ *    eigenvalue(1) <= 1e-8; written where the centre cell is finite.  normal_radius <= 0 falls back to raster
+ *    (normal_method_used = 1).  Raster: the five-cell stencil on interior cells, also for a NaN centre between two valid
+ *    neighbours; none on a grid of fewer than 3 rows or columns.  Both are flipped towards normal_axis;
+ *  - slope = acosf(normal_z), roughness = fabsf(input - smooth);
+ *  - edges, every cell: the standard deviation of slope over the window of edge_window_size cells (odd; 0: derived from
+ *    edge_window_length as round(length / resolution), plus 1 when even), cropped at the borders, float, column-major;
+ *  - traversability = w_s (1 - slope / s_crit) + w_r (1 - roughness / r_crit) in float, then !(t >= 0) -> 0 and
+ *    !(t <= 1) -> 1 as the two ThresholdFilters do: a cell without slope or roughness ends at 0, not NaN.
+ * LIO_ERR_ARG, never a clamp: non-finite or negative radii, window length, criticals or weights; resolution < 1e-4 or
+ * non-finite geometry; a method or axis out of range; an even or negative edge_window_size; bits beyond the eight layers;
+ * a radius or half-window above 32 cells (the limit of the kernels' LDS tile halo). */
+int  lio_terrain_layers(int32_t device_id, const float *elevation, int32_t rows, int32_t cols, double resolution,
+                        const double length[2], const double position[2], const lio_terrain_config *cfg,
+                        float *layers, size_t layers_cap, lio_terrain_info *info);
+/* lio_kf_store_height_map's chain (same arguments, same grid bytes; `grid` may be NULL), then the chain above on the
+ * device grid it leaves: only the elevation grid (when grid != NULL) and the requested layers cross to the host.  hm->
+ * resolution is the grid's.  An empty store or an empty local map: LIO_OK, rows = cols = 0.  Complete on return.  What
+ * would follow cloudMapInfoHandler in a planning node. */
+int  lio_kf_store_terrain_map(lio_kf_store *s, const lio_local_map_config *lm, const float pose[6],
+                              const lio_height_map_config *hm, const lio_terrain_config *cfg,
+                              float *grid, size_t grid_cap, float *layers, size_t layers_cap,
+                              lio_local_map_info *lm_info, lio_height_map_info *hm_info, lio_terrain_info *info);
+
 /* ------------------------------------------------ global map, map export, read-back (the last readers of surfCloudKeyFrames) */
 /* With the four calls below the store is the only owner of the keyframe clouds: a node needs no host copy of one to
  * visualise, save or publish.  Rules that hold for all four:

@@ -210,6 +210,27 @@ public:
         check(lio_kf_store_height_map(s_, &lm, transformTobeMapped, &c, grid, grid_cap, lm_info, &info), "lio_kf_store_height_map");
         return (size_t)info.rows * (size_t)info.cols;
     }
+    // heightMap followed by grid_map_demos' filter chain (smooth, surface normals, slope, roughness, edges, traversability) on
+    // the device grid: `layers` holds layers_cap floats and receives the layers whose bit is set in cfg.layers, in
+    // LIO_TERRAIN_* order, each info.rows x info.cols, column-major, NaN = no value; `grid` (may be nullptr) the elevation.
+    // The defaults of lio_terrain_default_config are tuned for a 0.02 m grid: at the loader's 0.2 m pass a config with
+    // normal_radius, smooth_radius and edge_window_length scaled by 10.  Returns the number of cells.
+    size_t terrainMap(const float transformTobeMapped[6], float* grid, size_t grid_cap, float* layers, size_t layers_cap,
+                      lio_terrain_info& info, const lio_terrain_config* cfg = nullptr, const lio_height_map_config* hm_cfg = nullptr,
+                      const lio_local_map_config* lm_cfg = nullptr, lio_height_map_info* hm_info = nullptr,
+                      lio_local_map_info* lm_info = nullptr)
+    {
+        lio_local_map_config lm;
+        if (lm_cfg) lm = *lm_cfg; else lio_local_map_default_config(&lm);
+        lio_height_map_config hm;
+        if (hm_cfg) hm = *hm_cfg; else lio_height_map_default_config(&hm);
+        lio_terrain_config c;
+        if (cfg) c = *cfg; else lio_terrain_default_config(&c);
+        lio_height_map_info hi;
+        check(lio_kf_store_terrain_map(s_, &lm, transformTobeMapped, &hm, &c, grid, grid_cap, layers, layers_cap, lm_info,
+                                       hm_info ? hm_info : &hi, &info), "lio_kf_store_terrain_map");
+        return (size_t)info.rows * (size_t)info.cols;
+    }
     // publishGlobalMap MO:992-1041 from the stored poses and clouds; `out` holds out_cap pcl::PointXYZI records.  Returns the
     // points written: what publishCloud(pubLaserCloudSurround, ...) MO:1040 sends.  cfg == nullptr: the yaml defaults.
     size_t publishGlobalMap(void* out, size_t out_cap, const lio_global_map_config* cfg = nullptr, lio_global_map_info* info = nullptr)

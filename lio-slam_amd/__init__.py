@@ -13,6 +13,7 @@ from .api import (LioError, ScanToMap, S2MConfig, S2MResult, S2MProfile, DeskewC
                   icp_debug_trace, ScConfig, ScResult, sc_default_config, sc_make, sc_distance,
                   LocalMapConfig, LocalMapInfo, sor_filter, local_map_default_config,
                   HeightMapConfig, HeightMapInfo, height_map, height_map_default_config,
+                  TerrainConfig, TerrainInfo, TERRAIN_LAYERS, terrain_layers, terrain_default_config,
                   GlobalMapConfig, GlobalMapInfo, ExportConfig, global_map_default_config, STAGED_DS, STAGED_RAW)
 
 __all__ = ["LioError", "ScanToMap", "S2MConfig", "S2MResult", "S2MProfile", "DeskewConfig",
@@ -23,4 +24,5 @@ __all__ = ["LioError", "ScanToMap", "S2MConfig", "S2MResult", "S2MProfile", "Des
            "icp_debug_trace", "ScConfig", "ScResult", "sc_default_config", "sc_make", "sc_distance",
            "LocalMapConfig", "LocalMapInfo", "sor_filter", "local_map_default_config",
            "HeightMapConfig", "HeightMapInfo", "height_map", "height_map_default_config",
+           "TerrainConfig", "TerrainInfo", "TERRAIN_LAYERS", "terrain_layers", "terrain_default_config",
            "GlobalMapConfig", "GlobalMapInfo", "ExportConfig", "global_map_default_config", "STAGED_DS", "STAGED_RAW"]

@@ -162,6 +162,21 @@ class HeightMapInfo(C.Structure):
                 ("n_valid_cells", C.c_int32), ("n_filled_cells", C.c_int32), ("voxel_passthrough", C.c_int32), ("pad", C.c_int32)]
 
 
+TERRAIN_LAYERS = ("smooth", "normal_x", "normal_y", "normal_z", "slope", "roughness", "edges", "traversability")   # LIO_TERRAIN_*
+
+
+class TerrainConfig(C.Structure):
+    """grid_map_demos' filters_demo_filter_chain.yaml behind elevation_inpainted (include/liogpu.h lio_terrain_config)."""
+    _fields_ = [("normal_method", C.c_int32), ("normal_axis", C.c_int32), ("normal_radius", C.c_double), ("smooth_radius", C.c_double),
+                ("edge_window_size", C.c_int32), ("edge_window_length", C.c_double), ("slope_critical", C.c_float),
+                ("roughness_critical", C.c_float), ("slope_weight", C.c_float), ("roughness_weight", C.c_float), ("layers", C.c_uint32)]
+
+
+class TerrainInfo(C.Structure):
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("n_valid_cells", C.c_int32), ("normal_method_used", C.c_int32),
+                ("n_normal_cells", C.c_int32), ("n_few_points", C.c_int32), ("n_degenerate", C.c_int32), ("edge_window_size", C.c_int32)]
+
+
 class GlobalMapConfig(C.Structure):
     """publishGlobalMap's parameters, globalMapVisualization* of the yaml files (include/liogpu.h lio_global_map_config)."""
     _fields_ = [("search_radius", C.c_float), ("pose_density", C.c_float), ("leaf", C.c_float)]
@@ -221,6 +236,7 @@ EXPORTS = [
     "lio_kf_store_sc_add_from_handle", "lio_kf_store_sc_count", "lio_kf_store_sc_geometry", "lio_kf_store_sc_get", "lio_kf_store_sc_detect",
     "lio_sor_filter", "lio_local_map_default_config", "lio_kf_store_local_map",
     "lio_height_map_default_config", "lio_height_map", "lio_kf_store_height_map",
+    "lio_terrain_default_config", "lio_terrain_layers", "lio_kf_store_terrain_map",
     "lio_global_map_default_config", "lio_kf_store_global_map", "lio_kf_store_export_map", "lio_kf_store_get_keyframe",
     "lio_s2m_registered_cloud",
 ]
@@ -350,6 +366,12 @@ def load_library():
     L.lio_height_map.argtypes = [i32, vp, sz, sz, C.POINTER(HeightMapConfig), vp, sz, C.POINTER(HeightMapInfo)]
     L.lio_kf_store_height_map.argtypes = [vp, C.POINTER(LocalMapConfig), C.POINTER(f32), C.POINTER(HeightMapConfig), vp, sz,
                                           C.POINTER(LocalMapInfo), C.POINTER(HeightMapInfo)]
+    L.lio_terrain_default_config.argtypes = [C.POINTER(TerrainConfig)]
+    L.lio_terrain_default_config.restype = None
+    L.lio_terrain_layers.argtypes = [i32, vp, i32, i32, f64, C.POINTER(f64), C.POINTER(f64), C.POINTER(TerrainConfig), vp, sz,
+                                     C.POINTER(TerrainInfo)]
+    L.lio_kf_store_terrain_map.argtypes = [vp, C.POINTER(LocalMapConfig), C.POINTER(f32), C.POINTER(HeightMapConfig), C.POINTER(TerrainConfig),
+                                           vp, sz, vp, sz, C.POINTER(LocalMapInfo), C.POINTER(HeightMapInfo), C.POINTER(TerrainInfo)]
     L.lio_global_map_default_config.argtypes = [C.POINTER(GlobalMapConfig)]
     L.lio_global_map_default_config.restype = None
     L.lio_kf_store_global_map.argtypes = [vp, C.POINTER(GlobalMapConfig), C.POINTER(i32), i32, C.POINTER(i32), vp, sz, sz, C.POINTER(sz),
@@ -1030,6 +1052,40 @@ def height_map(xyz, cfg=None, want_grid=True, device_id=0):
                             "lio_height_map", want_grid)
 
 
+def terrain_default_config(**overrides):
+    cfg = TerrainConfig()
+    load_library().lio_terrain_default_config(C.byref(cfg))
+    for k, v in overrides.items():
+        if not hasattr(cfg, k):
+            raise AttributeError(k)
+        setattr(cfg, k, v)
+    return cfg
+
+
+def _terrain_layers_out(buf, info, mask):
+    """the requested layers of one call -> {name: [rows, cols] float32 (NaN: no value)}, column-major as grid_map::Matrix"""
+    n = info.rows * info.cols
+    names = [name for k, name in enumerate(TERRAIN_LAYERS) if (mask >> k) & 1]
+    return {name: buf[i * n:(i + 1) * n].reshape((info.rows, info.cols), order="F").copy(order="F") for i, name in enumerate(names)}
+
+
+# grid_map_demos' filter chain behind elevation_inpainted (DESIGN.md section 4g)
+def terrain_layers(grid, resolution, length, position, cfg=None, device_id=0):
+    """-> ({layer name: [rows, cols] float32}, TerrainInfo).  grid: [rows, cols] float32, NaN = no elevation; length and
+    position: those of the HeightMapInfo the grid came with."""
+    cfg = cfg or terrain_default_config()
+    g = np.asfortranarray(np.asarray(grid, np.float32))
+    if g.ndim != 2:
+        raise ValueError("grid must be [rows, cols]")
+    rows, cols = g.shape
+    buf = np.empty(max(bin(cfg.layers & 0xff).count("1") * rows * cols, 1), np.float32)
+    info = TerrainInfo()
+    ln, ps = (C.c_double * 2)(*length), (C.c_double * 2)(*position)
+    _check(load_library().lio_terrain_layers(device_id, g.ctypes.data, rows, cols, float(resolution), ln, ps, C.byref(cfg), buf.ctypes.data,
+                                             buf.size, C.byref(info)), "lio_terrain_layers")
+    return _terrain_layers_out(buf, info, cfg.layers), info
+
+
 # extractCloud, MO:1556-1588
 def assemble_map(clouds_xyzi, poses, leaf, s2m=None, device_id=0, want_output=True):
     recs = [_as_xyzi_records(c) for c in clouds_xyzi]
@@ -1157,6 +1213,31 @@ class KeyframeStore:
             lambda g, cap, info: self.lib.lio_kf_store_height_map(self.h, C.byref(lm_cfg), _f32p(p), C.byref(cfg), g, cap, C.byref(lm_info),
                                                                   C.byref(info)), "lio_kf_store_height_map", want_grid)
         return grid, info, lm_info
+
+    def terrain_map(self, pose, lm_cfg=None, hm_cfg=None, cfg=None, want_grid=True):   # height_map, then the filter chain on the device grid
+        """-> (elevation grid [rows, cols] or None, {layer name: [rows, cols]}, TerrainInfo, HeightMapInfo, LocalMapInfo).  One
+        call into buffers kept from the last one; a second only when the grid has outgrown them."""
+        lm_cfg = lm_cfg or local_map_default_config()
+        hm_cfg = hm_cfg or height_map_default_config()
+        cfg = cfg or terrain_default_config()
+        p = np.ascontiguousarray(pose, np.float32).reshape(6)
+        n_layers = bin(cfg.layers & 0xff).count("1")
+        lm_info, hm_info, info = LocalMapInfo(), HeightMapInfo(), TerrainInfo()
+        cells = _SCRATCH_CELLS.get("terrain_map", 1 << 16)
+        while True:
+            grid = _scratch("terrain_grid", (cells,))
+            layers = _scratch("terrain_layers", (max(cells * n_layers, 1),))
+            rc = self.lib.lio_kf_store_terrain_map(self.h, C.byref(lm_cfg), _f32p(p), C.byref(hm_cfg), C.byref(cfg),
+                                                   grid.ctypes.data if want_grid else None, grid.size, layers.ctypes.data, layers.size,
+                                                   C.byref(lm_info), C.byref(hm_info), C.byref(info))
+            if rc == -1 and info.rows * info.cols > cells:
+                cells = _SCRATCH_CELLS["terrain_map"] = info.rows * info.cols
+                continue
+            _check(rc, "lio_kf_store_terrain_map")
+            break
+        n = info.rows * info.cols
+        elev = grid[:n].reshape((info.rows, info.cols), order="F").copy(order="F") if want_grid else None
+        return elev, _terrain_layers_out(layers, info, cfg.layers), info, hm_info, lm_info
 
     def global_map(self, cfg=None, want_ids=True, want_output=True):   # publishGlobalMap, MO:992-1041
         """-> (cloud [m,4] or None, ids (the kept list, duplicates included) or None, GlobalMapInfo)."""

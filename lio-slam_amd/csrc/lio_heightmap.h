@@ -28,6 +28,7 @@ void lio_hm_launch_keys(const float4* d_pts, int n, const LioHmGeom& g, uint2* p
 
 // From the pairs stably sorted by cell: the elevation layer, the hole filling, the grid copied to `grid` (host, column-major
 // rows x cols) and counters[0..2] = points binned, cells with an elevation, cells filled.  `counters`: the device words
-// lio_hm_launch_keys added to.  Synchronous.
+// lio_hm_launch_keys added to.  Synchronous.  `keep` (optional): receives the device grid instead of the pool, for a caller
+// that goes on from it (the terrain layers); `grid` may then be NULL, and nothing but the counters crosses.
 int lio_hm_grid(const float4* d_pts, const uint2* d_sorted, int n, const LioHmGeom& g, const lio_height_map_config* cfg, float* grid,
-                int* counters, int h_counters[3], hipStream_t s);
+                int* counters, int h_counters[3], hipStream_t s, LioTemp* keep = nullptr);

@@ -15,6 +15,7 @@
 #include <math.h>
 #include <cmath>
 #include <string.h>
+#include <utility>
 
 #include "lio_heightmap.h"
 #include "lio_compact.h"
@@ -348,7 +349,7 @@ __global__ __launch_bounds__(256) void k_hm_fill(const float* __restrict__ pre, 
 }
 
 int lio_hm_grid(const float4* d_pts, const uint2* d_sorted, int n, const LioHmGeom& g, const lio_height_map_config* cfg, float* grid,
-                int* counters, int h_counters[3], hipStream_t s)
+                int* counters, int h_counters[3], hipStream_t s, LioTemp* keep)
 {
     const int n_cells = g.rows * g.cols;
     LioTemp range, sorted_pts, label, pre, post;
@@ -373,9 +374,10 @@ int lio_hm_grid(const float4* d_pts, const uint2* d_sorted, int n, const LioHmGe
     }
     hipLaunchKernelGGL(k_hm_fill, dim3((n_cells + 255) / 256), dim3(256), 0, s, pre.as<float>(), post.as<float>(), g.rows, g.cols,
                        cfg->fill_holes, counters);
-    HIPCHK(hipMemcpyAsync(grid, post.p, sizeof(float) * (size_t)n_cells, hipMemcpyDeviceToHost, s));
+    if (grid) HIPCHK(hipMemcpyAsync(grid, post.p, sizeof(float) * (size_t)n_cells, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(h_counters, counters, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
+    if (keep) std::swap(keep->p, post.p);                  // the caller goes on from the device grid (and owns it)
     return LIO_OK;
 }

@@ -18,6 +18,7 @@
 #include "lio_localmap.h"
 #include "lio_pool.h"
 #include "lio_sc.h"
+#include "lio_terrain.h"
 #include "lio_device_math.h"
 #include "lio_scan2.h"
 #include "lio_voxsort.h"
@@ -1443,9 +1444,10 @@ int height_map_check(const lio_height_map_config* c)
 
 // helpers.cpp:97-105 on a device-resident float4 cloud (w is not read): the reference's order, everything on the device, the
 // grid copy last.  Host waits, each for a number that sizes the next launch: outlier filter 3 (box, grid choice, compaction
-// count), voxel filter 2, ego filter 1, the box, and the grid copy with the counters.
+// count), voxel filter 2, ego filter 1, the box, and the grid copy with the counters.  `keep` (optional) receives the device
+// grid, which is then built whether or not `grid` is given.
 int height_map_device(const float4* d_in, int n, const lio_height_map_config* cfg, float* grid, size_t grid_cap, lio_height_map_info* info,
-                      hipStream_t s)
+                      hipStream_t s, LioTemp* keep = nullptr)
 {
     int rc;
     const float4* cur = d_in;
@@ -1484,8 +1486,8 @@ int height_map_device(const float4* d_in, int n, const lio_height_map_config* cf
     if (g.rows == 0 || g.cols == 0) return LIO_OK;         // (the reference asserts in GridMap::setGeometry)
     if ((long long)g.rows * g.cols > 0x7fffffffLL - 1024) return lio_fail(LIO_ERR_CAPACITY, "the grid has more than 2^31 cells");
     const size_t n_cells = (size_t)g.rows * (size_t)g.cols;
-    if (!grid) return LIO_OK;                              // the geometry only
-    if (n_cells > grid_cap) return lio_fail(LIO_ERR_ARG, "grid holds fewer cells than rows x cols (info)");
+    if (!grid && !keep) return LIO_OK;                     // the geometry only
+    if (grid && n_cells > grid_cap) return lio_fail(LIO_ERR_ARG, "grid holds fewer cells than rows x cols (info)");
     // ---- cells: keys, K7's stable sort (the key space: the cells and one key behind them), then lio_hm_grid
     LioVoxWs<LioTemp> ws;
     LioTemp counters;
@@ -1501,7 +1503,7 @@ int height_map_device(const float4* d_in, int n, const lio_height_map_config* cf
     while (bits < 31 && (1LL << bits) < (long long)n_cells + 1) ++bits;
     const uint2* sorted = vsort_pairs<LioTemp>(n_cur, bits, s, ws);
     int hc[3] = { 0, 0, 0 };
-    if ((rc = lio_hm_grid(cur, sorted, n_cur, g, cfg, grid, counters.as<int>(), hc, s)) != LIO_OK) return rc;
+    if ((rc = lio_hm_grid(cur, sorted, n_cur, g, cfg, grid, counters.as<int>(), hc, s, keep)) != LIO_OK) return rc;
     info->n_binned = hc[0]; info->n_valid_cells = hc[1]; info->n_filled_cells = hc[2];
     return LIO_OK;
 }
@@ -1546,6 +1548,37 @@ try {
     if ((rc = local_map_device(st, lm, pose, B, &cur, &n_cur, nullptr, lm_info, s)) != LIO_OK) return rc;
     if (n_cur == 0) return LIO_OK;                         // an empty store or an empty crop: rows = cols = 0
     return height_map_device(cur, n_cur, cfg, grid, grid_cap, info, s);
+} LIO_CATCH
+
+// The height map's chain, then the terrain layers (lio_terrain.hip) on the device grid it leaves: the same null stream, complete
+// on return.
+extern "C" int lio_kf_store_terrain_map(lio_kf_store* st, const lio_local_map_config* lm, const float* pose, const lio_height_map_config* hm,
+                                        const lio_terrain_config* cfg, float* grid, size_t grid_cap, float* layers, size_t layers_cap,
+                                        lio_local_map_info* lm_info, lio_height_map_info* hm_info, lio_terrain_info* info)
+try {
+    if (!st || !lm || !pose || !hm || !cfg || !hm_info || !info) return lio_fail(LIO_ERR_ARG, "null argument");
+    int rc = height_map_check(hm);
+    if (rc != LIO_OK) return rc;
+    LioTerrPlan plan;
+    if ((rc = lio_terrain_check(cfg, hm->resolution, &plan)) != LIO_OK) return rc;
+    memset(hm_info, 0, sizeof(*hm_info));
+    memset(info, 0, sizeof(*info));
+    info->normal_method_used = plan.method_used; info->edge_window_size = plan.window;
+    hipStream_t s = nullptr;
+    LocalMapBufs B;
+    const float4* cur = nullptr;
+    int n_cur = 0;
+    if ((rc = local_map_device(st, lm, pose, B, &cur, &n_cur, nullptr, lm_info, s)) != LIO_OK) return rc;
+    if (n_cur == 0) return LIO_OK;                         // an empty store or an empty crop: rows = cols = 0
+    LioTemp d_grid;
+    rc = height_map_device(cur, n_cur, hm, grid, grid_cap, hm_info, s, &d_grid);
+    info->rows = hm_info->rows; info->cols = hm_info->cols;
+    if (rc != LIO_OK) return rc;
+    if (!d_grid.p) return LIO_OK;                          // no point left or no extent along an axis: no grid, no layers
+    const size_t n_cells = (size_t)info->rows * (size_t)info->cols;
+    if (layers && (size_t)plan.n_out * n_cells > layers_cap) return lio_fail(LIO_ERR_ARG, "layers holds fewer floats than the requested layers (info)");
+    if ((rc = lio_terrain_set_geometry(&plan, info->rows, info->cols, hm->resolution, hm_info->length, hm_info->position)) != LIO_OK) return rc;
+    return lio_terrain_device(d_grid.as<float>(), plan, layers, info, s);
 } LIO_CATCH
 
 // ------------------------------------------------ for lio_globalmap.hip (lio_kfstore.h): the global map, the map export,

@@ -1,0 +1,69 @@
+"""The terrain layers' part of the C ABI without a GPU: the library exports the three symbols, the two ctypes structs match
+gcc's layout of include/liogpu.h, the defaults are the yaml's literals, and what can be refused before a device is touched
+is refused."""
+import ctypes as C
+import os
+import subprocess
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_symbols_are_exported(pkg):
+    lib = pkg.load_library()
+    for name in ("lio_terrain_default_config", "lio_terrain_layers", "lio_kf_store_terrain_map"):
+        assert hasattr(lib, name), name
+    assert lib.lio_version() == 102                            # the library only gained functions
+
+
+def test_struct_layouts_match_c(pkg):
+    cfg_fields = [n for n, _ in pkg.TerrainConfig._fields_]
+    info_fields = [n for n, _ in pkg.TerrainInfo._fields_]
+    lines = ['printf("%zu %zu\\n", sizeof(lio_terrain_config), sizeof(lio_terrain_info));']
+    lines += [f'printf("%zu\\n", offsetof(lio_terrain_config, {n}));' for n in cfg_fields]
+    lines += [f'printf("%zu\\n", offsetof(lio_terrain_info, {n}));' for n in info_fields]
+    lines += ['printf("%d %d %d\\n", LIO_TERRAIN_SMOOTH, LIO_TERRAIN_TRAVERSABILITY, LIO_TERRAIN_N_LAYERS);']
+    src = '#include <stdio.h>\n#include <stddef.h>\n#include "liogpu.h"\nint main(void) {\n' + "\n".join(lines) + "\nreturn 0; }\n"
+    with tempfile.TemporaryDirectory() as d:
+        c = os.path.join(d, "t.c")
+        open(c, "w").write(src)
+        exe = os.path.join(d, "t")
+        subprocess.check_call(["gcc", "-std=c11", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
+        out = [int(v) for v in subprocess.check_output([exe], text=True).split()]
+    assert out[:2] == [C.sizeof(pkg.TerrainConfig), C.sizeof(pkg.TerrainInfo)]
+    k = 2
+    assert out[k:k + len(cfg_fields)] == [getattr(pkg.TerrainConfig, n).offset for n in cfg_fields]
+    k += len(cfg_fields)
+    assert out[k:k + len(info_fields)] == [getattr(pkg.TerrainInfo, n).offset for n in info_fields]
+    assert out[-3:] == [0, 7, 8] and len(pkg.TERRAIN_LAYERS) == 8
+
+
+def test_defaults_are_the_yaml_literals(pkg):
+    cfg = pkg.terrain_default_config()
+    assert (cfg.normal_method, cfg.normal_axis, cfg.normal_radius, cfg.smooth_radius) == (0, 2, 0.05, 0.06)
+    assert (cfg.edge_window_size, cfg.edge_window_length) == (0, 0.05)
+    f32 = np.float32
+    assert (cfg.slope_critical, cfg.roughness_critical, cfg.slope_weight, cfg.roughness_weight) == (f32(0.6), f32(0.1), f32(0.5), f32(0.5))
+    assert cfg.layers == 0xff
+
+
+def test_refused_before_any_device(pkg):
+    """the configuration is checked first: LIO_ERR_ARG, not LIO_ERR_NO_DEVICE, on a machine without a GPU too; an empty grid
+    is LIO_OK without one"""
+    lib = pkg.load_library()
+    grid = np.zeros((4, 5), np.float32, order="F")
+    ln, ps = (C.c_double * 2)(4 * 0.2, 5 * 0.2), (C.c_double * 2)(0.0, 0.0)
+    info = pkg.TerrainInfo()
+    out = np.zeros(8 * 20, np.float32)
+    for kw in (dict(normal_method=2), dict(normal_axis=3), dict(smooth_radius=-0.1), dict(edge_window_size=4), dict(layers=0x100),
+               dict(smooth_radius=0.2 * 32.5), dict(slope_weight=float("nan"))):
+        cfg = pkg.terrain_default_config(**kw)
+        assert lib.lio_terrain_layers(0, grid.ctypes.data, 4, 5, 0.2, ln, ps, C.byref(cfg), out.ctypes.data, out.size, C.byref(info)) == -1, kw
+    cfg = pkg.terrain_default_config()
+    assert lib.lio_terrain_layers(0, grid.ctypes.data, 4, 5, 5e-5, ln, ps, C.byref(cfg), out.ctypes.data, out.size, C.byref(info)) == -1
+    assert lib.lio_terrain_layers(0, grid.ctypes.data, 4, 5, 0.2, ln, ps, C.byref(cfg), out.ctypes.data, 8 * 20 - 1, C.byref(info)) == -1
+    assert (info.rows, info.cols) == (4, 5)                    # too small a buffer: the size comes back
+    assert lib.lio_terrain_layers(0, None, 0, 5, 0.2, ln, ps, C.byref(cfg), out.ctypes.data, out.size, C.byref(info)) == 0
+    assert (info.rows, info.cols, info.edge_window_size) == (0, 5, 1)
