@@ -898,6 +898,69 @@ enum { LIO_STAGED_DS = 0, LIO_STAGED_RAW = 1 };
 int  lio_s2m_registered_cloud(lio_s2m_handle *h, int32_t which, const float pose[6],
                               void *out, size_t out_stride_bytes, size_t out_cap, size_t *n_out);
 
+/* ------------------------------------------------ occupancy grid for a planner (the fork's draft ogmGeneration.cpp, OG) */
+/* src/liorf/src/ogmGeneration.tar.xz holds the draft of the node that turns the saved map into a nav_msgs/OccupancyGrid:
+ * pcl::PassThrough on z (OG:74-93), pcl::RadiusOutlierRemoval (OG:96-112), SetMapTopicMsg (OG:115-188).  The draft does not
+ * compile as archived; its three stages and their parameters are reproduced on the device.  DESIGN.md section 4h states the
+ * conventions (parity unpinned: PCL and FLANN are restated, not linked). */
+/* pcl::RadiusOutlierRemoval: a point stays iff k_i > min_neighbors, k_i = the points j of the cloud, the point itself and
+ * its duplicates included, with d2 < r2; d2 = ((dx dx) + dy dy) + dz dz in fp32 without contraction (FLANN L2_Simple),
+ * r2 = (float)((double)radius * radius), the comparison strict (the radius search's, as lio_kf_store_global_map's).  Records
+ * as for lio_sor_filter: x,y,z @0,4,8, intensity @16 when stride >= 20 (else 0); out records are PointXYZI (out_stride >=
+ * 20); `out` (may be NULL: count only) holds n records.  Input order and intensity are kept.  Points with a non-finite
+ * coordinate (or one beyond 1e15 m, which the search grid leaves out) are dropped and are nobody's neighbour.  A cloud of at
+ * most min_neighbors such points loses all of them: there is no pass-through here.  n_neighbors (may be NULL): n ints, the
+ * exact k_i per input point, -1 for a dropped one; with NULL a lane may stop counting once k_i > min_neighbors -- the kept
+ * set is the same.  radius not finite or <= 0, min_neighbors < 0 -> LIO_ERR_ARG, nothing is clamped. */
+int  lio_radius_filter(int32_t device_id, const void *pts, size_t n, size_t stride_bytes, float radius, int32_t min_neighbors,
+                       void *out, size_t out_stride_bytes, size_t *n_out, int32_t *n_neighbors);
+
+typedef struct lio_ogm_config {
+    float   z_min, z_max;      /* thre_z_min, thre_z_max     OG:205-206  0.2, 2.0                                    */
+    int32_t z_negative;        /* flag_pass_through          OG:207      0; 1 keeps the outside of [z_min, z_max]   */
+    int32_t remove_outliers;   /* 1: OG:227 runs the filter unconditionally; 0 = the commented-out call of OG:230   */
+    float   radius;            /* thre_radius                OG:208      0.5                                         */
+    int32_t min_neighbors;     /* thres_point_count          OG:210      10                                          */
+    double  resolution;        /* map_resolution             OG:209      0.05                                        */
+    int32_t whole_box;         /* 0: as written; 1: labelled extension -- the box over every point, the last row filled */
+} lio_ogm_config;
+typedef struct lio_ogm_info {
+    int32_t width, height;     /* cells along x and y (nav_msgs/MapMetaData)                                          */
+    double  origin[2];         /* x_min, y_min                                                                        */
+    int32_t n_in, n_slice, n_inliers, n_binned, n_occupied, pad;   /* points given, after the slice, after the filter,
+                                                                    * points that marked a cell, cells of value 100   */
+} lio_ogm_info;
+void lio_ogm_default_config(lio_ogm_config *cfg);
+/* The draft's chain on a host cloud (records as above; intensity is not read).  Stage by stage:
+ *  - slice: pcl::PassThrough<PointXYZ> on z: points with a non-finite coordinate go first, then z_min <= z <= z_max stays
+ *    (both limits inclusive; z_negative = 1 keeps the others instead);
+ *  - filter: lio_radius_filter on what the slice left, when remove_outliers;
+ *  - raster as written (whole_box = 0): the box in fp64 over the points 0 .. n - 2 of the filtered cloud (the loop of OG:139
+ *    stops one short; a one-point cloud has that point as its box); width = (int)((x_max - x_min) / resolution), height
+ *    likewise; i = (int)(((double)x - x_min) / resolution), j likewise, toward zero; a point is skipped iff i < 0 ||
+ *    i >= width || j < 0 || j >= height - 1 (OG:181: the last row is never filled); grid[i + j * width] = 100, every other
+ *    cell 0, row-major as the message is;
+ *  - raster, whole_box = 1 (extension): the box over every point, and the test is j >= height.
+ * `grid` (may be NULL: geometry and counts only) holds grid_cap cells.  More cells than grid_cap -> LIO_ERR_ARG with width,
+ * height and origin filled in; more than 2^31 - 1 cells -> LIO_ERR_CAPACITY.  width or height 0, or an empty cloud at any
+ * stage: LIO_OK, the dimensions reported, nothing written.  LIO_ERR_ARG before any device is touched, never a clamp:
+ * resolution < 1e-4 or not finite, limits not finite or z_min > z_max, flags other than 0 / 1, and lio_radius_filter's
+ * refusals when remove_outliers.  info may be NULL.  Replaces the main() of the draft up to the message. */
+int  lio_occupancy_grid(int32_t device_id, const void *pts, size_t n, size_t stride_bytes, const lio_ogm_config *cfg,
+                        int8_t *grid, size_t grid_cap, lio_ogm_info *info);
+/* The same chain on the cloud the draft would load from GlobalMap.pcd, where lio_kf_store_export_map leaves it on the
+ * device: map_resolution (save_map.srv `resolution`) 0 = every keyframe under its stored pose, summed; any other value =
+ * that cloud through lio_voxel_grid at map_resolution.  *n_map (may be NULL) = its points.  Only the grid and the info cross
+ * to the host.  The rules stated above lio_global_map_config hold: the store and the handles are left as found, the result
+ * is complete on return, calls on one store remain non-re-entrant.  An empty store: LIO_OK, width = height = 0.  A keyframe
+ * without a pose, a negative or non-finite map_resolution: LIO_ERR_ARG. */
+int  lio_kf_store_occupancy_grid(lio_kf_store *s, float map_resolution, const lio_ogm_config *cfg,
+                                 int8_t *grid, size_t grid_cap, size_t *n_map, lio_ogm_info *info);
+/* Measurement hook (tools/ogm_cost.py): enable != 0 makes the calling thread's following chains record their stage
+ * boundaries as HIP events; ms (may be NULL) receives the last such chain's slice, grid build, search, compaction, raster and
+ * grid copy, in milliseconds. */
+int  lio_ogm_debug_stage_ms(int32_t enable, float ms[6]);
+
 #ifdef __cplusplus
 }
 #endif

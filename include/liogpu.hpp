@@ -258,6 +258,18 @@ public:
         check(lio_kf_store_get_keyframe(s_, id, pose6d, out, 32, out_cap, &n), "lio_kf_store_get_keyframe");
         return n;
     }
+    // The draft ogmGeneration.cpp on the map saveMapService would write at `map_resolution` (0: unfiltered): slice on z, radius
+    // outlier removal, raster.  `grid` holds grid_cap cells (nullptr: geometry and counts only) and receives info.width x
+    // info.height bytes, row-major, 100 = occupied: the data of a nav_msgs::OccupancyGrid whose info.resolution is
+    // cfg->resolution and whose origin is info.origin.  Returns the number of cells.  cfg == nullptr: the draft's defaults.
+    size_t occupancyGrid(float map_resolution, int8_t* grid, size_t grid_cap, lio_ogm_info& info, const lio_ogm_config* cfg = nullptr,
+                         size_t* n_map = nullptr)
+    {
+        lio_ogm_config c;
+        if (cfg) c = *cfg; else lio_ogm_default_config(&c);
+        check(lio_kf_store_occupancy_grid(s_, map_resolution, &c, grid, grid_cap, n_map, &info), "lio_kf_store_occupancy_grid");
+        return (size_t)info.width * (size_t)info.height;
+    }
     lio_kf_store* get() { return s_; }
 
 private:

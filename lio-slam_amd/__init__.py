@@ -14,7 +14,8 @@ from .api import (LioError, ScanToMap, S2MConfig, S2MResult, S2MProfile, DeskewC
                   LocalMapConfig, LocalMapInfo, sor_filter, local_map_default_config,
                   HeightMapConfig, HeightMapInfo, height_map, height_map_default_config,
                   TerrainConfig, TerrainInfo, TERRAIN_LAYERS, terrain_layers, terrain_default_config,
-                  GlobalMapConfig, GlobalMapInfo, ExportConfig, global_map_default_config, STAGED_DS, STAGED_RAW)
+                  GlobalMapConfig, GlobalMapInfo, ExportConfig, global_map_default_config, STAGED_DS, STAGED_RAW,
+                  OgmConfig, OgmInfo, ogm_default_config, radius_filter, occupancy_grid)
 
 __all__ = ["LioError", "ScanToMap", "S2MConfig", "S2MResult", "S2MProfile", "DeskewConfig",
            "lib_path", "load_library", "build_library", "deskew", "curvature", "imu_deskew_info",
@@ -25,4 +26,5 @@ __all__ = ["LioError", "ScanToMap", "S2MConfig", "S2MResult", "S2MProfile", "Des
            "LocalMapConfig", "LocalMapInfo", "sor_filter", "local_map_default_config",
            "HeightMapConfig", "HeightMapInfo", "height_map", "height_map_default_config",
            "TerrainConfig", "TerrainInfo", "TERRAIN_LAYERS", "terrain_layers", "terrain_default_config",
-           "GlobalMapConfig", "GlobalMapInfo", "ExportConfig", "global_map_default_config", "STAGED_DS", "STAGED_RAW"]
+           "GlobalMapConfig", "GlobalMapInfo", "ExportConfig", "global_map_default_config", "STAGED_DS", "STAGED_RAW",
+           "OgmConfig", "OgmInfo", "ogm_default_config", "radius_filter", "occupancy_grid"]

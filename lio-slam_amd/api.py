@@ -191,6 +191,17 @@ class ExportConfig(C.Structure):
     _fields_ = [("resolution", C.c_float), ("chunk_points", C.c_int32)]
 
 
+class OgmConfig(C.Structure):
+    """The parameters of the fork's draft ogmGeneration.cpp (include/liogpu.h lio_ogm_config)."""
+    _fields_ = [("z_min", C.c_float), ("z_max", C.c_float), ("z_negative", C.c_int32), ("remove_outliers", C.c_int32),
+                ("radius", C.c_float), ("min_neighbors", C.c_int32), ("resolution", C.c_double), ("whole_box", C.c_int32)]
+
+
+class OgmInfo(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("origin", C.c_double * 2), ("n_in", C.c_int32), ("n_slice", C.c_int32),
+                ("n_inliers", C.c_int32), ("n_binned", C.c_int32), ("n_occupied", C.c_int32), ("pad", C.c_int32)]
+
+
 STAGED_DS, STAGED_RAW = 0, 1
 
 ICP_STATES = {0: "NOT_CONVERGED", 1: "ITERATIONS", 2: "TRANSFORM", 3: "ABS_MSE", 4: "REL_MSE", 5: "NO_CORRESPONDENCES"}
@@ -239,6 +250,7 @@ EXPORTS = [
     "lio_terrain_default_config", "lio_terrain_layers", "lio_kf_store_terrain_map",
     "lio_global_map_default_config", "lio_kf_store_global_map", "lio_kf_store_export_map", "lio_kf_store_get_keyframe",
     "lio_s2m_registered_cloud",
+    "lio_radius_filter", "lio_ogm_default_config", "lio_occupancy_grid", "lio_kf_store_occupancy_grid", "lio_ogm_debug_stage_ms",
 ]
 
 
@@ -379,6 +391,12 @@ def load_library():
     L.lio_kf_store_export_map.argtypes = [vp, C.POINTER(ExportConfig), vp, sz, sz, C.POINTER(sz), vp, sz, sz, C.POINTER(sz), C.POINTER(i32)]
     L.lio_kf_store_get_keyframe.argtypes = [vp, i32, C.POINTER(f32), vp, sz, sz, C.POINTER(sz)]
     L.lio_s2m_registered_cloud.argtypes = [vp, i32, C.POINTER(f32), vp, sz, sz, C.POINTER(sz)]
+    L.lio_radius_filter.argtypes = [i32, vp, sz, sz, f32, i32, vp, sz, C.POINTER(sz), vp]
+    L.lio_ogm_default_config.argtypes = [C.POINTER(OgmConfig)]
+    L.lio_ogm_default_config.restype = None
+    L.lio_occupancy_grid.argtypes = [i32, vp, sz, sz, C.POINTER(OgmConfig), vp, sz, C.POINTER(OgmInfo)]
+    L.lio_kf_store_occupancy_grid.argtypes = [vp, f32, C.POINTER(OgmConfig), vp, sz, C.POINTER(sz), C.POINTER(OgmInfo)]
+    L.lio_ogm_debug_stage_ms.argtypes = [i32, C.POINTER(f32)]
     _LIB = L
     return L
 
@@ -1086,6 +1104,54 @@ def terrain_layers(grid, resolution, length, position, cfg=None, device_id=0):
     return _terrain_layers_out(buf, info, cfg.layers), info
 
 
+# pcl::RadiusOutlierRemoval of the draft ogmGeneration.cpp
+def radius_filter(xyzi, radius=0.5, min_neighbors=10, want_counts=True, device_id=0):
+    """-> (kept [m,4], n_neighbors [n] int32 with -1 for a dropped point, or None).  xyzi: [n,4] float32 (x, y, z, intensity).
+    want_counts = False runs the form that stops counting once a point is known to stay: the same kept set."""
+    rec = _as_xyzi_records(np.asarray(xyzi, np.float32).reshape(-1, 4))
+    n = len(rec)
+    out = np.zeros((max(n, 1), 8), np.float32)
+    cnt = np.zeros(max(n, 1), np.int32) if want_counts else None
+    n_out = C.c_size_t()
+    _check(load_library().lio_radius_filter(device_id, rec.ctypes.data, n, 32, float(radius), int(min_neighbors), out.ctypes.data, 32,
+                                            C.byref(n_out), cnt.ctypes.data if want_counts else None), "lio_radius_filter")
+    return _from_records(out, n_out.value), (cnt[:n].copy() if want_counts else None)
+
+
+def ogm_default_config(**overrides):
+    cfg = OgmConfig()
+    load_library().lio_ogm_default_config(C.byref(cfg))
+    for k, v in overrides.items():
+        if not hasattr(cfg, k):
+            raise AttributeError(k)
+        setattr(cfg, k, v)
+    return cfg
+
+
+def _ogm_call(call, what, want_grid):
+    """One call that asks for the geometry and the counts, a second that fills a grid of that size.  -> (grid [height, width]
+    int8, row-major as nav_msgs/OccupancyGrid.data, or None; OgmInfo)."""
+    info = OgmInfo()
+    _check(call(None, 0, info), what)
+    cells = info.width * info.height
+    if not want_grid or cells == 0:
+        return (np.zeros((info.height, info.width), np.int8) if want_grid else None), info
+    buf = np.zeros(cells, np.int8)
+    _check(call(buf.ctypes.data, buf.size, info), what)
+    return buf.reshape(info.height, info.width), info
+
+
+# the draft's main(): PassThroughFilter, RadiusOutlierFilter, SetMapTopicMsg (DESIGN.md section 4h)
+def occupancy_grid(xyz, cfg=None, want_grid=True, device_id=0):
+    """-> (grid [height, width] int8 (100 = occupied) or None, OgmInfo).  xyz: [n, >= 3] float32."""
+    cfg = cfg or ogm_default_config()
+    a = np.asarray(xyz, np.float32)
+    p = np.ascontiguousarray((a if a.ndim == 2 else a.reshape(-1, 3))[:, :3])
+    lib = load_library()
+    return _ogm_call(lambda g, cap, info: lib.lio_occupancy_grid(device_id, p.ctypes.data, len(p), 12, C.byref(cfg), g, cap, C.byref(info)),
+                     "lio_occupancy_grid", want_grid)
+
+
 # extractCloud, MO:1556-1588
 def assemble_map(clouds_xyzi, poses, leaf, s2m=None, device_id=0, want_output=True):
     recs = [_as_xyzi_records(c) for c in clouds_xyzi]
@@ -1275,6 +1341,15 @@ class KeyframeStore:
                                                 C.byref(vpt)), "lio_kf_store_export_map")
         return ((_from_records_stride(full, n_full.value, stride) if want_full else None),
                 (_from_records_stride(ds, n_ds.value, stride) if want_ds else None), (n_full.value, n_ds.value, vpt.value))
+
+    def occupancy_grid(self, map_resolution=0.0, cfg=None, want_grid=True):   # the draft ogmGeneration.cpp on the saved map
+        """-> (grid [height, width] int8 or None, OgmInfo, n_map = the points of the map the chain ran on)."""
+        cfg = cfg or ogm_default_config()
+        n_map = C.c_size_t()
+        grid, info = _ogm_call(lambda g, cap, info: self.lib.lio_kf_store_occupancy_grid(self.h, float(map_resolution), C.byref(cfg), g, cap,
+                                                                                         C.byref(n_map), C.byref(info)),
+                               "lio_kf_store_occupancy_grid", want_grid)
+        return grid, info, n_map.value
 
     def get_keyframe(self, kid, pose=None):           # surfCloudKeyFrames[kid], or transformPointCloud of it (MO:849-868)
         """-> [n,4] (x, y, z, intensity): the stored cloud bit for bit, or under pose = [roll,pitch,yaw,x,y,z]."""

@@ -3,6 +3,7 @@
 //   lio_kf_store_export_map    saveMapService    MO:935-962   (k_export_chunk: every keyframe under its stored pose, streamed out)
 //   lio_kf_store_get_keyframe  the read-back of one keyframe, as stored or under a pose
 //   lio_s2m_registered_cloud   publishFrames     MO:2330-2345 (K6 over a cloud the handle still has staged)
+//   lio_kf_store_occupancy_grid  the draft ogmGeneration.cpp on the cloud the export leaves on the device (lio_ogm.hip)
 // MO = the reference's src/liorf/src/mapOptmization.cpp.  -ffp-contract=off.
 //
 // All four leave the store and the handle as they found them: they work in LioGlobalWs (on the store) or in the pub_*
@@ -18,6 +19,7 @@
 
 #include "lio_handle.h"
 #include "lio_kfstore.h"
+#include "lio_ogm.h"
 
 int lio_s2m_staged_scan(lio_s2m_handle* h, int scan, const unsigned char** d_rec, size_t* n, size_t* stride, size_t* xyz_off, int* int_off,
                         int* device_id, hipStream_t* stream);   // liogpu_api.hip
@@ -318,6 +320,49 @@ try {
     HIPCHK(err);
     HIPCHK(hipGetLastError());
     return LIO_OK;
+} LIO_CATCH
+
+// The fork's draft ogmGeneration.cpp on the cloud it would load from GlobalMap.pcd: the export's world-frame sum
+// (map_resolution 0) or its filtered copy, where lio_kf_store_export_map leaves them -- g->world, g->ds -- then the chain of
+// lio_ogm.hip on g->s.  Only the grid and the info cross to the host.
+extern "C" int lio_kf_store_occupancy_grid(lio_kf_store* st, float map_resolution, const lio_ogm_config* cfg, int8_t* grid, size_t grid_cap,
+                                           size_t* n_map, lio_ogm_info* info)
+try {
+    lio_ogm_info local;
+    if (!info) info = &local;
+    memset(info, 0, sizeof(*info));
+    if (n_map) *n_map = 0;
+    if (!st || !cfg) return lio_fail(LIO_ERR_ARG, "null argument");
+    if (!(map_resolution >= 0.0f) || !std::isfinite(map_resolution)) return lio_fail(LIO_ERR_ARG, "map_resolution must be finite and not negative");
+    int rc = lio_ogm_check(cfg);
+    if (rc != LIO_OK) return rc;
+    if ((rc = lio_mb_check_device(st->device_id)) != LIO_OK) return rc;
+    const int N = (int)st->off.size();
+    if (N == 0) return LIO_OK;
+    if (st->n_posed != (size_t)N) return lio_fail(LIO_ERR_ARG, "a keyframe has no pose (lio_kf_store_set_poses)");
+    LioGlobalWs* g = nullptr;
+    if ((rc = global_ws(st, &g)) != LIO_OK) return rc;
+    size_t total = 0;
+    if ((rc = export_tables(st, g, 0, N, nullptr, &total)) != LIO_OK) return rc;
+    if (total > 0x7fffffffull - 1024) return lio_fail(LIO_ERR_CAPACITY, "too many points");
+    const float4* cloud = nullptr;
+    int n_cloud = (int)total;
+    if (total) {
+        HIPCHK(g->world.alloc(sizeof(float4) * total));
+        export_world(st, g, N, total, g->world.as<float4>());
+        cloud = g->world.as<float4>();
+        if (map_resolution != 0.0f) {                 // MO:943
+            int no = 0;
+            rc = lio_mb_voxel_grid(g->world.as<float4>(), (int)total, map_resolution, g->ds, &no, g->s, g->vws);
+            if (rc < 0) { (void)hipStreamSynchronize(g->s); return rc; }
+            cloud = g->ds.as<float4>(); n_cloud = no;
+        }
+    }
+    if (n_map) *n_map = (size_t)n_cloud;
+    rc = lio_ogm_device(cloud, n_cloud, *cfg, grid, grid_cap, info, g->s, lio_ogm_times_wanted());
+    (void)hipStreamSynchronize(g->s);                 // complete on return, whatever the chain returned
+    if (rc == LIO_OK) HIPCHK(hipGetLastError());
+    return rc;
 } LIO_CATCH
 
 extern "C" int lio_kf_store_get_keyframe(lio_kf_store* st, int32_t id, const float* pose, void* out, size_t out_stride, size_t out_cap,
