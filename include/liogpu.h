@@ -258,6 +258,11 @@ int  lio_s2m_get_corner_correspondences(lio_s2m_handle *h, int32_t scan, uint8_t
                                         float *coeff4, int32_t *nn_idx5);
 
 int  lio_s2m_get_profile(lio_s2m_handle *h, lio_s2m_profile *out);
+/* Which instantiation of the Gauss-Newton kernel the surface launches of the last run used: bit 0 = the plain one (one
+ * device, no map sharding, no correspondence record, no phase clock, no corner batch; LIO_PLAIN_KERNEL=0 in the environment
+ * when the handle is created forces the general one), bits 8.. = the waves per SIMD it was compiled for.  0 before any run
+ * and after a one-launch loop; negative = error. */
+int  lio_s2m_kernel_variant(const lio_s2m_handle *h);
 /* Test hook for the one-launch loop (cfg.pipeline 0 / 4): spin_max = polls before a workgroup waiting at its scan's barrier
  * gives up (0 = default: 4096, a few milliseconds; LIO_PERSIST_SPIN_MAX in the environment), withhold_wg = index of an
  * association workgroup that never arrives (-1 = none).  A launch that times out is re-run through the launch loop inside

@@ -251,6 +251,7 @@ EXPORTS = [
     "lio_global_map_default_config", "lio_kf_store_global_map", "lio_kf_store_export_map", "lio_kf_store_get_keyframe",
     "lio_s2m_registered_cloud",
     "lio_radius_filter", "lio_ogm_default_config", "lio_occupancy_grid", "lio_kf_store_occupancy_grid", "lio_ogm_debug_stage_ms",
+    "lio_s2m_kernel_variant",
 ]
 
 
@@ -298,6 +299,7 @@ def load_library():
     L.lio_s2m_set_degeneracy.argtypes = [vp, i32, C.POINTER(f32), i32]
     L.lio_s2m_get_correspondences.argtypes = [vp, i32, vp, vp, vp]
     L.lio_s2m_get_profile.argtypes = [vp, C.POINTER(S2MProfile)]
+    L.lio_s2m_kernel_variant.argtypes = [vp]
     L.lio_s2m_set_corner_map.argtypes = [vp, vp, sz, sz]
     L.lio_s2m_batch_upload_corners.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz), sz]
     L.lio_s2m_register_cs.argtypes = [vp, vp, sz, vp, sz, sz, C.POINTER(f32), C.POINTER(S2MResult)]
@@ -604,6 +606,12 @@ class ScanToMap:
         p = S2MProfile()
         _check(self.lib.lio_s2m_get_profile(self.h, C.byref(p)), "lio_s2m_get_profile")
         return p
+
+    def kernel_variant(self):
+        """(plain, waves): whether the last run's surface launches used the plain k_s2m_iterate, and its occupancy target."""
+        v = self.lib.lio_s2m_kernel_variant(self.h)
+        _check(min(v, 0), "lio_s2m_kernel_variant")
+        return bool(v & 1), v >> 8
 
     def debug_persist_spin(self, spin_max=0, withhold_wg=-1):
         """Test hook of the one-launch loop: poll bound and a workgroup that never arrives (include/liogpu.h)."""

@@ -99,8 +99,11 @@ struct lio_s2m_handle {
     hipGraphExec_t graph_exec = nullptr;
     bool graph_dirty = true;
     int graph_chunk = 0, graph_blocks = 0, graph_ppt = 0;
+    bool graph_plain = true;          // ... and the plain_kernel switch it was captured under
     LioIterParams graph_params;       // arguments the cached graph was captured with
     int units_this_run = 0, unit_iters = 1;
+    bool plain_kernel = true;         // LIO_PLAIN_KERNEL=0 in the environment at lio_s2m_create: always the general k_s2m_iterate (A/B runs)
+    int iterate_variant = 0;          // instantiation of the last run's surface launches (lio_s2m_kernel_variant)
 
     // correspondence record (debug / parity)
     LioDevBuf<unsigned char> d_rec_flag;

@@ -46,7 +46,9 @@ void lio_launch_map_occupancy(const LioGrid& g, const float* x, const float* y, 
 int  lio_scan_tiles(int n_cells);
 void lio_launch_init_state(LioScanState* st, int n_scans, float* poses, bool from_state, const LioConsts& c,
                            int* n_active, hipStream_t s);
-void lio_launch_iterate(const LioIterParams& P, int n_blocks, int ppt, bool stage, hipStream_t s, bool corner = false);
+// (both return the instantiation chosen: bit 0 = plain, bits 8.. = its occupancy target)
+int  lio_iterate_variant(const LioIterParams& P, int ppt, bool stage, bool corner, bool allow_plain);
+int  lio_launch_iterate(const LioIterParams& P, int n_blocks, int ppt, bool stage, hipStream_t s, bool corner = false, bool allow_plain = true);
 void lio_launch_persist(const LioIterParams& P, int n_blocks, unsigned* gen, unsigned epoch, const unsigned char* stage, size_t stride,
                         int n_scans, unsigned* spec, double* spec_sums, const float* poses0, unsigned spin_max, int withhold_wg, hipStream_t s);
 void lio_launch_pack_summary(const LioScanState* st, int n_scans, float* out, hipStream_t s);

@@ -756,8 +756,15 @@ LIO_DEV void lio_knn_lds(const float4* s_pts, const int* s_cell, int rx1, int ry
 }
 
 #ifndef LIO_MIN_WAVES
-#define LIO_MIN_WAVES 5      // waves per SIMD asked of the register allocator for the default instantiation (<= 96 VGPRs, no scratch;
-                             // measured: 4 -> 5 is -6 % time, 6 spills and is 20 % slower); the other instantiations keep 4
+#define LIO_MIN_WAVES 5      // waves per SIMD asked of the register allocator for the general one-point instantiation (<= 96 VGPRs; it
+                             // spills 18 SGPRs to lanes and 12 VGPRs to 52 B of scratch; measured: 4 -> 5 is -6 % time, 6 spills
+                             // inside the candidate loop and is 20 % slower); the other instantiations keep 4
+#endif
+#ifndef LIO_MIN_WAVES_PLAIN
+#define LIO_MIN_WAVES_PLAIN 6   // the same for the plain instantiation (see k_s2m_iterate; make EXTRA=-DLIO_MIN_WAVES_PLAIN=5 for the A/B).
+                                // Measured: 5 is +2.2 % registrations/s over the general kernel, 6 another +1.9 %.
+                                // 6 (<= 80 VGPRs, 30 spilled, all of them in lio_gn_step) is admissible only while tools/count_valu.py
+                                // shows no scratch access and no lane move between the kernel's entry and the arrival atomic
 #endif
 #define LIO_LDS_PTS   2048     // staged map points per workgroup (32 KiB)
 #define LIO_LDS_CELLS 4096     // staged run offsets (16 KiB)
@@ -772,9 +779,16 @@ LIO_DEV void lio_knn_lds(const float4* s_pts, const int* s_cell, int rx1, int ry
 // CORNER (extension): the same workgroup structure over the scan's EDGE points against
 // the corner map with the point-to-line association of upstream LIO-SAM; its rows join the same
 // per-scan sums (combineOptimizationCoeffs) through the partials of chunks n_surf_chunks.. .
-template <int PPT, bool STAGE, bool CORNER>
-__global__ __launch_bounds__(LIO_BLOCK, (PPT == 1 && !STAGE && !CORNER) ? LIO_MIN_WAVES : 4) void k_s2m_iterate(LioIterParams P)
+// PLAIN (only with PPT == 1, !STAGE, !CORNER; chosen by lio_launch_iterate): the batch path of one device -- no map sharding
+// (P.shard.axis < 0, P.blk_skip and P.sums_out null), no association record (P.rec_*, P.perm unused) and no phase clock
+// (P.stamps null) are compile-time facts instead of wave-uniform values held in SGPRs across the whole kernel.  Same code,
+// same arithmetic; the conditions below fold.
+template <int PPT, bool STAGE, bool CORNER, bool PLAIN>
+__global__ __launch_bounds__(LIO_BLOCK, PLAIN ? LIO_MIN_WAVES_PLAIN : ((PPT == 1 && !STAGE && !CORNER) ? LIO_MIN_WAVES : 4))
+void k_s2m_iterate(LioIterParams P)
 {
+    static_assert(!PLAIN || (PPT == 1 && !STAGE && !CORNER), "the plain instantiation is the one-point, unstaged surface kernel");
+    const bool sharded = !PLAIN && P.shard.axis >= 0;
     __shared__ __attribute__((aligned(16))) double s_rows[LIO_BLOCK][8];  // [arz ary arx cx cy cz | -cw | accepted], widened once
     __shared__ double s_part[8][28];
     __shared__ double s_sum[28];
@@ -796,7 +810,7 @@ __global__ __launch_bounds__(LIO_BLOCK, (PPT == 1 && !STAGE && !CORNER) ? LIO_MI
     }
     // map sharding, decided per workgroup by k_shard_cull: 1 = it has already reported for this workgroup (not ours),
     // 2 = the WHOLE workgroup is ours (no per-point ownership test), 0 = per-point ownership
-    const int wg_mode = P.blk_skip != nullptr ? (int)P.blk_skip[wg] : 0;
+    const int wg_mode = (!PLAIN && P.blk_skip != nullptr) ? (int)P.blk_skip[wg] : 0;
     if (wg_mode == 1) return;
     const LioBlockDesc bd = P.blocks[wg];
     LioScanState* st = &P.state[bd.scan];
@@ -817,11 +831,11 @@ __global__ __launch_bounds__(LIO_BLOCK, (PPT == 1 && !STAGE && !CORNER) ? LIO_MI
     const int base = CORNER ? st->c_offset : st->offset;
     const int st_iter = st->iter;
     // diagnostic phase clock (P.stamps is null outside profiling experiments)
-    long long* stamp = P.stamps ? P.stamps + ((size_t)wg * (LIO_BLOCK / 64) + (threadIdx.x >> 6)) * 8 : nullptr;
+    long long* stamp = (!PLAIN && P.stamps) ? P.stamps + ((size_t)wg * (LIO_BLOCK / 64) + (threadIdx.x >> 6)) * 8 : nullptr;
 #define LIO_STAMP(k) do { if (stamp && (threadIdx.x & 63) == 0) stamp[k] = (long long)__builtin_readcyclecounter(); } while (0)
     LIO_STAMP(0);
 
-    const bool record = (P.rec_flag != nullptr) && (st_iter == P.c.record_iter);
+    const bool record = !PLAIN && (P.rec_flag != nullptr) && (st_iter == P.c.record_iter);
     const bool use_cache = (P.d5_cache != nullptr) && !STAGE && st_iter > 0;   // iteration 0 has nothing to re-use
     const LioGrid g = P.grid;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -841,7 +855,7 @@ __global__ __launch_bounds__(LIO_BLOCK, (PPT == 1 && !STAGE && !CORNER) ? LIO_MI
         qy[pp] = T[4] * px[pp] + T[5] * py[pp] + T[6]  * pz[pp] + T[7];
         qz[pp] = T[8] * px[pp] + T[9] * py[pp] + T[10] * pz[pp] + T[11];
         bool a = inr[pp];
-        if (P.shard.axis >= 0 && wg_mode != 2) {                     // owner-computes (multi-GPU)
+        if (sharded && wg_mode != 2) {                               // owner-computes (multi-GPU)
             const float qa = P.shard.axis == 0 ? qx[pp] : (P.shard.axis == 1 ? qy[pp] : qz[pp]);
             int gc = lio_cell_coord(qa, P.shard.gorigin, P.shard.inv_cell, P.shard.gdim);
             gc = min(max(gc, 0), P.shard.gdim - 1);
@@ -865,7 +879,7 @@ __global__ __launch_bounds__(LIO_BLOCK, (PPT == 1 && !STAGE && !CORNER) ? LIO_MI
 
     // A workgroup none of whose points is active (typically: owned by other ranks) only reports
     // an all-zero partial sum and leaves.
-    if (P.shard.axis >= 0) {
+    if (sharded) {
         bool any = false;
 #pragma unroll
         for (int pp = 0; pp < PPT; ++pp) any = any || act[pp];
@@ -879,7 +893,7 @@ __global__ __launch_bounds__(LIO_BLOCK, (PPT == 1 && !STAGE && !CORNER) ? LIO_MI
             if (wave != 0) return;
             double* part0 = P.partials + ((size_t)bd.scan * P.max_blk + bd.blk) * LIO_SUMS;
             if (lane < 28) __hip_atomic_store(part0 + lane, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            lio_arrive_and_finish(P, bd, st, lane, s_sum, &s_ws, stamp);   // (recorded flags stay "rejected")
+            lio_arrive_and_finish<PLAIN>(P, bd, st, lane, s_sum, &s_ws, stamp);   // (recorded flags stay "rejected")
             return;
         }
     }
@@ -1050,7 +1064,7 @@ __global__ __launch_bounds__(LIO_BLOCK, (PPT == 1 && !STAGE && !CORNER) ? LIO_MI
         // write-through (sc1) store: visible to the other XCDs without a release fence
         __hip_atomic_store(part + lane, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    lio_arrive_and_finish(P, bd, st, lane, s_sum, &s_ws, stamp);
+    lio_arrive_and_finish<PLAIN>(P, bd, st, lane, s_sum, &s_ws, stamp);
     LIO_STAMP(7);
 #undef LIO_STAMP
 }
@@ -1230,27 +1244,42 @@ void lio_launch_init_state(LioScanState* st, int n_scans, float* poses, bool fro
     hipLaunchKernelGGL(k_s2m_init_state<false>, dim3((n_scans + 63) / 64), dim3(64), 0, s, st, n_scans, poses, fs, c, n_active);
 }
 
-void lio_launch_iterate(const LioIterParams& P, int n_blocks, int ppt, bool stage, hipStream_t s, bool corner)
+// The instantiation a launch with these arguments gets: bit 0 = the plain one, bits 8.. = its occupancy target.  A pure function
+// of its arguments (`allow_plain`: the handle's LIO_PLAIN_KERNEL switch), so launches captured into a graph stay valid as long
+// as P and the switch do.
+int lio_iterate_variant(const LioIterParams& P, int ppt, bool stage, bool corner, bool allow_plain)
 {
-    if (n_blocks <= 0) return;
+    const bool plain = allow_plain && ppt == 1 && !stage && !corner && P.shard.axis < 0 && P.blk_skip == nullptr &&
+                       P.sums_out == nullptr && P.rec_flag == nullptr && P.stamps == nullptr;
+    if (plain) return 1 | (LIO_MIN_WAVES_PLAIN << 8);
+    return ((ppt == 1 && !stage && !corner) ? LIO_MIN_WAVES : 4) << 8;
+}
+
+int lio_launch_iterate(const LioIterParams& P, int n_blocks, int ppt, bool stage, hipStream_t s, bool corner, bool allow_plain)
+{
+    const int variant = lio_iterate_variant(P, ppt, stage, corner, allow_plain);
+    if (n_blocks <= 0) return variant;
     const dim3 gr(n_blocks), bl(LIO_BLOCK);
     if (corner) {                      // extension: edge points, always one point per thread from global memory
-        hipLaunchKernelGGL((k_s2m_iterate<1, false, true>), gr, bl, 0, s, P);
-        return;
+        hipLaunchKernelGGL((k_s2m_iterate<1, false, true, false>), gr, bl, 0, s, P);
+        return variant;
     }
     if (stage) {
         switch (ppt) {
-        case 1: hipLaunchKernelGGL((k_s2m_iterate<1, true, false>), gr, bl, 0, s, P); break;
-        case 2: hipLaunchKernelGGL((k_s2m_iterate<2, true, false>), gr, bl, 0, s, P); break;
-        default: hipLaunchKernelGGL((k_s2m_iterate<4, true, false>), gr, bl, 0, s, P); break;
+        case 1: hipLaunchKernelGGL((k_s2m_iterate<1, true, false, false>), gr, bl, 0, s, P); break;
+        case 2: hipLaunchKernelGGL((k_s2m_iterate<2, true, false, false>), gr, bl, 0, s, P); break;
+        default: hipLaunchKernelGGL((k_s2m_iterate<4, true, false, false>), gr, bl, 0, s, P); break;
         }
+    } else if (variant & 1) {
+        hipLaunchKernelGGL((k_s2m_iterate<1, false, false, true>), gr, bl, 0, s, P);
     } else {
         switch (ppt) {
-        case 1: hipLaunchKernelGGL((k_s2m_iterate<1, false, false>), gr, bl, 0, s, P); break;
-        case 2: hipLaunchKernelGGL((k_s2m_iterate<2, false, false>), gr, bl, 0, s, P); break;
-        default: hipLaunchKernelGGL((k_s2m_iterate<4, false, false>), gr, bl, 0, s, P); break;
+        case 1: hipLaunchKernelGGL((k_s2m_iterate<1, false, false, false>), gr, bl, 0, s, P); break;
+        case 2: hipLaunchKernelGGL((k_s2m_iterate<2, false, false, false>), gr, bl, 0, s, P); break;
+        default: hipLaunchKernelGGL((k_s2m_iterate<4, false, false, false>), gr, bl, 0, s, P); break;
         }
     }
+    return variant;
 }
 
 void lio_launch_pack_summary(const LioScanState* st, int n_scans, float* out, hipStream_t s)

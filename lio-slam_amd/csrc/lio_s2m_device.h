@@ -415,6 +415,8 @@ static __constant__ int c_pair_b[32] = { 0,1,2,3,4,5, 1,2,3,4,5, 2,3,4,5, 3,4,5,
 // Tail of an association workgroup, executed by its wave 0 after the partial sums were stored
 // write-through: drain, arrive on the scan's counter; the workgroup whose arrival is last adds up
 // the scan's partials in workgroup order and runs the Gauss-Newton step (or publishes the sums).
+// PLAIN: P.sums_out is known to be null (the caller solves in place) and there is no phase clock.
+template <bool PLAIN = false>
 LIO_DEV void lio_arrive_and_finish(const LioIterParams& P, const LioBlockDesc& bd, LioScanState* st, int lane,
                                    double* s_sum, LioSolveWs* s_ws, long long* stamp)
 {
@@ -437,7 +439,7 @@ LIO_DEV void lio_arrive_and_finish(const LioIterParams& P, const LioBlockDesc& b
         last = (old == (unsigned)bd.n_blk - 1u);
     }
     last = __shfl(last, 0);
-    if (stamp && lane == 0) stamp[6] = (long long)__builtin_readcyclecounter();
+    if (!PLAIN && stamp && lane == 0) stamp[6] = (long long)__builtin_readcyclecounter();
     if (!last) return;
 
     // last workgroup of this scan: fixed-order sum over the scan's chunks
@@ -454,13 +456,13 @@ LIO_DEV void lio_arrive_and_finish(const LioIterParams& P, const LioBlockDesc& b
             for (int u = 0; u < 8; ++u) v += (b + u < bd.n_blk) ? t[u] : 0.0;
         }
         s_sum[lane] = v;
-        if (P.sums_out) P.sums_out[(size_t)bd.scan * LIO_SUMS + lane] = v;
+        if (!PLAIN && P.sums_out) P.sums_out[(size_t)bd.scan * LIO_SUMS + lane] = v;
     }
     // ORDERING: the LDS writes of s_sum by lanes 0..27 are complete before lane 0 of the SAME wave reads them in lio_gn_step
     // (acquire half: the partials themselves were read with sc1 loads issued AFTER the atomic returned -- `last` depends on
     // its result --, so they cannot be older than the last arrival)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if (lane == 0) P.arrive[bd.scan] = 0;                  // re-arm for the next launch
-    if (!P.sums_out) lio_gn_step(st, s_sum, P.c, s_ws, P.n_active, lane);
+    if (PLAIN || !P.sums_out) lio_gn_step(st, s_sum, P.c, s_ws, P.n_active, lane);
 }
 

@@ -149,6 +149,9 @@ try {
     h->cfg = *cfg;
     lio_fill_consts(h.get());
     h->shard.axis = -1;
+    // the plain instantiation of k_s2m_iterate (lio_launch_iterate) unless LIO_PLAIN_KERNEL=0 in the environment: kept per
+    // handle, so one process can hold both kinds for A/B runs
+    { const char* e = getenv("LIO_PLAIN_KERNEL"); h->plain_kernel = !(e && *e && atoi(e) == 0); }
     const int rc = lio_s2m_init_resources(h.get());
     if (rc != LIO_OK) return rc;
     *out = h.release();
@@ -1069,7 +1072,8 @@ static void lio_fill_params_corner(lio_s2m_handle* h, LioIterParams& Pc, double*
 static void lio_launch_gn(lio_s2m_handle* h, const LioIterParams& P, const LioIterParams* Pc)
 {
     if (Pc) lio_launch_iterate(*Pc, h->corner->n_blocks, 1, false, h->stream, true);
-    lio_launch_iterate(P, h->n_blocks, h->ppt, h->cfg.use_lds != 0, h->stream);
+    // (a run with a corner batch keeps the general surface kernel: that path is as it was)
+    h->iterate_variant = lio_launch_iterate(P, h->n_blocks, h->ppt, h->cfg.use_lds != 0, h->stream, false, h->plain_kernel && !Pc);
 }
 
 extern "C" int lio_s2m_batch_begin(lio_s2m_handle* h)
@@ -1097,6 +1101,7 @@ try {
     h->launches_this_run = 0;
     h->units_this_run = 0;
     h->unit_iters = 1;
+    h->iterate_variant = 0;             // (set by the first k_s2m_iterate launch of the run; a one-launch loop leaves 0)
     h->ran = true;
     return LIO_OK;
 } LIO_CATCH
@@ -1109,7 +1114,7 @@ static int lio_graph_prepare(lio_s2m_handle* h, const LioIterParams& P, const Li
     // the cached graph stays valid as long as the kernel arguments and the launch geometry are the same
     const int nbc = Pc ? h->corner->n_blocks : -1;
     if (h->graph_exec && h->graph_chunk == chunk && h->graph_blocks == h->n_blocks && h->graph_ppt == h->ppt &&
-        memcmp(&h->graph_params, &P, sizeof(P)) == 0 && h->graph_blocks_c == nbc &&
+        h->graph_plain == h->plain_kernel && memcmp(&h->graph_params, &P, sizeof(P)) == 0 && h->graph_blocks_c == nbc &&
         (!Pc || memcmp(&h->graph_params_c, Pc, sizeof(P)) == 0))
         return LIO_OK;
     if (h->graph_exec) { HIPCHK(hipGraphExecDestroy(h->graph_exec)); h->graph_exec = nullptr; }
@@ -1118,7 +1123,7 @@ static int lio_graph_prepare(lio_s2m_handle* h, const LioIterParams& P, const Li
     for (int i = 0; i < chunk; ++i) lio_launch_gn(h, P, Pc);
     HIPCHK(hipStreamEndCapture(h->stream, &h->graph));
     HIPCHK(hipGraphInstantiate(&h->graph_exec, h->graph, nullptr, nullptr, 0));
-    h->graph_chunk = chunk; h->graph_blocks = h->n_blocks; h->graph_ppt = h->ppt;
+    h->graph_chunk = chunk; h->graph_blocks = h->n_blocks; h->graph_ppt = h->ppt; h->graph_plain = h->plain_kernel;
     memcpy(&h->graph_params, &P, sizeof(P));
     h->graph_blocks_c = nbc;
     if (Pc) memcpy(&h->graph_params_c, Pc, sizeof(P));
@@ -1204,6 +1209,9 @@ try {
         h->gen_epoch += 128;
         chunk = h->cfg.max_iters;                        // one unit = the whole loop
     }
+    // (a replayed graph launches nothing through lio_launch_gn: the same pure function of P and the switch says what it holds)
+    if (!h->run_persist)
+        h->iterate_variant = lio_iterate_variant(P, h->ppt, h->cfg.use_lds != 0, false, h->plain_kernel && !h->run_has_c);
     h->run_graph = graph;
     h->run_look = look;
     h->run_units = (h->cfg.max_iters + chunk - 1) / chunk;
@@ -1214,6 +1222,13 @@ try {
     h->run_pending = true;
     // a lone registration (lio_s2m_register) has nothing to overlap with: drive the loop to the end right away
     return lio_run_continue(h, h->defer_sync);
+} LIO_CATCH
+
+extern "C" int lio_s2m_kernel_variant(const lio_s2m_handle* h)
+try {
+    if (!h) return lio_fail(LIO_ERR_ARG, "null handle");
+    if (h->multi) return 0;            // (the devices' handles publish their sums: always the general instantiation)
+    return h->iterate_variant;
 } LIO_CATCH
 
 extern "C" int lio_s2m_batch_iter_partial(lio_s2m_handle* h, double* d_sums)
