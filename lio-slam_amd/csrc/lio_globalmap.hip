@@ -21,9 +21,6 @@
 #include "lio_kfstore.h"
 #include "lio_ogm.h"
 
-int lio_s2m_staged_scan(lio_s2m_handle* h, int scan, const unsigned char** d_rec, size_t* n, size_t* stride, size_t* xyz_off, int* int_off,
-                        int* device_id, hipStream_t* stream);   // liogpu_api.hip
-
 #define LIO_EXPORT_DEFAULT_CHUNK (1 << 22)
 #define LIO_EXPORT_LDS_DWORDS 16          // records of up to 64 bytes are assembled in LDS and leave as 16-byte stores
 
@@ -139,11 +136,9 @@ int export_tables(lio_kf_store* st, LioGlobalWs* g, int id0, int n, const float*
     size_t sum = 0;
     for (int k = 0; k < n; ++k) {
         const size_t id = (size_t)id0 + (size_t)k;
-        LioKfDesc& d = kf[(size_t)k];
-        d.src = (int)st->off[id]; d.first = (int)sum; d.n = (int)st->cnt[id]; d.pad = 0;
-        for (int j = 0; j < 12; ++j) d.T[j] = 0.0f;
-        const float own[6] = { st->proll[id], st->ppitch[id], st->pyaw[id], st->px[id], st->py[id], st->pz[id] };
-        for (int j = 0; j < 6; ++j) poses[(size_t)k * 6 + j] = pose ? pose[j] : own[j];
+        kf[(size_t)k] = lio_kf_desc(st, id, sum);
+        if (pose) memcpy(poses + (size_t)k * 6, pose, 6 * sizeof(float));
+        else lio_kf_stored_pose(st, id, poses + (size_t)k * 6);
         first[(size_t)k] = (int)sum;
         sum += st->cnt[id];
     }
@@ -155,7 +150,7 @@ int export_tables(lio_kf_store* st, LioGlobalWs* g, int id0, int n, const float*
     HIPCHK(hipMemcpyAsync(g->x_kf.p, kf, b_kf, hipMemcpyHostToDevice, g->s));
     HIPCHK(hipMemcpyAsync(g->x_poses.p, poses, b_poses, hipMemcpyHostToDevice, g->s));
     HIPCHK(hipMemcpyAsync(g->x_first.p, first, b_first, hipMemcpyHostToDevice, g->s));
-    lio_mb_launch_kf_transforms(g->x_kf.as<LioKfDesc>(), g->x_poses.as<float>(), n, g->s);
+    lio_kf_transforms(g->x_kf.as<LioKfDesc>(), g->x_poses.as<float>(), n, g->s);
     HIPCHK(hipStreamSynchronize(g->s));
     HIPCHK(hipGetLastError());
     return LIO_OK;
@@ -198,7 +193,7 @@ try {
     if (n_ids) *n_ids = 0;
     if (n_out) *n_out = 0;
     if (info) memset(info, 0, sizeof(*info));
-    int rc = lio_mb_check_device(st->device_id);
+    int rc = lio_check_device(st->device_id);
     if (rc != LIO_OK) return rc;
     const int N = (int)st->off.size();
     if (N == 0) return LIO_OK;                       // MO:997
@@ -206,11 +201,11 @@ try {
     LioGlobalWs* g = nullptr;
     if ((rc = global_ws(st, &g)) != LIO_OK) return rc;
     hipStream_t s = g->s;
-    if ((rc = lio_mb_upload_pose_tab(st, s)) != LIO_OK) return rc;
+    if ((rc = lio_kf_upload_pose_tab(st, s)) != LIO_OK) return rc;
     HIPCHK(g->h_meta.grow(sizeof(LioNbMeta) + sizeof(int) * (size_t)N, sizeof(LioNbMeta) + sizeof(int) * 2 * (size_t)N + 4096));
     LioNbMeta* hm = (LioNbMeta*)g->h_meta.p;
     LioNbBufs nb = { g->nws, g->nb_pts, g->nb_cent, g->nb_cid, g->nb_ids, g->nb_meta, g->d_kf, g->d_poses };
-    if ((rc = lio_mb_select(st, nb, R, cfg->pose_density, false, 0.0, 0.0, hm, s)) != LIO_OK) return rc;
+    if ((rc = lio_nb_select(st, nb, R, cfg->pose_density, false, 0.0, 0.0, hm, s)) != LIO_OK) return rc;
     const int n_sel = hm->n_ids, n_chunks = hm->n_chunks;
     const unsigned long long total = hm->total;
     if (n_ids) *n_ids = n_sel;
@@ -223,11 +218,10 @@ try {
     // K6 over the kept list, duplicates included, then K7 at the leaf (both wait: the ids are complete behind them)
     HIPCHK(g->d_chunks.alloc(sizeof(int2) * (size_t)(n_chunks ? n_chunks : 1)));
     HIPCHK(g->world.alloc(sizeof(float4) * (size_t)total));
-    lio_mb_launch_nb_chunks(g->d_kf.as<LioKfDesc>(), n_sel, g->d_chunks.as<int2>(), s);
-    lio_mb_launch_kf_transforms(g->d_kf.as<LioKfDesc>(), g->d_poses.as<float>(), n_sel, s);
-    lio_mb_launch_transform_clouds(st->d_pts, g->d_kf.as<LioKfDesc>(), g->d_chunks.as<int2>(), n_chunks, g->world.as<float4>(), s);
+    lio_nb_chunks(g->d_kf.as<LioKfDesc>(), n_sel, g->d_chunks.as<int2>(), s);
+    lio_kf_sum_launch(st, g->d_kf.as<LioKfDesc>(), g->d_poses.as<float>(), g->d_chunks.as<int2>(), n_sel, n_chunks, g->world.as<float4>(), s);
     int no = 0;
-    rc = lio_mb_voxel_grid(g->world.as<float4>(), (int)total, cfg->leaf, g->ds, &no, s, g->vws);
+    rc = lio_voxel_grid_device(g->world.as<float4>(), (int)total, cfg->leaf, g->ds, &no, s, g->vws, nullptr);
     if (rc < 0) { (void)hipStreamSynchronize(s); return rc; }
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
@@ -235,7 +229,7 @@ try {
     if (info) { info->n_out = no; info->voxel_passthrough = rc == 1 ? 1 : 0; }
     if (n_out) *n_out = (size_t)no;
     if (out && (size_t)no > out_cap) return lio_fail(LIO_ERR_ARG, "out holds fewer records than the global map (*n_out)");
-    const int rc2 = lio_mb_copy_out(g->ds.as<float4>(), no, out, out_stride, s);
+    const int rc2 = lio_copy_out(g->ds.as<float4>(), no, out, out_stride, s);
     if (rc2 < 0) return rc2;
     return LIO_OK;
 } LIO_CATCH
@@ -258,7 +252,7 @@ try {
     if (n_full) *n_full = 0;
     if (n_ds) *n_ds = 0;
     if (voxel_passthrough) *voxel_passthrough = 0;
-    int rc = lio_mb_check_device(st->device_id);
+    int rc = lio_check_device(st->device_id);
     if (rc != LIO_OK) return rc;
     const int N = (int)st->off.size();
     if (N == 0) return LIO_OK;
@@ -274,7 +268,7 @@ try {
         // PCL's filter is a global sort: the filtered copy needs the whole world-frame cloud on the device
         HIPCHK(g->world.alloc(sizeof(float4) * total));
         export_world(st, g, N, total, g->world.as<float4>());
-        rc = lio_mb_voxel_grid(g->world.as<float4>(), (int)total, cfg->resolution, g->ds, &no, g->s, g->vws);
+        rc = lio_voxel_grid_device(g->world.as<float4>(), (int)total, cfg->resolution, g->ds, &no, g->s, g->vws, nullptr);
         if (rc < 0) { (void)hipStreamSynchronize(g->s); return rc; }
         HIPCHK(hipStreamSynchronize(g->s));
         HIPCHK(hipGetLastError());
@@ -283,7 +277,7 @@ try {
     if (n_ds) *n_ds = (size_t)no;
     if ((out_full && total > full_cap) || (filtered && out_ds && (size_t)no > ds_cap))
         return lio_fail(LIO_ERR_ARG, "an output holds fewer records than its cloud (*n_full, *n_ds)");
-    if (filtered && out_ds && (rc = lio_mb_copy_out(g->ds.as<float4>(), no, out_ds, ds_stride, g->s)) < 0) return rc;
+    if (filtered && out_ds && (rc = lio_copy_out(g->ds.as<float4>(), no, out_ds, ds_stride, g->s)) < 0) return rc;
     if (!out_full || !total) return LIO_OK;
     // ---- the unfiltered cloud, chunk by chunk
     const size_t cp = std::min<size_t>(cfg->chunk_points ? (size_t)cfg->chunk_points : (size_t)LIO_EXPORT_DEFAULT_CHUNK, total);
@@ -336,7 +330,7 @@ try {
     if (!(map_resolution >= 0.0f) || !std::isfinite(map_resolution)) return lio_fail(LIO_ERR_ARG, "map_resolution must be finite and not negative");
     int rc = lio_ogm_check(cfg);
     if (rc != LIO_OK) return rc;
-    if ((rc = lio_mb_check_device(st->device_id)) != LIO_OK) return rc;
+    if ((rc = lio_check_device(st->device_id)) != LIO_OK) return rc;
     const int N = (int)st->off.size();
     if (N == 0) return LIO_OK;
     if (st->n_posed != (size_t)N) return lio_fail(LIO_ERR_ARG, "a keyframe has no pose (lio_kf_store_set_poses)");
@@ -353,7 +347,7 @@ try {
         cloud = g->world.as<float4>();
         if (map_resolution != 0.0f) {                 // MO:943
             int no = 0;
-            rc = lio_mb_voxel_grid(g->world.as<float4>(), (int)total, map_resolution, g->ds, &no, g->s, g->vws);
+            rc = lio_voxel_grid_device(g->world.as<float4>(), (int)total, map_resolution, g->ds, &no, g->s, g->vws, nullptr);
             if (rc < 0) { (void)hipStreamSynchronize(g->s); return rc; }
             cloud = g->ds.as<float4>(); n_cloud = no;
         }
@@ -377,20 +371,20 @@ try {
     if (n_out) *n_out = n;
     if (out && n > out_cap) return lio_fail(LIO_ERR_ARG, "out holds fewer records than the keyframe (*n_out)");
     if (!out || !n) return LIO_OK;
-    int rc = lio_mb_check_device(st->device_id);
+    int rc = lio_check_device(st->device_id);
     if (rc != LIO_OK) return rc;
     LioGlobalWs* g = nullptr;
     if ((rc = global_ws(st, &g)) != LIO_OK) return rc;
     // (every lio_kf_store_add* has waited for its write of d_pts before it returned)
     if (!pose) {
-        rc = lio_mb_copy_out(st->d_pts + st->off[(size_t)id], (int)n, out, out_stride, g->s);
+        rc = lio_copy_out(st->d_pts + st->off[(size_t)id], (int)n, out, out_stride, g->s);
         return rc < 0 ? rc : LIO_OK;
     }
     size_t total = 0;
     if ((rc = export_tables(st, g, id, 1, pose, &total)) != LIO_OK) return rc;
     HIPCHK(g->world.alloc(sizeof(float4) * total));
     export_world(st, g, 1, total, g->world.as<float4>());
-    if ((rc = lio_mb_copy_out(g->world.as<float4>(), (int)total, out, out_stride, g->s)) < 0) return rc;
+    if ((rc = lio_copy_out(g->world.as<float4>(), (int)total, out, out_stride, g->s)) < 0) return rc;
     HIPCHK(hipGetLastError());
     return LIO_OK;
 } LIO_CATCH
@@ -422,7 +416,7 @@ try {
     if (n_out) *n_out = n;
     if (out && n > out_cap) return lio_fail(LIO_ERR_ARG, "out holds fewer records than the staged cloud (*n_out)");
     if (!out || !n) return LIO_OK;
-    int rc = lio_mb_check_device(dev);
+    int rc = lio_check_device(dev);
     if (rc != LIO_OK) return rc;
     if (!h->raw_ws) h->raw_ws = new LioRawWs();
     LioRawWs* w = h->raw_ws;
@@ -446,16 +440,16 @@ try {
     LioKfDesc* d_kf = w->pub_kf.as<LioKfDesc>();
     const float* d_pose = reinterpret_cast<const float*>(w->pub_kf.as<unsigned char>() + offsetof(PubTab, pose));
     const int* d_first = reinterpret_cast<const int*>(w->pub_kf.as<unsigned char>() + offsetof(PubTab, first));
-    lio_mb_launch_kf_transforms(d_kf, d_pose, 1, s);
+    lio_kf_transforms(d_kf, d_pose, 1, s);
     const float4* src = reinterpret_cast<const float4*>(rec);       // the whole staged cloud is float4 (x, y, z, intensity) already
     if (which == LIO_STAGED_DS) {                                   // the staged scan: records as uploaded
         HIPCHK(w->pub_xyzi.alloc(sizeof(float4) * n));
-        lio_mb_launch_rec_to_xyzi4(rec, stride, xyz_off, int_off, (int)n, w->pub_xyzi.as<float4>(), s);
+        lio_rec_to_xyzi4(rec, stride, xyz_off, int_off, (int)n, w->pub_xyzi.as<float4>(), s);
         src = w->pub_xyzi.as<float4>();
     }
     hipLaunchKernelGGL((k_export_chunk<false, true>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, d_kf, d_first, 1, 0,
                        (int)n, w->pub_world.as<unsigned char>(), 16);
-    if ((rc = lio_mb_copy_out(w->pub_world.as<float4>(), (int)n, out, out_stride, s)) < 0) return rc;   // (waits for `s`)
+    if ((rc = lio_copy_out(w->pub_world.as<float4>(), (int)n, out, out_stride, s)) < 0) return rc;   // (waits for `s`)
     HIPCHK(hipGetLastError());
     return LIO_OK;
 } LIO_CATCH

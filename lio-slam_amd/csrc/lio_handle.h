@@ -1,5 +1,6 @@
-// lio_handle.h -- the opaque handle behind include/liogpu.h (liogpu_api.hip, lio_multi.hip, lio_mapbuild.hip).  Host-side
-// only; the error plumbing and the buffer types it is built from are in lio_pool.h.
+// lio_handle.h -- the opaque handle behind include/liogpu.h and what liogpu_api.hip offers the files that work on one
+// (lio_multi.hip, lio_mapbuild.hip, lio_kfstore.hip, lio_globalmap.hip).  Host-side only; the error plumbing and the buffer
+// types it is built from are in lio_pool.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -14,6 +15,15 @@
 
 int lio_pc2_check_xyz(const lio_pc2_layout* L);            // liogpu_api.hip
 void lio_raw_ws_free(struct LioRawWs* ws);                 // lio_mapbuild.hip
+
+// ---- liogpu_api.hip, for the map builders and the keyframe store
+int lio_s2m_set_map_device_xyzi(lio_s2m_handle* h, const float4* d_xyzi, size_t n);
+int lio_s2m_set_map_device_bbox(lio_s2m_handle* h, const float4* d_xyzi, size_t n, const float box[6]);
+hipStream_t lio_s2m_stream_of(lio_s2m_handle* h);
+bool lio_s2m_takes_device_map(const lio_s2m_handle* h);
+// the staged records of batch slot `scan` as they were uploaded
+int lio_s2m_staged_scan(lio_s2m_handle* h, int scan, const unsigned char** d_rec, size_t* n, size_t* stride, size_t* xyz_off, int* int_off,
+                        int* device_id, hipStream_t* stream);
 
 // Owns everything it points to except `map_src` and a stream installed by lio_s2m_set_stream (own_stream == false); the
 // destructor releases it on the current device, which lio_s2m_destroy sets.

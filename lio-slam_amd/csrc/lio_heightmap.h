@@ -1,4 +1,4 @@
-// lio_heightmap.h -- what the entry points of the planning height map (lio_mapbuild.hip) need from lio_heightmap.hip.
+// lio_heightmap.h -- what the planning height map (lio_heightmap.hip) offers the chain that goes on from it (lio_terrain.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/liogpu.h"
@@ -32,3 +32,12 @@ void lio_hm_launch_keys(const float4* d_pts, int n, const LioHmGeom& g, uint2* p
 // that goes on from it (the terrain layers); `grid` may then be NULL, and nothing but the counters crosses.
 int lio_hm_grid(const float4* d_pts, const uint2* d_sorted, int n, const LioHmGeom& g, const lio_height_map_config* cfg, float* grid,
                 int* counters, int h_counters[3], hipStream_t s, LioTemp* keep = nullptr);
+
+int lio_height_map_check(const lio_height_map_config* c);     // LIO_OK or LIO_ERR_ARG
+
+// helpers.cpp:97-105 on a device-resident float4 cloud (w is not read): the reference's order, everything on the device, the
+// grid copy last.  Host waits, each for a number that sizes the next launch: outlier filter 3 (box, grid choice, compaction
+// count), voxel filter 2, ego filter 1, the box, and the grid copy with the counters.  `keep` (optional) receives the device
+// grid, which is then built whether or not `grid` is given.
+int lio_height_map_device(const float4* d_in, int n, const lio_height_map_config* cfg, float* grid, size_t grid_cap, lio_height_map_info* info,
+                          hipStream_t s, LioTemp* keep = nullptr);

@@ -18,7 +18,9 @@
 #include <utility>
 
 #include "lio_heightmap.h"
+#include "lio_cloud.h"
 #include "lio_compact.h"
+#include "lio_localmap.h"
 #include "lio_pool.h"
 #include "lio_s2m_device.h"
 #include "lio_wg.h"
@@ -101,7 +103,7 @@ int lio_hm_level_ego(const float4* d_in, int n, const float R1[9], const float R
     return compact_device(pred, n, out, n_out, s);
 }
 
-// ---- geometry (the box comes from K7's k_vox_bbox, launched from lio_mapbuild.hip) -------------------------------------
+// ---- geometry (the box comes from K7's box pass, lio_cloud_box_launch) -----------------------------------------------
 void lio_hm_geometry(const float mn[3], const float mx[3], double resolution, LioHmGeom* g)
 {
     g->resolution = resolution;
@@ -381,3 +383,138 @@ int lio_hm_grid(const float4* d_pts, const uint2* d_sorted, int n, const LioHmGe
     if (keep) std::swap(keep->p, post.p);                  // the caller goes on from the device grid (and owns it)
     return LIO_OK;
 }
+
+// ------------------------------------------------ planning height map (grid_map_pcl's loader, helpers.cpp:97-105)
+// The chain (it needs the outlier filter, K7 and K7's sort) and the entry points.
+extern "C" void lio_height_map_default_config(lio_height_map_config* cfg)
+{
+    if (!cfg) return;
+    memset(cfg, 0, sizeof(*cfg));
+    cfg->roll = 0.0f; cfg->pitch = 0.0f;
+    cfg->level_and_ego_filter = 1;                         // GridMapPclLoader.cpp:80-85
+    cfg->remove_outliers = 1; cfg->mean_k = 10; cfg->stddev_mul = 1.0f;                  // parameters.yaml outlier_removal
+    cfg->downsample = 0; cfg->voxel[0] = cfg->voxel[1] = cfg->voxel[2] = 0.1f;           // downsampling
+    cfg->resolution = 0.2;                                 // grid_map
+    cfg->min_points_per_cell = 1; cfg->max_points_per_cell = 1000000000;
+    cfg->use_cluster = 0; cfg->cluster_tolerance = 1.0f;   // cluster_extraction
+    cfg->cluster_min_points = 1; cfg->cluster_max_points = 1000000000; cfg->use_max_height = 0;
+    cfg->fill_holes = 0;                                   // the reference as written
+}
+
+int lio_height_map_check(const lio_height_map_config* c)
+{
+    const int32_t flags[] = { c->level_and_ego_filter, c->remove_outliers, c->downsample, c->use_cluster, c->use_max_height, c->fill_holes };
+    for (int32_t f : flags)
+        if (f != 0 && f != 1) return lio_fail(LIO_ERR_ARG, "the flags of lio_height_map_config are 0 or 1");
+    if (!std::isfinite(c->roll) || !std::isfinite(c->pitch)) return lio_fail(LIO_ERR_ARG, "roll and pitch must be finite");
+    if (!(c->resolution >= 1e-4) || !std::isfinite(c->resolution)) return lio_fail(LIO_ERR_ARG, "resolution must be at least 1e-4");
+    int rc = lio_sor_check(c->mean_k, c->stddev_mul);
+    if (rc != LIO_OK) return rc;
+    if (c->downsample) {                                   // K7 takes one leaf
+        if (!(c->voxel[0] > 0.0f) || !std::isfinite(c->voxel[0]) || c->voxel[1] != c->voxel[0] || c->voxel[2] != c->voxel[0])
+            return lio_fail(LIO_ERR_ARG, "downsample needs one positive, finite voxel size on all three axes");
+    }
+    if (c->min_points_per_cell < 0 || c->max_points_per_cell < 0 || c->cluster_min_points < 0 || c->cluster_max_points < 0)
+        return lio_fail(LIO_ERR_ARG, "point counts must not be negative");
+    if (c->use_cluster && (!(c->cluster_tolerance >= 0.0f) || !std::isfinite(c->cluster_tolerance)))
+        return lio_fail(LIO_ERR_ARG, "cluster_tolerance must be finite and not negative");
+    return LIO_OK;
+}
+
+int lio_height_map_device(const float4* d_in, int n, const lio_height_map_config* cfg, float* grid, size_t grid_cap, lio_height_map_info* info,
+                          hipStream_t s, LioTemp* keep)
+{
+    int rc;
+    const float4* cur = d_in;
+    int n_cur = n;
+    LioTemp inl, ds, lev;
+    info->n_in = n;
+    if (cfg->remove_outliers) {                            // PointcloudProcessor.cpp:62-70
+        LioSorReport rep;
+        int n_inl = 0;
+        if ((rc = lio_sor_device(cur, n_cur, cfg->mean_k, cfg->stddev_mul, inl, &n_inl, nullptr, &rep, s)) < 0) return rc;
+        cur = inl.as<float4>(); n_cur = n_inl;
+    }
+    info->n_inliers = n_cur;
+    if (cfg->downsample && n_cur > 0) {                    // PointcloudProcessor.cpp:114-122
+        int n_ds = 0;
+        if ((rc = lio_voxel_grid_device(cur, n_cur, cfg->voxel[0], ds, &n_ds, s)) < 0) return rc;
+        info->voxel_passthrough = rc == 1 ? 1 : 0;
+        cur = ds.as<float4>(); n_cur = n_ds;
+    }
+    float R1[9], R2[9];
+    lio_hm_rotations(cfg->roll, cfg->pitch, R1, R2);
+    int n_lev = 0;
+    if ((rc = lio_hm_level_ego(cur, n_cur, R1, R2, cfg->level_and_ego_filter, lev, &n_lev, s)) != LIO_OK) return rc;
+    cur = lev.as<float4>(); n_cur = n_lev;
+    info->n_filtered = n_cur;
+    if (n_cur == 0) return LIO_OK;                         // no point: no grid
+    float mn[3], mx[3];
+    LioTemp bbox;                                          // K7's box pass (k_vox_bbox)
+    if ((rc = lio_cloud_box_launch(cur, n_cur, bbox, s)) != LIO_OK) return rc;
+    if ((rc = lio_cloud_box_wait(bbox, mn, mx, s)) != LIO_OK) return rc;
+    HIPCHK(hipGetLastError());
+    LioHmGeom g;
+    lio_hm_geometry(mn, mx, cfg->resolution, &g);
+    info->rows = g.rows; info->cols = g.cols;
+    for (int a = 0; a < 2; ++a) { info->length[a] = g.length[a]; info->position[a] = g.position[a]; }
+    if (g.rows == 0 || g.cols == 0) return LIO_OK;         // (the reference asserts in GridMap::setGeometry)
+    if ((long long)g.rows * g.cols > 0x7fffffffLL - 1024) return lio_fail(LIO_ERR_CAPACITY, "the grid has more than 2^31 cells");
+    const size_t n_cells = (size_t)g.rows * (size_t)g.cols;
+    if (!grid && !keep) return LIO_OK;                     // the geometry only
+    if (grid && n_cells > grid_cap) return lio_fail(LIO_ERR_ARG, "grid holds fewer cells than rows x cols (info)");
+    // ---- cells: keys, K7's stable sort (the key space: the cells and one key behind them), then lio_hm_grid
+    LioVoxWs<LioTemp> ws;
+    LioTemp counters;
+    const int n_blocks = (n_cur + LIO_VS_THREADS * 4 - 1) / (LIO_VS_THREADS * 4);
+    HIPCHK(ws.pairs_a.alloc(sizeof(uint2) * (size_t)n_cur));
+    HIPCHK(ws.pairs_b.alloc(sizeof(uint2) * (size_t)n_cur));
+    HIPCHK(ws.hist.alloc(sizeof(int) * (size_t)LIO_VS_BINS * n_blocks));
+    HIPCHK(ws.row_total.alloc(sizeof(int) * LIO_VS_BINS));
+    HIPCHK(counters.alloc(4 * sizeof(int)));
+    HIPCHK(hipMemsetAsync(counters.p, 0, 4 * sizeof(int), s));
+    lio_hm_launch_keys(cur, n_cur, g, ws.pairs_a.as<uint2>(), counters.as<int>(), s);
+    int bits = 1;
+    while (bits < 31 && (1LL << bits) < (long long)n_cells + 1) ++bits;
+    const uint2* sorted = lio_vsort_pairs<LioTemp>(n_cur, bits, s, ws);
+    int hc[3] = { 0, 0, 0 };
+    if ((rc = lio_hm_grid(cur, sorted, n_cur, g, cfg, grid, counters.as<int>(), hc, s, keep)) != LIO_OK) return rc;
+    info->n_binned = hc[0]; info->n_valid_cells = hc[1]; info->n_filled_cells = hc[2];
+    return LIO_OK;
+}
+
+extern "C" int lio_height_map(int32_t device_id, const void* pts, size_t n, size_t stride, const lio_height_map_config* cfg, float* grid,
+                              size_t grid_cap, lio_height_map_info* info)
+try {
+    if (!cfg || !info || (n && !pts)) return lio_fail(LIO_ERR_ARG, "null argument");
+    if (stride < 12 || (stride & 3)) return lio_fail(LIO_ERR_ARG, "stride must be >= 12 and a multiple of 4");
+    if (n > 0x7fffffffull - 1024) return lio_fail(LIO_ERR_CAPACITY, "cloud too large");
+    int rc = lio_height_map_check(cfg);
+    if (rc != LIO_OK) return rc;
+    memset(info, 0, sizeof(*info));
+    if (n == 0) return LIO_OK;                             // an empty cloud: rows = cols = 0
+    if ((rc = lio_check_device(device_id)) != LIO_OK) return rc;
+    hipStream_t s = nullptr;
+    LioTemp raw, xyzi;
+    HIPCHK(xyzi.alloc(n * sizeof(float4)));
+    if ((rc = lio_upload_xyzi(pts, n, stride, -1, raw, xyzi.as<float4>(), s)) != LIO_OK) return rc;
+    rc = lio_height_map_device(xyzi.as<float4>(), (int)n, cfg, grid, grid_cap, info, s);
+    const hipError_t e = hipStreamSynchronize(s);          // (an early return: `raw` goes back to the pool when this returns)
+    if (rc < 0) return rc;                                 // the chain's own error comes first
+    HIPCHK(e);
+    return rc;
+} LIO_CATCH
+
+extern "C" int lio_kf_store_height_map(lio_kf_store* st, const lio_local_map_config* lm, const float* pose, const lio_height_map_config* cfg,
+                                       float* grid, size_t grid_cap, lio_local_map_info* lm_info, lio_height_map_info* info)
+try {
+    if (!st || !lm || !pose || !cfg || !info) return lio_fail(LIO_ERR_ARG, "null argument");
+    int rc = lio_height_map_check(cfg);
+    if (rc != LIO_OK) return rc;
+    memset(info, 0, sizeof(*info));
+    hipStream_t s = nullptr;
+    LocalMapBufs B;
+    if ((rc = lio_local_map_device(st, lm, pose, B, nullptr, lm_info, s)) != LIO_OK) return rc;
+    if (B.n_cur == 0) return LIO_OK;                       // an empty store or an empty crop: rows = cols = 0
+    return lio_height_map_device(B.cur, B.n_cur, cfg, grid, grid_cap, info, s);
+} LIO_CATCH

@@ -1,4 +1,4 @@
-// lio_icp.h -- what the entry points of the loop-closure registration (lio_mapbuild.hip) need from lio_icp.hip.
+// lio_icp.h -- what lio_icp.hip, the loop-closure registration, offers the other chains (the local map's grid choice).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/liogpu.h"

@@ -17,6 +17,7 @@
 
 #include "lio_icp.h"
 #include "lio_kernels.h"
+#include "lio_kfstore.h"
 #include "lio_pool.h"
 #include "lio_wg.h"
 
@@ -570,3 +571,174 @@ int lio_icp_device(const float4* d_src, int n_src, const float4* d_tgt, int n_tg
     for (int i = 0; i < 16; ++i) res->T[i] = h_st.final_[i];
     return LIO_OK;
 }
+
+// ------------------------------------------------ loop-closure registration (performRSLoopClosure MO:1098-1143)
+// The entry points: host clouds, and submaps summed from the resident keyframe store (lio_kfstore.h).
+
+// host records (x,y,z @0,4,8) -> device float4 (x, y, z, 0)
+static int icp_upload(const void* pts, size_t n, size_t stride, LioTemp& raw, LioTemp& xyz4, hipStream_t s)
+{
+    HIPCHK(xyz4.alloc(sizeof(float4) * (n ? n : 1)));
+    if (!n) return LIO_OK;
+    return lio_upload_xyzi(pts, n, stride, -1, raw, xyz4.as<float4>(), s);
+}
+
+static int icp_align_host(int32_t device_id, const void* src, size_t n_src, size_t src_stride, const void* tgt, size_t n_tgt, size_t tgt_stride,
+                          const lio_icp_config* cfg, const float* guess, lio_icp_result* res, LioIcpTrace* trace)
+{
+    if (!res || (n_src && !src) || (n_tgt && !tgt)) return lio_fail(LIO_ERR_ARG, "null argument");
+    if (src_stride < 12 || (src_stride & 3) || tgt_stride < 12 || (tgt_stride & 3)) return lio_fail(LIO_ERR_ARG, "strides must be >= 12 and multiples of 4");
+    if (n_src > 0x7fffffffull - 1024 || n_tgt > 0x7fffffffull - 1024) return lio_fail(LIO_ERR_CAPACITY, "cloud too large");
+    int rc = lio_icp_check_config(cfg);
+    if (rc != LIO_OK) return rc;
+    if ((rc = lio_check_device(device_id)) != LIO_OK) return rc;
+    hipStream_t s = nullptr;
+    LioTemp raw_s, raw_t, d_src, d_tgt;
+    if ((rc = icp_upload(src, n_src, src_stride, raw_s, d_src, s)) != LIO_OK) return rc;
+    if ((rc = icp_upload(tgt, n_tgt, tgt_stride, raw_t, d_tgt, s)) != LIO_OK) return rc;
+    rc = lio_icp_device(d_src.as<float4>(), (int)n_src, d_tgt.as<float4>(), (int)n_tgt, *cfg, guess, res, s, trace, nullptr);
+    res->status = rc;
+    return rc;
+}
+
+extern "C" int lio_icp_align(int32_t device_id, const void* source, size_t n_source, size_t source_stride, const void* target, size_t n_target,
+                             size_t target_stride, const lio_icp_config* cfg, const float* guess, lio_icp_result* result)
+try {
+    return icp_align_host(device_id, source, n_source, source_stride, target, n_target, target_stride, cfg, guess, result, nullptr);
+} LIO_CATCH
+
+extern "C" int lio_icp_debug_trace(int32_t device_id, const void* source, size_t n_source, size_t source_stride, const void* target,
+                                   size_t n_target, size_t target_stride, const lio_icp_config* cfg, const float* guess, int32_t rec_iter,
+                                   lio_icp_result* result, float* steps, int32_t* n_corr, double* mse, int32_t* corr, int32_t* n_trace)
+try {
+    LioIcpTrace tr;
+    tr.step = steps; tr.n_corr = n_corr; tr.mse = mse; tr.corr = corr; tr.rec_iter = rec_iter;
+    if (n_trace) *n_trace = 0;
+    const int rc = icp_align_host(device_id, source, n_source, source_stride, target, n_target, target_stride, cfg, guess, result, &tr);
+    if (n_trace) *n_trace = tr.n_trace;
+    return rc;
+} LIO_CATCH
+
+// loopFindNearKeyframes MO:1360-1383: the keyframes key - search_num .. key + search_num the store holds, each under its own
+// stored pose or all under pose_index's, summed (the keyframe sum of lio_kfstore.h) and voxel-filtered.  An empty sum stays
+// empty (MO:1375-1376).
+static int loop_submap(lio_kf_store* st, int key, int search_num, int pose_index, float leaf, LioTemp& ds, int* n_out, hipStream_t s)
+{
+    *n_out = 0;
+    const int N = (int)st->off.size();
+    std::vector<int32_t> ids, pose_ids;
+    for (long long i = -(long long)search_num; i <= (long long)search_num; ++i) {
+        const long long near = (long long)key + i;
+        if (near < 0 || near >= N) continue;
+        const int32_t id = (int32_t)near, pid = pose_index >= 0 ? pose_index : id;
+        if (!st->has_pose[(size_t)pid]) return lio_fail(LIO_ERR_ARG, "a keyframe has no pose (lio_kf_store_set_poses)");
+        ids.push_back(id); pose_ids.push_back(pid);
+    }
+    LioKfSum t;
+    lio_kf_sum_tables(st, ids.data(), pose_ids.data(), (int)ids.size(), t);
+    if (t.total > 0x7fffffffull - 1024) return lio_fail(LIO_ERR_CAPACITY, "too many points");
+    if (t.total == 0) return LIO_OK;
+    LioTemp d_kf, d_poses, d_chunks, world;
+    int rc = lio_kf_sum_upload(t, t.poses.data(), d_kf, d_poses, d_chunks, s);
+    if (rc != LIO_OK) return rc;
+    HIPCHK(world.alloc(t.total * sizeof(float4)));
+    lio_kf_sum_launch(st, d_kf.as<LioKfDesc>(), d_poses.as<float>(), d_chunks.as<int2>(), (int)t.kf.size(), (int)t.chunks.size(), world.as<float4>(), s);
+    HIPCHK(hipStreamSynchronize(s));                       // (the descriptors are host arrays of this function)
+    rc = lio_voxel_grid_device(world.as<float4>(), (int)t.total, leaf, ds, n_out, s);
+    return rc < 0 ? rc : LIO_OK;                           // (1 = the leaf overflows PCL's voxel index: the sum passes through, as in PCL)
+}
+
+extern "C" int lio_kf_store_loop_icp(lio_kf_store* st, int32_t key_cur, int32_t key_pre, int32_t search_num, int32_t pose_index, float leaf,
+                                     const lio_icp_config* cfg, lio_icp_result* res, lio_icp_clouds* clouds)
+try {
+    if (!st || !res) return lio_fail(LIO_ERR_ARG, "null argument");
+    int rc = lio_icp_check_config(cfg);
+    if (rc != LIO_OK) return rc;
+    const int N = (int)st->off.size();
+    if (key_cur < 0 || key_cur >= N || key_pre < 0 || key_pre >= N || search_num < 0 || pose_index < -1 || pose_index >= N || !(leaf > 0.0f))
+        return lio_fail(LIO_ERR_ARG, "key_cur, key_pre and pose_index must name keyframes of the store; search_num >= 0; leaf > 0");
+    if (!st->has_pose[(size_t)key_cur]) return lio_fail(LIO_ERR_ARG, "a keyframe has no pose (lio_kf_store_set_poses)");
+    if (clouds && (clouds->stride < 20 || (clouds->stride & 3))) return lio_fail(LIO_ERR_ARG, "output stride must be >= 20 and a multiple of 4");
+    if ((rc = lio_check_device(st->device_id)) != LIO_OK) return rc;
+    memset(res, 0, sizeof(*res));
+    hipStream_t s = nullptr;
+    LioTemp src, tgt, closed;
+    int n_src = 0, n_tgt = 0;
+    if ((rc = loop_submap(st, key_cur, 0, pose_index, leaf, src, &n_src, s)) != LIO_OK) return rc;
+    if ((rc = loop_submap(st, key_pre, search_num, pose_index, leaf, tgt, &n_tgt, s)) != LIO_OK) return rc;
+    res->n_source = n_src; res->n_target = n_tgt;
+    if (clouds) {
+        clouds->n_source = (size_t)n_src; clouds->n_target = (size_t)n_tgt; clouds->n_closed = 0;
+        if ((clouds->source && clouds->cap_source < (size_t)n_src) || (clouds->target && clouds->cap_target < (size_t)n_tgt))
+            return lio_fail(LIO_ERR_ARG, "a submap holds more records than its output (n_source, n_target)");
+        if (clouds->source && (rc = lio_copy_out(src.as<float4>(), n_src, clouds->source, clouds->stride, s)) < 0) return rc;
+        if (clouds->target && (rc = lio_copy_out(tgt.as<float4>(), n_tgt, clouds->target, clouds->stride, s)) < 0) return rc;
+    }
+    if (n_src < cfg->min_source_points || n_tgt < cfg->min_target_points) {                  // MO:1104
+        res->status = LIO_TOO_FEW_POINTS;
+        res->state = LIO_ICP_NOT_CONVERGED;
+        res->fitness = DBL_MAX;
+        for (int i = 0; i < 16; i += 5) res->T[i] = 1.0f;
+        return LIO_TOO_FEW_POINTS;
+    }
+    const bool want_closed = clouds && clouds->closed;
+    if (want_closed) {
+        clouds->n_closed = (size_t)n_src;
+        if (clouds->cap_closed < (size_t)n_src) return lio_fail(LIO_ERR_ARG, "closed holds fewer records than the source submap (n_closed)");
+        HIPCHK(closed.alloc(sizeof(float4) * (size_t)(n_src ? n_src : 1)));
+    }
+    rc = lio_icp_device(src.as<float4>(), n_src, tgt.as<float4>(), n_tgt, *cfg, nullptr, res, s, nullptr, want_closed ? closed.as<float4>() : nullptr);
+    res->status = rc;
+    if (rc != LIO_OK) return rc;
+    if (want_closed && (rc = lio_copy_out(closed.as<float4>(), n_src, clouds->closed, clouds->stride, s)) < 0) return rc;
+    // tCorrect = correctionLidarFrame * tWrong, then pcl::getTranslationAndEulerAngles (MO:1136-1143); host, fp64 from the
+    // fp32 inputs, rounded once
+    {
+        const size_t k = (size_t)key_cur;
+        const double A = cos((double)st->pyaw[k]), B = sin((double)st->pyaw[k]), Cc = cos((double)st->ppitch[k]), D = sin((double)st->ppitch[k]),
+                     E = cos((double)st->proll[k]), F = sin((double)st->proll[k]), DE = D * E, DF = D * F;
+        const double W[16] = { A * Cc, A * DF - B * E, B * F + A * DE, (double)st->px[k],
+                               B * Cc, A * E + B * DF, B * DE - A * F, (double)st->py[k],
+                               -D, Cc * F, Cc * E, (double)st->pz[k], 0.0, 0.0, 0.0, 1.0 };
+        double Tc[16];
+        for (int a = 0; a < 4; ++a)
+            for (int b = 0; b < 4; ++b) {
+                double v = 0.0;
+                for (int j = 0; j < 4; ++j) v += (double)res->T[4 * a + j] * W[4 * j + b];
+                Tc[4 * a + b] = v;
+            }
+        res->pose_corrected[0] = (float)atan2(Tc[9], Tc[10]);
+        res->pose_corrected[1] = (float)asin(-Tc[8]);
+        res->pose_corrected[2] = (float)atan2(Tc[4], Tc[0]);
+        res->pose_corrected[3] = (float)Tc[3]; res->pose_corrected[4] = (float)Tc[7]; res->pose_corrected[5] = (float)Tc[11];
+    }
+    return LIO_OK;
+} LIO_CATCH
+
+extern "C" int lio_kf_store_detect_loop(lio_kf_store* st, float radius, double time_diff, double time_cur, int32_t* key_cur, int32_t* key_pre)
+try {
+    if (!st || !key_cur || !key_pre) return lio_fail(LIO_ERR_ARG, "null argument");
+    if (!(radius > 0.0f) || !std::isfinite(radius) || !std::isfinite(time_diff) || !std::isfinite(time_cur))
+        return lio_fail(LIO_ERR_ARG, "radius > 0 and finite; time_diff, time_cur finite");
+    *key_cur = -1; *key_pre = -1;
+    const int N = (int)st->off.size();
+    if (N == 0) return 0;                                  // MO:1083-1084
+    for (int i = 0; i < N; ++i)
+        if (!st->has_pose[(size_t)i] || !st->has_time[(size_t)i]) return lio_fail(LIO_ERR_ARG, "a keyframe has no pose or no time (lio_kf_store_set_poses)");
+    const int last = N - 1;
+    const float r2 = (float)((double)radius * (double)radius);          // what PCL hands FLANN
+    const float lx = st->px[(size_t)last], ly = st->py[(size_t)last], lz = st->pz[(size_t)last];
+    // the radius set is visited in (d2, index) order; only its first entry that is old enough matters
+    int best = -1;
+    float best_d2 = 0.0f;
+    for (int i = 0; i < N; ++i) {
+        const float dx = st->px[(size_t)i] - lx, dy = st->py[(size_t)i] - ly, dz = st->pz[(size_t)i] - lz;
+        const float d2 = (dx * dx + dy * dy) + dz * dz;
+        if (!(d2 < r2)) continue;
+        if (!(std::fabs(st->ptime[(size_t)i] - time_cur) > time_diff)) continue;            // MO:1290
+        if (best < 0 || d2 < best_d2) { best = i; best_d2 = d2; }
+    }
+    if (best < 0 || best == last) return 0;               // MO:1297-1298
+    *key_cur = last; *key_pre = best;
+    return 1;
+} LIO_CATCH

@@ -1,12 +1,12 @@
-// lio_kfstore.h -- what lio_globalmap.hip shares with lio_mapbuild.hip: the resident keyframe store, the descriptors of K6,
-// the workspace of K7, the staged cloud of lio_s2m_register_raw, and the launches of lio_mapbuild.hip's kernels that the
-// global map and the map export reuse (the selection k_nb_select .. k_nb_compact, K6, K7, the record conversions).
+// lio_kfstore.h -- the resident keyframe store (lio_kfstore.hip) and what its readers share: the descriptors of K6, the
+// key-pose table, the keyframe sum, and the cloud lio_s2m_register_raw keeps staged on the handle.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <vector>
 
 #include "../../include/liogpu.h"
+#include "lio_cloud.h"
 #include "lio_pool.h"
 #include "lio_sc.h"
 
@@ -18,9 +18,10 @@ struct LioKfDesc {       // one selected keyframe
     float T[12];         // pclPointToAffine3f of its pose (MO:856), filled on the device
 };
 
-// B: LioTemp (pool temporaries, recycled when the call returns) or LioDevBytes (a workspace kept from one call to the next,
-// so that nothing has to be waited for before the call returns)
-template <class B> struct LioVoxWs { B bbox, large, pairs_a, pairs_b, hist, blk_heads, seg_start, d_no, row_total; };
+struct LioKfSum {        // the host tables of one keyframe sum (below): descriptors, the 256-point chunks of K6, poses, points
+    std::vector<LioKfDesc> kf; std::vector<int2> chunks; std::vector<float> poses;
+    size_t total = 0;
+};
 
 struct LioPoseTab { const float *x, *y, *z, *roll, *pitch, *yaw; const double* t; const int *off, *cnt; };
 struct LioNbMeta { int n_sel, recent_fail; unsigned box[6]; int n_ids, n_chunks; unsigned long long total; };
@@ -43,8 +44,7 @@ struct lio_kf_store {
     // workspace of lio_assemble_map_resident when the map is installed in a handle (kept between calls)
     LioVoxWs<LioDevBytes> vws;
     LioDevBytes world, ds, d_kf, d_poses, d_chunks, blk_box;
-    std::vector<LioKfDesc> v_kf;
-    std::vector<int2> v_chunks;
+    LioKfSum v_sum;
     // key-pose table = cloudKeyPoses6D (x, y, z, roll, pitch, yaw, time): host copy written by lio_kf_store_set_poses (never
     // blocks), device SoA next to off / cnt uploaded -- the dirty range only -- on the stream of the next selection
     std::vector<float> px, py, pz, proll, ppitch, pyaw;
@@ -88,11 +88,22 @@ struct LioRawWs {
     LioPinned<unsigned char> pub_tab;                // the host image of pub_kf on its way up
 };
 
-// ---- lio_mapbuild.hip, for lio_globalmap.hip
-int lio_mb_check_device(int device_id);
 // the dirty range of the key-pose table (and off / cnt) to the device, on stream `s`, through the store's pinned stage
-int lio_mb_upload_pose_tab(lio_kf_store* st, hipStream_t s);
+int lio_kf_upload_pose_tab(lio_kf_store* st, hipStream_t s);
+LioPoseTab lio_kf_pose_tab(lio_kf_store* st);        // the columns of the uploaded table
 
+// ---- the keyframe sum: keyframes ids[k] under poses p[k], concatenated in the world frame (K6, MO:849-868)
+LioKfDesc lio_kf_desc(const lio_kf_store* st, size_t id, size_t first);     // T zeroed: k_kf_transforms fills it
+void lio_kf_stored_pose(const lio_kf_store* st, size_t id, float pose[6]);  // [roll, pitch, yaw, x, y, z]
+// The tables over ids[0 .. n), all ids of the store; with pose_ids, t.poses = the stored pose of pose_ids[k] for keyframe k.
+void lio_kf_sum_tables(const lio_kf_store* st, const int32_t* ids, const int32_t* pose_ids, int n, LioKfSum& t);
+// t.kf, t.chunks and `poses` to the device on `s`; the host arrays must outlive the copies.  B: LioTemp or LioDevBytes.
+template <class B> int lio_kf_sum_upload(const LioKfSum& t, const float* poses, B& d_kf, B& d_poses, B& d_chunks, hipStream_t s);
+void lio_kf_transforms(LioKfDesc* d_kf, const float* d_poses, int n_kf, hipStream_t s);                // k_kf_transforms
+// k_kf_transforms, then K6 into dst on `s`; nothing waits
+void lio_kf_sum_launch(const lio_kf_store* st, LioKfDesc* d_kf, const float* d_poses, const int2* d_chunks, int n_sel, int n_chunks, float4* dst, hipStream_t s);
+
+// ---- lio_mapbuild.hip: the selection of the surrounding keyframes, which the global map (lio_globalmap.hip) shares
 // The buffers one selection works in: lio_assemble_map_nearby passes the store's, the global map its own.
 struct LioNbBufs {
     LioVoxWs<LioDevBytes>& ws;
@@ -101,14 +112,7 @@ struct LioNbBufs {
 // k_nb_select .. k_nb_compact on stream `s` over the uploaded key-pose table, then ONE wait for *hm (pinned): n_ids, n_chunks
 // and total of the kept list, whose descriptors (T not yet filled), poses and ids lie in b.d_kf, b.d_poses and b.ids.
 // recent = false leaves the suffix of MO:1544-1551 out (publishGlobalMap has none) and reads no key-pose time.
-int lio_mb_select(lio_kf_store* st, LioNbBufs& b, float R, float density, bool recent, double time_cur, double window, LioNbMeta* hm,
+int lio_nb_select(lio_kf_store* st, LioNbBufs& b, float R, float density, bool recent, double time_cur, double window, LioNbMeta* hm,
                   hipStream_t s);
-void lio_mb_launch_nb_chunks(const LioKfDesc* kf, int n_sel, int2* chunks, hipStream_t s);
-void lio_mb_launch_kf_transforms(LioKfDesc* kf, const float* poses, int n_kf, hipStream_t s);          // k_kf_transforms
-void lio_mb_launch_transform_clouds(const float4* store, const LioKfDesc* kf, const int2* chunks, int n_chunks, float4* dst,
-                                    hipStream_t s);                                                    // K6
-void lio_mb_launch_rec_to_xyzi4(const unsigned char* src, size_t stride, size_t xyz_off, int int_off, int n, float4* dst, hipStream_t s);
-// K7 with a workspace kept between calls; LIO_OK, 1 for PCL's pass-through, < 0 on error.  Complete when it returns.
-int lio_mb_voxel_grid(const float4* d_in, int n, float leaf, LioDevBytes& out, int* n_out, hipStream_t s, LioVoxWs<LioDevBytes>& ws);
-// n float4 (x, y, z, intensity) -> PointXYZI-compatible host records; waits for `s`
-int lio_mb_copy_out(const float4* d_pts, int n, void* out, size_t out_stride, hipStream_t s);
+// the 256-point chunks of K6 for the kept list
+void lio_nb_chunks(const LioKfDesc* kf, int n_sel, int2* chunks, hipStream_t s);

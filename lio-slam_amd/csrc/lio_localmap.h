@@ -1,4 +1,4 @@
-// lio_localmap.h -- what the entry points of the planning local map (lio_mapbuild.hip) need from lio_localmap.hip.
+// lio_localmap.h -- what the planning local map (lio_localmap.hip) offers the chains that go on from it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/liogpu.h"
@@ -28,3 +28,14 @@ void lio_local_map_vehicle_frame(const float pose[6], float M[12]);
 // one order-preserving compaction: `out` receives the survivors, transformed.  Synchronous (the count sizes what follows).
 int lio_crop_device(const float4* d_in, int n, const float M[12], float front, float left, float back, float right, LioTemp& out,
                     int* n_out, hipStream_t s);
+
+struct LocalMapBufs {
+    LioTemp d_kf, d_poses, d_chunks, world, cropped, inl, ds;
+    const float4* cur = nullptr;   // the local map, in one of the buffers above
+    int n_cur = 0;
+};
+
+// MO:2447-2540 up to the cloud on the device: B.cur / B.n_cur = the local map (null / 0 for an empty store or an empty sum),
+// complete when this returns.  What lio_kf_store_local_map copies out and lio_kf_store_height_map goes on with.
+int lio_local_map_device(lio_kf_store* st, const lio_local_map_config* cfg, const float* pose, LocalMapBufs& B, size_t* n_out,
+                         lio_local_map_info* info, hipStream_t s);

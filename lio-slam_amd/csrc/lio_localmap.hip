@@ -17,6 +17,7 @@
 #include "lio_compact.h"
 #include "lio_icp.h"
 #include "lio_kernels.h"
+#include "lio_kfstore.h"
 #include "lio_pool.h"
 #include "lio_s2m_device.h"
 #include "lio_wg.h"
@@ -291,3 +292,126 @@ int lio_sor_device(const float4* d_pts, int n, int mean_k, float stddev_mul, Lio
     rep->mean = h_st.mean; rep->stddev = h_st.stddev; rep->threshold = h_st.threshold;
     return h_st.passthrough ? 1 : LIO_OK;
 }
+
+// ------------------------------------------------ planning local map (publishLocalMap MO:2442-2541)
+// The entry points: the outlier filter on a host cloud, and the chain on the resident keyframe store (lio_kfstore.h).
+extern "C" int lio_sor_filter(int32_t device_id, const void* pts, size_t n, size_t stride, int32_t mean_k, float stddev_mul, void* out,
+                              size_t out_stride, size_t* n_out, float* mean_dist, double stats[3])
+try {
+    if (!n_out || (n && !pts)) return lio_fail(LIO_ERR_ARG, "null argument");
+    if (stride < 12 || (stride & 3) || (out && (out_stride < 20 || (out_stride & 3))))
+        return lio_fail(LIO_ERR_ARG, "stride must be >= 12, the output stride >= 20, both multiples of 4");
+    if (n > 0x7fffffffull - 1024) return lio_fail(LIO_ERR_CAPACITY, "cloud too large");
+    int rc = lio_sor_check(mean_k, stddev_mul);
+    if (rc != LIO_OK) return rc;
+    *n_out = 0;
+    if (stats) { stats[0] = 0.0; stats[1] = 0.0; stats[2] = INFINITY; }
+    if (n == 0) return 1;                                  // nothing to filter: the pass-through of at most mean_k points
+    if ((rc = lio_check_device(device_id)) != LIO_OK) return rc;
+    hipStream_t s = nullptr;
+    LioTemp raw, xyzi, inl, dist;
+    HIPCHK(xyzi.alloc(n * sizeof(float4)));
+    if (mean_dist) HIPCHK(dist.alloc(n * sizeof(float)));
+    if ((rc = lio_upload_xyzi(pts, n, stride, stride >= 20 ? 16 : -1, raw, xyzi.as<float4>(), s)) != LIO_OK) return rc;
+    int no = 0;
+    LioSorReport rep;
+    rc = lio_sor_device(xyzi.as<float4>(), (int)n, mean_k, stddev_mul, inl, &no, mean_dist ? dist.as<float>() : nullptr, &rep, s);
+    if (rc < 0) return rc;
+    if (mean_dist) HIPCHK(hipMemcpyAsync(mean_dist, dist.p, n * sizeof(float), hipMemcpyDeviceToHost, s));
+    const int rc2 = lio_copy_out(inl.as<float4>(), no, out, out_stride, s);
+    if (rc2 < 0) return rc2;
+    HIPCHK(hipStreamSynchronize(s));
+    if (stats) { stats[0] = rep.mean; stats[1] = rep.stddev; stats[2] = rep.threshold; }
+    *n_out = (size_t)no;
+    return rc;
+} LIO_CATCH
+
+extern "C" void lio_local_map_default_config(lio_local_map_config* cfg)
+{
+    if (!cfg) return;
+    cfg->n_keyframes = 30;                                 // localMapKeyFramesNumber, UT:219
+    cfg->front = 70.0f; cfg->left = 40.0f; cfg->back = 20.0f; cfg->right = 40.0f;        // UT:220-223
+    cfg->remove_outliers = 1;                              // useRemovingOutliers, UT:227
+    cfg->mean_k = 10;                                      // meanK, UT:228
+    cfg->stddev_mul = 1.0f;                                // stddevThreshold, UT:229
+    cfg->downsample = 1;                                   // useDownSamplingLocalMap, UT:224
+    cfg->leaf = 0.01f;                                     // localMappingSurfLeafSize, UT:226
+}
+
+int lio_local_map_device(lio_kf_store* st, const lio_local_map_config* cfg, const float* pose, LocalMapBufs& B, size_t* n_out,
+                         lio_local_map_info* info, hipStream_t s)
+{
+    LioTemp &d_kf = B.d_kf, &d_poses = B.d_poses, &d_chunks = B.d_chunks, &world = B.world, &cropped = B.cropped, &inl = B.inl, &ds = B.ds;
+    B.cur = nullptr; B.n_cur = 0;
+    if (cfg->n_keyframes < 1) return lio_fail(LIO_ERR_ARG, "n_keyframes must be >= 1");
+    if (!std::isfinite(cfg->front) || !std::isfinite(cfg->left) || !std::isfinite(cfg->back) || !std::isfinite(cfg->right) ||
+        !(-cfg->left <= cfg->right) || !(-cfg->back <= cfg->front))
+        return lio_fail(LIO_ERR_ARG, "front, left, back, right must be finite with -left <= right and -back <= front");
+    if ((cfg->remove_outliers != 0 && cfg->remove_outliers != 1) || (cfg->downsample != 0 && cfg->downsample != 1))
+        return lio_fail(LIO_ERR_ARG, "remove_outliers and downsample are 0 or 1");
+    int rc = lio_sor_check(cfg->mean_k, cfg->stddev_mul);
+    if (rc != LIO_OK) return rc;
+    if (!(cfg->leaf > 0.0f) || !std::isfinite(cfg->leaf)) return lio_fail(LIO_ERR_ARG, "leaf must be positive and finite");
+    for (int j = 0; j < 6; ++j) if (!std::isfinite(pose[j])) return lio_fail(LIO_ERR_ARG, "non-finite pose");
+    if (n_out) *n_out = 0;
+    if (info) memset(info, 0, sizeof(*info));
+    if ((rc = lio_check_device(st->device_id)) != LIO_OK) return rc;
+    const int N = (int)st->off.size();
+    if (N == 0) return LIO_OK;                             // MO:2444-2445
+    const int first = N < cfg->n_keyframes ? 0 : N - cfg->n_keyframes;                     // startPoseNum, MO:2462
+    // ---- the keyframe sum (lio_kfstore.h) over first .. N - 1 under the stored poses
+    std::vector<int32_t> ids;
+    for (int id = first; id < N; ++id) {
+        if (!st->has_pose[(size_t)id]) return lio_fail(LIO_ERR_ARG, "a keyframe has no pose (lio_kf_store_set_poses)");
+        ids.push_back(id);
+    }
+    LioKfSum t;
+    lio_kf_sum_tables(st, ids.data(), ids.data(), (int)ids.size(), t);
+    const size_t total = t.total;
+    if (total > 0x7fffffffull - 1024) return lio_fail(LIO_ERR_CAPACITY, "too many points");
+    if (info) { info->first_keyframe = first; info->n_keyframes = N - first; info->n_summed = (int)total; }
+    if (total == 0) return LIO_OK;
+    if ((rc = lio_kf_sum_upload(t, t.poses.data(), d_kf, d_poses, d_chunks, s)) != LIO_OK) return rc;
+    HIPCHK(world.alloc(total * sizeof(float4)));
+    lio_kf_sum_launch(st, d_kf.as<LioKfDesc>(), d_poses.as<float>(), d_chunks.as<int2>(), (int)t.kf.size(), (int)t.chunks.size(), world.as<float4>(), s);
+    // ---- vehicle frame + the two pass-throughs (the wait for the count also covers the descriptors' copies)
+    float M[12];
+    lio_local_map_vehicle_frame(pose, M);
+    int n_cur = 0;
+    if ((rc = lio_crop_device(world.as<float4>(), (int)total, M, cfg->front, cfg->left, cfg->back, cfg->right, cropped, &n_cur, s)) != LIO_OK)
+        return rc;
+    const float4* cur = cropped.as<float4>();
+    if (info) info->n_cropped = n_cur;
+    if (cfg->remove_outliers) {                            // MO:2510-2516
+        LioSorReport rep;
+        int n_inl = 0;
+        if ((rc = lio_sor_device(cur, n_cur, cfg->mean_k, cfg->stddev_mul, inl, &n_inl, nullptr, &rep, s)) < 0) return rc;
+        cur = inl.as<float4>(); n_cur = n_inl;
+        if (info) { info->sor_mean = rep.mean; info->sor_stddev = rep.stddev; info->sor_threshold = rep.threshold; }
+    }
+    if (info) info->n_inliers = n_cur;
+    if (cfg->downsample) {                                 // MO:2517-2540
+        int n_ds = 0;
+        if ((rc = lio_voxel_grid_device(cur, n_cur, cfg->leaf, ds, &n_ds, s)) < 0) return rc;
+        if (info) info->voxel_passthrough = rc == 1 ? 1 : 0;
+        if (n_cur > 0) { cur = ds.as<float4>(); n_cur = n_ds; }
+    }
+    if (info) info->n_out = n_cur;
+    if (n_out) *n_out = (size_t)n_cur;
+    B.cur = cur; B.n_cur = n_cur;
+    return LIO_OK;
+}
+
+extern "C" int lio_kf_store_local_map(lio_kf_store* st, const lio_local_map_config* cfg, const float* pose, void* out, size_t out_stride,
+                                      size_t out_cap, size_t* n_out, lio_local_map_info* info)
+try {
+    if (!st || !cfg || !pose) return lio_fail(LIO_ERR_ARG, "null argument");
+    if (out && (out_stride < 20 || (out_stride & 3))) return lio_fail(LIO_ERR_ARG, "output stride must be >= 20 and a multiple of 4");
+    hipStream_t s = nullptr;
+    LocalMapBufs B;
+    int rc = lio_local_map_device(st, cfg, pose, B, n_out, info, s);
+    if (rc != LIO_OK) return rc;
+    if (out && (size_t)B.n_cur > out_cap) return lio_fail(LIO_ERR_ARG, "out holds fewer records than the local map (*n_out)");
+    if ((rc = lio_copy_out(B.cur, B.n_cur, out, out_stride, s)) < 0) return rc;
+    return LIO_OK;
+} LIO_CATCH

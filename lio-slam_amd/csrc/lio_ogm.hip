@@ -16,9 +16,9 @@
 #include <string.h>
 
 #include "lio_ogm.h"
+#include "lio_cloud.h"
 #include "lio_compact.h"
 #include "lio_kernels.h"
-#include "lio_kfstore.h"
 #include "lio_pool.h"
 #include "lio_wg.h"
 
@@ -354,19 +354,17 @@ try {
     if (rc != LIO_OK) return rc;
     *n_out = 0;
     if (n == 0) return LIO_OK;
-    if ((rc = lio_mb_check_device(device_id)) != LIO_OK) return rc;
+    if ((rc = lio_check_device(device_id)) != LIO_OK) return rc;
     hipStream_t s = nullptr;
     LioTemp raw, xyzi, inl, cnt;
-    HIPCHK(raw.alloc(n * stride));
     HIPCHK(xyzi.alloc(n * sizeof(float4)));
     if (n_neighbors) HIPCHK(cnt.alloc(n * sizeof(int)));
-    HIPCHK(hipMemcpyAsync(raw.p, pts, n * stride, hipMemcpyHostToDevice, s));
-    lio_mb_launch_rec_to_xyzi4(raw.as<unsigned char>(), stride, 0, stride >= 20 ? 16 : -1, (int)n, xyzi.as<float4>(), s);
+    if ((rc = lio_upload_xyzi(pts, n, stride, stride >= 20 ? 16 : -1, raw, xyzi.as<float4>(), s)) != LIO_OK) return rc;
     int no = 0;
     if ((rc = lio_radius_device(xyzi.as<float4>(), (int)n, radius, min_neighbors, inl, &no, n_neighbors ? cnt.as<int>() : nullptr, s)) != LIO_OK)
         return rc;
     if (n_neighbors) HIPCHK(hipMemcpyAsync(n_neighbors, cnt.p, n * sizeof(int), hipMemcpyDeviceToHost, s));
-    if ((rc = lio_mb_copy_out(inl.as<float4>(), no, out, out_stride, s)) < 0) return rc;
+    if ((rc = lio_copy_out(inl.as<float4>(), no, out, out_stride, s)) < 0) return rc;
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
     *n_out = (size_t)no;
@@ -385,13 +383,11 @@ try {
     int rc = lio_ogm_check(cfg);
     if (rc != LIO_OK) return rc;
     if (n == 0) return LIO_OK;                             // OG:134: an empty cloud, no grid
-    if ((rc = lio_mb_check_device(device_id)) != LIO_OK) return rc;
+    if ((rc = lio_check_device(device_id)) != LIO_OK) return rc;
     hipStream_t s = nullptr;
     LioTemp raw, xyzi;
-    HIPCHK(raw.alloc(n * stride));
     HIPCHK(xyzi.alloc(n * sizeof(float4)));
-    HIPCHK(hipMemcpyAsync(raw.p, pts, n * stride, hipMemcpyHostToDevice, s));
-    lio_mb_launch_rec_to_xyzi4(raw.as<unsigned char>(), stride, 0, stride >= 20 ? 16 : -1, (int)n, xyzi.as<float4>(), s);
+    if ((rc = lio_upload_xyzi(pts, n, stride, stride >= 20 ? 16 : -1, raw, xyzi.as<float4>(), s)) != LIO_OK) return rc;
     rc = lio_ogm_device(xyzi.as<float4>(), (int)n, *cfg, grid, grid_cap, info, s, lio_ogm_times_wanted());
     (void)hipStreamSynchronize(s);                         // (an early return above leaves nothing in flight on the temporaries)
     return rc;

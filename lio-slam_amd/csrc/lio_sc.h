@@ -1,4 +1,4 @@
-// lio_sc.h -- what the keyframe store (lio_mapbuild.hip) needs from lio_sc.hip: the Scan Context descriptors that live next
+// lio_sc.h -- what the keyframe store (lio_kfstore.h) needs from lio_sc.hip: the Scan Context descriptors that live next
 // to the resident keyframes, their build from a cloud on the device, and the loop detection over them.
 #pragma once
 #include <hip/hip_runtime.h>

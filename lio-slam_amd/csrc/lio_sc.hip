@@ -16,6 +16,8 @@
 #include <utility>
 
 #include "lio_sc.h"
+#include "lio_handle.h"
+#include "lio_kfstore.h"
 #include "lio_wg.h"
 
 #define SC_NO_POINT (-1000.0f)   // SC:158
@@ -411,3 +413,75 @@ int lio_sc_store_detect(LioScStore& sc, const lio_sc_config* cfg, lio_sc_result*
     res->yaw_diff_rad = (float)((double)deg * M_PI / 180.0);           // SC:17-20, SC:339
     return LIO_OK;
 }
+
+// ------------------------------------------------ Scan Context loop detection (performSCLoopClosure MO:1163-1269)
+// The entry points on the keyframe store, whose descriptor k belongs to keyframe k, and on the cloud a handle has staged.
+extern "C" int lio_kf_store_sc_add(lio_kf_store* s, const void* cloud, size_t n, size_t stride, const lio_sc_config* cfg, int32_t* id_out)
+try {
+    if (!s || (n && !cloud)) return lio_fail(LIO_ERR_ARG, "null argument");
+    if (stride < 12 || (stride & 3)) return lio_fail(LIO_ERR_ARG, "stride must be >= 12 and a multiple of 4");
+    if (n > 0x7fffffffull - 1024) return lio_fail(LIO_ERR_CAPACITY, "cloud too large");
+    int rc = lio_check_device(s->device_id);
+    if (rc != LIO_OK) return rc;
+    LioTemp raw;
+    if (n) {
+        HIPCHK(raw.alloc(n * stride));
+        HIPCHK(hipMemcpyAsync(raw.p, cloud, n * stride, hipMemcpyDefault, nullptr));
+    }
+    return lio_sc_store_append(s->sc, raw.as<unsigned char>(), stride, 0, n, cfg, nullptr, id_out);
+} LIO_CATCH
+
+extern "C" int lio_kf_store_sc_add_device(lio_kf_store* s, const void* d_cloud, size_t n, size_t stride, const lio_sc_config* cfg, int32_t* id_out)
+try {
+    if (!s || (n && !d_cloud)) return lio_fail(LIO_ERR_ARG, "null argument");
+    if (stride < 12 || (stride & 3)) return lio_fail(LIO_ERR_ARG, "stride must be >= 12 and a multiple of 4");
+    if ((uintptr_t)d_cloud & 3) return lio_fail(LIO_ERR_ARG, "d_cloud must be aligned to 4 bytes");      // k_sc_fold reads it as floats
+    int rc = lio_check_device(s->device_id);
+    if (rc != LIO_OK) return rc;
+    if (n) HIPCHK(hipDeviceSynchronize());               // the producer of d_cloud may have used any stream
+    return lio_sc_store_append(s->sc, (const unsigned char*)d_cloud, stride, 0, n, cfg, nullptr, id_out);
+} LIO_CATCH
+
+// thisRawCloudKeyFrame of MO:2149-2156 is cloud_info.cloud_deskewed: the cloud lio_s2m_register_raw has just turned into
+// float4 records on the handle (before the voxel filter).  Read where it lies, on the stream that wrote it.
+extern "C" int lio_kf_store_sc_add_from_handle(lio_kf_store* s, lio_s2m_handle* h, const lio_sc_config* cfg, int32_t* id_out)
+try {
+    if (!s || !h) return lio_fail(LIO_ERR_ARG, "null argument");
+    if (h->cfg.device_id != s->device_id) return lio_fail(LIO_ERR_ARG, "the handle and the keyframe store live on different devices");
+    if (h->multi || !h->raw_ws || !h->raw_ws->has_raw) return lio_fail(LIO_ERR_ARG, "the handle holds no cloud staged by lio_s2m_register_raw");
+    int rc = lio_check_device(s->device_id);
+    if (rc != LIO_OK) return rc;
+    LioRawWs* w = h->raw_ws;
+    return lio_sc_store_append(s->sc, w->xyzi.as<unsigned char>(), sizeof(float4), 0, w->n_raw, cfg, w->aux, id_out);
+} LIO_CATCH
+
+extern "C" int lio_kf_store_sc_count(const lio_kf_store* s)
+try {
+    return s ? (int)s->sc.count : 0;
+} LIO_CATCH
+
+extern "C" int lio_kf_store_sc_geometry(const lio_kf_store* s, int32_t* num_rings, int32_t* num_sectors)
+try {
+    if (!s || !num_rings || !num_sectors) return lio_fail(LIO_ERR_ARG, "null argument");
+    *num_rings = s->sc.count ? s->sc.rings : 0;
+    *num_sectors = s->sc.count ? s->sc.sectors : 0;
+    return LIO_OK;
+} LIO_CATCH
+
+extern "C" int lio_kf_store_sc_get(lio_kf_store* s, int32_t id, float* desc, float* ring_key, double* sector_key)
+try {
+    if (!s) return lio_fail(LIO_ERR_ARG, "null argument");
+    int rc = lio_check_device(s->device_id);
+    if (rc != LIO_OK) return rc;
+    return lio_sc_store_get(s->sc, id, desc, ring_key, sector_key);
+} LIO_CATCH
+
+extern "C" int lio_kf_store_sc_detect(lio_kf_store* s, const lio_sc_config* cfg, lio_sc_result* res)
+try {
+    if (!s || !res) return lio_fail(LIO_ERR_ARG, "null argument");
+    int rc = lio_check_device(s->device_id);
+    if (rc != LIO_OK) return rc;
+    rc = lio_sc_store_detect(s->sc, cfg, res, nullptr);
+    res->status = rc;
+    return rc;
+} LIO_CATCH

@@ -15,7 +15,9 @@
 #include <string.h>
 
 #include "lio_terrain.h"
-#include "lio_kfstore.h"
+#include "lio_cloud.h"
+#include "lio_heightmap.h"
+#include "lio_localmap.h"
 #include "lio_pool.h"
 
 #define TERR_ROWS 32               // the tile: rows are the contiguous axis of the column-major grid, a wave covers 32 x 2
@@ -207,7 +209,7 @@ try {
     if ((rc = lio_terrain_set_geometry(&plan, rows, cols, resolution, length, position)) != LIO_OK) return rc;
     const size_t n_cells = (size_t)rows * (size_t)cols;
     if (layers && (size_t)plan.n_out * n_cells > layers_cap) return lio_fail(LIO_ERR_ARG, "layers holds fewer floats than the requested layers (info)");
-    if ((rc = lio_mb_check_device(device_id)) != LIO_OK) return rc;
+    if ((rc = lio_check_device(device_id)) != LIO_OK) return rc;
     hipStream_t s = nullptr;
     LioTemp grid;
     HIPCHK(grid.alloc(sizeof(float) * n_cells));
@@ -217,4 +219,33 @@ try {
     if (rc < 0) return rc;
     HIPCHK(e);
     return rc;
+} LIO_CATCH
+
+// The height map's chain, then the terrain layers (lio_terrain.hip) on the device grid it leaves: the same null stream, complete
+// on return.
+extern "C" int lio_kf_store_terrain_map(lio_kf_store* st, const lio_local_map_config* lm, const float* pose, const lio_height_map_config* hm,
+                                        const lio_terrain_config* cfg, float* grid, size_t grid_cap, float* layers, size_t layers_cap,
+                                        lio_local_map_info* lm_info, lio_height_map_info* hm_info, lio_terrain_info* info)
+try {
+    if (!st || !lm || !pose || !hm || !cfg || !hm_info || !info) return lio_fail(LIO_ERR_ARG, "null argument");
+    int rc = lio_height_map_check(hm);
+    if (rc != LIO_OK) return rc;
+    LioTerrPlan plan;
+    if ((rc = lio_terrain_check(cfg, hm->resolution, &plan)) != LIO_OK) return rc;
+    memset(hm_info, 0, sizeof(*hm_info));
+    memset(info, 0, sizeof(*info));
+    info->normal_method_used = plan.method_used; info->edge_window_size = plan.window;
+    hipStream_t s = nullptr;
+    LocalMapBufs B;
+    if ((rc = lio_local_map_device(st, lm, pose, B, nullptr, lm_info, s)) != LIO_OK) return rc;
+    if (B.n_cur == 0) return LIO_OK;                       // an empty store or an empty crop: rows = cols = 0
+    LioTemp d_grid;
+    rc = lio_height_map_device(B.cur, B.n_cur, hm, grid, grid_cap, hm_info, s, &d_grid);
+    info->rows = hm_info->rows; info->cols = hm_info->cols;
+    if (rc != LIO_OK) return rc;
+    if (!d_grid.p) return LIO_OK;                          // no point left or no extent along an axis: no grid, no layers
+    const size_t n_cells = (size_t)info->rows * (size_t)info->cols;
+    if (layers && (size_t)plan.n_out * n_cells > layers_cap) return lio_fail(LIO_ERR_ARG, "layers holds fewer floats than the requested layers (info)");
+    if ((rc = lio_terrain_set_geometry(&plan, info->rows, info->cols, hm->resolution, hm_info->length, hm_info->position)) != LIO_OK) return rc;
+    return lio_terrain_device(d_grid.as<float>(), plan, layers, info, s);
 } LIO_CATCH

@@ -19,41 +19,8 @@
 // a prefix over the four waves -- no atomics, no sort inside the tile, deterministic.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "lio_cloud.h"             // LioVsGrid, lio_vs_key, LIO_VS_THREADS / LIO_VS_BINS
 #include "lio_wg.h"
-
-#define LIO_VS_THREADS 256
-#define LIO_VS_BINS 256
-
-struct LioVsGrid { float inv; int min_b0, min_b1, min_b2, mul1, mul2; };
-
-// pcl::VoxelGrid's grid over the cloud's bounding box mn / mx (inv = 1 / leaf), on the host (voxel_grid_device) or on the
-// device (the pose filter of lio_assemble_map_nearby, whose box never leaves the device).  Returns 0 and fills g / *n_keys;
-// 1 when PCL passes the input through (the index overflows; also a box that is not finite, which PCL does not define);
-// 2 when the grid holds more than 2^31 - 1 voxels although the extent test passed.
-__host__ __device__ inline int lio_vs_grid_from_box(const float mn[3], const float mx[3], float inv, LioVsGrid* g, long long* n_keys)
-{
-    const long long dx = (long long)((mx[0] - mn[0]) * inv) + 1, dy = (long long)((mx[1] - mn[1]) * inv) + 1,
-                    dz = (long long)((mx[2] - mn[2]) * inv) + 1;
-    bool finite_box = true;
-    for (int a = 0; a < 3; ++a) finite_box = finite_box && (mn[a] <= mx[a]) && fabsf(mn[a]) <= 3.0e38f && fabsf(mx[a]) <= 3.0e38f;
-    if (!finite_box || dx <= 0 || dy <= 0 || dz <= 0 || (double)dx * (double)dy * (double)dz > 2147483647.0) return 1;
-    g->inv = inv;
-    g->min_b0 = (int)floorf(mn[0] * inv); g->min_b1 = (int)floorf(mn[1] * inv); g->min_b2 = (int)floorf(mn[2] * inv);
-    const int d0 = (int)floorf(mx[0] * inv) - g->min_b0 + 1, d1 = (int)floorf(mx[1] * inv) - g->min_b1 + 1,
-              d2 = (int)floorf(mx[2] * inv) - g->min_b2 + 1;
-    g->mul1 = d0; g->mul2 = d0 * d1;
-    *n_keys = (long long)d0 * d1 * d2;
-    return *n_keys > 2147483647LL ? 2 : 0;
-}
-
-// the voxel index of pcl::VoxelGrid, x-fastest over the cloud's own bounding box
-__device__ __forceinline__ unsigned lio_vs_key(const LioVsGrid& g, float x, float y, float z)
-{
-    const int i0 = (int)(floorf(x * g.inv) - (float)g.min_b0);
-    const int i1 = (int)(floorf(y * g.inv) - (float)g.min_b1);
-    const int i2 = (int)(floorf(z * g.inv) - (float)g.min_b2);
-    return (unsigned)(i0 + i1 * g.mul1 + i2 * g.mul2);
-}
 
 // pairs[i] = (voxel key of point i, i)
 __global__ __launch_bounds__(256) void k_vsort_keys(LioVsGrid g, const float4* __restrict__ p, int n, uint2* __restrict__ pairs)

@@ -1494,7 +1494,7 @@ try {
     return rc;
 } LIO_CATCH
 
-// Internal (lio_mapbuild.hip): the staged records of batch slot `scan` as they were uploaded.
+// Internal (lio_handle.h): the staged records of batch slot `scan` as they were uploaded.
 int lio_s2m_staged_scan(lio_s2m_handle* h, int scan, const unsigned char** d_rec, size_t* n, size_t* stride, size_t* xyz_off, int* int_off,
                         int* device_id, hipStream_t* stream)
 {
