@@ -624,14 +624,24 @@ __global__ __launch_bounds__(LIO_BLOCK) void k_block_boxes(const LioBlockDesc* _
 //     1 m present, so its 5-NN set is the unsharded one; no wave runs for a handful of owned lanes any more.
 //   * otherwise (a workgroup longer than the halo allows, or no plan): per-point ownership by the cell of the point's
 //     own position (mode 0) on the ranks whose slab the interval meets, skipped (mode 1) elsewhere.
-// For a skipped workgroup this kernel reports the all-zero partial sum and the arrival in its place and drops the
-// points' search bounds; k_s2m_iterate returns on the flag before loading a point.  The rule never changes a result.
+// For a skipped workgroup this kernel reports the all-zero partial sum and the arrival in its place, drops the
+// points' search bounds and, in the recorded iteration, marks their record entries "not processed here";
+// k_s2m_iterate returns on the flag before loading a point.  The rule never changes a result.
 struct LioShardPlan {
     int n_ranks;            // 0 = no whole-workgroup ownership (lio_s2m_set_shard)
     int rank;
     int halo;               // cells of map held beyond the slab on each side (>= 1)
     int bounds[9];          // rank r owns cells [bounds[r], bounds[r+1])
 };
+
+// Record entry oi (caller's point order) of a point this rank does not process in the recorded iteration.
+__device__ __forceinline__ void lio_record_unprocessed(const LioIterParams& P, int oi)
+{
+    P.rec_flag[oi] = 0;
+    reinterpret_cast<float4*>(P.rec_coeff)[oi] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+#pragma unroll
+    for (int j = 0; j < 5; ++j) P.rec_nn[(size_t)oi * 5 + j] = -1;
+}
 
 __global__ __launch_bounds__(256) void k_shard_cull(LioIterParams P, LioShardPlan plan, const float* __restrict__ block_box, int n_blocks,
                                                     unsigned char* __restrict__ skip)
@@ -679,6 +689,14 @@ __global__ __launch_bounds__(256) void k_shard_cull(LioIterParams P, LioShardPla
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");      // (all eight lanes have read skip[i] before lane 0 rewrites it)
     if (c == 0) skip[i] = (unsigned char)mode;
     if (mode != 1) return;
+    // The association record of a skipped workgroup is "not processed here" (what the upload left in it): a second run on
+    // the same upload must not show the record of a run in which this rank did process these points.
+    if (P.rec_flag != nullptr && st->iter == P.c.record_iter) {
+        for (int j = c; j < LIO_BLOCK; j += 8) {
+            const int li = bd.first + j;
+            if (li < st->n_pts) lio_record_unprocessed(P, P.perm ? P.perm[base + li] : base + li);
+        }
+    }
     double* part0 = P.partials + ((size_t)bd.scan * P.max_blk + bd.blk) * LIO_SUMS;
     for (int j = c; j < 28; j += 8) __hip_atomic_store(part0 + j, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // (every lane of the wave has drained its stores before any lane arrives)
@@ -889,6 +907,14 @@ void k_s2m_iterate(LioIterParams P)
 #pragma unroll
                 for (int pp = 0; pp < PPT; ++pp)
                     if (inr[pp]) P.d5_cache[base + bd.first + pp * LIO_BLOCK + (int)threadIdx.x] = -1.0f;
+            }
+            // and their record is "not processed here", whatever an earlier run on the same upload left in it
+            if (record) {
+#pragma unroll
+                for (int pp = 0; pp < PPT; ++pp) {
+                    const int li = bd.first + pp * LIO_BLOCK + (int)threadIdx.x;
+                    if (inr[pp]) lio_record_unprocessed(P, P.perm ? P.perm[base + li] : base + li);
+                }
             }
             if (wave != 0) return;
             double* part0 = P.partials + ((size_t)bd.scan * P.max_blk + bd.blk) * LIO_SUMS;

@@ -134,6 +134,41 @@ def test_plan_shards_properties():
     assert len(mg.shard_points(np.zeros((0, 3), np.float32), empty, 2)) == 0
 
 
+@pytest.mark.parametrize("axis", [1, 2])
+def test_plan_shards_properties_on_the_other_axes(axis):
+    """The twin of test_plan_shards_properties for a map that is longest along y or z (a vehicle that drives north-south,
+    a shaft): the same properties, read along that axis."""
+    mg = importlib.import_module("lio-slam_amd.multigpu")
+    rng = np.random.default_rng(0)
+    extent = np.roll(np.array([120, 15, 4]), axis)
+    pts = (rng.uniform(-1, 1, (20000, 3)) * extent).astype(np.float32)
+    for world in (1, 2, 4, 8):
+        plan = mg.plan_shards(pts, world)
+        b = plan["bounds"]
+        assert plan["axis"] == axis
+        assert b[0] == 0 and b[-1] == plan["dims"][axis] and (np.diff(b) >= 0).all()
+        total = 0
+        for r in range(world):
+            idx = mg.shard_points(pts, plan, r)
+            own = mg.owner_mask(pts, plan, r)
+            total += own.sum()
+            assert set(np.nonzero(own)[0]) <= set(idx)
+            lo = pts[own][:, axis].min() - 1.0 if own.any() else 0
+            hi = pts[own][:, axis].max() + 1.0 if own.any() else 0
+            need = np.nonzero((pts[:, axis] > lo) & (pts[:, axis] < hi))[0]
+            assert set(need) <= set(idx)
+        assert total == len(pts)
+        counts = [mg.owner_mask(pts, plan, r).sum() for r in range(world)]
+        assert max(counts) < 2.0 * len(pts) / world + 500
+    # a plan balanced by a load sample, along the same axis
+    load = pts[np.abs(pts[:, axis]) < 30]
+    p_load = mg.plan_shards(pts, 4, load_xyz=load)
+    assert p_load["axis"] == axis and np.all(np.diff(p_load["bounds"]) >= 0)
+    c = np.clip(mg.cell_coord(load[:, axis], p_load["origin"][axis], p_load["inv_cell"], p_load["dims"][axis]), 0, p_load["dims"][axis] - 1)
+    share = np.array([((c >= p_load["bounds"][r]) & (c < p_load["bounds"][r + 1])).sum() for r in range(4)]) / len(load)
+    assert share.max() < 0.25 + 0.03, share
+
+
 def test_slab_plan_properties():
     """Host logic of the sharded map (lio-slam_amd/multigpu.py): bounds are monotone and cover the grid, a plan balanced by
     a load sample equalises that sample (not the map), a wider halo only ever adds map points, and every map point is held
