@@ -263,6 +263,11 @@ int  lio_s2m_get_profile(lio_s2m_handle *h, lio_s2m_profile *out);
  * when the handle is created forces the general one), bits 8.. = the waves per SIMD it was compiled for.  0 before any run
  * and after a one-launch loop; negative = error. */
 int  lio_s2m_kernel_variant(const lio_s2m_handle *h);
+/* How many surface launches of the last run had one workgroup per entry of the block list (*n_full) and how many were the
+ * looped form of the plain kernel on a fixed grid (*n_looped), which launches take from index LIO_TAIL_FROM of a run on
+ * (environment, read when the handle is created: -1 = never, 0 = every launch; LIO_TAIL_WGS = its workgroups, a multiple of
+ * 8).  Both forms compute the same bytes.  A one-launch loop and a multi-device front handle report 0 / 0. */
+int  lio_s2m_launch_forms(const lio_s2m_handle *h, int32_t *n_full, int32_t *n_looped);
 /* Test hook for the one-launch loop (cfg.pipeline 0 / 4): spin_max = polls before a workgroup waiting at its scan's barrier
  * gives up (0 = default: 4096, a few milliseconds; LIO_PERSIST_SPIN_MAX in the environment), withhold_wg = index of an
  * association workgroup that never arrives (-1 = none).  A launch that times out is re-run through the launch loop inside

@@ -251,7 +251,7 @@ EXPORTS = [
     "lio_global_map_default_config", "lio_kf_store_global_map", "lio_kf_store_export_map", "lio_kf_store_get_keyframe",
     "lio_s2m_registered_cloud",
     "lio_radius_filter", "lio_ogm_default_config", "lio_occupancy_grid", "lio_kf_store_occupancy_grid", "lio_ogm_debug_stage_ms",
-    "lio_s2m_kernel_variant",
+    "lio_s2m_kernel_variant", "lio_s2m_launch_forms",
 ]
 
 
@@ -300,6 +300,8 @@ def load_library():
     L.lio_s2m_get_correspondences.argtypes = [vp, i32, vp, vp, vp]
     L.lio_s2m_get_profile.argtypes = [vp, C.POINTER(S2MProfile)]
     L.lio_s2m_kernel_variant.argtypes = [vp]
+    if hasattr(L, "lio_s2m_launch_forms"):             # (A/B runs load older builds through LIOGPU_LIB)
+        L.lio_s2m_launch_forms.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
     L.lio_s2m_set_corner_map.argtypes = [vp, vp, sz, sz]
     L.lio_s2m_batch_upload_corners.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz), sz]
     L.lio_s2m_register_cs.argtypes = [vp, vp, sz, vp, sz, sz, C.POINTER(f32), C.POINTER(S2MResult)]
@@ -612,6 +614,13 @@ class ScanToMap:
         v = self.lib.lio_s2m_kernel_variant(self.h)
         _check(min(v, 0), "lio_s2m_kernel_variant")
         return bool(v & 1), v >> 8
+
+    def launch_forms(self):
+        """(full, looped): surface launches of the last run with one workgroup per block, and with the looped form of the plain
+        kernel (LIO_TAIL_FROM / LIO_TAIL_WGS in the environment when the handle was created; include/liogpu.h)."""
+        full, looped = C.c_int32(0), C.c_int32(0)
+        _check(self.lib.lio_s2m_launch_forms(self.h, C.byref(full), C.byref(looped)), "lio_s2m_launch_forms")
+        return full.value, looped.value
 
     def debug_persist_spin(self, spin_max=0, withhold_wg=-1):
         """Test hook of the one-launch loop: poll bound and a workgroup that never arrives (include/liogpu.h)."""

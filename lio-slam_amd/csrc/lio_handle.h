@@ -114,6 +114,12 @@ struct lio_s2m_handle {
     int units_this_run = 0, unit_iters = 1;
     bool plain_kernel = true;         // LIO_PLAIN_KERNEL=0 in the environment at lio_s2m_create: always the general k_s2m_iterate (A/B runs)
     int iterate_variant = 0;          // instantiation of the last run's surface launches (lio_s2m_kernel_variant)
+    // Looped form of the plain kernel for the late launches of a run (k_s2m_iterate_tail), read from the environment at lio_s2m_create:
+    int tail_from = LIO_TAIL_FROM_DEFAULT;   // LIO_TAIL_FROM: launches whose index within the run is >= this take it; -1 = never, 0 = all
+    int tail_wgs = LIO_TAIL_WGS_DEFAULT;     // LIO_TAIL_WGS: its grid, a multiple of 8 (>= 8)
+    int graph_tail_from = -1, graph_tail_wgs = 0;   // ... the cached graph was captured under
+    int graph_n_full = 0, graph_n_looped = 0;       // surface launches of each form in the cached graph
+    int run_n_full = 0, run_n_looped = 0;           // ... enqueued by the last run (lio_s2m_launch_forms)
 
     // correspondence record (debug / parity)
     LioDevBuf<unsigned char> d_rec_flag;

@@ -48,7 +48,13 @@ void lio_launch_init_state(LioScanState* st, int n_scans, float* poses, bool fro
                            int* n_active, hipStream_t s);
 // (both return the instantiation chosen: bit 0 = plain, bits 8.. = its occupancy target)
 int  lio_iterate_variant(const LioIterParams& P, int ppt, bool stage, bool corner, bool allow_plain);
-int  lio_launch_iterate(const LioIterParams& P, int n_blocks, int ppt, bool stage, hipStream_t s, bool corner = false, bool allow_plain = true);
+int  lio_launch_iterate(const LioIterParams& P, int n_blocks, int ppt, bool stage, hipStream_t s, bool corner = false, bool allow_plain = true,
+                         int tail_wgs = 0, bool* looped = nullptr);
+// Defaults of LIO_TAIL_FROM / LIO_TAIL_WGS (liogpu_api.hip), from the sweep in profiles/tail_launches_sweep.txt
+#define LIO_TAIL_FROM_DEFAULT 7
+#define LIO_TAIL_WGS_DEFAULT 1536
+// (lio_tail.hip) the looped form on n_wgs workgroups, a multiple of 8; the caller has checked that the launch is a plain one
+void lio_launch_iterate_tail(const LioIterParams& P, int n_blocks, int n_wgs, hipStream_t s);
 void lio_launch_persist(const LioIterParams& P, int n_blocks, unsigned* gen, unsigned epoch, const unsigned char* stage, size_t stride,
                         int n_scans, unsigned* spec, double* spec_sums, const float* poses0, unsigned spin_max, int withhold_wg, hipStream_t s);
 void lio_launch_pack_summary(const LioScanState* st, int n_scans, float* out, hipStream_t s);

@@ -463,6 +463,7 @@ LIO_DEV void lio_arrive_and_finish(const LioIterParams& P, const LioBlockDesc& b
     // its result --, so they cannot be older than the last arrival)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if (lane == 0) P.arrive[bd.scan] = 0;                  // re-arm for the next launch
-    if (PLAIN || !P.sums_out) lio_gn_step(st, s_sum, P.c, s_ws, P.n_active, lane);
+    // (always inline: as a call from inside the looped form's entry loop it would force every value that lives across it to scratch)
+    if (PLAIN || !P.sums_out) [[clang::always_inline]] lio_gn_step(st, s_sum, P.c, s_ws, P.n_active, lane);
 }
 

@@ -152,6 +152,10 @@ try {
     // the plain instantiation of k_s2m_iterate (lio_launch_iterate) unless LIO_PLAIN_KERNEL=0 in the environment: kept per
     // handle, so one process can hold both kinds for A/B runs
     { const char* e = getenv("LIO_PLAIN_KERNEL"); h->plain_kernel = !(e && *e && atoi(e) == 0); }
+    // the looped form of the plain kernel from launch LIO_TAIL_FROM of a run on (-1: never), on LIO_TAIL_WGS workgroups
+    { const char* e = getenv("LIO_TAIL_FROM"); if (e && *e) h->tail_from = atoi(e) < 0 ? -1 : atoi(e); }
+    { const char* e = getenv("LIO_TAIL_WGS"); if (e && *e) h->tail_wgs = atoi(e); }
+    h->tail_wgs = h->tail_wgs < 8 ? 8 : ((h->tail_wgs + 7) & ~7);
     const int rc = lio_s2m_init_resources(h.get());
     if (rc != LIO_OK) return rc;
     *out = h.release();
@@ -1069,11 +1073,16 @@ static void lio_fill_params_corner(lio_s2m_handle* h, LioIterParams& Pc, double*
 // One Gauss-Newton iteration of the batch: cornerOptimization (if a corner batch is resident), then
 // surfOptimization MO:1618-1687; the workgroup that arrives last on a scan's counter runs
 // LMOptimization MO:1702-1837 for it.
-static void lio_launch_gn(lio_s2m_handle* h, const LioIterParams& P, const LioIterParams* Pc)
+// `index`: the launch's position within the run (0-based); from h->tail_from on, a launch that qualifies for the plain
+// instantiation takes its looped form.  Returns whether it did.
+static bool lio_launch_gn(lio_s2m_handle* h, const LioIterParams& P, const LioIterParams* Pc, int index)
 {
     if (Pc) lio_launch_iterate(*Pc, h->corner->n_blocks, 1, false, h->stream, true);
     // (a run with a corner batch keeps the general surface kernel: that path is as it was)
-    h->iterate_variant = lio_launch_iterate(P, h->n_blocks, h->ppt, h->cfg.use_lds != 0, h->stream, false, h->plain_kernel && !Pc);
+    const int tail_wgs = (h->tail_from >= 0 && index >= h->tail_from) ? h->tail_wgs : 0;
+    bool looped = false;
+    h->iterate_variant = lio_launch_iterate(P, h->n_blocks, h->ppt, h->cfg.use_lds != 0, h->stream, false, h->plain_kernel && !Pc, tail_wgs, &looped);
+    return looped;
 }
 
 extern "C" int lio_s2m_batch_begin(lio_s2m_handle* h)
@@ -1102,6 +1111,7 @@ try {
     h->units_this_run = 0;
     h->unit_iters = 1;
     h->iterate_variant = 0;             // (set by the first k_s2m_iterate launch of the run; a one-launch loop leaves 0)
+    h->run_n_full = h->run_n_looped = 0;
     h->ran = true;
     return LIO_OK;
 } LIO_CATCH
@@ -1114,16 +1124,24 @@ static int lio_graph_prepare(lio_s2m_handle* h, const LioIterParams& P, const Li
     // the cached graph stays valid as long as the kernel arguments and the launch geometry are the same
     const int nbc = Pc ? h->corner->n_blocks : -1;
     if (h->graph_exec && h->graph_chunk == chunk && h->graph_blocks == h->n_blocks && h->graph_ppt == h->ppt &&
-        h->graph_plain == h->plain_kernel && memcmp(&h->graph_params, &P, sizeof(P)) == 0 && h->graph_blocks_c == nbc &&
+        h->graph_plain == h->plain_kernel && h->graph_tail_from == h->tail_from && h->graph_tail_wgs == h->tail_wgs &&
+        memcmp(&h->graph_params, &P, sizeof(P)) == 0 && h->graph_blocks_c == nbc &&
         (!Pc || memcmp(&h->graph_params_c, Pc, sizeof(P)) == 0))
         return LIO_OK;
     if (h->graph_exec) { HIPCHK(hipGraphExecDestroy(h->graph_exec)); h->graph_exec = nullptr; }
     if (h->graph) { HIPCHK(hipGraphDestroy(h->graph)); h->graph = nullptr; }
     HIPCHK(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-    for (int i = 0; i < chunk; ++i) lio_launch_gn(h, P, Pc);
+    // (every unit of a run replays this graph: the position in the chunk stands for the index within the run.  A launch of a
+    // later unit is then full-grid where its index alone would make it looped; both forms compute the same)
+    h->graph_n_full = h->graph_n_looped = 0;
+    for (int i = 0; i < chunk; ++i) {
+        if (lio_launch_gn(h, P, Pc, i)) h->graph_n_looped++;
+        else h->graph_n_full++;
+    }
     HIPCHK(hipStreamEndCapture(h->stream, &h->graph));
     HIPCHK(hipGraphInstantiate(&h->graph_exec, h->graph, nullptr, nullptr, 0));
     h->graph_chunk = chunk; h->graph_blocks = h->n_blocks; h->graph_ppt = h->ppt; h->graph_plain = h->plain_kernel;
+    h->graph_tail_from = h->tail_from; h->graph_tail_wgs = h->tail_wgs;
     memcpy(&h->graph_params, &P, sizeof(P));
     h->graph_blocks_c = nbc;
     if (Pc) memcpy(&h->graph_params_c, Pc, sizeof(P));
@@ -1160,8 +1178,11 @@ static int lio_run_continue(lio_s2m_handle* h, bool blocking)
             lio_launch_persist(h->run_P, h->n_blocks, h->d_gen, h->gen_epoch, h->soa_valid ? nullptr : h->last_stage + h->last_xyz_off,
                                h->last_stride, h->n_scans, getenv("LIO_NO_SPEC") ? nullptr : h->d_gen + h->n_scans, h->d_spec_sums, h->d_poses,
                                lio_persist_spin_max(h), h->persist_withhold, h->stream);
-        } else if (h->run_graph) HIPCHK(hipGraphLaunch(h->graph_exec, h->stream));
-        else lio_launch_gn(h, h->run_P, Pc);
+        } else if (h->run_graph) {
+            HIPCHK(hipGraphLaunch(h->graph_exec, h->stream));
+            h->run_n_full += h->graph_n_full; h->run_n_looped += h->graph_n_looped;
+        } else if (lio_launch_gn(h, h->run_P, Pc, u)) h->run_n_looped++;
+        else h->run_n_full++;
         if (prof) HIPCHK(hipEventRecord(h->ev_end[u], h->stream));
         if (!h->run_persist) HIPCHK(hipMemcpyAsync(&h->h_active[u], h->d_active, sizeof(int), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipEventRecord(h->ev_chk[u], h->stream));
@@ -1231,6 +1252,16 @@ try {
     return h->iterate_variant;
 } LIO_CATCH
 
+// Surface launches of the last run by form: *n_full with one workgroup per entry of the block list (k_s2m_iterate), *n_looped
+// with the looped form of the plain instantiation (k_s2m_iterate_tail).  A one-launch loop (k_s2m_persist) counts as neither.
+extern "C" int lio_s2m_launch_forms(const lio_s2m_handle* h, int32_t* n_full, int32_t* n_looped)
+try {
+    if (!h || !n_full || !n_looped) return lio_fail(LIO_ERR_ARG, "null argument");
+    *n_full = h->multi ? 0 : h->run_n_full;            // (the devices' handles publish their sums: never looped, not counted here)
+    *n_looped = h->multi ? 0 : h->run_n_looped;
+    return LIO_OK;
+} LIO_CATCH
+
 extern "C" int lio_s2m_batch_iter_partial(lio_s2m_handle* h, double* d_sums)
 try {
     if (!h || !d_sums) return lio_fail(LIO_ERR_ARG, "null argument");
@@ -1265,7 +1296,8 @@ try {
     } else {
         P.blk_skip = nullptr;
     }
-    lio_launch_gn(h, P, with_corners ? &Pcs : nullptr);
+    if (lio_launch_gn(h, P, with_corners ? &Pcs : nullptr, it)) h->run_n_looped++;     // (never: a launch that publishes its sums is not plain)
+    else h->run_n_full++;
     if (prof) HIPCHK(hipEventRecord(h->ev_end[it], h->stream));
     h->launches_this_run++;
     h->units_this_run = h->launches_this_run;
