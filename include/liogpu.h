@@ -971,6 +971,79 @@ int  lio_kf_store_occupancy_grid(lio_kf_store *s, float map_resolution, const li
  * grid copy, in milliseconds. */
 int  lio_ogm_debug_stage_ms(int32_t enable, float ms[6]);
 
+/* ------------------------------------------------ signed distance field (grid_map_sdf behind the height map) */
+/* src/grid_map/grid_map_sdf: the query a planner makes of the terrain -- how far a body point is from it and in which
+ * direction it lies.  SignedDistanceField (the 3-D field over the `elevation` layer with its three derivatives),
+ * SignedDistance2d (the planar field of an occupancy grid), Gridmap3dLookup (nearest node, first-order extrapolation).
+ * DESIGN.md section 4i states the conventions.  The arithmetic is the reference's fp32 text, serial sweep included; its own
+ * tests hold it to an N^2 definition within 1e-4 (distance from a cell centre to the border of the nearest cell column of
+ * the other class, the height difference as third component), and so do this repository's. */
+typedef struct lio_sdf lio_sdf;
+typedef struct lio_sdf_config {
+    double  min_height, max_height;  /* the field's band; NaN = the finite cells' minimum / maximum; max < min: LIO_ERR_ARG  */
+    int32_t nan_policy;              /* 0: a layer with a non-finite cell is refused (LIO_ERR_ARG, info.n_nan filled in; the
+                                      * reference warns that its result is invalid); 1: labelled extension -- such a cell
+                                      * reads as the smallest finite elevation                                                */
+    int32_t pad;
+} lio_sdf_config;
+typedef struct lio_sdf_info {
+    int32_t rows, cols, layers;      /* the 3-D grid: size(0) along x, size(1) along y, numZLayers = max(ceil(band / res), 2) */
+    int32_t n_nan;                   /* non-finite cells of the elevation layer                                              */
+    double  origin[3], resolution;   /* the centre of cell (0, 0) and the band's lower end: node (0, 0, 0)                    */
+    float   layer_min, layer_max;    /* minCoeff / maxCoeff of the layer (finite cells): they pick each layer's branch        */
+    int32_t n_all_obstacle, n_all_free, n_mixed;   /* layers below the minimum, above the maximum, between                   */
+    int32_t pad;
+} lio_sdf_info;
+#define LIO_SDF_NODE_LIMIT (1 << 25)   /* rows x cols x layers above it: LIO_ERR_CAPACITY (16 bytes a node)                  */
+void lio_sdf_default_config(lio_sdf_config *cfg);           /* NaN, NaN, 0 */
+/* The object owns the resident field (rows x cols x layers nodes of 16 bytes, plus 4 bytes a node of distances) and the
+ * workspace of the build, both reused between builds and grown, never shrunk.  The workspace of a build is 24 bytes x rows x
+ * cols x slab (8 of intermediate distances, 16 of the lines' lower bounds), slab = the layers swept at once: at most 32, fewer
+ * until that product fits 128 MiB, at least 1 -- so at most max(128 MiB, 24 bytes x rows x cols), for any aspect of the grid. */
+int  lio_sdf_create(int32_t device_id, lio_sdf **out);
+void lio_sdf_destroy(lio_sdf *sdf);
+/* SignedDistanceField's constructor on a host grid, column-major rows x cols floats (grid_map::Matrix); `length` and
+ * `position` are lio_height_map_info's.  Layer z lies at float(min_height) + z * resolution (formed in float as the reference
+ * forms it); per layer the two Euclidean distance transforms of SignedDistance2d.cpp in pixel units, combined to
+ * resolution * (to_obstacle - to_free), or one of them alone where the layer lies wholly below or above the terrain; then the
+ * central differences (one-sided at the six faces) along x, y with -resolution and along z with +resolution.  The previous
+ * field of the object is replaced; after a failure the object holds none.  LIO_ERR_ARG before any device is touched, never a
+ * clamp: rows or cols < 2 (the reference asserts), non-finite length or position, resolution < 1e-4 or not finite,
+ * length[a] != size[a] * resolution, max_height < min_height, a nan_policy other than 0 / 1, rows or cols >= 2^24.
+ * LIO_ERR_ARG after the layer was read: a non-finite cell under nan_policy 0, no finite cell at all.  More than
+ * LIO_SDF_NODE_LIMIT nodes: LIO_ERR_CAPACITY with info filled in (before any device is touched where 2 layers already exceed it).  info may be NULL.  Complete on return. */
+int  lio_sdf_build(lio_sdf *sdf, const float *elevation, int32_t rows, int32_t cols, double resolution,
+                   const double length[2], const double position[2], const lio_sdf_config *cfg, lio_sdf_info *info);
+/* lio_kf_store_height_map's chain (same arguments, same grid bytes; `grid` may be NULL), then the build above on the device
+ * grid it leaves: nothing else crosses to the host.  hm->resolution is the field's.  An empty store or an empty local map:
+ * LIO_OK, rows = cols = 0, the object holds no field.  A store and an sdf on different devices: LIO_ERR_ARG.  The rules stated
+ * above lio_global_map_config hold: the store is left as found, the result is complete on return, calls on one store and on
+ * one sdf remain non-re-entrant.  What a planning node calls after cloudMapInfoHandler. */
+int  lio_kf_store_sdf(lio_kf_store *s, const lio_local_map_config *lm, const float pose[6],
+                      const lio_height_map_config *hm, const lio_sdf_config *cfg, float *grid, size_t grid_cap,
+                      lio_sdf *sdf, lio_local_map_info *lm_info, lio_height_map_info *hm_info, lio_sdf_info *info);
+/* The field in the reference's data_ order: {distance, dx, dy, dz} as four floats at ((z * cols + col) * rows + row) * 4.
+ * cap_floats < 4 x rows x cols x layers, or no field: LIO_ERR_ARG. */
+int  lio_sdf_nodes(lio_sdf *sdf, float *nodes, size_t cap_floats);
+/* valueAndDerivative for n positions (x, y, z as doubles): the nearest node by std::round, clamped to the grid on all six
+ * sides in double, value = distance + derivative . (position - node position) in double, summed x, y, z.  `derivative` (n x 3,
+ * may be NULL) receives the node's.  n = 0: LIO_OK.  No field: LIO_ERR_ARG. */
+int  lio_sdf_query(lio_sdf *sdf, const double *positions, size_t n, double *value, double *derivative);
+/* signedDistanceFromOccupancy on a nav_msgs/OccupancyGrid.data as lio_occupancy_grid writes it: the row-major message is
+ * read as the column-major width x height matrix, a cell is an obstacle iff its value >= occupied_min (100 is what the draft
+ * writes besides 0).  out: width x height floats in the grid's layout, resolution * (pixels to the nearest obstacle - pixels
+ * to the nearest free cell); +INF everywhere without an obstacle, -INF everywhere without free space.  The same sweeps as the
+ * field's, with the offsets 0 / INF and one layer.  LIO_ERR_ARG: width or height < 1 or >= 2^24, more than 2^31 - 1 cells,
+ * resolution < 1e-4 or not finite. */
+int  lio_occupancy_sdf(int32_t device_id, const int8_t *grid, int32_t width, int32_t height, float resolution,
+                       int32_t occupied_min, float *out);
+/* The device memory the object holds now, in bytes: the field (nodes and distances) and the build's workspace.  Either may be NULL. */
+int  lio_sdf_memory(lio_sdf *sdf, size_t *field_bytes, size_t *workspace_bytes);
+/* Measurement hook (tools/sdf_cost.py): enable != 0 makes the calling thread's following builds record their stage
+ * boundaries as HIP events; ms (may be NULL) receives the last such build's layer statistics with their host wait, column
+ * sweeps, row sweeps and node stencil, in milliseconds (a build's allocations fall between the first and the second). */
+int  lio_sdf_debug_stage_ms(int32_t enable, float ms[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -270,6 +270,22 @@ public:
         check(lio_kf_store_occupancy_grid(s_, map_resolution, &c, grid, grid_cap, n_map, &info), "lio_kf_store_occupancy_grid");
         return (size_t)info.width * (size_t)info.height;
     }
+    // heightMap followed by grid_map_sdf's SignedDistanceField on the device grid: `sdf` (a SignedDistanceField below) receives
+    // the field, `grid` (may be nullptr) the elevation.  hm_cfg->resolution is the field's.  Returns the number of nodes.
+    size_t signedDistanceField(const float transformTobeMapped[6], lio_sdf* sdf, lio_sdf_info& info, float* grid = nullptr, size_t grid_cap = 0,
+                               const lio_sdf_config* cfg = nullptr, const lio_height_map_config* hm_cfg = nullptr,
+                               const lio_local_map_config* lm_cfg = nullptr, lio_height_map_info* hm_info = nullptr,
+                               lio_local_map_info* lm_info = nullptr)
+    {
+        lio_local_map_config lm;
+        if (lm_cfg) lm = *lm_cfg; else lio_local_map_default_config(&lm);
+        lio_height_map_config hm;
+        if (hm_cfg) hm = *hm_cfg; else lio_height_map_default_config(&hm);
+        lio_sdf_config c;
+        if (cfg) c = *cfg; else lio_sdf_default_config(&c);
+        check(lio_kf_store_sdf(s_, &lm, transformTobeMapped, &hm, &c, grid, grid_cap, sdf, lm_info, hm_info, &info), "lio_kf_store_sdf");
+        return (size_t)info.rows * (size_t)info.cols * (size_t)info.layers;
+    }
     lio_kf_store* get() { return s_; }
 
 private:
@@ -278,6 +294,45 @@ private:
         if (rc < 0) throw Error(rc, std::string(what) + ": " + lio_last_error());
     }
     lio_kf_store* s_ = nullptr;
+};
+
+// grid_map::SignedDistanceField resident on the device (grid_map_sdf/SignedDistanceField.hpp): built from an elevation grid
+// or by KeyframeStore::signedDistanceField, queried by valueAndDerivative.
+class SignedDistanceField {
+public:
+    explicit SignedDistanceField(int32_t device_id = 0)
+    {
+        const int rc = lio_sdf_create(device_id, &s_);
+        if (rc < 0) throw Error(rc, std::string("lio_sdf_create: ") + lio_last_error());
+    }
+    ~SignedDistanceField() { lio_sdf_destroy(s_); }
+    SignedDistanceField(const SignedDistanceField&) = delete;
+    SignedDistanceField& operator=(const SignedDistanceField&) = delete;
+
+    // SignedDistanceField(gridMap, "elevation", minHeight, maxHeight) on a host grid, column-major rows x cols
+    // (grid_map::Matrix); length and position: the grid map's.  cfg == nullptr: the band of the finite cells, NaN refused.
+    void build(const float* elevation, int32_t rows, int32_t cols, double resolution, const double length[2], const double position[2],
+               lio_sdf_info& info, const lio_sdf_config* cfg = nullptr)
+    {
+        lio_sdf_config c;
+        if (cfg) c = *cfg; else lio_sdf_default_config(&c);
+        check(lio_sdf_build(s_, elevation, rows, cols, resolution, length, position, &c, &info), "lio_sdf_build");
+    }
+    // valueAndDerivative for n positions (x, y, z); derivative (n x 3) may be nullptr
+    void valueAndDerivative(const double* positions, size_t n, double* value, double* derivative = nullptr)
+    {
+        check(lio_sdf_query(s_, positions, n, value, derivative), "lio_sdf_query");
+    }
+    // data_: {distance, dx, dy, dz} per node, (z * cols + col) * rows + row
+    void nodes(float* out, size_t cap_floats) { check(lio_sdf_nodes(s_, out, cap_floats), "lio_sdf_nodes"); }
+    lio_sdf* get() { return s_; }
+
+private:
+    static void check(int rc, const char* what)
+    {
+        if (rc < 0) throw Error(rc, std::string(what) + ": " + lio_last_error());
+    }
+    lio_sdf* s_ = nullptr;
 };
 
 }  // namespace liogpu

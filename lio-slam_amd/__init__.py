@@ -15,7 +15,8 @@ from .api import (LioError, ScanToMap, S2MConfig, S2MResult, S2MProfile, DeskewC
                   HeightMapConfig, HeightMapInfo, height_map, height_map_default_config,
                   TerrainConfig, TerrainInfo, TERRAIN_LAYERS, terrain_layers, terrain_default_config,
                   GlobalMapConfig, GlobalMapInfo, ExportConfig, global_map_default_config, STAGED_DS, STAGED_RAW,
-                  OgmConfig, OgmInfo, ogm_default_config, radius_filter, occupancy_grid)
+                  OgmConfig, OgmInfo, ogm_default_config, radius_filter, occupancy_grid,
+                  SdfConfig, SdfInfo, Sdf, SDF_NODE_LIMIT, sdf_default_config, occupancy_sdf)
 
 __all__ = ["LioError", "ScanToMap", "S2MConfig", "S2MResult", "S2MProfile", "DeskewConfig",
            "lib_path", "load_library", "build_library", "deskew", "curvature", "imu_deskew_info",
@@ -27,4 +28,5 @@ __all__ = ["LioError", "ScanToMap", "S2MConfig", "S2MResult", "S2MProfile", "Des
            "HeightMapConfig", "HeightMapInfo", "height_map", "height_map_default_config",
            "TerrainConfig", "TerrainInfo", "TERRAIN_LAYERS", "terrain_layers", "terrain_default_config",
            "GlobalMapConfig", "GlobalMapInfo", "ExportConfig", "global_map_default_config", "STAGED_DS", "STAGED_RAW",
-           "OgmConfig", "OgmInfo", "ogm_default_config", "radius_filter", "occupancy_grid"]
+           "OgmConfig", "OgmInfo", "ogm_default_config", "radius_filter", "occupancy_grid",
+           "SdfConfig", "SdfInfo", "Sdf", "SDF_NODE_LIMIT", "sdf_default_config", "occupancy_sdf"]

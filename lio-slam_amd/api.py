@@ -202,6 +202,18 @@ class OgmInfo(C.Structure):
                 ("n_inliers", C.c_int32), ("n_binned", C.c_int32), ("n_occupied", C.c_int32), ("pad", C.c_int32)]
 
 
+class SdfConfig(C.Structure):
+    """grid_map_sdf's band and what to do with a non-finite cell (include/liogpu.h lio_sdf_config)."""
+    _fields_ = [("min_height", C.c_double), ("max_height", C.c_double), ("nan_policy", C.c_int32), ("pad", C.c_int32)]
+
+
+class SdfInfo(C.Structure):
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("layers", C.c_int32), ("n_nan", C.c_int32), ("origin", C.c_double * 3),
+                ("resolution", C.c_double), ("layer_min", C.c_float), ("layer_max", C.c_float), ("n_all_obstacle", C.c_int32),
+                ("n_all_free", C.c_int32), ("n_mixed", C.c_int32), ("pad", C.c_int32)]
+
+
+SDF_NODE_LIMIT = 1 << 25
 STAGED_DS, STAGED_RAW = 0, 1
 
 ICP_STATES = {0: "NOT_CONVERGED", 1: "ITERATIONS", 2: "TRANSFORM", 3: "ABS_MSE", 4: "REL_MSE", 5: "NO_CORRESPONDENCES"}
@@ -252,6 +264,8 @@ EXPORTS = [
     "lio_s2m_registered_cloud",
     "lio_radius_filter", "lio_ogm_default_config", "lio_occupancy_grid", "lio_kf_store_occupancy_grid", "lio_ogm_debug_stage_ms",
     "lio_s2m_kernel_variant", "lio_s2m_launch_forms",
+    "lio_sdf_default_config", "lio_sdf_create", "lio_sdf_destroy", "lio_sdf_build", "lio_kf_store_sdf", "lio_sdf_nodes", "lio_sdf_query",
+    "lio_occupancy_sdf", "lio_sdf_debug_stage_ms", "lio_sdf_memory",
 ]
 
 
@@ -401,6 +415,19 @@ def load_library():
     L.lio_occupancy_grid.argtypes = [i32, vp, sz, sz, C.POINTER(OgmConfig), vp, sz, C.POINTER(OgmInfo)]
     L.lio_kf_store_occupancy_grid.argtypes = [vp, f32, C.POINTER(OgmConfig), vp, sz, C.POINTER(sz), C.POINTER(OgmInfo)]
     L.lio_ogm_debug_stage_ms.argtypes = [i32, C.POINTER(f32)]
+    L.lio_sdf_default_config.argtypes = [C.POINTER(SdfConfig)]
+    L.lio_sdf_default_config.restype = None
+    L.lio_sdf_create.argtypes = [i32, C.POINTER(vp)]
+    L.lio_sdf_destroy.argtypes = [vp]
+    L.lio_sdf_destroy.restype = None
+    L.lio_sdf_build.argtypes = [vp, vp, i32, i32, f64, C.POINTER(f64), C.POINTER(f64), C.POINTER(SdfConfig), C.POINTER(SdfInfo)]
+    L.lio_kf_store_sdf.argtypes = [vp, C.POINTER(LocalMapConfig), C.POINTER(f32), C.POINTER(HeightMapConfig), C.POINTER(SdfConfig), vp, sz, vp,
+                                   C.POINTER(LocalMapInfo), C.POINTER(HeightMapInfo), C.POINTER(SdfInfo)]
+    L.lio_sdf_nodes.argtypes = [vp, vp, sz]
+    L.lio_sdf_query.argtypes = [vp, vp, sz, vp, vp]
+    L.lio_occupancy_sdf.argtypes = [i32, vp, i32, i32, f32, i32, vp]
+    L.lio_sdf_debug_stage_ms.argtypes = [i32, C.POINTER(f32)]
+    L.lio_sdf_memory.argtypes = [vp, C.POINTER(sz), C.POINTER(sz)]
     _LIB = L
     return L
 
@@ -1169,6 +1196,84 @@ def occupancy_grid(xyz, cfg=None, want_grid=True, device_id=0):
                      "lio_occupancy_grid", want_grid)
 
 
+# grid_map_sdf
+def sdf_default_config(**overrides):
+    cfg = SdfConfig()
+    load_library().lio_sdf_default_config(C.byref(cfg))
+    for k, v in overrides.items():
+        if not hasattr(cfg, k):
+            raise AttributeError(k)
+        setattr(cfg, k, v)
+    return cfg
+
+
+class Sdf:
+    """grid_map::SignedDistanceField resident on the device: build it from an elevation grid (or from a keyframe store,
+    KeyframeStore.sdf_map), then query it."""
+
+    def __init__(self, device_id=0):
+        self.lib = load_library()
+        self.h = C.c_void_p()
+        self.info = SdfInfo()
+        _check(self.lib.lio_sdf_create(device_id, C.byref(self.h)), "lio_sdf_create")
+
+    def build(self, grid, resolution, length, position, cfg=None):
+        """-> SdfInfo.  grid: [rows, cols] float32; length and position: those of the HeightMapInfo the grid came with."""
+        cfg = cfg or sdf_default_config()
+        g = np.asfortranarray(np.asarray(grid, np.float32))
+        if g.ndim != 2:
+            raise ValueError("grid must be [rows, cols]")
+        ln, ps = (C.c_double * 2)(*length), (C.c_double * 2)(*position)
+        info = self.info = SdfInfo()
+        _check(self.lib.lio_sdf_build(self.h, g.ctypes.data, g.shape[0], g.shape[1], float(resolution), ln, ps, C.byref(cfg), C.byref(info)),
+               "lio_sdf_build")
+        return info
+
+    def nodes(self):
+        """-> [layers, cols, rows, 4] float32: {distance, dx, dy, dz} in the reference's data_ order."""
+        i = self.info
+        out = np.empty((i.layers, i.cols, i.rows, 4), np.float32)
+        _check(self.lib.lio_sdf_nodes(self.h, out.ctypes.data, out.size), "lio_sdf_nodes")
+        return out
+
+    def query(self, positions, want_derivative=True):
+        """valueAndDerivative -> (value [n] float64, derivative [n, 3] float64 or None)"""
+        p = np.ascontiguousarray(positions, np.float64).reshape(-1, 3)
+        val = np.empty(len(p), np.float64)
+        der = np.empty((len(p), 3), np.float64) if want_derivative else None
+        _check(self.lib.lio_sdf_query(self.h, p.ctypes.data, len(p), val.ctypes.data, der.ctypes.data if want_derivative else None), "lio_sdf_query")
+        return val, der
+
+    def memory(self):
+        """-> (bytes of the field, bytes of the build's workspace) the object holds on the device"""
+        field, work = C.c_size_t(), C.c_size_t()
+        _check(self.lib.lio_sdf_memory(self.h, C.byref(field), C.byref(work)), "lio_sdf_memory")
+        return field.value, work.value
+
+    def close(self):
+        if self.h:
+            self.lib.lio_sdf_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# signedDistanceFromOccupancy (SignedDistance2d.cpp:272-287) on the data of a nav_msgs/OccupancyGrid
+def occupancy_sdf(grid, resolution, occupied_min=100, device_id=0):
+    """-> [height, width] float32 in the grid's layout.  grid: [height, width] int8, row-major as occupancy_grid returns it."""
+    g = np.ascontiguousarray(grid, np.int8)
+    if g.ndim != 2:
+        raise ValueError("grid must be [height, width]")
+    out = np.empty(g.shape, np.float32)
+    _check(load_library().lio_occupancy_sdf(device_id, g.ctypes.data, g.shape[1], g.shape[0], float(resolution), int(occupied_min), out.ctypes.data),
+           "lio_occupancy_sdf")
+    return out
+
+
 # extractCloud, MO:1556-1588
 def assemble_map(clouds_xyzi, poses, leaf, s2m=None, device_id=0, want_output=True):
     recs = [_as_xyzi_records(c) for c in clouds_xyzi]
@@ -1321,6 +1426,28 @@ class KeyframeStore:
         n = info.rows * info.cols
         elev = grid[:n].reshape((info.rows, info.cols), order="F").copy(order="F") if want_grid else None
         return elev, _terrain_layers_out(layers, info, cfg.layers), info, hm_info, lm_info
+
+    def sdf_map(self, sdf, pose, lm_cfg=None, hm_cfg=None, cfg=None, want_grid=True):   # height_map, then grid_map_sdf on the device grid
+        """Builds `sdf` (an Sdf) -> (elevation grid [rows, cols] or None, SdfInfo, HeightMapInfo, LocalMapInfo)."""
+        lm_cfg = lm_cfg or local_map_default_config()
+        hm_cfg = hm_cfg or height_map_default_config()
+        cfg = cfg or sdf_default_config()
+        p = np.ascontiguousarray(pose, np.float32).reshape(6)
+        lm_info, hm_info = LocalMapInfo(), HeightMapInfo()
+        info = sdf.info = SdfInfo()
+        cells = _SCRATCH_CELLS.get("sdf_map", 1 << 16)
+        while True:
+            grid = _scratch("sdf_grid", (cells,))
+            rc = self.lib.lio_kf_store_sdf(self.h, C.byref(lm_cfg), _f32p(p), C.byref(hm_cfg), C.byref(cfg), grid.ctypes.data if want_grid else None,
+                                           grid.size, sdf.h, C.byref(lm_info), C.byref(hm_info), C.byref(info))
+            if rc == -1 and want_grid and hm_info.rows * hm_info.cols > cells:
+                cells = _SCRATCH_CELLS["sdf_map"] = hm_info.rows * hm_info.cols
+                continue
+            _check(rc, "lio_kf_store_sdf")
+            break
+        n = hm_info.rows * hm_info.cols
+        elev = grid[:n].reshape((hm_info.rows, hm_info.cols), order="F").copy(order="F") if want_grid else None
+        return elev, info, hm_info, lm_info
 
     def global_map(self, cfg=None, want_ids=True, want_output=True):   # publishGlobalMap, MO:992-1041
         """-> (cloud [m,4] or None, ids (the kept list, duplicates included) or None, GlobalMapInfo)."""
