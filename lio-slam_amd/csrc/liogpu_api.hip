@@ -254,6 +254,16 @@ static int lio_map_finish(lio_s2m_handle* h, size_t n, std::chrono::steady_clock
     // DESIGN.md section 6); LIO_X_SUB = 1 | 2 | 4 | 8 in the environment overrides it for A/B runs
     int xsub = h->cfg.x_sub > 0 ? h->cfg.x_sub : (h->cfg.max_batch >= 8 ? 4 : 1);
     { const char* e = getenv("LIO_X_SUB"); const int v = e ? atoi(e) : 0; if (v == 1 || v == 2 || v == 4 || v == 8) xsub = v; }
+    // Long maps.  lio_cell_coord rounds (v - origin) at the fp32 spacing of the grid's EXTENT, so along y and z -- where the rows
+    // around the query's are all the search sees -- a map point within the bound can be counted one cell too far once that
+    // spacing comes near the grid's slack: the width of the rows searched (k cells, one for a tight table) less the largest
+    // bound searched in them.  A grid is used only while the spacing at its far end is at most half of that slack; beyond,
+    // the main grid takes larger cells and a tight table is left out (about 4 km of extent for a 1 m gate; the tables at
+    // 4, 2 and 1 km).  Along x the row search takes the run [cell(qx - Rx), cell(qx + Rx)]: rounding is monotone, no margin to
+    // lose.  The LDS-staged search (cfg.use_lds, lio_knn_lds) walks cx - k .. cx + k instead: for it the main grid obeys the
+    // rule along x as well.  Half of the slack is a margin that held in every emulated case, not a proven bound: the four
+    // roundings of a cell difference can add up to about 2.8 spacings in the worst case.
+    auto spacing_fits = [](float far_end, float slack) { return nextafterf(far_end, INFINITY) - far_end <= 0.5f * slack; };
     LioGrid g;
     for (;;) {
         g.k = kdiv;
@@ -262,7 +272,9 @@ static int lio_map_finish(lio_s2m_handle* h, size_t n, std::chrono::steady_clock
         const double ex = ((double)mx[0] - g.ox) * g.inv_cell, ey = ((double)mx[1] - g.oy) * g.inv_cell,
                      ez = ((double)mx[2] - g.oz) * g.inv_cell;
         const double cells = (floor(ex) + 2.0) * (floor(ey) + 2.0) * (floor(ez) + 2.0);
-        if (cells * xsub <= 256.0 * 1024.0 * 1024.0) {
+        const float slack = (float)kdiv * cell - h->c.gate_reach;        // (grows by half a gate radius per step)
+        if (cells * xsub <= 256.0 * 1024.0 * 1024.0 && spacing_fits((mx[1] - g.oy) + cell, slack) && spacing_fits((mx[2] - g.oz) + cell, slack) &&
+            (!h->cfg.use_lds || spacing_fits((mx[0] - g.ox) + cell, slack))) {
             g.nx = (int)floor(ex) + 2; g.ny = (int)floor(ey) + 2; g.nz = (int)floor(ez) + 2;
             g.n_cells = g.nx * g.ny * g.nz;
             break;
@@ -325,6 +337,9 @@ static int lio_map_finish(lio_s2m_handle* h, size_t n, std::chrono::steady_clock
         // (bucket indices stay far inside 31 bits, and so do record offsets: every table adds 9 records per point + row padding)
         const double recs = (double)nn * ((2 * g.k + 1) * (2 * g.k + 1) + 9.0 * (l + 1)) + LIO_ROW_ALIGN * ((double)g.ny * g.nz + (double)rows_b + ny * nz);
         if ((double)g.n_cells * xsub + (double)len_b + ny * nz * g.nxf > 192.0 * 1024.0 * 1024.0 || recs > 2040.0 * 1024.0 * 1024.0) { n_tb = l; continue; }
+        // (long maps, see above: the bounded search walks this table for Rx <= reach, i.e. for true distances up to reach / 1.0001)
+        const float slack = cb - reach / 1.0001f;
+        if (!spacing_fits((mx[1] - oy) + cb, slack) || !spacing_fits((mx[2] - oz) + cb, slack)) { n_tb = l; continue; }
         g.tb_inv_cell[l] = inv; g.tb_oy[l] = oy; g.tb_oz[l] = oz; g.tb_ny[l] = (int)ny; g.tb_nz[l] = (int)nz;
         g.tb_row0[l] = (int)((size_t)g.n_cells * xsub + len_b);
         g.tb_reach[l] = reach;

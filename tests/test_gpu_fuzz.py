@@ -1,8 +1,9 @@
 """Randomised parity: the HIP association against the CPU oracle on clouds that are NOT
-lidar scenes -- uniform noise, tight clusters, exact lattices, collinear neighbours, large
+lidar scenes -- uniform noise, tight clusters, collinear neighbours, large
 coordinates, points outside the map -- where threshold decisions and pivoting paths differ from
 the street scenes.  One GN iteration, correspondences recorded: flags, 5-NN sets and plane
-coefficients must be bit-exact (NaN patterns included), the normal equations equal after rounding."""
+coefficients must be bit-exact (NaN patterns included), the normal equations equal after rounding.
+(Exact lattices, i.e. ties, and neighbours exactly at the gate or at a table's bound: tests/test_gpu_nn_margins.py.)"""
 import numpy as np
 import pytest
 
