@@ -278,6 +278,18 @@ int  lio_s2m_debug_persist_spin(lio_s2m_handle *h, int32_t spin_max, int32_t wit
  * and offset, plane test against plane_tol) on n neighbour sets, sets[n][5][3] in host memory.  out[n][8]: the raw bits of
  * X0[0..2], pa, pb, pc, pd, then planeValid (0 / 1). */
 int  lio_debug_plane_fit(int32_t device_id, const float *sets, size_t n, double plane_tol, uint32_t *out);
+/* Test hook: the association's fast fp32 operations against the device's plain operators, bit for bit.  op 0: square root,
+ * op 1: x / 5, op 2: sqrtf(sqrtf(r2)) of the scan point (x, 0, 0) as the association takes it, its guard riding on the plane fit's
+ * (a fixed neighbour set; raw ignored); raw != 0: the fast instruction sequence without its range guard (equal to the plain operator on the guarded
+ * range only), raw == 0: the guarded entry point (equal everywhere).  Operands: the bit patterns patterns[0..count), or with
+ * patterns NULL first, first + 1, ... (count <= 2^32; <= 2^27 with patterns or values).  *n_diff: results that differ from the
+ * plain operator (two NaNs are equal); first_diff[8]: up to eight such patterns, *n_first of them; values (may be NULL): the
+ * result bits. */
+int  lio_debug_fast_f32_ops(int32_t device_id, int32_t op, int32_t raw, const uint32_t *patterns, uint64_t first, uint64_t count,
+                            uint32_t *values, uint64_t *n_diff, uint32_t *first_diff, int32_t *n_first);
+/* Test hook (host only): the largest float not above t.  The surface association compares fp32 values against this in place
+ * of the double plane_tol / min_s: (double)v > t exactly when v > lio_debug_threshold_f32(t). */
+float lio_debug_threshold_f32(double t);
 /* Diagnostic (cfg.profile == 2): per-wave phase clock of the last GN launch,
  * n_blocks x 4 x 8 cycle counters; returns n_blocks.  Not for production. */
 int  lio_s2m_debug_stamps(lio_s2m_handle *h, long long *out, size_t cap_entries);

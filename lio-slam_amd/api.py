@@ -266,6 +266,7 @@ EXPORTS = [
     "lio_s2m_kernel_variant", "lio_s2m_launch_forms",
     "lio_sdf_default_config", "lio_sdf_create", "lio_sdf_destroy", "lio_sdf_build", "lio_kf_store_sdf", "lio_sdf_nodes", "lio_sdf_query",
     "lio_occupancy_sdf", "lio_sdf_debug_stage_ms", "lio_sdf_memory",
+    "lio_debug_fast_f32_ops", "lio_debug_threshold_f32",
 ]
 
 
@@ -854,6 +855,34 @@ def debug_plane_fit(sets, plane_tol=0.2, device_id=0):
     fn.argtypes = [C.c_int32, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p]
     _check(fn(device_id, a.ctypes.data, len(a), float(plane_tol), out.ctypes.data), "lio_debug_plane_fit")
     return out
+
+
+# test hook: the association's fast fp32 square root (op 0), x / 5 (op 1) or fourth root of the range of the scan point (x, 0, 0) (op 2) against the device's plain operator on the bit patterns
+# `patterns` (array) or first .. first + count; raw: the fast sequence without its guard.  Returns (number of differing results,
+# up to eight differing patterns, result bits or None) (include/liogpu.h)
+def debug_fast_f32_ops(op, raw=False, patterns=None, first=0, count=0, want_values=False, device_id=0):
+    fn = load_library().lio_debug_fast_f32_ops
+    fn.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
+                   C.POINTER(C.c_uint64), C.c_void_p, C.POINTER(C.c_int32)]
+    pat = None
+    if patterns is not None:
+        pat = np.ascontiguousarray(patterns, np.uint32)
+        count = len(pat)
+    vals = np.zeros(count, np.uint32) if want_values else None
+    n_diff, n_first = C.c_uint64(0), C.c_int32(0)
+    firsts = np.zeros(8, np.uint32)
+    _check(fn(device_id, int(op), 1 if raw else 0, pat.ctypes.data if pat is not None else None, int(first), int(count),
+              vals.ctypes.data if vals is not None else None, C.byref(n_diff), firsts.ctypes.data, C.byref(n_first)),
+           "lio_debug_fast_f32_ops")
+    return int(n_diff.value), firsts[:n_first.value].copy(), vals
+
+
+# test hook (host only): the largest float32 not above the double t, as the library converts plane_tol and min_s
+def debug_threshold_f32(t):
+    fn = load_library().lio_debug_threshold_f32
+    fn.argtypes = [C.c_double]
+    fn.restype = C.c_float
+    return np.float32(fn(float(t)))
 
 
 # extension (row A4): projectPointCloud + cloudExtraction of upstream LIO-SAM -> the cloud_info arrays FE consumes

@@ -63,13 +63,77 @@ LIO_DEV float lio_div_fast(float n, const LioDivisor& v)
 LIO_DEV float lio_min3_abs(float a, float b, float c) { return fminf(fminf(fabsf(a), fabsf(b)), fabsf(c)); }
 LIO_DEV float lio_max3_abs(float a, float b, float c) { return fmaxf(fmaxf(fabsf(a), fabsf(b)), fabsf(c)); }
 
+// x / 5 (the rank threshold of the plane fit), bit-identical to the plain `/`: lio_div_fast against the constant divisor where the
+// numerator is in its range, the plain `/` everywhere else (zero, denormals, huge values, NaN).
+LIO_DEV float lio_div5(float x)
+{
+    const LioDivisor five = lio_divisor(5.0f);
+    const float ax = fabsf(x);
+    if (LIO_SHARED_DIV && lio_div_mid(ax, ax)) return lio_div_fast(x, five);
+    return x / 5.0f;
+}
+
+// ------------------------------------------------------------------ square roots
+// sqrtf(x), bit-identical to the plain call.  What the compiler emits for an fp32 sqrtf on gfx950 (LLVM AMDGPU, correctly
+// rounded, fp32 denormals on; read off the disassembly of this repository's build) is
+//     small = x < 2^-96                 x' = small ? x * 2^32 : x
+//     s  = v_sqrt_f32(x')               sm = bits(s) - 1          sp = bits(s) + 1
+//     rm = fma(-sm, s, x')              rp = fma(-sp, s, x')
+//     s  = (rm <= 0) ? sm : s           s  = (rp > 0) ? sp : s
+//     s  = small ? s * 2^-16 : s        result = v_cmp_class(x', +0 | -0 | +inf) ? x' : s
+// -- 16 instructions, v_sqrt_f32 taking two issue slots.  The first line and the last only act on x < 2^-96 (denormal results
+// of the hardware root's intermediate steps), on zeros and on +inf; for x >= 2^-96 and finite they select what is already there.
+// The fast path is lines two to four on x itself: the same instructions on the same operands, hence the same (correctly rounded)
+// root.  +inf passes `x >= 2^-96` and needs no exclusion: v_sqrt_f32 gives +inf, both residuals are inf - inf = NaN, both
+// comparisons are false and +inf comes out, as from the class test; a NaN fails the guard (and would come out of either path as
+// v_sqrt_f32's quiet NaN, both comparisons false).  tests/test_gpu_fast_f32_ops.py runs both paths over all 2^32 patterns.
+// The explicit fma builtins are not subject to -ffp-contract.
+#ifndef LIO_FAST_SQRT
+#define LIO_FAST_SQRT 1       // 0: every root through the plain sqrtf (A/B and the tests)
+#endif
+#define LIO_SQRT_MIN 0x1p-96f
+
+// sqrtf(x); only for x >= LIO_SQRT_MIN
+LIO_DEV float lio_sqrt_fast(float x)
+{
+    const float s = __builtin_amdgcn_sqrtf(x);
+    const float sm = __int_as_float(__float_as_int(s) - 1), sp = __int_as_float(__float_as_int(s) + 1);
+    const float rm = __builtin_fmaf(-sm, s, x), rp = __builtin_fmaf(-sp, s, x);
+    float r = (rm <= 0.0f) ? sm : s;
+    r = (rp > 0.0f) ? sp : r;
+    return r;
+}
+
+LIO_DEV bool lio_sqrt_ok(float lo) { return LIO_FAST_SQRT && lo >= LIO_SQRT_MIN; }   // (false for NaN)
+
+// sqrtf(x) for any x: one comparison, then the fast path or the plain call
+LIO_DEV float lio_sqrt(float x)
+{
+    if (lio_sqrt_ok(x)) return lio_sqrt_fast(x);
+    return sqrtf(x);
+}
+
 // ---------------------------------------------------------------- plane fit
 // matA0.colPivHouseholderQr().solve(matB0) with matB0 = -1, MO:1633-1648
 // (Eigen 3.3 ColPivHouseholderQR: pivot on the largest updated column norm,
 // LAPACK-style norm downdating, makeHouseholderInPlace, column-oriented
 // back-substitution over nonzeroPivots()).  a[r][c]: 5 neighbours x (x,y,z).
-LIO_DEV void lio_plane_qr5x3(float a[5][3], float x[3])
+// FAST: every root is lio_sqrt_fast and `clean` is cleared where an operand is outside its range (LioRoots); the caller then
+// repeats the whole fit with FAST false, i.e. with the plain sqrtf.  No branch per root: the repeat is one cold copy of the fit.
+template <bool FAST> struct LioRoots {
+    bool clean = true;
+    LIO_DEV float operator()(float x)
+    {
+        if (!FAST) return sqrtf(x);
+        clean = clean && (x >= LIO_SQRT_MIN);                // (false for NaN)
+        return lio_sqrt_fast(x);
+    }
+};
+
+template <bool FAST>
+LIO_DEV bool lio_plane_qr5x3(float a[5][3], float x[3])
 {
+    LioRoots<FAST> root;
     float hc[3], direct[3], upd[3];
     int trans[3];
 #pragma unroll
@@ -77,14 +141,14 @@ LIO_DEV void lio_plane_qr5x3(float a[5][3], float x[3])
         float s = 0.0f;
 #pragma unroll
         for (int i = 0; i < 5; ++i) s += a[i][k] * a[i][k];
-        direct[k] = sqrtf(s);
+        direct[k] = root(s);
         upd[k] = direct[k];
     }
     float maxn = upd[0];
     if (upd[1] > maxn) maxn = upd[1];
     if (upd[2] > maxn) maxn = upd[2];
     const float th = maxn * FLT_EPSILON;
-    const float threshold_helper = (th * th) / 5.0f;
+    const float threshold_helper = lio_div5(th * th);
     const float downdate_thr = sqrtf(FLT_EPSILON);
     int nz = 3;
 
@@ -121,7 +185,7 @@ LIO_DEV void lio_plane_qr5x3(float a[5][3], float x[3])
 #pragma unroll
             for (int i = k + 1; i < 5; ++i) a[i][k] = 0.0f;
         } else {
-            beta = sqrtf(c0 * c0 + tail_sq);
+            beta = root(c0 * c0 + tail_sq);
             if (c0 >= 0.0f) beta = -beta;
             // the 4 / 3 / 2 quotients of this column share `den` (lio_div_fast); any operand outside its range: plain `/`
             const LioDivisor den = lio_divisor(c0 - beta);
@@ -159,15 +223,14 @@ LIO_DEV void lio_plane_qr5x3(float a[5][3], float x[3])
                 temp = temp < 0.0f ? 0.0f : temp;
                 const float ratio = upd[j] / direct[j];
                 const float temp2 = temp * (ratio * ratio);
-                if (temp2 <= downdate_thr) {
-                    float s = 0.0f;
+                // the two forms take one root between them: of the recomputed sum of squares, or of temp
+                const bool redo = temp2 <= downdate_thr;
+                float s = 0.0f;
 #pragma unroll
-                    for (int i = k + 1; i < 5; ++i) s += a[i][j] * a[i][j];
-                    direct[j] = sqrtf(s);
-                    upd[j] = direct[j];
-                } else {
-                    upd[j] *= sqrtf(temp);
-                }
+                for (int i = k + 1; i < 5; ++i) s += a[i][j] * a[i][j];
+                const float rt = root(redo ? s : temp);
+                direct[j] = redo ? rt : direct[j];
+                upd[j] = redo ? rt : upd[j] * rt;
             }
         }
     }
@@ -222,18 +285,45 @@ LIO_DEV void lio_plane_qr5x3(float a[5][3], float x[3])
 #pragma unroll
     for (int j = 0; j < 3; ++j)
         x[j] = (p0 == j) ? v0 : (p1 == j) ? v1 : (p2 == j) ? v2 : 0.0f;
+    return root.clean;
 }
 
 // Plane through five map points, MO:1648-1666: the solve above, unit normal and offset (MO:1650-1656), plane test
 // (MO:1658-1666).  m is left alone; X0 receives the raw solution.  Returns planeValid.
-LIO_DEV bool lio_plane_fit5(const float m[5][3], double plane_tol, float X0[3], float& pa, float& pb, float& pc, float& pd)
+// plane_tol_f: the reference's double tolerance as the largest float not above it (lio_threshold_f32 on the host): for a float v,
+// (double)v > tol holds exactly when v > plane_tol_f, so the five tests need no conversion and no fp64 comparison.
+// (px, py, pz): the scan point, of whose squared range r2 = px*px + py*py + pz*pz the caller needs the fourth root (MO:1671).
+// Its guard rides along as one more term of `clean` instead of a branch of its own in the caller: fast_ok = the caller may take
+// lio_sqrt_fast(lio_sqrt_fast(r2)), otherwise r4_plain = sqrtf(sqrtf(r2)) (set only then).
+// FAST: the fit with lio_sqrt_fast for every root and no branch per root; where an operand of any of them was below 2^-96 or
+// NaN (lio_plane_qr5x3), the whole fit is repeated with the plain sqrtf -- one cold copy, laid out off the hot path.  !FAST
+// (the looped form of the plain kernel, whose register allocation would otherwise add scratch accesses before the arrival
+// atomic; LIO_FAST_SQRT 0): the plain fit alone.
+template <bool FAST = true>
+LIO_DEV bool lio_plane_fit5(const float m[5][3], float plane_tol_f, float X0[3], float& pa, float& pb, float& pc, float& pd,
+                            float px, float py, float pz, bool& fast_ok, float& r4_plain)
 {
     float a[5][3];
+    float ps = 0.0f;
+    bool clean = false;
+    if (FAST && LIO_FAST_SQRT) {
 #pragma unroll
-    for (int j = 0; j < 5; ++j) { a[j][0] = m[j][0]; a[j][1] = m[j][1]; a[j][2] = m[j][2]; }
-    lio_plane_qr5x3(a, X0);                                   // MO:1648
+        for (int j = 0; j < 5; ++j) { a[j][0] = m[j][0]; a[j][1] = m[j][1]; a[j][2] = m[j][2]; }
+        clean = lio_plane_qr5x3<true>(a, X0);                 // MO:1648
+        const float sq = X0[0] * X0[0] + X0[1] * X0[1] + X0[2] * X0[2];
+        // (r2 >= 2^-96 puts its root above 2^-48; a NaN that fminf drops comes out of lio_sqrt_fast as out of sqrtf)
+        clean = clean && lio_sqrt_ok(fminf(sq, px * px + py * py + pz * pz));
+        ps = lio_sqrt_fast(sq);                               // MO:1655
+    }
+    if (__builtin_expect(!clean, 0)) {
+#pragma unroll
+        for (int j = 0; j < 5; ++j) { a[j][0] = m[j][0]; a[j][1] = m[j][1]; a[j][2] = m[j][2]; }
+        lio_plane_qr5x3<false>(a, X0);
+        ps = sqrtf(X0[0] * X0[0] + X0[1] * X0[1] + X0[2] * X0[2]);
+        r4_plain = sqrtf(sqrtf(px * px + py * py + pz * pz));
+    }
+    fast_ok = clean;
     pa = X0[0]; pb = X0[1]; pc = X0[2]; pd = 1;               // MO:1650-1653
-    const float ps = sqrtf(pa * pa + pb * pb + pc * pc);      // MO:1655
     const LioDivisor dv = lio_divisor(ps);                    // MO:1656: four quotients by one ps
     if (LIO_SHARED_DIV && dv.mid && lio_div_mid(lio_min3_abs(pa, pb, pc), lio_max3_abs(pa, pb, pc))) {
         pa = lio_div_fast(pa, dv); pb = lio_div_fast(pb, dv); pc = lio_div_fast(pc, dv); pd = lio_div_fast(pd, dv);
@@ -244,9 +334,15 @@ LIO_DEV bool lio_plane_fit5(const float m[5][3], double plane_tol, float X0[3], 
 #pragma unroll
     for (int j = 0; j < 5; ++j) {
         const float v = fabsf(pa * m[j][0] + pb * m[j][1] + pc * m[j][2] + pd);
-        if ((double)v > plane_tol) planeValid = false;
+        if (v > plane_tol_f) planeValid = false;
     }
     return planeValid;
+}
+
+// sqrtf(sqrtf(r2)) of the scan point handed to lio_plane_fit5, from what it returned.
+LIO_DEV float lio_fourth_root(bool fast_ok, float r2, float r4_plain)
+{
+    return fast_ok ? lio_sqrt_fast(lio_sqrt_fast(r2)) : r4_plain;
 }
 
 // --------------------------------------------------------------- Jacobian

@@ -753,7 +753,7 @@ void k_s2m_iterate(LioIterParams P)
 
 // Test hook (lio_debug_plane_fit): the device plane fit on caller-supplied neighbour sets, one set per thread --
 // lio_plane_fit5, the function lio_assoc_point calls.  out[8 i ..] = the bits of X0[0..2], pa, pb, pc, pd, then planeValid.
-__global__ __launch_bounds__(256) void k_debug_plane_fit(const float* __restrict__ sets, long long n, double plane_tol,
+__global__ __launch_bounds__(256) void k_debug_plane_fit(const float* __restrict__ sets, long long n, float plane_tol_f,
                                                          unsigned* __restrict__ out)
 {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -763,8 +763,9 @@ __global__ __launch_bounds__(256) void k_debug_plane_fit(const float* __restrict
     for (int j = 0; j < 5; ++j)
 #pragma unroll
         for (int c = 0; c < 3; ++c) m[j][c] = sets[i * 15 + j * 3 + c];
-    float X0[3], pa, pb, pc, pd;
-    const bool valid = lio_plane_fit5(m, plane_tol, X0, pa, pb, pc, pd);
+    float X0[3], pa, pb, pc, pd, r4;
+    bool fast_ok;
+    const bool valid = lio_plane_fit5(m, plane_tol_f, X0, pa, pb, pc, pd, 1.0f, 0.0f, 0.0f, fast_ok, r4);
     uint4* o = reinterpret_cast<uint4*>(out + i * 8);
     o[0] = make_uint4(__float_as_uint(X0[0]), __float_as_uint(X0[1]), __float_as_uint(X0[2]), __float_as_uint(pa));
     o[1] = make_uint4(__float_as_uint(pb), __float_as_uint(pc), __float_as_uint(pd), valid ? 1u : 0u);
@@ -773,7 +774,59 @@ __global__ __launch_bounds__(256) void k_debug_plane_fit(const float* __restrict
 void lio_launch_debug_plane_fit(const float* sets, long long n, double plane_tol, unsigned* out, hipStream_t s)
 {
     if (n <= 0) return;
-    hipLaunchKernelGGL(k_debug_plane_fit, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, sets, n, plane_tol, out);
+    hipLaunchKernelGGL(k_debug_plane_fit, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, sets, n, lio_threshold_f32(plane_tol), out);   // (as lio_fill_consts)
+}
+
+// Test hook (lio_debug_fast_f32_ops): the library's fast fp32 operations against the plain operators of the device, on the bit
+// patterns pat[i] (pat non-null) or first + i.  op 0: the square root, op 1: x / 5, op 2: the fourth root of the squared range of
+// the scan point (x, 0, 0) as the association takes it -- lio_plane_fit5 on a fixed, well-conditioned neighbour set, whose flag
+// also covers that root's operand, then lio_fourth_root -- against sqrtf(sqrtf(r2)) (raw is ignored).  raw: the fast sequence itself
+// (lio_sqrt_fast / lio_div_fast, meaningful on their guarded ranges only), otherwise the entry point with its guard (lio_sqrt /
+// lio_div5).  Counts the words that differ from sqrtf / `/` (two NaNs count as equal), keeps up to 8 differing patterns in
+// diff[1..8] (diff[0]: their number) and, when val is non-null, the library's result for every pattern.
+__global__ __launch_bounds__(256) void k_debug_fast_f32_ops(int op, int raw, const unsigned* __restrict__ pat, unsigned long long first,
+                                                            unsigned long long count, unsigned* __restrict__ val,
+                                                            unsigned long long* __restrict__ n_diff, unsigned* __restrict__ diff)
+{
+    unsigned long long mine = 0;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < count; i += (unsigned long long)gridDim.x * 256) {
+        const unsigned bits = pat ? pat[i] : (unsigned)(first + i);
+        const float x = __uint_as_float(bits);
+        float fast, plain;
+        if (op == 0) {
+            fast = raw ? lio_sqrt_fast(x) : lio_sqrt(x);
+            plain = sqrtf(x);
+        } else if (op == 1) {
+            fast = raw ? lio_div_fast(x, lio_divisor(5.0f)) : lio_div5(x);
+            plain = x / 5.0f;
+        } else {
+            const float m[5][3] = { { 10.25f, -3.5f, 1.0f }, { 10.75f, -3.25f, 1.03125f }, { 10.5f, -4.0f, 0.96875f },
+                                    { 11.0f, -3.75f, 1.015625f }, { 10.0f, -3.0f, 0.984375f } };
+            float X0[3], pa, pb, pc, pd, r4_plain = 0.0f;
+            bool fast_ok;
+            lio_plane_fit5(m, 0.2f, X0, pa, pb, pc, pd, x, 0.0f, 0.0f, fast_ok, r4_plain);
+            const float r2 = x * x + 0.0f * 0.0f + 0.0f * 0.0f;          // lio_assoc_point's expression
+            fast = lio_fourth_root(fast_ok, r2, r4_plain);
+            plain = sqrtf(sqrtf(r2));
+        }
+        if (val) val[i] = __float_as_uint(fast);
+        const bool same = __float_as_uint(fast) == __float_as_uint(plain) || (fast != fast && plain != plain);
+        if (!same) {
+            ++mine;
+            const unsigned slot = atomicAdd(&diff[0], 1u);
+            if (slot < 8) diff[1 + slot] = bits;
+        }
+    }
+    if (mine) atomicAdd(n_diff, mine);
+}
+
+void lio_launch_debug_fast_f32_ops(int op, int raw, const unsigned* pat, unsigned long long first, unsigned long long count,
+                                   unsigned* val, unsigned long long* n_diff, unsigned* diff, hipStream_t s)
+{
+    if (!count) return;
+    const unsigned long long blocks = (count + 255) / 256;
+    hipLaunchKernelGGL(k_debug_fast_f32_ops, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, s,
+                       op, raw, pat, first, count, val, n_diff, diff);
 }
 
 // Compact per-scan summary for callers that only want the poses: [pose x6 | iter | status | converged | is_degenerate]

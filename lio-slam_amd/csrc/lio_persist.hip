@@ -161,8 +161,9 @@ __global__ __launch_bounds__(LIO_BLOCK, 2) void k_s2m_persist(LioIterParams P, u
                 const float ox = Tp[0] * px + Tp[1] * py + Tp[2]  * pz + Tp[3];
                 const float oy = Tp[4] * px + Tp[5] * py + Tp[6]  * pz + Tp[7];
                 const float oz = Tp[8] * px + Tp[9] * py + Tp[10] * pz + Tp[11];
-                const float mv = sqrtf(lio_sqdist(qx, qy, qz, ox, oy, oz));
-                const float R = (sqrtf(d5) + mv) * 1.0001f + 1e-6f;
+                float rd5, mv;
+                lio_bound_roots<true>(d5, lio_sqdist(qx, qy, qz, ox, oy, oz), rd5, mv);
+                const float R = (rd5 + mv) * 1.0001f + 1e-6f;
                 const float r2 = R * R * 1.0001f;
                 if (r2 < bound2) { bound2 = r2; Rx = R; bounded = true; }
             }

@@ -308,8 +308,9 @@ __device__ __forceinline__ void lio_s2m_block(const LioIterParams& P, const int 
                 const float ox = Tp[0] * px[pp] + Tp[1] * py[pp] + Tp[2]  * pz[pp] + Tp[3];
                 const float oy = Tp[4] * px[pp] + Tp[5] * py[pp] + Tp[6]  * pz[pp] + Tp[7];
                 const float oz = Tp[8] * px[pp] + Tp[9] * py[pp] + Tp[10] * pz[pp] + Tp[11];
-                const float mv = sqrtf(lio_sqdist(qx[pp], qy[pp], qz[pp], ox, oy, oz));
-                const float R = (sqrtf(d5) + mv) * 1.0001f + 1e-6f;
+                float rd5, mv;
+                lio_bound_roots<!LOOPED>(d5, lio_sqdist(qx[pp], qy[pp], qz[pp], ox, oy, oz), rd5, mv);
+                const float R = (rd5 + mv) * 1.0001f + 1e-6f;
                 const float r2 = R * R * 1.0001f;
                 if (r2 < bound2) { bound2 = r2; Rx = R; bounded = true; }
             }
@@ -336,7 +337,7 @@ __device__ __forceinline__ void lio_s2m_block(const LioIterParams& P, const int 
         bool accept = false;
         // plane through the five neighbours, plane test, weight, coefficients MO:1642-1683 (the CORNER extension: point-to-line);
         // the same function the one-launch loop calls (lio_s2m_device.h): one copy of the arithmetic
-        if (ok) accept = lio_assoc_point<CORNER>(P, nn, qx[pp], qy[pp], qz[pp], px[pp], py[pp], pz[pp], cxx, cyy, czz, cww);
+        if (ok) accept = lio_assoc_point<CORNER, !LOOPED>(P, nn, qx[pp], qy[pp], qz[pp], px[pp], py[pp], pz[pp], cxx, cyy, czz, cww);
         if (record && inr[pp]) {
             // the record is kept in the CALLER's point order
             const int li = bd.first + pp * LIO_BLOCK + (int)tid;

@@ -82,6 +82,14 @@ LIO_DEV float lio_sqdist(float ax, float ay, float az, float bx, float by, float
     return r;
 }
 
+// The two roots of the search bound of the previous iteration (see lio_s2m_block): sqrtf(d5) and sqrtf(m2) under one guard.
+template <bool FAST>
+LIO_DEV void lio_bound_roots(float d5, float m2, float& rd5, float& mv)
+{
+    if (FAST && lio_sqrt_ok(fminf(d5, m2))) { rd5 = lio_sqrt_fast(d5); mv = lio_sqrt_fast(m2); }
+    else { rd5 = sqrtf(d5); mv = sqrtf(m2); }
+}
+
 // The serial Gauss-Newton step of one scan: LMOptimization MO:1702-1837 from
 // the reduced sums onward, plus the loop control of scan2MapOptimization
 // MO:1848-1859.  `ws` is LDS working storage.
@@ -379,7 +387,7 @@ LIO_DEV void lio_knn_global(const LioIterParams& P, const LioGrid& g, float qx, 
 // Association of one scan point from its five nearest map points (indices into the caller's map order):
 // surfOptimization MO:1642-1683 -- plane through the neighbours, plane test, weight, coefficients -- or, for
 // the CORNER extension, the point-to-line form of upstream LIO-SAM.  Returns "accepted" (MO:1679).
-template <bool CORNER>
+template <bool CORNER, bool FAST = true>
 LIO_DEV bool lio_assoc_point(const LioIterParams& P, const int nn[5], float qx, float qy, float qz,
                              float px, float py, float pz, float& cxx, float& cyy, float& czz, float& cww)
 {
@@ -394,15 +402,17 @@ LIO_DEV bool lio_assoc_point(const LioIterParams& P, const int nn[5], float qx, 
     if (CORNER) {
         accept = lio_corner_assoc(m, qx, qy, qz, P.c.weight, P.c.min_s, cxx, cyy, czz, cww);
     } else {
-        float X0[3], pa, pb, pc, pd;
-        const bool planeValid = lio_plane_fit5(m, P.c.plane_tol, X0, pa, pb, pc, pd);   // MO:1648-1666
+        float X0[3], pa, pb, pc, pd, r4_plain = 0.0f;
+        bool fast_ok;
+        const bool planeValid = lio_plane_fit5<FAST>(m, P.c.plane_tol_f, X0, pa, pb, pc, pd, px, py, pz, fast_ok, r4_plain);   // MO:1648-1666
         if (planeValid) {
-            const float pd2 = pa * qx + pb * qy + pc * qz + pd;   // MO:1669
             const float r2 = px * px + py * py + pz * pz;
+            const float r4 = lio_fourth_root(fast_ok, r2, r4_plain);               // sqrtf(sqrtf(r2))
+            const float pd2 = pa * qx + pb * qy + pc * qz + pd;   // MO:1669
             // MO:1671-1672 (product, quotient and difference in double)
-            const float s = (float)(1 - P.c.weight * (double)fabsf(pd2) / (double)sqrtf(sqrtf(r2)));
+            const float s = (float)(1 - P.c.weight * (double)fabsf(pd2) / (double)r4);
             cxx = s * pa; cyy = s * pb; czz = s * pc; cww = s * pd2;   // MO:1674-1677
-            accept = (double)s > P.c.min_s;                       // MO:1679
+            accept = s > P.c.min_s_f;                             // MO:1679 (min_s_f: see lio_plane_fit5)
         }
     }
     return accept;

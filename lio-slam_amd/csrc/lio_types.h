@@ -3,6 +3,8 @@
 // correspondence), MO = src/liorf/src/mapOptmization.cpp.
 #pragma once
 #include <stdint.h>
+#include <math.h>
+#include <float.h>
 
 #define LIO_SUMS 32          // per-scan sums: 21 upper JtJ + 6 Jtr + N_c + pad to 32 doubles
 #define LIO_SUM_NC 27
@@ -59,8 +61,22 @@ struct LioConsts {
     float  max_sq_dist, eig_thresh;
     float  gate_reach;       // sqrtf(max_sq_dist) * 1.0001f + 1e-6f: the search reach of an unbounded query, evaluated once on the
                              // host (IEEE sqrt, product and sum in fp32, no contraction: the bits the kernels used to compute per lane)
+    float  plane_tol_f, min_s_f;   // lio_threshold_f32 of plane_tol and of min_s: the surface association compares in fp32
     int32_t min_corr, max_iters, jac_exact, force_all, record_iter, min_scan_pts;
 };
+
+// The largest float not above the double t (host).  For every float v, (double)v > t holds exactly when v > lio_threshold_f32(t):
+// floats above t are the floats above that one, and a NaN on either side makes both comparisons false.  This is how the
+// reference's double literals (MO:1662, MO:1679) are compared against fp32 values without widening them on the device.
+static inline float lio_threshold_f32(double t)
+{
+    if (t != t) return NAN;
+    if (t > (double)FLT_MAX) return t == (double)INFINITY ? INFINITY : FLT_MAX;
+    if (t < -(double)FLT_MAX) return -INFINITY;
+    float f = (float)t;                                  // round to nearest ...
+    if ((double)f > t) f = nextafterf(f, -INFINITY);     // ... and one step down if that went above t
+    return f;
+}
 
 // Per-scan Gauss-Newton state (transformTobeMapped MO:171, isDegenerate/matP
 // MO:176-177, plus the transform of updatePointAssociateToMap MO:1613-1616 and

@@ -88,6 +88,7 @@ static void lio_fill_consts(lio_s2m_handle* h)
 {
     const lio_s2m_config& g = h->cfg;
     h->c.plane_tol = g.plane_tol; h->c.weight = g.weight; h->c.min_s = g.min_s;
+    h->c.plane_tol_f = lio_threshold_f32(g.plane_tol); h->c.min_s_f = lio_threshold_f32(g.min_s);
     h->c.conv_deg = g.conv_deg; h->c.conv_cm = g.conv_cm;
     h->c.max_sq_dist = g.max_sq_dist; h->c.eig_thresh = g.eig_thresh;
     {   // each step rounded to fp32 on its own, as the device did
@@ -641,6 +642,50 @@ try {
     HIPCHK(hipMemcpy(out, d_out, n * 8 * sizeof(unsigned), hipMemcpyDeviceToHost));
     return LIO_OK;
 } LIO_CATCH
+
+// Test hook: the fast fp32 operations of the association (lio_device_math.h) against the device's plain operators.  op 0: square
+// root, op 1: x / 5, op 2: the fourth root of the squared range of the scan point (x, 0, 0) through the plane fit's flag; raw != 0
+// (ops 0, 1): the fast sequence without its guard.  The operands are the bit patterns patterns[0..count) or, with
+// patterns null, first, first + 1, ...  *n_diff receives the number of results whose bits differ from the plain operator's (two
+// NaNs are equal), first_diff[0..8) up to eight such patterns (*n_first of them), values (may be null) the library's result bits.
+extern "C" int lio_debug_fast_f32_ops(int32_t device_id, int32_t op, int32_t raw, const uint32_t* patterns, uint64_t first, uint64_t count,
+                                      uint32_t* values, uint64_t* n_diff, uint32_t* first_diff, int32_t* n_first)
+try {
+    if (!n_diff || !first_diff || !n_first) return lio_fail(LIO_ERR_ARG, "null pointer");
+    if (op < 0 || op > 2) return lio_fail(LIO_ERR_ARG, "op must be 0 (sqrt), 1 (x / 5) or 2 (fourth root of the range)");
+    if (count > ((uint64_t)1 << 32)) return lio_fail(LIO_ERR_CAPACITY, "at most 2^32 patterns per call");
+    if ((patterns || values) && count > ((uint64_t)1 << 27)) return lio_fail(LIO_ERR_CAPACITY, "at most 2^27 listed patterns or returned values per call");
+    *n_diff = 0; *n_first = 0;
+    if (!count) return LIO_OK;
+    HIPCHK(hipSetDevice(device_id));
+    LioDevBuf<unsigned> d_pat, d_val, d_diff;
+    LioDevBuf<unsigned long long> d_n;
+    if (patterns) {
+        HIPCHK(d_pat.grow(count, 1.0, 0));
+        HIPCHK(hipMemcpy(d_pat, patterns, count * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    if (values) HIPCHK(d_val.grow(count, 1.0, 0));
+    HIPCHK(d_diff.grow(9, 1.0, 0));
+    HIPCHK(d_n.grow(1, 1.0, 0));
+    HIPCHK(hipMemset(d_diff, 0, 9 * sizeof(unsigned)));
+    HIPCHK(hipMemset(d_n, 0, sizeof(unsigned long long)));
+    lio_launch_debug_fast_f32_ops(op, raw ? 1 : 0, patterns ? (const unsigned*)d_pat : nullptr, first, count,
+                                  values ? (unsigned*)d_val : nullptr, d_n, d_diff, nullptr);
+    HIPCHK(hipGetLastError());
+    unsigned h_diff[9];
+    unsigned long long h_n = 0;
+    HIPCHK(hipMemcpy(h_diff, d_diff, sizeof(h_diff), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&h_n, d_n, sizeof(h_n), hipMemcpyDeviceToHost));
+    if (values) HIPCHK(hipMemcpy(values, d_val, count * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    *n_diff = h_n;
+    *n_first = (int32_t)(h_diff[0] < 8 ? h_diff[0] : 8);
+    for (int i = 0; i < 8; ++i) first_diff[i] = h_diff[1 + i];
+    return LIO_OK;
+} LIO_CATCH
+
+// Test hook: the fp32 threshold the surface association compares against in place of the double t (lio_threshold_f32: the
+// largest float not above t).  Host only.
+extern "C" float lio_debug_threshold_f32(double t) { return lio_threshold_f32(t); }
 
 // The SoA copy of the resident batch, for the paths that read it, if the upload skipped it.
 static int lio_ensure_soa(lio_s2m_handle* h)
