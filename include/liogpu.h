@@ -290,6 +290,26 @@ int  lio_debug_fast_f32_ops(int32_t device_id, int32_t op, int32_t raw, const ui
 /* Test hook (host only): the largest float not above t.  The surface association compares fp32 values against this in place
  * of the double plane_tol / min_s: (double)v > t exactly when v > lio_debug_threshold_f32(t). */
 float lio_debug_threshold_f32(double t);
+/* Test hook (host only): the search grid lio_s2m_set_map would lay out for cfg over n map points in the box [mn, mx] --
+ * the same override parser (LIO_X_SUB, LIO_TIGHT, LIO_TRY) and the same two planning steps, no device.  occupied = the
+ * grid cells that hold a point (negative: not counted); caller_box != 0: the box came from the caller, as for a map
+ * assembled on the device (that path counts no cells).  Arrays of 3: one entry per tight row table, reach descending,
+ * tb_reach < 0 = no such table. */
+typedef struct lio_grid_plan_info {
+    float   origin[3], inv_cell;
+    int32_t nx, ny, nz, n_cells, k, xs, nxf;
+    float   inv_cell_x;
+    int32_t tb_row0[3], tb_ny[3], tb_nz[3];
+    float   tb_oy[3], tb_oz[3], tb_inv_cell[3], tb_reach[3];
+    int32_t tb_try;
+    float   tb_try_b2[3];
+    float   cell;              /* edge of the main grid's cells after grow_steps growths by 1.5 */
+    int32_t n_tb, grow_steps, want_occupancy;
+    float   pts_per_cell;
+    int64_t buckets;           /* row buckets of the main grid and of every table */
+} lio_grid_plan_info;
+int  lio_debug_grid_plan(const lio_s2m_config *cfg, const float mn[3], const float mx[3], size_t n, int32_t occupied,
+                         int32_t caller_box, lio_grid_plan_info *out);
 /* Diagnostic (cfg.profile == 2): per-wave phase clock of the last GN launch,
  * n_blocks x 4 x 8 cycle counters; returns n_blocks.  Not for production. */
 int  lio_s2m_debug_stamps(lio_s2m_handle *h, long long *out, size_t cap_entries);

@@ -37,6 +37,19 @@ class S2MConfig(C.Structure):
     ]
 
 
+class GridPlanInfo(C.Structure):
+    _fields_ = [
+        ("origin", C.c_float * 3), ("inv_cell", C.c_float),
+        ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("n_cells", C.c_int32), ("k", C.c_int32), ("xs", C.c_int32), ("nxf", C.c_int32),
+        ("inv_cell_x", C.c_float),
+        ("tb_row0", C.c_int32 * 3), ("tb_ny", C.c_int32 * 3), ("tb_nz", C.c_int32 * 3),
+        ("tb_oy", C.c_float * 3), ("tb_oz", C.c_float * 3), ("tb_inv_cell", C.c_float * 3), ("tb_reach", C.c_float * 3),
+        ("tb_try", C.c_int32), ("tb_try_b2", C.c_float * 3),
+        ("cell", C.c_float), ("n_tb", C.c_int32), ("grow_steps", C.c_int32), ("want_occupancy", C.c_int32),
+        ("pts_per_cell", C.c_float), ("buckets", C.c_int64),
+    ]
+
+
 class S2MResult(C.Structure):
     _fields_ = [
         ("status", C.c_int32), ("iters", C.c_int32), ("converged", C.c_int32),
@@ -266,7 +279,7 @@ EXPORTS = [
     "lio_s2m_kernel_variant", "lio_s2m_launch_forms",
     "lio_sdf_default_config", "lio_sdf_create", "lio_sdf_destroy", "lio_sdf_build", "lio_kf_store_sdf", "lio_sdf_nodes", "lio_sdf_query",
     "lio_occupancy_sdf", "lio_sdf_debug_stage_ms", "lio_sdf_memory",
-    "lio_debug_fast_f32_ops", "lio_debug_threshold_f32",
+    "lio_debug_fast_f32_ops", "lio_debug_threshold_f32", "lio_debug_grid_plan",
 ]
 
 
@@ -883,6 +896,25 @@ def debug_threshold_f32(t):
     fn.argtypes = [C.c_double]
     fn.restype = C.c_float
     return np.float32(fn(float(t)))
+
+
+# test hook (host only): the search grid set_map would lay out over n map points in the box [mn, mx] under ScanToMap settings
+# `cfg_overrides` (and LIO_X_SUB / LIO_TIGHT / LIO_TRY in the environment); occupied = grid cells holding a point (negative:
+# not counted), caller_box: the box came from the caller, as for a map assembled on the device (include/liogpu.h)
+def debug_grid_plan(mn, mx, n, occupied=-1, caller_box=False, **cfg_overrides):
+    L = load_library()
+    fn = L.lio_debug_grid_plan
+    fn.argtypes = [C.POINTER(S2MConfig), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t, C.c_int32, C.c_int32, C.POINTER(GridPlanInfo)]
+    cfg = S2MConfig()
+    L.lio_s2m_default_config(C.byref(cfg))
+    for k, v in cfg_overrides.items():
+        if not hasattr(cfg, k):
+            raise AttributeError(k)
+        setattr(cfg, k, v)
+    lo, hi = np.ascontiguousarray(mn, np.float32).reshape(3), np.ascontiguousarray(mx, np.float32).reshape(3)
+    out = GridPlanInfo()
+    _check(fn(C.byref(cfg), _f32p(lo), _f32p(hi), int(n), int(occupied), 1 if caller_box else 0, C.byref(out)), "lio_debug_grid_plan")
+    return out
 
 
 # extension (row A4): projectPointCloud + cloudExtraction of upstream LIO-SAM -> the cloud_info arrays FE consumes

@@ -92,7 +92,7 @@ __global__ void k_map_cell_count(LioGrid g, const float* __restrict__ x, const f
 }
 
 // Occupied cells of the grid (flags[0..n_cells) zeroed by the caller, the count lands in flags[n_cells]): points per occupied
-// cell is the density estimate that decides how many tight row tables a map is worth (lio_map_finish).
+// cell is the density estimate that decides how many tight row tables a map is worth (lio_plan_tables, lio_gridplan.h).
 __global__ void k_map_occupancy(LioGrid g, const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z, int n,
                                 int* __restrict__ flags)
 {
@@ -318,7 +318,7 @@ __global__ __launch_bounds__(LIO_SORT_THREADS) void k_scan_sort_radix(const unsi
         }
         float tile = tile0, inv_tile;
         int ntx, nty, ntz;
-        for (;;) {                                          // (the host loop of lio_s2m_batch_upload, verbatim)
+        for (;;) {                                          // (the host loop of lio_plan_scan_tiles, verbatim)
             inv_tile = 1.0f / tile;
             const double ex = floor(((double)hi[0] - lo[0]) * inv_tile) + 1.0, ey = floor(((double)hi[1] - lo[1]) * inv_tile) + 1.0,
                          ez = floor(((double)hi[2] - lo[2]) * inv_tile) + 1.0;

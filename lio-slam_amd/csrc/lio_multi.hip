@@ -33,6 +33,7 @@
 #include <memory>
 #include <vector>
 
+#include "lio_gridplan.h"
 #include "lio_handle.h"
 #include "lio_multi.h"
 
@@ -163,7 +164,7 @@ int lio_multi_set_map(lio_s2m_handle* h, const void* pts, size_t n, size_t strid
     LioMulti* m = h->multi;
     const int world = (int)m->dev.size();
     const unsigned char* src = (const unsigned char*)pts;
-    const float cell = h->cfg.cell_size > 0.0f ? h->cfg.cell_size : sqrtf(h->cfg.max_sq_dist) * 1.001f;
+    const float cell = lio_gate_cell(h->cfg);
     const float inv_cell = 1.0f / cell;
     float mn[3] = { INFINITY, INFINITY, INFINITY }, mx[3] = { -INFINITY, -INFINITY, -INFINITY };
     for (size_t i = 0; i < n; ++i) {

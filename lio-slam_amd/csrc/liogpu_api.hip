@@ -12,6 +12,7 @@
 #include <mutex>
 #include <vector>
 
+#include "lio_gridplan.h"
 #include "lio_handle.h"
 #include "lio_multi.h"
 #include "lio_wg.h"
@@ -91,12 +92,7 @@ static void lio_fill_consts(lio_s2m_handle* h)
     h->c.plane_tol_f = lio_threshold_f32(g.plane_tol); h->c.min_s_f = lio_threshold_f32(g.min_s);
     h->c.conv_deg = g.conv_deg; h->c.conv_cm = g.conv_cm;
     h->c.max_sq_dist = g.max_sq_dist; h->c.eig_thresh = g.eig_thresh;
-    {   // each step rounded to fp32 on its own, as the device did
-        volatile float r = sqrtf(g.max_sq_dist);
-        r = r * 1.0001f;
-        r = r + 1e-6f;
-        h->c.gate_reach = r;
-    }
+    h->c.gate_reach = lio_gate_reach(g.max_sq_dist);
     h->c.min_corr = g.min_corr; h->c.max_iters = g.max_iters;
     h->c.jac_exact = g.jacobian_mode ? 1 : 0; h->c.force_all = g.force_all_iters ? 1 : 0;
     h->c.record_iter = g.record_corr_iter; h->c.min_scan_pts = g.min_scan_pts;
@@ -144,7 +140,7 @@ try {
         return rc;
     }
     HIPCHK(hipSetDevice(cfg->device_id));
-    if (cfg->cell_size > 0.0f && cfg->cell_size < sqrtf(cfg->max_sq_dist) * 1.001f)   // (before division by cell_div)
+    if (cfg->cell_size > 0.0f && cfg->cell_size < lio_gate_cell_min(*cfg))   // (before division by cell_div)
         return lio_fail(LIO_ERR_ARG, "cell_size must be >= sqrt(max_sq_dist)*1.001 for an exact 27-cell search");
     std::unique_ptr<lio_s2m_handle> h(new lio_s2m_handle());   // (releases whatever had been created if a step fails)
     h->cfg = *cfg;
@@ -216,6 +212,18 @@ static int lio_map_reserve(lio_s2m_handle* h, size_t n)
     return LIO_OK;
 }
 
+// common head of the set-map entry points: n is refused if too large, the handle's device made current, the buffers of the
+// points reserved; *t0 = the start of the upload time the profile reports
+static int lio_map_begin(lio_s2m_handle* h, size_t n, std::chrono::steady_clock::time_point* t0)
+{
+    if (n >= (1ull << 25)) return lio_fail(LIO_ERR_CAPACITY, "map too large ((2k+1)^2 x n records must fit a 31-bit offset)");
+    HIPCHK(hipSetDevice(h->cfg.device_id));
+    (void)hipGetLastError();   // drop stale codes left by other HIP users of this thread (e.g. hipErrorNotReady)
+    *t0 = std::chrono::steady_clock::now();
+    h->has_map = false;
+    return lio_map_reserve(h, n);
+}
+
 // common tail: d_mx/d_my/d_mz/d_map4 hold the n map points -> bounding box, grid, neighbourhood rows
 // `box` (optional): min[3], max[3] of a box known to contain every map point -- the grid is laid over it without a bounding-box
 // pass and its read-back (any enclosing box gives an exact search; the grid is only a few cells larger) -- and the call
@@ -223,7 +231,6 @@ static int lio_map_reserve(lio_s2m_handle* h, size_t n)
 // sharers wait for ev_mapl[1], the build time is resolved when the profile is read.
 static int lio_map_finish(lio_s2m_handle* h, size_t n, std::chrono::steady_clock::time_point t0, const float* box = nullptr)
 {
-    const size_t nn = n ? n : 1;
     float mn[3], mx[3];
     // (a box that is not finite -- a keyframe cloud of nothing but non-finite points -- is ignored: the box is then computed here)
     for (int a = 0; a < 3 && box; ++a)
@@ -247,121 +254,26 @@ static int lio_map_finish(lio_s2m_handle* h, size_t n, std::chrono::steady_clock
 
     auto t1 = std::chrono::steady_clock::now();
 
-    // cell edge = gate radius (+0.1 %) / k; the candidate scan visits (2k+1)^3 cells
-    int kdiv = h->cfg.cell_div;
-    if (kdiv != 1 && kdiv != 2 && kdiv != 3) kdiv = 2;
-    float cell = (h->cfg.cell_size > 0.0f ? h->cfg.cell_size : sqrtf(h->cfg.max_sq_dist) * 1.001f) / (float)kdiv;
-    // x subdivision of the row buckets (LioGrid::xs, cfg.x_sub): auto = 4 for a batch handle, 1 for a node's handle (measured,
-    // DESIGN.md section 6); LIO_X_SUB = 1 | 2 | 4 | 8 in the environment overrides it for A/B runs
-    int xsub = h->cfg.x_sub > 0 ? h->cfg.x_sub : (h->cfg.max_batch >= 8 ? 4 : 1);
-    { const char* e = getenv("LIO_X_SUB"); const int v = e ? atoi(e) : 0; if (v == 1 || v == 2 || v == 4 || v == 8) xsub = v; }
-    // Long maps.  lio_cell_coord rounds (v - origin) at the fp32 spacing of the grid's EXTENT, so along y and z -- where the rows
-    // around the query's are all the search sees -- a map point within the bound can be counted one cell too far once that
-    // spacing comes near the grid's slack: the width of the rows searched (k cells, one for a tight table) less the largest
-    // bound searched in them.  A grid is used only while the spacing at its far end is at most half of that slack; beyond,
-    // the main grid takes larger cells and a tight table is left out (about 4 km of extent for a 1 m gate; the tables at
-    // 4, 2 and 1 km).  Along x the row search takes the run [cell(qx - Rx), cell(qx + Rx)]: rounding is monotone, no margin to
-    // lose.  The LDS-staged search (cfg.use_lds, lio_knn_lds) walks cx - k .. cx + k instead: for it the main grid obeys the
-    // rule along x as well.  Half of the slack is a margin that held in every emulated case, not a proven bound: the four
-    // roundings of a cell difference can add up to about 2.8 spacings in the worst case.
-    auto spacing_fits = [](float far_end, float slack) { return nextafterf(far_end, INFINITY) - far_end <= 0.5f * slack; };
-    LioGrid g;
-    for (;;) {
-        g.k = kdiv;
-        g.inv_cell = 1.0f / cell;
-        g.ox = mn[0] - 0.5f * cell; g.oy = mn[1] - 0.5f * cell; g.oz = mn[2] - 0.5f * cell;
-        const double ex = ((double)mx[0] - g.ox) * g.inv_cell, ey = ((double)mx[1] - g.oy) * g.inv_cell,
-                     ez = ((double)mx[2] - g.oz) * g.inv_cell;
-        const double cells = (floor(ex) + 2.0) * (floor(ey) + 2.0) * (floor(ez) + 2.0);
-        const float slack = (float)kdiv * cell - h->c.gate_reach;        // (grows by half a gate radius per step)
-        if (cells * xsub <= 256.0 * 1024.0 * 1024.0 && spacing_fits((mx[1] - g.oy) + cell, slack) && spacing_fits((mx[2] - g.oz) + cell, slack) &&
-            (!h->cfg.use_lds || spacing_fits((mx[0] - g.ox) + cell, slack))) {
-            g.nx = (int)floor(ex) + 2; g.ny = (int)floor(ey) + 2; g.nz = (int)floor(ez) + 2;
-            g.n_cells = g.nx * g.ny * g.nz;
-            break;
-        }
-        cell *= 1.5f;   // larger cells keep the search exact, only less selective
+    // the plan (lio_gridplan.h): the main grid, the occupied cells where the table count hangs on them, then the tables
+    const LioGridOverrides ov = lio_grid_overrides_from_env();
+    LioGridPlan plan = lio_plan_grid(h->cfg, h->c.gate_reach, mn, mx, n, box != nullptr, ov);
+    int occ = -1;
+    if (plan.want_occupancy) {
+        const LioGrid& g = plan.grid;
+        HIPCHK(h->d_cell_count.grow((size_t)g.n_cells + 1));
+        lio_launch_map_occupancy(g, h->d_mx, h->d_my, h->d_mz, (int)n, h->d_cell_count, h->stream);
+        HIPCHK(hipMemcpyAsync(&occ, h->d_cell_count + g.n_cells, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
     }
-    g.xs = xsub; g.nxf = g.nx * xsub; g.inv_cell_x = g.inv_cell * (float)xsub;
-    // tight rows (LioGrid::tb_*, cfg.tight_rows): further row tables with k = 1 and cells of 0.6 / 0.3 / 0.15 x the gate radius
-    // for the queries whose search bound is that small -- most of them from the second iteration on.  LIO_TIGHT = a comma
-    // separated, descending list of fractions (0 = none) in the environment for A/B runs.
-    float frac[LIO_TB_MAX] = { 0.6f, 0.3f, 0.15f };
-    int n_tb = h->cfg.tight_rows > 0 ? std::min(h->cfg.tight_rows, LIO_TB_MAX) : 0;
-    float pts_per_cell = 0.0f;
-    int try_lvl = -1;
-    if (h->cfg.tight_rows == 0 && h->cfg.max_batch >= 8) {
-        // auto, a handle set up for batches: one table always; the finer ones where the map is dense enough to have queries for
-        // them.  Points per occupied cell -> point spacing on the surfaces, s = cell / sqrt(points per cell); the fifth neighbour
-        // of a query on such a surface is about 1.26 s away; a table is built when its reach is at least that.  (Measured on
-        // the parameter sets of tools/param_sets.sh: the sparse 0.5 m maps are fastest with one table -- a second one only adds
-        // build time --, the 0.1 m map with three: +39 % registrations/s over one.)  Costs one small kernel and a 4-byte
-        // read-back here; a map whose bounding box is still on the device (`box`) stays asynchronous and gets one table.
-        n_tb = 1;
-        if (!box && n > 0) {
-            HIPCHK(h->d_cell_count.grow((size_t)g.n_cells + 1));
-            lio_launch_map_occupancy(g, h->d_mx, h->d_my, h->d_mz, (int)n, h->d_cell_count, h->stream);
-            int occ = 0;
-            HIPCHK(hipMemcpyAsync(&occ, h->d_cell_count + g.n_cells, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
-            if (occ > 0) {
-                pts_per_cell = (float)n / (float)occ;
-                const float spacing = cell / sqrtf(pts_per_cell);
-                while (n_tb < LIO_TB_MAX && sqrtf(h->cfg.max_sq_dist) * frac[n_tb] >= 1.26f * spacing) ++n_tb;
-                // the table an unbounded query tries first (LioGrid::tb_try): the tightest one 1.75x as wide as the expected
-                // distance of the fifth neighbour.  (Measured: +27 % registrations/s on the 0.1 m map, +5 % on the 0.3 m map,
-                // -4 % on the 0.5 m maps if forced there: nearly every wave then pays both searches -- the rule leaves those out.)
-                for (int l = 0; l < n_tb; ++l)
-                    if (sqrtf(h->cfg.max_sq_dist) * frac[l] >= 2.2f * spacing) try_lvl = l;
-            }
-        }
-    }
-    if (const char* e = getenv("LIO_TIGHT")) {
-        n_tb = 0;
-        for (const char* p = e; *p && n_tb < LIO_TB_MAX;) {
-            char* q = nullptr;
-            const float v = strtof(p, &q);
-            if (q == p) break;
-            if (v >= 0.05f && v <= 1.0f && (n_tb == 0 || v < frac[n_tb - 1])) frac[n_tb++] = v;
-            p = (*q == ',') ? q + 1 : q;
-            if (*q != ',') break;
-        }
-    }
-    if ((double)g.n_cells * xsub > 64.0 * 1024.0 * 1024.0) n_tb = 0;        // (a grid that large is mostly empty buckets already)
-    size_t len_b = 0, rows_b = 0;
-    for (int l = 0; l < LIO_TB_MAX; ++l) {
-        g.tb_row0[l] = 0; g.tb_ny[l] = g.tb_nz[l] = 0; g.tb_oy[l] = g.tb_oz[l] = 0.0f; g.tb_inv_cell[l] = 0.0f; g.tb_reach[l] = -1.0f;
-        if (l >= n_tb) continue;
-        const float reach = sqrtf(h->cfg.max_sq_dist) * frac[l], cb = reach * 1.001f;
-        const float inv = 1.0f / cb, oy = mn[1] - 0.5f * cb, oz = mn[2] - 0.5f * cb;
-        const double ny = floor(((double)mx[1] - oy) * inv) + 2.0, nz = floor(((double)mx[2] - oz) * inv) + 2.0;
-        // (bucket indices stay far inside 31 bits, and so do record offsets: every table adds 9 records per point + row padding)
-        const double recs = (double)nn * ((2 * g.k + 1) * (2 * g.k + 1) + 9.0 * (l + 1)) + LIO_ROW_ALIGN * ((double)g.ny * g.nz + (double)rows_b + ny * nz);
-        if ((double)g.n_cells * xsub + (double)len_b + ny * nz * g.nxf > 192.0 * 1024.0 * 1024.0 || recs > 2040.0 * 1024.0 * 1024.0) { n_tb = l; continue; }
-        // (long maps, see above: the bounded search walks this table for Rx <= reach, i.e. for true distances up to reach / 1.0001)
-        const float slack = cb - reach / 1.0001f;
-        if (!spacing_fits((mx[1] - oy) + cb, slack) || !spacing_fits((mx[2] - oz) + cb, slack)) { n_tb = l; continue; }
-        g.tb_inv_cell[l] = inv; g.tb_oy[l] = oy; g.tb_oz[l] = oz; g.tb_ny[l] = (int)ny; g.tb_nz[l] = (int)nz;
-        g.tb_row0[l] = (int)((size_t)g.n_cells * xsub + len_b);
-        g.tb_reach[l] = reach;
-        rows_b += (size_t)g.tb_ny[l] * g.tb_nz[l];
-        len_b += (size_t)g.tb_ny[l] * g.tb_nz[l] * g.nxf;
-    }
-    if (const char* e = getenv("LIO_TRY")) try_lvl = atoi(e);            // (A/B runs)
-    g.tb_try = (try_lvl >= 0 && try_lvl < n_tb) ? try_lvl : (try_lvl >= n_tb ? n_tb - 1 : -1);
-    for (int l = 0; l < LIO_TB_MAX; ++l) {
-        // (reach / 1.0002)^2, rounded towards zero by one more part in 10^6
-        const float r = g.tb_reach[l] > 0.0f ? g.tb_reach[l] / 1.0002f : 0.0f;
-        g.tb_try_b2[l] = r * r * 0.999999f;
-    }
-    h->grid = g;
-    const size_t len_a = (size_t)g.n_cells * xsub, reps = (size_t)((2 * g.k + 1) * (2 * g.k + 1)) + 9 * (size_t)n_tb;
-    HIPCHK(h->d_cell_count.grow((size_t)g.n_cells + len_a + len_b));   // (point counts + row bucket lengths of both tables)
+    lio_plan_tables(plan, h->cfg, mn, mx, n, occ, ov);
+    h->grid = plan.grid;
+    const LioGrid& g = h->grid;
+    HIPCHK(h->d_cell_count.grow(plan.n_cell_count));
     HIPCHK(h->d_cell_start.grow((size_t)g.n_cells + 1));
-    HIPCHK(h->d_nbr_start.grow(len_a + len_b + 1));
-    HIPCHK(h->d_nbr_pts.grow(nn * reps + LIO_ROW_ALIGN * ((size_t)g.ny * g.nz + rows_b) + 4 * LIO_ROW_ALIGN, 1.05));
-    HIPCHK(h->d_tile_sums.grow(2 * ((size_t)lio_scan_tiles((int)(len_a + len_b)) + 1)));   // (64-bit pair sums)
-    HIPCHK(h->d_nbr_slot.grow(nn * reps, 1.05));
+    HIPCHK(h->d_nbr_start.grow(plan.n_nbr_start));
+    HIPCHK(h->d_nbr_pts.grow(plan.n_nbr_pts, 1.05));
+    HIPCHK(h->d_tile_sums.grow(2 * ((size_t)lio_scan_tiles((int)(plan.len_a + plan.len_b)) + 1)));   // (64-bit pair sums)
+    HIPCHK(h->d_nbr_slot.grow(plan.n_nbr_slot, 1.05));
 
     HIPCHK(hipEventRecord(box ? h->ev_mapl[0] : h->ev_map[0], h->stream));
     if (n) {
@@ -369,7 +281,7 @@ static int lio_map_finish(lio_s2m_handle* h, size_t n, std::chrono::steady_clock
                              h->d_cell_start, h->d_tile_sums, h->d_sorted, h->d_nbr_start, h->d_nbr_pts, h->d_nbr_slot, h->cfg.use_lds != 0, h->stream);
     } else {
         HIPCHK(hipMemsetAsync(h->d_cell_start, 0, sizeof(int) * ((size_t)g.n_cells + 1), h->stream));
-        HIPCHK(hipMemsetAsync(h->d_nbr_start, 0, sizeof(int) * (len_a + len_b + 1), h->stream));
+        HIPCHK(hipMemsetAsync(h->d_nbr_start, 0, sizeof(int) * plan.n_nbr_start, h->stream));
     }
     HIPCHK(hipEventRecord(box ? h->ev_mapl[1] : h->ev_map[1], h->stream));
     HIPCHK(hipGetLastError());
@@ -388,9 +300,9 @@ static int lio_map_finish(lio_s2m_handle* h, size_t n, std::chrono::steady_clock
     h->prof.n_map = (int64_t)n;
     h->prof.n_cells = g.n_cells;
     h->prof.map_x_sub = g.xs;
-    h->prof.map_tight_tables = n_tb;
+    h->prof.map_tight_tables = plan.n_tb;
     h->prof.map_first_try = g.tb_try;
-    h->prof.map_pts_per_cell = pts_per_cell;
+    h->prof.map_pts_per_cell = plan.pts_per_cell;
     h->n_map = n;
     h->has_map = true;
     h->graph_dirty = true;
@@ -404,13 +316,9 @@ try {
     if (n > 0 && !pts) return lio_fail(LIO_ERR_ARG, "null map pointer");
     if (stride < 12 || (stride & 3)) return lio_fail(LIO_ERR_ARG, "stride_bytes must be >= 12 and a multiple of 4");
     if (h->multi) return lio_multi_set_map(h, pts, n, stride);
-    if (n >= (1ull << 25)) return lio_fail(LIO_ERR_CAPACITY, "map too large ((2k+1)^2 x n records must fit a 31-bit offset)");
     if (h->map_src) return lio_fail(LIO_ERR_ARG, "this handle searches another handle's map (lio_s2m_share_map)");
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    (void)hipGetLastError();   // drop stale codes left by other HIP users of this thread (e.g. hipErrorNotReady)
-    auto t0 = std::chrono::steady_clock::now();
-    h->has_map = false;
-    int rc = lio_map_reserve(h, n);
+    std::chrono::steady_clock::time_point t0;
+    const int rc = lio_map_begin(h, n, &t0);
     if (rc != LIO_OK) return rc;
     HIPCHK(h->d_map_stage.grow((n ? n : 1) * stride));
     if (n) {
@@ -424,12 +332,8 @@ try {
 int lio_s2m_set_map_device_xyzi(lio_s2m_handle* h, const float4* d_xyzi, size_t n)
 {
     if (!h) return lio_fail(LIO_ERR_ARG, "null handle");
-    if (n >= (1ull << 25)) return lio_fail(LIO_ERR_CAPACITY, "map too large ((2k+1)^2 x n records must fit a 31-bit offset)");
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    (void)hipGetLastError();
-    auto t0 = std::chrono::steady_clock::now();
-    h->has_map = false;
-    int rc = lio_map_reserve(h, n);
+    std::chrono::steady_clock::time_point t0;
+    const int rc = lio_map_begin(h, n, &t0);
     if (rc != LIO_OK) return rc;
     HIPCHK(hipDeviceSynchronize());        // the producer ran on another stream
     lio_launch_xyzi4_to_soa(d_xyzi, (int)n, h->d_mx, h->d_my, h->d_mz, h->d_map4, h->stream);
@@ -442,13 +346,9 @@ int lio_s2m_set_map_device_bbox(lio_s2m_handle* h, const float4* d_xyzi, size_t 
 {
     if (!h || !box) return lio_fail(LIO_ERR_ARG, "null argument");
     if (h->multi || h->map_src) return lio_fail(LIO_ERR_ARG, "this handle cannot take a device-resident map");
-    if (n >= (1ull << 25)) return lio_fail(LIO_ERR_CAPACITY, "map too large ((2k+1)^2 x n records must fit a 31-bit offset)");
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    (void)hipGetLastError();
-    auto t0 = std::chrono::steady_clock::now();
-    h->has_map = false;
     h->run_pending = false;
-    int rc = lio_map_reserve(h, n);
+    std::chrono::steady_clock::time_point t0;
+    const int rc = lio_map_begin(h, n, &t0);
     if (rc != LIO_OK) return rc;
     lio_launch_xyzi4_to_soa(d_xyzi, (int)n, h->d_mx, h->d_my, h->d_mz, h->d_map4, h->stream);
     return lio_map_finish(h, n, t0, box);
@@ -550,7 +450,7 @@ try {
     if (!h) return lio_fail(LIO_ERR_ARG, "null handle");
     if (axis < 0) { h->shard.axis = -1; return LIO_OK; }
     if (axis > 2 || !h->has_global) return lio_fail(LIO_ERR_ARG, "set_global_grid first; axis in 0..2");
-    const float cell = h->cfg.cell_size > 0.0f ? h->cfg.cell_size : sqrtf(h->cfg.max_sq_dist) * 1.001f;
+    const float cell = lio_gate_cell(h->cfg);
     h->shard.axis = axis;
     h->shard.gorigin = h->gorigin[axis];
     h->shard.inv_cell = 1.0f / cell;
@@ -686,6 +586,30 @@ try {
 // Test hook: the fp32 threshold the surface association compares against in place of the double t (lio_threshold_f32: the
 // largest float not above t).  Host only.
 extern "C" float lio_debug_threshold_f32(double t) { return lio_threshold_f32(t); }
+
+// Test hook (host only): the plan of lio_map_finish for a box and a cell count given by the caller.
+extern "C" int lio_debug_grid_plan(const lio_s2m_config* cfg, const float mn[3], const float mx[3], size_t n, int32_t occupied,
+                                   int32_t caller_box, lio_grid_plan_info* out)
+try {
+    if (!cfg || !mn || !mx || !out) return lio_fail(LIO_ERR_ARG, "null argument");
+    const LioGridOverrides ov = lio_grid_overrides_from_env();
+    LioGridPlan plan = lio_plan_grid(*cfg, lio_gate_reach(cfg->max_sq_dist), mn, mx, n, caller_box != 0, ov);
+    lio_plan_tables(plan, *cfg, mn, mx, n, occupied, ov);
+    const LioGrid& g = plan.grid;
+    out->origin[0] = g.ox; out->origin[1] = g.oy; out->origin[2] = g.oz; out->inv_cell = g.inv_cell;
+    out->nx = g.nx; out->ny = g.ny; out->nz = g.nz; out->n_cells = g.n_cells; out->k = g.k; out->xs = g.xs; out->nxf = g.nxf;
+    out->inv_cell_x = g.inv_cell_x;
+    for (int l = 0; l < LIO_TB_MAX; ++l) {
+        out->tb_row0[l] = g.tb_row0[l]; out->tb_ny[l] = g.tb_ny[l]; out->tb_nz[l] = g.tb_nz[l];
+        out->tb_oy[l] = g.tb_oy[l]; out->tb_oz[l] = g.tb_oz[l]; out->tb_inv_cell[l] = g.tb_inv_cell[l]; out->tb_reach[l] = g.tb_reach[l];
+        out->tb_try_b2[l] = g.tb_try_b2[l];
+    }
+    out->tb_try = g.tb_try;
+    out->cell = plan.cell; out->n_tb = plan.n_tb; out->grow_steps = plan.grow_steps; out->want_occupancy = plan.want_occupancy ? 1 : 0;
+    out->pts_per_cell = plan.pts_per_cell;
+    out->buckets = (int64_t)(plan.len_a + plan.len_b);
+    return LIO_OK;
+} LIO_CATCH
 
 // The SoA copy of the resident batch, for the paths that read it, if the upload skipped it.
 static int lio_ensure_soa(lio_s2m_handle* h)
@@ -878,24 +802,8 @@ try {
                 mn[a] = none ? 0.0f : lio_ord2f(lo);
                 mx[a] = none ? 0.0f : lio_ord2f(hi);
             }
-            float tile = h->cfg.tile_size > 0.0f ? h->cfg.tile_size : 4.0f;
-            LioScanTiles t;
-            for (;;) {
-                t.inv_tile = 1.0f / tile;
-                const double ex = floor(((double)mx[0] - mn[0]) * t.inv_tile) + 1.0, ey = floor(((double)mx[1] - mn[1]) * t.inv_tile) + 1.0,
-                             ez = floor(((double)mx[2] - mn[2]) * t.inv_tile) + 1.0;
-                if (ex * ey * ez <= 262144.0) { t.ntx = (int)ex; t.nty = (int)ey; t.ntz = (int)ez; break; }
-                tile *= 2.0f;
-            }
-            t.ox = mn[0]; t.oy = mn[1]; t.oz = mn[2];
+            LioScanTiles t = lio_plan_scan_tiles(mn, mx, h->cfg.tile_size > 0.0f ? h->cfg.tile_size : 4.0f, h->shard.axis);
             t.key_offset = (int)n_keys;
-            // Order of the tiles = order of the association workgroups' points.  Unsharded: x fastest.  With a sharded map
-            // the shard axis varies slowest, so a workgroup's 256 points form a slice about one tile thick ACROSS that
-            // axis and k_shard_cull can drop it on every rank but one or two.  (Lidar frame; effective while the
-            // vehicle's heading stays within ~45 degrees of a map axis, merely less effective -- never wrong -- otherwise.)
-            t.mx = 1; t.my = t.ntx; t.mz = t.ntx * t.nty;
-            if (h->shard.axis == 0) { t.mz = 1; t.my = t.ntz; t.mx = t.ntz * t.nty; }
-            else if (h->shard.axis == 1) { t.mx = 1; t.mz = t.ntx; t.my = t.ntx * t.ntz; }
             tiles[s] = t;
             n_keys += (long long)t.ntx * t.nty * t.ntz;
         }

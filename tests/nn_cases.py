@@ -3,8 +3,8 @@
 The search of lio_knn_global / lio_knn_range (lio_s2m_device.h) is exact as long as three things hold: the fp32 cell
 arithmetic of lio_cell_coord puts every map point within the search bound into the (2k+1)^2 rows (3x3 for a tight table)
 around the query's row, the (d2, index) order breaks ties the way FLANN does, and the host picks grids and tables
-(lio_map_finish, liogpu_api.hip) whose margins cover the rounding.  This module restates the host arithmetic
-(`grid_of`), the device's cell formula (`cell_coord_f32`) and FLANN's squared distance (`d2_f32`) bit for bit, and builds
+(lio_plan_grid and lio_plan_tables, lio_gridplan.h) whose margins cover the rounding.  This module restates the host arithmetic
+(`grid_of`; tests/test_nn_cases_cpu.py holds it against the library's own plan, field for field), the device's cell formula (`cell_coord_f32`) and FLANN's squared distance (`d2_f32`) bit for bit, and builds
 the maps and scans on which those claims are tight: exact lattices, fifth neighbours exactly at the gate and at a table's
 acceptance bound, queries outside the grid, maps kilometres long and a few metres wide, and the size caps.
 
@@ -15,7 +15,7 @@ tests/test_nn_cases_cpu.py to verify under the oracle and tests/test_gpu_nn_marg
 import numpy as np
 
 F = np.float32
-FRAC = (0.6, 0.3, 0.15)            # tight tables: cell = reach * 1.001, reach = FRAC[l] * gate radius (lio_map_finish)
+FRAC = (0.6, 0.3, 0.15)            # tight tables: cell = reach * 1.001, reach = FRAC[l] * gate radius (lio_plan_tables)
 ROW_ALIGN = 8                      # LIO_ROW_ALIGN
 MI = 1024.0 * 1024.0
 POSE0 = np.zeros(6, F)             # identity: the transformed query IS the scan point, bit for bit
@@ -43,10 +43,12 @@ def _ulp(x):
 
 
 def grid_of(map_xyz, cfg=None, long_map_rule=True):
-    """The host arithmetic of lio_map_finish for a map and ScanToMap settings (environment overrides not modelled).
+    """The host arithmetic of lio_plan_grid and lio_plan_tables (lio_gridplan.h) for a map and ScanToMap settings, as
+    lio_s2m_set_map runs them (environment overrides not modelled).  g["occupied"] = the occupied cells the device would count
+    for the automatic table choice, -1 where it counts none.
 
     long_map_rule=False leaves out the rule "a grid is used only while the fp32 spacing at its far end along y and z is at most
-    half of its slack": the grid lio_map_finish laid out before it had that rule, tables at any extent.  The tests use it to
+    half of its slack": the grid the library laid out before it had that rule, tables at any extent.  The tests use it to
     show what the rule is for, and that maps under a kilometre get the same grid either way."""
     cfg = dict(cfg or {})
     gate = F(cfg.get("max_sq_dist", 1.0))
@@ -86,7 +88,7 @@ def grid_of(map_xyz, cfg=None, long_map_rule=True):
              inv_cell_x=inv * F(xsub), gate=gate, gate_reach=gate_reach, grow_steps=steps, mn=mn, mx=mx)
     tight = cfg.get("tight_rows", 0)
     n_tb = min(tight, 3) if tight > 0 else 0
-    ppc, try_lvl = F(0.0), -1
+    ppc, try_lvl, occ = F(0.0), -1, -1
     if tight == 0 and max_batch >= 8:
         n_tb = 1
         if n > 0:
@@ -124,10 +126,10 @@ def grid_of(map_xyz, cfg=None, long_map_rule=True):
                 break
         r = reach / F(1.0002)
         tables.append(dict(reach=reach, cell=cb, inv_cell=tinv, oy=oy, oz=oz, ny=int(tny), nz=int(tnz),
-                           try_b2=F(F(r * r) * F(0.999999))))
+                           try_b2=F(F(r * r) * F(0.999999)), row0=g["n_cells"] * xsub + len_b))
         rows_b += int(tny) * int(tnz)
         len_b += int(tny) * int(tnz) * g["nxf"]
-    g.update(n_tb=n_tb, tables=tables, pts_per_cell=ppc, buckets=g["n_cells"] * xsub + len_b,
+    g.update(n_tb=n_tb, tables=tables, pts_per_cell=ppc, occupied=occ, buckets=g["n_cells"] * xsub + len_b,
              tb_try=(try_lvl if 0 <= try_lvl < n_tb else (n_tb - 1 if try_lvl >= n_tb else -1)))
     return g
 
@@ -485,7 +487,7 @@ def _corner_box(rng, dims, cfg):
 
 
 def size_fallbacks(which, seed=5):
-    """Maps of a few hundred points whose bounding box alone trips a size rule of lio_map_finish.  note["expect"] = what
+    """Maps of a few hundred points whose bounding box alone trips a size rule of lio_plan_grid / lio_plan_tables.  note["expect"] = what
     grid_of must give (and the device profile report): grow_steps, n_tb.
       grow1 / grow3   the `cell *= 1.5` loop runs once / three times (cells * x_sub > 256 Mi)
       below64 / above64   n_cells * x_sub just below / just above 64 Mi: one tight table / none

@@ -1,11 +1,11 @@
 """The 5-NN grid search on the cases of tests/nn_cases.py -- exact lattices (ties), fifth neighbours exactly at the gate and at a
-tight table's acceptance bound, queries outside the grid, maps kilometres long, the size caps of lio_map_finish -- against the
+tight table's acceptance bound, queries outside the grid, maps kilometres long, the size caps of lio_plan_grid / lio_plan_tables (lio_gridplan.h) -- against the
 oracle's kd-tree search, the way tests/test_gpu_fuzz.py::_check compares: flags, 5-NN indices and the coefficients of accepted
 points bit for bit at the recorded iteration, the correspondence counts of every iteration, the pose within 1e-5.  Every case
 runs through the launch-per-iteration loop, the one-launch loop and a batch handle with its automatic row tables; the lattices
 the gate edges and the x strips also through the LDS-staged search; the bounded search (iteration 2) on a dense patch, alone
 and at the far end of grids just under the extents at which the long-map rule drops a table.  The grid the device reports (cells, tight tables, first try) must be
-the one tests/nn_cases.py::grid_of restates from lio_map_finish."""
+the one tests/nn_cases.py::grid_of restates from that plan (held against it field for field in tests/test_nn_cases_cpu.py)."""
 import os
 
 import numpy as np
@@ -82,7 +82,7 @@ def test_nn_margins(pkg, oracle, name, mode):
         np.testing.assert_array_equal(p, po)
     if it == 2:
         assert ro.iters == 3 and int(flag.sum()) > 1000
-    # the grid: what lio_map_finish laid out is what grid_of restates (cells after the size and long-map rules, tables, first try)
+    # the grid: what the plan laid out (lio_gridplan.h, through lio_map_finish) is what grid_of restates (cells after the size and long-map rules, tables, first try)
     assert (prof.n_cells, prof.map_x_sub, prof.map_tight_tables, prof.map_first_try) == (g["n_cells"], g["xs"], g["n_tb"], g["tb_try"]), seen
     if note["kind"] == "size" and mode != "batch":
         assert (g["grow_steps"], g["n_tb"]) == (note["expect"]["grow_steps"], note["expect"]["n_tb"])

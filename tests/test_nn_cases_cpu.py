@@ -1,4 +1,7 @@
-"""The case builders of tests/nn_cases.py checked on the CPU: `grid_of` gives the constants lio_map_finish documents, every
+"""The case builders of tests/nn_cases.py checked on the CPU: `grid_of` gives the constants lio_gridplan.h documents and, field
+for field and bit for bit, the plan the library itself lays out (lio_plan_grid and lio_plan_tables through the host-only hook
+lio_debug_grid_plan: every case under every handle setting of the GPU test, the size caps, the long-map thresholds, the
+caller's-box path, the environment overrides), every
 built case really has the ties and edges it claims (under the oracle's brute-force and kd-tree searches, which must agree),
 and the emulation of lio_cell_coord pins the long-map rule: two-cell misses exist without it on a strip of 8200 m, none
 with it at any extent from 100 m to 70 km.  The miss counts come from that emulation, not from hardware.  "Half of the slack" is
@@ -6,10 +9,14 @@ an empirical margin, not a bound: the four roundings of a cell difference (two s
 2.8 spacings of the extent in the worst case, 1.4 times the slack where slack / 2 lies just above a power of two -- the sweep
 includes such a gate (0.55: the 0.15 table's threshold falls at 1016 m with spacing / slack = 0.499) and finds nothing there
 either."""
+import importlib
+import os
+
 import numpy as np
 import pytest
 
 import nn_cases as nc
+from test_gpu_nn_margins import MODES, _iters              # the handle settings every case runs under on the device
 
 F = np.float32
 CASES = list(nc.all_cases())
@@ -91,6 +98,133 @@ def test_long_map_rule_thresholds():
         assert [n_tb(e, axis) for e in (1000.0, 1030.0, 2040.0, 2050.0, 4090.0, 4100.0)] == \
                [(3, 0), (2, 0), (2, 0), (1, 0), (1, 0), (0, 1)]
     assert n_tb(17000.0, 0) == (3, 0)
+
+
+# ------------------------------------------------------------------------------------------------ grid_of against the library
+# (host only: lio_debug_grid_plan runs the parser and the two steps lio_s2m_set_map runs, on grid_of's box and cell count)
+no_overrides = pytest.mark.skipif(any(os.environ.get(v) for v in ("LIO_TIGHT", "LIO_X_SUB", "LIO_TRY")),
+                                  reason="the row tables are overridden from the environment")
+SETTINGS = dict(MODES, plain_tables=None)
+
+
+@pytest.fixture(scope="module")
+def plan_of():
+    api = importlib.import_module("lio-slam_amd.api")
+
+    def run(m, cfg, caller_box=False):
+        g = nc.grid_of(m, cfg)
+        return g, api.debug_grid_plan(g["mn"], g["mx"], len(m), g["occupied"], caller_box, **cfg)
+    return run
+
+
+def _same_plan(g, p):
+    """grid_of's dict against lio_grid_plan_info: floats as uint32 words, counts as integers"""
+    want = dict(cell=_bits(g["cell"]), inv_cell=_bits(g["inv_cell"]), inv_cell_x=_bits(g["inv_cell_x"]), origin=_bits(g["origin"]).tolist(),
+                pts_per_cell=_bits(g["pts_per_cell"]),
+                counts=(g["nx"], g["ny"], g["nz"], g["n_cells"], g["k"], g["xs"], g["nxf"], g["n_tb"], g["tb_try"], g["grow_steps"], g["buckets"]),
+                tables=[(_bits(t["reach"]), _bits(t["inv_cell"]), _bits(t["oy"]), _bits(t["oz"]), _bits(t["try_b2"]), t["ny"], t["nz"], t["row0"])
+                        for t in g["tables"]] + [(_bits(-1.0), _bits(0.0), _bits(0.0), _bits(0.0), _bits(0.0), 0, 0, 0)] * (3 - g["n_tb"]))
+    seen = dict(cell=_bits(p.cell), inv_cell=_bits(p.inv_cell), inv_cell_x=_bits(p.inv_cell_x), origin=_bits(list(p.origin)).tolist(),
+                pts_per_cell=_bits(p.pts_per_cell),
+                counts=(p.nx, p.ny, p.nz, p.n_cells, p.k, p.xs, p.nxf, p.n_tb, p.tb_try, p.grow_steps, p.buckets),
+                tables=[(_bits(p.tb_reach[l]), _bits(p.tb_inv_cell[l]), _bits(p.tb_oy[l]), _bits(p.tb_oz[l]), _bits(p.tb_try_b2[l]),
+                         p.tb_ny[l], p.tb_nz[l], p.tb_row0[l]) for l in range(3)])
+    assert len(g["tables"]) == g["n_tb"]
+    assert seen == want
+
+
+@no_overrides
+@pytest.mark.parametrize("setting", SETTINGS)
+@pytest.mark.parametrize("name", CASES)
+def test_grid_of_is_the_librarys_plan(plan_of, name, setting):
+    m, _, _, cfg, _ = nc.build_case(name)
+    if setting == "plain_tables":
+        full = dict(cfg, tight_rows=3, x_sub=1)
+    else:                                                   # (as tests/test_gpu_nn_margins.py sets its handles up)
+        full = dict(cfg, **MODES[setting])
+        if setting != "batch":
+            full.update(_iters(name)[2])
+    _same_plan(*plan_of(m, full))
+
+
+@no_overrides
+@pytest.mark.parametrize("which", ["grow1", "grow3", "below64", "above64", "third192"])
+def test_size_caps_in_the_library(plan_of, which):
+    m, _, _, cfg, note = nc.build_case("size_" + which)
+    g, p = plan_of(m, cfg)
+    assert (p.grow_steps, p.n_tb) == (note["expect"]["grow_steps"], note["expect"]["n_tb"])
+    cells = float(p.n_cells) * p.xs
+    assert cells <= 256 * nc.MI
+    if which.startswith("grow"):
+        cell = F(1.001) / F(2)
+        for _ in range(note["expect"]["grow_steps"]):
+            cell = cell * F(1.5)
+        assert _bits(p.cell) == _bits(cell)
+        assert plan_of(m, dict(cfg, cell_size=float(F(p.cell) / F(1.5)) * p.k))[1].grow_steps >= 1      # one step less would not fit
+    if which == "below64":
+        assert cells <= 64 * nc.MI < cells + p.nx * p.ny
+    if which == "above64":
+        assert cells - p.nx * p.ny <= 64 * nc.MI < cells
+    if which == "third192":
+        full = plan_of(m, dict(cfg, tight_rows=2))[1]
+        assert full.n_tb == 2 and full.buckets == p.buckets <= 192 * nc.MI and cells <= 64 * nc.MI
+        assert p.buckets + 3.9 * p.tb_ny[1] * p.tb_nz[1] * p.nxf > 192 * nc.MI
+
+
+@no_overrides
+def test_long_map_rule_thresholds_in_the_library(plan_of):
+    def n_tb(extent, axis=1):
+        hi = [4.0, 4.0, 4.0]; hi[axis] = extent
+        p = plan_of(np.array([[0, 0, 0], hi], F), dict(tight_rows=3))[1]
+        return p.n_tb, p.grow_steps
+    for axis in (1, 2):
+        assert [n_tb(e, axis) for e in (1000.0, 1030.0, 2040.0, 2050.0, 4090.0, 4100.0)] == \
+               [(3, 0), (2, 0), (2, 0), (1, 0), (1, 0), (0, 1)]
+    assert n_tb(17000.0, 0) == (3, 0)
+
+
+@no_overrides
+def test_a_callers_box_counts_no_cells(plan_of):
+    """A map whose box the caller supplies (assembled on the device, installed without a read-back) gets the one table of an
+    automatic batch handle; the same map through lio_s2m_set_map gets what its density is worth."""
+    dense = nc._dense_patch(np.random.default_rng(5), size=6.0)
+    g, p = plan_of(dense, dict(max_batch=64), caller_box=True)
+    assert g["occupied"] > 0 and not p.want_occupancy
+    assert (p.n_tb, p.tb_try, p.pts_per_cell) == (1, -1, 0.0)
+    g, p = plan_of(dense, dict(max_batch=64))
+    assert p.want_occupancy and (p.n_tb, p.tb_try) == (3, 2) and p.pts_per_cell > 50
+    _same_plan(g, p)
+
+
+def test_environment_overrides(plan_of, monkeypatch):
+    """LIO_TIGHT, LIO_X_SUB and LIO_TRY as the library parses them at every map set (A/B runs)."""
+    for v in ("LIO_TIGHT", "LIO_X_SUB", "LIO_TRY"):
+        monkeypatch.delenv(v, raising=False)
+    m = nc._dense_patch(np.random.default_rng(5), size=6.0)
+    root = F(1.0)
+
+    def reaches(p):
+        return [_bits(p.tb_reach[l]) for l in range(p.n_tb)]
+    monkeypatch.setenv("LIO_TIGHT", "0.5,0.25")
+    p = plan_of(m, dict())[1]
+    assert p.n_tb == 2 and reaches(p) == [_bits(root * F(0.5)), _bits(root * F(0.25))]
+    assert plan_of(m, dict(tight_rows=3))[1].n_tb == 2                       # (whatever the handle asked for)
+    monkeypatch.setenv("LIO_TIGHT", "0")
+    assert plan_of(m, dict(tight_rows=3))[1].n_tb == 0 and plan_of(m, dict(max_batch=64))[1].n_tb == 0
+    monkeypatch.setenv("LIO_TIGHT", "0.3,0.6")                               # not descending: the list ends at the first entry
+    p = plan_of(m, dict())[1]
+    assert p.n_tb == 1 and reaches(p) == [_bits(root * F(0.3))]
+    monkeypatch.setenv("LIO_TIGHT", "0.5,0.25")
+    monkeypatch.setenv("LIO_TRY", "5")                                       # clamped to the tightest table there is
+    assert plan_of(m, dict())[1].tb_try == 1
+    monkeypatch.setenv("LIO_TRY", "0")
+    assert plan_of(m, dict())[1].tb_try == 0
+    monkeypatch.delenv("LIO_TIGHT"); monkeypatch.delenv("LIO_TRY")
+    monkeypatch.setenv("LIO_X_SUB", "8")
+    p = plan_of(m, dict())[1]
+    assert p.xs == 8 and p.nxf == 8 * p.nx
+    monkeypatch.setenv("LIO_X_SUB", "3")                                     # not 1, 2, 4 or 8: ignored
+    assert plan_of(m, dict())[1].xs == 1 and plan_of(m, dict(max_batch=64))[1].xs == 4
 
 
 # ------------------------------------------------------------------------------------------------ the emulation
