@@ -817,7 +817,7 @@ int  lio_kf_store_height_map(lio_kf_store *s, const lio_local_map_config *lm, co
  * surface normals (NormalVectorsFilter) -> slope -> roughness (MathExpressionFilter) -> edges
  * (SlidingWindowMathExpressionFilter) -> traversability -> its two ThresholdFilters.  The input grid stands for the
  * chain's `elevation_inpainted`: OpenCV's inpaint is not reproduced, fill_holes = 1 of the height map is the labelled
- * substitute.  DESIGN.md section 4g states the conventions (parity unpinned: Eigen, EigenLab and grid_map are restated, not
+ * substitute (lio_median_fill below is the reference tree's own inpainting filter, restated exactly).  DESIGN.md section 4g states the conventions (parity unpinned: Eigen, EigenLab and grid_map are restated, not
  * linked).  The defaults are the yaml's literal values, which are tuned for a 0.02 m grid: at the loader's 0.2 m resolution
  * a node scales the three lengths (normal_radius, smooth_radius, edge_window_length) accordingly, by 10. */
 enum { LIO_TERRAIN_SMOOTH = 0, LIO_TERRAIN_NORMAL_X, LIO_TERRAIN_NORMAL_Y, LIO_TERRAIN_NORMAL_Z,
@@ -1075,6 +1075,76 @@ int  lio_sdf_memory(lio_sdf *sdf, size_t *field_bytes, size_t *workspace_bytes);
  * boundaries as HIP events; ms (may be NULL) receives the last such build's layer statistics with their host wait, column
  * sweeps, row sweeps and node stencil, in milliseconds (a build's allocations fall between the first and the second). */
 int  lio_sdf_debug_stage_ms(int32_t enable, float ms[4]);
+
+/* ------------------------------------------------ median fill (grid_map_filters' MedianFillFilter behind the height map) */
+/* grid_map_filters/src/MedianFillFilter.cpp (plugin gridMapFilters/MedianFillFilter): the inpainting filter of the reference
+ * tree that can be restated exactly -- a validity mask, 3 x 3 morphology on it, and the median of the finite values in a square
+ * window for every hole the mask marks.  Every operation is a selection or a comparison, so the result equals the
+ * restatement (tests/median_fill_restate.py) bit for bit; parity is against that restatement, OpenCV and grid_map are not
+ * linked, and the reference's own test case (median_fill_filter_test.cpp) pins one input.  It is what SignedDistanceField.cpp:
+ * 46-51 asks for ("Apply inpainting first") and what may stand for the terrain chain's `elevation_inpainted`.  DESIGN.md
+ * section 4j states the conventions.  The defaults are the constructor's (:24-25). */
+typedef struct lio_median_fill_config {
+    double  fill_hole_radius;               /* the window of a hole, metres                                   0.05 */
+    double  existing_value_radius;          /* the window of a finite cell when filter_existing_values        0.0  */
+    int32_t filter_existing_values;         /* 1: masked finite cells become their window's median            0    */
+    int32_t num_erode_dilation_iterations;  /* N of fillHoles, 0 .. 15                                        4    */
+} lio_median_fill_config;
+typedef struct lio_median_fill_info {
+    int32_t rows, cols;
+    int32_t fill_radius_cells, existing_radius_cells;   /* static_cast<size_t>(radius / resolution): truncated, 0.6 / 0.2 = 2 */
+    int32_t n_nan_in;                       /* non-finite cells of the input (+-inf is a hole like NaN)                 */
+    int32_t n_mask;                         /* non-zero cells of the fill mask                                         */
+    int32_t n_filled;                       /* non-finite in, finite out                                               */
+    int32_t n_filtered;                     /* finite cells that went through the median (filter_existing_values)      */
+    int32_t n_nan_out;                      /* non-finite cells of the output                                          */
+    int32_t pad;
+} lio_median_fill_info;
+void lio_median_fill_default_config(lio_median_fill_config *cfg);
+/* update() on a host grid of rows x cols floats, column-major (grid_map::Matrix).  Stage by stage, as written there:
+ *  - validity: std::isfinite;
+ *  - cleaned mask (:212-224): dilate(erode(valid)) with the 3 x 3 rectangle -- the first dilate / erode pair is overwritten
+ *    by the third call, one opening survives;
+ *  - fill mask (:226-239): max(N, 1) dilations, then N erosions (one dilation is unconditional: N = 0 dilates once and never
+ *    erodes).  Cells outside the grid take no part in any minimum or maximum (OpenCV's default border);
+ *  - per cell (:132-145): input not finite and mask != 0 -> the median over [r - R, r + R] x [c - R, c + R] clamped into the
+ *    grid, R = fill_radius_cells; else filter_existing_values and mask != 0 -> the median with existing_radius_cells; else
+ *    the input's bits (NaN payloads and infinities pass through);
+ *  - the median (:153-186): the element at sorted position n / 2 of the n finite values (the upper median for even n), the
+ *    quiet NaN 0x7fc00000 for n = 0; -0 sorts below +0 (a convention: std::nth_element leaves it open).
+ * mask_in (may be NULL): the fill mask of a previous run, rows x cols floats, used as it is (non-zero = fill); none is
+ * computed and cleaned_mask is left alone.  filled: the output layer.  fill_mask, cleaned_mask (each may be NULL): the masks
+ * as 0.0f / 1.0f; cleaned_mask is the filter's debug layer.  rows or cols 0: LIO_OK, nothing written.  LIO_ERR_ARG before any
+ * device is touched, never a clamp: negative or non-finite radii, resolution < 1e-4 or not finite, a flag other than 0 / 1,
+ * N < 0 or N > 15 (the mask kernel's halo 2 + max(N, 1) + N is at most 32 cells), a radius above 32 cells, null arguments.
+ * More than 2^31 - 1024 cells: LIO_ERR_CAPACITY. */
+int  lio_median_fill(int32_t device_id, const float *elevation, int32_t rows, int32_t cols, double resolution,
+                     const lio_median_fill_config *cfg, const float *mask_in, float *filled, float *fill_mask,
+                     float *cleaned_mask, lio_median_fill_info *info);
+
+/* The host buffers of lio_kf_store_planning_map, each with its capacity in floats and each skipped when NULL. */
+typedef struct lio_planning_map_buffers {
+    float *grid;      size_t grid_cap;       /* the raw elevation grid: lio_kf_store_height_map's bytes   */
+    float *filled;    size_t filled_cap;     /* the filled grid (fill given)                              */
+    float *fill_mask; size_t fill_mask_cap;  /* its fill mask (fill given)                                */
+    float *layers;    size_t layers_cap;     /* the terrain layers as lio_terrain_layers lays them out    */
+} lio_planning_map_buffers;
+/* One chain for a planning node: lio_kf_store_height_map's stages run once, then on the device grid they leave
+ *  - fill != NULL: lio_median_fill (no mask_in);
+ *  - terrain != NULL: lio_terrain_layers on the filled grid (on the raw grid without fill);
+ *  - sdf != NULL (sdf_cfg then too): lio_sdf_build on the same grid; sdf_info->n_nan counts that grid.
+ * Every info (each may be NULL) is filled as the stand-alone call fills it; the stages run in this order on the null stream
+ * and all are complete on return, so a refusal of the field (holes left under nan_policy 0) still leaves the grids and the
+ * layers written.  With fill, terrain and sdf all NULL the call is lio_kf_store_height_map.  An empty store or an empty local
+ * map: LIO_OK, rows = cols = 0.  A store and an sdf on different devices: LIO_ERR_ARG.  A buffer smaller than rows x cols
+ * (layers: times the requested layers): LIO_ERR_ARG with rows and cols filled in.  The configurations are refused as their
+ * own calls refuse them, before any device is touched. */
+int  lio_kf_store_planning_map(lio_kf_store *s, const lio_local_map_config *lm, const float pose[6],
+                               const lio_height_map_config *hm, const lio_median_fill_config *fill,
+                               const lio_terrain_config *terrain, lio_sdf *sdf, const lio_sdf_config *sdf_cfg,
+                               const lio_planning_map_buffers *out, lio_local_map_info *lm_info,
+                               lio_height_map_info *hm_info, lio_median_fill_info *fill_info,
+                               lio_terrain_info *terrain_info, lio_sdf_info *sdf_info);
 
 #ifdef __cplusplus
 }

@@ -286,6 +286,23 @@ public:
         check(lio_kf_store_sdf(s_, &lm, transformTobeMapped, &hm, &c, grid, grid_cap, sdf, lm_info, hm_info, &info), "lio_kf_store_sdf");
         return (size_t)info.rows * (size_t)info.cols * (size_t)info.layers;
     }
+    // The one chain of a planning node: heightMap's stages once, then grid_map_filters' MedianFillFilter (fill), the terrain
+    // layers (terrain) and the signed distance field (sdf with sdf_cfg) on the grid left on the device; a stage whose pointer
+    // is nullptr is absent.  `out` names the host buffers (each may be nullptr).  Returns the number of cells.
+    size_t planningMap(const float transformTobeMapped[6], const lio_planning_map_buffers& out, const lio_median_fill_config* fill,
+                       const lio_terrain_config* terrain, lio_sdf* sdf, const lio_sdf_config* sdf_cfg, lio_height_map_info& hm_info,
+                       lio_median_fill_info* fill_info = nullptr, lio_terrain_info* terrain_info = nullptr, lio_sdf_info* sdf_info = nullptr,
+                       const lio_height_map_config* hm_cfg = nullptr, const lio_local_map_config* lm_cfg = nullptr,
+                       lio_local_map_info* lm_info = nullptr)
+    {
+        lio_local_map_config lm;
+        if (lm_cfg) lm = *lm_cfg; else lio_local_map_default_config(&lm);
+        lio_height_map_config hm;
+        if (hm_cfg) hm = *hm_cfg; else lio_height_map_default_config(&hm);
+        check(lio_kf_store_planning_map(s_, &lm, transformTobeMapped, &hm, fill, terrain, sdf, sdf_cfg, &out, lm_info, &hm_info, fill_info,
+                                        terrain_info, sdf_info), "lio_kf_store_planning_map");
+        return (size_t)hm_info.rows * (size_t)hm_info.cols;
+    }
     lio_kf_store* get() { return s_; }
 
 private:
@@ -334,5 +351,18 @@ private:
     }
     lio_sdf* s_ = nullptr;
 };
+
+// grid_map_filters' MedianFillFilter::update on a host grid, column-major rows x cols (grid_map::Matrix): `filled` receives
+// the output layer, fill_mask and cleaned_mask (each may be nullptr) the masks; mask_in (may be nullptr) is the fill mask of a
+// previous run.  cfg == nullptr: the constructor's defaults.
+inline void medianFill(const float* elevation, int32_t rows, int32_t cols, double resolution, float* filled, lio_median_fill_info& info,
+                       const lio_median_fill_config* cfg = nullptr, const float* mask_in = nullptr, float* fill_mask = nullptr,
+                       float* cleaned_mask = nullptr, int32_t device_id = 0)
+{
+    lio_median_fill_config c;
+    if (cfg) c = *cfg; else lio_median_fill_default_config(&c);
+    const int rc = lio_median_fill(device_id, elevation, rows, cols, resolution, &c, mask_in, filled, fill_mask, cleaned_mask, &info);
+    if (rc < 0) throw Error(rc, std::string("lio_median_fill: ") + lio_last_error());
+}
 
 }  // namespace liogpu

@@ -16,7 +16,8 @@ from .api import (LioError, ScanToMap, S2MConfig, S2MResult, S2MProfile, DeskewC
                   TerrainConfig, TerrainInfo, TERRAIN_LAYERS, terrain_layers, terrain_default_config,
                   GlobalMapConfig, GlobalMapInfo, ExportConfig, global_map_default_config, STAGED_DS, STAGED_RAW,
                   OgmConfig, OgmInfo, ogm_default_config, radius_filter, occupancy_grid,
-                  SdfConfig, SdfInfo, Sdf, SDF_NODE_LIMIT, sdf_default_config, occupancy_sdf)
+                  SdfConfig, SdfInfo, Sdf, SDF_NODE_LIMIT, sdf_default_config, occupancy_sdf,
+                  MedianFillConfig, MedianFillInfo, PlanningMapBuffers, median_fill, median_fill_default_config)
 
 __all__ = ["LioError", "ScanToMap", "S2MConfig", "S2MResult", "S2MProfile", "DeskewConfig",
            "lib_path", "load_library", "build_library", "deskew", "curvature", "imu_deskew_info",
@@ -29,4 +30,5 @@ __all__ = ["LioError", "ScanToMap", "S2MConfig", "S2MResult", "S2MProfile", "Des
            "TerrainConfig", "TerrainInfo", "TERRAIN_LAYERS", "terrain_layers", "terrain_default_config",
            "GlobalMapConfig", "GlobalMapInfo", "ExportConfig", "global_map_default_config", "STAGED_DS", "STAGED_RAW",
            "OgmConfig", "OgmInfo", "ogm_default_config", "radius_filter", "occupancy_grid",
-           "SdfConfig", "SdfInfo", "Sdf", "SDF_NODE_LIMIT", "sdf_default_config", "occupancy_sdf"]
+           "SdfConfig", "SdfInfo", "Sdf", "SDF_NODE_LIMIT", "sdf_default_config", "occupancy_sdf",
+           "MedianFillConfig", "MedianFillInfo", "PlanningMapBuffers", "median_fill", "median_fill_default_config"]

@@ -226,6 +226,24 @@ class SdfInfo(C.Structure):
                 ("n_all_free", C.c_int32), ("n_mixed", C.c_int32), ("pad", C.c_int32)]
 
 
+class MedianFillConfig(C.Structure):
+    """grid_map_filters' MedianFillFilter parameters (include/liogpu.h lio_median_fill_config)."""
+    _fields_ = [("fill_hole_radius", C.c_double), ("existing_value_radius", C.c_double), ("filter_existing_values", C.c_int32),
+                ("num_erode_dilation_iterations", C.c_int32)]
+
+
+class MedianFillInfo(C.Structure):
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("fill_radius_cells", C.c_int32), ("existing_radius_cells", C.c_int32),
+                ("n_nan_in", C.c_int32), ("n_mask", C.c_int32), ("n_filled", C.c_int32), ("n_filtered", C.c_int32),
+                ("n_nan_out", C.c_int32), ("pad", C.c_int32)]
+
+
+class PlanningMapBuffers(C.Structure):
+    """the host buffers of lio_kf_store_planning_map, each with its capacity in floats (lio_planning_map_buffers)"""
+    _fields_ = [("grid", C.c_void_p), ("grid_cap", C.c_size_t), ("filled", C.c_void_p), ("filled_cap", C.c_size_t),
+                ("fill_mask", C.c_void_p), ("fill_mask_cap", C.c_size_t), ("layers", C.c_void_p), ("layers_cap", C.c_size_t)]
+
+
 SDF_NODE_LIMIT = 1 << 25
 STAGED_DS, STAGED_RAW = 0, 1
 
@@ -279,6 +297,7 @@ EXPORTS = [
     "lio_s2m_kernel_variant", "lio_s2m_launch_forms",
     "lio_sdf_default_config", "lio_sdf_create", "lio_sdf_destroy", "lio_sdf_build", "lio_kf_store_sdf", "lio_sdf_nodes", "lio_sdf_query",
     "lio_occupancy_sdf", "lio_sdf_debug_stage_ms", "lio_sdf_memory",
+    "lio_median_fill_default_config", "lio_median_fill", "lio_kf_store_planning_map",
     "lio_debug_fast_f32_ops", "lio_debug_threshold_f32", "lio_debug_grid_plan",
 ]
 
@@ -442,6 +461,13 @@ def load_library():
     L.lio_occupancy_sdf.argtypes = [i32, vp, i32, i32, f32, i32, vp]
     L.lio_sdf_debug_stage_ms.argtypes = [i32, C.POINTER(f32)]
     L.lio_sdf_memory.argtypes = [vp, C.POINTER(sz), C.POINTER(sz)]
+    L.lio_median_fill_default_config.argtypes = [C.POINTER(MedianFillConfig)]
+    L.lio_median_fill_default_config.restype = None
+    L.lio_median_fill.argtypes = [i32, vp, i32, i32, f64, C.POINTER(MedianFillConfig), vp, vp, vp, vp, C.POINTER(MedianFillInfo)]
+    L.lio_kf_store_planning_map.argtypes = [vp, C.POINTER(LocalMapConfig), C.POINTER(f32), C.POINTER(HeightMapConfig), C.POINTER(MedianFillConfig),
+                                            C.POINTER(TerrainConfig), vp, C.POINTER(SdfConfig), C.POINTER(PlanningMapBuffers),
+                                            C.POINTER(LocalMapInfo), C.POINTER(HeightMapInfo), C.POINTER(MedianFillInfo), C.POINTER(TerrainInfo),
+                                            C.POINTER(SdfInfo)]
     _LIB = L
     return L
 
@@ -1323,6 +1349,37 @@ class Sdf:
             pass
 
 
+# grid_map_filters' MedianFillFilter
+def median_fill_default_config(**overrides):
+    cfg = MedianFillConfig()
+    load_library().lio_median_fill_default_config(C.byref(cfg))
+    for k, v in overrides.items():
+        if not hasattr(cfg, k):
+            raise AttributeError(k)
+        setattr(cfg, k, v)
+    return cfg
+
+
+def median_fill(grid, resolution, cfg=None, mask_in=None, want_fill_mask=True, want_cleaned_mask=False, device_id=0):
+    """-> (filled grid [rows, cols] float32, fill mask or None, cleaned mask or None, MedianFillInfo).  grid: [rows, cols]
+    float32, non-finite = hole; mask_in: the fill mask of a previous run (non-zero = fill), used as it is."""
+    cfg = cfg or median_fill_default_config()
+    g = np.asfortranarray(np.asarray(grid, np.float32))
+    if g.ndim != 2:
+        raise ValueError("grid must be [rows, cols]")
+    m = None if mask_in is None else np.asfortranarray(np.asarray(mask_in, np.float32))
+    if m is not None and m.shape != g.shape:
+        raise ValueError("mask_in must have the grid's shape")
+    filled = np.empty(g.shape, np.float32, order="F")
+    mask = np.empty(g.shape, np.float32, order="F") if want_fill_mask else None
+    cleaned = np.empty(g.shape, np.float32, order="F") if want_cleaned_mask and m is None else None
+    info = MedianFillInfo()
+    ptr = lambda a: None if a is None else a.ctypes.data
+    _check(load_library().lio_median_fill(device_id, g.ctypes.data, g.shape[0], g.shape[1], float(resolution), C.byref(cfg), ptr(m), filled.ctypes.data,
+                                          ptr(mask), ptr(cleaned), C.byref(info)), "lio_median_fill")
+    return filled, mask, cleaned, info
+
+
 # signedDistanceFromOccupancy (SignedDistance2d.cpp:272-287) on the data of a nav_msgs/OccupancyGrid
 def occupancy_sdf(grid, resolution, occupied_min=100, device_id=0):
     """-> [height, width] float32 in the grid's layout.  grid: [height, width] int8, row-major as occupancy_grid returns it."""
@@ -1509,6 +1566,44 @@ class KeyframeStore:
         n = hm_info.rows * hm_info.cols
         elev = grid[:n].reshape((hm_info.rows, hm_info.cols), order="F").copy(order="F") if want_grid else None
         return elev, info, hm_info, lm_info
+
+    def planning_map(self, pose, lm_cfg=None, hm_cfg=None, fill_cfg=None, terrain_cfg=None, sdf=None, sdf_cfg=None, want_grid=True,
+                     want_filled=True, want_fill_mask=True):
+        """The height map's chain once, then the median fill (fill_cfg), the terrain layers (terrain_cfg) and the field (sdf, an
+        Sdf) on the grid it leaves on the device; a stage whose argument is None is absent.  -> dict: grid, filled, fill_mask
+        ([rows, cols] or None), layers ({name: [rows, cols]} or None), lm_info, hm_info, fill_info, terrain_info, sdf_info."""
+        lm_cfg = lm_cfg or local_map_default_config()
+        hm_cfg = hm_cfg or height_map_default_config()
+        if sdf is not None and sdf_cfg is None:
+            sdf_cfg = sdf_default_config()
+        p = np.ascontiguousarray(pose, np.float32).reshape(6)
+        n_layers = bin(terrain_cfg.layers & 0xff).count("1") if terrain_cfg is not None else 0
+        lm_info, hm_info, fill_info, terrain_info, sdf_info = LocalMapInfo(), HeightMapInfo(), MedianFillInfo(), TerrainInfo(), SdfInfo()
+        if sdf is not None:
+            sdf.info = sdf_info
+        want_filled = want_filled and fill_cfg is not None
+        want_fill_mask = want_fill_mask and fill_cfg is not None
+        ref = lambda c: None if c is None else C.byref(c)
+        cells = _SCRATCH_CELLS.get("planning_map", 1 << 16)
+        while True:
+            bufs = {k: _scratch("planning_" + k, (max(cells * m, 1),)) for k, m in (("grid", 1), ("filled", 1), ("fill_mask", 1), ("layers", n_layers))}
+            io = PlanningMapBuffers()
+            for k, want in (("grid", want_grid), ("filled", want_filled), ("fill_mask", want_fill_mask), ("layers", n_layers > 0)):
+                setattr(io, k, bufs[k].ctypes.data if want else None)
+                setattr(io, k + "_cap", bufs[k].size if want else 0)
+            rc = self.lib.lio_kf_store_planning_map(self.h, C.byref(lm_cfg), _f32p(p), C.byref(hm_cfg), ref(fill_cfg), ref(terrain_cfg),
+                                                    sdf.h if sdf is not None else None, ref(sdf_cfg), C.byref(io), C.byref(lm_info),
+                                                    C.byref(hm_info), C.byref(fill_info), C.byref(terrain_info), C.byref(sdf_info))
+            if rc == -1 and hm_info.rows * hm_info.cols > cells:
+                cells = _SCRATCH_CELLS["planning_map"] = hm_info.rows * hm_info.cols
+                continue
+            _check(rc, "lio_kf_store_planning_map")
+            break
+        n, shape = hm_info.rows * hm_info.cols, (hm_info.rows, hm_info.cols)
+        take = lambda k, want: bufs[k][:n].reshape(shape, order="F").copy(order="F") if want else None
+        return dict(grid=take("grid", want_grid), filled=take("filled", want_filled), fill_mask=take("fill_mask", want_fill_mask),
+                    layers=_terrain_layers_out(bufs["layers"], terrain_info, terrain_cfg.layers) if n_layers else None,
+                    lm_info=lm_info, hm_info=hm_info, fill_info=fill_info, terrain_info=terrain_info, sdf_info=sdf_info)
 
     def global_map(self, cfg=None, want_ids=True, want_output=True):   # publishGlobalMap, MO:992-1041
         """-> (cloud [m,4] or None, ids (the kept list, duplicates included) or None, GlobalMapInfo)."""

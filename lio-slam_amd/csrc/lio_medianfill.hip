@@ -1,0 +1,281 @@
+// lio_medianfill.hip -- grid_map_filters' MedianFillFilter on the elevation grid the height map leaves on the device: the
+// inpainting the reference asks for in front of the terrain chain and the signed distance field (SignedDistanceField.cpp:46-51).
+//   k_mf_mask   the validity mask of a tile with the halo of all four box operations, opened (cleanedMask) and closed
+//               (fillHoles) in LDS: eight separable passes over two byte planes, each window clipped to the grid, so a cell
+//               outside the image never takes part (morphologyDefaultBorderValue) and nothing has to be reset between an
+//               erosion and a dilation.  Every pass is computed for the whole staged region; what a pass cannot know (its
+//               window leaves the region) lies in the rim the next passes no longer read.
+//   k_mf_fill   update(): one lane per cell on the 32 x 8 tile of lio_terrain.h staged with the halo of the larger radius.
+//               A lane that fills selects the median by counting over the LDS window (lio_mf_median): 33 (2R + 1)^2 reads,
+//               none for a lane that copies.  The five counts by ballot, one atomic per wave and counter.
+// The per-cell arithmetic is lio_medianfill.h's.  DESIGN.md section 4j: conventions, resources, what was measured.
+// Also here: lio_kf_store_planning_map, the one chain that feeds the filled grid to the terrain layers and the field.
+#include <hip/hip_runtime.h>
+#include <float.h>
+#include <math.h>
+#include <cmath>
+#include <string.h>
+
+#include "lio_medianfill.h"
+#include "lio_cloud.h"
+#include "lio_heightmap.h"
+#include "lio_kfstore.h"
+#include "lio_localmap.h"
+#include "lio_pool.h"
+#include "lio_sdf.h"
+#include "lio_terrain.h"
+
+struct MfLine {                    // a line of a byte plane in LDS: entry k at p[k * stride]
+    const unsigned char* p;
+    int stride;
+    __device__ __forceinline__ unsigned at(int k) const { return p[k * stride]; }
+};
+
+// fill_mask, cleaned (may be NULL): rows x cols floats, 0.0f / 1.0f as cv2eigen leaves a Mat_<bool>
+__global__ __launch_bounds__(TERR_ROWS * TERR_COLS) void k_mf_mask(LioMfParams P, const float* __restrict__ in, float* __restrict__ fill_mask,
+                                                                    float* __restrict__ cleaned)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_planes[];
+    const int h = P.halo_mask, pitch = TERR_ROWS + 2 * h, width = TERR_COLS + 2 * h, n = pitch * width;
+    const int tiles_r = (P.rows + TERR_ROWS - 1) / TERR_ROWS;
+    const int r0 = ((int)blockIdx.x % tiles_r) * TERR_ROWS - h, c0 = ((int)blockIdx.x / tiles_r) * TERR_COLS - h;   // the region's first cell
+    unsigned char* a = s_planes;
+    unsigned char* b = s_planes + n;
+    for (int k = (int)threadIdx.x; k < n; k += TERR_ROWS * TERR_COLS) {
+        const int i = r0 + k % pitch, j = c0 + k / pitch;
+        a[k] = (i >= 0 && i < P.rows && j >= 0 && j < P.cols && lio_mf_finite(in[(size_t)i + (size_t)j * (size_t)P.rows])) ? 1 : 0;
+    }
+    __syncthreads();
+    // the part of the region that lies in the grid, in the region's own indices
+    const int i_min = r0 < 0 ? -r0 : 0, i_max = (P.rows - 1 - r0 < pitch - 1) ? P.rows - 1 - r0 : pitch - 1;
+    const int j_min = c0 < 0 ? -c0 : 0, j_max = (P.cols - 1 - c0 < width - 1) ? P.cols - 1 - c0 : width - 1;
+    const int ti = h + ((int)threadIdx.x % TERR_ROWS), tj = h + ((int)threadIdx.x / TERR_ROWS);      // this lane's cell
+    const bool in_grid = r0 + ti < P.rows && c0 + tj < P.cols;
+    const size_t at = (size_t)(r0 + ti) + (size_t)(c0 + tj) * (size_t)P.rows;
+    for (int op = 0; op < LIO_MF_N_OPS; ++op) {
+        const int R = lio_mf_op_radius(P, op);
+        const bool erode = lio_mf_op_erodes(op);
+        if (R > 0) {                                       // (N = 0: no erosion at all)
+            for (int k = (int)threadIdx.x; k < n; k += TERR_ROWS * TERR_COLS) {        // along the rows: a -> b
+                const int i = k % pitch, j = k / pitch;
+                const MfLine line = { a + j * pitch, 1 };
+                b[k] = (unsigned char)lio_mf_line(line, i - R < i_min ? i_min : i - R, i + R > i_max ? i_max : i + R, erode);
+            }
+            __syncthreads();
+            for (int k = (int)threadIdx.x; k < n; k += TERR_ROWS * TERR_COLS) {        // along the columns: b -> a
+                const int i = k % pitch, j = k / pitch;
+                const MfLine line = { b + i, pitch };
+                a[k] = (unsigned char)lio_mf_line(line, j - R < j_min ? j_min : j - R, j + R > j_max ? j_max : j + R, erode);
+            }
+            __syncthreads();
+        }
+        if (op == LIO_MF_OP_CLEANED && cleaned && in_grid) cleaned[at] = a[ti + tj * pitch] ? 1.0f : 0.0f;
+    }
+    if (in_grid) fill_mask[at] = a[ti + tj * pitch] ? 1.0f : 0.0f;
+}
+
+// counters[0..4] += non-finite input cells, non-zero mask cells, cells filled, finite cells filtered, non-finite output cells
+__global__ __launch_bounds__(TERR_ROWS * TERR_COLS) void k_mf_fill(LioMfParams P, const float* __restrict__ in, const float* __restrict__ mask,
+                                                                    float* __restrict__ out, int* __restrict__ counters)
+{
+    extern __shared__ __attribute__((aligned(16))) float s_tile[];
+    int r, c;
+    const TerrTile T = terr_stage(in, P.rows, P.cols, P.halo_fill, s_tile, r, c);
+    LioMfCell o;
+    o.nan_in = o.masked = o.filled = o.filtered = o.nan_out = false;
+    if (r < P.rows && c < P.cols) {
+        const size_t at = (size_t)r + (size_t)c * (size_t)P.rows;
+        lio_mf_cell(P, T, mask[at], r, c, &o);
+        out[at] = o.out;
+    }
+    const unsigned long long m0 = __ballot(o.nan_in), m1 = __ballot(o.masked), m2 = __ballot(o.filled), m3 = __ballot(o.filtered),
+                             m4 = __ballot(o.nan_out);
+    if ((threadIdx.x & 63) == 0) {
+        if (m0) atomicAdd(&counters[0], __popcll(m0));
+        if (m1) atomicAdd(&counters[1], __popcll(m1));
+        if (m2) atomicAdd(&counters[2], __popcll(m2));
+        if (m3) atomicAdd(&counters[3], __popcll(m3));
+        if (m4) atomicAdd(&counters[4], __popcll(m4));
+    }
+}
+
+// ---- the host side ------------------------------------------------------------------------------------------------------
+extern "C" void lio_median_fill_default_config(lio_median_fill_config* cfg)
+{
+    if (!cfg) return;
+    memset(cfg, 0, sizeof(*cfg));
+    cfg->fill_hole_radius = 0.05;                          // the constructor's, MedianFillFilter.cpp:24-25
+    cfg->existing_value_radius = 0.0;
+    cfg->filter_existing_values = 0;
+    cfg->num_erode_dilation_iterations = 4;
+}
+
+int lio_median_fill_check(const lio_median_fill_config* c, double resolution, LioMfParams* P)
+{
+    memset(P, 0, sizeof(*P));
+    if (!(resolution >= 1e-4) || !std::isfinite(resolution)) return lio_fail(LIO_ERR_ARG, "resolution must be at least 1e-4");
+    const double radii[] = { c->fill_hole_radius, c->existing_value_radius };
+    int cells[2];
+    for (int k = 0; k < 2; ++k) {
+        if (!std::isfinite(radii[k]) || radii[k] < 0.0) return lio_fail(LIO_ERR_ARG, "radii must be finite and not negative");
+        const double q = radii[k] / resolution;            // static_cast<size_t>(radius / resolution): truncated
+        if (!(q < (double)(LIO_TERR_MAX_CELLS + 1))) return lio_fail(LIO_ERR_ARG, "a radius reaches further than 32 cells");
+        cells[k] = (int)q;
+    }
+    if (c->filter_existing_values != 0 && c->filter_existing_values != 1) return lio_fail(LIO_ERR_ARG, "filter_existing_values is 0 or 1");
+    if (c->num_erode_dilation_iterations < 0 || c->num_erode_dilation_iterations > LIO_MF_MAX_ITERATIONS)
+        return lio_fail(LIO_ERR_ARG, "num_erode_dilation_iterations must be in [0, 15]");
+    P->r_fill = cells[0]; P->r_existing = cells[1];
+    P->filter_existing = c->filter_existing_values;
+    P->n_iter = c->num_erode_dilation_iterations;
+    P->n_dilate = P->n_iter > 1 ? P->n_iter : 1;           // one dilation before the loop that starts at 1
+    P->halo_mask = 2 + P->n_dilate + P->n_iter;
+    P->halo_fill = (P->filter_existing && P->r_existing > P->r_fill) ? P->r_existing : P->r_fill;
+    return LIO_OK;
+}
+
+static void mf_info_begin(lio_median_fill_info* info, const LioMfParams& P, int rows, int cols)
+{
+    memset(info, 0, sizeof(*info));
+    info->rows = rows; info->cols = cols;
+    info->fill_radius_cells = P.r_fill; info->existing_radius_cells = P.r_existing;
+}
+
+int lio_median_fill_device(const float* d_in, const LioMfParams& P, const float* mask_in, float* d_filled, float* filled, float* fill_mask,
+                           float* cleaned_mask, lio_median_fill_info* info, hipStream_t s)
+{
+    const size_t n_cells = (size_t)P.rows * (size_t)P.cols;
+    LioTemp mask, cleaned, counters;
+    HIPCHK(mask.alloc(sizeof(float) * n_cells));
+    HIPCHK(counters.alloc(5 * sizeof(int)));
+    HIPCHK(hipMemsetAsync(counters.p, 0, 5 * sizeof(int), s));
+    const unsigned tiles = (unsigned)((P.rows + TERR_ROWS - 1) / TERR_ROWS) * (unsigned)((P.cols + TERR_COLS - 1) / TERR_COLS);
+    if (mask_in) {                                         // :119-125: the mask of a previous run, as it is
+        HIPCHK(hipMemcpyAsync(mask.p, mask_in, sizeof(float) * n_cells, hipMemcpyHostToDevice, s));
+    } else {
+        if (cleaned_mask) HIPCHK(cleaned.alloc(sizeof(float) * n_cells));
+        const size_t lds = 2 * (size_t)(TERR_ROWS + 2 * P.halo_mask) * (size_t)(TERR_COLS + 2 * P.halo_mask);
+        hipLaunchKernelGGL(k_mf_mask, dim3(tiles), dim3(TERR_ROWS * TERR_COLS), lds, s, P, d_in, mask.as<float>(),
+                           cleaned_mask ? cleaned.as<float>() : nullptr);
+    }
+    const size_t lds_fill = sizeof(float) * (size_t)(TERR_ROWS + 2 * P.halo_fill) * (size_t)(TERR_COLS + 2 * P.halo_fill);
+    hipLaunchKernelGGL(k_mf_fill, dim3(tiles), dim3(TERR_ROWS * TERR_COLS), lds_fill, s, P, d_in, (const float*)mask.p, d_filled, counters.as<int>());
+    if (filled) HIPCHK(hipMemcpyAsync(filled, d_filled, sizeof(float) * n_cells, hipMemcpyDeviceToHost, s));
+    if (fill_mask) HIPCHK(hipMemcpyAsync(fill_mask, mask.p, sizeof(float) * n_cells, hipMemcpyDeviceToHost, s));
+    if (cleaned_mask && !mask_in) HIPCHK(hipMemcpyAsync(cleaned_mask, cleaned.p, sizeof(float) * n_cells, hipMemcpyDeviceToHost, s));
+    int hc[5] = { 0, 0, 0, 0, 0 };
+    HIPCHK(hipMemcpyAsync(hc, counters.p, sizeof(hc), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    info->n_nan_in = hc[0]; info->n_mask = hc[1]; info->n_filled = hc[2]; info->n_filtered = hc[3]; info->n_nan_out = hc[4];
+    return LIO_OK;
+}
+
+extern "C" int lio_median_fill(int32_t device_id, const float* elevation, int32_t rows, int32_t cols, double resolution,
+                               const lio_median_fill_config* cfg, const float* mask_in, float* filled, float* fill_mask, float* cleaned_mask,
+                               lio_median_fill_info* info)
+try {
+    if (!cfg || !info) return lio_fail(LIO_ERR_ARG, "null argument");
+    if (rows < 0 || cols < 0) return lio_fail(LIO_ERR_ARG, "rows and cols must not be negative");
+    LioMfParams P;
+    int rc = lio_median_fill_check(cfg, resolution, &P);
+    if (rc != LIO_OK) return rc;
+    mf_info_begin(info, P, rows, cols);
+    if (rows == 0 || cols == 0) return LIO_OK;             // no cell: nothing written
+    if (!elevation || !filled) return lio_fail(LIO_ERR_ARG, "null argument");
+    if ((long long)rows * cols > 0x7fffffffLL - 1024) return lio_fail(LIO_ERR_CAPACITY, "the grid has more than 2^31 cells");
+    P.rows = rows; P.cols = cols;
+    if ((rc = lio_check_device(device_id)) != LIO_OK) return rc;
+    hipStream_t s = nullptr;
+    const size_t n_cells = (size_t)rows * (size_t)cols;
+    LioTemp grid, out;
+    HIPCHK(grid.alloc(sizeof(float) * n_cells));
+    HIPCHK(out.alloc(sizeof(float) * n_cells));
+    HIPCHK(hipMemcpyAsync(grid.p, elevation, sizeof(float) * n_cells, hipMemcpyHostToDevice, s));
+    rc = lio_median_fill_device(grid.as<float>(), P, mask_in, out.as<float>(), filled, fill_mask, cleaned_mask, info, s);
+    const hipError_t e = hipStreamSynchronize(s);          // (an early return: the temporaries go back to the pool when this returns)
+    if (rc < 0) return rc;
+    HIPCHK(e);
+    return rc;
+} LIO_CATCH
+
+// The height map's chain once, then whichever of the fill, the terrain layers and the field was asked for, each on the grid
+// the stage before it left on the device: the same null stream, complete on return.
+extern "C" int lio_kf_store_planning_map(lio_kf_store* st, const lio_local_map_config* lm, const float* pose, const lio_height_map_config* hm,
+                                         const lio_median_fill_config* fill, const lio_terrain_config* terrain, lio_sdf* sdf,
+                                         const lio_sdf_config* sdf_cfg, const lio_planning_map_buffers* out, lio_local_map_info* lm_info,
+                                         lio_height_map_info* hm_info, lio_median_fill_info* fill_info, lio_terrain_info* terrain_info,
+                                         lio_sdf_info* sdf_info)
+try {
+    lio_height_map_info hm_local;
+    lio_median_fill_info fill_local;
+    lio_terrain_info terrain_local;
+    lio_sdf_info sdf_local;
+    lio_planning_map_buffers no_out;
+    memset(&no_out, 0, sizeof(no_out));
+    if (!hm_info) hm_info = &hm_local;
+    if (!fill_info) fill_info = &fill_local;
+    if (!terrain_info) terrain_info = &terrain_local;
+    if (!sdf_info) sdf_info = &sdf_local;
+    if (!out) out = &no_out;
+    memset(hm_info, 0, sizeof(*hm_info));
+    memset(fill_info, 0, sizeof(*fill_info));
+    memset(terrain_info, 0, sizeof(*terrain_info));
+    memset(sdf_info, 0, sizeof(*sdf_info));
+    if (!st || !lm || !pose || !hm || (sdf && !sdf_cfg)) return lio_fail(LIO_ERR_ARG, "null argument");
+    int rc = lio_height_map_check(hm);
+    if (rc != LIO_OK) return rc;
+    LioMfParams P;
+    LioTerrPlan plan;
+    if (fill) {
+        if ((rc = lio_median_fill_check(fill, hm->resolution, &P)) != LIO_OK) return rc;
+        mf_info_begin(fill_info, P, 0, 0);
+    }
+    if (terrain) {
+        if ((rc = lio_terrain_check(terrain, hm->resolution, &plan)) != LIO_OK) return rc;
+        terrain_info->normal_method_used = plan.method_used; terrain_info->edge_window_size = plan.window;
+    }
+    if (sdf) {
+        if ((rc = lio_sdf_config_check(sdf_cfg)) != LIO_OK) return rc;
+        if ((rc = lio_sdf_begin(sdf, st->device_id)) != LIO_OK) return rc;
+    }
+    hipStream_t s = nullptr;
+    LocalMapBufs B;
+    if ((rc = lio_local_map_device(st, lm, pose, B, nullptr, lm_info, s)) != LIO_OK) return rc;
+    if (B.n_cur == 0) return LIO_OK;                       // an empty store or an empty crop: rows = cols = 0
+    LioTemp d_grid, d_filled;
+    if (!fill && !terrain && !sdf) return lio_height_map_device(B.cur, B.n_cur, hm, out->grid, out->grid_cap, hm_info, s);      // lio_kf_store_height_map
+    rc = lio_height_map_device(B.cur, B.n_cur, hm, out->grid, out->grid_cap, hm_info, s, &d_grid);
+    const int rows = hm_info->rows, cols = hm_info->cols;
+    if (fill) { fill_info->rows = rows; fill_info->cols = cols; }
+    if (terrain) { terrain_info->rows = rows; terrain_info->cols = cols; }
+    if (sdf) { sdf_info->rows = rows; sdf_info->cols = cols; }
+    if (rc != LIO_OK) return rc;
+    if (!d_grid.p) return LIO_OK;                          // no point left or no extent along an axis: no grid, nothing behind it
+    const size_t n_cells = (size_t)rows * (size_t)cols;
+    if (fill && ((out->filled && n_cells > out->filled_cap) || (out->fill_mask && n_cells > out->fill_mask_cap)))
+        return lio_fail(LIO_ERR_ARG, "filled or fill_mask holds fewer floats than the grid has cells (info)");
+    if (terrain && out->layers && (size_t)plan.n_out * n_cells > out->layers_cap)
+        return lio_fail(LIO_ERR_ARG, "layers holds fewer floats than the requested layers (info)");
+    const float* d_elev = d_grid.as<float>();
+    if (fill) {
+        P.rows = rows; P.cols = cols;
+        HIPCHK(d_filled.alloc(sizeof(float) * n_cells));
+        if ((rc = lio_median_fill_device(d_elev, P, nullptr, d_filled.as<float>(), out->filled, out->fill_mask, nullptr, fill_info, s)) != LIO_OK) {
+            (void)hipStreamSynchronize(s);                 // (an early return leaves nothing in flight on the temporaries)
+            return rc;
+        }
+        d_elev = d_filled.as<float>();
+    }
+    if (terrain) {
+        if ((rc = lio_terrain_set_geometry(&plan, rows, cols, hm->resolution, hm_info->length, hm_info->position)) != LIO_OK) return rc;
+        rc = lio_terrain_device(d_elev, plan, out->layers, terrain_info, s);
+        if (rc != LIO_OK) { (void)hipStreamSynchronize(s); return rc; }
+    }
+    if (sdf) {
+        if ((rc = lio_sdf_check(sdf_cfg, rows, cols, hm->resolution, hm_info->length, hm_info->position)) != LIO_OK) return rc;
+        rc = lio_sdf_build_device(sdf, d_elev, rows, cols, hm->resolution, hm_info->length, hm_info->position, *sdf_cfg, sdf_info, s);
+        (void)hipStreamSynchronize(s);
+    }
+    return rc;
+} LIO_CATCH

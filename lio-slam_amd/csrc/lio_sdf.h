@@ -255,3 +255,12 @@ LIO_SDF_HD double lio_sdf_value(const LioSdfLookup& L, const N& nodes, const dou
 // ---- the host side (lio_sdf.hip) --------------------------------------------------------------------------------------------
 // what can be refused before any device is touched: LIO_OK or LIO_ERR_ARG
 int lio_sdf_check(const lio_sdf_config* cfg, int rows, int cols, double resolution, const double length[2], const double position[2]);
+// the configuration alone: LIO_OK or LIO_ERR_ARG
+int lio_sdf_config_check(const lio_sdf_config* cfg);
+// What a chained entry point does before its first launch: LIO_ERR_ARG for an object on another device than `device_id`; the
+// object then holds no field until a build succeeds.
+int lio_sdf_begin(lio_sdf* sdf, int device_id);
+// SignedDistanceField's constructor on the device grid d_elev (rows x cols, column-major) on stream s, for an entry point that
+// has the grid on the device already; the geometry was checked (lio_sdf_check).  Synchronous.
+int lio_sdf_build_device(lio_sdf* sdf, const float* d_elev, int rows, int cols, double resolution, const double* length, const double* position,
+                         const lio_sdf_config& cfg, lio_sdf_info* info, hipStream_t s);

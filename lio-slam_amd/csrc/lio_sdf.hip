@@ -254,9 +254,11 @@ void sdf_launch_slab(const SdfPass& P, const void* src, float* mid, float* dist,
     if (clk) clk->mark(s);
 }
 
+}  // namespace
+
 // SignedDistanceField's constructor on a device grid; synchronous.  The geometry was checked (lio_sdf_check).
-int sdf_build_device(lio_sdf* sdf, const float* d_elev, int rows, int cols, double resolution, const double* length, const double* position,
-                     const lio_sdf_config& cfg, lio_sdf_info* info, hipStream_t s)
+int lio_sdf_build_device(lio_sdf* sdf, const float* d_elev, int rows, int cols, double resolution, const double* length, const double* position,
+                         const lio_sdf_config& cfg, lio_sdf_info* info, hipStream_t s)
 {
     sdf->built = false;
     memset(info, 0, sizeof(*info));
@@ -334,7 +336,7 @@ int sdf_build_device(lio_sdf* sdf, const float* d_elev, int rows, int cols, doub
     return LIO_OK;
 }
 
-int sdf_config_check(const lio_sdf_config* cfg)
+int lio_sdf_config_check(const lio_sdf_config* cfg)
 {
     if (!cfg) return lio_fail(LIO_ERR_ARG, "null argument");
     if (cfg->nan_policy != 0 && cfg->nan_policy != 1) return lio_fail(LIO_ERR_ARG, "nan_policy is 0 (refuse) or 1 (the smallest finite elevation)");
@@ -343,11 +345,16 @@ int sdf_config_check(const lio_sdf_config* cfg)
     return LIO_OK;
 }
 
-}  // namespace
+int lio_sdf_begin(lio_sdf* sdf, int device_id)
+{
+    if (device_id != sdf->device_id) return lio_fail(LIO_ERR_ARG, "the keyframe store and the sdf live on different devices");
+    sdf->built = false;
+    return LIO_OK;
+}
 
 int lio_sdf_check(const lio_sdf_config* cfg, int rows, int cols, double resolution, const double length[2], const double position[2])
 {
-    int rc = sdf_config_check(cfg);
+    int rc = lio_sdf_config_check(cfg);
     if (rc != LIO_OK) return rc;
     if (!length || !position) return lio_fail(LIO_ERR_ARG, "null argument");
     if (rows < 2 || cols < 2) return lio_fail(LIO_ERR_ARG, "rows and cols must be at least 2 (the finite differences)");
@@ -404,7 +411,7 @@ try {
     const size_t cells = (size_t)rows * (size_t)cols;
     HIPCHK(sdf->d_elev.grow(cells, 1.0, 64, true));
     HIPCHK(hipMemcpyAsync(sdf->d_elev.p, elevation, sizeof(float) * cells, hipMemcpyHostToDevice, s));
-    rc = sdf_build_device(sdf, sdf->d_elev.p, rows, cols, resolution, length, position, *cfg, info, s);
+    rc = lio_sdf_build_device(sdf, sdf->d_elev.p, rows, cols, resolution, length, position, *cfg, info, s);
     const hipError_t e = hipStreamSynchronize(s);
     if (rc < 0) return rc;
     HIPCHK(e);
@@ -425,9 +432,8 @@ try {
     if (!st || !lm || !pose || !hm || !cfg || !sdf) return lio_fail(LIO_ERR_ARG, "null argument");
     int rc = lio_height_map_check(hm);
     if (rc != LIO_OK) return rc;
-    if ((rc = sdf_config_check(cfg)) != LIO_OK) return rc;
-    if (st->device_id != sdf->device_id) return lio_fail(LIO_ERR_ARG, "the keyframe store and the sdf live on different devices");
-    sdf->built = false;
+    if ((rc = lio_sdf_config_check(cfg)) != LIO_OK) return rc;
+    if ((rc = lio_sdf_begin(sdf, st->device_id)) != LIO_OK) return rc;
     hipStream_t s = nullptr;
     LocalMapBufs B;
     if ((rc = lio_local_map_device(st, lm, pose, B, nullptr, lm_info, s)) != LIO_OK) return rc;
@@ -438,7 +444,7 @@ try {
     if (rc != LIO_OK) return rc;
     if (!d_grid.p) return LIO_OK;                          // no point left or no extent along an axis: no grid, no field
     if ((rc = lio_sdf_check(cfg, hm_info->rows, hm_info->cols, hm->resolution, hm_info->length, hm_info->position)) != LIO_OK) return rc;
-    rc = sdf_build_device(sdf, d_grid.as<float>(), hm_info->rows, hm_info->cols, hm->resolution, hm_info->length, hm_info->position, *cfg, info, s);
+    rc = lio_sdf_build_device(sdf, d_grid.as<float>(), hm_info->rows, hm_info->cols, hm->resolution, hm_info->length, hm_info->position, *cfg, info, s);
     (void)hipStreamSynchronize(s);                         // (an early return leaves nothing in flight on `d_grid`)
     return rc;
 } LIO_CATCH

@@ -20,34 +20,6 @@
 #include "lio_localmap.h"
 #include "lio_pool.h"
 
-#define TERR_ROWS 32               // the tile: rows are the contiguous axis of the column-major grid, a wave covers 32 x 2
-#define TERR_COLS 8
-
-struct TerrTile {                  // the LDS tile: rows [r0, r0 + pitch), columns from c0
-    const float* t;
-    int r0, c0, pitch;
-    __device__ __forceinline__ float at(int i, int j) const { return t[(i - r0) + (j - c0) * pitch]; }
-};
-
-// The workgroup's tile of `src` and h cells around it -> LDS (NaN outside the grid); the cell of this lane -> (r, c).
-// Ends with the barrier.
-__device__ __forceinline__ TerrTile terr_stage(const float* __restrict__ src, int rows, int cols, int h, float* tile, int& r, int& c)
-{
-    const int tiles_r = (rows + TERR_ROWS - 1) / TERR_ROWS;
-    const int tr0 = ((int)blockIdx.x % tiles_r) * TERR_ROWS, tc0 = ((int)blockIdx.x / tiles_r) * TERR_COLS;
-    const int pitch = TERR_ROWS + 2 * h, n = pitch * (TERR_COLS + 2 * h);
-    for (int k = (int)threadIdx.x; k < n; k += TERR_ROWS * TERR_COLS) {
-        const int i = tr0 - h + k % pitch, j = tc0 - h + k / pitch;
-        tile[k] = (i >= 0 && i < rows && j >= 0 && j < cols) ? src[(size_t)i + (size_t)j * (size_t)rows] : LIO_TERR_NAN;
-    }
-    __syncthreads();
-    r = tr0 + ((int)threadIdx.x % TERR_ROWS);
-    c = tc0 + ((int)threadIdx.x / TERR_ROWS);
-    TerrTile T;
-    T.t = tile; T.r0 = tr0 - h; T.c0 = tc0 - h; T.pitch = pitch;
-    return T;
-}
-
 // out: LIO_TERRAIN_N_LAYERS layers of rows x cols (this kernel writes all but LIO_TERRAIN_EDGES).  counters[0..3] += finite
 // input cells, normals written, circles of fewer than 3 points, degenerate covariances.
 __global__ __launch_bounds__(TERR_ROWS * TERR_COLS) void k_terr_main(LioTerrParams P, const float* __restrict__ in, float* __restrict__ out,
