@@ -1146,6 +1146,91 @@ int  lio_kf_store_planning_map(lio_kf_store *s, const lio_local_map_config *lm, 
                                lio_height_map_info *hm_info, lio_median_fill_info *fill_info,
                                lio_terrain_info *terrain_info, lio_sdf_info *sdf_info);
 
+/* ------------------------------------------------ resident planning layers, sampled on the device (GridMap::atPosition) */
+/* grid_map_core's GridMap::atPosition with its four InterpolationMethods (GridMap.cpp:161-210, :777-846,
+ * CubicInterpolation.cpp): what a planner asks of the elevation grid and the terrain layers, once per trajectory point and
+ * footprint corner.  The layers stay on the device in a lio_grid; only positions go up and values come down.  DESIGN.md
+ * section 4k states the conventions.  Every operation is fp64 in the reference's order on taps widened from float; parity is
+ * against the restatement (tests/grid_sample_restate.py), with the reference's own test values on top (parity unpinned:
+ * Eigen and grid_map are restated, not linked). */
+typedef struct lio_grid lio_grid;
+#define LIO_GRID_MAX_LAYERS 16
+enum { LIO_GRID_NEAREST = 0, LIO_GRID_LINEAR = 1, LIO_GRID_CUBIC_CONVOLUTION = 2, LIO_GRID_CUBIC = 3,   /* InterpolationMethods, TypeDefs.hpp:39-44 */
+       LIO_GRID_OUTSIDE = 255 };                                                                       /* method used: the position is not in the map */
+/* the layers lio_kf_store_planning_grid leaves: the raw grid, the filled grid, then the terrain layers in their enum order */
+enum { LIO_GRID_LAYER_ELEVATION = 0, LIO_GRID_LAYER_FILLED = 1, LIO_GRID_LAYER_TERRAIN = 2 };
+typedef struct lio_grid_sample_config {
+    int32_t method;               /* LIO_GRID_NEAREST .. LIO_GRID_CUBIC                                        0 */
+    int32_t border_mode;          /* 0: tap indices wrap and fail as the reference's do; 1: labelled extension --
+                                   * every tap index of the three interpolating methods clamped into the grid  0 */
+} lio_grid_sample_config;
+typedef struct lio_grid_sample_info {
+    int64_t n_outside;            /* (layer, position) pairs answered LIO_GRID_OUTSIDE: the positions outside x the layers */
+    int64_t n_method[4];          /* pairs per method used; with n_outside they sum to n_layers x n             */
+} lio_grid_sample_info;
+typedef struct lio_grid_desc {
+    int32_t  rows, cols;          /* 0, 0: the object holds no layer                                            */
+    double   resolution, length[2], position[2];
+    uint32_t layer_mask;          /* bit k set: layer k is present                                              */
+    int32_t  pad;
+} lio_grid_desc;                 /* what lio_grid_info reports */
+void lio_grid_sample_default_config(lio_grid_sample_config *cfg);   /* nearest, 0 */
+/* The object owns up to LIO_GRID_MAX_LAYERS column-major rows x cols float layers on one device, each kept between calls and
+ * grown, never shrunk.  Calls on one object are non-re-entrant.  Destroying NULL does nothing. */
+int  lio_grid_create(int32_t device_id, lio_grid **out);
+void lio_grid_destroy(lio_grid *g);
+/* Uploads n_layers host layers, laid out layer after layer, each rows x cols floats, column-major (grid_map::Matrix), as
+ * layers 0 .. n_layers - 1; what the object held is replaced.  `length` and `position` are the grid map's.  LIO_ERR_ARG
+ * before any device is touched, never a clamp: null arguments, n_layers outside 1 .. 16, rows or cols < 1 or >= 2^24,
+ * non-finite length or position, resolution < 1e-4 or not finite, length[a] != size[a] * resolution.  More than 2^31 - 1024
+ * cells a layer: LIO_ERR_CAPACITY.  Complete on return. */
+int  lio_grid_set_layers(lio_grid *g, const float *layers, int32_t n_layers, int32_t rows, int32_t cols, double resolution,
+                         const double length[2], const double position[2]);
+/* Layer `layer` to the host.  An absent layer, or cap_floats < rows x cols: LIO_ERR_ARG. */
+int  lio_grid_get_layer(lio_grid *g, int32_t layer, float *out, size_t cap_floats);
+/* The geometry and the layers present.  Never touches a device. */
+int  lio_grid_info(lio_grid *g, lio_grid_desc *info);
+/* The device memory the object holds now, in bytes. */
+int  lio_grid_memory(lio_grid *g, size_t *bytes);
+/* atPosition for n positions (x, y as doubles, pair after pair) on the n_layers layers named by layer_ids, in that order:
+ * values[k * n + q] is layer layer_ids[k] at position q, method_used (may be NULL) the same for the method that produced it,
+ * 0 .. 3 in the reference's enum order, or LIO_GRID_OUTSIDE.  The position's cell, the taps and the normalised coordinates
+ * are formed once per position; the taps are gathered and the fall-back chain of GridMap.cpp:161-204 runs per layer:
+ *  - outside: the position fails checkIfPositionWithinMap (GridMapMath.cpp:162-172: above the high edge or at or below the
+ *    low edge of either axis; non-finite), or its index does.  Nothing is read, the value is the quiet NaN 0x7fc00000.  A
+ *    labelled deviation: the reference throws there (its linear step can "succeed" on wrapped cells by accident);
+ *  - nearest: the cell's bits, NaN payloads and infinities included;
+ *  - linear (GridMap.cpp:777-846): the four taps around the position, each tested through its column-major linear index
+ *    alone, so a row index of `rows` reads row 0 of the next column and -1 the last row of the column before -- for positions
+ *    inside the map, reproduced as written; a tap whose linear index is negative or >= rows x cols fails and the query falls
+ *    back to nearest (the reference lets rows x cols itself pass and reads one float past the buffer: labelled deviation).
+ *    No finiteness test: a non-finite tap gives NaN with method used = linear;
+ *  - cubic convolution (CubicInterpolation.cpp:44-135) and bicubic (:150-432): 16 taps, resp. 4 corners with their central
+ *    differences; indices are bound as unsigned, so an index below 0 goes to the last row or column, as written; a result
+ *    that is not finite falls back to linear, and linear to nearest;
+ *  - border_mode 1: every tap index of the three interpolating methods is formed in int and clamped into the grid; no wrap,
+ *    no linear-index test, nothing else changed.
+ * info (may be NULL): the counts of the call.  n = 0: LIO_OK.  LIO_ERR_ARG: null arguments, an object without layers,
+ * n_layers < 1 or > 16, an absent or repeated layer id, a method outside 0 .. 3, a border mode outside 0 / 1.  More than
+ * 2^27 positions: LIO_ERR_CAPACITY.  Complete on return, one host wait per call. */
+int  lio_grid_sample(lio_grid *g, const int32_t *layer_ids, int32_t n_layers, const lio_grid_sample_config *cfg,
+                     const double *positions, size_t n, float *values, uint8_t *method_used, lio_grid_sample_info *info);
+/* lio_kf_store_planning_map (same arguments, same bytes in every buffer and info), which also leaves its grids in grid_out
+ * by device-to-device copy: layer 0 the raw elevation grid, layer 1 the filled grid (with fill), layers 2 .. 9 the eight
+ * terrain layers in enum order (with terrain; all eight, whatever terrain->layers copies to the host).  The geometry is
+ * hm_info's.  grid_out == NULL: lio_kf_store_planning_map.  An empty store or an empty map leaves the object without
+ * layers.  A store and a grid on different devices: LIO_ERR_ARG. */
+int  lio_kf_store_planning_grid(lio_kf_store *s, const lio_local_map_config *lm, const float pose[6],
+                                const lio_height_map_config *hm, const lio_median_fill_config *fill,
+                                const lio_terrain_config *terrain, lio_sdf *sdf, const lio_sdf_config *sdf_cfg,
+                                const lio_planning_map_buffers *out, lio_local_map_info *lm_info,
+                                lio_height_map_info *hm_info, lio_median_fill_info *fill_info,
+                                lio_terrain_info *terrain_info, lio_sdf_info *sdf_info, lio_grid *grid_out);
+/* Measurement hook (tools/grid_sample_cost.py): enable != 0 makes the calling thread's following sampling calls record their
+ * stage boundaries as HIP events; ms (may be NULL) receives the last such call's positions up, kernel and values down, in
+ * milliseconds. */
+int  lio_grid_debug_stage_ms(int32_t enable, float ms[3]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -303,6 +303,23 @@ public:
                                         terrain_info, sdf_info), "lio_kf_store_planning_map");
         return (size_t)hm_info.rows * (size_t)hm_info.cols;
     }
+    // planningMap, which also leaves its grids on the device in `grid` (a GridLayers below, may be nullptr): layer 0 the raw
+    // grid, layer 1 the filled grid, layers 2 .. 9 the terrain layers.  `out` may name no buffer at all: then only positions go
+    // up and values come down (GridLayers::atPosition).
+    size_t planningGrid(const float transformTobeMapped[6], lio_grid* grid, const lio_planning_map_buffers& out, const lio_median_fill_config* fill,
+                        const lio_terrain_config* terrain, lio_sdf* sdf, const lio_sdf_config* sdf_cfg, lio_height_map_info& hm_info,
+                        lio_median_fill_info* fill_info = nullptr, lio_terrain_info* terrain_info = nullptr, lio_sdf_info* sdf_info = nullptr,
+                        const lio_height_map_config* hm_cfg = nullptr, const lio_local_map_config* lm_cfg = nullptr,
+                        lio_local_map_info* lm_info = nullptr)
+    {
+        lio_local_map_config lm;
+        if (lm_cfg) lm = *lm_cfg; else lio_local_map_default_config(&lm);
+        lio_height_map_config hm;
+        if (hm_cfg) hm = *hm_cfg; else lio_height_map_default_config(&hm);
+        check(lio_kf_store_planning_grid(s_, &lm, transformTobeMapped, &hm, fill, terrain, sdf, sdf_cfg, &out, lm_info, &hm_info, fill_info,
+                                         terrain_info, sdf_info, grid), "lio_kf_store_planning_grid");
+        return (size_t)hm_info.rows * (size_t)hm_info.cols;
+    }
     lio_kf_store* get() { return s_; }
 
 private:
@@ -350,6 +367,51 @@ private:
         if (rc < 0) throw Error(rc, std::string(what) + ": " + lio_last_error());
     }
     lio_sdf* s_ = nullptr;
+};
+
+// The layers of a grid_map::GridMap resident on the device: uploaded, or left there by KeyframeStore::planningGrid, and sampled
+// by GridMap::atPosition with its four InterpolationMethods.
+class GridLayers {
+public:
+    explicit GridLayers(int32_t device_id = 0)
+    {
+        const int rc = lio_grid_create(device_id, &g_);
+        if (rc < 0) throw Error(rc, std::string("lio_grid_create: ") + lio_last_error());
+    }
+    ~GridLayers() { lio_grid_destroy(g_); }
+    GridLayers(const GridLayers&) = delete;
+    GridLayers& operator=(const GridLayers&) = delete;
+
+    // n_layers host layers, one after the other, each column-major rows x cols (grid_map::Matrix); length and position: the grid map's
+    void setLayers(const float* layers, int32_t n_layers, int32_t rows, int32_t cols, double resolution, const double length[2], const double position[2])
+    {
+        check(lio_grid_set_layers(g_, layers, n_layers, rows, cols, resolution, length, position), "lio_grid_set_layers");
+    }
+    // atPosition(layer, position, method) for n positions (x, y) on each of the n_layers layers of layer_ids: values[k * n + q];
+    // method_used (may be nullptr) the same for the method that produced the value, LIO_GRID_OUTSIDE where the reference throws
+    void atPosition(const int32_t* layer_ids, int32_t n_layers, const double* positions, size_t n, float* values, int32_t method = LIO_GRID_NEAREST,
+                    uint8_t* method_used = nullptr, lio_grid_sample_info* info = nullptr, int32_t border_mode = 0)
+    {
+        lio_grid_sample_config c;
+        lio_grid_sample_default_config(&c);
+        c.method = method; c.border_mode = border_mode;
+        check(lio_grid_sample(g_, layer_ids, n_layers, &c, positions, n, values, method_used, info), "lio_grid_sample");
+    }
+    void layer(int32_t k, float* out, size_t cap_floats) { check(lio_grid_get_layer(g_, k, out, cap_floats), "lio_grid_get_layer"); }
+    lio_grid_desc info()
+    {
+        lio_grid_desc d;
+        check(lio_grid_info(g_, &d), "lio_grid_info");
+        return d;
+    }
+    lio_grid* get() { return g_; }
+
+private:
+    static void check(int rc, const char* what)
+    {
+        if (rc < 0) throw Error(rc, std::string(what) + ": " + lio_last_error());
+    }
+    lio_grid* g_ = nullptr;
 };
 
 // grid_map_filters' MedianFillFilter::update on a host grid, column-major rows x cols (grid_map::Matrix): `filled` receives

@@ -17,7 +17,10 @@ from .api import (LioError, ScanToMap, S2MConfig, S2MResult, S2MProfile, DeskewC
                   GlobalMapConfig, GlobalMapInfo, ExportConfig, global_map_default_config, STAGED_DS, STAGED_RAW,
                   OgmConfig, OgmInfo, ogm_default_config, radius_filter, occupancy_grid,
                   SdfConfig, SdfInfo, Sdf, SDF_NODE_LIMIT, sdf_default_config, occupancy_sdf,
-                  MedianFillConfig, MedianFillInfo, PlanningMapBuffers, median_fill, median_fill_default_config)
+                  MedianFillConfig, MedianFillInfo, PlanningMapBuffers, median_fill, median_fill_default_config,
+                  Grid, GridSampleConfig, GridSampleInfo, GridInfo, grid_sample_default_config, kf_store_planning_grid, GRID_MAX_LAYERS,
+                  GRID_NEAREST, GRID_LINEAR, GRID_CUBIC_CONVOLUTION, GRID_CUBIC, GRID_OUTSIDE, GRID_LAYER_ELEVATION, GRID_LAYER_FILLED,
+                  GRID_LAYER_TERRAIN)
 
 __all__ = ["LioError", "ScanToMap", "S2MConfig", "S2MResult", "S2MProfile", "DeskewConfig",
            "lib_path", "load_library", "build_library", "deskew", "curvature", "imu_deskew_info",
@@ -31,4 +34,7 @@ __all__ = ["LioError", "ScanToMap", "S2MConfig", "S2MResult", "S2MProfile", "Des
            "GlobalMapConfig", "GlobalMapInfo", "ExportConfig", "global_map_default_config", "STAGED_DS", "STAGED_RAW",
            "OgmConfig", "OgmInfo", "ogm_default_config", "radius_filter", "occupancy_grid",
            "SdfConfig", "SdfInfo", "Sdf", "SDF_NODE_LIMIT", "sdf_default_config", "occupancy_sdf",
-           "MedianFillConfig", "MedianFillInfo", "PlanningMapBuffers", "median_fill", "median_fill_default_config"]
+           "MedianFillConfig", "MedianFillInfo", "PlanningMapBuffers", "median_fill", "median_fill_default_config",
+           "Grid", "GridSampleConfig", "GridSampleInfo", "GridInfo", "grid_sample_default_config", "kf_store_planning_grid", "GRID_MAX_LAYERS",
+           "GRID_NEAREST", "GRID_LINEAR", "GRID_CUBIC_CONVOLUTION", "GRID_CUBIC", "GRID_OUTSIDE", "GRID_LAYER_ELEVATION", "GRID_LAYER_FILLED",
+           "GRID_LAYER_TERRAIN"]

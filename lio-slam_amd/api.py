@@ -244,6 +244,24 @@ class PlanningMapBuffers(C.Structure):
                 ("fill_mask", C.c_void_p), ("fill_mask_cap", C.c_size_t), ("layers", C.c_void_p), ("layers_cap", C.c_size_t)]
 
 
+class GridSampleConfig(C.Structure):
+    """GridMap::atPosition's interpolation method and the border mode (include/liogpu.h lio_grid_sample_config)."""
+    _fields_ = [("method", C.c_int32), ("border_mode", C.c_int32)]
+
+
+class GridSampleInfo(C.Structure):
+    _fields_ = [("n_outside", C.c_int64), ("n_method", C.c_int64 * 4)]
+
+
+class GridInfo(C.Structure):
+    """what lio_grid_info reports (include/liogpu.h lio_grid_desc)"""
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("resolution", C.c_double), ("length", C.c_double * 2), ("position", C.c_double * 2),
+                ("layer_mask", C.c_uint32), ("pad", C.c_int32)]
+
+
+GRID_MAX_LAYERS = 16
+GRID_NEAREST, GRID_LINEAR, GRID_CUBIC_CONVOLUTION, GRID_CUBIC, GRID_OUTSIDE = 0, 1, 2, 3, 255
+GRID_LAYER_ELEVATION, GRID_LAYER_FILLED, GRID_LAYER_TERRAIN = 0, 1, 2
 SDF_NODE_LIMIT = 1 << 25
 STAGED_DS, STAGED_RAW = 0, 1
 
@@ -298,6 +316,8 @@ EXPORTS = [
     "lio_sdf_default_config", "lio_sdf_create", "lio_sdf_destroy", "lio_sdf_build", "lio_kf_store_sdf", "lio_sdf_nodes", "lio_sdf_query",
     "lio_occupancy_sdf", "lio_sdf_debug_stage_ms", "lio_sdf_memory",
     "lio_median_fill_default_config", "lio_median_fill", "lio_kf_store_planning_map",
+    "lio_grid_sample_default_config", "lio_grid_create", "lio_grid_destroy", "lio_grid_set_layers", "lio_grid_get_layer", "lio_grid_info",
+    "lio_grid_memory", "lio_grid_sample", "lio_kf_store_planning_grid", "lio_grid_debug_stage_ms",
     "lio_debug_fast_f32_ops", "lio_debug_threshold_f32", "lio_debug_grid_plan",
 ]
 
@@ -468,6 +488,18 @@ def load_library():
                                             C.POINTER(TerrainConfig), vp, C.POINTER(SdfConfig), C.POINTER(PlanningMapBuffers),
                                             C.POINTER(LocalMapInfo), C.POINTER(HeightMapInfo), C.POINTER(MedianFillInfo), C.POINTER(TerrainInfo),
                                             C.POINTER(SdfInfo)]
+    L.lio_grid_sample_default_config.argtypes = [C.POINTER(GridSampleConfig)]
+    L.lio_grid_sample_default_config.restype = None
+    L.lio_grid_create.argtypes = [i32, C.POINTER(vp)]
+    L.lio_grid_destroy.argtypes = [vp]
+    L.lio_grid_destroy.restype = None
+    L.lio_grid_set_layers.argtypes = [vp, vp, i32, i32, i32, f64, C.POINTER(f64), C.POINTER(f64)]
+    L.lio_grid_get_layer.argtypes = [vp, i32, vp, sz]
+    L.lio_grid_info.argtypes = [vp, C.POINTER(GridInfo)]
+    L.lio_grid_memory.argtypes = [vp, C.POINTER(sz)]
+    L.lio_grid_sample.argtypes = [vp, C.POINTER(i32), i32, C.POINTER(GridSampleConfig), vp, sz, vp, vp, C.POINTER(GridSampleInfo)]
+    L.lio_kf_store_planning_grid.argtypes = L.lio_kf_store_planning_map.argtypes + [vp]
+    L.lio_grid_debug_stage_ms.argtypes = [i32, C.POINTER(f32)]
     _LIB = L
     return L
 
@@ -1380,6 +1412,83 @@ def median_fill(grid, resolution, cfg=None, mask_in=None, want_fill_mask=True, w
     return filled, mask, cleaned, info
 
 
+# GridMap::atPosition on layers resident on the device
+def grid_sample_default_config(**overrides):
+    cfg = GridSampleConfig()
+    load_library().lio_grid_sample_default_config(C.byref(cfg))
+    for k, v in overrides.items():
+        if not hasattr(cfg, k):
+            raise AttributeError(k)
+        setattr(cfg, k, v)
+    return cfg
+
+
+class Grid:
+    """A set of up to GRID_MAX_LAYERS [rows, cols] float32 layers resident on the device: upload them (or let
+    KeyframeStore.planning_grid leave its grids here), then sample them at positions."""
+
+    def __init__(self, device_id=0):
+        self.lib = load_library()
+        self.h = C.c_void_p()
+        _check(self.lib.lio_grid_create(device_id, C.byref(self.h)), "lio_grid_create")
+
+    def set_layers(self, layers, resolution, length, position):
+        """layers: [n_layers, rows, cols] float32 (or a list of [rows, cols]); they become layers 0 .. n_layers - 1"""
+        a = np.asarray(layers, np.float32)
+        if a.ndim != 3:
+            raise ValueError("layers must be [n_layers, rows, cols]")
+        flat = np.ascontiguousarray(np.stack([l.ravel(order="F") for l in a]))
+        ln, ps = (C.c_double * 2)(*length), (C.c_double * 2)(*position)
+        _check(self.lib.lio_grid_set_layers(self.h, flat.ctypes.data, a.shape[0], a.shape[1], a.shape[2], float(resolution), ln, ps), "lio_grid_set_layers")
+
+    def info(self):
+        info = GridInfo()
+        _check(self.lib.lio_grid_info(self.h, C.byref(info)), "lio_grid_info")
+        return info
+
+    def layer(self, k):
+        """-> layer k as [rows, cols] float32"""
+        i = self.info()
+        out = np.empty((i.rows, i.cols), np.float32, order="F")
+        _check(self.lib.lio_grid_get_layer(self.h, int(k), out.ctypes.data, out.size), "lio_grid_get_layer")
+        return out
+
+    def sample(self, positions, layer_ids=(0,), cfg=None, want_method=True, **overrides):
+        """atPosition -> (values [n_layers, n] float32, method used [n_layers, n] uint8 or None, GridSampleInfo).
+        positions: [n, 2] float64 (x, y); overrides: method, border_mode."""
+        cfg = cfg or grid_sample_default_config(**overrides)
+        p = np.ascontiguousarray(positions, np.float64).reshape(-1, 2)
+        ids = np.ascontiguousarray(layer_ids, np.int32).reshape(-1)
+        val = np.empty((len(ids), len(p)), np.float32)
+        used = np.empty((len(ids), len(p)), np.uint8) if want_method else None
+        info = GridSampleInfo()
+        _check(self.lib.lio_grid_sample(self.h, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids), C.byref(cfg), p.ctypes.data, len(p),
+                                        val.ctypes.data, used.ctypes.data if want_method else None, C.byref(info)), "lio_grid_sample")
+        return val, used, info
+
+    def memory(self):
+        """-> bytes the object holds on the device"""
+        n = C.c_size_t()
+        _check(self.lib.lio_grid_memory(self.h, C.byref(n)), "lio_grid_memory")
+        return n.value
+
+    def close(self):
+        if self.h:
+            self.lib.lio_grid_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def kf_store_planning_grid(store, grid, pose, *args, **kw):
+    """KeyframeStore.planning_map's arguments and result; the chain also leaves its grids in `grid` (a Grid, or None)"""
+    return store.planning_grid(grid, pose, *args, **kw)
+
+
 # signedDistanceFromOccupancy (SignedDistance2d.cpp:272-287) on the data of a nav_msgs/OccupancyGrid
 def occupancy_sdf(grid, resolution, occupied_min=100, device_id=0):
     """-> [height, width] float32 in the grid's layout.  grid: [height, width] int8, row-major as occupancy_grid returns it."""
@@ -1567,11 +1676,22 @@ class KeyframeStore:
         elev = grid[:n].reshape((hm_info.rows, hm_info.cols), order="F").copy(order="F") if want_grid else None
         return elev, info, hm_info, lm_info
 
+    def planning_grid(self, grid_out, pose, *args, **kw):
+        """planning_map, which also leaves the raw grid (layer 0), the filled grid (1) and the eight terrain layers (2 .. 9) in
+        grid_out (a Grid; None: planning_map through the same entry point)."""
+        return self._planning("lio_kf_store_planning_grid", (grid_out.h if grid_out is not None else None,), pose, *args, **kw)
+
     def planning_map(self, pose, lm_cfg=None, hm_cfg=None, fill_cfg=None, terrain_cfg=None, sdf=None, sdf_cfg=None, want_grid=True,
                      want_filled=True, want_fill_mask=True):
         """The height map's chain once, then the median fill (fill_cfg), the terrain layers (terrain_cfg) and the field (sdf, an
         Sdf) on the grid it leaves on the device; a stage whose argument is None is absent.  -> dict: grid, filled, fill_mask
         ([rows, cols] or None), layers ({name: [rows, cols]} or None), lm_info, hm_info, fill_info, terrain_info, sdf_info."""
+        return self._planning("lio_kf_store_planning_map", (), pose, lm_cfg, hm_cfg, fill_cfg, terrain_cfg, sdf, sdf_cfg, want_grid, want_filled,
+                              want_fill_mask)
+
+    def _planning(self, entry, more_args, pose, lm_cfg=None, hm_cfg=None, fill_cfg=None, terrain_cfg=None, sdf=None, sdf_cfg=None, want_grid=True,
+                  want_filled=True, want_fill_mask=True):
+        """the entry point `entry` with the chain's arguments followed by more_args"""
         lm_cfg = lm_cfg or local_map_default_config()
         hm_cfg = hm_cfg or height_map_default_config()
         if sdf is not None and sdf_cfg is None:
@@ -1591,13 +1711,13 @@ class KeyframeStore:
             for k, want in (("grid", want_grid), ("filled", want_filled), ("fill_mask", want_fill_mask), ("layers", n_layers > 0)):
                 setattr(io, k, bufs[k].ctypes.data if want else None)
                 setattr(io, k + "_cap", bufs[k].size if want else 0)
-            rc = self.lib.lio_kf_store_planning_map(self.h, C.byref(lm_cfg), _f32p(p), C.byref(hm_cfg), ref(fill_cfg), ref(terrain_cfg),
-                                                    sdf.h if sdf is not None else None, ref(sdf_cfg), C.byref(io), C.byref(lm_info),
-                                                    C.byref(hm_info), C.byref(fill_info), C.byref(terrain_info), C.byref(sdf_info))
+            rc = getattr(self.lib, entry)(self.h, C.byref(lm_cfg), _f32p(p), C.byref(hm_cfg), ref(fill_cfg), ref(terrain_cfg),
+                                          sdf.h if sdf is not None else None, ref(sdf_cfg), C.byref(io), C.byref(lm_info),
+                                          C.byref(hm_info), C.byref(fill_info), C.byref(terrain_info), C.byref(sdf_info), *more_args)
             if rc == -1 and hm_info.rows * hm_info.cols > cells:
                 cells = _SCRATCH_CELLS["planning_map"] = hm_info.rows * hm_info.cols
                 continue
-            _check(rc, "lio_kf_store_planning_map")
+            _check(rc, entry)
             break
         n, shape = hm_info.rows * hm_info.cols, (hm_info.rows, hm_info.cols)
         take = lambda k, want: bufs[k][:n].reshape(shape, order="F").copy(order="F") if want else None

@@ -1,0 +1,316 @@
+// lio_gridsample.hip -- the planning layers resident on the device and grid_map's GridMap::atPosition on them: the query a
+// planner makes of the elevation grid and the terrain layers, once per trajectory point and footprint corner.  The arithmetic
+// is lio_gridsample.h's; this file is the object and the data movement.
+//   k_grid_sample   one lane per position, 256 lanes a block, one instance per interpolation method.  The lane reads its
+//                   position as one 16-byte load and forms the geometry once in fp64 (cell, quadrant, tap indices, normalised
+//                   coordinates), then loops over the requested layers: gathers the taps, evaluates, runs the fall-back chain.
+//                   Finiteness differs from layer to layer; geometry does not.  Values and method bytes of a layer are
+//                   written coalesced (lane q to [layer][q]).  Taps are plain global loads: a 550 x 400 layer is 0.88 MB and
+//                   stays in L2, so there is no LDS staging and the queries are not sorted by cell.  The counts are per-wave
+//                   ballots summed over the layers in lane 0 and one atomic per wave and count, as in k_terr_main.
+// conventions, deviations, resources, host waits.  -ffp-contract=off.
+#include <hip/hip_runtime.h>
+#include <float.h>
+#include <math.h>
+#include <cmath>
+#include <string.h>
+#include <vector>
+
+#include "lio_gridsample.h"
+#include "lio_cloud.h"
+#include "lio_pool.h"
+
+struct lio_grid {
+    int device_id = 0;
+    unsigned mask = 0;             // bit k: layer k is present
+    LioTerrGeom G{};               // rows = cols = 0: no geometry yet
+    LioDevBuf<float> d_layer[LIO_GRID_MAX_LAYERS];
+};
+
+namespace {
+
+struct GsLayer {                   // a layer on the device
+    const float* p;
+    int rows;
+    __device__ __forceinline__ float at(int r, int c) const { return p[(size_t)r + (size_t)c * (size_t)rows]; }
+    __device__ __forceinline__ float at_lin(int k) const { return p[k]; }
+};
+
+struct GsLayers { const float* p[LIO_GRID_MAX_LAYERS]; };          // the requested layers, in the caller's order
+
+// counters[0..3] += pairs per method used, counters[4] += pairs outside
+template <int METHOD>
+__global__ __launch_bounds__(256) void k_grid_sample(LioTerrGeom G, GsLayers L, int n_layers, int border, const double2* __restrict__ pos, int n,
+                                                     float* __restrict__ values, unsigned char* __restrict__ method_used,
+                                                     unsigned long long* __restrict__ counters)
+{
+    const int q = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    const bool live = q < n;
+    LioGsQuery Q;
+    Q.outside = true;
+    if (live) {
+        const double2 p = pos[q];
+        lio_gs_query(G, METHOD, border, p.x, p.y, &Q);
+    }
+    unsigned cnt[5] = { 0u, 0u, 0u, 0u, 0u };              // (lane 0's are the wave's)
+    for (int k = 0; k < n_layers; ++k) {
+        int used = -1;
+        if (live) {
+            const GsLayer in = { L.p[k], G.rows };
+            float v;
+            used = lio_gs_eval(G, Q, METHOD, in, &v);
+            const size_t at = (size_t)k * (size_t)n + (size_t)q;
+            values[at] = v;
+            if (method_used) method_used[at] = (unsigned char)used;
+        }
+        cnt[0] += (unsigned)__popcll(__ballot(used == LIO_GRID_NEAREST));
+        if (METHOD >= LIO_GRID_LINEAR) cnt[1] += (unsigned)__popcll(__ballot(used == LIO_GRID_LINEAR));
+        if (METHOD == LIO_GRID_CUBIC_CONVOLUTION) cnt[2] += (unsigned)__popcll(__ballot(used == LIO_GRID_CUBIC_CONVOLUTION));
+        if (METHOD == LIO_GRID_CUBIC) cnt[3] += (unsigned)__popcll(__ballot(used == LIO_GRID_CUBIC));
+        cnt[4] += (unsigned)__popcll(__ballot(used == LIO_GRID_OUTSIDE));
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int m = 0; m < 5; ++m)
+            if (cnt[m]) atomicAdd(&counters[m], (unsigned long long)cnt[m]);
+    }
+}
+
+thread_local float t_stage_ms[3] = { 0, 0, 0 };
+thread_local bool t_stage_on = false;
+
+struct GsClock {                   // four marks around the three stages, only when a caller asked for the times
+    hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
+    int n = 0;
+    bool on = false;
+    ~GsClock() { for (int k = 0; k < n; ++k) (void)hipEventDestroy(ev[k]); }
+    void mark(hipStream_t s)
+    {
+        if (!on || n >= 4) return;
+        if (hipEventCreate(&ev[n]) != hipSuccess) { on = false; return; }
+        (void)hipEventRecord(ev[n++], s);
+    }
+};
+
+int grid_geometry_check(int rows, int cols, double resolution, const double* length, const double* position)
+{
+    if (rows < 1 || cols < 1) return lio_fail(LIO_ERR_ARG, "rows and cols must be at least 1");
+    if (rows >= LIO_GS_MAX_LINE || cols >= LIO_GS_MAX_LINE) return lio_fail(LIO_ERR_ARG, "rows and cols must be below 2^24");
+    if (!std::isfinite(resolution) || resolution < 1e-4) return lio_fail(LIO_ERR_ARG, "resolution must be finite and at least 1e-4");
+    for (int a = 0; a < 2; ++a) {
+        if (!std::isfinite(length[a]) || !std::isfinite(position[a])) return lio_fail(LIO_ERR_ARG, "length and position must be finite");
+        if (length[a] != (double)(a == 0 ? rows : cols) * resolution) return lio_fail(LIO_ERR_ARG, "length must be size * resolution (GridMap::setGeometry)");
+    }
+    if ((long long)rows * cols > 0x7fffffffLL - 1024) return lio_fail(LIO_ERR_CAPACITY, "a layer has more than 2^31 - 1024 cells");
+    return LIO_OK;
+}
+
+void grid_apply_geometry(lio_grid* g, int rows, int cols, double resolution, const double* length, const double* position)
+{
+    LioTerrGeom& G = g->G;
+    G.rows = rows; G.cols = cols; G.res = resolution;
+    for (int a = 0; a < 2; ++a) {
+        G.len[a] = length[a]; G.pos[a] = position[a];
+        G.half[a] = 0.5 * length[a];                       // getVectorToOrigin
+        G.base[a] = position[a] + (G.half[a] - 0.5 * resolution);          // mapPosition + getVectorToFirstCell
+    }
+}
+
+}  // namespace
+
+void lio_grid_clear(lio_grid* g)
+{
+    g->mask = 0;
+    g->G.rows = g->G.cols = 0;
+}
+
+int lio_grid_begin(lio_grid* g, int device_id)
+{
+    if (device_id != g->device_id) return lio_fail(LIO_ERR_ARG, "the keyframe store and the grid live on different devices");
+    lio_grid_clear(g);
+    return LIO_OK;
+}
+
+int lio_grid_set_geometry(lio_grid* g, int rows, int cols, double resolution, const double length[2], const double position[2])
+{
+    lio_grid_clear(g);
+    const int rc = grid_geometry_check(rows, cols, resolution, length, position);
+    if (rc != LIO_OK) return rc;
+    grid_apply_geometry(g, rows, cols, resolution, length, position);
+    return LIO_OK;
+}
+
+int lio_grid_layer_slot(lio_grid* g, int layer, float** d_out)
+{
+    *d_out = nullptr;
+    if (layer < 0 || layer >= LIO_GRID_MAX_LAYERS || g->G.rows < 1 || g->G.cols < 1) return lio_fail(LIO_ERR_ARG, "no such layer slot");
+    HIPCHK(g->d_layer[layer].grow((size_t)g->G.rows * (size_t)g->G.cols, 1.0, 64, true));
+    g->mask |= 1u << layer;
+    *d_out = g->d_layer[layer].p;
+    return LIO_OK;
+}
+
+extern "C" void lio_grid_sample_default_config(lio_grid_sample_config* cfg)
+{
+    if (!cfg) return;
+    memset(cfg, 0, sizeof(*cfg));
+    cfg->method = LIO_GRID_NEAREST;                        // atPosition's default argument
+    cfg->border_mode = 0;
+}
+
+extern "C" int lio_grid_create(int32_t device_id, lio_grid** out)
+try {
+    if (!out) return lio_fail(LIO_ERR_ARG, "null argument");
+    int rc = lio_check_device(device_id);
+    if (rc != LIO_OK) return rc;
+    lio_grid* g = new lio_grid();
+    g->device_id = device_id;
+    *out = g;
+    return LIO_OK;
+} LIO_CATCH
+
+extern "C" void lio_grid_destroy(lio_grid* g)
+{
+    if (!g) return;
+    (void)hipSetDevice(g->device_id);
+    (void)hipDeviceSynchronize();
+    delete g;
+}
+
+extern "C" int lio_grid_set_layers(lio_grid* g, const float* layers, int32_t n_layers, int32_t rows, int32_t cols, double resolution,
+                                   const double* length, const double* position)
+try {
+    if (!length || !position) return lio_fail(LIO_ERR_ARG, "null argument");
+    if (n_layers < 1 || n_layers > LIO_GRID_MAX_LAYERS) return lio_fail(LIO_ERR_ARG, "n_layers must be in [1, LIO_GRID_MAX_LAYERS]");
+    int rc = grid_geometry_check(rows, cols, resolution, length, position);
+    if (rc != LIO_OK) return rc;
+    if (!g || !layers) return lio_fail(LIO_ERR_ARG, "null argument");
+    if ((rc = lio_check_device(g->device_id)) != LIO_OK) return rc;
+    if ((rc = lio_grid_set_geometry(g, rows, cols, resolution, length, position)) != LIO_OK) return rc;
+    hipStream_t s = nullptr;
+    const size_t cells = (size_t)rows * (size_t)cols;
+    for (int k = 0; k < n_layers; ++k) {
+        float* d = nullptr;
+        if ((rc = lio_grid_layer_slot(g, k, &d)) != LIO_OK) { g->mask = 0; return rc; }
+        const hipError_t e = hipMemcpyAsync(d, layers + (size_t)k * cells, sizeof(float) * cells, hipMemcpyHostToDevice, s);
+        if (e != hipSuccess) { g->mask = 0; (void)hipStreamSynchronize(s); HIPCHK(e); }
+    }
+    const hipError_t e = hipStreamSynchronize(s);
+    if (e != hipSuccess) g->mask = 0;
+    HIPCHK(e);
+    return LIO_OK;
+} LIO_CATCH
+
+extern "C" int lio_grid_get_layer(lio_grid* g, int32_t layer, float* out, size_t cap_floats)
+try {
+    if (!g || !out) return lio_fail(LIO_ERR_ARG, "null argument");
+    if (layer < 0 || layer >= LIO_GRID_MAX_LAYERS || !((g->mask >> layer) & 1u)) return lio_fail(LIO_ERR_ARG, "the object holds no such layer");
+    const size_t cells = (size_t)g->G.rows * (size_t)g->G.cols;
+    if (cap_floats < cells) return lio_fail(LIO_ERR_ARG, "out holds fewer than rows x cols floats");
+    int rc = lio_check_device(g->device_id);
+    if (rc != LIO_OK) return rc;
+    HIPCHK(hipMemcpy(out, g->d_layer[layer].p, sizeof(float) * cells, hipMemcpyDeviceToHost));
+    return LIO_OK;
+} LIO_CATCH
+
+extern "C" int lio_grid_info(lio_grid* g, lio_grid_desc* info)
+try {
+    if (!g || !info) return lio_fail(LIO_ERR_ARG, "null argument");
+    memset(info, 0, sizeof(*info));
+    info->layer_mask = g->mask;
+    if (!g->mask) return LIO_OK;
+    info->rows = g->G.rows; info->cols = g->G.cols; info->resolution = g->G.res;
+    for (int a = 0; a < 2; ++a) { info->length[a] = g->G.len[a]; info->position[a] = g->G.pos[a]; }
+    return LIO_OK;
+} LIO_CATCH
+
+extern "C" int lio_grid_memory(lio_grid* g, size_t* bytes)
+try {
+    if (!g || !bytes) return lio_fail(LIO_ERR_ARG, "null argument");
+    size_t n = 0;
+    for (const LioDevBuf<float>& b : g->d_layer) n += b.cap * sizeof(float);
+    *bytes = n;
+    return LIO_OK;
+} LIO_CATCH
+
+extern "C" int lio_grid_sample(lio_grid* g, const int32_t* layer_ids, int32_t n_layers, const lio_grid_sample_config* cfg, const double* positions,
+                               size_t n, float* values, uint8_t* method_used, lio_grid_sample_info* info)
+try {
+    if (info) memset(info, 0, sizeof(*info));
+    if (!layer_ids || !cfg || (n && (!positions || !values))) return lio_fail(LIO_ERR_ARG, "null argument");
+    if (cfg->method < LIO_GRID_NEAREST || cfg->method > LIO_GRID_CUBIC) return lio_fail(LIO_ERR_ARG, "method is 0 (nearest), 1 (linear), 2 (cubic convolution) or 3 (cubic)");
+    if (cfg->border_mode != 0 && cfg->border_mode != 1) return lio_fail(LIO_ERR_ARG, "border_mode is 0 (as written) or 1 (clamped)");
+    if (n_layers < 1 || n_layers > LIO_GRID_MAX_LAYERS) return lio_fail(LIO_ERR_ARG, "n_layers must be in [1, LIO_GRID_MAX_LAYERS]");
+    if (!g) return lio_fail(LIO_ERR_ARG, "null argument");
+    if (!g->mask) return lio_fail(LIO_ERR_ARG, "the object holds no layers (lio_grid_set_layers, lio_kf_store_planning_grid)");
+    GsLayers L;
+    memset(&L, 0, sizeof(L));
+    unsigned seen = 0;
+    for (int k = 0; k < n_layers; ++k) {
+        const int id = layer_ids[k];
+        if (id < 0 || id >= LIO_GRID_MAX_LAYERS || !((g->mask >> id) & 1u)) return lio_fail(LIO_ERR_ARG, "a layer id names a layer the object does not hold");
+        if ((seen >> id) & 1u) return lio_fail(LIO_ERR_ARG, "a layer id is repeated");
+        seen |= 1u << id;
+        L.p[k] = g->d_layer[id].p;
+    }
+    if (n > (size_t)1 << 27) return lio_fail(LIO_ERR_CAPACITY, "more than 2^27 positions in one call");
+    if (n == 0) return LIO_OK;
+    int rc = lio_check_device(g->device_id);
+    if (rc != LIO_OK) return rc;
+    hipStream_t s = nullptr;
+    const size_t pairs = (size_t)n_layers * n;
+    LioTemp pos, val, used, counters;
+    HIPCHK(pos.alloc(sizeof(double) * 2 * n));
+    HIPCHK(val.alloc(sizeof(float) * pairs));
+    if (method_used) HIPCHK(used.alloc(pairs));
+    HIPCHK(counters.alloc(5 * sizeof(unsigned long long)));
+    GsClock clk;
+    clk.on = t_stage_on;
+    clk.mark(s);
+    HIPCHK(hipMemcpyAsync(pos.p, positions, sizeof(double) * 2 * n, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(counters.p, 0, 5 * sizeof(unsigned long long), s));
+    clk.mark(s);
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    const double2* d_pos = (const double2*)pos.p;
+    unsigned char* d_used = method_used ? used.as<unsigned char>() : nullptr;
+    unsigned long long* d_cnt = counters.as<unsigned long long>();
+    switch (cfg->method) {
+    case LIO_GRID_NEAREST:
+        hipLaunchKernelGGL(k_grid_sample<LIO_GRID_NEAREST>, grid, block, 0, s, g->G, L, n_layers, cfg->border_mode, d_pos, (int)n, val.as<float>(), d_used, d_cnt);
+        break;
+    case LIO_GRID_LINEAR:
+        hipLaunchKernelGGL(k_grid_sample<LIO_GRID_LINEAR>, grid, block, 0, s, g->G, L, n_layers, cfg->border_mode, d_pos, (int)n, val.as<float>(), d_used, d_cnt);
+        break;
+    case LIO_GRID_CUBIC_CONVOLUTION:
+        hipLaunchKernelGGL(k_grid_sample<LIO_GRID_CUBIC_CONVOLUTION>, grid, block, 0, s, g->G, L, n_layers, cfg->border_mode, d_pos, (int)n, val.as<float>(), d_used,
+                           d_cnt);
+        break;
+    default:
+        hipLaunchKernelGGL(k_grid_sample<LIO_GRID_CUBIC>, grid, block, 0, s, g->G, L, n_layers, cfg->border_mode, d_pos, (int)n, val.as<float>(), d_used, d_cnt);
+        break;
+    }
+    clk.mark(s);
+    unsigned long long hc[5] = { 0, 0, 0, 0, 0 };
+    HIPCHK(hipMemcpyAsync(values, val.p, sizeof(float) * pairs, hipMemcpyDeviceToHost, s));
+    if (method_used) HIPCHK(hipMemcpyAsync(method_used, used.p, pairs, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(hc, counters.p, sizeof(hc), hipMemcpyDeviceToHost, s));
+    clk.mark(s);
+    const hipError_t e = hipStreamSynchronize(s);          // the call's one host wait (the temporaries go back to the pool after it)
+    HIPCHK(e);
+    HIPCHK(hipGetLastError());
+    if (info) {
+        for (int m = 0; m < 4; ++m) info->n_method[m] = (int64_t)hc[m];
+        info->n_outside = (int64_t)hc[4];
+    }
+    if (clk.on && clk.n == 4)
+        for (int k = 0; k < 3; ++k)
+            if (hipEventElapsedTime(&t_stage_ms[k], clk.ev[k], clk.ev[k + 1]) != hipSuccess) t_stage_ms[k] = 0.0f;
+    return LIO_OK;
+} LIO_CATCH
+
+extern "C" int lio_grid_debug_stage_ms(int32_t enable, float ms[3])
+try {
+    if (ms) memcpy(ms, t_stage_ms, sizeof(t_stage_ms));
+    t_stage_on = enable != 0;
+    return LIO_OK;
+} LIO_CATCH

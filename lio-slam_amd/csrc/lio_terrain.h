@@ -344,5 +344,7 @@ int lio_terrain_check(const lio_terrain_config* cfg, double resolution, LioTerrP
 // The geometry; LIO_ERR_ARG for non-finite values and for length != size * resolution.
 int lio_terrain_set_geometry(LioTerrPlan* plan, int rows, int cols, double resolution, const double length[2], const double position[2]);
 // The two kernels on the device grid d_grid (rows x cols, column-major) on stream s, the requested layers copied to `layers`
-// (host; NULL: none) and the counts to *info.  Synchronous.
-int lio_terrain_device(const float* d_grid, const LioTerrPlan& plan, float* layers, lio_terrain_info* info, hipStream_t s);
+// (host; NULL: none) and the counts to *info.  d_dst (may be NULL): LIO_TERRAIN_N_LAYERS device pointers, each of which (where
+// not NULL) receives that layer, rows x cols floats, by device-to-device copy, whatever the mask.  Synchronous.
+int lio_terrain_device(const float* d_grid, const LioTerrPlan& plan, float* layers, lio_terrain_info* info, hipStream_t s,
+                       float* const* d_dst = nullptr);

@@ -130,7 +130,7 @@ int lio_terrain_set_geometry(LioTerrPlan* plan, int rows, int cols, double resol
     return LIO_OK;
 }
 
-int lio_terrain_device(const float* d_grid, const LioTerrPlan& plan, float* layers, lio_terrain_info* info, hipStream_t s)
+int lio_terrain_device(const float* d_grid, const LioTerrPlan& plan, float* layers, lio_terrain_info* info, hipStream_t s, float* const* d_dst)
 {
     const LioTerrParams& P = plan.P;
     const size_t n_cells = (size_t)P.G.rows * (size_t)P.G.cols;
@@ -156,6 +156,9 @@ int lio_terrain_device(const float* d_grid, const LioTerrPlan& plan, float* laye
             k = e;
         }
     }
+    if (d_dst)                                             // a resident layer set takes all of them
+        for (int k = 0; k < LIO_TERRAIN_N_LAYERS; ++k)
+            if (d_dst[k]) HIPCHK(hipMemcpyAsync(d_dst[k], d_out + (size_t)k * n_cells, sizeof(float) * n_cells, hipMemcpyDeviceToDevice, s));
     int hc[4] = { 0, 0, 0, 0 };
     HIPCHK(hipMemcpyAsync(hc, counters.p, sizeof(hc), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
