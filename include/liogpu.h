@@ -620,8 +620,13 @@ typedef struct lio_icp_clouds {
 
 void lio_icp_default_config(lio_icp_config *cfg);
 /* icp.setInputSource(source); icp.setInputTarget(target); icp.align(unused, guess); icp.getFitnessScore() on two host
- * clouds (x,y,z @0,4,8; strides >= 12, multiples of 4).  guess: 16 floats row-major, or NULL for the identity.  Non-finite
- * points of either cloud are skipped.  An empty cloud: LIO_OK, state NO_CORRESPONDENCES, converged 0, T = guess. */
+ * clouds (x,y,z @0,4,8; strides >= 12, multiples of 4).  guess: 16 floats row-major, or NULL for the identity (a non-finite
+ * entry: LIO_ERR_ARG).  Which points take part: a TARGET point when all three of its coordinates are at most 1e15 in magnitude
+ * (the bound of the cell sort; NaN, inf and larger finite values leave the point out, and the grid's box takes each axis from
+ * the coordinates within the bound on that axis); a SOURCE point when its coordinates are finite, before and after it is
+ * transformed.  A source point beyond 1e15 is searched like any other: its squared distance is huge or overflows to inf, so it
+ * fails every gate, and the fitness score counts it only while that distance is finite.  An empty cloud, or a target without
+ * a point that takes part: LIO_OK, state NO_CORRESPONDENCES, converged 0, T = guess. */
 int  lio_icp_align(int32_t device_id, const void *source, size_t n_source, size_t source_stride,
                    const void *target, size_t n_target, size_t target_stride,
                    const lio_icp_config *cfg, const float *guess, lio_icp_result *result);
@@ -646,6 +651,17 @@ int  lio_icp_debug_trace(int32_t device_id, const void *source, size_t n_source,
                          const void *target, size_t n_target, size_t target_stride,
                          const lio_icp_config *cfg, const float *guess, int32_t rec_iter, lio_icp_result *result,
                          float *steps, int32_t *n_corr, double *mse, int32_t *corr, int32_t *n_trace);
+/* Test hook, read-only: the search grid an alignment lays over `target`, by the very code the alignment runs (the box, the
+ * trial grid of 64 cells along the longest side, the edge for four points per occupied cell).  any = 0: no target point
+ * within the coordinate bound, every other field 0.  occupied = -1: the box is a point and no trial grid is laid (edge 1). */
+typedef struct lio_icp_grid_info {
+    float   origin[3];          /* the box's minimum corner = the corner of cell (0, 0, 0) */
+    float   edge, inv_cell;     /* cell edge and the factor the cell formula multiplies with */
+    int32_t nx, ny, nz, n_cells;
+    int32_t occupied;           /* occupied cells of the trial grid */
+    int32_t any;
+} lio_icp_grid_info;
+int  lio_icp_debug_grid(int32_t device_id, const void *target, size_t n_target, size_t target_stride, lio_icp_grid_info *out);
 
 /* ------------------------------------------------ Scan Context loop detection (performSCLoopClosure MO:1163-1269) */
 /* SCManager (Scancontext.cpp, "SC:") on the device: makeScancontext + the two keys of every keyframe, kept next to the

@@ -124,6 +124,12 @@ class IcpResult(C.Structure):
                 ("pose_corrected", C.c_float * 6)]
 
 
+class IcpGridInfo(C.Structure):
+    """The search grid of an alignment's target (include/liogpu.h lio_icp_grid_info)."""
+    _fields_ = [("origin", C.c_float * 3), ("edge", C.c_float), ("inv_cell", C.c_float), ("nx", C.c_int32), ("ny", C.c_int32),
+                ("nz", C.c_int32), ("n_cells", C.c_int32), ("occupied", C.c_int32), ("any", C.c_int32)]
+
+
 class IcpClouds(C.Structure):
     _fields_ = [("source", C.c_void_p), ("target", C.c_void_p), ("closed", C.c_void_p),
                 ("cap_source", C.c_size_t), ("cap_target", C.c_size_t), ("cap_closed", C.c_size_t),
@@ -303,7 +309,7 @@ EXPORTS = [
     "lio_host_unregister", "lio_s2m_set_shard_plan", "lio_s2m_register_pc2", "lio_deskew_pc2", "lio_kf_store_add_device", "lio_kf_store_add_from_handle",
     "lio_s2m_register_raw", "lio_s2m_debug_persist_spin", "lio_device_alloc", "lio_device_free", "lio_device_upload",
     "lio_nearby_default_config", "lio_kf_store_set_poses", "lio_assemble_map_nearby", "lio_debug_plane_fit",
-    "lio_icp_default_config", "lio_icp_align", "lio_kf_store_loop_icp", "lio_kf_store_detect_loop", "lio_icp_debug_trace",
+    "lio_icp_default_config", "lio_icp_align", "lio_kf_store_loop_icp", "lio_kf_store_detect_loop", "lio_icp_debug_trace", "lio_icp_debug_grid",
     "lio_sc_default_config", "lio_sc_make", "lio_sc_distance", "lio_kf_store_sc_add", "lio_kf_store_sc_add_device",
     "lio_kf_store_sc_add_from_handle", "lio_kf_store_sc_count", "lio_kf_store_sc_geometry", "lio_kf_store_sc_get", "lio_kf_store_sc_detect",
     "lio_sor_filter", "lio_local_map_default_config", "lio_kf_store_local_map",
@@ -1116,6 +1122,16 @@ def icp_debug_trace(source, target, cfg=None, guess=None, rec_iter=-1, device_id
                                               corr.ctypes.data, C.byref(nt)), "lio_icp_debug_trace")
     k = nt.value
     return res, steps[:k].reshape(k, 4, 4).copy(), n_corr[:k].copy(), mse[:k].copy(), corr[:len(src)].copy()
+
+
+def icp_debug_grid(target, device_id=0):
+    """Test hook, read-only -> IcpGridInfo: the grid lio_icp_align lays over `target`, by the alignment's own code."""
+    tgt, ts = _as_points(target)
+    out = IcpGridInfo()
+    fn = load_library().lio_icp_debug_grid         # bound on first use: A/B runs load older builds through LIOGPU_LIB
+    fn.argtypes = [C.c_int32, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(IcpGridInfo)]
+    _check(fn(device_id, tgt.ctypes.data, len(tgt), ts, C.byref(out)), "lio_icp_debug_grid")
+    return out
 
 
 def sc_default_config(**overrides):

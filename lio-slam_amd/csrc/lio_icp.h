@@ -24,6 +24,7 @@ int lio_icp_device(const float4* d_src, int n_src, const float4* d_tgt, int n_tg
                    const float* guess, lio_icp_result* res, hipStream_t s, LioIcpTrace* trace, float4* d_closed);
 
 // The uniform grid of a cell-walking search over the box mn .. mx of n device points (SoA): the edge (*edge) from their
-// density, about `per_cell` points per occupied cell, at most 2^22 cells.  One host wait (the occupied cells of a trial grid).
+// density, about `per_cell` points per occupied cell, at most 2^22 cells.  One host wait (the occupied cells of a trial grid,
+// also written to *occupied when it is given and a trial grid is laid).
 int lio_icp_choose_grid(const float* x, const float* y, const float* z, int n, const float mn[3], const float mx[3], float per_cell,
-                        hipStream_t s, LioGrid* g, float* edge);
+                        hipStream_t s, LioGrid* g, float* edge, int* occupied = nullptr);

@@ -411,7 +411,7 @@ void icp_empty_result(lio_icp_result* res, const float* guess, int n_src, int n_
 // along the longest side), scaled as for points on surfaces (count ~ edge^2) to about `per_cell` per occupied cell (the
 // alignment asks for four).
 int lio_icp_choose_grid(const float* x, const float* y, const float* z, int n, const float mn[3], const float mx[3], float per_cell,
-                        hipStream_t s, LioGrid* g, float* edge)
+                        hipStream_t s, LioGrid* g, float* edge, int* occupied)
 {
     const float ext = fmaxf(fmaxf(mx[0] - mn[0], mx[1] - mn[1]), mx[2] - mn[2]);
     auto lay = [&](float e) {
@@ -437,6 +437,7 @@ int lio_icp_choose_grid(const float* x, const float* y, const float* z, int n, c
         int occ = 0;
         HIPCHK(hipMemcpyAsync(&occ, flags.as<int>() + g->n_cells, sizeof(int), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
+        if (occupied) *occupied = occ;
         const float ppc = occ > 0 ? (float)n / (float)occ : 1.0f;
         e = e0 * sqrtf(per_cell / ppc);
         e = fminf(fmaxf(e, ext / 500.0f), ext);
@@ -446,6 +447,39 @@ int lio_icp_choose_grid(const float* x, const float* y, const float* z, int n, c
     *edge = e;
     return LIO_OK;
 }
+
+// The target side of an alignment up to its grid: SoA copy, the box of the coordinates within LIO_MAX_COORD (per axis), the
+// grid at four points per occupied cell.  lio_icp_device and the test hook lio_icp_debug_grid both go through here.
+namespace {
+struct IcpTarget {
+    LioTemp tx, ty, tz, t4;
+    LioGrid g;
+    float edge = 1.0f;
+    bool any = false;         // the box holds a point on every axis
+    int occupied = -1;        // occupied cells of the trial grid (-1: none was laid, the box is a point)
+};
+
+int icp_target_grid(const float4* d_tgt, int n_tgt, hipStream_t s, IcpTarget& T)
+{
+    LioTemp bbox;
+    HIPCHK(T.tx.alloc(sizeof(float) * (size_t)n_tgt)); HIPCHK(T.ty.alloc(sizeof(float) * (size_t)n_tgt)); HIPCHK(T.tz.alloc(sizeof(float) * (size_t)n_tgt));
+    HIPCHK(T.t4.alloc(sizeof(float4) * (size_t)n_tgt));
+    HIPCHK(bbox.alloc(6 * sizeof(unsigned)));
+    lio_launch_xyzi4_to_soa(d_tgt, n_tgt, T.tx.as<float>(), T.ty.as<float>(), T.tz.as<float>(), T.t4.as<float4>(), s);
+    unsigned hb[6];
+    lio_ord_box_clear(hb);
+    HIPCHK(hipMemcpyAsync(bbox.p, hb, sizeof(hb), hipMemcpyHostToDevice, s));
+    lio_launch_map_bbox(T.tx.as<float>(), T.ty.as<float>(), T.tz.as<float>(), n_tgt, bbox.as<unsigned>(), s);
+    HIPCHK(hipMemcpyAsync(hb, bbox.p, sizeof(hb), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    float mn[3], mx[3];
+    lio_ord_box_decode(hb, mn, mx);
+    T.any = true;
+    for (int a = 0; a < 3; ++a) T.any = T.any && hb[a] != LIO_ORD_NO_MIN && mn[a] <= mx[a];
+    if (!T.any) return LIO_OK;
+    return lio_icp_choose_grid(T.tx.as<float>(), T.ty.as<float>(), T.tz.as<float>(), n_tgt, mn, mx, 4.0f, s, &T.g, &T.edge, &T.occupied);
+}
+}  // namespace
 
 int lio_icp_device(const float4* d_src, int n_src, const float4* d_tgt, int n_tgt, const lio_icp_config& cfg, const float* guess,
                    lio_icp_result* res, hipStream_t s, LioIcpTrace* trace, float4* d_closed)
@@ -458,31 +492,18 @@ int lio_icp_device(const float4* d_src, int n_src, const float4* d_tgt, int n_tg
         HIPCHK(hipStreamSynchronize(s));
         return LIO_OK;
     }
-    // ---- the target: SoA, box of its finite points, grid, cell sort
-    LioTemp tx, ty, tz, t4, bbox;
-    HIPCHK(tx.alloc(sizeof(float) * (size_t)n_tgt)); HIPCHK(ty.alloc(sizeof(float) * (size_t)n_tgt)); HIPCHK(tz.alloc(sizeof(float) * (size_t)n_tgt));
-    HIPCHK(t4.alloc(sizeof(float4) * (size_t)n_tgt));
-    HIPCHK(bbox.alloc(6 * sizeof(unsigned)));
-    lio_launch_xyzi4_to_soa(d_tgt, n_tgt, tx.as<float>(), ty.as<float>(), tz.as<float>(), t4.as<float4>(), s);
-    unsigned hb[6];
-    lio_ord_box_clear(hb);
-    HIPCHK(hipMemcpyAsync(bbox.p, hb, sizeof(hb), hipMemcpyHostToDevice, s));
-    lio_launch_map_bbox(tx.as<float>(), ty.as<float>(), tz.as<float>(), n_tgt, bbox.as<unsigned>(), s);
-    HIPCHK(hipMemcpyAsync(hb, bbox.p, sizeof(hb), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    float mn[3], mx[3];
-    lio_ord_box_decode(hb, mn, mx);
-    bool any = true;
-    for (int a = 0; a < 3; ++a) any = any && hb[a] != LIO_ORD_NO_MIN && mn[a] <= mx[a];
-    LioGrid g;
-    float edge = 1.0f;
-    if (!any) {                                                        // no finite target point: nothing to correspond with
+    // ---- the target: SoA, box, grid (icp_target_grid), cell sort
+    IcpTarget tg;
+    int rc = icp_target_grid(d_tgt, n_tgt, s, tg);
+    if (rc != LIO_OK) return rc;
+    if (!tg.any) {                                                     // no target point within the bound: nothing to correspond with
         if (d_closed) HIPCHK(hipMemcpyAsync(d_closed, d_src, sizeof(float4) * (size_t)n_src, hipMemcpyDeviceToDevice, s));
         HIPCHK(hipStreamSynchronize(s));
         return LIO_OK;
     }
-    int rc = lio_icp_choose_grid(tx.as<float>(), ty.as<float>(), tz.as<float>(), n_tgt, mn, mx, 4.0f, s, &g, &edge);
-    if (rc != LIO_OK) return rc;
+    LioTemp &tx = tg.tx, &ty = tg.ty, &tz = tg.tz;
+    const LioGrid& g = tg.g;
+    const float edge = tg.edge;
     LioTemp cell_of, cell_count, cell_start, tiles, sorted;
     HIPCHK(cell_of.alloc(sizeof(int) * (size_t)n_tgt));
     HIPCHK(cell_count.alloc(sizeof(int) * (size_t)g.n_cells));
@@ -617,6 +638,30 @@ try {
     const int rc = icp_align_host(device_id, source, n_source, source_stride, target, n_target, target_stride, cfg, guess, result, &tr);
     if (n_trace) *n_trace = tr.n_trace;
     return rc;
+} LIO_CATCH
+
+extern "C" int lio_icp_debug_grid(int32_t device_id, const void* target, size_t n_target, size_t target_stride, lio_icp_grid_info* out)
+try {
+    if (!out || (n_target && !target)) return lio_fail(LIO_ERR_ARG, "null argument");
+    if (target_stride < 12 || (target_stride & 3)) return lio_fail(LIO_ERR_ARG, "strides must be >= 12 and multiples of 4");
+    if (n_target > 0x7fffffffull - 1024) return lio_fail(LIO_ERR_CAPACITY, "cloud too large");
+    memset(out, 0, sizeof(*out));
+    out->occupied = -1;
+    int rc = lio_check_device(device_id);
+    if (rc != LIO_OK) return rc;
+    if (!n_target) return LIO_OK;
+    hipStream_t s = nullptr;
+    LioTemp raw_t, d_tgt;
+    if ((rc = icp_upload(target, n_target, target_stride, raw_t, d_tgt, s)) != LIO_OK) return rc;
+    IcpTarget tg;
+    if ((rc = icp_target_grid(d_tgt.as<float4>(), (int)n_target, s, tg)) != LIO_OK) return rc;
+    if (!tg.any) return LIO_OK;
+    out->any = 1;
+    out->origin[0] = tg.g.ox; out->origin[1] = tg.g.oy; out->origin[2] = tg.g.oz;
+    out->edge = tg.edge; out->inv_cell = tg.g.inv_cell;
+    out->nx = tg.g.nx; out->ny = tg.g.ny; out->nz = tg.g.nz; out->n_cells = tg.g.n_cells;
+    out->occupied = tg.occupied;
+    return LIO_OK;
 } LIO_CATCH
 
 // loopFindNearKeyframes MO:1360-1383: the keyframes key - search_num .. key + search_num the store holds, each under its own

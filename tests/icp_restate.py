@@ -1,7 +1,8 @@
 """numpy restatement of pcl::IterativeClosestPoint<PointXYZI, PointXYZI>::computeTransformation (PCL 1.10, no rejectors,
 TransformationEstimationSVD, DefaultConvergenceCriteria) and getFitnessScore as include/liogpu.h lio_icp_align states them:
-the checker of tests/test_icp_cpu.py and tests/test_gpu_icp.py.  Brute-force fp32 1-NN, np.linalg.svd in fp64, the criteria
-line by line.  The conventions where PCL is not a function of its inputs are DESIGN.md section 2's (parity unpinned)."""
+the checker of tests/test_icp_cpu.py, tests/test_gpu_icp.py and tests/test_gpu_icp_edges.py.  Brute-force fp32 1-NN,
+np.linalg.svd in fp64, the criteria line by line, and grid_of: the search grid of the target in np.float32, which the hook
+lio_icp_debug_grid arbitrates.  The conventions where PCL is not a function of its inputs are DESIGN.md section 2's (parity unpinned)."""
 import numpy as np
 
 NOT_CONVERGED, ITERATIONS, TRANSFORM, ABS_MSE, REL_MSE, NO_CORRESPONDENCES = range(6)
@@ -11,12 +12,23 @@ DEFAULTS = dict(max_corr_dist=30.0, transform_eps=1e-6, fitness_eps=1e-6, rel_ms
                 fitness_max=0.3, max_iters=100, min_corr=3, max_similar=0, min_source_points=300, min_target_points=1000)
 
 
+MAX_COORD = np.float32(1.0e15)                              # LIO_MAX_COORD: the bound of the target's cell sort
+F32 = np.float32
+
+
+def target_ok(tgt):
+    """The target points that take part (include/liogpu.h lio_icp_align): every coordinate within MAX_COORD in magnitude."""
+    with np.errstate(invalid="ignore"):
+        return (np.abs(np.asarray(tgt, np.float32)[:, :3]) <= MAX_COORD).all(1)
+
+
 def nn_brute(src, tgt, chunk=512):
     """1-NN of every src point in tgt: FLANN L2_Simple ((dx*dx)+dy*dy)+dz*dz in fp32, ties to the lower index.
-    -> (idx int64 [n], d2 float32 [n]); non-finite src points get idx -1."""
+    -> (idx int64 [n], d2 float32 [n]); non-finite src points get idx -1.  A target point takes part when all three of its
+    coordinates are within MAX_COORD (a distance that overflows is inf and still orders: the lowest index of those)."""
     src = np.asarray(src, np.float32)
     tgt = np.asarray(tgt, np.float32)
-    ok_t = np.isfinite(tgt).all(1)
+    ok_t = target_ok(tgt)
     ids = np.nonzero(ok_t)[0]
     t = tgt[ok_t]
     idx = np.full(len(src), -1, np.int64)
@@ -35,6 +47,67 @@ def nn_brute(src, tgt, chunk=512):
             idx[a:a + chunk] = np.where(fin, ids[j], -1)
             d2o[a:a + chunk] = np.where(fin, d2[np.arange(len(s)), j], np.inf)
     return idx, d2o
+
+
+def _ord(v):
+    """float32 -> uint32 whose unsigned order is the float order (-0 below +0), as the device's box reduction orders them."""
+    b = np.asarray(v, np.float32).view(np.uint32)
+    return np.where(b & np.uint32(0x80000000), ~b, b | np.uint32(0x80000000))
+
+
+def grid_cells(G, pts):
+    """floor((p - origin) * inv_cell) per axis in fp32 (the formula that bins the target and places a query), unclamped,
+    as float64 integers [n, 3]."""
+    p = np.asarray(pts, np.float32)[:, :3]
+    o = np.asarray(G["origin"], np.float32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        return np.floor((p - o[None, :]) * F32(G["inv_cell"])).astype(np.float64)
+
+
+def _lay(mn, mx, e):
+    inv = F32(1.0) / F32(e)
+    n = [int(np.floor((mx[a] - mn[a]) * inv)) + 1 for a in range(3)]
+    return inv, n
+
+
+def grid_of(target):
+    """The grid lio_icp_align lays over `target` (lio_icp_choose_grid with per_cell = 4), in np.float32 arithmetic:
+    -> dict(origin [3], edge, inv_cell, nx, ny, nz, n_cells, occupied) or None when an axis has no coordinate in range.
+    occupied = -1: the box is a point, no trial grid, edge 1."""
+    t = np.asarray(target, np.float32)[:, :3]
+    n = len(t)
+    with np.errstate(invalid="ignore"):
+        ok = np.abs(t) <= MAX_COORD                         # the box: per axis, whatever the point's other coordinates are
+    if n == 0 or not ok.any(0).all():
+        return None
+    mn = np.zeros(3, np.float32)
+    mx = np.zeros(3, np.float32)
+    for a in range(3):
+        v = t[ok[:, a], a]
+        o = _ord(v)
+        mn[a], mx[a] = v[np.argmin(o)], v[np.argmax(o)]
+    ext = max(max(mx[0] - mn[0], mx[1] - mn[1]), mx[2] - mn[2])
+    e, occ = F32(1.0), -1
+    if ext > F32(1.0e-6):
+        e0 = ext / F32(64.0)
+        inv0, n0 = _lay(mn, mx, e0)
+        pts = t[ok.all(1)]                                  # lio_map_cell: the point's three coordinates in range ...
+        c = np.floor((pts - mn[None, :]) * inv0)
+        c = np.minimum(np.maximum(c, F32(-4.0)), np.array(n0, np.float32)[None, :] + F32(3.0)).astype(np.int64)
+        inside = ((c >= 0) & (c < np.array(n0)[None, :])).all(1)                                    # ... and its cell in the grid
+        c = c[inside]
+        occ = len(np.unique((c[:, 2] * n0[1] + c[:, 1]) * n0[0] + c[:, 0]))
+        ppc = F32(n) / F32(occ) if occ > 0 else F32(1.0)
+        e = e0 * np.sqrt(F32(4.0) / ppc)
+        e = min(max(e, ext / F32(500.0)), ext)
+        while True:
+            _, nn = _lay(mn, mx, e)
+            if nn[0] * nn[1] * nn[2] <= (1 << 22):
+                break
+            e = e * F32(1.26)
+    inv, nn = _lay(mn, mx, e)
+    nc = nn[0] * nn[1] * nn[2]
+    return dict(origin=mn, edge=F32(e), inv_cell=F32(inv), nx=nn[0], ny=nn[1], nz=nn[2], n_cells=min(nc, 0x7fffffff), occupied=occ)
 
 
 def transform_points(M, p):
