@@ -1247,6 +1247,67 @@ int  lio_kf_store_planning_grid(lio_kf_store *s, const lio_local_map_config *lm,
  * milliseconds. */
 int  lio_grid_debug_stage_ms(int32_t enable, float ms[3]);
 
+/* ------------------------------------------------ resident planning layers, reduced over regions (grid_map's iterators) */
+/* grid_map_core's LineIterator, CircleIterator, EllipseIterator and PolygonIterator (src/iterators/) on a lio_grid: the cells
+ * a region covers, and per requested layer the reduction a planner would loop for (is this footprint free of cells below a
+ * traversability threshold, the worst slope under a swath).  Only regions go up and one record per (layer, region) comes
+ * down.  DESIGN.md section 4l states the conventions; parity is against the restatement (tests/grid_region_restate.py) with
+ * the reference's own test sequences on top (parity unpinned).
+ *  - circle   p = (cx, cy, r): window by findSubmapParameters, member when dx dx + dy dy <= r r on the cell's centre;
+ *  - ellipse  p = (cx, cy, lx, ly, rotation): the lengths are full axes (EllipseIterator.cpp:17-28, :74-97); sin and cos of
+ *             the rotation are taken on the host (libm);
+ *  - polygon  n_vertices (x, y) pairs from first_vertex of `vertices`: window from the vertex extremes, member by
+ *             Polygon::isInside (even-odd);
+ *  - line     p = (x0, y0, x1, y1): both ends limited to the map by getIndexLimitedToMapRange, Bresenham between them.
+ * Cells come in the iterator's order: SubmapIterator's (row index outer, column index inner) for the three area kinds, start
+ * to end for the line.  The status is per region and never fails the call: OK; EMPTY (no cell: a line whose constructor
+ * throws, an area that misses every centre); INVALID (nothing is read, 0 cells: a non-finite parameter or vertex, r < 0, an
+ * ellipse length not > 0, a line end whose walk exceeds LIO_REGION_MAX_WALK steps -- a labelled deviation, the reference
+ * keeps walking). */
+enum { LIO_REGION_LINE = 0, LIO_REGION_CIRCLE = 1, LIO_REGION_ELLIPSE = 2, LIO_REGION_POLYGON = 3 };
+enum { LIO_REGION_OK = 0, LIO_REGION_EMPTY = 1, LIO_REGION_INVALID = 2 };
+#define LIO_REGION_MAX_VERTICES 64
+#define LIO_REGION_MAX_WALK 4096
+typedef struct lio_grid_region {
+    int32_t kind, n_vertices;     /* LIO_REGION_*; n_vertices and first_vertex: polygons only                   */
+    int64_t first_vertex;
+    double  p[5];                 /* the kind's parameters, the rest ignored                                    */
+} lio_grid_region;
+typedef struct lio_grid_region_config {
+    float   threshold;            /* n_below counts finite member cells with value < threshold (float)      0.5 */
+    int32_t pad;
+} lio_grid_region_config;
+typedef struct lio_grid_region_stat {
+    double  sum;                  /* fp64 over the finite member cells, in the fixed order below                */
+    float   min, max;             /* over the finite member cells, -0.0 < +0.0; none: the quiet NaN 0x7fc00000  */
+    int32_t n_finite, n_below;
+} lio_grid_region_stat;
+typedef struct lio_grid_region_info {
+    int64_t n_ok, n_empty, n_invalid, n_cells;     /* regions per status; cells over all regions                */
+} lio_grid_region_info;
+void lio_grid_region_default_config(lio_grid_region_config *cfg);   /* threshold 0.5 */
+/* stats[k * n + q]: layer layer_ids[k] over region q.  n_cells[q] (may be NULL): the region's cells, status[q] (may be NULL)
+ * its status, info (may be NULL) the counts of the call.  The sum's order is part of the interface: number the window's
+ * cells column-major (row fastest; a line's cells by their place on it); partial p of 64 adds the finite member cells of
+ * number = p (mod 64), ascending, from +0.0; then for s = 32, 16, .. 1: part[k] += part[k + s], k < s; sum = part[0].
+ * n = 0: LIO_OK.  LIO_ERR_ARG before any device is touched: null arguments, a non-finite threshold, n_layers outside 1 .. 16,
+ * a layer id outside 0 .. 15, repeated or absent, a kind outside the enum, a polygon with fewer than 3 or more than
+ * LIO_REGION_MAX_VERTICES vertices or whose vertices leave [0, n_vertices), an object without layers.  More than 2^24
+ * regions: LIO_ERR_CAPACITY.  Complete on return, one host wait per call; the layers are only read. */
+int  lio_grid_region_reduce(lio_grid *g, const int32_t *layer_ids, int32_t n_layers, const lio_grid_region_config *cfg,
+                            const lio_grid_region *regions, size_t n, const double *vertices, size_t n_vertices,
+                            lio_grid_region_stat *stats, int32_t *n_cells, uint8_t *status, lio_grid_region_info *info);
+/* The cells themselves: cells[offsets[q] .. offsets[q + 1]) are region q's, as column-major linear indices col * rows + row,
+ * in the iterator's order; offsets has n + 1 entries.  Reads no layer.  status and info may be NULL.  cap_cells smaller than
+ * offsets[n]: LIO_ERR_CAPACITY with offsets filled (offsets[n] tells the need) and cells untouched; so are more than
+ * 2^31 - 1 cells in one call.  The other refusals are lio_grid_region_reduce's.  Complete on return; two host waits: the
+ * sizes, then exactly offsets[n] cells. */
+int  lio_grid_region_cells(lio_grid *g, const lio_grid_region *regions, size_t n, const double *vertices, size_t n_vertices,
+                           int64_t *offsets, int32_t *cells, size_t cap_cells, uint8_t *status, lio_grid_region_info *info);
+/* Measurement hook (tools/grid_region_cost.py), as lio_grid_debug_stage_ms: the last lio_grid_region_reduce of the calling
+ * thread as regions up, plan kernel, reduce kernel and results down, in milliseconds. */
+int  lio_grid_region_debug_stage_ms(int32_t enable, float ms[4]);
+
 #ifdef __cplusplus
 }
 #endif

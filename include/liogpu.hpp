@@ -397,6 +397,27 @@ public:
         c.method = method; c.border_mode = border_mode;
         check(lio_grid_sample(g_, layer_ids, n_layers, &c, positions, n, values, method_used, info), "lio_grid_sample");
     }
+    // grid_map's Line / Circle / Ellipse / PolygonIterator over n regions with the reduction a caller would loop for:
+    // stats[k * n + q] is layer layer_ids[k] over region q; n_cells and status (each may be nullptr) per region; `vertices` holds
+    // the polygons' (x, y) pairs.  threshold: what n_below counts below.
+    void regionReduce(const int32_t* layer_ids, int32_t n_layers, const lio_grid_region* regions, size_t n, const double* vertices, size_t n_vertices,
+                      lio_grid_region_stat* stats, float threshold = 0.5f, int32_t* n_cells = nullptr, uint8_t* status = nullptr,
+                      lio_grid_region_info* info = nullptr)
+    {
+        lio_grid_region_config c;
+        lio_grid_region_default_config(&c);
+        c.threshold = threshold;
+        check(lio_grid_region_reduce(g_, layer_ids, n_layers, &c, regions, n, vertices, n_vertices, stats, n_cells, status, info), "lio_grid_region_reduce");
+    }
+    // the cells themselves, in the iterator's order: returns LIO_ERR_CAPACITY (no throw) when cap_cells is too small, with
+    // offsets[n] the need
+    int regionCells(const lio_grid_region* regions, size_t n, const double* vertices, size_t n_vertices, int64_t* offsets, int32_t* cells, size_t cap_cells,
+                    uint8_t* status = nullptr, lio_grid_region_info* info = nullptr)
+    {
+        const int rc = lio_grid_region_cells(g_, regions, n, vertices, n_vertices, offsets, cells, cap_cells, status, info);
+        if (rc != LIO_ERR_CAPACITY) check(rc, "lio_grid_region_cells");
+        return rc;
+    }
     void layer(int32_t k, float* out, size_t cap_floats) { check(lio_grid_get_layer(g_, k, out, cap_floats), "lio_grid_get_layer"); }
     lio_grid_desc info()
     {

@@ -20,7 +20,10 @@ from .api import (LioError, ScanToMap, S2MConfig, S2MResult, S2MProfile, DeskewC
                   MedianFillConfig, MedianFillInfo, PlanningMapBuffers, median_fill, median_fill_default_config,
                   Grid, GridSampleConfig, GridSampleInfo, GridInfo, grid_sample_default_config, kf_store_planning_grid, GRID_MAX_LAYERS,
                   GRID_NEAREST, GRID_LINEAR, GRID_CUBIC_CONVOLUTION, GRID_CUBIC, GRID_OUTSIDE, GRID_LAYER_ELEVATION, GRID_LAYER_FILLED,
-                  GRID_LAYER_TERRAIN)
+                  GRID_LAYER_TERRAIN,
+                  GridRegion, GridRegionConfig, GridRegionStat, GridRegionInfo, GRID_REGION_DTYPE, GRID_REGION_STAT_DTYPE,
+                  grid_region_default_config, pack_regions, footprint_polygons, REGION_LINE, REGION_CIRCLE, REGION_ELLIPSE, REGION_POLYGON,
+                  REGION_OK, REGION_EMPTY, REGION_INVALID, REGION_MAX_VERTICES, REGION_MAX_WALK)
 
 __all__ = ["LioError", "ScanToMap", "S2MConfig", "S2MResult", "S2MProfile", "DeskewConfig",
            "lib_path", "load_library", "build_library", "deskew", "curvature", "imu_deskew_info",
@@ -37,4 +40,7 @@ __all__ = ["LioError", "ScanToMap", "S2MConfig", "S2MResult", "S2MProfile", "Des
            "MedianFillConfig", "MedianFillInfo", "PlanningMapBuffers", "median_fill", "median_fill_default_config",
            "Grid", "GridSampleConfig", "GridSampleInfo", "GridInfo", "grid_sample_default_config", "kf_store_planning_grid", "GRID_MAX_LAYERS",
            "GRID_NEAREST", "GRID_LINEAR", "GRID_CUBIC_CONVOLUTION", "GRID_CUBIC", "GRID_OUTSIDE", "GRID_LAYER_ELEVATION", "GRID_LAYER_FILLED",
-           "GRID_LAYER_TERRAIN"]
+           "GRID_LAYER_TERRAIN",
+           "GridRegion", "GridRegionConfig", "GridRegionStat", "GridRegionInfo", "GRID_REGION_DTYPE", "GRID_REGION_STAT_DTYPE",
+           "grid_region_default_config", "pack_regions", "footprint_polygons", "REGION_LINE", "REGION_CIRCLE", "REGION_ELLIPSE", "REGION_POLYGON",
+           "REGION_OK", "REGION_EMPTY", "REGION_INVALID", "REGION_MAX_VERTICES", "REGION_MAX_WALK"]

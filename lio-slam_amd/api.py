@@ -265,6 +265,29 @@ class GridInfo(C.Structure):
                 ("layer_mask", C.c_uint32), ("pad", C.c_int32)]
 
 
+class GridRegion(C.Structure):
+    """one region of lio_grid_region_reduce / lio_grid_region_cells (include/liogpu.h lio_grid_region)"""
+    _fields_ = [("kind", C.c_int32), ("n_vertices", C.c_int32), ("first_vertex", C.c_int64), ("p", C.c_double * 5)]
+
+
+class GridRegionConfig(C.Structure):
+    _fields_ = [("threshold", C.c_float), ("pad", C.c_int32)]
+
+
+class GridRegionStat(C.Structure):
+    _fields_ = [("sum", C.c_double), ("min", C.c_float), ("max", C.c_float), ("n_finite", C.c_int32), ("n_below", C.c_int32)]
+
+
+class GridRegionInfo(C.Structure):
+    _fields_ = [("n_ok", C.c_int64), ("n_empty", C.c_int64), ("n_invalid", C.c_int64), ("n_cells", C.c_int64)]
+
+
+GRID_REGION_DTYPE = np.dtype({"names": ["kind", "n_vertices", "first_vertex", "p"], "formats": [np.int32, np.int32, np.int64, (np.float64, 5)],
+                              "offsets": [0, 4, 8, 16], "itemsize": 56})
+GRID_REGION_STAT_DTYPE = np.dtype([("sum", np.float64), ("min", np.float32), ("max", np.float32), ("n_finite", np.int32), ("n_below", np.int32)])
+REGION_LINE, REGION_CIRCLE, REGION_ELLIPSE, REGION_POLYGON = 0, 1, 2, 3
+REGION_OK, REGION_EMPTY, REGION_INVALID = 0, 1, 2
+REGION_MAX_VERTICES, REGION_MAX_WALK = 64, 4096
 GRID_MAX_LAYERS = 16
 GRID_NEAREST, GRID_LINEAR, GRID_CUBIC_CONVOLUTION, GRID_CUBIC, GRID_OUTSIDE = 0, 1, 2, 3, 255
 GRID_LAYER_ELEVATION, GRID_LAYER_FILLED, GRID_LAYER_TERRAIN = 0, 1, 2
@@ -324,6 +347,7 @@ EXPORTS = [
     "lio_median_fill_default_config", "lio_median_fill", "lio_kf_store_planning_map",
     "lio_grid_sample_default_config", "lio_grid_create", "lio_grid_destroy", "lio_grid_set_layers", "lio_grid_get_layer", "lio_grid_info",
     "lio_grid_memory", "lio_grid_sample", "lio_kf_store_planning_grid", "lio_grid_debug_stage_ms",
+    "lio_grid_region_default_config", "lio_grid_region_reduce", "lio_grid_region_cells", "lio_grid_region_debug_stage_ms",
     "lio_debug_fast_f32_ops", "lio_debug_threshold_f32", "lio_debug_grid_plan",
 ]
 
@@ -506,6 +530,11 @@ def load_library():
     L.lio_grid_sample.argtypes = [vp, C.POINTER(i32), i32, C.POINTER(GridSampleConfig), vp, sz, vp, vp, C.POINTER(GridSampleInfo)]
     L.lio_kf_store_planning_grid.argtypes = L.lio_kf_store_planning_map.argtypes + [vp]
     L.lio_grid_debug_stage_ms.argtypes = [i32, C.POINTER(f32)]
+    L.lio_grid_region_default_config.argtypes = [C.POINTER(GridRegionConfig)]
+    L.lio_grid_region_default_config.restype = None
+    L.lio_grid_region_reduce.argtypes = [vp, C.POINTER(i32), i32, C.POINTER(GridRegionConfig), vp, sz, vp, sz, vp, vp, vp, C.POINTER(GridRegionInfo)]
+    L.lio_grid_region_cells.argtypes = [vp, vp, sz, vp, sz, vp, vp, sz, vp, C.POINTER(GridRegionInfo)]
+    L.lio_grid_region_debug_stage_ms.argtypes = [i32, C.POINTER(f32)]
     _LIB = L
     return L
 
@@ -1439,6 +1468,52 @@ def grid_sample_default_config(**overrides):
     return cfg
 
 
+# grid_map's region iterators on layers resident on the device
+def grid_region_default_config(**overrides):
+    cfg = GridRegionConfig()
+    load_library().lio_grid_region_default_config(C.byref(cfg))
+    for k, v in overrides.items():
+        if not hasattr(cfg, k):
+            raise AttributeError(k)
+        setattr(cfg, k, v)
+    return cfg
+
+
+_REGION_KINDS = {"line": (REGION_LINE, 4), "circle": (REGION_CIRCLE, 3), "ellipse": (REGION_ELLIPSE, 5), "polygon": (REGION_POLYGON, 0)}
+
+
+def pack_regions(regions):
+    """regions: ("line", x0, y0, x1, y1), ("circle", cx, cy, r), ("ellipse", cx, cy, lx, ly, rotation) and
+    ("polygon", [(x, y), ...]) tuples -> (a GRID_REGION_DTYPE array, the polygons' vertices [m, 2] float64)"""
+    rec = np.zeros(len(regions), GRID_REGION_DTYPE)
+    verts = []
+    for q, r in enumerate(regions):
+        kind, n_par = _REGION_KINDS[r[0]]
+        rec["kind"][q] = kind
+        if kind == REGION_POLYGON:
+            v = np.asarray(r[1], np.float64).reshape(-1, 2)
+            rec["first_vertex"][q], rec["n_vertices"][q] = len(verts), len(v)
+            verts.extend(v.tolist())
+        else:
+            rec["p"][q, :n_par] = r[1:1 + n_par]
+    return rec, np.asarray(verts, np.float64).reshape(-1, 2)
+
+
+def footprint_polygons(poses, length, width):
+    """poses: [n, 3] (x, y, yaw) -> (regions, vertices) of the n rectangles length (along the heading) x width centred on them:
+    what Grid.region_reduce takes for a vehicle footprint along a path"""
+    p = np.asarray(poses, np.float64).reshape(-1, 3)
+    c, s = np.cos(p[:, 2]), np.sin(p[:, 2])
+    hl, hw = 0.5 * float(length), 0.5 * float(width)
+    corners = np.array([[hl, hw], [-hl, hw], [-hl, -hw], [hl, -hw]])
+    verts = np.empty((len(p), 4, 2))
+    verts[:, :, 0] = p[:, None, 0] + c[:, None] * corners[None, :, 0] - s[:, None] * corners[None, :, 1]
+    verts[:, :, 1] = p[:, None, 1] + s[:, None] * corners[None, :, 0] + c[:, None] * corners[None, :, 1]
+    rec = np.zeros(len(p), GRID_REGION_DTYPE)
+    rec["kind"], rec["n_vertices"], rec["first_vertex"] = REGION_POLYGON, 4, 4 * np.arange(len(p))
+    return rec, verts.reshape(-1, 2)
+
+
 class Grid:
     """A set of up to GRID_MAX_LAYERS [rows, cols] float32 layers resident on the device: upload them (or let
     KeyframeStore.planning_grid leave its grids here), then sample them at positions."""
@@ -1481,6 +1556,50 @@ class Grid:
         _check(self.lib.lio_grid_sample(self.h, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids), C.byref(cfg), p.ctypes.data, len(p),
                                         val.ctypes.data, used.ctypes.data if want_method else None, C.byref(info)), "lio_grid_sample")
         return val, used, info
+
+    @staticmethod
+    def _regions(regions, vertices):
+        if isinstance(regions, np.ndarray) and regions.dtype == GRID_REGION_DTYPE:
+            rec = np.ascontiguousarray(regions)
+            verts = np.zeros((0, 2)) if vertices is None else vertices
+        else:
+            rec, verts = pack_regions(regions)
+        return rec, np.ascontiguousarray(verts, np.float64).reshape(-1, 2)
+
+    def region_reduce(self, regions, layer_ids=(0,), vertices=None, cfg=None, **overrides):
+        """grid_map's Line / Circle / Ellipse / PolygonIterator with the reduction a caller would loop for ->
+        (stats [n_layers, n] GRID_REGION_STAT_DTYPE, n_cells [n] int32, status [n] uint8, GridRegionInfo).
+        regions: the tuples pack_regions takes, or a GRID_REGION_DTYPE array with `vertices`; overrides: threshold."""
+        cfg = cfg or grid_region_default_config(**overrides)
+        rec, verts = self._regions(regions, vertices)
+        ids = np.ascontiguousarray(layer_ids, np.int32).reshape(-1)
+        n = len(rec)
+        stats = np.zeros((len(ids), n), GRID_REGION_STAT_DTYPE)
+        n_cells, status = np.zeros(n, np.int32), np.zeros(n, np.uint8)
+        info = GridRegionInfo()
+        _check(self.lib.lio_grid_region_reduce(self.h, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids), C.byref(cfg), rec.ctypes.data, n,
+                                               verts.ctypes.data, len(verts), stats.ctypes.data, n_cells.ctypes.data, status.ctypes.data, C.byref(info)),
+               "lio_grid_region_reduce")
+        return stats, n_cells, status, info
+
+    def region_cells(self, regions, vertices=None, cap_cells=None):
+        """-> (offsets [n + 1] int64, cells int32: column-major linear indices col * rows + row in the iterator's order,
+        status [n] uint8, GridRegionInfo).  cap_cells None: asks for the need first, then for the cells."""
+        rec, verts = self._regions(regions, vertices)
+        n = len(rec)
+        offsets, status = np.zeros(n + 1, np.int64), np.zeros(n, np.uint8)
+        info = GridRegionInfo()
+
+        def call(cells):
+            return self.lib.lio_grid_region_cells(self.h, rec.ctypes.data, n, verts.ctypes.data, len(verts), offsets.ctypes.data,
+                                                  cells.ctypes.data if cells.size else None, cells.size, status.ctypes.data, C.byref(info))
+        cells = np.zeros(0 if cap_cells is None else int(cap_cells), np.int32)
+        rc = call(cells)
+        if rc == -3 and cap_cells is None and 0 < offsets[n] < 2 ** 31:         # LIO_ERR_CAPACITY: offsets[n] tells the need
+            cells = np.zeros(int(offsets[n]), np.int32)
+            rc = call(cells)
+        _check(rc, "lio_grid_region_cells")
+        return offsets, cells[:int(offsets[n])], status, info
 
     def memory(self):
         """-> bytes the object holds on the device"""

@@ -17,15 +17,10 @@
 #include <vector>
 
 #include "lio_gridsample.h"
+#include "lio_gridobj.h"
 #include "lio_cloud.h"
 #include "lio_pool.h"
 
-struct lio_grid {
-    int device_id = 0;
-    unsigned mask = 0;             // bit k: layer k is present
-    LioTerrGeom G{};               // rows = cols = 0: no geometry yet
-    LioDevBuf<float> d_layer[LIO_GRID_MAX_LAYERS];
-};
 
 namespace {
 
@@ -229,6 +224,7 @@ try {
     if (!g || !bytes) return lio_fail(LIO_ERR_ARG, "null argument");
     size_t n = 0;
     for (const LioDevBuf<float>& b : g->d_layer) n += b.cap * sizeof(float);
+    for (const LioDevBytes& b : g->d_region) n += b.cap;
     *bytes = n;
     return LIO_OK;
 } LIO_CATCH

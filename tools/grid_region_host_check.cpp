@@ -1,0 +1,295 @@
+// grid_region_host_check.cpp -- the arithmetic of the region reductions (lio-slam_amd/csrc/lio_gridregion.h) run on the host:
+// the text the kernels run, over an accessor that counts every read outside the layer, on a lattice of lines, circles,
+// ellipses and polygons that puts centres, radii, vertices and endpoints on cell centres, cell edges, map edges and one step
+// outside, on grids with and without holes.  Stand-alone, needs no GPU:
+//
+//   hipcc -x hip --offload-arch=gfx950 -O1 -g -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
+//         -fno-sanitize-recover=undefined tools/grid_region_host_check.cpp -o /tmp/grid_region_host_check && /tmp/grid_region_host_check
+//
+// Prints one line per grid with the regions per status, the cells and a checksum (FNV-1a over every output word), then the
+// single-thread time per region and kind on a 550 x 400 layer, and "out-of-range accesses: 0, inconsistencies: 0" at the end;
+// the exit status is their sum (capped).
+//   grid_region_host_check dump ROWS COLS RES POS_X POS_Y THRESHOLD LAYER REGIONS N VERTICES NV OUT
+//       LAYER: rows x cols floats, column-major; REGIONS: N lio_grid_region; VERTICES: NV pairs of doubles.  OUT receives N
+//       lio_grid_region_stat, N int32 n_cells, N status bytes, N + 1 int64 offsets, then the cells (int32, column-major
+//       linear indices in the iterator's order).
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <chrono>
+#include <vector>
+
+#include "../lio-slam_amd/csrc/lio_gridregion.h"
+
+static long long g_oob = 0, g_bad = 0;
+
+struct CheckedLayer {
+    const float* g;
+    int rows, cols;
+    float at(int r, int c) const
+    {
+        if (r < 0 || r >= rows || c < 0 || c >= cols) { ++g_oob; return 0.0f; }
+        return g[(size_t)r + (size_t)c * (size_t)rows];
+    }
+};
+
+static void geometry(LioTerrGeom& G, int rows, int cols, double res, double px, double py)
+{
+    G.rows = rows; G.cols = cols; G.res = res;
+    const double pos[2] = { px, py };
+    for (int a = 0; a < 2; ++a) {
+        G.len[a] = (double)(a == 0 ? rows : cols) * res;
+        G.pos[a] = pos[a];
+        G.half[a] = 0.5 * G.len[a];
+        G.base[a] = pos[a] + (G.half[a] - 0.5 * res);
+    }
+}
+
+struct Result {
+    std::vector<lio_grid_region_stat> stat;
+    std::vector<int32_t> n_cells, cells;
+    std::vector<uint8_t> status;
+    std::vector<int64_t> offsets;
+};
+
+// both entry points' outputs for one layer, through the header alone: the plan's two halves, the cells by order, the
+// reduction by rank
+static void run(const LioTerrGeom& G, const std::vector<float>& layer, const std::vector<lio_grid_region>& regions, const std::vector<double>& verts,
+                float threshold, Result& o)
+{
+    const size_t n = regions.size();
+    o.stat.assign(n, lio_grid_region_stat());
+    o.n_cells.assign(n, 0);
+    o.status.assign(n, 0);
+    o.offsets.assign(n + 1, 0);
+    o.cells.clear();
+    const CheckedLayer in = { layer.data(), G.rows, G.cols };
+    for (size_t q = 0; q < n; ++q) {
+        LioRgRegion R;
+        lio_rg_pack(regions[q], &R);
+        int lo[2], hi[2], s[2];
+        for (int e = 0; e < 2; ++e) s[e] = lio_rg_plan_half(G, R, verts.data(), e, &lo[e], &hi[e]);
+        LioRgPlan P;
+        lio_rg_plan_join(R, s[0], lo[0], hi[0], s[1], lo[1], hi[1], &P);
+        const double* v = R.kind == LIO_REGION_POLYGON ? verts.data() + 2 * R.first_vertex : verts.data();
+        const int slots = lio_rg_n_slots(P);
+        int members = 0;
+        for (int t = 0; t < slots; ++t) {
+            int r, c;
+            lio_rg_cell_by_order(P, t, &r, &c);
+            if (r < 0 || r >= G.rows || c < 0 || c >= G.cols) { ++g_oob; continue; }
+            if (!lio_rg_member(G, R, v, r, c)) continue;
+            ++members;
+            o.cells.push_back(c * G.rows + r);
+        }
+        const int reduced = lio_rg_reduce_serial(G, R, v, P, in, threshold, &o.stat[q]);
+        if (reduced != members) ++g_bad;                   // the two numberings name the same cells
+        const lio_grid_region_stat& st = o.stat[q];
+        if (st.n_finite > members || st.n_below > st.n_finite || st.n_finite < 0 || st.n_below < 0) ++g_bad;
+        if (st.n_finite > 0 && !(st.min <= st.max)) ++g_bad;
+        if (P.status != LIO_REGION_OK && slots != 0) ++g_bad;
+        if (P.status == LIO_REGION_OK && R.kind == LIO_REGION_LINE) {              // a line's cells are neighbours, end to end
+            int r0, c0, r1, c1;
+            lio_rg_line_cell(P, 0, &r0, &c0);
+            if (r0 != lo[0] || c0 != hi[0]) ++g_bad;
+            for (int k = 1; k < slots; ++k) {
+                lio_rg_line_cell(P, k, &r1, &c1);
+                if (abs(r1 - r0) > 1 || abs(c1 - c0) > 1 || (r1 == r0 && c1 == c0)) ++g_bad;
+                r0 = r1; c0 = c1;
+            }
+            if (r0 != lo[1] || c0 != hi[1]) ++g_bad;
+        }
+        o.n_cells[q] = members;
+        o.status[q] = (uint8_t)(P.status == LIO_REGION_OK && members == 0 ? LIO_REGION_EMPTY : P.status);
+        o.offsets[q + 1] = o.offsets[q] + members;
+    }
+}
+
+static uint64_t fnv(uint64_t h, const void* p, size_t bytes)
+{
+    const unsigned char* b = (const unsigned char*)p;
+    for (size_t k = 0; k < bytes; ++k) h = (h ^ b[k]) * 0x100000001b3ull;
+    return h;
+}
+
+static uint64_t checksum(const Result& o)
+{
+    uint64_t h = 0xcbf29ce484222325ull;
+    for (const lio_grid_region_stat& s : o.stat) {
+        h = fnv(h, &s.sum, 8); h = fnv(h, &s.min, 4); h = fnv(h, &s.max, 4); h = fnv(h, &s.n_finite, 4); h = fnv(h, &s.n_below, 4);
+    }
+    h = fnv(h, o.n_cells.data(), 4 * o.n_cells.size());
+    h = fnv(h, o.status.data(), o.status.size());
+    h = fnv(h, o.cells.data(), 4 * o.cells.size());
+    return h;
+}
+
+static lio_grid_region region(int kind, double a, double b, double c, double d, double e)
+{
+    lio_grid_region r;
+    memset(&r, 0, sizeof(r));
+    r.kind = kind;
+    r.p[0] = a; r.p[1] = b; r.p[2] = c; r.p[3] = d; r.p[4] = e;
+    return r;
+}
+
+static void polygon(std::vector<lio_grid_region>& regions, std::vector<double>& verts, const double* xy, int nv)
+{
+    lio_grid_region r = region(LIO_REGION_POLYGON, 0, 0, 0, 0, 0);
+    r.first_vertex = (int64_t)(verts.size() / 2);
+    r.n_vertices = nv;
+    verts.insert(verts.end(), xy, xy + 2 * nv);
+    regions.push_back(r);
+}
+
+static void lattice(const LioTerrGeom& G, std::vector<lio_grid_region>& regions, std::vector<double>& verts)
+{
+    std::vector<double> ax[2];
+    for (int a = 0; a < 2; ++a) {
+        const int n = a == 0 ? G.rows : G.cols;
+        const double hi = G.pos[a] + G.half[a], lo = G.pos[a] - G.half[a];
+        ax[a].push_back(hi + G.res); ax[a].push_back(hi + 0.3 * G.res);
+        for (int k = 0; k <= n; k += (n > 12 ? n / 6 : 1)) {
+            ax[a].push_back(hi - k * G.res);
+            if (k < n) ax[a].push_back(hi - (k + 0.5) * G.res);
+        }
+        ax[a].push_back(lo); ax[a].push_back(lo - 0.3 * G.res); ax[a].push_back(lo - G.res);
+    }
+    const double res = G.res, radii[] = { 0.0, 0.5 * res, res, 1.5 * res, 2.5 * res + 1e-9, 40.0 * res };
+    int k = 0;
+    std::vector<double> px, py;
+    for (double x : ax[0])
+        for (double y : ax[1]) { px.push_back(x); py.push_back(y); }
+    for (size_t q = 0; q < px.size(); ++q, ++k) {
+        const double x = px[q], y = py[q];
+        regions.push_back(region(LIO_REGION_CIRCLE, x, y, radii[k % 6], 0, 0));
+        regions.push_back(region(LIO_REGION_ELLIPSE, x, y, (1 + k % 4) * res, (0.5 + k % 3) * res, 0.4 * (k % 8) - 1.0));
+        const size_t o = (7 * q + 3) % px.size();
+        regions.push_back(region(LIO_REGION_LINE, x, y, px[o], py[o], 0));
+        const double w = (0.5 + k % 3) * res, h = (1 + k % 2) * res;
+        const double box[] = { x + w, y + h, x + w, y - h, x - w, y - h, x - w, y + h };
+        polygon(regions, verts, box, 4);
+        const double tri[] = { x, y, x + 2 * w, y - 0.5 * h, x + 0.5 * w, y - 2 * h };
+        polygon(regions, verts, tri, 3);
+    }
+    const double nan = __builtin_nan(""), inf = __builtin_huge_val(), cx = G.pos[0], cy = G.pos[1];
+    regions.push_back(region(LIO_REGION_CIRCLE, nan, cy, res, 0, 0));
+    regions.push_back(region(LIO_REGION_CIRCLE, cx, cy, -res, 0, 0));
+    regions.push_back(region(LIO_REGION_CIRCLE, cx, cy, inf, 0, 0));
+    regions.push_back(region(LIO_REGION_ELLIPSE, cx, cy, 0.0, res, 0.0));
+    regions.push_back(region(LIO_REGION_ELLIPSE, cx, cy, res, res, inf));
+    regions.push_back(region(LIO_REGION_LINE, cx, cy, inf, cy, 0));
+    regions.push_back(region(LIO_REGION_LINE, cx + G.half[0] + (LIO_REGION_MAX_WALK + 10) * res, cy, cx, cy, 0));
+    regions.push_back(region(LIO_REGION_LINE, cx, cy, cx, cy - G.half[1] - (LIO_REGION_MAX_WALK + 10) * res, 0));
+    const double bad[] = { cx, cy, nan, cy, cx, cy + res };
+    polygon(regions, verts, bad, 3);
+}
+
+static bool read_file(const char* path, void* dst, size_t bytes)
+{
+    if (!bytes) return true;
+    FILE* f = fopen(path, "rb");
+    if (!f) return false;
+    const size_t got = fread(dst, 1, bytes, f);
+    fclose(f);
+    return got == bytes;
+}
+
+int main(int argc, char** argv)
+{
+    if (argc >= 14 && !strcmp(argv[1], "dump")) {
+        const int rows = atoi(argv[2]), cols = atoi(argv[3]);
+        const double res = atof(argv[4]);
+        const float threshold = (float)atof(argv[7]);
+        const size_t n = (size_t)atoll(argv[10]), nv = (size_t)atoll(argv[12]);
+        if (rows < 1 || cols < 1 || !(res > 0.0)) { fprintf(stderr, "bad arguments\n"); return 2; }
+        LioTerrGeom G;
+        geometry(G, rows, cols, res, atof(argv[5]), atof(argv[6]));
+        std::vector<float> layer((size_t)rows * (size_t)cols);
+        std::vector<lio_grid_region> regions(n);
+        std::vector<double> verts(2 * nv + 2);
+        if (!read_file(argv[8], layer.data(), 4 * layer.size()) || !read_file(argv[9], regions.data(), sizeof(lio_grid_region) * n) ||
+            !read_file(argv[11], verts.data(), 16 * nv)) { fprintf(stderr, "cannot read the inputs\n"); return 2; }
+        for (const lio_grid_region& r : regions) {         // what the library refuses with LIO_ERR_ARG
+            const bool poly = r.kind == LIO_REGION_POLYGON;
+            if (r.kind < 0 || r.kind > 3 || (poly && (r.n_vertices < 3 || r.n_vertices > LIO_REGION_MAX_VERTICES || r.first_vertex < 0 ||
+                                                       (size_t)r.first_vertex + (size_t)r.n_vertices > nv))) { fprintf(stderr, "bad region\n"); return 2; }
+        }
+        Result o;
+        run(G, layer, regions, verts, threshold, o);
+        FILE* f = fopen(argv[13], "wb");
+        if (!f) { fprintf(stderr, "cannot write\n"); return 2; }
+        fwrite(o.stat.data(), sizeof(lio_grid_region_stat), n, f);
+        fwrite(o.n_cells.data(), 4, n, f);
+        fwrite(o.status.data(), 1, n, f);
+        fwrite(o.offsets.data(), 8, n + 1, f);
+        fwrite(o.cells.data(), 4, o.cells.size(), f);
+        fclose(f);
+        printf("out-of-range accesses: %lld, inconsistencies: %lld\n", g_oob, g_bad);
+        return g_oob + g_bad ? 1 : 0;
+    }
+    const int shapes[][2] = { { 1, 1 }, { 3, 3 }, { 8, 5 }, { 5, 8 }, { 70, 50 } };
+    for (const auto& s : shapes)
+        for (int holes = 0; holes < 2; ++holes) {
+            LioTerrGeom G;
+            geometry(G, s[0], s[1], holes ? 0.2 : 1.0, holes ? 1e3 : 0.0, holes ? -3e3 : 0.0);
+            std::vector<float> layer((size_t)s[0] * (size_t)s[1]);
+            for (size_t k = 0; k < layer.size(); ++k) layer[k] = 0.001f * (float)((k * 37) % 1000);
+            if (holes)
+                for (size_t k = 0; k < layer.size(); ++k) {
+                    if (k % 5 == 1) layer[k] = __builtin_nanf("");
+                    if (k % 11 == 3) layer[k] = __builtin_huge_valf();
+                    if (k % 7 == 4) layer[k] = -0.0f;
+                    if (k % 7 == 5) layer[k] = 0.0f;
+                }
+            std::vector<lio_grid_region> regions;
+            std::vector<double> verts;
+            lattice(G, regions, verts);
+            Result o;
+            run(G, layer, regions, verts, 0.5f, o);
+            long long cnt[3] = { 0, 0, 0 };
+            for (uint8_t st : o.status) ++cnt[st > 2 ? 2 : st];
+            printf("%2dx%-2d %s regions %5zu  ok %5lld empty %5lld invalid %5lld  cells %8lld  checksum %016llx\n", s[0], s[1], holes ? "holes" : "plain",
+                   regions.size(), cnt[0], cnt[1], cnt[2], (long long)o.offsets.back(), (unsigned long long)checksum(o));
+        }
+    {                                                      // the single-thread cost of a region
+        LioTerrGeom G;
+        geometry(G, 550, 400, 0.2, 0.0, 0.0);
+        std::vector<float> layer((size_t)550 * 400);
+        for (size_t k = 0; k < layer.size(); ++k) layer[k] = 0.001f * (float)(k % 977);
+        const char* names[] = { "line (40 cells)", "circle (r 1 m)", "ellipse (4 x 2 m)", "polygon (4 x 2 m)" };
+        for (int kind = 0; kind < 4; ++kind) {
+            uint32_t seed = 12345u;
+            std::vector<lio_grid_region> regions;
+            std::vector<double> verts;
+            for (int q = 0; q < 20000; ++q) {
+                seed = seed * 1664525u + 1013904223u;
+                const double x = ((double)(seed >> 8) / 16777216.0 - 0.5) * 0.9 * G.len[0];
+                seed = seed * 1664525u + 1013904223u;
+                const double y = ((double)(seed >> 8) / 16777216.0 - 0.5) * 0.9 * G.len[1];
+                seed = seed * 1664525u + 1013904223u;
+                const double yaw = (double)(seed >> 8) / 16777216.0 * 6.283185307179586;
+                const double c = cos(yaw), s = sin(yaw);
+                if (kind == LIO_REGION_LINE) regions.push_back(region(kind, x, y, x + 8.0 * c, y + 8.0 * s, 0));
+                else if (kind == LIO_REGION_CIRCLE) regions.push_back(region(kind, x, y, 1.0, 0, 0));
+                else if (kind == LIO_REGION_ELLIPSE) regions.push_back(region(kind, x, y, 4.0, 2.0, yaw));
+                else {
+                    const double hx = 2.0, hy = 1.0;
+                    const double box[] = { x + c * hx - s * hy, y + s * hx + c * hy, x - c * hx - s * hy, y - s * hx + c * hy,
+                                           x - c * hx + s * hy, y - s * hx - c * hy, x + c * hx + s * hy, y + s * hx - c * hy };
+                    polygon(regions, verts, box, 4);
+                }
+            }
+            Result o;
+            const auto t0 = std::chrono::steady_clock::now();
+            run(G, layer, regions, verts, 0.5f, o);
+            const double ns = std::chrono::duration<double, std::nano>(std::chrono::steady_clock::now() - t0).count();
+            printf("single thread, 550 x 400, 1 layer, %-18s %9.1f ns per region, %6.1f cells per region  (checksum %016llx)\n", names[kind],
+                   ns / (double)regions.size(), (double)o.offsets.back() / (double)regions.size(), (unsigned long long)checksum(o));
+        }
+    }
+    printf("out-of-range accesses: %lld, inconsistencies: %lld\n", g_oob, g_bad);
+    const long long rc = g_oob + g_bad;
+    return rc > 100 ? 100 : (int)rc;
+}
