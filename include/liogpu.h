@@ -745,6 +745,12 @@ int  lio_sc_distance(int32_t device_id, const float *desc_a, const float *desc_b
 int  lio_sor_filter(int32_t device_id, const void *pts, size_t n, size_t stride_bytes, int32_t mean_k, float stddev_mul,
                     void *out, size_t out_stride_bytes, size_t *n_out, float *mean_dist, double stats[3]);
 
+/* Test hook, read-only: the search grid lio_sor_filter lays over the cloud at `mean_k`, by the very code the filter runs (the
+ * box of the coordinates within 1e15 m, the trial grid, the edge for (mean_k + 1) / 3 points per occupied cell).  any = 0: no
+ * participating point on some axis, the grid is one empty cell at the origin (edge 1).  occupied = -1: no trial grid was laid.
+ * An empty cloud: LIO_OK, every field 0 but occupied = -1.  mean_k outside [1, 32] -> LIO_ERR_ARG. */
+int  lio_sor_debug_grid(int32_t device_id, const void *pts, size_t n, size_t stride_bytes, int32_t mean_k, lio_icp_grid_info *out);
+
 typedef struct lio_local_map_config {
     int32_t n_keyframes;      /* localMapKeyFramesNumber  UT:219  30   */
     float   front, left, back, right; /* localMapFront .. localMapRight UT:220-223  70, 40, 20, 40 */

@@ -10,7 +10,7 @@ from .api import (LioError, ScanToMap, S2MConfig, S2MResult, S2MProfile, DeskewC
                   transform_update, pack_xyzirt, deskew_default_config, voxel_grid, assemble_map, KeyframeStore, STATUS_NAMES,
                   extract_features, FeatureConfig, range_image, RangeImageConfig, PinnedBuffer, DeviceBuffer, PC2Layout, deskew_pc2,
                   NearbyConfig, nearby_default_config, IcpConfig, IcpResult, IcpClouds, ICP_STATES, icp_default_config, icp_align,
-                  icp_debug_trace, IcpGridInfo, icp_debug_grid, ScConfig, ScResult, sc_default_config, sc_make, sc_distance,
+                  icp_debug_trace, IcpGridInfo, icp_debug_grid, sor_debug_grid, ScConfig, ScResult, sc_default_config, sc_make, sc_distance,
                   LocalMapConfig, LocalMapInfo, sor_filter, local_map_default_config,
                   HeightMapConfig, HeightMapInfo, height_map, height_map_default_config,
                   TerrainConfig, TerrainInfo, TERRAIN_LAYERS, terrain_layers, terrain_default_config,
@@ -30,7 +30,7 @@ __all__ = ["LioError", "ScanToMap", "S2MConfig", "S2MResult", "S2MProfile", "Des
            "transform_update", "pack_xyzirt", "deskew_default_config", "voxel_grid", "assemble_map", "KeyframeStore", "STATUS_NAMES",
            "extract_features", "FeatureConfig", "range_image", "RangeImageConfig", "PinnedBuffer", "DeviceBuffer", "PC2Layout", "deskew_pc2",
            "NearbyConfig", "nearby_default_config", "IcpConfig", "IcpResult", "IcpClouds", "ICP_STATES", "icp_default_config", "icp_align",
-           "icp_debug_trace", "IcpGridInfo", "icp_debug_grid", "ScConfig", "ScResult", "sc_default_config", "sc_make", "sc_distance",
+           "icp_debug_trace", "IcpGridInfo", "icp_debug_grid", "sor_debug_grid", "ScConfig", "ScResult", "sc_default_config", "sc_make", "sc_distance",
            "LocalMapConfig", "LocalMapInfo", "sor_filter", "local_map_default_config",
            "HeightMapConfig", "HeightMapInfo", "height_map", "height_map_default_config",
            "TerrainConfig", "TerrainInfo", "TERRAIN_LAYERS", "terrain_layers", "terrain_default_config",

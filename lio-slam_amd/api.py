@@ -332,7 +332,7 @@ EXPORTS = [
     "lio_host_unregister", "lio_s2m_set_shard_plan", "lio_s2m_register_pc2", "lio_deskew_pc2", "lio_kf_store_add_device", "lio_kf_store_add_from_handle",
     "lio_s2m_register_raw", "lio_s2m_debug_persist_spin", "lio_device_alloc", "lio_device_free", "lio_device_upload",
     "lio_nearby_default_config", "lio_kf_store_set_poses", "lio_assemble_map_nearby", "lio_debug_plane_fit",
-    "lio_icp_default_config", "lio_icp_align", "lio_kf_store_loop_icp", "lio_kf_store_detect_loop", "lio_icp_debug_trace", "lio_icp_debug_grid",
+    "lio_icp_default_config", "lio_icp_align", "lio_kf_store_loop_icp", "lio_kf_store_detect_loop", "lio_icp_debug_trace", "lio_icp_debug_grid", "lio_sor_debug_grid",
     "lio_sc_default_config", "lio_sc_make", "lio_sc_distance", "lio_kf_store_sc_add", "lio_kf_store_sc_add_device",
     "lio_kf_store_sc_add_from_handle", "lio_kf_store_sc_count", "lio_kf_store_sc_geometry", "lio_kf_store_sc_get", "lio_kf_store_sc_detect",
     "lio_sor_filter", "lio_local_map_default_config", "lio_kf_store_local_map",
@@ -1208,6 +1208,16 @@ def sor_filter(xyzi, mean_k=10, stddev_mul=1.0, device_id=0):
     rc = _check(load_library().lio_sor_filter(device_id, rec.ctypes.data, n, 32, int(mean_k), float(stddev_mul), out.ctypes.data, 32,
                                               C.byref(n_out), dist.ctypes.data, stats), "lio_sor_filter")
     return _from_records(out, n_out.value), dist[:n].copy(), tuple(stats), rc
+
+
+def sor_debug_grid(xyz, mean_k=10, device_id=0):
+    """Test hook, read-only -> IcpGridInfo: the grid lio_sor_filter lays over the cloud at `mean_k`, by the filter's own code."""
+    pts, stride = _as_points(xyz)
+    out = IcpGridInfo()
+    fn = load_library().lio_sor_debug_grid         # bound on first use: A/B runs load older builds through LIOGPU_LIB
+    fn.argtypes = [C.c_int32, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int32, C.POINTER(IcpGridInfo)]
+    _check(fn(device_id, pts.ctypes.data, len(pts), stride, int(mean_k), C.byref(out)), "lio_sor_debug_grid")
+    return out
 
 
 def local_map_default_config(**overrides):

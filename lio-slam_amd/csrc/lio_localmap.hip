@@ -232,6 +232,42 @@ int lio_sor_check(int32_t mean_k, float stddev_mul)
     return LIO_OK;
 }
 
+// The filter's steps up to its grid: SoA copy, the box of the participating coordinates (per axis), lio_icp_choose_grid at
+// (mean_k + 1) / 3 points per occupied cell.  lio_sor_device and the test hook lio_sor_debug_grid both go through here.
+namespace {
+struct SorTarget {
+    LioTemp tx, ty, tz, t4;
+    LioGrid g;
+    float edge = 1.0f;
+    bool any = false;         // the box holds a point on every axis (else: one empty cell at the origin)
+    int occupied = -1;        // occupied cells of the trial grid (-1: none was laid, the box is a point)
+};
+
+int sor_target_grid(const float4* d_pts, int n, int mean_k, hipStream_t s, SorTarget& T)
+{
+    LioTemp bbox;
+    HIPCHK(T.tx.alloc(sizeof(float) * (size_t)n)); HIPCHK(T.ty.alloc(sizeof(float) * (size_t)n)); HIPCHK(T.tz.alloc(sizeof(float) * (size_t)n));
+    HIPCHK(T.t4.alloc(sizeof(float4) * (size_t)n));
+    HIPCHK(bbox.alloc(6 * sizeof(unsigned)));
+    lio_launch_xyzi4_to_soa(d_pts, n, T.tx.as<float>(), T.ty.as<float>(), T.tz.as<float>(), T.t4.as<float4>(), s);
+    unsigned hb[6];
+    lio_ord_box_clear(hb);
+    HIPCHK(hipMemcpyAsync(bbox.p, hb, sizeof(hb), hipMemcpyHostToDevice, s));
+    lio_launch_map_bbox(T.tx.as<float>(), T.ty.as<float>(), T.tz.as<float>(), n, bbox.as<unsigned>(), s);
+    HIPCHK(hipMemcpyAsync(hb, bbox.p, sizeof(hb), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    float mn[3], mx[3];
+    lio_ord_box_decode(hb, mn, mx);
+    T.any = true;
+    for (int a = 0; a < 3; ++a) T.any = T.any && hb[a] != LIO_ORD_NO_MIN && mn[a] <= mx[a];
+    if (!T.any) { mn[0] = mn[1] = mn[2] = 0.0f; mx[0] = mx[1] = mx[2] = 0.0f; }       // no finite point: one empty cell
+    // Edge: the walk stops after shell 1 once the sphere of one edge around the point holds the k entries; on a surface
+    // that sphere holds about pi times the points of a cell, so k / 3 per occupied cell (3.7 at mean_k 10).
+    return lio_icp_choose_grid(T.tx.as<float>(), T.ty.as<float>(), T.tz.as<float>(), n, mn, mx, (float)(mean_k + 1) / 3.0f, s, &T.g, &T.edge,
+                               &T.occupied);
+}
+}  // namespace
+
 int lio_sor_device(const float4* d_pts, int n, int mean_k, float stddev_mul, LioTemp& out, int* n_out, float* d_mean_dist,
                    LioSorReport* rep, hipStream_t s)
 {
@@ -240,30 +276,14 @@ int lio_sor_device(const float4* d_pts, int n, int mean_k, float stddev_mul, Lio
     int rc = lio_sor_check(mean_k, stddev_mul);
     if (rc != LIO_OK) return rc;
     if (n <= 0) { rep->passthrough = 1; rep->threshold = INFINITY; HIPCHK(out.alloc(16)); return 1; }
-    // ---- the cloud as its own search target: SoA, box of its finite points, grid, cell sort (as the alignment's target)
-    LioTemp tx, ty, tz, t4, bbox, dist;
-    HIPCHK(tx.alloc(sizeof(float) * (size_t)n)); HIPCHK(ty.alloc(sizeof(float) * (size_t)n)); HIPCHK(tz.alloc(sizeof(float) * (size_t)n));
-    HIPCHK(t4.alloc(sizeof(float4) * (size_t)n));
-    HIPCHK(bbox.alloc(6 * sizeof(unsigned)));
+    // ---- the cloud as its own search target: SoA, box of its finite points, grid (sor_target_grid), cell sort
+    SorTarget tg;
+    LioTemp dist;
     if (!d_mean_dist) { HIPCHK(dist.alloc(sizeof(float) * (size_t)n)); d_mean_dist = dist.as<float>(); }
-    lio_launch_xyzi4_to_soa(d_pts, n, tx.as<float>(), ty.as<float>(), tz.as<float>(), t4.as<float4>(), s);
-    unsigned hb[6];
-    lio_ord_box_clear(hb);
-    HIPCHK(hipMemcpyAsync(bbox.p, hb, sizeof(hb), hipMemcpyHostToDevice, s));
-    lio_launch_map_bbox(tx.as<float>(), ty.as<float>(), tz.as<float>(), n, bbox.as<unsigned>(), s);
-    HIPCHK(hipMemcpyAsync(hb, bbox.p, sizeof(hb), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    float mn[3], mx[3];
-    lio_ord_box_decode(hb, mn, mx);
-    bool any = true;
-    for (int a = 0; a < 3; ++a) any = any && hb[a] != LIO_ORD_NO_MIN && mn[a] <= mx[a];
-    if (!any) { mn[0] = mn[1] = mn[2] = 0.0f; mx[0] = mx[1] = mx[2] = 0.0f; }       // no finite point: one empty cell
-    // Edge: the walk stops after shell 1 once the sphere of one edge around the point holds the k entries; on a surface
-    // that sphere holds about pi times the points of a cell, so k / 3 per occupied cell (3.7 at mean_k 10).
-    LioGrid g;
-    float edge = 1.0f;
-    if ((rc = lio_icp_choose_grid(tx.as<float>(), ty.as<float>(), tz.as<float>(), n, mn, mx, (float)(mean_k + 1) / 3.0f, s, &g, &edge)) != LIO_OK)
-        return rc;
+    if ((rc = sor_target_grid(d_pts, n, mean_k, s, tg)) != LIO_OK) return rc;
+    LioTemp &tx = tg.tx, &ty = tg.ty, &tz = tg.tz;
+    const LioGrid& g = tg.g;
+    const float edge = tg.edge;
     LioTemp cell_of, cell_count, cell_start, tiles, sorted, partials, d_st;
     const int n_wg = (n + 255) / 256;
     HIPCHK(cell_of.alloc(sizeof(int) * (size_t)n));
@@ -324,6 +344,31 @@ try {
     if (stats) { stats[0] = rep.mean; stats[1] = rep.stddev; stats[2] = rep.threshold; }
     *n_out = (size_t)no;
     return rc;
+} LIO_CATCH
+
+extern "C" int lio_sor_debug_grid(int32_t device_id, const void* pts, size_t n, size_t stride, int32_t mean_k, lio_icp_grid_info* out)
+try {
+    if (!out || (n && !pts)) return lio_fail(LIO_ERR_ARG, "null argument");
+    if (stride < 12 || (stride & 3)) return lio_fail(LIO_ERR_ARG, "stride must be >= 12 and a multiple of 4");
+    if (n > 0x7fffffffull - 1024) return lio_fail(LIO_ERR_CAPACITY, "cloud too large");
+    int rc = lio_sor_check(mean_k, 1.0f);
+    if (rc != LIO_OK) return rc;
+    memset(out, 0, sizeof(*out));
+    out->occupied = -1;
+    if ((rc = lio_check_device(device_id)) != LIO_OK) return rc;
+    if (!n) return LIO_OK;
+    hipStream_t s = nullptr;
+    LioTemp raw, xyzi;
+    HIPCHK(xyzi.alloc(n * sizeof(float4)));
+    if ((rc = lio_upload_xyzi(pts, n, stride, stride >= 20 ? 16 : -1, raw, xyzi.as<float4>(), s)) != LIO_OK) return rc;
+    SorTarget tg;
+    if ((rc = sor_target_grid(xyzi.as<float4>(), (int)n, mean_k, s, tg)) != LIO_OK) return rc;
+    out->any = tg.any ? 1 : 0;
+    out->origin[0] = tg.g.ox; out->origin[1] = tg.g.oy; out->origin[2] = tg.g.oz;
+    out->edge = tg.edge; out->inv_cell = tg.g.inv_cell;
+    out->nx = tg.g.nx; out->ny = tg.g.ny; out->nz = tg.g.nz; out->n_cells = tg.g.n_cells;
+    out->occupied = tg.occupied;
+    return LIO_OK;
 } LIO_CATCH
 
 extern "C" void lio_local_map_default_config(lio_local_map_config* cfg)

@@ -70,8 +70,9 @@ def _lay(mn, mx, e):
     return inv, n
 
 
-def grid_of(target):
-    """The grid lio_icp_align lays over `target` (lio_icp_choose_grid with per_cell = 4), in np.float32 arithmetic:
+def grid_of(target, per_cell=F32(4.0)):
+    """The grid lio_icp_choose_grid lays over `target` at `per_cell` points per occupied cell (the alignment's 4; the outlier
+    filter passes (mean_k + 1) / 3, tests/localmap_restate.py sor_grid), in np.float32 arithmetic:
     -> dict(origin [3], edge, inv_cell, nx, ny, nz, n_cells, occupied) or None when an axis has no coordinate in range.
     occupied = -1: the box is a point, no trial grid, edge 1."""
     t = np.asarray(target, np.float32)[:, :3]
@@ -98,7 +99,7 @@ def grid_of(target):
         c = c[inside]
         occ = len(np.unique((c[:, 2] * n0[1] + c[:, 1]) * n0[0] + c[:, 0]))
         ppc = F32(n) / F32(occ) if occ > 0 else F32(1.0)
-        e = e0 * np.sqrt(F32(4.0) / ppc)
+        e = e0 * np.sqrt(F32(per_cell) / ppc)
         e = min(max(e, ext / F32(500.0)), ext)
         while True:
             _, nn = _lay(mn, mx, e)

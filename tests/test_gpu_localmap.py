@@ -1,7 +1,9 @@
 """The planning local map on the device (lio_sor_filter, lio_kf_store_local_map) against the numpy restatement of
 tests/localmap_restate.py, stage by stage.  The inputs of the filter tests are tests/test_localmap_cpu.py's, which shows
-that none of their points lies inside the threshold bracket: the kept sets must be equal."""
+that none of their points lies inside the threshold bracket: the kept sets must be equal.  At the end: the device's crop on
+its four limits, the compaction's patterns beyond 256 workgroups, and crops that leave 1, mean_k and mean_k + 1 points."""
 import ctypes as C
+import math
 import os
 import sys
 
@@ -24,20 +26,31 @@ def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
-def check_filter(got, ref, pts, what):
-    """mean_dist bit for bit, stats to 64 n 2^-52, the kept records = the restatement's (its bracket is empty)."""
+def stat_difference(a, b):
+    """Relative difference of a statistic from the restatement's; NaN must meet NaN, and 0 and inf themselves (inf otherwise)."""
+    if math.isnan(b) or math.isnan(a):
+        return 0.0 if math.isnan(a) and math.isnan(b) else math.inf
+    if b in (0.0, math.inf):
+        return 0.0 if a == b else math.inf
+    return abs(a - b) / abs(b)
+
+
+def check_filter(got, ref, pts, what, bracket=True):
+    """mean_dist bit for bit, stats to 64 n 2^-52 (NaN = NaN and 0 = 0 exactly), the kept records = the restatement's (its
+    bracket is empty; bracket=False for the inputs of tests/sor_cases.py whose note replaces that rule by a sign condition)."""
     inl, dist, stats, rc = got
     n = ref["n_finite"]
     assert rc == ref["rc"], what
     nan_d, nan_r = np.isnan(dist), np.isnan(ref["mean_dist"])
     assert np.array_equal(nan_d, nan_r), what
     n_diff = int((bits(dist)[~nan_d] != bits(ref["mean_dist"])[~nan_r]).sum())
-    rel = [abs(a - b) / abs(b) if b not in (0.0, np.inf) else float(a != b) for a, b in zip(stats, ref["stats"])]
+    rel = [stat_difference(a, b) for a, b in zip(stats, ref["stats"])]
     print(f"  {what}: n {n}, kept {len(inl)} / restatement {int(ref['keep'].sum())}, mean_dist differing in {n_diff} points, "
           f"stats {stats} relative differences {rel} (bound {64 * n * EPS52:.3g})")
     assert n_diff == 0, what
     assert max(rel) <= 64 * n * EPS52, what
-    assert_bracket_empty(ref, what)
+    if bracket:
+        assert_bracket_empty(ref, what)
     assert np.array_equal(bits(inl), bits(pts[ref["keep"]])), what
 
 
@@ -211,3 +224,108 @@ def test_local_map_follows_the_poses_and_leaves_the_store_alone(pkg, street):
     out1, _, _ = st.local_map(POSE, cfg)
     assert np.array_equal(bits(out1), bits(stages(pkg, c, 6, poses=moved)["inliers"])) and not np.array_equal(bits(out1), bits(out0))
     st.close()
+
+
+# ---- the crop and the pass-through at their edges (one keyframe under the zero pose, the vehicle at the zero pose) ---------
+ZERO = np.zeros(6, np.float32)
+
+
+def one_keyframe_store(pkg, oracle, cloud):
+    """A store whose only keyframe is `cloud` under the zero pose.  First, on the CPU: K6 under the zero pose returns its
+    input bits (the oracle's transform; a NaN stays a NaN), so what reaches the crop is the cloud itself."""
+    moved = oracle.transform_point_cloud(cloud, ZERO)
+    fin = np.isfinite(cloud).all(1)
+    assert np.array_equal(bits(moved[fin]), bits(cloud[fin])) and np.isnan(moved[~fin]).any(1).all()
+    st = pkg.KeyframeStore()
+    st.add(cloud)
+    st.set_poses(0, ZERO[None], times=[0.0])
+    return st
+
+
+def limit_records():
+    """The records of tests/test_localmap_cpu.py::test_crop_keeps_its_four_limits: each limit, one ulp outside, a NaN."""
+    up, dn = lambda v: np.nextafter(np.float32(v), np.float32(np.inf)), lambda v: np.nextafter(np.float32(v), np.float32(-np.inf))
+    return np.array([[40, 0, 1, 7], [up(40), 0, 1, 7], [-40, 0, 1, 7], [dn(-40), 0, 1, 7],
+                     [0, 70, 1, 7], [0, up(70), 1, 7], [0, -20, 1, 7], [0, dn(-20), 1, 7], [np.nan, 0, 0, 7]], np.float32)
+
+
+def test_device_crop_keeps_its_four_limits(pkg, oracle):
+    pts = limit_records()
+    want, keep = L.crop(pts, ZERO)
+    assert keep.tolist() == [True, False] * 4 + [False] and np.array_equal(bits(want), bits(pts[keep]))
+    st = one_keyframe_store(pkg, oracle, pts)
+    out, info, rc = st.local_map(ZERO, pkg.local_map_default_config(remove_outliers=0, downsample=0))
+    st.close()
+    assert rc == 0 and (info.n_summed, info.n_cropped, info.n_inliers, info.n_out) == (9, 4, 4, 4)
+    assert np.array_equal(bits(out), bits(pts[keep]))
+
+
+@pytest.fixture(scope="module")
+def compaction_case():
+    """65 793 records = 257 workgroups + 1 (tests/sor_cases.py wg_257, the size case): from there the scan over the workgroups'
+    counts takes its second chunk.  Rejected records are moved out of the crop by workgroup and lane."""
+    import sor_cases as S
+    cloud = S.build_case("wg_257")[0].copy()
+    n = len(cloud)
+    wg, lane = np.arange(n) // 256, np.arange(n) % 256
+    keep = np.ones(n, bool)
+    keep[wg == 0] = False                                                     # a whole workgroup of rejects, the first
+    keep[wg == 130] = False                                                   # ... and one in the middle
+    keep[(wg == 1) & (lane != 0)] = False                                     # survivors only in lane 0
+    keep[(wg == 2) & (lane != 255)] = False                                   # ... only in lane 255
+    keep[(wg == 3) & (lane != 63) & (lane != 64)] = False                     # ... only across the wave boundary
+    keep[(wg == 255) & (lane % 2 == 0)] = False                               # around the scan's chunk boundary
+    keep[(wg == 256) & (lane < 128)] = False
+    assert keep[wg == 4].all() and keep[n - 1] and wg[n - 1] == 257           # whole workgroups kept; the last, one-point workgroup kept
+    cloud[~keep, 0] += np.float32(200.0)
+    crop = dict(front=70.0, left=40.0, back=20.0, right=70.0)
+    want, kept = L.crop(cloud, ZERO, **crop)
+    assert np.array_equal(kept, keep) and np.array_equal(bits(want), bits(cloud[keep]))
+    ref = L.sor(want, 1, 1.0, knn=L.knn_d2_fast)
+    assert_bracket_empty(ref, "compaction")
+    return dict(cloud=cloud, crop=crop, want=want, sor=ref)
+
+
+def test_compaction_patterns_beyond_256_workgroups(pkg, oracle, compaction_case):
+    c = compaction_case
+    st = one_keyframe_store(pkg, oracle, c["cloud"])
+    out, info, rc = st.local_map(ZERO, pkg.local_map_default_config(remove_outliers=0, downsample=0, **c["crop"]))
+    assert rc == 0 and (info.n_summed, info.n_cropped, info.n_out) == (len(c["cloud"]), len(c["want"]), len(c["want"]))
+    assert np.array_equal(bits(out), bits(c["want"]))                          # = L.crop, in order
+    # the filter on that crop, alone and inside the chain
+    check_filter(pkg.sor_filter(c["want"], 1, 1.0), c["sor"], c["want"], "the filter on the crop")
+    out, info, rc = st.local_map(ZERO, pkg.local_map_default_config(mean_k=1, downsample=0, **c["crop"]))
+    st.close()
+    inl = c["want"][c["sor"]["keep"]]
+    assert rc == 0 and info.n_inliers == info.n_out == len(inl) < info.n_cropped and np.array_equal(bits(out), bits(inl))
+    assert max(stat_difference(a, b) for a, b in zip((info.sor_mean, info.sor_stddev, info.sor_threshold), c["sor"]["stats"])) \
+        <= 64 * len(c["want"]) * EPS52
+
+
+def test_a_crop_that_leaves_at_most_mean_k_points_passes_through(pkg, oracle):
+    """mean_k 10.  Eleven points at x = 1 .. 11 m (uneven in y and z) and 400 beyond the crop; `right` leaves 1, 10 and 11."""
+    rng = np.random.default_rng(31)
+    near = np.stack([np.arange(1.0, 12.0), rng.uniform(-3, 3, 11), rng.uniform(0, 1, 11)], 1)
+    far = rng.uniform(-5, 5, (400, 3)) + np.array([100.0, 0, 0])
+    cloud = xyzi(np.concatenate([far[:200], near, far[200:]], 0), rng)
+    st = one_keyframe_store(pkg, oracle, cloud)
+    for right, n in ((1.5, 1), (10.5, 10)):
+        want, _ = L.crop(cloud, ZERO, right=right)
+        assert len(want) == n
+        out, info, rc = st.local_map(ZERO, pkg.local_map_default_config(right=right, downsample=0))
+        assert rc == 0 and info.n_cropped == info.n_inliers == info.n_out == n
+        assert (info.sor_mean, info.sor_stddev, info.sor_threshold) == (0.0, 0.0, np.inf)
+        assert np.array_equal(bits(out), bits(want))
+        out, info, rc = st.local_map(ZERO, pkg.local_map_default_config(right=right, leaf=2.5))      # K7 behind it still runs
+        vox, vrc = pkg.voxel_grid(want, 2.5)
+        assert rc == 0 and vrc == 0 and info.voxel_passthrough == 0 and info.n_inliers == n and info.n_out == len(vox)
+        assert np.array_equal(bits(out), bits(vox)) and (n == 1 or len(vox) < n)
+    want, _ = L.crop(cloud, ZERO, right=11.5)                                  # mean_k + 1 points: the filter proper
+    ref = L.sor(want, 10, 1.0)
+    assert len(want) == 11 and ref["rc"] == 0 and 0 < int(ref["keep"].sum()) < 11
+    assert_bracket_empty(ref, "mean_k + 1")
+    out, info, rc = st.local_map(ZERO, pkg.local_map_default_config(right=11.5, downsample=0))
+    st.close()
+    assert rc == 0 and info.n_cropped == 11 and info.n_inliers == info.n_out == int(ref["keep"].sum())
+    assert np.array_equal(bits(out), bits(want[ref["keep"]]))
+    assert max(stat_difference(a, b) for a, b in zip((info.sor_mean, info.sor_stddev, info.sor_threshold), ref["stats"])) <= 64 * 11 * EPS52
