@@ -313,6 +313,17 @@ int  lio_debug_grid_plan(const lio_s2m_config *cfg, const float mn[3], const flo
 /* Diagnostic (cfg.profile == 2): per-wave phase clock of the last GN launch,
  * n_blocks x 4 x 8 cycle counters; returns n_blocks.  Not for production. */
 int  lio_s2m_debug_stamps(lio_s2m_handle *h, long long *out, size_t cap_entries);
+/* Test hook: the order the upload-time tile sort gave the resident batch.  Waits for the handle's stream and returns the
+ * batch's total point count (all scans), or a negative LIO_ERR_*.  *sorted (may be NULL): 1 when the batch was tile-sorted.
+ * With perm / xyz non-NULL and cap_points >= that count: perm[j] = the caller's (batch-wide) index of the record at sorted
+ * position j (copied only when sorted), xyz = the SoA the Gauss-Newton loop reads as three runs of `count` floats -- all x,
+ * all y, all z -- (copied only when the upload filled it).  perm == NULL, xyz == NULL, cap_points == 0 asks for the count.
+ * A null handle, a multi-device handle and a capacity below the count are LIO_ERR_ARG. */
+int  lio_s2m_debug_scan_order(lio_s2m_handle *h, int32_t *perm, float *xyz, size_t cap_points, int32_t *sorted);
+/* Test hook (host only): the scan-local tile grid the upload lays over a scan whose finite coordinates span [mn, mx], asked
+ * for tiles of edge `tile`, under shard axis -1 (unsharded), 0, 1 or 2.  out_i = tiles along x, y, z and the key strides of
+ * x, y, z; out_f = the grid's origin and 1 / (the edge after doubling). */
+int  lio_debug_scan_tile_plan(const float mn[3], const float mx[3], float tile, int32_t shard_axis, int32_t out_i[6], float out_f[4]);
 
 /* Multi-GPU hooks (one process per GPU; the caller owns the collective).
  * The map given to set_map is this rank's shard INCLUDING a halo of one cell;

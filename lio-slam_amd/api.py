@@ -349,6 +349,7 @@ EXPORTS = [
     "lio_grid_memory", "lio_grid_sample", "lio_kf_store_planning_grid", "lio_grid_debug_stage_ms",
     "lio_grid_region_default_config", "lio_grid_region_reduce", "lio_grid_region_cells", "lio_grid_region_debug_stage_ms",
     "lio_debug_fast_f32_ops", "lio_debug_threshold_f32", "lio_debug_grid_plan",
+    "lio_s2m_debug_scan_order", "lio_debug_scan_tile_plan",
 ]
 
 
@@ -433,6 +434,9 @@ def load_library():
     L.lio_extract_features.argtypes = [C.POINTER(FeatureConfig), vp, sz, sz, vp, vp, vp, vp, vp, C.POINTER(sz), vp,
                                        C.POINTER(sz), sz, vp, vp, vp]
     L.lio_s2m_debug_stamps.argtypes = [vp, vp, sz]
+    if hasattr(L, "lio_s2m_debug_scan_order"):         # (A/B runs load older builds through LIOGPU_LIB)
+        L.lio_s2m_debug_scan_order.argtypes = [vp, vp, vp, sz, C.POINTER(i32)]
+        L.lio_debug_scan_tile_plan.argtypes = [C.POINTER(f32), C.POINTER(f32), f32, i32, C.POINTER(i32), C.POINTER(f32)]
     L.lio_voxel_grid.argtypes = [i32, vp, sz, sz, f32, vp, sz, C.POINTER(sz)]
     L.lio_kf_store_create.argtypes = [i32, C.POINTER(vp)]
     L.lio_kf_store_destroy.argtypes = [vp]
@@ -767,6 +771,16 @@ class ScanToMap:
             self.lib.lio_s2m_debug_stamps(self.h, out.ctypes.data, out.size)
         return out
 
+    def debug_scan_order(self):
+        """Test hook of the upload-time tile sort (include/liogpu.h) -> (sorted, perm, xyz): perm[j] = the caller's batch-wide
+        index of the record at sorted position j (None when the batch was not sorted), xyz [n, 3] = the SoA as uploaded."""
+        srt = C.c_int32(0)
+        n = _check(self.lib.lio_s2m_debug_scan_order(self.h, None, None, 0, C.byref(srt)), "lio_s2m_debug_scan_order")
+        perm = np.full(n, -1, np.int32)
+        soa = np.zeros((3, n), np.float32)
+        _check(self.lib.lio_s2m_debug_scan_order(self.h, perm.ctypes.data, soa.ctypes.data, n, C.byref(srt)), "lio_s2m_debug_scan_order")
+        return bool(srt.value), (perm if srt.value else None), np.ascontiguousarray(soa.T)
+
     # multi-GPU hooks
     def set_stream(self, hip_stream):
         _check(self.lib.lio_s2m_set_stream(self.h, C.c_void_p(hip_stream)), "lio_s2m_set_stream")
@@ -1008,6 +1022,16 @@ def debug_grid_plan(mn, mx, n, occupied=-1, caller_box=False, **cfg_overrides):
     out = GridPlanInfo()
     _check(fn(C.byref(cfg), _f32p(lo), _f32p(hi), int(n), int(occupied), 1 if caller_box else 0, C.byref(out)), "lio_debug_grid_plan")
     return out
+
+
+# test hook (host only): the scan-local tile grid of the upload-time sort over the box [mn, mx] (include/liogpu.h)
+def debug_scan_tile_plan(mn, mx, tile, shard_axis=-1):
+    lo, hi = np.ascontiguousarray(mn, np.float32).reshape(3), np.ascontiguousarray(mx, np.float32).reshape(3)
+    oi, of = np.zeros(6, np.int32), np.zeros(4, np.float32)
+    _check(load_library().lio_debug_scan_tile_plan(_f32p(lo), _f32p(hi), float(tile), int(shard_axis),
+                                                   oi.ctypes.data_as(C.POINTER(C.c_int32)), _f32p(of)), "lio_debug_scan_tile_plan")
+    return dict(ntx=int(oi[0]), nty=int(oi[1]), ntz=int(oi[2]), mx=int(oi[3]), my=int(oi[4]), mz=int(oi[5]),
+                ox=of[0], oy=of[1], oz=of[2], inv_tile=of[3])
 
 
 # extension (row A4): projectPointCloud + cloudExtraction of upstream LIO-SAM -> the cloud_info arrays FE consumes

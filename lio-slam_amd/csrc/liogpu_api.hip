@@ -1687,6 +1687,41 @@ extern "C" int lio_s2m_debug_stamps(lio_s2m_handle* h, long long* out, size_t ca
     return h->n_blocks;
 }
 
+// Test hook: the permutation and the SoA the upload-time tile sort left for the resident batch (include/liogpu.h).
+extern "C" int lio_s2m_debug_scan_order(lio_s2m_handle* h, int32_t* perm, float* xyz, size_t cap_points, int32_t* sorted)
+try {
+    if (!h) return lio_fail(LIO_ERR_ARG, "null handle");
+    if (h->multi) return lio_fail(LIO_ERR_ARG, "not available on a multi-device handle");
+    HIPCHK(hipSetDevice(h->cfg.device_id));
+    (void)hipGetLastError();
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const size_t total = h->total_pts;
+    if (sorted) *sorted = h->sorted ? 1 : 0;
+    if (perm || xyz) {
+        if (cap_points < total) return lio_fail(LIO_ERR_ARG, "cap_points is below the batch's point count");
+        if (perm && total && h->sorted)
+            HIPCHK(hipMemcpy(perm, h->d_perm, total * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (xyz && total && h->soa_valid) {
+            HIPCHK(hipMemcpy(xyz, h->d_sx, total * sizeof(float), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(xyz + total, h->d_sy, total * sizeof(float), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(xyz + 2 * total, h->d_sz, total * sizeof(float), hipMemcpyDeviceToHost));
+        }
+    }
+    return (int)total;
+} LIO_CATCH
+
+// Test hook (host only): lio_plan_scan_tiles on a box given by the caller.
+extern "C" int lio_debug_scan_tile_plan(const float mn[3], const float mx[3], float tile, int32_t shard_axis, int32_t out_i[6],
+                                        float out_f[4])
+try {
+    if (!mn || !mx || !out_i || !out_f) return lio_fail(LIO_ERR_ARG, "null argument");
+    if (!(tile > 0.0f) || shard_axis < -1 || shard_axis > 2) return lio_fail(LIO_ERR_ARG, "need tile > 0 and shard_axis in -1..2");
+    const LioScanTiles t = lio_plan_scan_tiles(mn, mx, tile, shard_axis);
+    out_i[0] = t.ntx; out_i[1] = t.nty; out_i[2] = t.ntz; out_i[3] = t.mx; out_i[4] = t.my; out_i[5] = t.mz;
+    out_f[0] = t.ox; out_f[1] = t.oy; out_f[2] = t.oz; out_f[3] = t.inv_tile;
+    return LIO_OK;
+} LIO_CATCH
+
 // ------------------------------------------------------------- temporary pool
 namespace {
 struct PoolBlock { void* p; size_t cap; int device; bool busy; };

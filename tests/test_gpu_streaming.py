@@ -140,9 +140,10 @@ def test_oversized_tiles_are_ordered_deterministically(pkg, oracle, synth):
 
 
 def test_one_launch_lds_sort_equals_the_counting_sort(pkg, small_case):
-    """Scans of at most 16384 points are reordered by ONE launch (k_scan_sort_lds: box, tile keys, bitonic sort in LDS,
-    gather); it must produce the permutation of the multi-kernel counting sort + rank sort (cfg.sort_scan = 3), so every
-    sum -- and with it every bit of the result -- is the same.  Ragged batch, tiny and empty-ish scans included."""
+    """Scans of at most 16383 points are reordered by ONE launch (k_scan_sort_radix: box, tile keys, a stable radix sort with
+    the keys in registers, gather); it must produce the permutation of the multi-kernel counting sort + rank sort
+    (cfg.sort_scan = 3), so every sum -- and with it every bit of the result -- is the same.  Ragged batch, tiny and empty-ish
+    scans included.  (The permutation itself is pinned in tests/test_gpu_scan_order.py.)"""
     qs = small_case["queries"]
     scans = [q["scan"] for q in qs] + [qs[0]["scan"][:20], qs[1]["scan"][::2], qs[2]["scan"][:1], qs[0]["scan"][:257]]
     poses0 = np.stack([q["pose_init"] for q in qs] + [qs[0]["pose_init"], qs[1]["pose_init"], qs[2]["pose_init"], qs[0]["pose_init"]])
