@@ -278,6 +278,44 @@ int  lio_s2m_debug_persist_spin(lio_s2m_handle *h, int32_t spin_max, int32_t wit
  * and offset, plane test against plane_tol) on n neighbour sets, sets[n][5][3] in host memory.  out[n][8]: the raw bits of
  * X0[0..2], pa, pb, pc, pd, then planeValid (0 / 1). */
 int  lio_debug_plane_fit(int32_t device_id, const float *sets, size_t n, double plane_tol, uint32_t *out);
+/* Test hook: the serial Gauss-Newton step that ends every launch (MO:1784-1833 from the reduced sums onward and the loop
+ * control MO:1848-1859: QR solve; on iteration 0 the eigen-decomposition, the degeneracy rule, matV.inv() * matV2; the
+ * projection, the pose update, the convergence test) on n independent cases, one wave each, every case with a scan state of its
+ * own.  It runs the source function of the library's kernels as compiled into the hook's kernel.
+ * cfg: NULL = the defaults.  Per case i: sums[28 i ..] = the 21 upper-triangle entries of JtJ (row by row), the 6 of Jtr and the
+ * correspondence count, in fp64 as the reduction leaves them; pose[6 i ..] the incoming pose; iter[i] the iteration number (0 ..
+ * LIO_MAX_ITERS - 1); is_degenerate[i] and matP[36 i ..] the stored members MO:176-177.  For the whole call, the speculation
+ * arguments of the one-launch loop: deg_override >= 0 takes the place of the stored is_degenerate (iterations > 0);
+ * skip_eigen != 0: iteration 0 without the eigen-decomposition (matP / is_degenerate left alone, the non-degenerate update);
+ * hold_if_done != 0: a step that would end the registration changes nothing it decides and returns 2.
+ * out[i]: the state after the step, layout below (109 words of 4 bytes, no padding); T / trig are rewritten only when done == 0.
+ * NON-FINITE POLICY: a sum that is not finite (as fp64 or as the fp32 the step converts it to), a count outside [0, 2^31) and a
+ * non-finite pose are LIO_ERR_ARG before any launch.  The wave-parallel pivot search is defined for finite matrices only -- a
+ * NaN compares unequal to the maximum it produced, and the search would then index lanes the serial code never reads; the
+ * library keeps non-finite values out of the sums at the association (tests/test_gpu_nonfinite.py). */
+typedef struct lio_debug_gn_record {
+    float   pose[6];         /* word   0 */
+    float   matP[36];        /* word   6 */
+    float   AtA[36];         /* word  42 */
+    float   AtB[6];          /* word  78 */
+    float   T[12];           /* word  84 */
+    float   trig[6];         /* word  96 */
+    int32_t iter;            /* word 102 */
+    int32_t done;            /* word 103 */
+    int32_t status;          /* word 104 */
+    int32_t converged;       /* word 105 */
+    int32_t is_degenerate;   /* word 106 */
+    int32_t n_corr_last;     /* word 107 */
+    int32_t ret;             /* word 108: what the step returned (0, or 2 when held) */
+} lio_debug_gn_record;
+int  lio_debug_gn_step(int32_t device_id, const lio_s2m_config *cfg, size_t n, const double *sums, const float *pose,
+                       const int32_t *iter, const int32_t *is_degenerate, const float *matP, int32_t deg_override,
+                       int32_t skip_eigen, int32_t hold_if_done, lio_debug_gn_record *out);
+/* Test hook: the line fit of the corner association (upstream cornerOptimization after the 5-NN gate: centroid, covariance,
+ * cv::eigen 3x3, line iff e0 > 3 e1, point-to-line distance and gradient, s = 1 - weight |ld2|, accept iff s > min_s) on n cases,
+ * one per thread: sets[n][5][3] = the five neighbours in the caller's order, pts[n][3] = the transformed points.  out[n][5]: the
+ * raw bits of the four coefficients, then the accept flag (0 / 1).  Non-finite inputs are allowed (the code is serial). */
+int  lio_debug_corner_fit(int32_t device_id, const float *sets, const float *pts, size_t n, double weight, double min_s, uint32_t *out);
 /* Test hook: the association's fast fp32 operations against the device's plain operators, bit for bit.  op 0: square root,
  * op 1: x / 5, op 2: sqrtf(sqrtf(r2)) of the scan point (x, 0, 0) as the association takes it, its guard riding on the plane fit's
  * (a fixed neighbour set; raw ignored); raw != 0: the fast instruction sequence without its range guard (equal to the plain operator on the guarded

@@ -348,7 +348,7 @@ EXPORTS = [
     "lio_grid_sample_default_config", "lio_grid_create", "lio_grid_destroy", "lio_grid_set_layers", "lio_grid_get_layer", "lio_grid_info",
     "lio_grid_memory", "lio_grid_sample", "lio_kf_store_planning_grid", "lio_grid_debug_stage_ms",
     "lio_grid_region_default_config", "lio_grid_region_reduce", "lio_grid_region_cells", "lio_grid_region_debug_stage_ms",
-    "lio_debug_fast_f32_ops", "lio_debug_threshold_f32", "lio_debug_grid_plan",
+    "lio_debug_fast_f32_ops", "lio_debug_threshold_f32", "lio_debug_grid_plan", "lio_debug_gn_step", "lio_debug_corner_fit",
     "lio_s2m_debug_scan_order", "lio_debug_scan_tile_plan",
 ]
 
@@ -974,6 +974,65 @@ def debug_plane_fit(sets, plane_tol=0.2, device_id=0):
     fn = load_library().lio_debug_plane_fit        # bound on first use: A/B runs load older builds through LIOGPU_LIB
     fn.argtypes = [C.c_int32, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p]
     _check(fn(device_id, a.ctypes.data, len(a), float(plane_tol), out.ctypes.data), "lio_debug_plane_fit")
+    return out
+
+
+# the packed record of lio_debug_gn_step (include/liogpu.h): 109 words of 4 bytes, no padding
+class DebugGnRecord(C.Structure):
+    _fields_ = [
+        ("pose", C.c_float * 6), ("matP", C.c_float * 36), ("AtA", C.c_float * 36), ("AtB", C.c_float * 6),
+        ("T", C.c_float * 12), ("trig", C.c_float * 6),
+        ("iter", C.c_int32), ("done", C.c_int32), ("status", C.c_int32), ("converged", C.c_int32),
+        ("is_degenerate", C.c_int32), ("n_corr_last", C.c_int32), ("ret", C.c_int32),
+    ]
+
+
+DEBUG_GN_RECORD_DTYPE = np.dtype([
+    ("pose", np.float32, 6), ("matP", np.float32, 36), ("AtA", np.float32, 36), ("AtB", np.float32, 6),
+    ("T", np.float32, 12), ("trig", np.float32, 6),
+    ("iter", np.int32), ("done", np.int32), ("status", np.int32), ("converged", np.int32),
+    ("is_degenerate", np.int32), ("n_corr_last", np.int32), ("ret", np.int32)])
+assert DEBUG_GN_RECORD_DTYPE.itemsize == C.sizeof(DebugGnRecord) == 436
+
+
+# test hook: the serial Gauss-Newton step (lio_gn_step) on n independent cases, one wave each.  sums (n, 28) float64: the 21
+# upper-triangle JtJ entries, the 6 of Jtr, the correspondence count; pose (n, 6); it, is_degenerate (n,); matP (n, 36);
+# the three speculation arguments hold for the whole call; cfg_overrides: fields of the scan-to-map configuration.
+# Returns a structured array of DEBUG_GN_RECORD_DTYPE.  Non-finite sums or poses are refused (include/liogpu.h)
+def debug_gn_step(sums, pose, it, is_degenerate, matP, deg_override=-1, skip_eigen=False, hold_if_done=False, device_id=0,
+                  **cfg_overrides):
+    L = load_library()
+    fn = L.lio_debug_gn_step                       # bound on first use: A/B runs load older builds through LIOGPU_LIB
+    fn.argtypes = [C.c_int32, C.POINTER(S2MConfig), C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                   C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+    cfg = S2MConfig()
+    L.lio_s2m_default_config(C.byref(cfg))
+    for k, v in cfg_overrides.items():
+        if not hasattr(cfg, k):
+            raise AttributeError(k)
+        setattr(cfg, k, v)
+    sums = np.ascontiguousarray(sums, np.float64).reshape(-1, 28)
+    n = len(sums)
+    pose = np.ascontiguousarray(pose, np.float32).reshape(n, 6)
+    it = np.ascontiguousarray(it, np.int32).reshape(n)
+    deg = np.ascontiguousarray(is_degenerate, np.int32).reshape(n)
+    matP = np.ascontiguousarray(matP, np.float32).reshape(n, 36)
+    out = np.zeros(n, DEBUG_GN_RECORD_DTYPE)
+    _check(fn(device_id, C.byref(cfg) if cfg_overrides else None, n, sums.ctypes.data, pose.ctypes.data, it.ctypes.data,
+              deg.ctypes.data, matP.ctypes.data, int(deg_override), 1 if skip_eigen else 0, 1 if hold_if_done else 0,
+              out.ctypes.data), "lio_debug_gn_step")
+    return out
+
+
+# test hook: the line fit of the corner association (lio_corner_assoc) on (n, 5, 3) neighbour sets in the caller's order and
+# (n, 3) transformed points -> (n, 5) uint32: the bits of the four coefficients, then the accept flag (include/liogpu.h)
+def debug_corner_fit(sets, pts, weight=0.9, min_s=0.1, device_id=0):
+    a = np.ascontiguousarray(sets, np.float32).reshape(-1, 15)
+    q = np.ascontiguousarray(pts, np.float32).reshape(len(a), 3)
+    out = np.zeros((len(a), 5), np.uint32)
+    fn = load_library().lio_debug_corner_fit
+    fn.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_double, C.c_void_p]
+    _check(fn(device_id, a.ctypes.data, q.ctypes.data, len(a), float(weight), float(min_s), out.ctypes.data), "lio_debug_corner_fit")
     return out
 
 

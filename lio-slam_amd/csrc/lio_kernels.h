@@ -77,5 +77,8 @@ void lio_launch_scan_tile_sort(const void* stage, size_t stride, int total_pts,
 void lio_launch_exclusive_scan(const int* in, int n, int* tile_sums, int* out, hipStream_t s);
 void lio_launch_xyzi4_to_soa(const float4* src, int n, float* x, float* y, float* z, float4* xyz4, hipStream_t s);
 void lio_launch_debug_plane_fit(const float* sets, long long n, double plane_tol, unsigned* out, hipStream_t s);
+void lio_launch_debug_gn_step(LioScanState* st, long long n, const double* sums, const LioConsts& c, int deg_override, int skip_eigen,
+                              int hold_if_done, int* ret, hipStream_t s);
+void lio_launch_debug_corner_fit(const float* sets, const float* pts, long long n, double weight, double min_s, unsigned* out, hipStream_t s);
 void lio_launch_debug_fast_f32_ops(int op, int raw, const unsigned* pat, unsigned long long first, unsigned long long count,
                                    unsigned* val, unsigned long long* n_diff, unsigned* diff, hipStream_t s);

@@ -85,18 +85,19 @@ extern "C" void lio_s2m_default_config(lio_s2m_config* c)
     c->tight_rows = 0;
 }
 
-static void lio_fill_consts(lio_s2m_handle* h)
+static void lio_consts_from_config(const lio_s2m_config& g, LioConsts& c)
 {
-    const lio_s2m_config& g = h->cfg;
-    h->c.plane_tol = g.plane_tol; h->c.weight = g.weight; h->c.min_s = g.min_s;
-    h->c.plane_tol_f = lio_threshold_f32(g.plane_tol); h->c.min_s_f = lio_threshold_f32(g.min_s);
-    h->c.conv_deg = g.conv_deg; h->c.conv_cm = g.conv_cm;
-    h->c.max_sq_dist = g.max_sq_dist; h->c.eig_thresh = g.eig_thresh;
-    h->c.gate_reach = lio_gate_reach(g.max_sq_dist);
-    h->c.min_corr = g.min_corr; h->c.max_iters = g.max_iters;
-    h->c.jac_exact = g.jacobian_mode ? 1 : 0; h->c.force_all = g.force_all_iters ? 1 : 0;
-    h->c.record_iter = g.record_corr_iter; h->c.min_scan_pts = g.min_scan_pts;
+    c.plane_tol = g.plane_tol; c.weight = g.weight; c.min_s = g.min_s;
+    c.plane_tol_f = lio_threshold_f32(g.plane_tol); c.min_s_f = lio_threshold_f32(g.min_s);
+    c.conv_deg = g.conv_deg; c.conv_cm = g.conv_cm;
+    c.max_sq_dist = g.max_sq_dist; c.eig_thresh = g.eig_thresh;
+    c.gate_reach = lio_gate_reach(g.max_sq_dist);
+    c.min_corr = g.min_corr; c.max_iters = g.max_iters;
+    c.jac_exact = g.jacobian_mode ? 1 : 0; c.force_all = g.force_all_iters ? 1 : 0;
+    c.record_iter = g.record_corr_iter; c.min_scan_pts = g.min_scan_pts;
 }
+
+static void lio_fill_consts(lio_s2m_handle* h) { lio_consts_from_config(h->cfg, h->c); }
 
 static int lio_s2m_init_resources(lio_s2m_handle* h)
 {
@@ -540,6 +541,91 @@ try {
     lio_launch_debug_plane_fit(d_sets, (long long)n, plane_tol, d_out, nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(out, d_out, n * 8 * sizeof(unsigned), hipMemcpyDeviceToHost));
+    return LIO_OK;
+} LIO_CATCH
+
+// Test hook: the serial Gauss-Newton step that ends every launch (lio_gn_step: the 6x6 QR solve, on iteration 0 the Jacobi
+// eigen-decomposition over a wave, the degeneracy rule, the LU inverse and the product, then the projection, the pose update, the
+// convergence test and the loop control) on n independent cases, one wave each.  The source function as compiled into the hook's
+// kernel, not as inlined into k_s2m_iterate / k_s2m_persist.  Non-finite sums or poses are refused before any launch: the lane
+// code's pivot search is defined for finite matrices only (a NaN would make it index lanes the serial code never reads), and
+// the library keeps non-finite values out of the sums (tests/test_gpu_nonfinite.py).
+extern "C" int lio_debug_gn_step(int32_t device_id, const lio_s2m_config* cfg, size_t n, const double* sums, const float* pose,
+                                 const int32_t* iter, const int32_t* is_degenerate, const float* matP, int32_t deg_override,
+                                 int32_t skip_eigen, int32_t hold_if_done, lio_debug_gn_record* out)
+try {
+    if ((!sums || !pose || !iter || !is_degenerate || !matP || !out) && n) return lio_fail(LIO_ERR_ARG, "null pointer");
+    if (n > ((size_t)1 << 18)) return lio_fail(LIO_ERR_CAPACITY, "at most 2^18 cases per call");
+    lio_s2m_config g;
+    if (cfg) g = *cfg; else lio_s2m_default_config(&g);
+    if (g.max_iters < 1 || g.max_iters > LIO_MAX_ITERS) return lio_fail(LIO_ERR_ARG, "max_iters out of range");
+    for (size_t i = 0; i < n; ++i) {
+        for (int k = 0; k < 27; ++k)                       // finite as the fp32 value the step takes, too
+            if (!std::isfinite(sums[i * 28 + k]) || !std::isfinite((float)sums[i * 28 + k])) return lio_fail(LIO_ERR_ARG, "non-finite sum");
+        const double nc = sums[i * 28 + LIO_SUM_NC];
+        if (!(nc >= 0.0 && nc <= 2147483647.0)) return lio_fail(LIO_ERR_ARG, "the correspondence count must be in [0, 2^31)");
+        for (int k = 0; k < 6; ++k) if (!std::isfinite(pose[i * 6 + k])) return lio_fail(LIO_ERR_ARG, "non-finite pose");
+        if (iter[i] < 0 || iter[i] >= LIO_MAX_ITERS) return lio_fail(LIO_ERR_ARG, "iter out of range");
+    }
+    if (!n) return LIO_OK;
+    LioConsts c;
+    lio_consts_from_config(g, c);
+    std::vector<LioScanState> st(n);
+    std::vector<double> h_sums(n * LIO_SUMS, 0.0);
+    std::vector<int> ret(n, 0);
+    memset(st.data(), 0, n * sizeof(LioScanState));
+    for (size_t i = 0; i < n; ++i) {
+        memcpy(st[i].pose, pose + i * 6, sizeof(float) * 6);
+        memcpy(st[i].matP, matP + i * 36, sizeof(float) * 36);
+        st[i].iter = iter[i];
+        st[i].is_degenerate = is_degenerate[i];
+        memcpy(&h_sums[i * LIO_SUMS], sums + i * 28, sizeof(double) * 28);
+    }
+    HIPCHK(hipSetDevice(device_id));
+    LioDevBuf<LioScanState> d_st;
+    LioDevBuf<double> d_sums;
+    LioDevBuf<int> d_ret;
+    HIPCHK(d_st.grow(n, 1.0, 0));
+    HIPCHK(d_sums.grow(n * LIO_SUMS, 1.0, 0));
+    HIPCHK(d_ret.grow(n, 1.0, 0));
+    HIPCHK(hipMemcpy(d_st, st.data(), n * sizeof(LioScanState), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_sums, h_sums.data(), n * LIO_SUMS * sizeof(double), hipMemcpyHostToDevice));
+    lio_launch_debug_gn_step(d_st, (long long)n, d_sums, c, deg_override, skip_eigen, hold_if_done, d_ret, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(st.data(), d_st, n * sizeof(LioScanState), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ret.data(), d_ret, n * sizeof(int), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) {
+        lio_debug_gn_record& o = out[i];
+        const LioScanState& s = st[i];
+        memcpy(o.pose, s.pose, sizeof(o.pose)); memcpy(o.matP, s.matP, sizeof(o.matP));
+        memcpy(o.AtA, s.AtA, sizeof(o.AtA)); memcpy(o.AtB, s.AtB, sizeof(o.AtB));
+        memcpy(o.T, s.T, sizeof(o.T)); memcpy(o.trig, s.trig, sizeof(o.trig));
+        o.iter = s.iter; o.done = s.done; o.status = s.status; o.converged = s.converged;
+        o.is_degenerate = s.is_degenerate; o.n_corr_last = s.n_corr_last; o.ret = ret[i];
+    }
+    return LIO_OK;
+} LIO_CATCH
+
+// Test hook: the line fit of the corner association (lio_corner_assoc: centroid, covariance, the 3x3 Jacobi, the e0 > 3 e1 test,
+// the point-to-line distance and its gradient, the weight) on n cases: sets[n][5][3] = the five neighbours in the caller's order,
+// pts[n][3] = the transformed points.  out[n][5]: the raw bits of the four coefficients, then the accept flag (0 / 1).  Non-finite
+// inputs are allowed: the code is serial.
+extern "C" int lio_debug_corner_fit(int32_t device_id, const float* sets, const float* pts, size_t n, double weight, double min_s, uint32_t* out)
+try {
+    if ((!sets || !pts || !out) && n) return lio_fail(LIO_ERR_ARG, "null pointer");
+    if (n > ((size_t)1 << 27)) return lio_fail(LIO_ERR_CAPACITY, "at most 2^27 cases per call");
+    if (!n) return LIO_OK;
+    HIPCHK(hipSetDevice(device_id));
+    LioDevBuf<float> d_sets, d_pts;
+    LioDevBuf<unsigned> d_out;
+    HIPCHK(d_sets.grow(n * 15, 1.0, 0));
+    HIPCHK(d_pts.grow(n * 3, 1.0, 0));
+    HIPCHK(d_out.grow(n * 5, 1.0, 0));
+    HIPCHK(hipMemcpy(d_sets, sets, n * 15 * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_pts, pts, n * 3 * sizeof(float), hipMemcpyHostToDevice));
+    lio_launch_debug_corner_fit(d_sets, d_pts, (long long)n, weight, min_s, d_out, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out, d_out, n * 5 * sizeof(unsigned), hipMemcpyDeviceToHost));
     return LIO_OK;
 } LIO_CATCH
 

@@ -718,35 +718,12 @@ void lo_jacobian_row(const float trig[6], const float p[3], const float c[4],
     *rhs = -c[3];                                                      /* MO:1778 */
 }
 
-int lo_lm_optimization(const lo_s2m_config *cfg, int iter_count,
-                       const float *ori_xyz, const float *coeff4, int n_corr,
-                       float pose[6], float matP[36], int32_t *is_degenerate,
-                       float AtA_out[36], float AtB_out[6])
+/* The tail of LMOptimization, MO:1784-1833: solve, eigen-decomposition and degeneracy rule of the first
+ * iteration, projection, pose update, convergence test. */
+int lo_lm_step(const lo_s2m_config *cfg, int iter_count, const float AtA[36], const float AtB[6],
+               float pose[6], float matP[36], int32_t *is_degenerate)
 {
-    float trig[6];
-    trig[0] = lo_sinf(pose[2], cfg->trig_mode); trig[1] = lo_cosf(pose[2], cfg->trig_mode); /* MO:1714-1715 */
-    trig[2] = lo_sinf(pose[1], cfg->trig_mode); trig[3] = lo_cosf(pose[1], cfg->trig_mode); /* MO:1716-1717 */
-    trig[4] = lo_sinf(pose[0], cfg->trig_mode); trig[5] = lo_cosf(pose[0], cfg->trig_mode); /* MO:1718-1719 */
-
-    if (n_corr < cfg->min_corr) return 0;                              /* MO:1721-1724 */
-
-    /* matA (n x 6), matB (n x 1); matAtA = matAt*matA, matAtB = matAt*matB
-     * (MO:1781-1783) with OpenCV's double accumulation over rows in order. */
-    double acc[6][6], accb[6];
-    memset(acc, 0, sizeof(acc)); memset(accb, 0, sizeof(accb));
-    for (int i = 0; i < n_corr; ++i) {
-        float row[6], rhs;
-        lo_jacobian_row(trig, ori_xyz + 3 * (size_t)i, coeff4 + 4 * (size_t)i, cfg->jacobian_mode, row, &rhs);
-        for (int a = 0; a < 6; ++a) {
-            for (int b = 0; b < 6; ++b) acc[a][b] += (double)row[a] * (double)row[b];
-            accb[a] += (double)row[a] * (double)rhs;
-        }
-    }
-    float AtA[36], AtB[6], X[6];
-    for (int a = 0; a < 6; ++a) { for (int b = 0; b < 6; ++b) AtA[a * 6 + b] = (float)acc[a][b]; AtB[a] = (float)accb[a]; }
-    if (AtA_out) memcpy(AtA_out, AtA, sizeof(AtA));
-    if (AtB_out) memcpy(AtB_out, AtB, sizeof(AtB));
-
+    float X[6];
     lo_solve6_qr(AtA, AtB, X);                                          /* MO:1784 */
 
     if (iter_count == 0) {                                              /* MO:1786-1808 */
@@ -783,6 +760,46 @@ int lo_lm_optimization(const lo_s2m_config *cfg, int iter_count,
 
     if ((double)deltaR < cfg->conv_deg && (double)deltaT < cfg->conv_cm) return 1; /* MO:1833-1835 */
     return 0;
+}
+
+int lo_lm_optimization(const lo_s2m_config *cfg, int iter_count,
+                       const float *ori_xyz, const float *coeff4, int n_corr,
+                       float pose[6], float matP[36], int32_t *is_degenerate,
+                       float AtA_out[36], float AtB_out[6])
+{
+    float trig[6];
+    trig[0] = lo_sinf(pose[2], cfg->trig_mode); trig[1] = lo_cosf(pose[2], cfg->trig_mode); /* MO:1714-1715 */
+    trig[2] = lo_sinf(pose[1], cfg->trig_mode); trig[3] = lo_cosf(pose[1], cfg->trig_mode); /* MO:1716-1717 */
+    trig[4] = lo_sinf(pose[0], cfg->trig_mode); trig[5] = lo_cosf(pose[0], cfg->trig_mode); /* MO:1718-1719 */
+
+    if (n_corr < cfg->min_corr) return 0;                              /* MO:1721-1724 */
+
+    /* matA (n x 6), matB (n x 1); matAtA = matAt*matA, matAtB = matAt*matB
+     * (MO:1781-1783) with OpenCV's double accumulation over rows in order. */
+    double acc[6][6], accb[6];
+    memset(acc, 0, sizeof(acc)); memset(accb, 0, sizeof(accb));
+    for (int i = 0; i < n_corr; ++i) {
+        float row[6], rhs;
+        lo_jacobian_row(trig, ori_xyz + 3 * (size_t)i, coeff4 + 4 * (size_t)i, cfg->jacobian_mode, row, &rhs);
+        for (int a = 0; a < 6; ++a) {
+            for (int b = 0; b < 6; ++b) acc[a][b] += (double)row[a] * (double)row[b];
+            accb[a] += (double)row[a] * (double)rhs;
+        }
+    }
+    float AtA[36], AtB[6];
+    for (int a = 0; a < 6; ++a) { for (int b = 0; b < 6; ++b) AtA[a * 6 + b] = (float)acc[a][b]; AtB[a] = (float)accb[a]; }
+    if (AtA_out) memcpy(AtA_out, AtA, sizeof(AtA));
+    if (AtB_out) memcpy(AtB_out, AtB, sizeof(AtB));
+
+    return lo_lm_step(cfg, iter_count, AtA, AtB, pose, matP, is_degenerate);
+}
+
+/* LMOptimization from the normal equations onward (`lo_lm_step_batch`: n independent cases, each with its own iteration number) */
+void lo_lm_step_batch(const lo_s2m_config *cfg, size_t n, const int32_t *iter, const float *AtA, const float *AtB,
+                      float *pose, float *matP, int32_t *is_degenerate, int32_t *converged)
+{
+    for (size_t i = 0; i < n; ++i)
+        converged[i] = lo_lm_step(cfg, iter[i], AtA + 36 * i, AtB + 6 * i, pose + 6 * i, matP + 36 * i, is_degenerate + i);
 }
 
 /* ----------------------------------------------------- scan2MapOptimization */
@@ -1510,32 +1527,21 @@ void lo_eigen3_sym(const float A_in[9], float W[3], float V[9])
     }
 }
 
-static void lo_corner_point(const lo_s2m_config *cfg, const float T[12], const float *pointOri,
-                            const float *map_xyz, size_t n_map, const lo_kdtree *tree,
-                            uint8_t *flag, float *coeff, int32_t *nn)
+/* cornerOptimization after the 5-NN gate: five = the neighbours in the search's order, pointSel = the transformed point */
+void lo_corner_fit(const lo_s2m_config *cfg, const float five[15], const float pointSel[3], uint8_t *flag, float coeff[4])
 {
-    float pointSel[3];
-    int32_t ind[5];
-    float sq[5];
     *flag = 0;
     coeff[0] = coeff[1] = coeff[2] = coeff[3] = 0.0f;
-    for (int j = 0; j < 5; ++j) nn[j] = -1;
-    lo_point_associate(T, pointOri, pointSel);
-    if (cfg->knn_mode == 0 || tree == NULL) lo_knn5_brute(map_xyz, n_map, pointSel, ind, sq);
-    else                                    lo_kdtree_knn5(tree, pointSel, ind, sq);
-    if (!((double)sq[4] < (double)cfg->max_sq_dist)) return;
-    for (int j = 0; j < 5; ++j) nn[j] = ind[j];
-
     float cx = 0, cy = 0, cz = 0;
     for (int j = 0; j < 5; ++j) {
-        cx += map_xyz[3 * (size_t)ind[j] + 0]; cy += map_xyz[3 * (size_t)ind[j] + 1]; cz += map_xyz[3 * (size_t)ind[j] + 2];
+        cx += five[3 * j + 0]; cy += five[3 * j + 1]; cz += five[3 * j + 2];
     }
     cx /= 5; cy /= 5; cz /= 5;
     float a11 = 0, a12 = 0, a13 = 0, a22 = 0, a23 = 0, a33 = 0;
     for (int j = 0; j < 5; ++j) {
-        float ax = map_xyz[3 * (size_t)ind[j] + 0] - cx;
-        float ay = map_xyz[3 * (size_t)ind[j] + 1] - cy;
-        float az = map_xyz[3 * (size_t)ind[j] + 2] - cz;
+        float ax = five[3 * j + 0] - cx;
+        float ay = five[3 * j + 1] - cy;
+        float az = five[3 * j + 2] - cz;
         a11 += ax * ax; a12 += ax * ay; a13 += ax * az;
         a22 += ay * ay; a23 += ay * az;
         a33 += az * az;
@@ -1562,6 +1568,33 @@ static void lo_corner_point(const lo_s2m_config *cfg, const float T[12], const f
     float s = (float)(1 - cfg->weight * (double)fabsf(ld2));
     coeff[0] = s * la; coeff[1] = s * lb; coeff[2] = s * lc; coeff[3] = s * ld2;
     if ((double)s > cfg->min_s) *flag = 1;
+}
+
+void lo_corner_fit_batch(const lo_s2m_config *cfg, size_t n, const float *five, const float *pointSel, uint8_t *flag, float *coeff)
+{
+    for (size_t i = 0; i < n; ++i) lo_corner_fit(cfg, five + 15 * i, pointSel + 3 * i, flag + i, coeff + 4 * i);
+}
+
+static void lo_corner_point(const lo_s2m_config *cfg, const float T[12], const float *pointOri,
+                            const float *map_xyz, size_t n_map, const lo_kdtree *tree,
+                            uint8_t *flag, float *coeff, int32_t *nn)
+{
+    float pointSel[3];
+    int32_t ind[5];
+    float sq[5];
+    *flag = 0;
+    coeff[0] = coeff[1] = coeff[2] = coeff[3] = 0.0f;
+    for (int j = 0; j < 5; ++j) nn[j] = -1;
+    lo_point_associate(T, pointOri, pointSel);
+    if (cfg->knn_mode == 0 || tree == NULL) lo_knn5_brute(map_xyz, n_map, pointSel, ind, sq);
+    else                                    lo_kdtree_knn5(tree, pointSel, ind, sq);
+    if (!((double)sq[4] < (double)cfg->max_sq_dist)) return;
+    for (int j = 0; j < 5; ++j) nn[j] = ind[j];
+
+    float five[15];
+    for (int j = 0; j < 5; ++j)
+        for (int c = 0; c < 3; ++c) five[3 * j + c] = map_xyz[3 * (size_t)ind[j] + c];
+    lo_corner_fit(cfg, five, pointSel, flag, coeff);
 }
 
 void lo_corner_optimization(const lo_s2m_config *cfg, const float pose[6],

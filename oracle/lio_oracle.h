@@ -124,6 +124,17 @@ int lo_lm_optimization(const lo_s2m_config *cfg, int iter_count,
                        float pose[6], float matP[36], int32_t *is_degenerate,
                        float AtA_out[36], float AtB_out[6]);
 
+/*
+ * The tail of LMOptimization from the normal equations onward, MO:1784-1833: cv::solve, on iteration 0 cv::eigen, the
+ * degeneracy rule, matV.inv() * matV2, then the projection, the pose update and the convergence test.  AtA / AtB are
+ * the CV_32F matAtA / matAtB; lo_lm_optimization forms them and calls this.  Returns 1 when converged.
+ * _batch: n independent cases in a plain loop (arrays of n x the single form; pose, matP, is_degenerate in place).
+ */
+int lo_lm_step(const lo_s2m_config *cfg, int iter_count, const float AtA[36], const float AtB[6],
+               float pose[6], float matP[36], int32_t *is_degenerate);
+void lo_lm_step_batch(const lo_s2m_config *cfg, size_t n, const int32_t *iter, const float *AtA, const float *AtB,
+                      float *pose, float *matP, int32_t *is_degenerate, int32_t *converged);
+
 /* one row of matA / matB, MO:1735-1778: row = [arz, ary, arx, cx, cy, cz], rhs = -c.w */
 void lo_jacobian_row(const float trig[6] /* srx,crx,sry,cry,srz,crz */, const float p[3],
                      const float c[4], int jacobian_mode, float row[6], float *rhs);
@@ -223,6 +234,11 @@ int lo_extract_features(const float *cloud_xyzi, size_t n, int n_scan,
 /* ---- EXTENSION beyond the reference: point-to-line residuals (upstream LIO-SAM
  * cornerOptimization; absent from this fork; parity unpinned) ---- */
 void lo_eigen3_sym(const float A[9], float evals[3], float evecs[9]);
+/* cornerOptimization after the 5-NN gate: five[5][3] = the neighbours in the search's order, point_sel = the transformed
+ * point; writes flag (0 / 1) and coeff = s * (la, lb, lc, ld2).  lo_corner_optimization calls it per point.
+ * _batch: n independent cases in a plain loop. */
+void lo_corner_fit(const lo_s2m_config *cfg, const float five[15], const float point_sel[3], uint8_t *flag, float coeff[4]);
+void lo_corner_fit_batch(const lo_s2m_config *cfg, size_t n, const float *five, const float *point_sel, uint8_t *flag, float *coeff);
 void lo_corner_optimization(const lo_s2m_config *cfg, const float pose[6],
                             const float *scan_xyz, size_t n_scan,
                             const float *map_xyz, size_t n_map, const lo_kdtree *tree,

@@ -88,6 +88,9 @@ class Oracle:
                                            C.c_size_t, C.c_void_p, _u8p, _f32p, _i32p]
         L.lo_lm_optimization.argtypes = [C.POINTER(S2MConfig), C.c_int, _f32p, _f32p, C.c_int,
                                          _f32p, _f32p, _i32p, _f32p, _f32p]
+        L.lo_lm_step.argtypes = [C.POINTER(S2MConfig), C.c_int, _f32p, _f32p, _f32p, _f32p, _i32p]
+        L.lo_lm_step_batch.argtypes = [C.POINTER(S2MConfig), C.c_size_t, _i32p, _f32p, _f32p, _f32p, _f32p, _i32p, _i32p]
+        L.lo_lm_step_batch.restype = None
         L.lo_jacobian_row.argtypes = [_f32p, _f32p, _f32p, C.c_int, _f32p, _f32p]
         L.lo_scan2map.argtypes = [C.POINTER(S2MConfig), _f32p, C.c_size_t, _f32p, C.c_size_t,
                                   _f32p, _f32p, _i32p, C.POINTER(S2MResult),
@@ -119,6 +122,10 @@ class Oracle:
         L.lo_extract_features.restype = C.c_int
         L.lo_corner_optimization.argtypes = [C.POINTER(S2MConfig), _f32p, _f32p, C.c_size_t, _f32p,
                                              C.c_size_t, C.c_void_p, _u8p, _f32p, _i32p]
+        L.lo_corner_fit.argtypes = [C.POINTER(S2MConfig), _f32p, _f32p, _u8p, _f32p]
+        L.lo_corner_fit.restype = None
+        L.lo_corner_fit_batch.argtypes = [C.POINTER(S2MConfig), C.c_size_t, _f32p, _f32p, _u8p, _f32p]
+        L.lo_corner_fit_batch.restype = None
         L.lo_scan2map_cs.argtypes = [C.POINTER(S2MConfig), _f32p, C.c_size_t, _f32p, C.c_size_t, _f32p, C.c_size_t,
                                      _f32p, C.c_size_t, _f32p, _f32p, _i32p, C.POINTER(S2MResult),
                                      C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -222,6 +229,30 @@ class Oracle:
                 self.lib.lo_kdtree_free(tree)
         return flag, coeff, nn
 
+    def lm_step(self, cfg, it, AtA, AtB, pose, matP, is_degenerate):
+        """LMOptimization from the normal equations onward -> (pose, matP (6, 6), is_degenerate, converged)."""
+        pose = np.array(pose, np.float32).copy()
+        matP = np.array(matP, np.float32).reshape(36).copy()
+        deg = np.array([is_degenerate], np.int32)
+        conv = self.lib.lo_lm_step(C.byref(cfg), int(it), np.ascontiguousarray(AtA, np.float32).reshape(36),
+                                   np.ascontiguousarray(AtB, np.float32).reshape(6), pose, matP, deg)
+        return pose, matP.reshape(6, 6), int(deg[0]), int(conv)
+
+    def lm_step_batch(self, cfg, it, AtA, AtB, pose, matP, is_degenerate):
+        """n cases of lm_step: it (n,), AtA (n, 36), AtB (n, 6), pose (n, 6), matP (n, 36), is_degenerate (n,)
+        -> (pose, matP, is_degenerate, converged), the inputs left unchanged."""
+        it = np.ascontiguousarray(it, np.int32)
+        n = len(it)
+        AtA = np.ascontiguousarray(AtA, np.float32).reshape(n, 36)
+        AtB = np.ascontiguousarray(AtB, np.float32).reshape(n, 6)
+        pose = np.array(pose, np.float32).reshape(n, 6).copy()
+        matP = np.array(matP, np.float32).reshape(n, 36).copy()
+        deg = np.array(is_degenerate, np.int32).reshape(n).copy()
+        conv = np.zeros(n, np.int32)
+        if n:
+            self.lib.lo_lm_step_batch(C.byref(cfg), n, it, AtA.reshape(-1), AtB.reshape(-1), pose.reshape(-1), matP.reshape(-1), deg, conv)
+        return pose, matP, deg, conv
+
     def scan2map(self, cfg, scan_xyz, map_xyz, pose, matP=None, is_degenerate=0, corr_iter=-1):
         """Returns (pose_out, result, matP, corr) -- corr is None unless corr_iter >= 0."""
         scan_xyz = np.ascontiguousarray(scan_xyz, np.float32)
@@ -312,6 +343,23 @@ class Oracle:
             if tree:
                 self.lib.lo_kdtree_free(tree)
         return flag, coeff, nn
+
+    def corner_fit(self, cfg, five, point_sel):
+        """cornerOptimization after the 5-NN gate on one neighbour set (5, 3) and transformed point -> (flag, coeff)."""
+        flag = np.zeros(1, np.uint8); coeff = np.zeros(4, np.float32)
+        self.lib.lo_corner_fit(C.byref(cfg), np.ascontiguousarray(five, np.float32).reshape(15),
+                               np.ascontiguousarray(point_sel, np.float32).reshape(3), flag, coeff)
+        return int(flag[0]), coeff
+
+    def corner_fit_batch(self, cfg, five, point_sel):
+        """n cases of corner_fit: five (n, 5, 3), point_sel (n, 3) -> (flag (n,), coeff (n, 4))."""
+        five = np.ascontiguousarray(five, np.float32).reshape(-1, 15)
+        n = len(five)
+        pts = np.ascontiguousarray(point_sel, np.float32).reshape(n, 3)
+        flag = np.zeros(n, np.uint8); coeff = np.zeros((n, 4), np.float32)
+        if n:
+            self.lib.lo_corner_fit_batch(C.byref(cfg), n, five.reshape(-1), pts.reshape(-1), flag, coeff.reshape(-1))
+        return flag, coeff
 
     def scan2map_cs(self, cfg, corner_scan, corner_map, surf_scan, surf_map, pose, corr_iter=-1):
         cs = np.ascontiguousarray(corner_scan, np.float32).reshape(-1, 3)
