@@ -878,7 +878,9 @@ int  lio_height_map(int32_t device_id, const void *pts, size_t n, size_t stride_
                     float *grid, size_t grid_cap, lio_height_map_info *info);
 /* lio_kf_store_local_map's stages, then the chain above on the device cloud they leave: nothing goes to the host in between,
  * only the grid crosses.  lm_info (may be NULL) = what lio_kf_store_local_map reports for the same arguments.  An empty
- * store or an empty local map: LIO_OK, rows = cols = 0.  Replaces cloudMapInfoHandler, grid_map_pcl_loader_node.cpp:47-54. */
+ * store or an empty local map: LIO_OK, rows = cols = 0.  Replaces cloudMapInfoHandler, grid_map_pcl_loader_node.cpp:47-54.
+ * This call and the four lio_kf_store_* planning calls below are one chain with different stages behind the height map: on
+ * any return other than for a null argument the infos are zeroed or filled. */
 int  lio_kf_store_height_map(lio_kf_store *s, const lio_local_map_config *lm, const float pose[6],
                              const lio_height_map_config *cfg, float *grid, size_t grid_cap,
                              lio_local_map_info *lm_info, lio_height_map_info *info);
@@ -1290,7 +1292,8 @@ int  lio_grid_sample(lio_grid *g, const int32_t *layer_ids, int32_t n_layers, co
  * by device-to-device copy: layer 0 the raw elevation grid, layer 1 the filled grid (with fill), layers 2 .. 9 the eight
  * terrain layers in enum order (with terrain; all eight, whatever terrain->layers copies to the host).  The geometry is
  * hm_info's.  grid_out == NULL: lio_kf_store_planning_map.  An empty store or an empty map leaves the object without
- * layers.  A store and a grid on different devices: LIO_ERR_ARG. */
+ * layers, and so does a failure of the fill, of the terrain layers or of a copy into the object; a refusal of the field
+ * leaves them in place.  A store and a grid on different devices: LIO_ERR_ARG. */
 int  lio_kf_store_planning_grid(lio_kf_store *s, const lio_local_map_config *lm, const float pose[6],
                                 const lio_height_map_config *hm, const lio_median_fill_config *fill,
                                 const lio_terrain_config *terrain, lio_sdf *sdf, const lio_sdf_config *sdf_cfg,

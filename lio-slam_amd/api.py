@@ -1343,21 +1343,29 @@ def _height_map_call(call, what, want_grid):
     """One call into a grid buffer kept from the last one, as a node keeps it; a second only when the grid has outgrown the
     buffer (ERR_ARG with rows x cols filled in).  -> (grid [rows, cols] float32 (NaN: no elevation) or None, HeightMapInfo)."""
     info = HeightMapInfo()
-    if not want_grid:
-        _check(call(None, 0, info), what)
-        return None, info
-    buf = _scratch("height_map", (_SCRATCH_CELLS.get("height_map", 1 << 18),))
-    rc = call(buf.ctypes.data, buf.size, info)
-    if rc == -1 and info.rows * info.cols > buf.size:
-        _SCRATCH_CELLS["height_map"] = info.rows * info.cols
-        buf = _scratch("height_map", (info.rows * info.cols,))
-        rc = call(buf.ctypes.data, buf.size, info)
-    _check(rc, what)
+
+    def make_call(cells):
+        buf = _scratch("height_map", (cells if want_grid else 0,))
+        return call(buf.ctypes.data if want_grid else None, buf.size, info), buf
+    buf = _call_with_cells("height_map", 1 << 18, make_call, lambda: info.rows * info.cols if want_grid else 0, what)
     n = info.rows * info.cols
-    return buf[:n].reshape((info.rows, info.cols), order="F").copy(order="F"), info     # grid_map::Matrix is column-major
+    return (buf[:n].reshape((info.rows, info.cols), order="F").copy(order="F") if want_grid else None), info     # grid_map::Matrix is column-major
 
 
 _SCRATCH_CELLS = {}
+
+
+def _call_with_cells(key, default_cells, make_call, cells_of, what):
+    """make_call(cells) -> (rc, its buffers): one call into scratch buffers sized for `cells` grid cells, the size the last call
+    under `key` needed.  When it is refused (-1) with cells_of() -- the rows x cols it reports -- above that, the size is
+    remembered and the call is made once more.  -> the buffers of the call that counts, its rc checked."""
+    cells = _SCRATCH_CELLS.get(key, default_cells)
+    rc, bufs = make_call(cells)
+    if rc == -1 and cells_of() > cells:
+        cells = _SCRATCH_CELLS[key] = cells_of()
+        rc, bufs = make_call(cells)
+    _check(rc, what)
+    return bufs
 
 
 # processPointcloud, helpers.cpp:97-105 (grid_map_pcl's loader; DESIGN.md section 4e)
@@ -1866,18 +1874,14 @@ class KeyframeStore:
         p = np.ascontiguousarray(pose, np.float32).reshape(6)
         n_layers = bin(cfg.layers & 0xff).count("1")
         lm_info, hm_info, info = LocalMapInfo(), HeightMapInfo(), TerrainInfo()
-        cells = _SCRATCH_CELLS.get("terrain_map", 1 << 16)
-        while True:
+
+        def make_call(cells):
             grid = _scratch("terrain_grid", (cells,))
             layers = _scratch("terrain_layers", (max(cells * n_layers, 1),))
-            rc = self.lib.lio_kf_store_terrain_map(self.h, C.byref(lm_cfg), _f32p(p), C.byref(hm_cfg), C.byref(cfg),
-                                                   grid.ctypes.data if want_grid else None, grid.size, layers.ctypes.data, layers.size,
-                                                   C.byref(lm_info), C.byref(hm_info), C.byref(info))
-            if rc == -1 and info.rows * info.cols > cells:
-                cells = _SCRATCH_CELLS["terrain_map"] = info.rows * info.cols
-                continue
-            _check(rc, "lio_kf_store_terrain_map")
-            break
+            return self.lib.lio_kf_store_terrain_map(self.h, C.byref(lm_cfg), _f32p(p), C.byref(hm_cfg), C.byref(cfg),
+                                                     grid.ctypes.data if want_grid else None, grid.size, layers.ctypes.data, layers.size,
+                                                     C.byref(lm_info), C.byref(hm_info), C.byref(info)), (grid, layers)
+        grid, layers = _call_with_cells("terrain_map", 1 << 16, make_call, lambda: info.rows * info.cols, "lio_kf_store_terrain_map")
         n = info.rows * info.cols
         elev = grid[:n].reshape((info.rows, info.cols), order="F").copy(order="F") if want_grid else None
         return elev, _terrain_layers_out(layers, info, cfg.layers), info, hm_info, lm_info
@@ -1890,16 +1894,12 @@ class KeyframeStore:
         p = np.ascontiguousarray(pose, np.float32).reshape(6)
         lm_info, hm_info = LocalMapInfo(), HeightMapInfo()
         info = sdf.info = SdfInfo()
-        cells = _SCRATCH_CELLS.get("sdf_map", 1 << 16)
-        while True:
+
+        def make_call(cells):
             grid = _scratch("sdf_grid", (cells,))
-            rc = self.lib.lio_kf_store_sdf(self.h, C.byref(lm_cfg), _f32p(p), C.byref(hm_cfg), C.byref(cfg), grid.ctypes.data if want_grid else None,
-                                           grid.size, sdf.h, C.byref(lm_info), C.byref(hm_info), C.byref(info))
-            if rc == -1 and want_grid and hm_info.rows * hm_info.cols > cells:
-                cells = _SCRATCH_CELLS["sdf_map"] = hm_info.rows * hm_info.cols
-                continue
-            _check(rc, "lio_kf_store_sdf")
-            break
+            return self.lib.lio_kf_store_sdf(self.h, C.byref(lm_cfg), _f32p(p), C.byref(hm_cfg), C.byref(cfg), grid.ctypes.data if want_grid else None,
+                                             grid.size, sdf.h, C.byref(lm_info), C.byref(hm_info), C.byref(info)), grid
+        grid = _call_with_cells("sdf_map", 1 << 16, make_call, lambda: hm_info.rows * hm_info.cols if want_grid else 0, "lio_kf_store_sdf")
         n = hm_info.rows * hm_info.cols
         elev = grid[:n].reshape((hm_info.rows, hm_info.cols), order="F").copy(order="F") if want_grid else None
         return elev, info, hm_info, lm_info
@@ -1932,21 +1932,17 @@ class KeyframeStore:
         want_filled = want_filled and fill_cfg is not None
         want_fill_mask = want_fill_mask and fill_cfg is not None
         ref = lambda c: None if c is None else C.byref(c)
-        cells = _SCRATCH_CELLS.get("planning_map", 1 << 16)
-        while True:
+
+        def make_call(cells):
             bufs = {k: _scratch("planning_" + k, (max(cells * m, 1),)) for k, m in (("grid", 1), ("filled", 1), ("fill_mask", 1), ("layers", n_layers))}
             io = PlanningMapBuffers()
             for k, want in (("grid", want_grid), ("filled", want_filled), ("fill_mask", want_fill_mask), ("layers", n_layers > 0)):
                 setattr(io, k, bufs[k].ctypes.data if want else None)
                 setattr(io, k + "_cap", bufs[k].size if want else 0)
-            rc = getattr(self.lib, entry)(self.h, C.byref(lm_cfg), _f32p(p), C.byref(hm_cfg), ref(fill_cfg), ref(terrain_cfg),
-                                          sdf.h if sdf is not None else None, ref(sdf_cfg), C.byref(io), C.byref(lm_info),
-                                          C.byref(hm_info), C.byref(fill_info), C.byref(terrain_info), C.byref(sdf_info), *more_args)
-            if rc == -1 and hm_info.rows * hm_info.cols > cells:
-                cells = _SCRATCH_CELLS["planning_map"] = hm_info.rows * hm_info.cols
-                continue
-            _check(rc, entry)
-            break
+            return getattr(self.lib, entry)(self.h, C.byref(lm_cfg), _f32p(p), C.byref(hm_cfg), ref(fill_cfg), ref(terrain_cfg),
+                                            sdf.h if sdf is not None else None, ref(sdf_cfg), C.byref(io), C.byref(lm_info),
+                                            C.byref(hm_info), C.byref(fill_info), C.byref(terrain_info), C.byref(sdf_info), *more_args), bufs
+        bufs = _call_with_cells("planning_map", 1 << 16, make_call, lambda: hm_info.rows * hm_info.cols, entry)
         n, shape = hm_info.rows * hm_info.cols, (hm_info.rows, hm_info.cols)
         take = lambda k, want: bufs[k][:n].reshape(shape, order="F").copy(order="F") if want else None
         return dict(grid=take("grid", want_grid), filled=take("filled", want_filled), fill_mask=take("fill_mask", want_fill_mask),

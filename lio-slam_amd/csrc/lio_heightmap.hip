@@ -21,6 +21,7 @@
 #include "lio_cloud.h"
 #include "lio_compact.h"
 #include "lio_localmap.h"
+#include "lio_planning.h"
 #include "lio_pool.h"
 #include "lio_s2m_device.h"
 #include "lio_wg.h"
@@ -505,16 +506,11 @@ try {
     return rc;
 } LIO_CATCH
 
+// The local map's stages, then the chain above on the device cloud they leave: the planning chain (lio_planning.hip) without a
+// stage behind the height map.
 extern "C" int lio_kf_store_height_map(lio_kf_store* st, const lio_local_map_config* lm, const float* pose, const lio_height_map_config* cfg,
                                        float* grid, size_t grid_cap, lio_local_map_info* lm_info, lio_height_map_info* info)
 try {
     if (!st || !lm || !pose || !cfg || !info) return lio_fail(LIO_ERR_ARG, "null argument");
-    int rc = lio_height_map_check(cfg);
-    if (rc != LIO_OK) return rc;
-    memset(info, 0, sizeof(*info));
-    hipStream_t s = nullptr;
-    LocalMapBufs B;
-    if ((rc = lio_local_map_device(st, lm, pose, B, nullptr, lm_info, s)) != LIO_OK) return rc;
-    if (B.n_cur == 0) return LIO_OK;                       // an empty store or an empty crop: rows = cols = 0
-    return lio_height_map_device(B.cur, B.n_cur, cfg, grid, grid_cap, info, s);
+    return lio_planning_chain(st, lm, pose, cfg, { .out = { .grid = grid, .grid_cap = grid_cap }, .lm_info = lm_info, .hm_info = info });
 } LIO_CATCH

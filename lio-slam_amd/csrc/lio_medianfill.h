@@ -114,6 +114,8 @@ LIO_MF_HD void lio_mf_cell(const LioMfParams& P, const M& in, float mask, int r,
 // The configuration against `resolution`, before any device is touched: LIO_ERR_ARG as include/liogpu.h lists.  Fills
 // everything of *P but rows and cols.
 int lio_median_fill_check(const lio_median_fill_config* cfg, double resolution, LioMfParams* P);
+// *info zeroed, then the size and the two radii in cells: what the info holds before the filter has run.
+void lio_median_fill_info_begin(lio_median_fill_info* info, const LioMfParams& P, int rows, int cols);
 // The filter on the device grid d_in (P.rows x P.cols, column-major) on stream s: the filled grid to d_filled (device, the
 // same size, not d_in), and to the host whatever of filled / fill_mask / cleaned_mask is not NULL.  mask_in (host, may be
 // NULL): the mask of a previous run, used as it is; cleaned_mask is then left alone.  Synchronous.

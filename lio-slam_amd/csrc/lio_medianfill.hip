@@ -9,8 +9,7 @@
 //               A lane that fills selects the median by counting over the LDS window (lio_mf_median): 33 (2R + 1)^2 reads,
 //               none for a lane that copies.  The five counts by ballot, one atomic per wave and counter.
 // The per-cell arithmetic is lio_medianfill.h's.  DESIGN.md section 4j: conventions, resources, what was measured.
-// Also here: lio_kf_store_planning_map, the one chain that feeds the filled grid to the terrain layers and the field, and
-// lio_kf_store_planning_grid, the same body with a resident layer set (lio_gridsample.hip) as a sink for its grids.
+// The median fill only: the chain that runs it behind the height map of the resident keyframes is lio_planning.hip.
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <math.h>
@@ -18,13 +17,8 @@
 #include <string.h>
 
 #include "lio_medianfill.h"
-#include "lio_gridsample.h"
 #include "lio_cloud.h"
-#include "lio_heightmap.h"
-#include "lio_kfstore.h"
-#include "lio_localmap.h"
 #include "lio_pool.h"
-#include "lio_sdf.h"
 #include "lio_terrain.h"
 
 struct MfLine {                    // a line of a byte plane in LDS: entry k at p[k * stride]
@@ -136,7 +130,7 @@ int lio_median_fill_check(const lio_median_fill_config* c, double resolution, Li
     return LIO_OK;
 }
 
-static void mf_info_begin(lio_median_fill_info* info, const LioMfParams& P, int rows, int cols)
+void lio_median_fill_info_begin(lio_median_fill_info* info, const LioMfParams& P, int rows, int cols)
 {
     memset(info, 0, sizeof(*info));
     info->rows = rows; info->cols = cols;
@@ -182,7 +176,7 @@ try {
     LioMfParams P;
     int rc = lio_median_fill_check(cfg, resolution, &P);
     if (rc != LIO_OK) return rc;
-    mf_info_begin(info, P, rows, cols);
+    lio_median_fill_info_begin(info, P, rows, cols);
     if (rows == 0 || cols == 0) return LIO_OK;             // no cell: nothing written
     if (!elevation || !filled) return lio_fail(LIO_ERR_ARG, "null argument");
     if ((long long)rows * cols > 0x7fffffffLL - 1024) return lio_fail(LIO_ERR_CAPACITY, "the grid has more than 2^31 cells");
@@ -199,134 +193,4 @@ try {
     if (rc < 0) return rc;
     HIPCHK(e);
     return rc;
-} LIO_CATCH
-
-// A stage failed with the sink half written: the object holds no layers.  Returns rc.
-static int planning_sink_failed(lio_grid* sink, int rc)
-{
-    if (sink) lio_grid_clear(sink);
-    return rc;
-}
-
-// The height map's chain once, then whichever of the fill, the terrain layers and the field was asked for, each on the grid
-// the stage before it left on the device: the same null stream, complete on return.  `sink` (may be NULL): a resident layer
-// set (lio_gridsample.hip) that receives the raw grid, the filled grid and the eight terrain layers by device-to-device copy.
-static int planning_chain(lio_kf_store* st, const lio_local_map_config* lm, const float* pose, const lio_height_map_config* hm,
-                          const lio_median_fill_config* fill, const lio_terrain_config* terrain, lio_sdf* sdf, const lio_sdf_config* sdf_cfg,
-                          const lio_planning_map_buffers* out, lio_local_map_info* lm_info, lio_height_map_info* hm_info,
-                          lio_median_fill_info* fill_info, lio_terrain_info* terrain_info, lio_sdf_info* sdf_info, lio_grid* sink)
-{
-    lio_height_map_info hm_local;
-    lio_median_fill_info fill_local;
-    lio_terrain_info terrain_local;
-    lio_sdf_info sdf_local;
-    lio_planning_map_buffers no_out;
-    memset(&no_out, 0, sizeof(no_out));
-    if (!hm_info) hm_info = &hm_local;
-    if (!fill_info) fill_info = &fill_local;
-    if (!terrain_info) terrain_info = &terrain_local;
-    if (!sdf_info) sdf_info = &sdf_local;
-    if (!out) out = &no_out;
-    memset(hm_info, 0, sizeof(*hm_info));
-    memset(fill_info, 0, sizeof(*fill_info));
-    memset(terrain_info, 0, sizeof(*terrain_info));
-    memset(sdf_info, 0, sizeof(*sdf_info));
-    if (!st || !lm || !pose || !hm || (sdf && !sdf_cfg)) return lio_fail(LIO_ERR_ARG, "null argument");
-    int rc = lio_height_map_check(hm);
-    if (rc != LIO_OK) return rc;
-    LioMfParams P;
-    LioTerrPlan plan;
-    if (fill) {
-        if ((rc = lio_median_fill_check(fill, hm->resolution, &P)) != LIO_OK) return rc;
-        mf_info_begin(fill_info, P, 0, 0);
-    }
-    if (terrain) {
-        if ((rc = lio_terrain_check(terrain, hm->resolution, &plan)) != LIO_OK) return rc;
-        terrain_info->normal_method_used = plan.method_used; terrain_info->edge_window_size = plan.window;
-    }
-    if (sdf) {
-        if ((rc = lio_sdf_config_check(sdf_cfg)) != LIO_OK) return rc;
-        if ((rc = lio_sdf_begin(sdf, st->device_id)) != LIO_OK) return rc;
-    }
-    if (sink && (rc = lio_grid_begin(sink, st->device_id)) != LIO_OK) return rc;
-    hipStream_t s = nullptr;
-    LocalMapBufs B;
-    if ((rc = lio_local_map_device(st, lm, pose, B, nullptr, lm_info, s)) != LIO_OK) return rc;
-    if (B.n_cur == 0) return LIO_OK;                       // an empty store or an empty crop: rows = cols = 0
-    LioTemp d_grid, d_filled;
-    if (!fill && !terrain && !sdf && !sink) return lio_height_map_device(B.cur, B.n_cur, hm, out->grid, out->grid_cap, hm_info, s);      // lio_kf_store_height_map
-    rc = lio_height_map_device(B.cur, B.n_cur, hm, out->grid, out->grid_cap, hm_info, s, &d_grid);
-    const int rows = hm_info->rows, cols = hm_info->cols;
-    if (fill) { fill_info->rows = rows; fill_info->cols = cols; }
-    if (terrain) { terrain_info->rows = rows; terrain_info->cols = cols; }
-    if (sdf) { sdf_info->rows = rows; sdf_info->cols = cols; }
-    if (rc != LIO_OK) return rc;
-    if (!d_grid.p) return LIO_OK;                          // no point left or no extent along an axis: no grid, nothing behind it
-    const size_t n_cells = (size_t)rows * (size_t)cols;
-    if (fill && ((out->filled && n_cells > out->filled_cap) || (out->fill_mask && n_cells > out->fill_mask_cap)))
-        return lio_fail(LIO_ERR_ARG, "filled or fill_mask holds fewer floats than the grid has cells (info)");
-    if (terrain && out->layers && (size_t)plan.n_out * n_cells > out->layers_cap)
-        return lio_fail(LIO_ERR_ARG, "layers holds fewer floats than the requested layers (info)");
-    const float* d_elev = d_grid.as<float>();
-    float* d_sink[LIO_GRID_LAYER_TERRAIN + LIO_TERRAIN_N_LAYERS];      // the sink's slots in use; copies into them are waited for below
-    memset(d_sink, 0, sizeof(d_sink));
-    if (sink) {
-        if ((rc = lio_grid_set_geometry(sink, rows, cols, hm->resolution, hm_info->length, hm_info->position)) != LIO_OK) return rc;
-        if ((rc = lio_grid_layer_slot(sink, LIO_GRID_LAYER_ELEVATION, &d_sink[LIO_GRID_LAYER_ELEVATION])) != LIO_OK) return rc;
-        if (fill && (rc = lio_grid_layer_slot(sink, LIO_GRID_LAYER_FILLED, &d_sink[LIO_GRID_LAYER_FILLED])) != LIO_OK) return planning_sink_failed(sink, rc);
-        for (int k = 0; terrain && k < LIO_TERRAIN_N_LAYERS; ++k)
-            if ((rc = lio_grid_layer_slot(sink, LIO_GRID_LAYER_TERRAIN + k, &d_sink[LIO_GRID_LAYER_TERRAIN + k])) != LIO_OK) return planning_sink_failed(sink, rc);
-        const hipError_t e = hipMemcpyAsync(d_sink[LIO_GRID_LAYER_ELEVATION], d_elev, sizeof(float) * n_cells, hipMemcpyDeviceToDevice, s);
-        if (e != hipSuccess) { planning_sink_failed(sink, 0); HIPCHK(e); }
-    }
-    if (fill) {
-        P.rows = rows; P.cols = cols;
-        HIPCHK(d_filled.alloc(sizeof(float) * n_cells));
-        if ((rc = lio_median_fill_device(d_elev, P, nullptr, d_filled.as<float>(), out->filled, out->fill_mask, nullptr, fill_info, s)) != LIO_OK) {
-            (void)hipStreamSynchronize(s);                 // (an early return leaves nothing in flight on the temporaries)
-            return planning_sink_failed(sink, rc);
-        }
-        d_elev = d_filled.as<float>();
-        if (sink) {
-            const hipError_t e = hipMemcpyAsync(d_sink[LIO_GRID_LAYER_FILLED], d_elev, sizeof(float) * n_cells, hipMemcpyDeviceToDevice, s);
-            if (e != hipSuccess) { (void)hipStreamSynchronize(s); planning_sink_failed(sink, 0); HIPCHK(e); }
-        }
-    }
-    if (terrain) {
-        if ((rc = lio_terrain_set_geometry(&plan, rows, cols, hm->resolution, hm_info->length, hm_info->position)) != LIO_OK) {
-            (void)hipStreamSynchronize(s);
-            return planning_sink_failed(sink, rc);
-        }
-        rc = lio_terrain_device(d_elev, plan, out->layers, terrain_info, s, sink ? d_sink + LIO_GRID_LAYER_TERRAIN : nullptr);
-        if (rc != LIO_OK) { (void)hipStreamSynchronize(s); return planning_sink_failed(sink, rc); }
-    }
-    if (sink) {                                            // the copies out of the temporaries are complete before these go back to the pool
-        const hipError_t e = hipStreamSynchronize(s);
-        if (e != hipSuccess) { planning_sink_failed(sink, 0); HIPCHK(e); }
-    }
-    if (sdf) {
-        if ((rc = lio_sdf_check(sdf_cfg, rows, cols, hm->resolution, hm_info->length, hm_info->position)) != LIO_OK) return rc;
-        rc = lio_sdf_build_device(sdf, d_elev, rows, cols, hm->resolution, hm_info->length, hm_info->position, *sdf_cfg, sdf_info, s);
-        (void)hipStreamSynchronize(s);
-    }
-    return rc;
-}
-
-extern "C" int lio_kf_store_planning_map(lio_kf_store* st, const lio_local_map_config* lm, const float* pose, const lio_height_map_config* hm,
-                                         const lio_median_fill_config* fill, const lio_terrain_config* terrain, lio_sdf* sdf,
-                                         const lio_sdf_config* sdf_cfg, const lio_planning_map_buffers* out, lio_local_map_info* lm_info,
-                                         lio_height_map_info* hm_info, lio_median_fill_info* fill_info, lio_terrain_info* terrain_info,
-                                         lio_sdf_info* sdf_info)
-try {
-    return planning_chain(st, lm, pose, hm, fill, terrain, sdf, sdf_cfg, out, lm_info, hm_info, fill_info, terrain_info, sdf_info, nullptr);
-} LIO_CATCH
-
-// The same chain, which also leaves its grids in the resident layer set `grid_out` (NULL: none).
-extern "C" int lio_kf_store_planning_grid(lio_kf_store* st, const lio_local_map_config* lm, const float* pose, const lio_height_map_config* hm,
-                                          const lio_median_fill_config* fill, const lio_terrain_config* terrain, lio_sdf* sdf,
-                                          const lio_sdf_config* sdf_cfg, const lio_planning_map_buffers* out, lio_local_map_info* lm_info,
-                                          lio_height_map_info* hm_info, lio_median_fill_info* fill_info, lio_terrain_info* terrain_info,
-                                          lio_sdf_info* sdf_info, lio_grid* grid_out)
-try {
-    return planning_chain(st, lm, pose, hm, fill, terrain, sdf, sdf_cfg, out, lm_info, hm_info, fill_info, terrain_info, sdf_info, grid_out);
 } LIO_CATCH

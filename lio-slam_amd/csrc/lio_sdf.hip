@@ -25,9 +25,7 @@
 
 #include "lio_sdf.h"
 #include "lio_cloud.h"
-#include "lio_heightmap.h"
-#include "lio_kfstore.h"
-#include "lio_localmap.h"
+#include "lio_planning.h"
 #include "lio_pool.h"
 #include "lio_wg.h"
 
@@ -418,35 +416,15 @@ try {
     return rc;
 } LIO_CATCH
 
-// The height map's chain, then the build on the device grid it leaves: the same null stream, complete on return.
+// The height map's chain, then the build on the device grid it leaves: the planning chain (lio_planning.hip) with the field as
+// its one stage.  info and hm_info may be NULL.
 extern "C" int lio_kf_store_sdf(lio_kf_store* st, const lio_local_map_config* lm, const float* pose, const lio_height_map_config* hm,
                                 const lio_sdf_config* cfg, float* grid, size_t grid_cap, lio_sdf* sdf, lio_local_map_info* lm_info,
                                 lio_height_map_info* hm_info, lio_sdf_info* info)
 try {
-    lio_sdf_info local;
-    lio_height_map_info hlocal;
-    if (!info) info = &local;
-    if (!hm_info) hm_info = &hlocal;
-    memset(info, 0, sizeof(*info));
-    memset(hm_info, 0, sizeof(*hm_info));
     if (!st || !lm || !pose || !hm || !cfg || !sdf) return lio_fail(LIO_ERR_ARG, "null argument");
-    int rc = lio_height_map_check(hm);
-    if (rc != LIO_OK) return rc;
-    if ((rc = lio_sdf_config_check(cfg)) != LIO_OK) return rc;
-    if ((rc = lio_sdf_begin(sdf, st->device_id)) != LIO_OK) return rc;
-    hipStream_t s = nullptr;
-    LocalMapBufs B;
-    if ((rc = lio_local_map_device(st, lm, pose, B, nullptr, lm_info, s)) != LIO_OK) return rc;
-    if (B.n_cur == 0) return LIO_OK;                       // an empty store or an empty crop: rows = cols = 0
-    LioTemp d_grid;
-    rc = lio_height_map_device(B.cur, B.n_cur, hm, grid, grid_cap, hm_info, s, &d_grid);
-    info->rows = hm_info->rows; info->cols = hm_info->cols;
-    if (rc != LIO_OK) return rc;
-    if (!d_grid.p) return LIO_OK;                          // no point left or no extent along an axis: no grid, no field
-    if ((rc = lio_sdf_check(cfg, hm_info->rows, hm_info->cols, hm->resolution, hm_info->length, hm_info->position)) != LIO_OK) return rc;
-    rc = lio_sdf_build_device(sdf, d_grid.as<float>(), hm_info->rows, hm_info->cols, hm->resolution, hm_info->length, hm_info->position, *cfg, info, s);
-    (void)hipStreamSynchronize(s);                         // (an early return leaves nothing in flight on `d_grid`)
-    return rc;
+    return lio_planning_chain(st, lm, pose, hm, { .sdf_cfg = cfg, .sdf = sdf, .out = { .grid = grid, .grid_cap = grid_cap }, .lm_info = lm_info,
+                                                  .hm_info = hm_info, .sdf_info = info });
 } LIO_CATCH
 
 extern "C" int lio_sdf_nodes(lio_sdf* sdf, float* nodes, size_t cap_floats)

@@ -16,8 +16,7 @@
 
 #include "lio_terrain.h"
 #include "lio_cloud.h"
-#include "lio_heightmap.h"
-#include "lio_localmap.h"
+#include "lio_planning.h"
 #include "lio_pool.h"
 
 // out: LIO_TERRAIN_N_LAYERS layers of rows x cols (this kernel writes all but LIO_TERRAIN_EDGES).  counters[0..3] += finite
@@ -196,31 +195,13 @@ try {
     return rc;
 } LIO_CATCH
 
-// The height map's chain, then the terrain layers (lio_terrain.hip) on the device grid it leaves: the same null stream, complete
-// on return.
+// The height map's chain, then the terrain layers on the device grid it leaves: the planning chain (lio_planning.hip) with the
+// terrain layers as its one stage.
 extern "C" int lio_kf_store_terrain_map(lio_kf_store* st, const lio_local_map_config* lm, const float* pose, const lio_height_map_config* hm,
                                         const lio_terrain_config* cfg, float* grid, size_t grid_cap, float* layers, size_t layers_cap,
                                         lio_local_map_info* lm_info, lio_height_map_info* hm_info, lio_terrain_info* info)
 try {
     if (!st || !lm || !pose || !hm || !cfg || !hm_info || !info) return lio_fail(LIO_ERR_ARG, "null argument");
-    int rc = lio_height_map_check(hm);
-    if (rc != LIO_OK) return rc;
-    LioTerrPlan plan;
-    if ((rc = lio_terrain_check(cfg, hm->resolution, &plan)) != LIO_OK) return rc;
-    memset(hm_info, 0, sizeof(*hm_info));
-    memset(info, 0, sizeof(*info));
-    info->normal_method_used = plan.method_used; info->edge_window_size = plan.window;
-    hipStream_t s = nullptr;
-    LocalMapBufs B;
-    if ((rc = lio_local_map_device(st, lm, pose, B, nullptr, lm_info, s)) != LIO_OK) return rc;
-    if (B.n_cur == 0) return LIO_OK;                       // an empty store or an empty crop: rows = cols = 0
-    LioTemp d_grid;
-    rc = lio_height_map_device(B.cur, B.n_cur, hm, grid, grid_cap, hm_info, s, &d_grid);
-    info->rows = hm_info->rows; info->cols = hm_info->cols;
-    if (rc != LIO_OK) return rc;
-    if (!d_grid.p) return LIO_OK;                          // no point left or no extent along an axis: no grid, no layers
-    const size_t n_cells = (size_t)info->rows * (size_t)info->cols;
-    if (layers && (size_t)plan.n_out * n_cells > layers_cap) return lio_fail(LIO_ERR_ARG, "layers holds fewer floats than the requested layers (info)");
-    if ((rc = lio_terrain_set_geometry(&plan, info->rows, info->cols, hm->resolution, hm_info->length, hm_info->position)) != LIO_OK) return rc;
-    return lio_terrain_device(d_grid.as<float>(), plan, layers, info, s);
+    return lio_planning_chain(st, lm, pose, hm, { .terrain = cfg, .out = { .grid = grid, .grid_cap = grid_cap, .layers = layers, .layers_cap = layers_cap },
+                                                  .lm_info = lm_info, .hm_info = hm_info, .terrain_info = info });
 } LIO_CATCH

@@ -280,3 +280,73 @@ def test_planning_map_with_holes_left_and_refusals(pkg, dense_store):
     with pytest.raises(pkg.LioError, match="ERR_ARG"):         # an empty local map leaves no field
         sdf.nodes()
     sdf.close()
+
+
+def test_the_older_store_entries_are_the_chain_with_one_stage(pkg, dense_store):
+    """lio_kf_store_height_map, lio_kf_store_terrain_map and lio_kf_store_sdf against lio_kf_store_planning_map with only their
+    stage requested: the bytes of the grid, of every layer and of the nodes, and every info field; the same on an empty store and
+    without the grid; a grid buffer of one float is refused by both with rows and cols filled in."""
+    pose = np.zeros(6, f32)
+    lm = pkg.local_map_default_config(n_keyframes=4, front=8.0, left=6.0, back=5.0, right=6.0)
+    hm = pkg.height_map_default_config(resolution=RES, fill_holes=0)
+    terrain = pkg.terrain_default_config(normal_radius=0.5, smooth_radius=0.6, edge_window_length=0.5)
+    sdf_cfg = pkg.sdf_default_config(nan_policy=1)
+    own, chained = pkg.Sdf(), pkg.Sdf()
+    empty = pkg.KeyframeStore()
+
+    def same_grid(a, b, what):
+        assert (a is None) == (b is None), what
+        if a is not None:
+            assert a.shape == b.shape and a.tobytes() == b.tobytes(), what
+
+    for st, want_grid in ((dense_store, True), (dense_store, False), (empty, True), (empty, False)):
+        what = ("empty store" if st is empty else "dense store", "grid" if want_grid else "no grid")
+        grid, hm_info, lm_info = st.height_map(pose, lm, hm, want_grid=want_grid)
+        out = st.planning_map(pose, lm, hm, want_grid=want_grid)
+        same_grid(grid, out["grid"], (what, "height_map"))
+        same_struct(hm_info, out["hm_info"], (what, "height_map, hm_info"))
+        same_struct(lm_info, out["lm_info"], (what, "height_map, lm_info"))
+        assert (hm_info.rows > 40 and hm_info.cols > 40) if st is dense_store else (hm_info.rows, hm_info.cols) == (0, 0), what
+
+        grid, layers, info, hm_info, lm_info = st.terrain_map(pose, lm, hm, terrain, want_grid=want_grid)
+        out = st.planning_map(pose, lm, hm, None, terrain, want_grid=want_grid)
+        same_grid(grid, out["grid"], (what, "terrain_map"))
+        for name in pkg.TERRAIN_LAYERS:
+            same_grid(layers[name], out["layers"][name], (what, name))
+        same_struct(info, out["terrain_info"], (what, "terrain_info"))
+        same_struct(hm_info, out["hm_info"], (what, "terrain_map, hm_info"))
+        same_struct(lm_info, out["lm_info"], (what, "terrain_map, lm_info"))
+        assert (info.rows, info.cols) == (hm_info.rows, hm_info.cols), what
+
+        grid, info, hm_info, lm_info = st.sdf_map(own, pose, lm, hm, sdf_cfg, want_grid=want_grid)
+        out = st.planning_map(pose, lm, hm, None, None, chained, sdf_cfg, want_grid=want_grid)
+        same_grid(grid, out["grid"], (what, "sdf_map"))
+        same_struct(info, out["sdf_info"], (what, "sdf_info"))
+        same_struct(hm_info, out["hm_info"], (what, "sdf_map, hm_info"))
+        same_struct(lm_info, out["lm_info"], (what, "sdf_map, lm_info"))
+        if st is dense_store:
+            assert info.layers >= 2 and own.nodes().tobytes() == chained.nodes().tobytes(), what
+        else:                                                  # an empty local map leaves no field in either object
+            for sdf in (own, chained):
+                with pytest.raises(pkg.LioError, match="ERR_ARG"):
+                    sdf.nodes()
+    empty.close()
+
+    # a grid buffer of one float: refused, with rows x cols in the height map's info and in the stage's
+    st, lib = dense_store, pkg.load_library()
+    _, hm_ref, _ = st.height_map(pose, lm, hm)
+    one = np.zeros(1, f32)
+    layers = np.zeros(8 * hm_ref.rows * hm_ref.cols, f32)
+    p = pose.ctypes.data_as(C.POINTER(C.c_float))
+    lm_info, hm_info, t_info, s_info = pkg.LocalMapInfo(), pkg.HeightMapInfo(), pkg.TerrainInfo(), pkg.SdfInfo()
+    rc = lib.lio_kf_store_terrain_map(st.h, C.byref(lm), p, C.byref(hm), C.byref(terrain), one.ctypes.data, one.size, layers.ctypes.data, layers.size,
+                                      C.byref(lm_info), C.byref(hm_info), C.byref(t_info))
+    assert rc == -1 and b"grid holds fewer cells" in lib.lio_last_error()
+    assert (hm_info.rows, hm_info.cols) == (t_info.rows, t_info.cols) == (hm_ref.rows, hm_ref.cols)
+    hm_info = pkg.HeightMapInfo()
+    rc = lib.lio_kf_store_sdf(st.h, C.byref(lm), p, C.byref(hm), C.byref(sdf_cfg), one.ctypes.data, one.size, own.h, C.byref(lm_info),
+                              C.byref(hm_info), C.byref(s_info))
+    assert rc == -1 and b"grid holds fewer cells" in lib.lio_last_error()
+    assert (hm_info.rows, hm_info.cols) == (s_info.rows, s_info.cols) == (hm_ref.rows, hm_ref.cols)
+    own.close()
+    chained.close()
