@@ -312,235 +312,179 @@ def build_library(verbose=False):
     return lib_path()
 
 
+# The C ABI: one line per symbol of include/liogpu.h, in the header's order.  name -> argtypes, or (restype, argtypes) where the
+# function does not return int.  load_library() binds from this table, EXPORTS is its names, and tests/test_capi_signatures.py
+# holds every line to the header's prototype.  A new entry point takes one line here.
+vp, i32, f32, f64, sz, u64, P = C.c_void_p, C.c_int32, C.c_float, C.c_double, C.c_size_t, C.c_uint64, C.POINTER
+pvp, pi, pf, pd, psz = P(vp), P(i32), P(f32), P(f64), P(sz)
+_PLANNING = [vp, P(LocalMapConfig), pf, P(HeightMapConfig), P(MedianFillConfig), P(TerrainConfig), vp, P(SdfConfig), P(PlanningMapBuffers),
+             P(LocalMapInfo), P(HeightMapInfo), P(MedianFillInfo), P(TerrainInfo), P(SdfInfo)]      # lio_kf_store_planning_map's
+CAPI = {
+    "lio_version": [],
+    "lio_s2m_default_config": (None, [P(S2MConfig)]),
+    "lio_last_error": (C.c_char_p, []),
+    "lio_s2m_create": [P(S2MConfig), pvp],
+    "lio_s2m_destroy": (None, [vp]),
+    "lio_s2m_set_map": [vp, vp, sz, sz],
+    "lio_s2m_register": [vp, vp, sz, sz, pf, P(S2MResult)],
+    "lio_s2m_batch_upload": [vp, i32, pvp, psz, sz],
+    "lio_s2m_batch_set_poses": [vp, pf],
+    "lio_s2m_batch_run": [vp],
+    "lio_s2m_batch_sync": [vp],
+    "lio_s2m_batch_results": [vp, pf, P(S2MResult)],
+    "lio_s2m_share_map": [vp, vp],
+    "lio_s2m_batch_upload_async": [vp, i32, pvp, psz, sz],
+    "lio_host_alloc": (vp, [sz]),
+    "lio_host_free": (None, [vp]),
+    "lio_host_register": [vp, sz],
+    "lio_host_unregister": [vp],
+    "lio_device_alloc": (vp, [i32, sz]),
+    "lio_device_free": (None, [i32, vp]),
+    "lio_device_upload": [i32, vp, vp, sz],
+    "lio_s2m_set_degeneracy": [vp, i32, pf, i32],
+    "lio_s2m_get_correspondences": [vp, i32, vp, vp, vp],
+    "lio_s2m_set_corner_map": [vp, vp, sz, sz],
+    "lio_s2m_batch_upload_corners": [vp, i32, pvp, psz, sz],
+    "lio_s2m_register_cs": [vp, vp, sz, vp, sz, sz, pf, P(S2MResult)],
+    "lio_s2m_get_corner_correspondences": [vp, i32, vp, vp, vp],
+    "lio_s2m_get_profile": [vp, P(S2MProfile)],
+    "lio_s2m_kernel_variant": [vp],
+    "lio_s2m_launch_forms": [vp, pi, pi],
+    "lio_s2m_debug_persist_spin": [vp, i32, i32],
+    "lio_debug_plane_fit": [i32, vp, sz, f64, vp],
+    "lio_debug_gn_step": [i32, P(S2MConfig), sz, vp, vp, vp, vp, vp, i32, i32, i32, vp],
+    "lio_debug_corner_fit": [i32, vp, vp, sz, f64, f64, vp],
+    "lio_debug_fast_f32_ops": [i32, i32, i32, vp, u64, u64, vp, P(u64), vp, pi],
+    "lio_debug_threshold_f32": (f32, [f64]),
+    "lio_debug_grid_plan": [P(S2MConfig), pf, pf, sz, i32, i32, P(GridPlanInfo)],
+    "lio_s2m_debug_stamps": [vp, vp, sz],
+    "lio_s2m_debug_scan_order": [vp, vp, vp, sz, pi],
+    "lio_debug_scan_tile_plan": [pf, pf, f32, i32, pi, pf],
+    "lio_s2m_set_stream": [vp, vp],
+    "lio_s2m_set_global_grid": [vp, pf, pi],
+    "lio_s2m_set_shard": [vp, i32, i32, i32],
+    "lio_s2m_set_shard_plan": [vp, i32, i32, i32, pi, i32],
+    "lio_s2m_set_scan_shard": [vp, i32, i32],
+    "lio_s2m_batch_begin": [vp],
+    "lio_s2m_batch_iter_partial": [vp, vp],
+    "lio_s2m_batch_iter_apply": [vp, vp],
+    "lio_s2m_batch_n_active": [vp, pi],
+    "lio_s2m_batch_poll_active": [vp, i32, pi],
+    "lio_transform_update": (None, [pf, i32, i32, f32, f32, f32, f32, f32]),
+    "lio_deskew_default_config": (None, [P(DeskewConfig)]),
+    "lio_imu_deskew_info": [pd, pd, pd, pd, i32, f64, f64, pd, pd, pd, pd],
+    "lio_deskew": [P(DeskewConfig), vp, sz, sz, f64, pd, pd, pd, pd, i32, vp, sz, psz],
+    "lio_s2m_register_pc2": [vp, vp, sz, P(PC2Layout), pf, P(S2MResult)],
+    "lio_s2m_register_raw": [vp, vp, sz, P(PC2Layout), f32, pf, P(S2MResult), vp, sz, psz],
+    "lio_deskew_pc2": [P(DeskewConfig), vp, sz, P(PC2Layout), f64, pd, pd, pd, pd, i32, vp, sz, psz],
+    "lio_range_image_default_config": (None, [P(RangeImageConfig)]),
+    "lio_range_image": [P(RangeImageConfig), vp, sz, sz, f64, pd, pd, pd, pd, i32, vp, sz, psz, vp, vp, vp, vp],
+    "lio_curvature": [i32, vp, sz, vp, vp, vp],
+    "lio_feature_default_config": (None, [P(FeatureConfig)]),
+    "lio_extract_features": [P(FeatureConfig), vp, sz, sz, vp, vp, vp, vp, vp, psz, vp, psz, sz, vp, vp, vp],
+    "lio_voxel_grid": [i32, vp, sz, sz, f32, vp, sz, psz],
+    "lio_assemble_map": [vp, i32, i32, pvp, psz, sz, pf, f32, vp, sz, psz],
+    "lio_kf_store_create": [i32, pvp],
+    "lio_kf_store_destroy": (None, [vp]),
+    "lio_kf_store_add": [vp, vp, sz, sz, pi],
+    "lio_kf_store_count": [vp],
+    "lio_kf_store_points": (sz, [vp, i32]),
+    "lio_kf_store_add_device": [vp, vp, sz, sz, pi],
+    "lio_kf_store_add_from_handle": [vp, vp, i32, pi],
+    "lio_assemble_map_resident": [vp, vp, i32, pi, pf, f32, vp, sz, psz],
+    "lio_nearby_default_config": (None, [P(NearbyConfig)]),
+    "lio_kf_store_set_poses": [vp, i32, i32, pf, pd],
+    "lio_assemble_map_nearby": [vp, vp, P(NearbyConfig), f64, f32, pi, i32, pi, vp, sz, sz, psz],
+    "lio_icp_default_config": (None, [P(IcpConfig)]),
+    "lio_icp_align": [i32, vp, sz, sz, vp, sz, sz, P(IcpConfig), pf, P(IcpResult)],
+    "lio_kf_store_loop_icp": [vp, i32, i32, i32, i32, f32, P(IcpConfig), P(IcpResult), P(IcpClouds)],
+    "lio_kf_store_detect_loop": [vp, f32, f64, f64, pi, pi],
+    "lio_icp_debug_trace": [i32, vp, sz, sz, vp, sz, sz, P(IcpConfig), pf, i32, P(IcpResult), vp, vp, vp, vp, pi],
+    "lio_icp_debug_grid": [i32, vp, sz, sz, P(IcpGridInfo)],
+    "lio_sc_default_config": (None, [P(ScConfig)]),
+    "lio_sc_make": [i32, vp, sz, sz, P(ScConfig), vp, vp, vp],
+    "lio_kf_store_sc_add": [vp, vp, sz, sz, P(ScConfig), pi],
+    "lio_kf_store_sc_add_device": [vp, vp, sz, sz, P(ScConfig), pi],
+    "lio_kf_store_sc_add_from_handle": [vp, vp, P(ScConfig), pi],
+    "lio_kf_store_sc_count": [vp],
+    "lio_kf_store_sc_geometry": [vp, pi, pi],
+    "lio_kf_store_sc_get": [vp, i32, vp, vp, vp],
+    "lio_kf_store_sc_detect": [vp, P(ScConfig), P(ScResult)],
+    "lio_sc_distance": [i32, vp, vp, P(ScConfig), pd, pi],
+    "lio_sor_filter": [i32, vp, sz, sz, i32, f32, vp, sz, psz, vp, pd],
+    "lio_sor_debug_grid": [i32, vp, sz, sz, i32, P(IcpGridInfo)],
+    "lio_local_map_default_config": (None, [P(LocalMapConfig)]),
+    "lio_kf_store_local_map": [vp, P(LocalMapConfig), pf, vp, sz, sz, psz, P(LocalMapInfo)],
+    "lio_height_map_default_config": (None, [P(HeightMapConfig)]),
+    "lio_height_map": [i32, vp, sz, sz, P(HeightMapConfig), vp, sz, P(HeightMapInfo)],
+    "lio_kf_store_height_map": [vp, P(LocalMapConfig), pf, P(HeightMapConfig), vp, sz, P(LocalMapInfo), P(HeightMapInfo)],
+    "lio_terrain_default_config": (None, [P(TerrainConfig)]),
+    "lio_terrain_layers": [i32, vp, i32, i32, f64, pd, pd, P(TerrainConfig), vp, sz, P(TerrainInfo)],
+    "lio_kf_store_terrain_map": [vp, P(LocalMapConfig), pf, P(HeightMapConfig), P(TerrainConfig), vp, sz, vp, sz, P(LocalMapInfo), P(HeightMapInfo),
+                                 P(TerrainInfo)],
+    "lio_global_map_default_config": (None, [P(GlobalMapConfig)]),
+    "lio_kf_store_global_map": [vp, P(GlobalMapConfig), pi, i32, pi, vp, sz, sz, psz, P(GlobalMapInfo)],
+    "lio_kf_store_export_map": [vp, P(ExportConfig), vp, sz, sz, psz, vp, sz, sz, psz, pi],
+    "lio_kf_store_get_keyframe": [vp, i32, pf, vp, sz, sz, psz],
+    "lio_s2m_registered_cloud": [vp, i32, pf, vp, sz, sz, psz],
+    "lio_radius_filter": [i32, vp, sz, sz, f32, i32, vp, sz, psz, vp],
+    "lio_ogm_default_config": (None, [P(OgmConfig)]),
+    "lio_occupancy_grid": [i32, vp, sz, sz, P(OgmConfig), vp, sz, P(OgmInfo)],
+    "lio_kf_store_occupancy_grid": [vp, f32, P(OgmConfig), vp, sz, psz, P(OgmInfo)],
+    "lio_ogm_debug_stage_ms": [i32, pf],
+    "lio_sdf_default_config": (None, [P(SdfConfig)]),
+    "lio_sdf_create": [i32, pvp],
+    "lio_sdf_destroy": (None, [vp]),
+    "lio_sdf_build": [vp, vp, i32, i32, f64, pd, pd, P(SdfConfig), P(SdfInfo)],
+    "lio_kf_store_sdf": [vp, P(LocalMapConfig), pf, P(HeightMapConfig), P(SdfConfig), vp, sz, vp, P(LocalMapInfo), P(HeightMapInfo), P(SdfInfo)],
+    "lio_sdf_nodes": [vp, vp, sz],
+    "lio_sdf_query": [vp, vp, sz, vp, vp],
+    "lio_occupancy_sdf": [i32, vp, i32, i32, f32, i32, vp],
+    "lio_sdf_memory": [vp, psz, psz],
+    "lio_sdf_debug_stage_ms": [i32, pf],
+    "lio_median_fill_default_config": (None, [P(MedianFillConfig)]),
+    "lio_median_fill": [i32, vp, i32, i32, f64, P(MedianFillConfig), vp, vp, vp, vp, P(MedianFillInfo)],
+    "lio_kf_store_planning_map": _PLANNING,
+    "lio_grid_sample_default_config": (None, [P(GridSampleConfig)]),
+    "lio_grid_create": [i32, pvp],
+    "lio_grid_destroy": (None, [vp]),
+    "lio_grid_set_layers": [vp, vp, i32, i32, i32, f64, pd, pd],
+    "lio_grid_get_layer": [vp, i32, vp, sz],
+    "lio_grid_info": [vp, P(GridInfo)],
+    "lio_grid_memory": [vp, psz],
+    "lio_grid_sample": [vp, pi, i32, P(GridSampleConfig), vp, sz, vp, vp, P(GridSampleInfo)],
+    "lio_kf_store_planning_grid": _PLANNING + [vp],
+    "lio_grid_debug_stage_ms": [i32, pf],
+    "lio_grid_region_default_config": (None, [P(GridRegionConfig)]),
+    "lio_grid_region_reduce": [vp, pi, i32, P(GridRegionConfig), vp, sz, vp, sz, vp, vp, vp, P(GridRegionInfo)],
+    "lio_grid_region_cells": [vp, vp, sz, vp, sz, vp, vp, sz, vp, P(GridRegionInfo)],
+    "lio_grid_region_debug_stage_ms": [i32, pf],
+}
+CAPI = {name: sig if isinstance(sig, tuple) else (C.c_int, sig) for name, sig in CAPI.items()}     # -> (restype, argtypes), all of them
+EXPORTS = list(CAPI)
 _LIB = None
 
-# every symbol include/liogpu.h declares
-EXPORTS = [
-    "lio_version", "lio_s2m_default_config", "lio_last_error", "lio_s2m_create", "lio_s2m_destroy",
-    "lio_s2m_set_map", "lio_s2m_register", "lio_s2m_batch_upload", "lio_s2m_batch_set_poses",
-    "lio_s2m_batch_run", "lio_s2m_batch_sync", "lio_s2m_batch_results", "lio_s2m_set_degeneracy",
-    "lio_s2m_get_correspondences", "lio_s2m_get_profile", "lio_s2m_set_stream",
-    "lio_s2m_set_global_grid", "lio_s2m_set_shard", "lio_s2m_batch_begin",
-    "lio_s2m_batch_iter_partial", "lio_s2m_batch_iter_apply", "lio_s2m_batch_n_active",
-    "lio_transform_update", "lio_deskew_default_config", "lio_imu_deskew_info", "lio_deskew",
-    "lio_curvature", "lio_s2m_debug_stamps", "lio_s2m_batch_poll_active", "lio_voxel_grid", "lio_assemble_map", "lio_kf_store_create", "lio_kf_store_destroy", "lio_kf_store_add",
-    "lio_kf_store_count", "lio_kf_store_points", "lio_assemble_map_resident", "lio_s2m_set_scan_shard",
-    "lio_s2m_set_corner_map", "lio_s2m_batch_upload_corners", "lio_s2m_register_cs",
-    "lio_s2m_get_corner_correspondences", "lio_feature_default_config", "lio_extract_features",
-    "lio_range_image_default_config", "lio_range_image",
-    "lio_s2m_share_map", "lio_s2m_batch_upload_async", "lio_host_alloc", "lio_host_free", "lio_host_register",
-    "lio_host_unregister", "lio_s2m_set_shard_plan", "lio_s2m_register_pc2", "lio_deskew_pc2", "lio_kf_store_add_device", "lio_kf_store_add_from_handle",
-    "lio_s2m_register_raw", "lio_s2m_debug_persist_spin", "lio_device_alloc", "lio_device_free", "lio_device_upload",
-    "lio_nearby_default_config", "lio_kf_store_set_poses", "lio_assemble_map_nearby", "lio_debug_plane_fit",
-    "lio_icp_default_config", "lio_icp_align", "lio_kf_store_loop_icp", "lio_kf_store_detect_loop", "lio_icp_debug_trace", "lio_icp_debug_grid", "lio_sor_debug_grid",
-    "lio_sc_default_config", "lio_sc_make", "lio_sc_distance", "lio_kf_store_sc_add", "lio_kf_store_sc_add_device",
-    "lio_kf_store_sc_add_from_handle", "lio_kf_store_sc_count", "lio_kf_store_sc_geometry", "lio_kf_store_sc_get", "lio_kf_store_sc_detect",
-    "lio_sor_filter", "lio_local_map_default_config", "lio_kf_store_local_map",
-    "lio_height_map_default_config", "lio_height_map", "lio_kf_store_height_map",
-    "lio_terrain_default_config", "lio_terrain_layers", "lio_kf_store_terrain_map",
-    "lio_global_map_default_config", "lio_kf_store_global_map", "lio_kf_store_export_map", "lio_kf_store_get_keyframe",
-    "lio_s2m_registered_cloud",
-    "lio_radius_filter", "lio_ogm_default_config", "lio_occupancy_grid", "lio_kf_store_occupancy_grid", "lio_ogm_debug_stage_ms",
-    "lio_s2m_kernel_variant", "lio_s2m_launch_forms",
-    "lio_sdf_default_config", "lio_sdf_create", "lio_sdf_destroy", "lio_sdf_build", "lio_kf_store_sdf", "lio_sdf_nodes", "lio_sdf_query",
-    "lio_occupancy_sdf", "lio_sdf_debug_stage_ms", "lio_sdf_memory",
-    "lio_median_fill_default_config", "lio_median_fill", "lio_kf_store_planning_map",
-    "lio_grid_sample_default_config", "lio_grid_create", "lio_grid_destroy", "lio_grid_set_layers", "lio_grid_get_layer", "lio_grid_info",
-    "lio_grid_memory", "lio_grid_sample", "lio_kf_store_planning_grid", "lio_grid_debug_stage_ms",
-    "lio_grid_region_default_config", "lio_grid_region_reduce", "lio_grid_region_cells", "lio_grid_region_debug_stage_ms",
-    "lio_debug_fast_f32_ops", "lio_debug_threshold_f32", "lio_debug_grid_plan", "lio_debug_gn_step", "lio_debug_corner_fit",
-    "lio_s2m_debug_scan_order", "lio_debug_scan_tile_plan",
-]
+
+def _bind(L):
+    """Gives every symbol of CAPI its types on the library L.  One that L lacks is skipped (A/B runs load older builds through
+    LIOGPU_LIB); calling it later raises ctypes' own AttributeError."""
+    for name, (restype, argtypes) in CAPI.items():
+        fn = getattr(L, name, None)
+        if fn is not None:
+            fn.restype, fn.argtypes = restype, argtypes
+    return L
 
 
 def load_library():
     """Loads lio-slam_amd/libliogpu.so; raises LioError when it is missing (no fallback)."""
     global _LIB
-    if _LIB is not None:
-        return _LIB
-    p = lib_path()
-    if not os.path.exists(p):
-        raise LioError(f"{p} is missing: run __graft_entry__.build() (hipcc --offload-arch=gfx950). "
-                       "There is no CPU fallback.")
-    L = C.CDLL(p)
-    vp, i32, f32, f64, sz = C.c_void_p, C.c_int32, C.c_float, C.c_double, C.c_size_t
-    L.lio_version.restype = C.c_int
-    L.lio_last_error.restype = C.c_char_p
-    L.lio_s2m_default_config.argtypes = [C.POINTER(S2MConfig)]
-    L.lio_s2m_default_config.restype = None
-    L.lio_s2m_create.argtypes = [C.POINTER(S2MConfig), C.POINTER(vp)]
-    L.lio_s2m_destroy.argtypes = [vp]
-    L.lio_s2m_destroy.restype = None
-    L.lio_s2m_set_map.argtypes = [vp, vp, sz, sz]
-    L.lio_s2m_register.argtypes = [vp, vp, sz, sz, C.POINTER(f32), C.POINTER(S2MResult)]
-    L.lio_s2m_register_pc2.argtypes = [vp, vp, sz, C.POINTER(PC2Layout), C.POINTER(f32), C.POINTER(S2MResult)]
-    L.lio_s2m_register_raw.argtypes = [vp, vp, sz, C.POINTER(PC2Layout), f32, C.POINTER(f32), C.POINTER(S2MResult), vp, sz, C.POINTER(sz)]
-    L.lio_s2m_debug_persist_spin.argtypes = [vp, i32, i32]
-    L.lio_s2m_batch_upload.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz), sz]
-    L.lio_s2m_batch_upload_async.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz), sz]
-    L.lio_s2m_share_map.argtypes = [vp, vp]
-    L.lio_host_alloc.argtypes = [sz]
-    L.lio_host_alloc.restype = vp
-    L.lio_host_free.argtypes = [vp]
-    L.lio_host_free.restype = None
-    L.lio_device_alloc.argtypes = [i32, sz]
-    L.lio_device_alloc.restype = vp
-    L.lio_device_free.argtypes = [i32, vp]
-    L.lio_device_free.restype = None
-    L.lio_device_upload.argtypes = [i32, vp, vp, sz]
-    L.lio_host_register.argtypes = [vp, sz]
-    L.lio_host_unregister.argtypes = [vp]
-    L.lio_s2m_batch_set_poses.argtypes = [vp, C.POINTER(f32)]
-    L.lio_s2m_batch_run.argtypes = [vp]
-    L.lio_s2m_batch_sync.argtypes = [vp]
-    L.lio_s2m_batch_results.argtypes = [vp, C.POINTER(f32), C.POINTER(S2MResult)]
-    L.lio_s2m_set_degeneracy.argtypes = [vp, i32, C.POINTER(f32), i32]
-    L.lio_s2m_get_correspondences.argtypes = [vp, i32, vp, vp, vp]
-    L.lio_s2m_get_profile.argtypes = [vp, C.POINTER(S2MProfile)]
-    L.lio_s2m_kernel_variant.argtypes = [vp]
-    if hasattr(L, "lio_s2m_launch_forms"):             # (A/B runs load older builds through LIOGPU_LIB)
-        L.lio_s2m_launch_forms.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
-    L.lio_s2m_set_corner_map.argtypes = [vp, vp, sz, sz]
-    L.lio_s2m_batch_upload_corners.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz), sz]
-    L.lio_s2m_register_cs.argtypes = [vp, vp, sz, vp, sz, sz, C.POINTER(f32), C.POINTER(S2MResult)]
-    L.lio_s2m_get_corner_correspondences.argtypes = [vp, i32, vp, vp, vp]
-    L.lio_s2m_set_stream.argtypes = [vp, vp]
-    L.lio_s2m_set_global_grid.argtypes = [vp, C.POINTER(f32), C.POINTER(i32)]
-    L.lio_s2m_set_shard.argtypes = [vp, i32, i32, i32]
-    L.lio_s2m_set_scan_shard.argtypes = [vp, i32, i32]
-    L.lio_s2m_set_shard_plan.argtypes = [vp, i32, i32, i32, C.POINTER(i32), i32]
-    L.lio_s2m_batch_begin.argtypes = [vp]
-    L.lio_s2m_batch_iter_partial.argtypes = [vp, vp]
-    L.lio_s2m_batch_iter_apply.argtypes = [vp, vp]
-    L.lio_s2m_batch_n_active.argtypes = [vp, C.POINTER(i32)]
-    L.lio_s2m_batch_poll_active.argtypes = [vp, i32, C.POINTER(i32)]
-    L.lio_transform_update.argtypes = [C.POINTER(f32), i32, i32, f32, f32, f32, f32, f32]
-    L.lio_transform_update.restype = None
-    L.lio_deskew_default_config.argtypes = [C.POINTER(DeskewConfig)]
-    L.lio_deskew_default_config.restype = None
-    dp = C.POINTER(f64)
-    L.lio_imu_deskew_info.argtypes = [dp, dp, dp, dp, i32, f64, f64, dp, dp, dp, dp]
-    L.lio_deskew.argtypes = [C.POINTER(DeskewConfig), vp, sz, sz, f64, dp, dp, dp, dp, i32, vp, sz,
-                             C.POINTER(sz)]
-    L.lio_deskew_pc2.argtypes = [C.POINTER(DeskewConfig), vp, sz, C.POINTER(PC2Layout), f64, dp, dp, dp, dp, i32, vp, sz,
-                                 C.POINTER(sz)]
-    L.lio_curvature.argtypes = [i32, vp, sz, vp, vp, vp]
-    L.lio_range_image_default_config.argtypes = [C.POINTER(RangeImageConfig)]
-    L.lio_range_image_default_config.restype = None
-    L.lio_range_image.argtypes = [C.POINTER(RangeImageConfig), vp, sz, sz, f64, dp, dp, dp, dp, i32, vp, sz, C.POINTER(sz),
-                                  vp, vp, vp, vp]
-    L.lio_feature_default_config.argtypes = [C.POINTER(FeatureConfig)]
-    L.lio_feature_default_config.restype = None
-    L.lio_extract_features.argtypes = [C.POINTER(FeatureConfig), vp, sz, sz, vp, vp, vp, vp, vp, C.POINTER(sz), vp,
-                                       C.POINTER(sz), sz, vp, vp, vp]
-    L.lio_s2m_debug_stamps.argtypes = [vp, vp, sz]
-    if hasattr(L, "lio_s2m_debug_scan_order"):         # (A/B runs load older builds through LIOGPU_LIB)
-        L.lio_s2m_debug_scan_order.argtypes = [vp, vp, vp, sz, C.POINTER(i32)]
-        L.lio_debug_scan_tile_plan.argtypes = [C.POINTER(f32), C.POINTER(f32), f32, i32, C.POINTER(i32), C.POINTER(f32)]
-    L.lio_voxel_grid.argtypes = [i32, vp, sz, sz, f32, vp, sz, C.POINTER(sz)]
-    L.lio_kf_store_create.argtypes = [i32, C.POINTER(vp)]
-    L.lio_kf_store_destroy.argtypes = [vp]
-    L.lio_kf_store_destroy.restype = None
-    L.lio_kf_store_add.argtypes = [vp, vp, sz, sz, C.POINTER(i32)]
-    L.lio_kf_store_count.argtypes = [vp]
-    L.lio_kf_store_points.argtypes = [vp, C.c_int32]
-    L.lio_kf_store_points.restype = C.c_size_t
-    L.lio_kf_store_add_device.argtypes = [vp, vp, sz, sz, C.POINTER(i32)]
-    L.lio_kf_store_add_from_handle.argtypes = [vp, vp, i32, C.POINTER(i32)]
-    L.lio_assemble_map_resident.argtypes = [vp, vp, i32, C.POINTER(i32), C.POINTER(f32), f32, vp, sz, C.POINTER(sz)]
-    L.lio_assemble_map.argtypes = [vp, i32, i32, C.POINTER(vp), C.POINTER(sz), sz, C.POINTER(f32), f32, vp, sz,
-                                   C.POINTER(sz)]
-    L.lio_nearby_default_config.argtypes = [C.POINTER(NearbyConfig)]
-    L.lio_nearby_default_config.restype = None
-    L.lio_kf_store_set_poses.argtypes = [vp, i32, i32, C.POINTER(f32), C.POINTER(f64)]
-    L.lio_assemble_map_nearby.argtypes = [vp, vp, C.POINTER(NearbyConfig), f64, f32, C.POINTER(i32), i32, C.POINTER(i32), vp, sz, sz,
-                                          C.POINTER(sz)]
-    L.lio_icp_default_config.argtypes = [C.POINTER(IcpConfig)]
-    L.lio_icp_default_config.restype = None
-    L.lio_icp_align.argtypes = [i32, vp, sz, sz, vp, sz, sz, C.POINTER(IcpConfig), C.POINTER(f32), C.POINTER(IcpResult)]
-    L.lio_kf_store_loop_icp.argtypes = [vp, i32, i32, i32, i32, f32, C.POINTER(IcpConfig), C.POINTER(IcpResult), C.POINTER(IcpClouds)]
-    L.lio_kf_store_detect_loop.argtypes = [vp, f32, f64, f64, C.POINTER(i32), C.POINTER(i32)]
-    L.lio_icp_debug_trace.argtypes = [i32, vp, sz, sz, vp, sz, sz, C.POINTER(IcpConfig), C.POINTER(f32), i32, C.POINTER(IcpResult),
-                                      vp, vp, vp, vp, C.POINTER(i32)]
-    scp = C.POINTER(ScConfig)
-    L.lio_sc_default_config.argtypes = [scp]
-    L.lio_sc_default_config.restype = None
-    L.lio_sc_make.argtypes = [i32, vp, sz, sz, scp, vp, vp, vp]
-    L.lio_sc_distance.argtypes = [i32, vp, vp, scp, C.POINTER(f64), C.POINTER(i32)]
-    L.lio_kf_store_sc_add.argtypes = [vp, vp, sz, sz, scp, C.POINTER(i32)]
-    L.lio_kf_store_sc_add_device.argtypes = [vp, vp, sz, sz, scp, C.POINTER(i32)]
-    L.lio_kf_store_sc_add_from_handle.argtypes = [vp, vp, scp, C.POINTER(i32)]
-    L.lio_kf_store_sc_count.argtypes = [vp]
-    L.lio_kf_store_sc_geometry.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
-    L.lio_kf_store_sc_get.argtypes = [vp, i32, vp, vp, vp]
-    L.lio_kf_store_sc_detect.argtypes = [vp, scp, C.POINTER(ScResult)]
-    L.lio_sor_filter.argtypes = [i32, vp, sz, sz, i32, f32, vp, sz, C.POINTER(sz), vp, C.POINTER(f64)]
-    L.lio_local_map_default_config.argtypes = [C.POINTER(LocalMapConfig)]
-    L.lio_local_map_default_config.restype = None
-    L.lio_kf_store_local_map.argtypes = [vp, C.POINTER(LocalMapConfig), C.POINTER(f32), vp, sz, sz, C.POINTER(sz), C.POINTER(LocalMapInfo)]
-    L.lio_height_map_default_config.argtypes = [C.POINTER(HeightMapConfig)]
-    L.lio_height_map_default_config.restype = None
-    L.lio_height_map.argtypes = [i32, vp, sz, sz, C.POINTER(HeightMapConfig), vp, sz, C.POINTER(HeightMapInfo)]
-    L.lio_kf_store_height_map.argtypes = [vp, C.POINTER(LocalMapConfig), C.POINTER(f32), C.POINTER(HeightMapConfig), vp, sz,
-                                          C.POINTER(LocalMapInfo), C.POINTER(HeightMapInfo)]
-    L.lio_terrain_default_config.argtypes = [C.POINTER(TerrainConfig)]
-    L.lio_terrain_default_config.restype = None
-    L.lio_terrain_layers.argtypes = [i32, vp, i32, i32, f64, C.POINTER(f64), C.POINTER(f64), C.POINTER(TerrainConfig), vp, sz,
-                                     C.POINTER(TerrainInfo)]
-    L.lio_kf_store_terrain_map.argtypes = [vp, C.POINTER(LocalMapConfig), C.POINTER(f32), C.POINTER(HeightMapConfig), C.POINTER(TerrainConfig),
-                                           vp, sz, vp, sz, C.POINTER(LocalMapInfo), C.POINTER(HeightMapInfo), C.POINTER(TerrainInfo)]
-    L.lio_global_map_default_config.argtypes = [C.POINTER(GlobalMapConfig)]
-    L.lio_global_map_default_config.restype = None
-    L.lio_kf_store_global_map.argtypes = [vp, C.POINTER(GlobalMapConfig), C.POINTER(i32), i32, C.POINTER(i32), vp, sz, sz, C.POINTER(sz),
-                                          C.POINTER(GlobalMapInfo)]
-    L.lio_kf_store_export_map.argtypes = [vp, C.POINTER(ExportConfig), vp, sz, sz, C.POINTER(sz), vp, sz, sz, C.POINTER(sz), C.POINTER(i32)]
-    L.lio_kf_store_get_keyframe.argtypes = [vp, i32, C.POINTER(f32), vp, sz, sz, C.POINTER(sz)]
-    L.lio_s2m_registered_cloud.argtypes = [vp, i32, C.POINTER(f32), vp, sz, sz, C.POINTER(sz)]
-    L.lio_radius_filter.argtypes = [i32, vp, sz, sz, f32, i32, vp, sz, C.POINTER(sz), vp]
-    L.lio_ogm_default_config.argtypes = [C.POINTER(OgmConfig)]
-    L.lio_ogm_default_config.restype = None
-    L.lio_occupancy_grid.argtypes = [i32, vp, sz, sz, C.POINTER(OgmConfig), vp, sz, C.POINTER(OgmInfo)]
-    L.lio_kf_store_occupancy_grid.argtypes = [vp, f32, C.POINTER(OgmConfig), vp, sz, C.POINTER(sz), C.POINTER(OgmInfo)]
-    L.lio_ogm_debug_stage_ms.argtypes = [i32, C.POINTER(f32)]
-    L.lio_sdf_default_config.argtypes = [C.POINTER(SdfConfig)]
-    L.lio_sdf_default_config.restype = None
-    L.lio_sdf_create.argtypes = [i32, C.POINTER(vp)]
-    L.lio_sdf_destroy.argtypes = [vp]
-    L.lio_sdf_destroy.restype = None
-    L.lio_sdf_build.argtypes = [vp, vp, i32, i32, f64, C.POINTER(f64), C.POINTER(f64), C.POINTER(SdfConfig), C.POINTER(SdfInfo)]
-    L.lio_kf_store_sdf.argtypes = [vp, C.POINTER(LocalMapConfig), C.POINTER(f32), C.POINTER(HeightMapConfig), C.POINTER(SdfConfig), vp, sz, vp,
-                                   C.POINTER(LocalMapInfo), C.POINTER(HeightMapInfo), C.POINTER(SdfInfo)]
-    L.lio_sdf_nodes.argtypes = [vp, vp, sz]
-    L.lio_sdf_query.argtypes = [vp, vp, sz, vp, vp]
-    L.lio_occupancy_sdf.argtypes = [i32, vp, i32, i32, f32, i32, vp]
-    L.lio_sdf_debug_stage_ms.argtypes = [i32, C.POINTER(f32)]
-    L.lio_sdf_memory.argtypes = [vp, C.POINTER(sz), C.POINTER(sz)]
-    L.lio_median_fill_default_config.argtypes = [C.POINTER(MedianFillConfig)]
-    L.lio_median_fill_default_config.restype = None
-    L.lio_median_fill.argtypes = [i32, vp, i32, i32, f64, C.POINTER(MedianFillConfig), vp, vp, vp, vp, C.POINTER(MedianFillInfo)]
-    L.lio_kf_store_planning_map.argtypes = [vp, C.POINTER(LocalMapConfig), C.POINTER(f32), C.POINTER(HeightMapConfig), C.POINTER(MedianFillConfig),
-                                            C.POINTER(TerrainConfig), vp, C.POINTER(SdfConfig), C.POINTER(PlanningMapBuffers),
-                                            C.POINTER(LocalMapInfo), C.POINTER(HeightMapInfo), C.POINTER(MedianFillInfo), C.POINTER(TerrainInfo),
-                                            C.POINTER(SdfInfo)]
-    L.lio_grid_sample_default_config.argtypes = [C.POINTER(GridSampleConfig)]
-    L.lio_grid_sample_default_config.restype = None
-    L.lio_grid_create.argtypes = [i32, C.POINTER(vp)]
-    L.lio_grid_destroy.argtypes = [vp]
-    L.lio_grid_destroy.restype = None
-    L.lio_grid_set_layers.argtypes = [vp, vp, i32, i32, i32, f64, C.POINTER(f64), C.POINTER(f64)]
-    L.lio_grid_get_layer.argtypes = [vp, i32, vp, sz]
-    L.lio_grid_info.argtypes = [vp, C.POINTER(GridInfo)]
-    L.lio_grid_memory.argtypes = [vp, C.POINTER(sz)]
-    L.lio_grid_sample.argtypes = [vp, C.POINTER(i32), i32, C.POINTER(GridSampleConfig), vp, sz, vp, vp, C.POINTER(GridSampleInfo)]
-    L.lio_kf_store_planning_grid.argtypes = L.lio_kf_store_planning_map.argtypes + [vp]
-    L.lio_grid_debug_stage_ms.argtypes = [i32, C.POINTER(f32)]
-    L.lio_grid_region_default_config.argtypes = [C.POINTER(GridRegionConfig)]
-    L.lio_grid_region_default_config.restype = None
-    L.lio_grid_region_reduce.argtypes = [vp, C.POINTER(i32), i32, C.POINTER(GridRegionConfig), vp, sz, vp, sz, vp, vp, vp, C.POINTER(GridRegionInfo)]
-    L.lio_grid_region_cells.argtypes = [vp, vp, sz, vp, sz, vp, vp, sz, vp, C.POINTER(GridRegionInfo)]
-    L.lio_grid_region_debug_stage_ms.argtypes = [i32, C.POINTER(f32)]
-    _LIB = L
-    return L
+    if _LIB is None:
+        p = lib_path()
+        if not os.path.exists(p):
+            raise LioError(f"{p} is missing: run __graft_entry__.build() (hipcc --offload-arch=gfx950). "
+                           "There is no CPU fallback.")
+        _LIB = _bind(C.CDLL(p))
+    return _LIB
 
 
 def _check(rc, what):
@@ -562,36 +506,59 @@ def _as_points(a):
     return a, a.shape[1] * 4
 
 
-class ScanToMap:
-    """Device-resident replacement of mapOptimization's scan-to-map block (MO:1839-1865)."""
+def _default_config(struct_cls, entry_name, overrides, convert=None):
+    """A struct_cls as the library's entry_name fills it, then the overrides: a key that is no field raises AttributeError,
+    convert = {field: function} turns that field's value into what the struct takes."""
+    cfg = struct_cls()
+    getattr(load_library(), entry_name)(C.byref(cfg))
+    for k, v in overrides.items():
+        if not hasattr(cfg, k):
+            raise AttributeError(k)
+        setattr(cfg, k, convert[k](v) if convert and k in convert else v)
+    return cfg
 
-    def __init__(self, **cfg_overrides):
-        self.lib = load_library()
-        self.cfg = S2MConfig()
-        self.lib.lio_s2m_default_config(C.byref(self.cfg))
-        for k, v in cfg_overrides.items():
-            if not hasattr(self.cfg, k):
-                raise AttributeError(k)
-            if k == "device_ids":
-                for i, d in enumerate(v):
-                    self.cfg.device_ids[i] = int(d)
-                continue
-            setattr(self.cfg, k, v)
-        self.h = C.c_void_p()
-        _check(self.lib.lio_s2m_create(C.byref(self.cfg), C.byref(self.h)), "lio_s2m_create")
-        self._n_scans = 0
-        self._npts = []
+
+def s2m_config(**overrides):
+    """The scan-to-map configuration: the library's defaults, then the overrides; device_ids sets the leading elements."""
+    ids = overrides.pop("device_ids", ())
+    cfg = _default_config(S2MConfig, "lio_s2m_default_config", overrides)
+    for i, d in enumerate(ids):
+        cfg.device_ids[i] = int(d)
+    return cfg
+
+
+class _Owner:
+    """close() and __del__ of an object that owns one resource of the library, under the attribute `_owned` names: a handle
+    (c_void_p) or an address (int).  A subclass supplies _release().  It runs once: not again on a second close(), and not at
+    all when __init__ raised before the resource existed.  close() leaves the attribute empty (c_void_p() or 0)."""
+    _owned = "h"
 
     def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            self.lib.lio_s2m_destroy(self.h)
-            self.h = C.c_void_p()
+        r = getattr(self, self._owned, None)
+        if r:
+            self._release()
+            setattr(self, self._owned, type(r)())
 
     def __del__(self):
         try:
             self.close()
         except Exception:
             pass
+
+
+class ScanToMap(_Owner):
+    """Device-resident replacement of mapOptimization's scan-to-map block (MO:1839-1865)."""
+
+    def __init__(self, **cfg_overrides):
+        self.lib = load_library()
+        self.cfg = s2m_config(**cfg_overrides)
+        self.h = C.c_void_p()
+        _check(self.lib.lio_s2m_create(C.byref(self.cfg), C.byref(self.h)), "lio_s2m_create")
+        self._n_scans = 0
+        self._npts = []
+
+    def _release(self):
+        self.lib.lio_s2m_destroy(self.h)
 
     # kdtreeSurfFromMap->setInputCloud(laserCloudSurfFromMapDS), MO:1846
     def set_map(self, map_pts):
@@ -820,8 +787,9 @@ class ScanToMap:
         return v.value
 
 
-class DeviceBuffer:
+class DeviceBuffer(_Owner):
     """hipMalloc'ed bytes on `device_id` holding a copy of a numpy array (a cloud that already lives in HBM)."""
+    _owned = "ptr"
 
     def __init__(self, array, device_id=0):
         self.lib = load_library()
@@ -833,20 +801,13 @@ class DeviceBuffer:
             raise LioError("lio_device_alloc failed")
         _check(self.lib.lio_device_upload(self.device_id, self.ptr, a.ctypes.data, self.nbytes), "lio_device_upload")
 
-    def close(self):
-        if getattr(self, "ptr", None):
-            self.lib.lio_device_free(self.device_id, self.ptr)
-            self.ptr = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _release(self):
+        self.lib.lio_device_free(self.device_id, self.ptr)
 
 
-class PinnedBuffer:
+class PinnedBuffer(_Owner):
     """hipHostMalloc'ed bytes as a numpy array (true-DMA source for batch_upload_raw)."""
+    _owned = "ptr"
 
     def __init__(self, nbytes):
         self.lib = load_library()
@@ -856,17 +817,9 @@ class PinnedBuffer:
             raise LioError("lio_host_alloc failed")
         self.array = np.ctypeslib.as_array((C.c_uint8 * self.nbytes).from_address(self.ptr))
 
-    def close(self):
-        if getattr(self, "ptr", None):
-            self.array = None
-            self.lib.lio_host_free(self.ptr)
-            self.ptr = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _release(self):
+        self.array = None                  # the view goes before the bytes under it
+        self.lib.lio_host_free(self.ptr)
 
 
 # transformUpdate, MO:1867-1907
@@ -947,12 +900,8 @@ def deskew_pc2(dcfg, blob, n_points, layout, t_cur, imu):
     return np.concatenate([o[:, :3], o[:, 4:5]], axis=1).copy()
 
 
-def deskew_default_config(**kw):
-    c = DeskewConfig()
-    load_library().lio_deskew_default_config(C.byref(c))
-    for k, v in kw.items():
-        setattr(c, k, v)
-    return c
+def deskew_default_config(**overrides):
+    return _default_config(DeskewConfig, "lio_deskew_default_config", overrides)
 
 
 # calculateSmoothness, FE:81-101
@@ -971,9 +920,7 @@ def curvature(rng, device_id=0):
 def debug_plane_fit(sets, plane_tol=0.2, device_id=0):
     a = np.ascontiguousarray(sets, np.float32).reshape(-1, 15)
     out = np.zeros((len(a), 8), np.uint32)
-    fn = load_library().lio_debug_plane_fit        # bound on first use: A/B runs load older builds through LIOGPU_LIB
-    fn.argtypes = [C.c_int32, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p]
-    _check(fn(device_id, a.ctypes.data, len(a), float(plane_tol), out.ctypes.data), "lio_debug_plane_fit")
+    _check(load_library().lio_debug_plane_fit(device_id, a.ctypes.data, len(a), float(plane_tol), out.ctypes.data), "lio_debug_plane_fit")
     return out
 
 
@@ -1001,16 +948,7 @@ assert DEBUG_GN_RECORD_DTYPE.itemsize == C.sizeof(DebugGnRecord) == 436
 # Returns a structured array of DEBUG_GN_RECORD_DTYPE.  Non-finite sums or poses are refused (include/liogpu.h)
 def debug_gn_step(sums, pose, it, is_degenerate, matP, deg_override=-1, skip_eigen=False, hold_if_done=False, device_id=0,
                   **cfg_overrides):
-    L = load_library()
-    fn = L.lio_debug_gn_step                       # bound on first use: A/B runs load older builds through LIOGPU_LIB
-    fn.argtypes = [C.c_int32, C.POINTER(S2MConfig), C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                   C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
-    cfg = S2MConfig()
-    L.lio_s2m_default_config(C.byref(cfg))
-    for k, v in cfg_overrides.items():
-        if not hasattr(cfg, k):
-            raise AttributeError(k)
-        setattr(cfg, k, v)
+    cfg = s2m_config(**cfg_overrides)
     sums = np.ascontiguousarray(sums, np.float64).reshape(-1, 28)
     n = len(sums)
     pose = np.ascontiguousarray(pose, np.float32).reshape(n, 6)
@@ -1018,9 +956,9 @@ def debug_gn_step(sums, pose, it, is_degenerate, matP, deg_override=-1, skip_eig
     deg = np.ascontiguousarray(is_degenerate, np.int32).reshape(n)
     matP = np.ascontiguousarray(matP, np.float32).reshape(n, 36)
     out = np.zeros(n, DEBUG_GN_RECORD_DTYPE)
-    _check(fn(device_id, C.byref(cfg) if cfg_overrides else None, n, sums.ctypes.data, pose.ctypes.data, it.ctypes.data,
-              deg.ctypes.data, matP.ctypes.data, int(deg_override), 1 if skip_eigen else 0, 1 if hold_if_done else 0,
-              out.ctypes.data), "lio_debug_gn_step")
+    _check(load_library().lio_debug_gn_step(device_id, C.byref(cfg) if cfg_overrides else None, n, sums.ctypes.data, pose.ctypes.data,
+                                            it.ctypes.data, deg.ctypes.data, matP.ctypes.data, int(deg_override), 1 if skip_eigen else 0,
+                                            1 if hold_if_done else 0, out.ctypes.data), "lio_debug_gn_step")
     return out
 
 
@@ -1030,9 +968,8 @@ def debug_corner_fit(sets, pts, weight=0.9, min_s=0.1, device_id=0):
     a = np.ascontiguousarray(sets, np.float32).reshape(-1, 15)
     q = np.ascontiguousarray(pts, np.float32).reshape(len(a), 3)
     out = np.zeros((len(a), 5), np.uint32)
-    fn = load_library().lio_debug_corner_fit
-    fn.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_double, C.c_void_p]
-    _check(fn(device_id, a.ctypes.data, q.ctypes.data, len(a), float(weight), float(min_s), out.ctypes.data), "lio_debug_corner_fit")
+    _check(load_library().lio_debug_corner_fit(device_id, a.ctypes.data, q.ctypes.data, len(a), float(weight), float(min_s), out.ctypes.data),
+           "lio_debug_corner_fit")
     return out
 
 
@@ -1040,9 +977,6 @@ def debug_corner_fit(sets, pts, weight=0.9, min_s=0.1, device_id=0):
 # `patterns` (array) or first .. first + count; raw: the fast sequence without its guard.  Returns (number of differing results,
 # up to eight differing patterns, result bits or None) (include/liogpu.h)
 def debug_fast_f32_ops(op, raw=False, patterns=None, first=0, count=0, want_values=False, device_id=0):
-    fn = load_library().lio_debug_fast_f32_ops
-    fn.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
-                   C.POINTER(C.c_uint64), C.c_void_p, C.POINTER(C.c_int32)]
     pat = None
     if patterns is not None:
         pat = np.ascontiguousarray(patterns, np.uint32)
@@ -1050,36 +984,26 @@ def debug_fast_f32_ops(op, raw=False, patterns=None, first=0, count=0, want_valu
     vals = np.zeros(count, np.uint32) if want_values else None
     n_diff, n_first = C.c_uint64(0), C.c_int32(0)
     firsts = np.zeros(8, np.uint32)
-    _check(fn(device_id, int(op), 1 if raw else 0, pat.ctypes.data if pat is not None else None, int(first), int(count),
-              vals.ctypes.data if vals is not None else None, C.byref(n_diff), firsts.ctypes.data, C.byref(n_first)),
-           "lio_debug_fast_f32_ops")
+    _check(load_library().lio_debug_fast_f32_ops(device_id, int(op), 1 if raw else 0, pat.ctypes.data if pat is not None else None, int(first),
+                                                 int(count), vals.ctypes.data if vals is not None else None, C.byref(n_diff),
+                                                 firsts.ctypes.data, C.byref(n_first)), "lio_debug_fast_f32_ops")
     return int(n_diff.value), firsts[:n_first.value].copy(), vals
 
 
 # test hook (host only): the largest float32 not above the double t, as the library converts plane_tol and min_s
 def debug_threshold_f32(t):
-    fn = load_library().lio_debug_threshold_f32
-    fn.argtypes = [C.c_double]
-    fn.restype = C.c_float
-    return np.float32(fn(float(t)))
+    return np.float32(load_library().lio_debug_threshold_f32(float(t)))
 
 
 # test hook (host only): the search grid set_map would lay out over n map points in the box [mn, mx] under ScanToMap settings
 # `cfg_overrides` (and LIO_X_SUB / LIO_TIGHT / LIO_TRY in the environment); occupied = grid cells holding a point (negative:
 # not counted), caller_box: the box came from the caller, as for a map assembled on the device (include/liogpu.h)
 def debug_grid_plan(mn, mx, n, occupied=-1, caller_box=False, **cfg_overrides):
-    L = load_library()
-    fn = L.lio_debug_grid_plan
-    fn.argtypes = [C.POINTER(S2MConfig), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t, C.c_int32, C.c_int32, C.POINTER(GridPlanInfo)]
-    cfg = S2MConfig()
-    L.lio_s2m_default_config(C.byref(cfg))
-    for k, v in cfg_overrides.items():
-        if not hasattr(cfg, k):
-            raise AttributeError(k)
-        setattr(cfg, k, v)
+    cfg = s2m_config(**cfg_overrides)
     lo, hi = np.ascontiguousarray(mn, np.float32).reshape(3), np.ascontiguousarray(mx, np.float32).reshape(3)
     out = GridPlanInfo()
-    _check(fn(C.byref(cfg), _f32p(lo), _f32p(hi), int(n), int(occupied), 1 if caller_box else 0, C.byref(out)), "lio_debug_grid_plan")
+    _check(load_library().lio_debug_grid_plan(C.byref(cfg), _f32p(lo), _f32p(hi), int(n), int(occupied), 1 if caller_box else 0, C.byref(out)),
+           "lio_debug_grid_plan")
     return out
 
 
@@ -1097,13 +1021,7 @@ def debug_scan_tile_plan(mn, mx, tile, shard_axis=-1):
 def range_image(records, t_cur, imu, device_id=0, **cfg_overrides):
     """PointXYZIRT records -> dict(cloud [n,4], start_ring, end_ring, col, range) like synth.organize_scan."""
     L = load_library()
-    cfg = RangeImageConfig()
-    L.lio_range_image_default_config(C.byref(cfg))
-    cfg.device_id = device_id
-    for k, v in cfg_overrides.items():
-        if not hasattr(cfg, k):
-            raise AttributeError(k)
-        setattr(cfg, k, v)
+    cfg = _default_config(RangeImageConfig, "lio_range_image_default_config", {"device_id": device_id, **cfg_overrides})
     cur, T, RX, RY, RZ = imu
     rec = np.ascontiguousarray(records)
     cells = int(cfg.N_SCAN) * int(cfg.Horizon_SCAN)
@@ -1125,14 +1043,7 @@ def range_image(records, t_cur, imu, device_id=0, **cfg_overrides):
 def extract_features(cloud_xyzi, start_ring, end_ring, point_col, point_range, device_id=0, **cfg_overrides):
     """cloud_xyzi [n,4] -> dict(corner [n_c,4], surface [n_s,4], curvature, picked, label)."""
     L = load_library()
-    cfg = FeatureConfig()
-    L.lio_feature_default_config(C.byref(cfg))
-    cfg.N_SCAN = len(start_ring)
-    cfg.device_id = device_id
-    for k, v in cfg_overrides.items():
-        if not hasattr(cfg, k):
-            raise AttributeError(k)
-        setattr(cfg, k, v)
+    cfg = _default_config(FeatureConfig, "lio_feature_default_config", {"N_SCAN": len(start_ring), "device_id": device_id, **cfg_overrides})
     rec = _as_xyzi_records(np.asarray(cloud_xyzi, np.float32).reshape(-1, 4))
     n = len(rec)
     sr = np.ascontiguousarray(start_ring, np.int32)
@@ -1178,23 +1089,11 @@ def voxel_grid(xyzi, leaf, device_id=0):
 
 
 def nearby_default_config(**overrides):
-    cfg = NearbyConfig()
-    load_library().lio_nearby_default_config(C.byref(cfg))
-    for k, v in overrides.items():
-        if not hasattr(cfg, k):
-            raise AttributeError(k)
-        setattr(cfg, k, v)
-    return cfg
+    return _default_config(NearbyConfig, "lio_nearby_default_config", overrides)
 
 
 def icp_default_config(**overrides):
-    cfg = IcpConfig()
-    load_library().lio_icp_default_config(C.byref(cfg))
-    for k, v in overrides.items():
-        if not hasattr(cfg, k):
-            raise AttributeError(k)
-        setattr(cfg, k, v)
-    return cfg
+    return _default_config(IcpConfig, "lio_icp_default_config", overrides)
 
 
 def _guess_ptr(guess):
@@ -1240,20 +1139,12 @@ def icp_debug_grid(target, device_id=0):
     """Test hook, read-only -> IcpGridInfo: the grid lio_icp_align lays over `target`, by the alignment's own code."""
     tgt, ts = _as_points(target)
     out = IcpGridInfo()
-    fn = load_library().lio_icp_debug_grid         # bound on first use: A/B runs load older builds through LIOGPU_LIB
-    fn.argtypes = [C.c_int32, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(IcpGridInfo)]
-    _check(fn(device_id, tgt.ctypes.data, len(tgt), ts, C.byref(out)), "lio_icp_debug_grid")
+    _check(load_library().lio_icp_debug_grid(device_id, tgt.ctypes.data, len(tgt), ts, C.byref(out)), "lio_icp_debug_grid")
     return out
 
 
 def sc_default_config(**overrides):
-    cfg = ScConfig()
-    load_library().lio_sc_default_config(C.byref(cfg))
-    for k, v in overrides.items():
-        if not hasattr(cfg, k):
-            raise AttributeError(k)
-        setattr(cfg, k, v)
-    return cfg
+    return _default_config(ScConfig, "lio_sc_default_config", overrides)
 
 
 # scManager.makeAndSaveScancontextAndKeys without the store, SC:236-246
@@ -1297,30 +1188,16 @@ def sor_debug_grid(xyz, mean_k=10, device_id=0):
     """Test hook, read-only -> IcpGridInfo: the grid lio_sor_filter lays over the cloud at `mean_k`, by the filter's own code."""
     pts, stride = _as_points(xyz)
     out = IcpGridInfo()
-    fn = load_library().lio_sor_debug_grid         # bound on first use: A/B runs load older builds through LIOGPU_LIB
-    fn.argtypes = [C.c_int32, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int32, C.POINTER(IcpGridInfo)]
-    _check(fn(device_id, pts.ctypes.data, len(pts), stride, int(mean_k), C.byref(out)), "lio_sor_debug_grid")
+    _check(load_library().lio_sor_debug_grid(device_id, pts.ctypes.data, len(pts), stride, int(mean_k), C.byref(out)), "lio_sor_debug_grid")
     return out
 
 
 def local_map_default_config(**overrides):
-    cfg = LocalMapConfig()
-    load_library().lio_local_map_default_config(C.byref(cfg))
-    for k, v in overrides.items():
-        if not hasattr(cfg, k):
-            raise AttributeError(k)
-        setattr(cfg, k, v)
-    return cfg
+    return _default_config(LocalMapConfig, "lio_local_map_default_config", overrides)
 
 
 def global_map_default_config(**overrides):
-    cfg = GlobalMapConfig()
-    load_library().lio_global_map_default_config(C.byref(cfg))
-    for k, v in overrides.items():
-        if not hasattr(cfg, k):
-            raise AttributeError(k)
-        setattr(cfg, k, v)
-    return cfg
+    return _default_config(GlobalMapConfig, "lio_global_map_default_config", overrides)
 
 
 def _from_records_stride(buf, n, stride):
@@ -1330,13 +1207,7 @@ def _from_records_stride(buf, n, stride):
 
 
 def height_map_default_config(**overrides):
-    cfg = HeightMapConfig()
-    load_library().lio_height_map_default_config(C.byref(cfg))
-    for k, v in overrides.items():
-        if not hasattr(cfg, k):
-            raise AttributeError(k)
-        setattr(cfg, k, (C.c_float * 3)(*v) if k == "voxel" else v)
-    return cfg
+    return _default_config(HeightMapConfig, "lio_height_map_default_config", overrides, convert={"voxel": lambda v: (C.c_float * 3)(*v)})
 
 
 def _height_map_call(call, what, want_grid):
@@ -1380,13 +1251,7 @@ def height_map(xyz, cfg=None, want_grid=True, device_id=0):
 
 
 def terrain_default_config(**overrides):
-    cfg = TerrainConfig()
-    load_library().lio_terrain_default_config(C.byref(cfg))
-    for k, v in overrides.items():
-        if not hasattr(cfg, k):
-            raise AttributeError(k)
-        setattr(cfg, k, v)
-    return cfg
+    return _default_config(TerrainConfig, "lio_terrain_default_config", overrides)
 
 
 def _terrain_layers_out(buf, info, mask):
@@ -1428,13 +1293,7 @@ def radius_filter(xyzi, radius=0.5, min_neighbors=10, want_counts=True, device_i
 
 
 def ogm_default_config(**overrides):
-    cfg = OgmConfig()
-    load_library().lio_ogm_default_config(C.byref(cfg))
-    for k, v in overrides.items():
-        if not hasattr(cfg, k):
-            raise AttributeError(k)
-        setattr(cfg, k, v)
-    return cfg
+    return _default_config(OgmConfig, "lio_ogm_default_config", overrides)
 
 
 def _ogm_call(call, what, want_grid):
@@ -1463,16 +1322,10 @@ def occupancy_grid(xyz, cfg=None, want_grid=True, device_id=0):
 
 # grid_map_sdf
 def sdf_default_config(**overrides):
-    cfg = SdfConfig()
-    load_library().lio_sdf_default_config(C.byref(cfg))
-    for k, v in overrides.items():
-        if not hasattr(cfg, k):
-            raise AttributeError(k)
-        setattr(cfg, k, v)
-    return cfg
+    return _default_config(SdfConfig, "lio_sdf_default_config", overrides)
 
 
-class Sdf:
+class Sdf(_Owner):
     """grid_map::SignedDistanceField resident on the device: build it from an elevation grid (or from a keyframe store,
     KeyframeStore.sdf_map), then query it."""
 
@@ -1515,27 +1368,13 @@ class Sdf:
         _check(self.lib.lio_sdf_memory(self.h, C.byref(field), C.byref(work)), "lio_sdf_memory")
         return field.value, work.value
 
-    def close(self):
-        if self.h:
-            self.lib.lio_sdf_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _release(self):
+        self.lib.lio_sdf_destroy(self.h)
 
 
 # grid_map_filters' MedianFillFilter
 def median_fill_default_config(**overrides):
-    cfg = MedianFillConfig()
-    load_library().lio_median_fill_default_config(C.byref(cfg))
-    for k, v in overrides.items():
-        if not hasattr(cfg, k):
-            raise AttributeError(k)
-        setattr(cfg, k, v)
-    return cfg
+    return _default_config(MedianFillConfig, "lio_median_fill_default_config", overrides)
 
 
 def median_fill(grid, resolution, cfg=None, mask_in=None, want_fill_mask=True, want_cleaned_mask=False, device_id=0):
@@ -1560,24 +1399,12 @@ def median_fill(grid, resolution, cfg=None, mask_in=None, want_fill_mask=True, w
 
 # GridMap::atPosition on layers resident on the device
 def grid_sample_default_config(**overrides):
-    cfg = GridSampleConfig()
-    load_library().lio_grid_sample_default_config(C.byref(cfg))
-    for k, v in overrides.items():
-        if not hasattr(cfg, k):
-            raise AttributeError(k)
-        setattr(cfg, k, v)
-    return cfg
+    return _default_config(GridSampleConfig, "lio_grid_sample_default_config", overrides)
 
 
 # grid_map's region iterators on layers resident on the device
 def grid_region_default_config(**overrides):
-    cfg = GridRegionConfig()
-    load_library().lio_grid_region_default_config(C.byref(cfg))
-    for k, v in overrides.items():
-        if not hasattr(cfg, k):
-            raise AttributeError(k)
-        setattr(cfg, k, v)
-    return cfg
+    return _default_config(GridRegionConfig, "lio_grid_region_default_config", overrides)
 
 
 _REGION_KINDS = {"line": (REGION_LINE, 4), "circle": (REGION_CIRCLE, 3), "ellipse": (REGION_ELLIPSE, 5), "polygon": (REGION_POLYGON, 0)}
@@ -1615,7 +1442,7 @@ def footprint_polygons(poses, length, width):
     return rec, verts.reshape(-1, 2)
 
 
-class Grid:
+class Grid(_Owner):
     """A set of up to GRID_MAX_LAYERS [rows, cols] float32 layers resident on the device: upload them (or let
     KeyframeStore.planning_grid leave its grids here), then sample them at positions."""
 
@@ -1708,16 +1535,8 @@ class Grid:
         _check(self.lib.lio_grid_memory(self.h, C.byref(n)), "lio_grid_memory")
         return n.value
 
-    def close(self):
-        if self.h:
-            self.lib.lio_grid_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _release(self):
+        self.lib.lio_grid_destroy(self.h)
 
 
 def kf_store_planning_grid(store, grid, pose, *args, **kw):
@@ -1753,7 +1572,7 @@ def assemble_map(clouds_xyzi, poses, leaf, s2m=None, device_id=0, want_output=Tr
     return (_from_records(out, n_out.value) if want_output else None), n_out.value, rc
 
 
-class KeyframeStore:
+class KeyframeStore(_Owner):
     """surfCloudKeyFrames (MO:128) kept in HBM."""
 
     def __init__(self, device_id=0):
@@ -2057,13 +1876,5 @@ class KeyframeStore:
         _check(self.lib.lio_kf_store_sc_detect(self.h, C.byref(cfg), C.byref(res)), "lio_kf_store_sc_detect")
         return res
 
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            self.lib.lio_kf_store_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _release(self):
+        self.lib.lio_kf_store_destroy(self.h)

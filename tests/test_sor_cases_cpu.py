@@ -232,7 +232,6 @@ def test_the_hook_refuses_what_the_filter_refuses(pkg):
     pts = np.zeros((16, 8), np.float32)
     out = pkg.IcpGridInfo()
     fn = lib.lio_sor_debug_grid
-    fn.argtypes = [C.c_int32, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int32, C.POINTER(pkg.IcpGridInfo)]
     for k in (0, 33, -1):
         assert fn(0, pts.ctypes.data, 16, 32, k, C.byref(out)) == -1                       # LIO_ERR_ARG before any device
     assert fn(0, pts.ctypes.data, 16, 10, 10, C.byref(out)) == -1 and fn(0, pts.ctypes.data, 16, 32, 10, None) == -1
