@@ -1,5 +1,5 @@
 // lio_gridplan.h -- the host arithmetic that lays out a map's search grid, its tight row tables and a scan's tile grid.
-// Plain host C++, no HIP and no handle: lio_map_finish (liogpu_api.hip) runs the two steps around the device's occupancy
+// Plain host C++, no HIP and no handle: lio_map_finish (lio_s2m_map.hip) runs the two steps around the device's occupancy
 // count, lio_debug_grid_plan runs the same two for tests/test_nn_cases_cpu.py, which pins every field without a GPU.
 // The search's exactness rests on these bits (-ffp-contract=off): which operand is float, which double, and the order stay.
 #pragma once

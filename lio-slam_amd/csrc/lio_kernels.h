@@ -50,7 +50,7 @@ void lio_launch_init_state(LioScanState* st, int n_scans, float* poses, bool fro
 int  lio_iterate_variant(const LioIterParams& P, int ppt, bool stage, bool corner, bool allow_plain);
 int  lio_launch_iterate(const LioIterParams& P, int n_blocks, int ppt, bool stage, hipStream_t s, bool corner = false, bool allow_plain = true,
                          int tail_wgs = 0, bool* looped = nullptr);
-// Defaults of LIO_TAIL_FROM / LIO_TAIL_WGS (liogpu_api.hip), from the sweep in profiles/tail_launches_sweep.txt
+// Defaults of LIO_TAIL_FROM / LIO_TAIL_WGS (read in lio_s2m_create, liogpu_api.hip), from the sweep in profiles/tail_launches_sweep.txt
 #define LIO_TAIL_FROM_DEFAULT 7
 #define LIO_TAIL_WGS_DEFAULT 1536
 // (lio_tail.hip) the looped form on n_wgs workgroups, a multiple of 8; the caller has checked that the launch is a plain one

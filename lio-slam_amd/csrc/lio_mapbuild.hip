@@ -489,9 +489,9 @@ try {
     // the filter's last kernels (centroids) may still be in flight: the registration on the handle's stream waits for them
     HIPCHK(hipEventRecord(w->ev_done, s));
     HIPCHK(hipStreamWaitEvent(h->stream, w->ev_done, 0));
-    h->int_off = 12;                                     // the staged records are float4 (x, y, z, intensity)
-    const int rr = lio_s2m_register(h, w->ds.p, (size_t)no, sizeof(float4), pose, res);
-    h->int_off = -2;
+    LioUploadOpts o;
+    o.int_off = 12;                                      // the staged records are float4 (x, y, z, intensity)
+    const int rr = lio_s2m_register_opts(h, w->ds.p, (size_t)no, sizeof(float4), pose, res, o);
     if (rr < 0) return rr;
     if (ds_out) { const int rc2 = lio_copy_out(w->ds.as<float4>(), no, ds_out, ds_out_stride, h->stream); if (rc2 < 0) return rc2; }
     if (n_ds) *n_ds = (size_t)no;

@@ -228,20 +228,19 @@ int lio_multi_set_map(lio_s2m_handle* h, const void* pts, size_t n, size_t strid
     return LIO_OK;
 }
 
-int lio_multi_upload(lio_s2m_handle* h, int32_t n_scans, const void* const* scans, const size_t* n_pts, size_t stride)
+int lio_multi_upload(lio_s2m_handle* h, int32_t n_scans, const void* const* scans, const size_t* n_pts, size_t stride, const LioUploadOpts& o)
 {
     // Every device holds every scan: which device owns a point follows the pose, iteration by iteration.  All H2D
     // copies are in flight together (each device has its own PCIe link), one wait per device below.
     LioMulti* m = h->multi;
+    LioUploadOpts co;                                    // the record layout; no pose, no wait
+    co.xyz_off = o.xyz_off;
+    co.int_off = o.int_off;
+    co.wait = LIO_WAIT_NONE;
     for (auto& c : m->dev) {
-        lio_s2m_handle* ch = c->h;
-        ch->defer_sync = true;
-        ch->xyz_off = h->xyz_off;
-        const int rc = lio_s2m_batch_upload(ch, n_scans, scans, n_pts, stride);
-        ch->defer_sync = false;
+        const int rc = lio_s2m_upload(c->h, n_scans, scans, n_pts, stride, co);
         if (rc != LIO_OK) return rc;
     }
-    h->xyz_off = 0;
     for (auto& c : m->dev) { const int rc = lio_s2m_batch_sync(c->h); if (rc != LIO_OK) return rc; }
     m->n_scans = n_scans;
     h->n_scans = n_scans;

@@ -12,7 +12,7 @@ import zlib
 
 import numpy as np
 
-ONE_LAUNCH_MAX = 16383                  # points per scan the one-launch form takes (liogpu_api.hip)
+ONE_LAUNCH_MAX = 16383                  # points per scan the one-launch form takes (lio_s2m_upload.hip)
 TILE_CAP = 1024                         # LIO_TILE_CAP: occupancy above which a tile goes to k_scan_tile_bigsort
 BIGSORT_WGS = 64                        # workgroups of k_scan_tile_bigsort
 SCAN_CHUNK = 4096                       # LIO_SCAN_TILE: keys per workgroup of the three-phase scan

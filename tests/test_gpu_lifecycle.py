@@ -132,6 +132,74 @@ def test_error_then_reuse(pkg, small_case):
     s.close(); ref.close()
 
 
+def test_upload_options_do_not_outlive_their_call(pkg, small_case):
+    """What one entry asks of its upload -- a record layout (register_pc2), a pose carried inside the state and no wait
+    (register), a wait for the copy only (batch_upload_async), the launch loop in place of the one-launch loop (the
+    fall-back inside batch_results) -- holds for that call alone: six different calls in a row on ONE handle give, each,
+    the bits the same call gives on a fresh handle."""
+    qs = small_case["queries"]
+    scan, pose0 = qs[0]["scan"], qs[0]["pose_init"]
+    blob = np.zeros((len(scan), 4), np.float32)            # records of 16 bytes: intensity, x, y, z
+    blob[:, 0] = 7.0; blob[:, 1:] = scan
+    lay = pkg.PC2Layout(point_step=16, off_x=4, off_intensity=0, off_ring=-1, off_time=-1, pin_host=0)
+    two = [qs[1]["scan"], qs[2]["scan"]]
+    two_poses = np.stack([qs[1]["pose_init"], qs[2]["pose_init"]])
+    rec = np.ascontiguousarray(np.concatenate(two), np.float32)
+    pin = pkg.PinnedBuffer(rec.nbytes)
+    pin.array[:] = rec.view(np.uint8).reshape(-1)
+
+    def lone(out):
+        p, r, rc = out
+        assert rc == r.status
+        return p[None], [r]
+
+    def pc2(h):
+        return lone(h.scan2MapOptimizationPC2(blob, len(blob), lay, pose0))
+
+    def plain(h):
+        return lone(h.scan2MapOptimization(scan, pose0))
+
+    def async_batch(h):
+        h.batch_upload_raw(pin.ptr, [len(s) for s in two], 12, asynchronous=True)
+        h.batch_set_poses(two_poses); h.batch_run()
+        return h.batch_results()
+
+    def corners(h):
+        h.set_corner_map(small_case["map"][::3])
+        return lone(h.scan2MapOptimizationCS(scan[::4], scan, pose0))
+
+    def timed_out(h):
+        h.debug_persist_spin(spin_max=1, withhold_wg=0)    # the one-launch loop gives up: batch_results re-runs the launch loop
+        out = lone(h.scan2MapOptimization(scan, pose0))
+        assert h.profile().persist_fallbacks == 1 and h.profile().pipeline == 1
+        h.debug_persist_spin(spin_max=0, withhold_wg=-1)
+        return out
+
+    def healthy(h):
+        out = lone(h.scan2MapOptimization(scan, pose0))
+        assert h.profile().pipeline == 4                   # the launch loop of the re-run did not stick
+        return out
+
+    steps = [pc2, plain, async_batch, corners, timed_out, healthy]
+    shared = pkg.ScanToMap(pipeline=4)
+    shared.set_map(small_case["map"])
+    got = [step(shared) for step in steps]
+    assert shared.profile().persist_fallbacks == 1
+    shared.close()
+    for step, (p, r) in zip(steps, got):
+        fresh = pkg.ScanToMap(pipeline=4)
+        fresh.set_map(small_case["map"])
+        pw, rw = step(fresh)
+        fresh.close()
+        np.testing.assert_array_equal(p.view(np.uint32), pw.view(np.uint32), err_msg=step.__name__)
+        for a, b in zip(r, rw):
+            np.testing.assert_array_equal([a.iters, a.status], [b.iters, b.status], err_msg=step.__name__)
+            for f in ("AtA", "AtB"):
+                np.testing.assert_array_equal(np.array(getattr(a, f), np.float32).view(np.uint32),
+                                              np.array(getattr(b, f), np.float32).view(np.uint32), err_msg=step.__name__)
+    pin.close()
+
+
 def test_sharer_follows_an_asynchronously_installed_map(pkg, small_case):
     """lio_assemble_map_resident returns with the owner's grid build still in flight on the owner's stream; a handle
     sharing that map runs on its own stream and must wait for the build (event), not read a half-built grid."""
