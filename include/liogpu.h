@@ -1366,6 +1366,64 @@ int  lio_grid_region_cells(lio_grid *g, const lio_grid_region *regions, size_t n
  * thread as regions up, plan kernel, reduce kernel and results down, in milliseconds. */
 int  lio_grid_region_debug_stage_ms(int32_t enable, float ms[4]);
 
+/* ------------------------------------------------ resident planning layers into another frame, and out as an occupancy grid */
+/* grid_map's GridMap::getTransformedMap (GridMap.cpp:332-436) from one lio_grid into another on the same device, and
+ * GridMapRosConverter::toOccupancyGrid (GridMapRosConverter.cpp:329-365) on one resident layer: the planning grid moved into a
+ * yaw-aligned vehicle frame and a layer handed to a nav_msgs/OccupancyGrid consumer without the layers crossing PCIe.
+ * DESIGN.md section 4m states the conventions; parity is against the restatement (tests/grid_transform_restate.py) with the
+ * reference's own test values on top (parity unpinned).
+ *  - new geometry   on the host in fp64: the corners position +- 0.5 length at z = 0 in the order (+, +), (+, -), (-, +),
+ *                   (-, -), each transformed, summed from zero in that order and multiplied by 0.25 (the centre); the largest
+ *                   fabs(corner - centre) per axis by fmax, doubled; setGeometry: size = (int)round(length / resolution),
+ *                   length = size * resolution, position = the centre;
+ *  - transform * p  ((R_i0 x + R_i1 y) + R_i2 z) + t_i per component, fp64, no contraction;
+ *  - visit order    source cells by column-major linear index ascending; a cell whose height is not finite is skipped; with
+ *                   sample_ratio > 0 five samples, the centre then x - l, x + l, y - l, y + l with l = resolution *
+ *                   sample_ratio, otherwise the centre alone; a sample whose getIndex on the new map fails is dropped;
+ *  - the rule       a sample is skipped when the new cell's height is not NaN and, widened to double, greater than the
+ *                   sample's fp64 z; otherwise the new cell's height becomes (float)z and every other layer takes the source
+ *                   cell's bits, NaN included.  Cells nothing reaches are the quiet NaN 0x7fc00000 in every layer.
+ * The result is the serial loop's bit for bit, on every run (integer atomics only).  The structs are declared apart from their
+ * typedefs; they are the same types. */
+struct lio_grid_transform_info {
+    int32_t rows, cols;           /* the new grid                                                               */
+    double  length[2], position[2];
+    int64_t n_source_cells;       /* cells with a finite height (getPosition3 succeeded)                        */
+    int64_t n_samples_outside;    /* samples whose getIndex on the new map failed                               */
+    int64_t n_cells_written;      /* new cells that received a value                                            */
+};
+typedef struct lio_grid_transform_info lio_grid_transform_info;
+struct lio_grid_occupancy_desc {
+    uint32_t width, height;       /* rows, cols (info.width = getSize()(0), info.height = getSize()(1))         */
+    float    resolution;          /* the double narrowed to float, as the message field does                    */
+    int32_t  pad;
+    double   origin[2];           /* position - 0.5 length                                                      */
+};
+typedef struct lio_grid_occupancy_desc lio_grid_occupancy_desc;
+/* 5 x source cells is the largest visit number + 1 and must fit 31 bits of the winner's key */
+#define LIO_GRID_TRANSFORM_MAX_SOURCE_CELLS 429496729
+/* Afterwards dst holds every layer src holds, under the same ids, in the new geometry; what dst held is replaced (after a
+ * failure past the refusals it holds none); src is only read.  transform: the rows of [R | t].  info may be NULL.
+ * LIO_ERR_ARG before any device is touched and with dst untouched: null src, dst or transform, src == dst, grids on
+ * different devices, src without layers, height_layer absent, a non-finite transform entry or sample_ratio, a new size below
+ * 1 on either axis (the reference asserts there), and a z row so large that a transformed height could overflow fp64 (a
+ * labelled deviation: the reference would store NaN).  LIO_ERR_CAPACITY, dst untouched as well: a new axis >= 2^24, more than
+ * 2^31 - 1024 new cells, more than LIO_GRID_TRANSFORM_MAX_SOURCE_CELLS source cells.  Complete on return, one host wait per
+ * call (the counters). */
+int  lio_grid_transform(lio_grid *src, const double transform[12], int32_t height_layer, double sample_ratio, lio_grid *dst,
+                        lio_grid_transform_info *info);
+/* Layer `layer` as the cells of a nav_msgs/OccupancyGrid; only the int8 cells come down.  In float, as written:
+ * value = (v - data_min) / (data_max - data_min); NaN gives -1, otherwise 0 + min(max(0, value), 1) * 100, converted to int8_t
+ * by truncation.  The cell of column-major linear index col * rows + row goes to data[n - 1 - index], n = rows x cols.
+ * data_min == data_max is not refused: the division's infinities clamp and its NaN gives -1.  desc may be NULL.  LIO_ERR_ARG:
+ * a null grid or data, an absent layer, cap_cells < rows x cols (data untouched), a non-finite data_min or data_max.
+ * Complete on return, one host wait per call. */
+int  lio_grid_to_occupancy(lio_grid *g, int32_t layer, float data_min, float data_max, int8_t *data, size_t cap_cells,
+                           lio_grid_occupancy_desc *desc);
+/* Measurement hook (tools/grid_transform_cost.py), as lio_grid_debug_stage_ms: the last lio_grid_transform of the calling
+ * thread as keys cleared, scatter kernel, gather kernel with the counters down, in milliseconds. */
+int  lio_grid_transform_debug_stage_ms(int32_t enable, float ms[3]);
+
 #ifdef __cplusplus
 }
 #endif

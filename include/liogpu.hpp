@@ -418,6 +418,18 @@ public:
         if (rc != LIO_ERR_CAPACITY) check(rc, "lio_grid_region_cells");
         return rc;
     }
+    // GridMap::getTransformedMap into dst (on the same device): dst then holds every layer this object holds, in the new geometry.
+    // transform: the rows of [R | t]
+    void transformInto(GridLayers& dst, const double transform[12], int32_t height_layer = LIO_GRID_LAYER_ELEVATION, double sample_ratio = 0.0,
+                       lio_grid_transform_info* info = nullptr)
+    {
+        check(lio_grid_transform(g_, transform, height_layer, sample_ratio, dst.g_, info), "lio_grid_transform");
+    }
+    // GridMapRosConverter::toOccupancyGrid on one layer: data receives rows x cols cells in the message's order
+    void toOccupancyGrid(int32_t layer, float data_min, float data_max, int8_t* data, size_t cap_cells, lio_grid_occupancy_desc* desc = nullptr)
+    {
+        check(lio_grid_to_occupancy(g_, layer, data_min, data_max, data, cap_cells, desc), "lio_grid_to_occupancy");
+    }
     void layer(int32_t k, float* out, size_t cap_floats) { check(lio_grid_get_layer(g_, k, out, cap_floats), "lio_grid_get_layer"); }
     lio_grid_desc info()
     {

@@ -23,7 +23,8 @@ from .api import (LioError, ScanToMap, S2MConfig, S2MResult, S2MProfile, DeskewC
                   GRID_LAYER_TERRAIN,
                   GridRegion, GridRegionConfig, GridRegionStat, GridRegionInfo, GRID_REGION_DTYPE, GRID_REGION_STAT_DTYPE,
                   grid_region_default_config, pack_regions, footprint_polygons, REGION_LINE, REGION_CIRCLE, REGION_ELLIPSE, REGION_POLYGON,
-                  REGION_OK, REGION_EMPTY, REGION_INVALID, REGION_MAX_VERTICES, REGION_MAX_WALK)
+                  REGION_OK, REGION_EMPTY, REGION_INVALID, REGION_MAX_VERTICES, REGION_MAX_WALK,
+                  GRID_TRANSFORM_INFO_DTYPE, GRID_OCCUPANCY_DESC_DTYPE, GRID_TRANSFORM_MAX_SOURCE_CELLS)
 
 __all__ = ["LioError", "ScanToMap", "S2MConfig", "S2MResult", "S2MProfile", "DeskewConfig",
            "lib_path", "load_library", "build_library", "deskew", "curvature", "imu_deskew_info",
@@ -43,4 +44,5 @@ __all__ = ["LioError", "ScanToMap", "S2MConfig", "S2MResult", "S2MProfile", "Des
            "GRID_LAYER_TERRAIN",
            "GridRegion", "GridRegionConfig", "GridRegionStat", "GridRegionInfo", "GRID_REGION_DTYPE", "GRID_REGION_STAT_DTYPE",
            "grid_region_default_config", "pack_regions", "footprint_polygons", "REGION_LINE", "REGION_CIRCLE", "REGION_ELLIPSE", "REGION_POLYGON",
-           "REGION_OK", "REGION_EMPTY", "REGION_INVALID", "REGION_MAX_VERTICES", "REGION_MAX_WALK"]
+           "REGION_OK", "REGION_EMPTY", "REGION_INVALID", "REGION_MAX_VERTICES", "REGION_MAX_WALK",
+           "GRID_TRANSFORM_INFO_DTYPE", "GRID_OCCUPANCY_DESC_DTYPE", "GRID_TRANSFORM_MAX_SOURCE_CELLS"]

@@ -285,6 +285,15 @@ class GridRegionInfo(C.Structure):
 GRID_REGION_DTYPE = np.dtype({"names": ["kind", "n_vertices", "first_vertex", "p"], "formats": [np.int32, np.int32, np.int64, (np.float64, 5)],
                               "offsets": [0, 4, 8, 16], "itemsize": 56})
 GRID_REGION_STAT_DTYPE = np.dtype([("sum", np.float64), ("min", np.float32), ("max", np.float32), ("n_finite", np.int32), ("n_below", np.int32)])
+# lio_grid_transform_info and lio_grid_occupancy_desc of include/liogpu.h, one record each (tests/test_grid_transform_capi.py
+# holds the layouts to gcc's)
+GRID_TRANSFORM_INFO_DTYPE = np.dtype({"names": ["rows", "cols", "length", "position", "n_source_cells", "n_samples_outside", "n_cells_written"],
+                                      "formats": [np.int32, np.int32, (np.float64, 2), (np.float64, 2), np.int64, np.int64, np.int64],
+                                      "offsets": [0, 4, 8, 24, 40, 48, 56], "itemsize": 64})
+GRID_OCCUPANCY_DESC_DTYPE = np.dtype({"names": ["width", "height", "resolution", "pad", "origin"],
+                                      "formats": [np.uint32, np.uint32, np.float32, np.int32, (np.float64, 2)],
+                                      "offsets": [0, 4, 8, 12, 16], "itemsize": 32})
+GRID_TRANSFORM_MAX_SOURCE_CELLS = 429496729
 REGION_LINE, REGION_CIRCLE, REGION_ELLIPSE, REGION_POLYGON = 0, 1, 2, 3
 REGION_OK, REGION_EMPTY, REGION_INVALID = 0, 1, 2
 REGION_MAX_VERTICES, REGION_MAX_WALK = 64, 4096
@@ -459,6 +468,9 @@ CAPI = {
     "lio_grid_region_reduce": [vp, pi, i32, P(GridRegionConfig), vp, sz, vp, sz, vp, vp, vp, P(GridRegionInfo)],
     "lio_grid_region_cells": [vp, vp, sz, vp, sz, vp, vp, sz, vp, P(GridRegionInfo)],
     "lio_grid_region_debug_stage_ms": [i32, pf],
+    "lio_grid_transform": [vp, pd, i32, f64, vp, vp],
+    "lio_grid_to_occupancy": [vp, i32, f32, f32, vp, sz, vp],
+    "lio_grid_transform_debug_stage_ms": [i32, pf],
 }
 CAPI = {name: sig if isinstance(sig, tuple) else (C.c_int, sig) for name, sig in CAPI.items()}     # -> (restype, argtypes), all of them
 EXPORTS = list(CAPI)
@@ -1528,6 +1540,26 @@ class Grid(_Owner):
             rc = call(cells)
         _check(rc, "lio_grid_region_cells")
         return offsets, cells[:int(offsets[n])], status, info
+
+    def transform(self, dst, transform, height_layer=0, sample_ratio=0.0):
+        """GridMap::getTransformedMap into `dst` (another Grid on the same device): afterwards it holds every layer this one
+        holds, in the new geometry.  transform: [3, 4] (or [4, 4]) float64, the rows of [R | t].
+        -> a GRID_TRANSFORM_INFO_DTYPE record."""
+        t = np.ascontiguousarray(np.asarray(transform, np.float64).reshape(-1, 4)[:3]).reshape(12)
+        info = np.zeros(1, GRID_TRANSFORM_INFO_DTYPE)
+        _check(self.lib.lio_grid_transform(self.h, t.ctypes.data_as(C.POINTER(C.c_double)), int(height_layer), float(sample_ratio), dst.h, info.ctypes.data),
+               "lio_grid_transform")
+        return info[0]
+
+    def to_occupancy(self, layer, data_min, data_max):
+        """GridMapRosConverter::toOccupancyGrid on layer `layer` -> (data [rows * cols] int8 in the message's order, a
+        GRID_OCCUPANCY_DESC_DTYPE record)"""
+        i = self.info()
+        data = np.zeros(i.rows * i.cols, np.int8)
+        desc = np.zeros(1, GRID_OCCUPANCY_DESC_DTYPE)
+        _check(self.lib.lio_grid_to_occupancy(self.h, int(layer), float(data_min), float(data_max), data.ctypes.data, data.size, desc.ctypes.data),
+               "lio_grid_to_occupancy")
+        return data, desc[0]
 
     def memory(self):
         """-> bytes the object holds on the device"""
