@@ -1424,6 +1424,90 @@ int  lio_grid_to_occupancy(lio_grid *g, int32_t layer, float data_min, float dat
  * thread as keys cleared, scatter kernel, gather kernel with the counters down, in milliseconds. */
 int  lio_grid_transform_debug_stage_ms(int32_t enable, float ms[3]);
 
+/* ------------------------------------------------ resident planning layers cropped, moved, extended and merged on the device */
+/* grid_map's GridMap::getSubmap (GridMap.cpp:282-330), move (:442-507), extendToInclude (:554-627) and addDataFrom (:514-552)
+ * on lio_grid objects of one device: a persistent map that grows as the vehicle drives, a window of it, a map that follows the
+ * vehicle, without a layer crossing PCIe.  DESIGN.md section 4n states the conventions; parity is against the restatement
+ * (tests/grid_geom_restate.py) with the reference's own test values on top (parity unpinned).  A lio_grid keeps startIndex 0:
+ * every result is the reference's after convertToDefaultStartIndex (:677-707).  All geometry is decided on the host in fp64,
+ * in the order the source writes it:
+ *  - submap   getSubmapInformation (GridMapMath.cpp:287-341): both corners position +- 0.5 length through
+ *             boundPositionToRange and getIndexFromPosition, size = bottom right - top left + 1, length = size * resolution,
+ *             position = the top-left cell's centre + 0.5 resolution - 0.5 length, and getIndexFromPosition of the requested
+ *             position in the submap, whose failure (a requested centre outside the map) fails the call;
+ *  - move     getIndexShiftFromPositionShift (:183-196): per axis v = (position - map position) / resolution, index shift =
+ *             -(int)(v + 0.5 * (v > 0 ? 1 : -1)); the map's position moves by (double)(-index shift) * resolution; new cell
+ *             (r, c) takes old cell (r + shift0, c + shift1) where that exists, the quiet NaN 0x7fc00000 elsewhere;
+ *  - extend   the four corner comparisons and their half differences, setGeometry (size = (int)round(length / resolution)),
+ *             the alignment by fmod, the `< resolution / 2` branch and the parity correction by copysign; then every new cell
+ *             takes its centre, isInside and getIndex on the old geometry, and the old cell's bits (the quiet NaN elsewhere);
+ *  - add      after the extension (if asked for) and after the layers this map lacks were added as NaN: per cell, valid =
+ *             every basic layer finite (no basic layer: never valid); a valid cell is skipped unless overwrite; the cell's
+ *             centre, isInside and getIndex on `other`; each listed layer takes other's bits where they are finite.
+ * Labelled deviations: where isInside holds and getIndex fails (a centre within an ulp of the low edge) the reference reads
+ * past the buffer; such a cell is skipped and counted in n_index_outside.  A bounded submap corner whose index still falls
+ * outside is brought back to the last cell, where the reference fails.  |v| >= 2^30 or a non-finite v in move is LIO_ERR_ARG
+ * (the reference's cast is undefined).  Layers are matched by id, as the reference matches them by name.  Every result is the
+ * serial loop's bit for bit (no cell reads another cell of the map it writes).  The structs are declared apart from their
+ * typedefs; they are the same types. */
+struct lio_grid_submap_info {
+    int32_t success;              /* getSubmap's isSuccess; 0: dst holds no layers                              */
+    int32_t rows, cols, pad;
+    double  length[2], position[2];
+    int32_t top_left[2];          /* the submap's first cell in src                                             */
+    int32_t requested_index[2];   /* the requested position's cell in the submap                                */
+};
+typedef struct lio_grid_submap_info lio_grid_submap_info;
+struct lio_grid_move_info {
+    int32_t moved, pad;           /* move's return value: the index shift is not (0, 0)                         */
+    int32_t index_shift[2];
+    double  position[2];          /* the map's position afterwards (aligned to the cells)                       */
+    int64_t n_cells_cleared;      /* cells per layer that became NaN                                            */
+};
+typedef struct lio_grid_move_info lio_grid_move_info;
+struct lio_grid_extend_info {
+    int32_t resized, rows, cols, pad;              /* the geometry afterwards                                   */
+    double  length[2], position[2];
+    int64_t n_cells_kept;         /* new cells that took an old cell                                            */
+    int64_t n_index_outside;      /* isInside held, getIndex failed: skipped (the labelled deviation)           */
+};
+typedef struct lio_grid_extend_info lio_grid_extend_info;
+struct lio_grid_add_info {
+    int32_t resized, rows, cols, pad;              /* the geometry afterwards                                   */
+    double  length[2], position[2];
+    int64_t n_cells_skipped_valid;                 /* valid and not overwrite                                   */
+    int64_t n_cells_outside_other;                 /* the centre is not inside `other`                          */
+    int64_t n_index_outside;      /* as above, on the old map (the extension) or on `other`                     */
+    int64_t n_values_copied;      /* finite values taken from `other`, over all layers                          */
+};
+typedef struct lio_grid_add_info lio_grid_add_info;
+/* Refusals common to the four: LIO_ERR_ARG before any device is touched and with every object untouched for a null argument,
+ * src == dst or g == other, grids on different devices, a source (src, other, or the g that is moved, extended or added to)
+ * without layers, a non-finite position or length, a negative length, a flag outside 0 / 1.  LIO_ERR_CAPACITY, untouched as
+ * well: a new axis >= 2^24, more than 2^31 - 1024 new cells.  Every call is complete on return with one host wait (the
+ * counters); info may be NULL; src and other are only read.
+ *
+ * getSubmap: dst then holds every layer src holds, under the same ids, cropped; what it held is replaced.  A requested centre
+ * outside the map is not an error: LIO_OK, info->success = 0, dst without layers. */
+int  lio_grid_submap(lio_grid *src, const double position[2], const double length[2], lio_grid *dst, lio_grid_submap_info *info);
+/* move, in place: every layer of g is shifted through a second buffer from the library's pool, which then takes the layer's
+ * place (the old one goes back to the pool).  An index shift of (0, 0) launches nothing; the position still takes the aligned
+ * shift, as written. */
+int  lio_grid_move(lio_grid *g, const double position[2], lio_grid_move_info *info);
+/* extendToInclude.  Nothing to extend: LIO_OK, info->resized = 0, nothing touched.  `other` may have any resolution: the
+ * reference reads its corners only, and the new map keeps g's resolution and is aligned with g's cells.  (With differing
+ * resolutions there is nothing else to align: none is refused for it; a g without layers has no geometry to extend and is.) */
+int  lio_grid_extend_to_include(lio_grid *g, lio_grid *other, lio_grid_extend_info *info);
+/* addDataFrom(other, extend, overwrite, copyAllLayers, layers).  n_layers = 0: every layer `other` holds.  An id g lacks is
+ * added, NaN-filled.  basic_mask (bit k: layer k) stands for basicLayers_ and may be 0.  With extend and a resize, extension
+ * and addition are one launch; otherwise the addition works in place.  Further LIO_ERR_ARG: n_layers outside 0 .. 16, an id
+ * outside 0 .. 15, repeated or absent from `other`, a basic_mask bit for a layer g does not hold. */
+int  lio_grid_add_data_from(lio_grid *g, lio_grid *other, int32_t extend, int32_t overwrite, const int32_t *layer_ids,
+                            int32_t n_layers, uint32_t basic_mask, lio_grid_add_info *info);
+/* Measurement hook (tools/grid_geom_cost.py), as lio_grid_debug_stage_ms: the kernel of the calling thread's last call of the
+ * four, in milliseconds (0 where none was launched). */
+int  lio_grid_geom_debug_kernel_ms(int32_t enable, float *ms);
+
 #ifdef __cplusplus
 }
 #endif

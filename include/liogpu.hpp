@@ -430,6 +430,37 @@ public:
     {
         check(lio_grid_to_occupancy(g_, layer, data_min, data_max, data, cap_cells, desc), "lio_grid_to_occupancy");
     }
+    // GridMap::getSubmap into dst (on the same device): every layer this object holds, cropped.  Returns isSuccess; false (a
+    // requested centre outside the map) leaves dst without layers
+    bool getSubmap(GridLayers& dst, const double position[2], const double length[2], lio_grid_submap_info* info = nullptr)
+    {
+        lio_grid_submap_info i;
+        check(lio_grid_submap(g_, position, length, dst.g_, &i), "lio_grid_submap");
+        if (info) *info = i;
+        return i.success != 0;
+    }
+    // GridMap::move, in place: returns whether the map moved by at least one cell
+    bool move(const double position[2], lio_grid_move_info* info = nullptr)
+    {
+        lio_grid_move_info i;
+        check(lio_grid_move(g_, position, &i), "lio_grid_move");
+        if (info) *info = i;
+        return i.moved != 0;
+    }
+    // GridMap::extendToInclude: returns whether the map was resized
+    bool extendToInclude(GridLayers& other, lio_grid_extend_info* info = nullptr)
+    {
+        lio_grid_extend_info i;
+        check(lio_grid_extend_to_include(g_, other.g_, &i), "lio_grid_extend_to_include");
+        if (info) *info = i;
+        return i.resized != 0;
+    }
+    // GridMap::addDataFrom.  n_layers = 0 (layer_ids nullptr): copyAllLayers.  basic_mask: bit k, layer k is one of basicLayers_
+    void addDataFrom(GridLayers& other, bool extend_map, bool overwrite_data, const int32_t* layer_ids = nullptr, int32_t n_layers = 0,
+                     uint32_t basic_mask = 0, lio_grid_add_info* info = nullptr)
+    {
+        check(lio_grid_add_data_from(g_, other.g_, extend_map ? 1 : 0, overwrite_data ? 1 : 0, layer_ids, n_layers, basic_mask, info), "lio_grid_add_data_from");
+    }
     void layer(int32_t k, float* out, size_t cap_floats) { check(lio_grid_get_layer(g_, k, out, cap_floats), "lio_grid_get_layer"); }
     lio_grid_desc info()
     {

@@ -24,7 +24,8 @@ from .api import (LioError, ScanToMap, S2MConfig, S2MResult, S2MProfile, DeskewC
                   GridRegion, GridRegionConfig, GridRegionStat, GridRegionInfo, GRID_REGION_DTYPE, GRID_REGION_STAT_DTYPE,
                   grid_region_default_config, pack_regions, footprint_polygons, REGION_LINE, REGION_CIRCLE, REGION_ELLIPSE, REGION_POLYGON,
                   REGION_OK, REGION_EMPTY, REGION_INVALID, REGION_MAX_VERTICES, REGION_MAX_WALK,
-                  GRID_TRANSFORM_INFO_DTYPE, GRID_OCCUPANCY_DESC_DTYPE, GRID_TRANSFORM_MAX_SOURCE_CELLS)
+                  GRID_TRANSFORM_INFO_DTYPE, GRID_OCCUPANCY_DESC_DTYPE, GRID_TRANSFORM_MAX_SOURCE_CELLS,
+                  GRID_SUBMAP_INFO_DTYPE, GRID_MOVE_INFO_DTYPE, GRID_EXTEND_INFO_DTYPE, GRID_ADD_INFO_DTYPE)
 
 __all__ = ["LioError", "ScanToMap", "S2MConfig", "S2MResult", "S2MProfile", "DeskewConfig",
            "lib_path", "load_library", "build_library", "deskew", "curvature", "imu_deskew_info",
@@ -45,4 +46,5 @@ __all__ = ["LioError", "ScanToMap", "S2MConfig", "S2MResult", "S2MProfile", "Des
            "GridRegion", "GridRegionConfig", "GridRegionStat", "GridRegionInfo", "GRID_REGION_DTYPE", "GRID_REGION_STAT_DTYPE",
            "grid_region_default_config", "pack_regions", "footprint_polygons", "REGION_LINE", "REGION_CIRCLE", "REGION_ELLIPSE", "REGION_POLYGON",
            "REGION_OK", "REGION_EMPTY", "REGION_INVALID", "REGION_MAX_VERTICES", "REGION_MAX_WALK",
-           "GRID_TRANSFORM_INFO_DTYPE", "GRID_OCCUPANCY_DESC_DTYPE", "GRID_TRANSFORM_MAX_SOURCE_CELLS"]
+           "GRID_TRANSFORM_INFO_DTYPE", "GRID_OCCUPANCY_DESC_DTYPE", "GRID_TRANSFORM_MAX_SOURCE_CELLS",
+           "GRID_SUBMAP_INFO_DTYPE", "GRID_MOVE_INFO_DTYPE", "GRID_EXTEND_INFO_DTYPE", "GRID_ADD_INFO_DTYPE"]

@@ -294,6 +294,20 @@ GRID_OCCUPANCY_DESC_DTYPE = np.dtype({"names": ["width", "height", "resolution",
                                       "formats": [np.uint32, np.uint32, np.float32, np.int32, (np.float64, 2)],
                                       "offsets": [0, 4, 8, 12, 16], "itemsize": 32})
 GRID_TRANSFORM_MAX_SOURCE_CELLS = 429496729
+# lio_grid_submap_info, lio_grid_move_info, lio_grid_extend_info and lio_grid_add_info (tests/test_grid_geom_capi.py holds the
+# layouts to gcc's)
+GRID_SUBMAP_INFO_DTYPE = np.dtype({"names": ["success", "rows", "cols", "pad", "length", "position", "top_left", "requested_index"],
+                                   "formats": [np.int32, np.int32, np.int32, np.int32, (np.float64, 2), (np.float64, 2), (np.int32, 2), (np.int32, 2)],
+                                   "offsets": [0, 4, 8, 12, 16, 32, 48, 56], "itemsize": 64})
+GRID_MOVE_INFO_DTYPE = np.dtype({"names": ["moved", "pad", "index_shift", "position", "n_cells_cleared"],
+                                 "formats": [np.int32, np.int32, (np.int32, 2), (np.float64, 2), np.int64], "offsets": [0, 4, 8, 16, 32], "itemsize": 40})
+GRID_EXTEND_INFO_DTYPE = np.dtype({"names": ["resized", "rows", "cols", "pad", "length", "position", "n_cells_kept", "n_index_outside"],
+                                   "formats": [np.int32, np.int32, np.int32, np.int32, (np.float64, 2), (np.float64, 2), np.int64, np.int64],
+                                   "offsets": [0, 4, 8, 12, 16, 32, 48, 56], "itemsize": 64})
+GRID_ADD_INFO_DTYPE = np.dtype({"names": ["resized", "rows", "cols", "pad", "length", "position", "n_cells_skipped_valid", "n_cells_outside_other",
+                                          "n_index_outside", "n_values_copied"],
+                                "formats": [np.int32, np.int32, np.int32, np.int32, (np.float64, 2), (np.float64, 2), np.int64, np.int64, np.int64, np.int64],
+                                "offsets": [0, 4, 8, 12, 16, 32, 48, 56, 64, 72], "itemsize": 80})
 REGION_LINE, REGION_CIRCLE, REGION_ELLIPSE, REGION_POLYGON = 0, 1, 2, 3
 REGION_OK, REGION_EMPTY, REGION_INVALID = 0, 1, 2
 REGION_MAX_VERTICES, REGION_MAX_WALK = 64, 4096
@@ -471,6 +485,11 @@ CAPI = {
     "lio_grid_transform": [vp, pd, i32, f64, vp, vp],
     "lio_grid_to_occupancy": [vp, i32, f32, f32, vp, sz, vp],
     "lio_grid_transform_debug_stage_ms": [i32, pf],
+    "lio_grid_submap": [vp, pd, pd, vp, vp],
+    "lio_grid_move": [vp, pd, vp],
+    "lio_grid_extend_to_include": [vp, vp, vp],
+    "lio_grid_add_data_from": [vp, vp, i32, i32, pi, i32, C.c_uint32, vp],
+    "lio_grid_geom_debug_kernel_ms": [i32, pf],
 }
 CAPI = {name: sig if isinstance(sig, tuple) else (C.c_int, sig) for name, sig in CAPI.items()}     # -> (restype, argtypes), all of them
 EXPORTS = list(CAPI)
@@ -1560,6 +1579,46 @@ class Grid(_Owner):
         _check(self.lib.lio_grid_to_occupancy(self.h, int(layer), float(data_min), float(data_max), data.ctypes.data, data.size, desc.ctypes.data),
                "lio_grid_to_occupancy")
         return data, desc[0]
+
+    def submap(self, dst, position, length):
+        """GridMap::getSubmap into `dst` (another Grid on the same device): every layer this one holds, cropped to the cells
+        the window position +- length / 2 covers.  -> a GRID_SUBMAP_INFO_DTYPE record; success = 0 (a requested centre outside
+        the map) leaves dst without layers."""
+        ps, ln = (C.c_double * 2)(*position), (C.c_double * 2)(*length)
+        info = np.zeros(1, GRID_SUBMAP_INFO_DTYPE)
+        _check(self.lib.lio_grid_submap(self.h, ps, ln, dst.h, info.ctypes.data), "lio_grid_submap")
+        return info[0]
+
+    def move(self, position):
+        """GridMap::move, in place: the map is re-centred on `position` by whole cells; the cells that enter are NaN.
+        -> a GRID_MOVE_INFO_DTYPE record"""
+        ps = (C.c_double * 2)(*position)
+        info = np.zeros(1, GRID_MOVE_INFO_DTYPE)
+        _check(self.lib.lio_grid_move(self.h, ps, info.ctypes.data), "lio_grid_move")
+        return info[0]
+
+    def extend_to_include(self, other):
+        """GridMap::extendToInclude: this map grows, aligned with its own cells, until it covers `other` (another Grid on the
+        same device).  -> a GRID_EXTEND_INFO_DTYPE record"""
+        info = np.zeros(1, GRID_EXTEND_INFO_DTYPE)
+        _check(self.lib.lio_grid_extend_to_include(self.h, other.h, info.ctypes.data), "lio_grid_extend_to_include")
+        return info[0]
+
+    def add_data_from(self, other, extend=True, overwrite=True, layer_ids=None, basic_layers=()):
+        """GridMap::addDataFrom(other, extend, overwrite, copyAllLayers, layers).  layer_ids None: every layer `other` holds.
+        basic_layers: the ids that stand for basicLayers_ (the validity test that `overwrite` = False respects).
+        -> a GRID_ADD_INFO_DTYPE record"""
+        ids = np.zeros(0, np.int32) if layer_ids is None else np.ascontiguousarray(layer_ids, np.int32).reshape(-1)
+        if layer_ids is not None and len(ids) == 0:
+            raise ValueError("layer_ids is empty: pass None to copy every layer")
+        mask = 0
+        for k in basic_layers:
+            mask |= 1 << int(k)
+        info = np.zeros(1, GRID_ADD_INFO_DTYPE)
+        _check(self.lib.lio_grid_add_data_from(self.h, other.h, int(bool(extend)), int(bool(overwrite)),
+                                               ids.ctypes.data_as(C.POINTER(C.c_int32)) if len(ids) else None, len(ids), mask, info.ctypes.data),
+               "lio_grid_add_data_from")
+        return info[0]
 
     def memory(self):
         """-> bytes the object holds on the device"""

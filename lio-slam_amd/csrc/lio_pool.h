@@ -103,6 +103,11 @@ struct LioPinned {
 hipError_t lio_pool_acquire(void** p, size_t bytes);   // on the current device
 void lio_pool_release(void* p);
 void lio_pool_trim(void);                               // frees every idle block
+// A busy block leaves the pool: the caller owns it from now on (hipFree).  Returns its capacity in bytes; 0 for a pointer the
+// pool does not hold.
+size_t lio_pool_disown(void* p);
+// A hipMalloc'd block of `cap` bytes on `device` that nothing reads or writes any more joins the pool, idle.
+void lio_pool_adopt(void* p, size_t cap, int device);
 
 struct LioTemp {            // RAII temporary from the pool
     void* p = nullptr;

@@ -60,6 +60,27 @@ void lio_pool_release(void* p)
         if (b.p == p) { b.busy = false; return; }
 }
 
+size_t lio_pool_disown(void* p)
+{
+    std::lock_guard<std::mutex> lk(g_pool_mu);
+    for (size_t i = 0; i < g_pool.size(); ++i)
+        if (g_pool[i].p == p) {
+            const size_t cap = g_pool[i].cap;
+            g_pool_bytes -= cap;
+            g_pool[i] = g_pool.back();
+            g_pool.pop_back();
+            return cap;
+        }
+    return 0;
+}
+
+void lio_pool_adopt(void* p, size_t cap, int device)
+{
+    std::lock_guard<std::mutex> lk(g_pool_mu);
+    g_pool.push_back({ p, cap, device, false });
+    g_pool_bytes += cap;
+}
+
 void lio_pool_trim(void)
 {
     std::lock_guard<std::mutex> lk(g_pool_mu);
