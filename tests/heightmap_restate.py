@@ -1,8 +1,8 @@
 """numpy restatement of the planning height map (include/liogpu.h lio_height_map) behind the outlier and voxel filters:
 stages 3-7 of DESIGN.md section 4e -- level / ego filter / un-level, geometry, binning, elevation (ordered mean or
 clusters), hole filling -- written from the semantics stated there, fp32 wherever the reference is fp32 and fp64 wherever it
-is fp64.  The outlier filter comes from tests/localmap_restate.py.  The checker of tests/test_heightmap_cpu.py and
-tests/test_gpu_heightmap.py.  Parity with PCL, Eigen and grid_map themselves is unpinned: none of them can be built here."""
+is fp64.  The outlier filter comes from tests/localmap_restate.py.  The checker of tests/test_heightmap_cpu.py,
+tests/test_gpu_heightmap.py and, on the designed inputs of tests/heightmap_cases.py, tests/test_gpu_heightmap_edges.py.  Parity with PCL, Eigen and grid_map themselves is unpinned: none of them can be built here."""
 import math
 import os
 import sys
