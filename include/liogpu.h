@@ -1508,6 +1508,101 @@ int  lio_grid_add_data_from(lio_grid *g, lio_grid *other, int32_t extend, int32_
  * four, in milliseconds (0 where none was launched). */
 int  lio_grid_geom_debug_kernel_ms(int32_t enable, float *ms);
 
+/* ------------------------------------------------ resident planning layers out as images, clouds and grid cells, and in again */
+/* grid_map_cv's GridMapCvConverter (toImage, addLayerFromImage, addColorLayerFromImage, initializeFromImage) and
+ * GridMapRosConverter's toPointCloud (both), toGridCells and fromOccupancyGrid on resident objects: what a node publishes
+ * comes down in the format it is published in, and a costmap or a mask that arrives as an image or an occupancy grid becomes a
+ * layer beside the terrain layers.  DESIGN.md section 4o states the conventions and the labelled deviations; parity is
+ * against the restatement (tests/grid_convert_restate.py) with the reference's own test values on top (parity unpinned).
+ * Layers are column-major rows x cols with start index 0: GridMapIterator's linear order is the storage order.  Images are
+ * row-major rows x cols x channels, tightly packed, image row = grid row, image column = grid column, little-endian elements.
+ * Every call is complete on return on the null stream; info may be NULL; the four to_* calls only read their object.
+ * LIO_ERR_ARG is returned before any device is touched wherever that is possible, never a clamp. */
+#define LIO_IMAGE_8U  0
+#define LIO_IMAGE_16U 1
+#define LIO_IMAGE_32F 2
+struct lio_grid_image_info {
+    int32_t rows, cols;
+    float   lower, upper;         /* the bounds used (the layer's finite extremes when both arguments were NaN)  */
+    int64_t n_pixels;             /* pixels that received a value                                               */
+    int64_t n_clamped_low;        /* cells below lower                                                          */
+    int64_t n_clamped_high;       /* cells above upper                                                          */
+    int64_t n_nonfinite;          /* cells whose clamped value is not finite: the pixel is zero in every channel */
+};
+typedef struct lio_grid_image_info lio_grid_image_info;
+struct lio_grid_from_image_info {
+    int32_t rows, cols;
+    int32_t geometry_set, pad;    /* 1: the grid held no layers and took its geometry from the call             */
+    int64_t n_cells_set;          /* cells that received a value                                                */
+    int64_t n_cells_transparent;  /* cells whose alpha is below the threshold: NaN                              */
+};
+typedef struct lio_grid_from_image_info lio_grid_from_image_info;
+struct lio_grid_from_occupancy_info {
+    int32_t rows, cols;           /* width, height                                                              */
+    int32_t geometry_replaced, pad;   /* 1: setGeometry ran, every other layer reads NaN at the new size        */
+    double  length[2], position[2];
+    int64_t n_unknown;            /* cells of -1: NaN                                                           */
+};
+typedef struct lio_grid_from_occupancy_info lio_grid_from_occupancy_info;
+/* toImage<Type, NChannels> (GridMapCvConverter.hpp:173-247) of layer `layer`: channels 1, 3 or 4, depth LIO_IMAGE_*.  Per
+ * cell in float, as written: v = x < lower ? lower : (x > upper ? upper : x) (a NaN stays NaN); a non-finite v leaves the
+ * pixel zero in every channel, alpha included; otherwise (Type)(((v - lower) / (upper - lower)) * (float)max) by truncation,
+ * max = 255, 65535 or 1.0f, repeated in three channels when there are at least 3, and max in the last of 4.  lower and upper
+ * both NaN: the layer's minCoeffOfFinites / maxCoeffOfFinites (the same on every run).  image holds cap_bytes bytes; fewer
+ * than rows x cols x channels x element size: LIO_ERR_ARG, image untouched.  Also LIO_ERR_ARG (the reference divides by zero
+ * and casts NaN there): !(upper > lower), a non-finite upper - lower, one bound NaN alone, automatic bounds on a layer without
+ * a finite cell or whose extremes are equal.  Two host waits with automatic bounds (the bounds decide the refusal), else one. */
+int  lio_grid_to_image(lio_grid *g, int32_t layer, int32_t channels, int32_t depth, float lower, float upper, void *image,
+                       size_t cap_bytes, lio_grid_image_info *info);
+/* addLayerFromImage<Type, NChannels> (:58-119) into layer `layer`: replaced when present, the other layers untouched.  A
+ * cell whose alpha (the last of 4 channels) is below (Type)(alpha_threshold * max) stays NaN; otherwise it is
+ * lower + (upper - lower) * ((float)v / max), v the single channel or, for 3 and 4 channels, the grey value
+ * (c0 * 1868 + c1 * 9617 + c2 * 4899 + 8192) >> 14 (cvtColor's BGR2GRAY as published, unpinned; equal channels return the
+ * channel exactly).  A grid that holds layers must have the image's size; one that holds none takes rows, cols, resolution
+ * and position as initializeFromImage does (length = resolution * size).  LIO_ERR_ARG: channels other than 1, 3, 4 (the
+ * reference reads 2 channels as garbage), 32F with more than one channel, alpha_threshold outside [0, 1], a size that does
+ * not match, on an empty grid what lio_grid_set_layers refuses of a geometry. */
+int  lio_grid_add_layer_from_image(lio_grid *g, int32_t layer, const void *image, int32_t rows, int32_t cols, int32_t channels,
+                                   int32_t depth, float lower, float upper, double alpha_threshold, double resolution,
+                                   const double position[2], lio_grid_from_image_info *info);
+/* addColorLayerFromImage<unsigned char, NChannels> (:128-159): 8U with 3 or 4 channels; the cell is the word
+ * (c0 << 16) + (c1 << 8) + c2 read as a float (colorVectorToValue).  As written, with 4 channels c0 and c2 are swapped first
+ * (cvtColor BGRA2RGB), with 3 they are not.  Geometry as above. */
+int  lio_grid_add_color_layer_from_image(lio_grid *g, int32_t layer, const void *image, int32_t rows, int32_t cols,
+                                         int32_t channels, int32_t depth, double resolution, const double position[2],
+                                         lio_grid_from_image_info *info);
+/* fromOccupancyGrid (GridMapRosConverter.cpp:283-327) into layer `layer`: cell i (column-major linear index) takes
+ * data[n - 1 - i], -1 as NaN; length = (double)resolution * (width, height), position = origin + 0.5 * length.  Where size,
+ * resolution, length or position differ from the grid's (or it holds no layers) the geometry is replaced and every layer it
+ * held reads NaN at the new size (setGeometry's clearAll).  LIO_ERR_ARG: width * height != n, width or height below 1 or at
+ * or above 2^24, a resolution below 1e-4 or not finite, a non-finite origin.  With lio_grid_to_occupancy(layer, 0, 100)
+ * this is the reference's round trip. */
+int  lio_grid_from_occupancy(lio_grid *g, int32_t layer, const int8_t *data, size_t n, uint32_t width, uint32_t height,
+                             float resolution, const double origin[2], lio_grid_from_occupancy_info *info);
+/* toPointCloud (:124-223).  layer_ids: the distinct layers whose fields a point carries, in this order: point_layer gives
+ * x, y, z, every other layer one float; *n_fields (may be NULL) receives their number F.  point_layer need not be listed.
+ * basic_mask (bit k: layer k) stands for basicLayers_; 0: no validity test.  A cell stays iff every basic layer and the
+ * point layer are finite there; x and y are getPositionFromIndex's doubles narrowed to float, z the point layer's value,
+ * the other fields the layers' words unchanged.  Survivors keep the iterator's order.  points holds cap_points records of F
+ * floats; *n_out receives the count.  More survivors than cap_points: LIO_ERR_CAPACITY, *n_out set, points untouched.
+ * LIO_ERR_ARG: n_layers outside 1 .. 16, an id repeated or absent, an absent point_layer, a basic_mask bit of an absent layer. */
+int  lio_grid_to_point_cloud(lio_grid *g, int32_t point_layer, const int32_t *layer_ids, int32_t n_layers, uint32_t basic_mask,
+                             float *points, size_t cap_points, size_t *n_out, int32_t *n_fields);
+/* toGridCells (:367-388): the centres, as pairs of doubles in the iterator's order, of the cells of `layer` that are finite
+ * and >= lower && <= upper, compared in float.  Capacity as above.  A NaN bound is LIO_ERR_ARG. */
+int  lio_grid_to_grid_cells(lio_grid *g, int32_t layer, float lower, float upper, double *cells, size_t cap_cells, size_t *n_out);
+/* toPointCloud(SignedDistanceField) (:225-281) over filterPoints (SignedDistanceField.cpp:186-196): every decimation-th node
+ * along z, then y, then x (x fastest) whose distance lies in [lower, upper] (a NaN bound: none on that side) as
+ * {x, y, z, intensity}: nodePosition's doubles narrowed to float and the distance.  Only the kept nodes come down.  Capacity
+ * as above.  LIO_ERR_ARG: no field in the object, decimation below 1. */
+int  lio_sdf_to_point_cloud(lio_sdf *sdf, int32_t decimation, float lower, float upper, float *points, size_t cap_points,
+                            size_t *n_out);
+/* Measurement hook (tools/grid_convert_cost.py), as lio_grid_debug_stage_ms: the calling thread's last call of the seven as
+ * its first stage (the extremes; count and scan; the image up), its second (the image kernel; emit; the ingest kernel) and the
+ * result down, in milliseconds (0 for a stage that did not run).  use_tiled != 0 makes the image entries of the calling thread
+ * launch their LDS-tiled kernels instead of the direct ones they run by default, for comparison (the same bytes). */
+int  lio_grid_convert_debug_stage_ms(int32_t enable, int32_t use_tiled, float ms[3]);
+
 #ifdef __cplusplus
 }
 #endif

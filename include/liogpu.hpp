@@ -461,6 +461,47 @@ public:
     {
         check(lio_grid_add_data_from(g_, other.g_, extend_map ? 1 : 0, overwrite_data ? 1 : 0, layer_ids, n_layers, basic_mask, info), "lio_grid_add_data_from");
     }
+    // GridMapCvConverter::toImage<Type, NChannels>: depth LIO_IMAGE_*; lower = upper = NAN: the layer's finite extremes
+    void toImage(int32_t layer, int32_t channels, int32_t depth, float lower, float upper, void* image, size_t cap_bytes, lio_grid_image_info* info = nullptr)
+    {
+        check(lio_grid_to_image(g_, layer, channels, depth, lower, upper, image, cap_bytes, info), "lio_grid_to_image");
+    }
+    // GridMapCvConverter::addLayerFromImage; a grid without layers takes its geometry from the call (initializeFromImage)
+    void addLayerFromImage(int32_t layer, const void* image, int32_t rows, int32_t cols, int32_t channels, int32_t depth, float lower = 0.0f,
+                           float upper = 1.0f, double alpha_threshold = 0.5, double resolution = 0.0, const double* position = nullptr,
+                           lio_grid_from_image_info* info = nullptr)
+    {
+        check(lio_grid_add_layer_from_image(g_, layer, image, rows, cols, channels, depth, lower, upper, alpha_threshold, resolution, position, info),
+              "lio_grid_add_layer_from_image");
+    }
+    // GridMapCvConverter::addColorLayerFromImage (8U, 3 or 4 channels)
+    void addColorLayerFromImage(int32_t layer, const void* image, int32_t rows, int32_t cols, int32_t channels, double resolution = 0.0,
+                                const double* position = nullptr, lio_grid_from_image_info* info = nullptr)
+    {
+        check(lio_grid_add_color_layer_from_image(g_, layer, image, rows, cols, channels, LIO_IMAGE_8U, resolution, position, info),
+              "lio_grid_add_color_layer_from_image");
+    }
+    // GridMapRosConverter::fromOccupancyGrid into `layer`
+    void fromOccupancyGrid(int32_t layer, const int8_t* data, size_t n, uint32_t width, uint32_t height, float resolution, const double origin[2],
+                           lio_grid_from_occupancy_info* info = nullptr)
+    {
+        check(lio_grid_from_occupancy(g_, layer, data, n, width, height, resolution, origin, info), "lio_grid_from_occupancy");
+    }
+    // GridMapRosConverter::toPointCloud / toGridCells: return LIO_ERR_CAPACITY (no throw) when the buffer is too small, with
+    // *n_out the need
+    int toPointCloud(int32_t point_layer, const int32_t* layer_ids, int32_t n_layers, uint32_t basic_mask, float* points, size_t cap_points, size_t* n_out,
+                     int32_t* n_fields = nullptr)
+    {
+        const int rc = lio_grid_to_point_cloud(g_, point_layer, layer_ids, n_layers, basic_mask, points, cap_points, n_out, n_fields);
+        if (rc != LIO_ERR_CAPACITY) check(rc, "lio_grid_to_point_cloud");
+        return rc;
+    }
+    int toGridCells(int32_t layer, float lower, float upper, double* cells, size_t cap_cells, size_t* n_out)
+    {
+        const int rc = lio_grid_to_grid_cells(g_, layer, lower, upper, cells, cap_cells, n_out);
+        if (rc != LIO_ERR_CAPACITY) check(rc, "lio_grid_to_grid_cells");
+        return rc;
+    }
     void layer(int32_t k, float* out, size_t cap_floats) { check(lio_grid_get_layer(g_, k, out, cap_floats), "lio_grid_get_layer"); }
     lio_grid_desc info()
     {

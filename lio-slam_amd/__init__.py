@@ -25,7 +25,8 @@ from .api import (LioError, ScanToMap, S2MConfig, S2MResult, S2MProfile, DeskewC
                   grid_region_default_config, pack_regions, footprint_polygons, REGION_LINE, REGION_CIRCLE, REGION_ELLIPSE, REGION_POLYGON,
                   REGION_OK, REGION_EMPTY, REGION_INVALID, REGION_MAX_VERTICES, REGION_MAX_WALK,
                   GRID_TRANSFORM_INFO_DTYPE, GRID_OCCUPANCY_DESC_DTYPE, GRID_TRANSFORM_MAX_SOURCE_CELLS,
-                  GRID_SUBMAP_INFO_DTYPE, GRID_MOVE_INFO_DTYPE, GRID_EXTEND_INFO_DTYPE, GRID_ADD_INFO_DTYPE)
+                  GRID_SUBMAP_INFO_DTYPE, GRID_MOVE_INFO_DTYPE, GRID_EXTEND_INFO_DTYPE, GRID_ADD_INFO_DTYPE,
+                  GRID_IMAGE_INFO_DTYPE, GRID_FROM_IMAGE_INFO_DTYPE, GRID_FROM_OCCUPANCY_INFO_DTYPE, IMAGE_8U, IMAGE_16U, IMAGE_32F)
 
 __all__ = ["LioError", "ScanToMap", "S2MConfig", "S2MResult", "S2MProfile", "DeskewConfig",
            "lib_path", "load_library", "build_library", "deskew", "curvature", "imu_deskew_info",
@@ -47,4 +48,5 @@ __all__ = ["LioError", "ScanToMap", "S2MConfig", "S2MResult", "S2MProfile", "Des
            "grid_region_default_config", "pack_regions", "footprint_polygons", "REGION_LINE", "REGION_CIRCLE", "REGION_ELLIPSE", "REGION_POLYGON",
            "REGION_OK", "REGION_EMPTY", "REGION_INVALID", "REGION_MAX_VERTICES", "REGION_MAX_WALK",
            "GRID_TRANSFORM_INFO_DTYPE", "GRID_OCCUPANCY_DESC_DTYPE", "GRID_TRANSFORM_MAX_SOURCE_CELLS",
-           "GRID_SUBMAP_INFO_DTYPE", "GRID_MOVE_INFO_DTYPE", "GRID_EXTEND_INFO_DTYPE", "GRID_ADD_INFO_DTYPE"]
+           "GRID_SUBMAP_INFO_DTYPE", "GRID_MOVE_INFO_DTYPE", "GRID_EXTEND_INFO_DTYPE", "GRID_ADD_INFO_DTYPE",
+           "GRID_IMAGE_INFO_DTYPE", "GRID_FROM_IMAGE_INFO_DTYPE", "GRID_FROM_OCCUPANCY_INFO_DTYPE", "IMAGE_8U", "IMAGE_16U", "IMAGE_32F"]

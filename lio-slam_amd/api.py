@@ -308,6 +308,18 @@ GRID_ADD_INFO_DTYPE = np.dtype({"names": ["resized", "rows", "cols", "pad", "len
                                           "n_index_outside", "n_values_copied"],
                                 "formats": [np.int32, np.int32, np.int32, np.int32, (np.float64, 2), (np.float64, 2), np.int64, np.int64, np.int64, np.int64],
                                 "offsets": [0, 4, 8, 12, 16, 32, 48, 56, 64, 72], "itemsize": 80})
+# lio_grid_image_info, lio_grid_from_image_info and lio_grid_from_occupancy_info (tests/test_grid_convert_capi.py holds the
+# layouts to gcc's)
+GRID_IMAGE_INFO_DTYPE = np.dtype({"names": ["rows", "cols", "lower", "upper", "n_pixels", "n_clamped_low", "n_clamped_high", "n_nonfinite"],
+                                  "formats": [np.int32, np.int32, np.float32, np.float32, np.int64, np.int64, np.int64, np.int64],
+                                  "offsets": [0, 4, 8, 12, 16, 24, 32, 40], "itemsize": 48})
+GRID_FROM_IMAGE_INFO_DTYPE = np.dtype({"names": ["rows", "cols", "geometry_set", "pad", "n_cells_set", "n_cells_transparent"],
+                                       "formats": [np.int32, np.int32, np.int32, np.int32, np.int64, np.int64], "offsets": [0, 4, 8, 12, 16, 24], "itemsize": 32})
+GRID_FROM_OCCUPANCY_INFO_DTYPE = np.dtype({"names": ["rows", "cols", "geometry_replaced", "pad", "length", "position", "n_unknown"],
+                                           "formats": [np.int32, np.int32, np.int32, np.int32, (np.float64, 2), (np.float64, 2), np.int64],
+                                           "offsets": [0, 4, 8, 12, 16, 32, 48], "itemsize": 56})
+IMAGE_8U, IMAGE_16U, IMAGE_32F = 0, 1, 2
+IMAGE_DTYPES = {IMAGE_8U: np.uint8, IMAGE_16U: np.uint16, IMAGE_32F: np.float32}
 REGION_LINE, REGION_CIRCLE, REGION_ELLIPSE, REGION_POLYGON = 0, 1, 2, 3
 REGION_OK, REGION_EMPTY, REGION_INVALID = 0, 1, 2
 REGION_MAX_VERTICES, REGION_MAX_WALK = 64, 4096
@@ -490,6 +502,14 @@ CAPI = {
     "lio_grid_extend_to_include": [vp, vp, vp],
     "lio_grid_add_data_from": [vp, vp, i32, i32, pi, i32, C.c_uint32, vp],
     "lio_grid_geom_debug_kernel_ms": [i32, pf],
+    "lio_grid_to_image": [vp, i32, i32, i32, f32, f32, vp, sz, vp],
+    "lio_grid_add_layer_from_image": [vp, i32, vp, i32, i32, i32, i32, f32, f32, f64, f64, pd, vp],
+    "lio_grid_add_color_layer_from_image": [vp, i32, vp, i32, i32, i32, i32, f64, pd, vp],
+    "lio_grid_from_occupancy": [vp, i32, vp, sz, C.c_uint32, C.c_uint32, f32, pd, vp],
+    "lio_grid_to_point_cloud": [vp, i32, pi, i32, C.c_uint32, vp, sz, psz, pi],
+    "lio_grid_to_grid_cells": [vp, i32, f32, f32, vp, sz, psz],
+    "lio_sdf_to_point_cloud": [vp, i32, f32, f32, vp, sz, psz],
+    "lio_grid_convert_debug_stage_ms": [i32, i32, pf],
 }
 CAPI = {name: sig if isinstance(sig, tuple) else (C.c_int, sig) for name, sig in CAPI.items()}     # -> (restype, argtypes), all of them
 EXPORTS = list(CAPI)
@@ -1393,6 +1413,23 @@ class Sdf(_Owner):
         _check(self.lib.lio_sdf_query(self.h, p.ctypes.data, len(p), val.ctypes.data, der.ctypes.data if want_derivative else None), "lio_sdf_query")
         return val, der
 
+    def to_point_cloud(self, decimation=1, lower=float("nan"), upper=float("nan"), cap_points=None):
+        """GridMapRosConverter::toPointCloud(SignedDistanceField) -> [n, 4] float32 {x, y, z, distance}: every decimation-th
+        node whose distance lies in [lower, upper] (NaN: no bound on that side), z, then y, then x.  cap_points None: asks for
+        the count first, then for the points; only the kept nodes cross PCIe."""
+        n = C.c_size_t()
+
+        def call(out):
+            return self.lib.lio_sdf_to_point_cloud(self.h, int(decimation), float(lower), float(upper), out.ctypes.data if out.size else None, len(out),
+                                                   C.byref(n))
+        out = np.zeros((0 if cap_points is None else int(cap_points), 4), np.float32)
+        rc = call(out)
+        if rc == -3 and cap_points is None:                                     # LIO_ERR_CAPACITY: n tells the need
+            out = np.zeros((n.value, 4), np.float32)
+            rc = call(out)
+        _check(rc, "lio_sdf_to_point_cloud")
+        return out[:n.value]
+
     def memory(self):
         """-> (bytes of the field, bytes of the build's workspace) the object holds on the device"""
         field, work = C.c_size_t(), C.c_size_t()
@@ -1619,6 +1656,90 @@ class Grid(_Owner):
                                                ids.ctypes.data_as(C.POINTER(C.c_int32)) if len(ids) else None, len(ids), mask, info.ctypes.data),
                "lio_grid_add_data_from")
         return info[0]
+
+    @staticmethod
+    def _image_in(image):
+        """-> (contiguous [rows, cols, channels] array, channels, depth code)"""
+        a = np.asarray(image)
+        if a.ndim == 2:
+            a = a[:, :, None]
+        depth = {np.dtype(np.uint8): IMAGE_8U, np.dtype(np.uint16): IMAGE_16U, np.dtype(np.float32): IMAGE_32F}.get(a.dtype)
+        if a.ndim != 3 or depth is None:
+            raise ValueError("image must be [rows, cols] or [rows, cols, channels] of uint8, uint16 or float32")
+        return np.ascontiguousarray(a), a.shape[2], depth
+
+    def to_image(self, layer, channels=1, depth=IMAGE_8U, lower=float("nan"), upper=float("nan")):
+        """GridMapCvConverter::toImage -> ([rows, cols, channels] uint8 / uint16 / float32, a GRID_IMAGE_INFO_DTYPE record).
+        lower and upper both NaN: the layer's finite extremes."""
+        i = self.info()
+        img = np.zeros((i.rows, i.cols, int(channels) if channels in (1, 3, 4) else 1), IMAGE_DTYPES.get(depth, np.uint8))
+        info = np.zeros(1, GRID_IMAGE_INFO_DTYPE)
+        _check(self.lib.lio_grid_to_image(self.h, int(layer), int(channels), int(depth), float(lower), float(upper), img.ctypes.data, img.nbytes,
+                                          info.ctypes.data), "lio_grid_to_image")
+        return img, info[0]
+
+    def add_layer_from_image(self, layer, image, lower=0.0, upper=1.0, alpha_threshold=0.5, resolution=0.0, position=(0.0, 0.0)):
+        """GridMapCvConverter::addLayerFromImage into layer `layer`; a grid without layers takes its geometry from the image's
+        size, `resolution` and `position` (initializeFromImage).  -> a GRID_FROM_IMAGE_INFO_DTYPE record"""
+        a, channels, depth = self._image_in(image)
+        ps = (C.c_double * 2)(*position)
+        info = np.zeros(1, GRID_FROM_IMAGE_INFO_DTYPE)
+        _check(self.lib.lio_grid_add_layer_from_image(self.h, int(layer), a.ctypes.data, a.shape[0], a.shape[1], channels, depth, float(lower), float(upper),
+                                                      float(alpha_threshold), float(resolution), ps, info.ctypes.data), "lio_grid_add_layer_from_image")
+        return info[0]
+
+    def add_color_layer_from_image(self, layer, image, resolution=0.0, position=(0.0, 0.0)):
+        """GridMapCvConverter::addColorLayerFromImage (uint8, 3 or 4 channels): the cells hold (c0 << 16) + (c1 << 8) + c2 as
+        a float's bits.  -> a GRID_FROM_IMAGE_INFO_DTYPE record"""
+        a, channels, depth = self._image_in(image)
+        ps = (C.c_double * 2)(*position)
+        info = np.zeros(1, GRID_FROM_IMAGE_INFO_DTYPE)
+        _check(self.lib.lio_grid_add_color_layer_from_image(self.h, int(layer), a.ctypes.data, a.shape[0], a.shape[1], channels, depth, float(resolution), ps,
+                                                            info.ctypes.data), "lio_grid_add_color_layer_from_image")
+        return info[0]
+
+    def from_occupancy(self, layer, data, width, height, resolution, origin):
+        """GridMapRosConverter::fromOccupancyGrid into layer `layer`: data [width * height] int8 in the message's order.
+        -> a GRID_FROM_OCCUPANCY_INFO_DTYPE record"""
+        d = np.ascontiguousarray(data, np.int8).reshape(-1)
+        og = (C.c_double * 2)(*origin)
+        info = np.zeros(1, GRID_FROM_OCCUPANCY_INFO_DTYPE)
+        _check(self.lib.lio_grid_from_occupancy(self.h, int(layer), d.ctypes.data, d.size, int(width), int(height), float(resolution), og, info.ctypes.data),
+               "lio_grid_from_occupancy")
+        return info[0]
+
+    def _compacted(self, what, call, fields, dtype, cap):
+        """asks for the count first when cap is None (LIO_ERR_CAPACITY tells the need), then for the records"""
+        n = C.c_size_t()
+        out = np.zeros((0 if cap is None else int(cap), fields), dtype)
+        rc = call(out, n)
+        if rc == -3 and cap is None:
+            out = np.zeros((n.value, fields), dtype)
+            rc = call(out, n)
+        _check(rc, what)
+        return out[:n.value]
+
+    def to_point_cloud(self, point_layer, layer_ids=None, basic_layers=(), cap_points=None):
+        """GridMapRosConverter::toPointCloud -> [n, F] float32 in the iterator's order: point_layer gives x, y, z, every other
+        listed layer one field (its words unchanged).  layer_ids None: every layer the grid holds, ascending."""
+        held = self.info().layer_mask
+        ids = np.ascontiguousarray([k for k in range(GRID_MAX_LAYERS) if (held >> k) & 1] if layer_ids is None else layer_ids, np.int32).reshape(-1)
+        mask = 0
+        for k in basic_layers:
+            mask |= 1 << int(k)
+        fields = sum(3 if int(k) == int(point_layer) else 1 for k in ids)
+        nf = C.c_int32()
+
+        def call(out, n):
+            return self.lib.lio_grid_to_point_cloud(self.h, int(point_layer), ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids), mask,
+                                                    out.ctypes.data if out.size else None, len(out), C.byref(n), C.byref(nf))
+        return self._compacted("lio_grid_to_point_cloud", call, max(fields, 1), np.float32, cap_points)
+
+    def to_grid_cells(self, layer, lower, upper, cap_cells=None):
+        """GridMapRosConverter::toGridCells -> [n, 2] float64: the centres of the cells of `layer` within [lower, upper]"""
+        def call(out, n):
+            return self.lib.lio_grid_to_grid_cells(self.h, int(layer), float(lower), float(upper), out.ctypes.data if out.size else None, len(out), C.byref(n))
+        return self._compacted("lio_grid_to_grid_cells", call, 2, np.float64, cap_cells)
 
     def memory(self):
         """-> bytes the object holds on the device"""

@@ -265,6 +265,8 @@ LIO_GS_HD int lio_gs_eval(const LioTerrGeom& G, const LioGsQuery& Q, int method,
 int lio_grid_begin(lio_grid* g, int device_id);
 // The object holds no layer (its memory stays).
 void lio_grid_clear(lio_grid* g);
+// What lio_grid_set_geometry refuses, with the object untouched: LIO_OK, LIO_ERR_ARG or LIO_ERR_CAPACITY.
+int lio_grid_geometry_check(int rows, int cols, double resolution, const double* length, const double* position);
 // The geometry of the layers to come, checked as the upload's: LIO_ERR_ARG / LIO_ERR_CAPACITY as include/liogpu.h lists.
 int lio_grid_set_geometry(lio_grid* g, int rows, int cols, double resolution, const double length[2], const double position[2]);
 // Slot `layer` of the object, grown to the geometry's cells and marked present: where a chain copies or writes that layer on

@@ -87,19 +87,6 @@ struct GsClock {                   // four marks around the three stages, only w
     }
 };
 
-int grid_geometry_check(int rows, int cols, double resolution, const double* length, const double* position)
-{
-    if (rows < 1 || cols < 1) return lio_fail(LIO_ERR_ARG, "rows and cols must be at least 1");
-    if (rows >= LIO_GS_MAX_LINE || cols >= LIO_GS_MAX_LINE) return lio_fail(LIO_ERR_ARG, "rows and cols must be below 2^24");
-    if (!std::isfinite(resolution) || resolution < 1e-4) return lio_fail(LIO_ERR_ARG, "resolution must be finite and at least 1e-4");
-    for (int a = 0; a < 2; ++a) {
-        if (!std::isfinite(length[a]) || !std::isfinite(position[a])) return lio_fail(LIO_ERR_ARG, "length and position must be finite");
-        if (length[a] != (double)(a == 0 ? rows : cols) * resolution) return lio_fail(LIO_ERR_ARG, "length must be size * resolution (GridMap::setGeometry)");
-    }
-    if ((long long)rows * cols > 0x7fffffffLL - 1024) return lio_fail(LIO_ERR_CAPACITY, "a layer has more than 2^31 - 1024 cells");
-    return LIO_OK;
-}
-
 void grid_apply_geometry(lio_grid* g, int rows, int cols, double resolution, const double* length, const double* position)
 {
     LioTerrGeom& G = g->G;
@@ -112,6 +99,19 @@ void grid_apply_geometry(lio_grid* g, int rows, int cols, double resolution, con
 }
 
 }  // namespace
+
+int lio_grid_geometry_check(int rows, int cols, double resolution, const double* length, const double* position)
+{
+    if (rows < 1 || cols < 1) return lio_fail(LIO_ERR_ARG, "rows and cols must be at least 1");
+    if (rows >= LIO_GS_MAX_LINE || cols >= LIO_GS_MAX_LINE) return lio_fail(LIO_ERR_ARG, "rows and cols must be below 2^24");
+    if (!std::isfinite(resolution) || resolution < 1e-4) return lio_fail(LIO_ERR_ARG, "resolution must be finite and at least 1e-4");
+    for (int a = 0; a < 2; ++a) {
+        if (!std::isfinite(length[a]) || !std::isfinite(position[a])) return lio_fail(LIO_ERR_ARG, "length and position must be finite");
+        if (length[a] != (double)(a == 0 ? rows : cols) * resolution) return lio_fail(LIO_ERR_ARG, "length must be size * resolution (GridMap::setGeometry)");
+    }
+    if ((long long)rows * cols > 0x7fffffffLL - 1024) return lio_fail(LIO_ERR_CAPACITY, "a layer has more than 2^31 - 1024 cells");
+    return LIO_OK;
+}
 
 void lio_grid_clear(lio_grid* g)
 {
@@ -129,7 +129,7 @@ int lio_grid_begin(lio_grid* g, int device_id)
 int lio_grid_set_geometry(lio_grid* g, int rows, int cols, double resolution, const double length[2], const double position[2])
 {
     lio_grid_clear(g);
-    const int rc = grid_geometry_check(rows, cols, resolution, length, position);
+    const int rc = lio_grid_geometry_check(rows, cols, resolution, length, position);
     if (rc != LIO_OK) return rc;
     grid_apply_geometry(g, rows, cols, resolution, length, position);
     return LIO_OK;
@@ -177,7 +177,7 @@ extern "C" int lio_grid_set_layers(lio_grid* g, const float* layers, int32_t n_l
 try {
     if (!length || !position) return lio_fail(LIO_ERR_ARG, "null argument");
     if (n_layers < 1 || n_layers > LIO_GRID_MAX_LAYERS) return lio_fail(LIO_ERR_ARG, "n_layers must be in [1, LIO_GRID_MAX_LAYERS]");
-    int rc = grid_geometry_check(rows, cols, resolution, length, position);
+    int rc = lio_grid_geometry_check(rows, cols, resolution, length, position);
     if (rc != LIO_OK) return rc;
     if (!g || !layers) return lio_fail(LIO_ERR_ARG, "null argument");
     if ((rc = lio_check_device(g->device_id)) != LIO_OK) return rc;

@@ -24,24 +24,13 @@
 #include <vector>
 
 #include "lio_sdf.h"
+#include "lio_sdfobj.h"
 #include "lio_cloud.h"
 #include "lio_planning.h"
 #include "lio_pool.h"
 #include "lio_wg.h"
 
 #define SDF_CHUNK 32               // entries of a line staged per flush of k_sdf_cols; the rows a wave of k_sdf_rows owns
-
-struct lio_sdf {
-    int device_id = 0;
-    bool built = false;
-    LioSdfLookup L{};
-    LioDevBuf<float> d_elev;       // the host grid of lio_sdf_build on its way in
-    LioDevBuf<float> d_dist;       // [layer][col][row]
-    LioDevBuf<float4> d_nodes;     // the same order
-    LioDevBuf<float> d_mid;        // a slab's intermediate [col][2 slab][row]
-    LioDevBuf<uint2> d_stack;      // the lines' lower bounds, [depth][line]
-    LioDevBuf<unsigned> d_stats;   // min, max (ordered words), non-finite cells
-};
 
 namespace {
 
