@@ -1,11 +1,12 @@
 // lio_cloud.h -- what every chain over a device-resident float4 cloud (x, y, z, intensity) shares, defined in lio_cloud.hip:
-// the device check, the record conversions in and out, the upload of a host cloud, the box pass and K7 (pcl::VoxelGrid by
-// sorting, kernels in lio_voxsort.h).
+// the device check, the record conversions in and out, the upload of a host cloud, the box pass, the cloud laid out as its
+// own search target and K7 (pcl::VoxelGrid by sorting, kernels in lio_voxsort.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
 
 #include "lio_pool.h"
+#include "lio_types.h"
 
 #define LIO_VS_THREADS 256
 #define LIO_VS_BINS 256
@@ -59,6 +60,22 @@ int lio_copy_out(const float4* d_pts, int n, void* out, size_t out_stride, hipSt
 // (k_transform_clouds_bbox) takes the second alone: clear + k_vox_bbox, then the copy, the wait and the decoding.
 template <class B> int lio_cloud_box_launch(const float4* d_in, int n, B& bbox, hipStream_t s);
 template <class B> int lio_cloud_box_wait(B& bbox, float mn[3], float mx[3], hipStream_t s);
+
+// A cloud as its own search target (the loop-closure alignment, the outlier filter, the radius filter): the cloud as SoA and
+// as (x, y, z, 0), a uniform grid over the box of the coordinates that take part, the cloud cell-sorted into it.
+struct LioSearchTarget {
+    LioTemp tx, ty, tz, t4;
+    LioTemp cell_of, cell_count, cell_start, tiles, sorted;
+    LioGrid g;                // the caller's choice between the two steps
+    float edge = 1.0f;
+    bool any = false;         // the box holds a point on every axis
+    int occupied = -1;        // occupied cells of a trial grid (-1: none was laid)
+};
+// n > 0 points: the SoA copy, then the box of the coordinates within LIO_MAX_COORD (per axis) -> mn / mx and T.any, under one
+// host wait.  Without a point on some axis mn / mx are not a box: the caller's rule decides what follows.
+int lio_search_target_box(const float4* d_pts, int n, hipStream_t s, LioSearchTarget& T, float mn[3], float mx[3]);
+// the cell sort into T.g: T.cell_start (n_cells + 1) and T.sorted (x, y, z, bits(index in the caller's order)); nothing waits
+int lio_search_target_sort(int n, hipStream_t s, LioSearchTarget& T);
 
 // Room for sorting n pairs and summing their segments (ws) and for n centroids (out).
 template <class B> int lio_vsort_reserve(int n, B& out, LioVoxWs<B>& ws);

@@ -1,10 +1,11 @@
 // lio_cloud.hip -- what every chain over a device-resident float4 cloud uses (lio_cloud.h): the record conversions and the
-// upload of a host cloud, the box pass (pcl::getMinMax3D) and K7, the pcl::VoxelGrid centroid filter of MO:1605-1611 (scan) and
+// upload of a host cloud, the box pass (pcl::getMinMax3D), the cloud as its own search target (box step, cell sort) and K7, the pcl::VoxelGrid centroid filter of MO:1605-1611 (scan) and
 // MO:1581-1583 (local map) with its kernels in lio_voxsort.h; lio_voxel_grid is nothing more than these.
 // MO = the reference's src/liorf/src/mapOptmization.cpp.  -ffp-contract=off.
 #include <hip/hip_runtime.h>
 
 #include "lio_cloud.h"
+#include "lio_kernels.h"
 #include "lio_voxsort.h"
 
 // getMinMax3D (PCL): bbox[0..2] = min, bbox[3..5] = max as order-preserving uints
@@ -154,6 +155,38 @@ int lio_cloud_box_wait(B& bbox, float mn[3], float mx[3], hipStream_t s)
     HIPCHK(hipMemcpyAsync(hb, bbox.p, sizeof(hb), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     lio_ord_box_decode(hb, mn, mx);
+    return LIO_OK;
+}
+
+int lio_search_target_box(const float4* d_pts, int n, hipStream_t s, LioSearchTarget& T, float mn[3], float mx[3])
+{
+    LioTemp bbox;
+    HIPCHK(T.tx.alloc(sizeof(float) * (size_t)n)); HIPCHK(T.ty.alloc(sizeof(float) * (size_t)n)); HIPCHK(T.tz.alloc(sizeof(float) * (size_t)n));
+    HIPCHK(T.t4.alloc(sizeof(float4) * (size_t)n));
+    HIPCHK(bbox.alloc(6 * sizeof(unsigned)));
+    lio_launch_xyzi4_to_soa(d_pts, n, T.tx.as<float>(), T.ty.as<float>(), T.tz.as<float>(), T.t4.as<float4>(), s);
+    unsigned hb[6];
+    lio_ord_box_clear(hb);
+    HIPCHK(hipMemcpyAsync(bbox.p, hb, sizeof(hb), hipMemcpyHostToDevice, s));
+    lio_launch_map_bbox(T.tx.as<float>(), T.ty.as<float>(), T.tz.as<float>(), n, bbox.as<unsigned>(), s);
+    HIPCHK(hipMemcpyAsync(hb, bbox.p, sizeof(hb), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    lio_ord_box_decode(hb, mn, mx);
+    T.any = true;
+    for (int a = 0; a < 3; ++a) T.any = T.any && hb[a] != LIO_ORD_NO_MIN && mn[a] <= mx[a];
+    return LIO_OK;
+}
+
+int lio_search_target_sort(int n, hipStream_t s, LioSearchTarget& T)
+{
+    const LioGrid& g = T.g;
+    HIPCHK(T.cell_of.alloc(sizeof(int) * (size_t)n));
+    HIPCHK(T.cell_count.alloc(sizeof(int) * (size_t)g.n_cells));
+    HIPCHK(T.cell_start.alloc(sizeof(int) * ((size_t)g.n_cells + 1)));
+    HIPCHK(T.tiles.alloc(sizeof(int) * ((size_t)lio_scan_tiles(g.n_cells) + 2)));
+    HIPCHK(T.sorted.alloc(sizeof(float4) * (size_t)n));
+    lio_launch_map_cell_sort(g, T.tx.as<float>(), T.ty.as<float>(), T.tz.as<float>(), n, T.cell_of.as<int>(), T.cell_count.as<int>(),
+                             T.cell_start.as<int>(), T.tiles.as<int>(), T.sorted.as<float4>(), s);
     return LIO_OK;
 }
 

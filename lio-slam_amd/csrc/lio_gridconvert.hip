@@ -40,12 +40,6 @@ namespace {
 
 enum { GC_CNT_A = 0, GC_CNT_B, GC_CNT_C, GC_N_CNT };      // to_image: clamped low, clamped high, non-finite; ingest: transparent / unknown
 
-__device__ __forceinline__ void gc_count(unsigned long long* counters, int which, bool flag)
-{
-    const unsigned long long m = __ballot(flag);
-    if ((threadIdx.x & 63) == 0 && m) atomicAdd(&counters[which], (unsigned long long)__popcll(m));
-}
-
 struct GcTileLine {                // a line of the tile: pixel -> word
     const unsigned* p;
     __device__ __forceinline__ unsigned at(int pixel) const { return p[pixel]; }
@@ -74,9 +68,9 @@ __global__ __launch_bounds__(256) void k_gc_to_image(const float* __restrict__ l
     for (int c = wave; c < LIO_GC_TILE; c += 4) {            // (the whole wave stays for the ballots)
         int cls = LIO_GC_IN_RANGE;
         if (lane < nr && c < nc) s_tile[lane * LIO_GC_PITCH + c] = lio_gc_pixel(layer[(size_t)(c0 + c) * (size_t)rows + (size_t)(r0 + lane)], lo, hi, depth, &cls);
-        gc_count(counters, GC_CNT_A, cls == LIO_GC_CLAMPED_LOW);
-        gc_count(counters, GC_CNT_B, cls == LIO_GC_CLAMPED_HIGH);
-        gc_count(counters, GC_CNT_C, cls == LIO_GC_NONFINITE);
+        lio_wave_count(counters, GC_CNT_A, cls == LIO_GC_CLAMPED_LOW);
+        lio_wave_count(counters, GC_CNT_B, cls == LIO_GC_CLAMPED_HIGH);
+        lio_wave_count(counters, GC_CNT_C, cls == LIO_GC_NONFINITE);
     }
     __syncthreads();
     const int px = channels * lio_gc_elem_bytes(depth);
@@ -102,9 +96,9 @@ __global__ __launch_bounds__(256) void k_gc_to_image_direct(const float* __restr
         const int px = channels * lio_gc_elem_bytes(depth);
         for (int b = 0; b < px; ++b) image[(size_t)q * (size_t)px + b] = (unsigned char)lio_gc_pixel_byte(w, b, channels, depth);
     }
-    gc_count(counters, GC_CNT_A, cls == LIO_GC_CLAMPED_LOW);
-    gc_count(counters, GC_CNT_B, cls == LIO_GC_CLAMPED_HIGH);
-    gc_count(counters, GC_CNT_C, cls == LIO_GC_NONFINITE);
+    lio_wave_count(counters, GC_CNT_A, cls == LIO_GC_CLAMPED_LOW);
+    lio_wave_count(counters, GC_CNT_B, cls == LIO_GC_CLAMPED_HIGH);
+    lio_wave_count(counters, GC_CNT_C, cls == LIO_GC_NONFINITE);
 }
 
 __global__ __launch_bounds__(256) void k_gc_from_image(LioGcIngest I, int tiles_r, const unsigned char* __restrict__ image, unsigned* __restrict__ layer,
@@ -119,7 +113,7 @@ __global__ __launch_bounds__(256) void k_gc_from_image(LioGcIngest I, int tiles_
         bool transparent = false;
         if (r < nr && lane < nc)
             s_tile[lane * LIO_GC_PITCH + r] = lio_gc_word_from_pixel(I, image + ((size_t)(r0 + r) * (size_t)I.cols + (size_t)(c0 + lane)) * (size_t)px, &transparent);
-        gc_count(counters, GC_CNT_A, transparent);
+        lio_wave_count(counters, GC_CNT_A, transparent);
     }
     __syncthreads();
     for (int c = wave; c < nc; c += 4)
@@ -136,7 +130,7 @@ __global__ __launch_bounds__(256) void k_gc_from_image_direct(LioGcIngest I, con
         const int px = I.channels * lio_gc_elem_bytes(I.depth);
         layer[i] = lio_gc_word_from_pixel(I, image + ((size_t)r * (size_t)I.cols + (size_t)c) * (size_t)px, &transparent);
     }
-    gc_count(counters, GC_CNT_A, transparent);
+    lio_wave_count(counters, GC_CNT_A, transparent);
 }
 
 struct GcFill { unsigned* p[LIO_GRID_MAX_LAYERS]; int n; };          // the layers setGeometry clears
@@ -152,7 +146,7 @@ __global__ __launch_bounds__(256) void k_gc_occupancy(const int8_t* __restrict__
         layer[i] = w;
         for (int k = 0; k < F.n; ++k) F.p[k][i] = LIO_GC_QNAN;
     }
-    gc_count(counters, GC_CNT_A, unknown);
+    lio_wave_count(counters, GC_CNT_A, unknown);
 }
 
 // ---- the compactions' predicates and sinks --------------------------------------------------------------------------------
@@ -194,37 +188,17 @@ struct GcSdfPred {
     }
 };
 
-thread_local float t_gc_ms[3] = { 0, 0, 0 };
-thread_local bool t_gc_on = false, t_gc_tiled = false;
-
-struct GcClock {                   // four marks around the three stages, only when a caller asked for the times
-    hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
-    int n = 0;
-    bool on = false;
-    GcClock() { on = t_gc_on; t_gc_ms[0] = t_gc_ms[1] = t_gc_ms[2] = 0.0f; }
-    ~GcClock() { for (int k = 0; k < n; ++k) (void)hipEventDestroy(ev[k]); }
-    void mark(hipStream_t s)
-    {
-        if (!on || n >= 4) return;
-        if (hipEventCreate(&ev[n]) != hipSuccess) { on = false; return; }
-        (void)hipEventRecord(ev[n++], s);
-    }
-    void read()                    // after the call's last wait
-    {
-        if (!on || n != 4) return;
-        for (int k = 0; k < 3; ++k)
-            if (hipEventElapsedTime(&t_gc_ms[k], ev[k], ev[k + 1]) != hipSuccess) t_gc_ms[k] = 0.0f;
-    }
-};
-
-bool gc_has_layer(const lio_grid* g, int layer) { return layer >= 0 && layer < LIO_GRID_MAX_LAYERS && ((g->mask >> layer) & 1u); }
+// four marks around the three stages; cleared where a call makes its clock, so a stage that did not run reads 0
+thread_local LioStageTimes<3> t_gc;
+thread_local bool t_gc_tiled = false;
 
 // Count and scan, the one wait for the count, the capacity test, emit into a block of the count's size, the records down.
 template <class Rec, class Pred, class MakeSink>
 int gc_compact_out(const Pred& pred, int n, size_t record_bytes, void* out, size_t cap, size_t* n_out, const MakeSink& make_sink)
 {
     hipStream_t s = nullptr;
-    GcClock clk;
+    t_gc.clear();
+    LioStageClock clk(t_gc.on);
     clk.mark(s);
     LioTemp counts, recs;
     int rc = compact_count<Rec>(pred, n, counts, s);
@@ -244,7 +218,7 @@ int gc_compact_out(const Pred& pred, int n, size_t record_bytes, void* out, size
     clk.mark(s);
     HIPCHK(hipStreamSynchronize(s));                       // (the temporaries go back to the pool after it)
     HIPCHK(hipGetLastError());
-    clk.read();
+    t_gc.read(clk);
     return LIO_OK;
 }
 
@@ -272,41 +246,34 @@ int gc_from_image(lio_grid* g, int layer, const void* image, int rows, int cols,
         if ((rc = lio_grid_geometry_check(rows, cols, resolution, length, position)) != LIO_OK) return rc;
     } else if (g->G.rows != rows || g->G.cols != cols) return lio_fail(LIO_ERR_ARG, "the image's size is not the grid's");
     if ((rc = lio_check_device(g->device_id)) != LIO_OK) return rc;
-    struct Undo {
-        lio_grid* g;
-        unsigned mask;
-        bool empty;
-        ~Undo() { if (g) { if (empty) lio_grid_clear(g); else g->mask = mask; } }
-    } undo = { g, g->mask, empty };
+    LioGridRollback undo(g, empty);                          // after a failure: what it held, nothing where the geometry was set here
     if (empty && (rc = lio_grid_set_geometry(g, rows, cols, resolution, length, position)) != LIO_OK) return rc;
     float* d = nullptr;
     if ((rc = lio_grid_layer_slot(g, layer, &d)) != LIO_OK) return rc;
     hipStream_t s = nullptr;
     const size_t cells = (size_t)rows * (size_t)cols, bytes = cells * (size_t)I.channels * (size_t)lio_gc_elem_bytes(I.depth);
-    LioTemp img, counters;
+    LioTemp img;
+    LioGridCounters counters;
     HIPCHK(img.alloc(bytes));
-    HIPCHK(counters.alloc(GC_N_CNT * sizeof(unsigned long long)));
-    GcClock clk;
+    HIPCHK(counters.alloc(GC_N_CNT));
+    t_gc.clear();
+    LioStageClock clk(t_gc.on);
     clk.mark(s);
     HIPCHK(hipMemcpyAsync(img.p, image, bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(counters.p, 0, GC_N_CNT * sizeof(unsigned long long), s));
+    HIPCHK(counters.clear(s));
     clk.mark(s);
     if (!t_gc_tiled) {
-        hipLaunchKernelGGL(k_gc_from_image_direct, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, I, img.as<unsigned char>(), (unsigned*)d,
-                           counters.as<unsigned long long>());
+        hipLaunchKernelGGL(k_gc_from_image_direct, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, I, img.as<unsigned char>(), (unsigned*)d, counters.d());
     } else {
         const int tiles_r = (rows + LIO_GC_TILE - 1) / LIO_GC_TILE, tiles_c = (cols + LIO_GC_TILE - 1) / LIO_GC_TILE;
         hipLaunchKernelGGL(k_gc_from_image, dim3((unsigned)tiles_r * (unsigned)tiles_c), dim3(256), 0, s, I, tiles_r, img.as<unsigned char>(), (unsigned*)d,
-                           counters.as<unsigned long long>());
+                           counters.d());
     }
     clk.mark(s);
     unsigned long long hc[GC_N_CNT] = { 0, 0, 0 };
-    HIPCHK(hipMemcpyAsync(hc, counters.p, sizeof(hc), hipMemcpyDeviceToHost, s));
-    clk.mark(s);
-    HIPCHK(hipStreamSynchronize(s));                       // the call's one host wait
-    HIPCHK(hipGetLastError());
-    clk.read();
-    undo.g = nullptr;
+    if ((rc = counters.finish(hc, s, &clk)) != LIO_OK) return rc;       // the call's one host wait
+    t_gc.read(clk);
+    undo.commit();
     if (info) {
         info->rows = rows; info->cols = cols;
         info->geometry_set = empty ? 1 : 0;
@@ -331,20 +298,22 @@ try {
         if (!lio_gc_finite(upper - lower)) return lio_fail(LIO_ERR_ARG, "upper - lower must be finite");
     }
     if (!g || !image) return lio_fail(LIO_ERR_ARG, "null argument");
-    if (!gc_has_layer(g, layer)) return lio_fail(LIO_ERR_ARG, "the object holds no such layer");
+    if (!lio_grid_has_layer(g, layer)) return lio_fail(LIO_ERR_ARG, "the object holds no such layer");
     const int rows = g->G.rows, cols = g->G.cols;
     const size_t cells = (size_t)rows * (size_t)cols, bytes = cells * (size_t)channels * (size_t)lio_gc_elem_bytes(depth);
     if (cap_bytes < bytes) return lio_fail(LIO_ERR_ARG, "image holds fewer than rows x cols x channels x element size bytes");
     if ((rc = lio_check_device(g->device_id)) != LIO_OK) return rc;
     hipStream_t s = nullptr;
     const float* d_layer = g->d_layer[layer].p;
-    LioTemp img, counters;
+    LioTemp img;
+    LioGridCounters counters;
     HIPCHK(img.alloc(bytes + 4));
-    HIPCHK(counters.alloc((GC_N_CNT + 1) * sizeof(unsigned long long)));
-    unsigned* d_stats = (unsigned*)(counters.as<unsigned long long>() + GC_N_CNT);
-    GcClock clk;
+    HIPCHK(counters.alloc(GC_N_CNT, 1));                   // (the word behind them: the extremes)
+    unsigned* d_stats = (unsigned*)(counters.d() + GC_N_CNT);
+    t_gc.clear();
+    LioStageClock clk(t_gc.on);
     clk.mark(s);
-    HIPCHK(hipMemsetAsync(counters.p, 0, GC_N_CNT * sizeof(unsigned long long), s));
+    HIPCHK(counters.clear(s));
     if (automatic) {
         unsigned hs[2] = { LIO_ORD_NO_MIN, LIO_ORD_NO_MAX };
         HIPCHK(hipMemcpyAsync(d_stats, hs, sizeof(hs), hipMemcpyHostToDevice, s));
@@ -361,20 +330,17 @@ try {
     clk.mark(s);
     if (!t_gc_tiled) {
         hipLaunchKernelGGL(k_gc_to_image_direct, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, d_layer, rows, cols, lower, upper, channels, depth,
-                           img.as<unsigned char>(), counters.as<unsigned long long>());
+                           img.as<unsigned char>(), counters.d());
     } else {
         const int tiles_r = (rows + LIO_GC_TILE - 1) / LIO_GC_TILE, tiles_c = (cols + LIO_GC_TILE - 1) / LIO_GC_TILE;
         hipLaunchKernelGGL(k_gc_to_image, dim3((unsigned)tiles_r * (unsigned)tiles_c), dim3(256), 0, s, d_layer, rows, cols, tiles_r, lower, upper, channels, depth,
-                           img.as<unsigned char>(), counters.as<unsigned long long>());
+                           img.as<unsigned char>(), counters.d());
     }
     clk.mark(s);
     unsigned long long hc[GC_N_CNT] = { 0, 0, 0 };
     HIPCHK(hipMemcpyAsync(image, img.p, bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(hc, counters.p, sizeof(hc), hipMemcpyDeviceToHost, s));
-    clk.mark(s);
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipGetLastError());
-    clk.read();
+    if ((rc = counters.finish(hc, s, &clk)) != LIO_OK) return rc;
+    t_gc.read(clk);
     if (info) {
         info->rows = rows; info->cols = cols;
         info->lower = lower; info->upper = upper;
@@ -439,12 +405,7 @@ try {
                          G.pos[0] != position[0] || G.pos[1] != position[1];
     if ((rc = lio_check_device(g->device_id)) != LIO_OK) return rc;
     const unsigned old_mask = g->mask;
-    struct Undo {                  // after a failure: what it held where the geometry stayed, nothing where it was replaced
-        lio_grid* g;
-        unsigned mask;
-        bool replace;
-        ~Undo() { if (g) { if (replace) lio_grid_clear(g); else g->mask = mask; } }
-    } undo = { g, old_mask, replace };
+    LioGridRollback undo(g, replace);                      // after a failure: what it held where the geometry stayed, nothing where it was replaced
     GcFill F;
     memset(&F, 0, sizeof(F));
     if (replace) {
@@ -459,23 +420,22 @@ try {
     float* d = nullptr;
     if ((rc = lio_grid_layer_slot(g, layer, &d)) != LIO_OK) return rc;
     hipStream_t s = nullptr;
-    LioTemp msg, counters;
+    LioTemp msg;
+    LioGridCounters counters;
     HIPCHK(msg.alloc(n));
-    HIPCHK(counters.alloc(GC_N_CNT * sizeof(unsigned long long)));
-    GcClock clk;
+    HIPCHK(counters.alloc(GC_N_CNT));
+    t_gc.clear();
+    LioStageClock clk(t_gc.on);
     clk.mark(s);
     HIPCHK(hipMemcpyAsync(msg.p, data, n, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(counters.p, 0, GC_N_CNT * sizeof(unsigned long long), s));
+    HIPCHK(counters.clear(s));
     clk.mark(s);
-    hipLaunchKernelGGL(k_gc_occupancy, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, msg.as<int8_t>(), (int)n, (unsigned*)d, F, counters.as<unsigned long long>());
+    hipLaunchKernelGGL(k_gc_occupancy, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, msg.as<int8_t>(), (int)n, (unsigned*)d, F, counters.d());
     clk.mark(s);
     unsigned long long hc[GC_N_CNT] = { 0, 0, 0 };
-    HIPCHK(hipMemcpyAsync(hc, counters.p, sizeof(hc), hipMemcpyDeviceToHost, s));
-    clk.mark(s);
-    HIPCHK(hipStreamSynchronize(s));                       // the call's one host wait
-    HIPCHK(hipGetLastError());
-    clk.read();
-    undo.g = nullptr;
+    if ((rc = counters.finish(hc, s, &clk)) != LIO_OK) return rc;       // the call's one host wait
+    t_gc.read(clk);
+    undo.commit();
     if (info) {
         info->rows = rows; info->cols = cols;
         info->geometry_replaced = replace ? 1 : 0;
@@ -493,17 +453,13 @@ try {
     if (!layer_ids || !n_out || (cap_points && !points)) return lio_fail(LIO_ERR_ARG, "null argument");
     if (n_layers < 1 || n_layers > LIO_GRID_MAX_LAYERS) return lio_fail(LIO_ERR_ARG, "n_layers must be in [1, LIO_GRID_MAX_LAYERS]");
     unsigned listed = 0;
-    for (int k = 0; k < n_layers; ++k) {
-        const int id = layer_ids[k];
-        if (id < 0 || id >= LIO_GRID_MAX_LAYERS) return lio_fail(LIO_ERR_ARG, "a layer id is outside 0 .. 15");
-        if ((listed >> id) & 1u) return lio_fail(LIO_ERR_ARG, "a layer id is repeated");
-        listed |= 1u << id;
-    }
+    int rc = lio_grid_layer_list(layer_ids, n_layers, &listed);
+    if (rc != LIO_OK) return rc;
     if (basic_mask >> LIO_GRID_MAX_LAYERS) return lio_fail(LIO_ERR_ARG, "basic_mask names a layer the object does not hold");
     if (!g) return lio_fail(LIO_ERR_ARG, "null argument");
     if (!g->mask) return lio_fail(LIO_ERR_ARG, "the object holds no layers (lio_grid_set_layers, lio_kf_store_planning_grid)");
     if (listed & ~g->mask) return lio_fail(LIO_ERR_ARG, "a layer id names a layer the object does not hold");
-    if (!gc_has_layer(g, point_layer)) return lio_fail(LIO_ERR_ARG, "the object does not hold point_layer");
+    if (!lio_grid_has_layer(g, point_layer)) return lio_fail(LIO_ERR_ARG, "the object does not hold point_layer");
     if (basic_mask & ~g->mask) return lio_fail(LIO_ERR_ARG, "basic_mask names a layer the object does not hold");
     GcCloudPred pred;
     memset(&pred, 0, sizeof(pred));
@@ -519,8 +475,7 @@ try {
     for (int k = 0; k < LIO_GRID_MAX_LAYERS; ++k)
         if ((basic_mask >> k) & 1u) C.basic[C.n_basic++] = (const unsigned*)g->d_layer[k].p;
     if (n_fields) *n_fields = C.n_fields;
-    int rc = lio_check_device(g->device_id);
-    if (rc != LIO_OK) return rc;
+    if ((rc = lio_check_device(g->device_id)) != LIO_OK) return rc;
     const LioTerrGeom G = g->G;
     return gc_compact_out<int>(pred, G.rows * G.cols, sizeof(float) * (size_t)C.n_fields, points, cap_points, n_out,
                                [&](void* p) { return GcCloudSink{ C, G, (unsigned*)p }; });
@@ -532,7 +487,7 @@ try {
     if (!n_out || (cap_cells && !cells)) return lio_fail(LIO_ERR_ARG, "null argument");
     if (lower != lower || upper != upper) return lio_fail(LIO_ERR_ARG, "lower and upper must not be NaN");
     if (!g) return lio_fail(LIO_ERR_ARG, "null argument");
-    if (!gc_has_layer(g, layer)) return lio_fail(LIO_ERR_ARG, "the object holds no such layer");
+    if (!lio_grid_has_layer(g, layer)) return lio_fail(LIO_ERR_ARG, "the object holds no such layer");
     int rc = lio_check_device(g->device_id);
     if (rc != LIO_OK) return rc;
     const LioTerrGeom G = g->G;
@@ -560,8 +515,6 @@ try {
 
 extern "C" int lio_grid_convert_debug_stage_ms(int32_t enable, int32_t use_tiled, float ms[3])
 try {
-    if (ms) memcpy(ms, t_gc_ms, sizeof(t_gc_ms));
-    t_gc_on = enable != 0;
     t_gc_tiled = use_tiled != 0;
-    return LIO_OK;
+    return t_gc.hook(enable, ms);
 } LIO_CATCH

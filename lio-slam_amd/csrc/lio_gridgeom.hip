@@ -10,8 +10,9 @@
 //                   test on the gathered values and the gather from `other` are this one launch; without a resize the map is
 //                   worked on in place and only the words that change are written.
 // The table (up to 16 self, 16 destination and 16 other pointers) is a kernel argument by value; the loop index is uniform, so
-// the pointers are scalar loads.  Counters: per-wave ballots and one integer atomic per wave and counter.  A resized or moved
-// layer is written into a block from the pool that then takes the layer's place; the old block goes to the pool.
+// the pointers are scalar loads.  Counters: per-wave ballots and one integer atomic per wave and counter (lio_wave_count,
+// lio_wg.h).  A resized or moved layer is written into a block from the pool that then takes the layer's place; the old block
+// goes to the pool.
 // conventions, deviations, resources, times.  -ffp-contract=off.
 #include <hip/hip_runtime.h>
 #include <float.h>
@@ -23,16 +24,11 @@
 #include "lio_gridobj.h"
 #include "lio_cloud.h"
 #include "lio_pool.h"
+#include "lio_wg.h"
 
 namespace {
 
 enum { GG_CNT_CLEARED = 0, GG_CNT_KEPT, GG_CNT_SKIPPED, GG_CNT_OUTSIDE, GG_CNT_INDEX, GG_CNT_COPIED, GG_N_CNT };
-
-__device__ __forceinline__ void gg_count(unsigned long long* counters, int which, bool flag)
-{
-    const unsigned long long m = __ballot(flag);
-    if ((threadIdx.x & 63) == 0 && m) atomicAdd(&counters[which], (unsigned long long)__popcll(m));
-}
 
 __global__ __launch_bounds__(256) void k_gg_offset(LioGgTable T, int d_rows, int n_cells, int s_rows, int s_cols, int off0, int off1,
                                                    unsigned long long* __restrict__ counters)
@@ -40,7 +36,7 @@ __global__ __launch_bounds__(256) void k_gg_offset(LioGgTable T, int d_rows, int
     const int lin = (int)blockIdx.x * 256 + (int)threadIdx.x;
     bool cleared = false;
     if (lin < n_cells) cleared = lio_gg_offset_cell(T, d_rows, s_rows, s_cols, off0, off1, lin % d_rows, lin / d_rows);
-    gg_count(counters, GG_CNT_CLEARED, cleared);
+    lio_wave_count(counters, GG_CNT_CLEARED, cleared);
 }
 
 __global__ __launch_bounds__(256) void k_gg_position(LioGgTable T, LioTerrGeom N, LioTerrGeom O, LioTerrGeom X, int flags, int n_cells,
@@ -51,37 +47,18 @@ __global__ __launch_bounds__(256) void k_gg_position(LioGgTable T, LioTerrGeom N
     n.kept = n.skipped_valid = n.outside_other = n.index_outside_self = n.index_outside_other = false;
     n.copied = 0;
     if (lin < n_cells) lio_gg_position_cell(T, N, O, X, flags, lin % N.rows, lin / N.rows, &n);
-    gg_count(counters, GG_CNT_KEPT, n.kept);
-    gg_count(counters, GG_CNT_SKIPPED, n.skipped_valid);
-    gg_count(counters, GG_CNT_OUTSIDE, n.outside_other);
-    gg_count(counters, GG_CNT_INDEX, n.index_outside_self);
-    gg_count(counters, GG_CNT_INDEX, n.index_outside_other);
+    lio_wave_count(counters, GG_CNT_KEPT, n.kept);
+    lio_wave_count(counters, GG_CNT_SKIPPED, n.skipped_valid);
+    lio_wave_count(counters, GG_CNT_OUTSIDE, n.outside_other);
+    lio_wave_count(counters, GG_CNT_INDEX, n.index_outside_self);
+    lio_wave_count(counters, GG_CNT_INDEX, n.index_outside_other);
     unsigned long long copied = 0;                           // a lane copies 0 .. 16 values: five ballots, one per bit
 #pragma unroll
     for (int b = 0; b < 5; ++b) copied += (unsigned long long)__popcll(__ballot((n.copied >> b) & 1)) << b;
     if ((threadIdx.x & 63) == 0 && copied) atomicAdd(&counters[GG_CNT_COPIED], copied);
 }
 
-thread_local float t_gg_ms = 0.0f;
-thread_local bool t_gg_on = false;
-
-struct GgClock {                   // two marks around the kernel, only when a caller asked for the time
-    hipEvent_t ev[2] = { nullptr, nullptr };
-    int n = 0;
-    bool on = false;
-    ~GgClock() { for (int k = 0; k < n; ++k) (void)hipEventDestroy(ev[k]); }
-    void mark(hipStream_t s)
-    {
-        if (!on || n >= 2) return;
-        if (hipEventCreate(&ev[n]) != hipSuccess) { on = false; return; }
-        (void)hipEventRecord(ev[n++], s);
-    }
-    void read()
-    {
-        t_gg_ms = 0.0f;
-        if (on && n == 2 && hipEventElapsedTime(&t_gg_ms, ev[0], ev[1]) != hipSuccess) t_gg_ms = 0.0f;
-    }
-};
+thread_local LioStageTimes<1> t_gg;                        // two marks around the kernel; 0 where none was launched
 
 // Blocks from the pool that take the place of layers once the kernel that filled them has completed.
 struct GgFresh {
@@ -110,14 +87,20 @@ int gg_pair_check(const lio_grid* a, const lio_grid* b, const char* same, bool b
     return LIO_OK;
 }
 
-// the counters down and the call's one host wait
-int gg_finish(hipStream_t s, LioTemp& counters, GgClock& clk, unsigned long long hc[GG_N_CNT])
+// One launch between the clock's two marks: the counters cleared before it, then down under the call's one host wait.
+template <class Launch>
+int gg_run(hipStream_t s, unsigned long long hc[GG_N_CNT], const Launch& launch)
 {
-    HIPCHK(hipMemcpyAsync(hc, counters.p, GG_N_CNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipGetLastError());
-    clk.read();
-    return LIO_OK;
+    LioGridCounters counters;
+    HIPCHK(counters.alloc(GG_N_CNT));
+    HIPCHK(counters.clear(s));
+    LioStageClock clk(t_gg.on);
+    clk.mark(s);
+    launch(counters.d());
+    clk.mark(s);
+    const int rc = counters.finish(hc, s, nullptr);
+    if (rc == LIO_OK) t_gg.read(clk);
+    return rc;
 }
 
 struct GgAddResult {
@@ -129,7 +112,7 @@ struct GgAddResult {
 int gg_extend_add(lio_grid* g, lio_grid* other, bool extend, bool add, bool overwrite, unsigned listed, unsigned basic_mask, GgAddResult* out)
 {
     memset(out, 0, sizeof(*out));
-    t_gg_ms = 0.0f;
+    t_gg.clear();
     const LioTerrGeom O = g->G, X = other->G;
     LioTerrGeom N = O;
     bool resized = false;
@@ -163,11 +146,7 @@ int gg_extend_add(lio_grid* g, lio_grid* other, bool extend, bool add, bool over
     // in place, only the layers that are read (basic) or may be written (listed, new among them) enter the table
     const unsigned in_table = resized ? final_mask : ((listed | basic_mask) & final_mask);
     const size_t cells = (size_t)N.rows * (size_t)N.cols;
-    struct Undo {                  // after a failure g holds the layers it held
-        lio_grid* g;
-        unsigned mask;
-        ~Undo() { if (g) g->mask = mask; }
-    } undo = { g, old_mask };
+    LioGridRollback undo(g, false);                          // after a failure g holds the layers it held
     GgFresh fresh;
     LioGgTable T;
     memset(&T, 0, sizeof(T));
@@ -188,24 +167,18 @@ int gg_extend_add(lio_grid* g, lio_grid* other, bool extend, bool add, bool over
         ++T.n;
     }
     hipStream_t s = nullptr;
-    LioTemp counters;
-    HIPCHK(counters.alloc(GG_N_CNT * sizeof(unsigned long long)));
-    HIPCHK(hipMemsetAsync(counters.p, 0, GG_N_CNT * sizeof(unsigned long long), s));
-    GgClock clk;
-    clk.on = t_gg_on;
-    clk.mark(s);
     const int flags = (resized ? LIO_GG_RESIZE : 0) | (add ? LIO_GG_ADD : 0) | (overwrite ? LIO_GG_OVERWRITE : 0);
-    hipLaunchKernelGGL(k_gg_position, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, T, N, O, X, flags, (int)cells,
-                       counters.as<unsigned long long>());
-    clk.mark(s);
-    if ((rc = gg_finish(s, counters, clk, out->cnt)) != LIO_OK) return rc;
+    rc = gg_run(s, out->cnt, [&](unsigned long long* d_cnt) {
+        hipLaunchKernelGGL(k_gg_position, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, T, N, O, X, flags, (int)cells, d_cnt);
+    });
+    if (rc != LIO_OK) return rc;
     if (resized) {
         for (int k = 0; k < LIO_GRID_MAX_LAYERS; ++k)
             if ((final_mask >> k) & 1u) fresh.swap_in(g, k);
         g->G = N;
     }
+    undo.commit();
     g->mask = final_mask;
-    undo.g = nullptr;
     return LIO_OK;
 }
 
@@ -220,7 +193,7 @@ void gg_fill_geometry(const lio_grid* g, int32_t* rows, int32_t* cols, double le
 extern "C" int lio_grid_submap(lio_grid* src, const double position[2], const double length[2], lio_grid* dst, lio_grid_submap_info* info)
 try {
     if (info) memset(info, 0, sizeof(*info));
-    t_gg_ms = 0.0f;
+    t_gg.clear();
     if (!position || !length) return lio_fail(LIO_ERR_ARG, "null argument");
     for (int a = 0; a < 2; ++a) {
         if (!std::isfinite(position[a]) || !std::isfinite(length[a])) return lio_fail(LIO_ERR_ARG, "position and length must be finite");
@@ -237,10 +210,7 @@ try {
     }
     if ((rc = lio_check_device(src->device_id)) != LIO_OK) return rc;
     if ((rc = lio_grid_set_geometry(dst, M.size[0], M.size[1], S.res, M.length, M.position)) != LIO_OK) return rc;
-    struct Undo {                  // after a failure dst holds no layer
-        lio_grid* g;
-        ~Undo() { if (g) lio_grid_clear(g); }
-    } undo = { dst };
+    LioGridRollback undo(dst, true);                         // after a failure dst holds no layer
     LioGgTable T;
     memset(&T, 0, sizeof(T));
     for (int k = 0; k < LIO_GRID_MAX_LAYERS; ++k) {
@@ -252,19 +222,14 @@ try {
         ++T.n;
     }
     hipStream_t s = nullptr;
-    LioTemp counters;
-    HIPCHK(counters.alloc(GG_N_CNT * sizeof(unsigned long long)));
-    HIPCHK(hipMemsetAsync(counters.p, 0, GG_N_CNT * sizeof(unsigned long long), s));
-    GgClock clk;
-    clk.on = t_gg_on;
-    clk.mark(s);
     const long long cells = (long long)M.size[0] * (long long)M.size[1];
-    hipLaunchKernelGGL(k_gg_offset, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, T, M.size[0], (int)cells, S.rows, S.cols, M.top_left[0],
-                       M.top_left[1], counters.as<unsigned long long>());
-    clk.mark(s);
     unsigned long long hc[GG_N_CNT];
-    if ((rc = gg_finish(s, counters, clk, hc)) != LIO_OK) return rc;
-    undo.g = nullptr;
+    rc = gg_run(s, hc, [&](unsigned long long* d_cnt) {
+        hipLaunchKernelGGL(k_gg_offset, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, T, M.size[0], (int)cells, S.rows, S.cols, M.top_left[0],
+                           M.top_left[1], d_cnt);
+    });
+    if (rc != LIO_OK) return rc;
+    undo.commit();
     if (info) {
         info->success = 1;
         info->rows = M.size[0]; info->cols = M.size[1];
@@ -279,7 +244,7 @@ try {
 extern "C" int lio_grid_move(lio_grid* g, const double position[2], lio_grid_move_info* info)
 try {
     if (info) memset(info, 0, sizeof(*info));
-    t_gg_ms = 0.0f;
+    t_gg.clear();
     if (!position) return lio_fail(LIO_ERR_ARG, "null argument");
     if (!std::isfinite(position[0]) || !std::isfinite(position[1])) return lio_fail(LIO_ERR_ARG, "position must be finite");
     if (!g) return lio_fail(LIO_ERR_ARG, "null argument");
@@ -310,16 +275,10 @@ try {
             ++T.n;
         }
         hipStream_t s = nullptr;
-        LioTemp counters;
-        HIPCHK(counters.alloc(GG_N_CNT * sizeof(unsigned long long)));
-        HIPCHK(hipMemsetAsync(counters.p, 0, GG_N_CNT * sizeof(unsigned long long), s));
-        GgClock clk;
-        clk.on = t_gg_on;
-        clk.mark(s);
-        hipLaunchKernelGGL(k_gg_offset, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, T, O.rows, (int)cells, O.rows, O.cols, shift[0], shift[1],
-                           counters.as<unsigned long long>());
-        clk.mark(s);
-        if ((rc = gg_finish(s, counters, clk, hc)) != LIO_OK) return rc;
+        rc = gg_run(s, hc, [&](unsigned long long* d_cnt) {
+            hipLaunchKernelGGL(k_gg_offset, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, T, O.rows, (int)cells, O.rows, O.cols, shift[0], shift[1], d_cnt);
+        });
+        if (rc != LIO_OK) return rc;
         for (int k = 0; k < LIO_GRID_MAX_LAYERS; ++k)
             if ((g->mask >> k) & 1u) fresh.swap_in(g, k);
     }
@@ -356,15 +315,10 @@ try {
     if (n_layers < 0 || n_layers > LIO_GRID_MAX_LAYERS) return lio_fail(LIO_ERR_ARG, "n_layers must be in [0, LIO_GRID_MAX_LAYERS]");
     if (n_layers > 0 && !layer_ids) return lio_fail(LIO_ERR_ARG, "null argument");
     unsigned listed = 0;
-    for (int k = 0; k < n_layers; ++k) {
-        const int id = layer_ids[k];
-        if (id < 0 || id >= LIO_GRID_MAX_LAYERS) return lio_fail(LIO_ERR_ARG, "a layer id is outside 0 .. 15");
-        if ((listed >> id) & 1u) return lio_fail(LIO_ERR_ARG, "a layer id is repeated");
-        listed |= 1u << id;
-    }
-    if (basic_mask >> LIO_GRID_MAX_LAYERS) return lio_fail(LIO_ERR_ARG, "basic_mask names a layer g does not hold");
-    int rc = gg_pair_check(g, other, "g and other are the same object", true);
+    int rc = lio_grid_layer_list(layer_ids, n_layers, &listed);
     if (rc != LIO_OK) return rc;
+    if (basic_mask >> LIO_GRID_MAX_LAYERS) return lio_fail(LIO_ERR_ARG, "basic_mask names a layer g does not hold");
+    if ((rc = gg_pair_check(g, other, "g and other are the same object", true)) != LIO_OK) return rc;
     if (n_layers == 0) listed = other->mask;                // copyAllLayers
     if (listed & ~other->mask) return lio_fail(LIO_ERR_ARG, "a layer id names a layer other does not hold");
     if (basic_mask & ~g->mask) return lio_fail(LIO_ERR_ARG, "basic_mask names a layer g does not hold");
@@ -383,7 +337,5 @@ try {
 
 extern "C" int lio_grid_geom_debug_kernel_ms(int32_t enable, float* ms)
 try {
-    if (ms) *ms = t_gg_ms;
-    t_gg_on = enable != 0;
-    return LIO_OK;
+    return t_gg.hook(enable, ms);
 } LIO_CATCH

@@ -200,21 +200,7 @@ __global__ __launch_bounds__(256) void k_rg_cells(LioTerrGeom G, const LioRgRegi
     }
 }
 
-thread_local float t_rg_ms[4] = { 0, 0, 0, 0 };
-thread_local bool t_rg_on = false;
-
-struct RgClock {                   // five marks around the four stages, only when a caller asked for the times
-    hipEvent_t ev[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
-    int n = 0;
-    bool on = false;
-    ~RgClock() { for (int k = 0; k < n; ++k) (void)hipEventDestroy(ev[k]); }
-    void mark(hipStream_t s)
-    {
-        if (!on || n >= 5) return;
-        if (hipEventCreate(&ev[n]) != hipSuccess) { on = false; return; }
-        (void)hipEventRecord(ev[n++], s);
-    }
-};
+thread_local LioStageTimes<4> t_rg;                        // five marks around the four stages of lio_grid_region_reduce
 
 // What both entry points refuse before the object or a device is looked at, and the regions as the device reads them.
 int rg_pack(const lio_grid_region* regions, size_t n, const double* vertices, size_t n_vertices, std::vector<LioRgRegion>& out)
@@ -243,7 +229,7 @@ unsigned rg_info_blocks(size_t n) { const size_t b = (n + 255) / 256; return (un
 
 // regions and vertices up, the counters cleared, the plans made: on stream s, nothing waited for
 int rg_upload_and_plan(lio_grid* g, const std::vector<LioRgRegion>& packed, const double* vertices, size_t n_vertices, size_t small_bytes, hipStream_t s,
-                       RgClock& clk)
+                       LioStageClock& clk)
 {
     const size_t n = packed.size();
     LioDevBytes* B = g->d_region;
@@ -286,19 +272,14 @@ try {
     if (!layer_ids || !cfg || (n && (!regions || !stats))) return lio_fail(LIO_ERR_ARG, "null argument");
     if (!std::isfinite(cfg->threshold)) return lio_fail(LIO_ERR_ARG, "threshold must be finite");
     if (n_layers < 1 || n_layers > LIO_GRID_MAX_LAYERS) return lio_fail(LIO_ERR_ARG, "n_layers must be in [1, LIO_GRID_MAX_LAYERS]");
-    unsigned seen = 0;
-    for (int k = 0; k < n_layers; ++k) {
-        const int id = layer_ids[k];
-        if (id < 0 || id >= LIO_GRID_MAX_LAYERS) return lio_fail(LIO_ERR_ARG, "a layer id is outside 0 .. LIO_GRID_MAX_LAYERS - 1");
-        if ((seen >> id) & 1u) return lio_fail(LIO_ERR_ARG, "a layer id is repeated");
-        seen |= 1u << id;
-    }
-    std::vector<LioRgRegion> packed;
-    int rc = rg_pack(regions, n, vertices, n_vertices, packed);
+    unsigned listed = 0;
+    int rc = lio_grid_layer_list(layer_ids, n_layers, &listed);
     if (rc != LIO_OK) return rc;
+    std::vector<LioRgRegion> packed;
+    if ((rc = rg_pack(regions, n, vertices, n_vertices, packed)) != LIO_OK) return rc;
     if (!g) return lio_fail(LIO_ERR_ARG, "null argument");
     if (!g->mask) return lio_fail(LIO_ERR_ARG, "the object holds no layers (lio_grid_set_layers, lio_kf_store_planning_grid)");
-    if ((seen & g->mask) != seen) return lio_fail(LIO_ERR_ARG, "a layer id names a layer the object does not hold");
+    if (listed & ~g->mask) return lio_fail(LIO_ERR_ARG, "a layer id names a layer the object does not hold");
     if (n == 0) return LIO_OK;
     RgLayers L;
     memset(&L, 0, sizeof(L));
@@ -309,8 +290,7 @@ try {
     const size_t pairs = (size_t)n_layers * n;
     const size_t off_cells = 64, off_status = off_cells + rg_up8(sizeof(int) * n);
     HIPCHK(B[LIO_RG_BUF_STATS].alloc(sizeof(lio_grid_region_stat) * pairs));
-    RgClock clk;
-    clk.on = t_rg_on;
+    LioStageClock clk(t_rg.on);
     if ((rc = rg_upload_and_plan(g, packed, vertices, n_vertices, off_status + n, s, clk)) != LIO_OK) return rc;
     unsigned char* small = B[LIO_RG_BUF_SMALL].p;
     hipLaunchKernelGGL(k_rg_reduce, dim3((unsigned)((n + RG_WAVES - 1) / RG_WAVES)), dim3(64 * RG_WAVES), 0, s, g->G, L, n_layers, cfg->threshold,
@@ -328,9 +308,7 @@ try {
     HIPCHK(hipStreamSynchronize(s));                       // the call's one host wait
     HIPCHK(hipGetLastError());
     rg_fill_info(info, hc);
-    if (clk.on && clk.n == 5)
-        for (int k = 0; k < 4; ++k)
-            if (hipEventElapsedTime(&t_rg_ms[k], clk.ev[k], clk.ev[k + 1]) != hipSuccess) t_rg_ms[k] = 0.0f;
+    t_rg.read(clk);
     return LIO_OK;
 } LIO_CATCH
 
@@ -358,7 +336,7 @@ try {
     const size_t off_tiles = off_occ + rg_up8(sizeof(int) * (n + 1));
     HIPCHK(B[LIO_RG_BUF_SCAN].alloc(off_tiles + sizeof(unsigned long long) * n_tiles));
     HIPCHK(B[LIO_RG_BUF_CELLS].alloc(sizeof(int) * (size_t)cap));
-    RgClock clk;                                           // (off: the stage times are lio_grid_region_reduce's)
+    LioStageClock clk(false);                              // (off: the stage times are lio_grid_region_reduce's)
     if ((rc = rg_upload_and_plan(g, packed, vertices, n_vertices, 64 + n, s, clk)) != LIO_OK) return rc;
     unsigned char* small = B[LIO_RG_BUF_SMALL].p;
     unsigned char* scan = B[LIO_RG_BUF_SCAN].p;
@@ -392,7 +370,5 @@ try {
 
 extern "C" int lio_grid_region_debug_stage_ms(int32_t enable, float ms[4])
 try {
-    if (ms) memcpy(ms, t_rg_ms, sizeof(t_rg_ms));
-    t_rg_on = enable != 0;
-    return LIO_OK;
+    return t_rg.hook(enable, ms);
 } LIO_CATCH

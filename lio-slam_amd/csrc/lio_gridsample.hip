@@ -1,6 +1,6 @@
 // lio_gridsample.hip -- the planning layers resident on the device and grid_map's GridMap::atPosition on them: the query a
 // planner makes of the elevation grid and the terrain layers, once per trajectory point and footprint corner.  The arithmetic
-// is lio_gridsample.h's; this file is the object and the data movement.
+// is lio_gridsample.h's; this file is the object, the guards its entry points share (lio_gridobj.h) and the data movement.
 //   k_grid_sample   one lane per position, 256 lanes a block, one instance per interpolation method.  The lane reads its
 //                   position as one 16-byte load and forms the geometry once in fp64 (cell, quadrant, tap indices, normalised
 //                   coordinates), then loops over the requested layers: gathers the taps, evaluates, runs the fall-back chain.
@@ -71,21 +71,7 @@ __global__ __launch_bounds__(256) void k_grid_sample(LioTerrGeom G, GsLayers L, 
     }
 }
 
-thread_local float t_stage_ms[3] = { 0, 0, 0 };
-thread_local bool t_stage_on = false;
-
-struct GsClock {                   // four marks around the three stages, only when a caller asked for the times
-    hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
-    int n = 0;
-    bool on = false;
-    ~GsClock() { for (int k = 0; k < n; ++k) (void)hipEventDestroy(ev[k]); }
-    void mark(hipStream_t s)
-    {
-        if (!on || n >= 4) return;
-        if (hipEventCreate(&ev[n]) != hipSuccess) { on = false; return; }
-        (void)hipEventRecord(ev[n++], s);
-    }
-};
+thread_local LioStageTimes<3> t_stage;                     // four marks around the three stages of lio_grid_sample
 
 void grid_apply_geometry(lio_grid* g, int rows, int cols, double resolution, const double* length, const double* position)
 {
@@ -117,6 +103,29 @@ void lio_grid_clear(lio_grid* g)
 {
     g->mask = 0;
     g->G.rows = g->G.cols = 0;
+}
+
+bool lio_grid_has_layer(const lio_grid* g, int layer) { return layer >= 0 && layer < LIO_GRID_MAX_LAYERS && ((g->mask >> layer) & 1u); }
+
+int lio_grid_layer_list(const int32_t* ids, int n, unsigned* listed)
+{
+    *listed = 0;
+    for (int k = 0; k < n; ++k) {
+        const int id = ids[k];
+        if (id < 0 || id >= LIO_GRID_MAX_LAYERS) return lio_fail(LIO_ERR_ARG, "a layer id is outside 0 .. 15");
+        if ((*listed >> id) & 1u) return lio_fail(LIO_ERR_ARG, "a layer id is repeated");
+        *listed |= 1u << id;
+    }
+    return LIO_OK;
+}
+
+int LioGridCounters::finish(unsigned long long* host, hipStream_t s, LioStageClock* clk)
+{
+    HIPCHK(hipMemcpyAsync(host, t.p, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    if (clk) clk->mark(s);
+    HIPCHK(hipStreamSynchronize(s));                       // (the temporaries go back to the pool after it)
+    HIPCHK(hipGetLastError());
+    return LIO_OK;
 }
 
 int lio_grid_begin(lio_grid* g, int device_id)
@@ -184,22 +193,22 @@ try {
     if ((rc = lio_grid_set_geometry(g, rows, cols, resolution, length, position)) != LIO_OK) return rc;
     hipStream_t s = nullptr;
     const size_t cells = (size_t)rows * (size_t)cols;
+    LioGridRollback undo(g, false);                        // after a failure the geometry holds no layer
     for (int k = 0; k < n_layers; ++k) {
         float* d = nullptr;
-        if ((rc = lio_grid_layer_slot(g, k, &d)) != LIO_OK) { g->mask = 0; return rc; }
+        if ((rc = lio_grid_layer_slot(g, k, &d)) != LIO_OK) return rc;
         const hipError_t e = hipMemcpyAsync(d, layers + (size_t)k * cells, sizeof(float) * cells, hipMemcpyHostToDevice, s);
-        if (e != hipSuccess) { g->mask = 0; (void)hipStreamSynchronize(s); HIPCHK(e); }
+        if (e != hipSuccess) { (void)hipStreamSynchronize(s); HIPCHK(e); }
     }
-    const hipError_t e = hipStreamSynchronize(s);
-    if (e != hipSuccess) g->mask = 0;
-    HIPCHK(e);
+    HIPCHK(hipStreamSynchronize(s));
+    undo.commit();
     return LIO_OK;
 } LIO_CATCH
 
 extern "C" int lio_grid_get_layer(lio_grid* g, int32_t layer, float* out, size_t cap_floats)
 try {
     if (!g || !out) return lio_fail(LIO_ERR_ARG, "null argument");
-    if (layer < 0 || layer >= LIO_GRID_MAX_LAYERS || !((g->mask >> layer) & 1u)) return lio_fail(LIO_ERR_ARG, "the object holds no such layer");
+    if (!lio_grid_has_layer(g, layer)) return lio_fail(LIO_ERR_ARG, "the object holds no such layer");
     const size_t cells = (size_t)g->G.rows * (size_t)g->G.cols;
     if (cap_floats < cells) return lio_fail(LIO_ERR_ARG, "out holds fewer than rows x cols floats");
     int rc = lio_check_device(g->device_id);
@@ -239,37 +248,33 @@ try {
     if (n_layers < 1 || n_layers > LIO_GRID_MAX_LAYERS) return lio_fail(LIO_ERR_ARG, "n_layers must be in [1, LIO_GRID_MAX_LAYERS]");
     if (!g) return lio_fail(LIO_ERR_ARG, "null argument");
     if (!g->mask) return lio_fail(LIO_ERR_ARG, "the object holds no layers (lio_grid_set_layers, lio_kf_store_planning_grid)");
+    unsigned listed = 0;
+    int rc = lio_grid_layer_list(layer_ids, n_layers, &listed);
+    if (rc != LIO_OK) return rc;
+    if (listed & ~g->mask) return lio_fail(LIO_ERR_ARG, "a layer id names a layer the object does not hold");
     GsLayers L;
     memset(&L, 0, sizeof(L));
-    unsigned seen = 0;
-    for (int k = 0; k < n_layers; ++k) {
-        const int id = layer_ids[k];
-        if (id < 0 || id >= LIO_GRID_MAX_LAYERS || !((g->mask >> id) & 1u)) return lio_fail(LIO_ERR_ARG, "a layer id names a layer the object does not hold");
-        if ((seen >> id) & 1u) return lio_fail(LIO_ERR_ARG, "a layer id is repeated");
-        seen |= 1u << id;
-        L.p[k] = g->d_layer[id].p;
-    }
+    for (int k = 0; k < n_layers; ++k) L.p[k] = g->d_layer[layer_ids[k]].p;
     if (n > (size_t)1 << 27) return lio_fail(LIO_ERR_CAPACITY, "more than 2^27 positions in one call");
     if (n == 0) return LIO_OK;
-    int rc = lio_check_device(g->device_id);
-    if (rc != LIO_OK) return rc;
+    if ((rc = lio_check_device(g->device_id)) != LIO_OK) return rc;
     hipStream_t s = nullptr;
     const size_t pairs = (size_t)n_layers * n;
-    LioTemp pos, val, used, counters;
+    LioTemp pos, val, used;
+    LioGridCounters counters;
     HIPCHK(pos.alloc(sizeof(double) * 2 * n));
     HIPCHK(val.alloc(sizeof(float) * pairs));
     if (method_used) HIPCHK(used.alloc(pairs));
-    HIPCHK(counters.alloc(5 * sizeof(unsigned long long)));
-    GsClock clk;
-    clk.on = t_stage_on;
+    HIPCHK(counters.alloc(5));
+    LioStageClock clk(t_stage.on);
     clk.mark(s);
     HIPCHK(hipMemcpyAsync(pos.p, positions, sizeof(double) * 2 * n, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(counters.p, 0, 5 * sizeof(unsigned long long), s));
+    HIPCHK(counters.clear(s));
     clk.mark(s);
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
     const double2* d_pos = (const double2*)pos.p;
     unsigned char* d_used = method_used ? used.as<unsigned char>() : nullptr;
-    unsigned long long* d_cnt = counters.as<unsigned long long>();
+    unsigned long long* d_cnt = counters.d();
     switch (cfg->method) {
     case LIO_GRID_NEAREST:
         hipLaunchKernelGGL(k_grid_sample<LIO_GRID_NEAREST>, grid, block, 0, s, g->G, L, n_layers, cfg->border_mode, d_pos, (int)n, val.as<float>(), d_used, d_cnt);
@@ -289,24 +294,16 @@ try {
     unsigned long long hc[5] = { 0, 0, 0, 0, 0 };
     HIPCHK(hipMemcpyAsync(values, val.p, sizeof(float) * pairs, hipMemcpyDeviceToHost, s));
     if (method_used) HIPCHK(hipMemcpyAsync(method_used, used.p, pairs, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(hc, counters.p, sizeof(hc), hipMemcpyDeviceToHost, s));
-    clk.mark(s);
-    const hipError_t e = hipStreamSynchronize(s);          // the call's one host wait (the temporaries go back to the pool after it)
-    HIPCHK(e);
-    HIPCHK(hipGetLastError());
+    if ((rc = counters.finish(hc, s, &clk)) != LIO_OK) return rc;       // the call's one host wait
     if (info) {
         for (int m = 0; m < 4; ++m) info->n_method[m] = (int64_t)hc[m];
         info->n_outside = (int64_t)hc[4];
     }
-    if (clk.on && clk.n == 4)
-        for (int k = 0; k < 3; ++k)
-            if (hipEventElapsedTime(&t_stage_ms[k], clk.ev[k], clk.ev[k + 1]) != hipSuccess) t_stage_ms[k] = 0.0f;
+    t_stage.read(clk);
     return LIO_OK;
 } LIO_CATCH
 
 extern "C" int lio_grid_debug_stage_ms(int32_t enable, float ms[3])
 try {
-    if (ms) memcpy(ms, t_stage_ms, sizeof(t_stage_ms));
-    t_stage_on = enable != 0;
-    return LIO_OK;
+    return t_stage.hook(enable, ms);
 } LIO_CATCH

@@ -119,21 +119,7 @@ __global__ __launch_bounds__(256) void k_gt_occupancy(const float* __restrict__ 
     if (q < n) data[q] = lio_gt_occupancy(layer[n - 1 - q], data_min, data_max);
 }
 
-thread_local float t_gt_ms[3] = { 0, 0, 0 };
-thread_local bool t_gt_on = false;
-
-struct GtClock {                   // four marks around the three stages, only when a caller asked for the times
-    hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
-    int n = 0;
-    bool on = false;
-    ~GtClock() { for (int k = 0; k < n; ++k) (void)hipEventDestroy(ev[k]); }
-    void mark(hipStream_t s)
-    {
-        if (!on || n >= 4) return;
-        if (hipEventCreate(&ev[n]) != hipSuccess) { on = false; return; }
-        (void)hipEventRecord(ev[n++], s);
-    }
-};
+thread_local LioStageTimes<3> t_gt;                        // four marks around the three stages of lio_grid_transform
 
 // No transformed height may be NaN (the rule's premise): with every term of the z row bounded so that the sum of their
 // magnitudes stays far below DBL_MAX, no partial sum overflows, and a sum of finite terms that does not overflow is finite.
@@ -161,8 +147,7 @@ try {
     if (src == dst) return lio_fail(LIO_ERR_ARG, "src and dst are the same object");
     if (src->device_id != dst->device_id) return lio_fail(LIO_ERR_ARG, "src and dst live on different devices");
     if (!src->mask) return lio_fail(LIO_ERR_ARG, "src holds no layers (lio_grid_set_layers, lio_kf_store_planning_grid)");
-    if (height_layer < 0 || height_layer >= LIO_GRID_MAX_LAYERS || !((src->mask >> height_layer) & 1u))
-        return lio_fail(LIO_ERR_ARG, "height_layer names a layer src does not hold");
+    if (!lio_grid_has_layer(src, height_layer)) return lio_fail(LIO_ERR_ARG, "height_layer names a layer src does not hold");
     const LioTerrGeom S = src->G;
     const double sample_length = S.res * sample_ratio;       // GM:344
     if (!gt_height_row_is_safe(S, T, sample_length)) return lio_fail(LIO_ERR_ARG, "the transform's z row could overflow a transformed height");
@@ -183,33 +168,30 @@ try {
     int rc = lio_check_device(src->device_id);
     if (rc != LIO_OK) return rc;
     if ((rc = lio_grid_set_geometry(dst, size[0], size[1], S.res, length, centre)) != LIO_OK) return rc;
+    LioGridRollback undo(dst, true);                         // after a failure dst holds no layer
     GtLayers L;
     memset(&L, 0, sizeof(L));
     for (int k = 0; k < LIO_GRID_MAX_LAYERS; ++k) {
         if (!((src->mask >> k) & 1u)) continue;
         float* d = nullptr;
-        if ((rc = lio_grid_layer_slot(dst, k, &d)) != LIO_OK) { lio_grid_clear(dst); return rc; }
+        if ((rc = lio_grid_layer_slot(dst, k, &d)) != LIO_OK) return rc;
         if (k == height_layer) L.height = L.n;
         L.src[L.n] = (const unsigned*)src->d_layer[k].p;
         L.dst[L.n] = (unsigned*)d;
         ++L.n;
     }
     const LioTerrGeom D = dst->G;
-    struct Undo {                  // after a failure dst holds no layer
-        lio_grid* g;
-        ~Undo() { if (g) lio_grid_clear(g); }
-    } undo = { dst };
     hipStream_t s = nullptr;
-    LioTemp keys, counters;
+    LioTemp keys;
+    LioGridCounters counters;
     HIPCHK(keys.alloc(sizeof(unsigned long long) * (size_t)n_new));
-    HIPCHK(counters.alloc(GT_N_CNT * sizeof(unsigned long long)));
-    GtClock clk;
-    clk.on = t_gt_on;
+    HIPCHK(counters.alloc(GT_N_CNT));
+    LioStageClock clk(t_gt.on);
     clk.mark(s);
     HIPCHK(hipMemsetAsync(keys.p, 0, sizeof(unsigned long long) * (size_t)n_new, s));
-    HIPCHK(hipMemsetAsync(counters.p, 0, GT_N_CNT * sizeof(unsigned long long), s));
+    HIPCHK(counters.clear(s));
     clk.mark(s);
-    unsigned long long* d_cnt = counters.as<unsigned long long>();
+    unsigned long long* d_cnt = counters.d();
     hipLaunchKernelGGL(k_gt_scatter, dim3((unsigned)((n_src + 255) / 256)), dim3(256), 0, s, S, D, T, sample_length, sample_ratio > 0.0 ? 5 : 1,
                        (const float*)src->d_layer[height_layer].p, (int)n_src, keys.as<unsigned long long>(), d_cnt);
     clk.mark(s);
@@ -217,11 +199,8 @@ try {
     hipLaunchKernelGGL(k_gt_gather, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, s, S, T, sample_length, L, keys.as<const unsigned long long>(), n_new,
                        d_cnt);
     unsigned long long hc[GT_N_CNT] = { 0, 0, 0 };
-    HIPCHK(hipMemcpyAsync(hc, counters.p, sizeof(hc), hipMemcpyDeviceToHost, s));
-    clk.mark(s);
-    HIPCHK(hipStreamSynchronize(s));                       // the call's one host wait (the temporaries go back to the pool after it)
-    HIPCHK(hipGetLastError());
-    undo.g = nullptr;
+    if ((rc = counters.finish(hc, s, &clk)) != LIO_OK) return rc;       // the call's one host wait
+    undo.commit();
     if (info) {
         info->rows = size[0]; info->cols = size[1];
         for (int a = 0; a < 2; ++a) { info->length[a] = length[a]; info->position[a] = centre[a]; }
@@ -229,9 +208,7 @@ try {
         info->n_samples_outside = (int64_t)hc[GT_CNT_OUTSIDE];
         info->n_cells_written = (int64_t)hc[GT_CNT_WRITTEN];
     }
-    if (clk.on && clk.n == 4)
-        for (int k = 0; k < 3; ++k)
-            if (hipEventElapsedTime(&t_gt_ms[k], clk.ev[k], clk.ev[k + 1]) != hipSuccess) t_gt_ms[k] = 0.0f;
+    t_gt.read(clk);
     return LIO_OK;
 } LIO_CATCH
 
@@ -241,7 +218,7 @@ try {
     if (desc) memset(desc, 0, sizeof(*desc));
     if (!std::isfinite(data_min) || !std::isfinite(data_max)) return lio_fail(LIO_ERR_ARG, "data_min and data_max must be finite");
     if (!g || !data) return lio_fail(LIO_ERR_ARG, "null argument");
-    if (layer < 0 || layer >= LIO_GRID_MAX_LAYERS || !((g->mask >> layer) & 1u)) return lio_fail(LIO_ERR_ARG, "the object holds no such layer");
+    if (!lio_grid_has_layer(g, layer)) return lio_fail(LIO_ERR_ARG, "the object holds no such layer");
     const size_t cells = (size_t)g->G.rows * (size_t)g->G.cols;
     if (cap_cells < cells) return lio_fail(LIO_ERR_ARG, "data holds fewer than rows x cols cells");
     int rc = lio_check_device(g->device_id);
@@ -264,7 +241,5 @@ try {
 
 extern "C" int lio_grid_transform_debug_stage_ms(int32_t enable, float ms[3])
 try {
-    if (ms) memcpy(ms, t_gt_ms, sizeof(t_gt_ms));
-    t_gt_on = enable != 0;
-    return LIO_OK;
+    return t_gt.hook(enable, ms);
 } LIO_CATCH

@@ -16,6 +16,7 @@
 #include <string.h>
 
 #include "lio_icp.h"
+#include "lio_cloud.h"
 #include "lio_kernels.h"
 #include "lio_kfstore.h"
 #include "lio_pool.h"
@@ -448,38 +449,15 @@ int lio_icp_choose_grid(const float* x, const float* y, const float* z, int n, c
     return LIO_OK;
 }
 
-// The target side of an alignment up to its grid: SoA copy, the box of the coordinates within LIO_MAX_COORD (per axis), the
-// grid at four points per occupied cell.  lio_icp_device and the test hook lio_icp_debug_grid both go through here.
-namespace {
-struct IcpTarget {
-    LioTemp tx, ty, tz, t4;
-    LioGrid g;
-    float edge = 1.0f;
-    bool any = false;         // the box holds a point on every axis
-    int occupied = -1;        // occupied cells of the trial grid (-1: none was laid, the box is a point)
-};
-
-int icp_target_grid(const float4* d_tgt, int n_tgt, hipStream_t s, IcpTarget& T)
+// The target side of an alignment up to its grid: the box step of lio_cloud.h, then the grid at four points per occupied
+// cell; no grid without a point on some axis.  lio_icp_device and the test hook lio_icp_debug_grid both go through here.
+static int icp_lay_grid(const float4* d_tgt, int n_tgt, hipStream_t s, LioSearchTarget& T)
 {
-    LioTemp bbox;
-    HIPCHK(T.tx.alloc(sizeof(float) * (size_t)n_tgt)); HIPCHK(T.ty.alloc(sizeof(float) * (size_t)n_tgt)); HIPCHK(T.tz.alloc(sizeof(float) * (size_t)n_tgt));
-    HIPCHK(T.t4.alloc(sizeof(float4) * (size_t)n_tgt));
-    HIPCHK(bbox.alloc(6 * sizeof(unsigned)));
-    lio_launch_xyzi4_to_soa(d_tgt, n_tgt, T.tx.as<float>(), T.ty.as<float>(), T.tz.as<float>(), T.t4.as<float4>(), s);
-    unsigned hb[6];
-    lio_ord_box_clear(hb);
-    HIPCHK(hipMemcpyAsync(bbox.p, hb, sizeof(hb), hipMemcpyHostToDevice, s));
-    lio_launch_map_bbox(T.tx.as<float>(), T.ty.as<float>(), T.tz.as<float>(), n_tgt, bbox.as<unsigned>(), s);
-    HIPCHK(hipMemcpyAsync(hb, bbox.p, sizeof(hb), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
     float mn[3], mx[3];
-    lio_ord_box_decode(hb, mn, mx);
-    T.any = true;
-    for (int a = 0; a < 3; ++a) T.any = T.any && hb[a] != LIO_ORD_NO_MIN && mn[a] <= mx[a];
-    if (!T.any) return LIO_OK;
+    const int rc = lio_search_target_box(d_tgt, n_tgt, s, T, mn, mx);
+    if (rc != LIO_OK || !T.any) return rc;
     return lio_icp_choose_grid(T.tx.as<float>(), T.ty.as<float>(), T.tz.as<float>(), n_tgt, mn, mx, 4.0f, s, &T.g, &T.edge, &T.occupied);
 }
-}  // namespace
 
 int lio_icp_device(const float4* d_src, int n_src, const float4* d_tgt, int n_tgt, const lio_icp_config& cfg, const float* guess,
                    lio_icp_result* res, hipStream_t s, LioIcpTrace* trace, float4* d_closed)
@@ -492,26 +470,16 @@ int lio_icp_device(const float4* d_src, int n_src, const float4* d_tgt, int n_tg
         HIPCHK(hipStreamSynchronize(s));
         return LIO_OK;
     }
-    // ---- the target: SoA, box, grid (icp_target_grid), cell sort
-    IcpTarget tg;
-    int rc = icp_target_grid(d_tgt, n_tgt, s, tg);
+    // ---- the target: SoA, box, grid (icp_lay_grid), cell sort
+    LioSearchTarget tg;
+    int rc = icp_lay_grid(d_tgt, n_tgt, s, tg);
     if (rc != LIO_OK) return rc;
     if (!tg.any) {                                                     // no target point within the bound: nothing to correspond with
         if (d_closed) HIPCHK(hipMemcpyAsync(d_closed, d_src, sizeof(float4) * (size_t)n_src, hipMemcpyDeviceToDevice, s));
         HIPCHK(hipStreamSynchronize(s));
         return LIO_OK;
     }
-    LioTemp &tx = tg.tx, &ty = tg.ty, &tz = tg.tz;
-    const LioGrid& g = tg.g;
-    const float edge = tg.edge;
-    LioTemp cell_of, cell_count, cell_start, tiles, sorted;
-    HIPCHK(cell_of.alloc(sizeof(int) * (size_t)n_tgt));
-    HIPCHK(cell_count.alloc(sizeof(int) * (size_t)g.n_cells));
-    HIPCHK(cell_start.alloc(sizeof(int) * ((size_t)g.n_cells + 1)));
-    HIPCHK(tiles.alloc(sizeof(int) * ((size_t)lio_scan_tiles(g.n_cells) + 2)));
-    HIPCHK(sorted.alloc(sizeof(float4) * (size_t)n_tgt));
-    lio_launch_map_cell_sort(g, tx.as<float>(), ty.as<float>(), tz.as<float>(), n_tgt, cell_of.as<int>(), cell_count.as<int>(),
-                             cell_start.as<int>(), tiles.as<int>(), sorted.as<float4>(), s);
+    if ((rc = lio_search_target_sort(n_tgt, s, tg)) != LIO_OK) return rc;
     // ---- state, trace, loop
     const int n_wg = (n_src + 255) / 256, mi = cfg.max_iters;
     LioTemp cur, d_st, partials, tr_step, tr_ncorr, tr_mse, corr_rec;
@@ -534,10 +502,10 @@ int lio_icp_device(const float4* d_src, int n_src, const float4* d_tgt, int n_tg
     HIPCHK(hipMemcpyAsync(cur.p, d_src, sizeof(float4) * (size_t)n_src, hipMemcpyDeviceToDevice, s));
     LioIcpParams P;
     memset(&P, 0, sizeof(P));
-    P.g = g; P.cell = edge;
+    P.g = tg.g; P.cell = tg.edge;
     P.gate2 = cfg.max_corr_dist * cfg.max_corr_dist;
     P.reach = (float)cfg.max_corr_dist * 1.0001f + 1.0e-6f;
-    P.cell_start = cell_start.as<int>(); P.sorted = sorted.as<float4>();
+    P.cell_start = tg.cell_start.as<int>(); P.sorted = tg.sorted.as<float4>();
     P.src = d_src; P.cur = cur.as<float4>(); P.closed = d_closed; P.n_src = n_src;
     P.st = d_st.as<LioIcpState>(); P.partials = partials.as<double>();
     P.tr_step = tr_step.as<float>(); P.tr_ncorr = tr_ncorr.as<int>(); P.tr_mse = tr_mse.as<double>();
@@ -653,8 +621,8 @@ try {
     hipStream_t s = nullptr;
     LioTemp raw_t, d_tgt;
     if ((rc = icp_upload(target, n_target, target_stride, raw_t, d_tgt, s)) != LIO_OK) return rc;
-    IcpTarget tg;
-    if ((rc = icp_target_grid(d_tgt.as<float4>(), (int)n_target, s, tg)) != LIO_OK) return rc;
+    LioSearchTarget tg;
+    if ((rc = icp_lay_grid(d_tgt.as<float4>(), (int)n_target, s, tg)) != LIO_OK) return rc;
     if (!tg.any) return LIO_OK;
     out->any = 1;
     out->origin[0] = tg.g.ox; out->origin[1] = tg.g.oy; out->origin[2] = tg.g.oz;

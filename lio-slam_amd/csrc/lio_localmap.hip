@@ -14,6 +14,7 @@
 #include <string.h>
 
 #include "lio_localmap.h"
+#include "lio_cloud.h"
 #include "lio_compact.h"
 #include "lio_icp.h"
 #include "lio_kernels.h"
@@ -232,41 +233,20 @@ int lio_sor_check(int32_t mean_k, float stddev_mul)
     return LIO_OK;
 }
 
-// The filter's steps up to its grid: SoA copy, the box of the participating coordinates (per axis), lio_icp_choose_grid at
-// (mean_k + 1) / 3 points per occupied cell.  lio_sor_device and the test hook lio_sor_debug_grid both go through here.
-namespace {
-struct SorTarget {
-    LioTemp tx, ty, tz, t4;
-    LioGrid g;
-    float edge = 1.0f;
-    bool any = false;         // the box holds a point on every axis (else: one empty cell at the origin)
-    int occupied = -1;        // occupied cells of the trial grid (-1: none was laid, the box is a point)
-};
-
-int sor_target_grid(const float4* d_pts, int n, int mean_k, hipStream_t s, SorTarget& T)
+// The filter's steps up to its grid: the box step of lio_cloud.h (one empty cell at the origin without a point on some axis),
+// then lio_icp_choose_grid at (mean_k + 1) / 3 points per occupied cell.  lio_sor_device and the test hook
+// lio_sor_debug_grid both go through here.
+static int sor_lay_grid(const float4* d_pts, int n, int mean_k, hipStream_t s, LioSearchTarget& T)
 {
-    LioTemp bbox;
-    HIPCHK(T.tx.alloc(sizeof(float) * (size_t)n)); HIPCHK(T.ty.alloc(sizeof(float) * (size_t)n)); HIPCHK(T.tz.alloc(sizeof(float) * (size_t)n));
-    HIPCHK(T.t4.alloc(sizeof(float4) * (size_t)n));
-    HIPCHK(bbox.alloc(6 * sizeof(unsigned)));
-    lio_launch_xyzi4_to_soa(d_pts, n, T.tx.as<float>(), T.ty.as<float>(), T.tz.as<float>(), T.t4.as<float4>(), s);
-    unsigned hb[6];
-    lio_ord_box_clear(hb);
-    HIPCHK(hipMemcpyAsync(bbox.p, hb, sizeof(hb), hipMemcpyHostToDevice, s));
-    lio_launch_map_bbox(T.tx.as<float>(), T.ty.as<float>(), T.tz.as<float>(), n, bbox.as<unsigned>(), s);
-    HIPCHK(hipMemcpyAsync(hb, bbox.p, sizeof(hb), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
     float mn[3], mx[3];
-    lio_ord_box_decode(hb, mn, mx);
-    T.any = true;
-    for (int a = 0; a < 3; ++a) T.any = T.any && hb[a] != LIO_ORD_NO_MIN && mn[a] <= mx[a];
+    const int rc = lio_search_target_box(d_pts, n, s, T, mn, mx);
+    if (rc != LIO_OK) return rc;
     if (!T.any) { mn[0] = mn[1] = mn[2] = 0.0f; mx[0] = mx[1] = mx[2] = 0.0f; }       // no finite point: one empty cell
     // Edge: the walk stops after shell 1 once the sphere of one edge around the point holds the k entries; on a surface
     // that sphere holds about pi times the points of a cell, so k / 3 per occupied cell (3.7 at mean_k 10).
     return lio_icp_choose_grid(T.tx.as<float>(), T.ty.as<float>(), T.tz.as<float>(), n, mn, mx, (float)(mean_k + 1) / 3.0f, s, &T.g, &T.edge,
                                &T.occupied);
 }
-}  // namespace
 
 int lio_sor_device(const float4* d_pts, int n, int mean_k, float stddev_mul, LioTemp& out, int* n_out, float* d_mean_dist,
                    LioSorReport* rep, hipStream_t s)
@@ -276,29 +256,19 @@ int lio_sor_device(const float4* d_pts, int n, int mean_k, float stddev_mul, Lio
     int rc = lio_sor_check(mean_k, stddev_mul);
     if (rc != LIO_OK) return rc;
     if (n <= 0) { rep->passthrough = 1; rep->threshold = INFINITY; HIPCHK(out.alloc(16)); return 1; }
-    // ---- the cloud as its own search target: SoA, box of its finite points, grid (sor_target_grid), cell sort
-    SorTarget tg;
-    LioTemp dist;
+    // ---- the cloud as its own search target: SoA, box of its finite points, grid (sor_lay_grid), cell sort
+    LioSearchTarget tg;
+    LioTemp dist, partials, d_st;
     if (!d_mean_dist) { HIPCHK(dist.alloc(sizeof(float) * (size_t)n)); d_mean_dist = dist.as<float>(); }
-    if ((rc = sor_target_grid(d_pts, n, mean_k, s, tg)) != LIO_OK) return rc;
-    LioTemp &tx = tg.tx, &ty = tg.ty, &tz = tg.tz;
-    const LioGrid& g = tg.g;
-    const float edge = tg.edge;
-    LioTemp cell_of, cell_count, cell_start, tiles, sorted, partials, d_st;
+    if ((rc = sor_lay_grid(d_pts, n, mean_k, s, tg)) != LIO_OK) return rc;
     const int n_wg = (n + 255) / 256;
-    HIPCHK(cell_of.alloc(sizeof(int) * (size_t)n));
-    HIPCHK(cell_count.alloc(sizeof(int) * (size_t)g.n_cells));
-    HIPCHK(cell_start.alloc(sizeof(int) * ((size_t)g.n_cells + 1)));
-    HIPCHK(tiles.alloc(sizeof(int) * ((size_t)lio_scan_tiles(g.n_cells) + 2)));
-    HIPCHK(sorted.alloc(sizeof(float4) * (size_t)n));
     HIPCHK(partials.alloc(sizeof(double) * 3 * (size_t)n_wg));
     HIPCHK(d_st.alloc(sizeof(LioSorStats)));
-    lio_launch_map_cell_sort(g, tx.as<float>(), ty.as<float>(), tz.as<float>(), n, cell_of.as<int>(), cell_count.as<int>(),
-                             cell_start.as<int>(), tiles.as<int>(), sorted.as<float4>(), s);
+    if ((rc = lio_search_target_sort(n, s, tg)) != LIO_OK) return rc;
     LioSorParams P;
     memset(&P, 0, sizeof(P));
-    P.g = g; P.cell = edge;
-    P.cell_start = cell_start.as<int>(); P.sorted = sorted.as<float4>(); P.pts = d_pts;
+    P.g = tg.g; P.cell = tg.edge;
+    P.cell_start = tg.cell_start.as<int>(); P.sorted = tg.sorted.as<float4>(); P.pts = d_pts;
     P.n = n; P.k = mean_k + 1;
     P.mean_dist = d_mean_dist; P.partials = partials.as<double>();
     hipLaunchKernelGGL(k_sor_search, dim3(n_wg), dim3(256), 0, s, P);
@@ -361,8 +331,8 @@ try {
     LioTemp raw, xyzi;
     HIPCHK(xyzi.alloc(n * sizeof(float4)));
     if ((rc = lio_upload_xyzi(pts, n, stride, stride >= 20 ? 16 : -1, raw, xyzi.as<float4>(), s)) != LIO_OK) return rc;
-    SorTarget tg;
-    if ((rc = sor_target_grid(xyzi.as<float4>(), (int)n, mean_k, s, tg)) != LIO_OK) return rc;
+    LioSearchTarget tg;
+    if ((rc = sor_lay_grid(xyzi.as<float4>(), (int)n, mean_k, s, tg)) != LIO_OK) return rc;
     out->any = tg.any ? 1 : 0;
     out->origin[0] = tg.g.ox; out->origin[1] = tg.g.oy; out->origin[2] = tg.g.oz;
     out->edge = tg.edge; out->inv_cell = tg.g.inv_cell;

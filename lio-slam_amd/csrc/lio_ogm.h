@@ -147,11 +147,11 @@ int lio_ogm_check(const lio_ogm_config* cfg);
 // null selects the form that stops a lane once k_i > min_neighbors.
 int lio_radius_device(const float4* d_pts, int n, float radius, int min_neighbors, LioTemp& out, int* n_out, int* d_count, hipStream_t s);
 
-// stage times of one chain, in ms (HIP events on the chain's stream): filled when lio_ogm_device is given one
-struct LioOgmTimes { float slice, grid_build, search, compact, raster, copy; };
+// stage times of one chain, in ms (HIP events on the chain's stream): slice, grid build, search, compaction, raster, grid copy
+enum { LIO_OGM_N_STAGES = 6 };
 
 // The draft's chain on a device-resident float4 cloud on stream `s`: slice, filter, raster; the grid (may be null) and *info
-// to the host.  Synchronous.  info->n_in is set to n.
+// to the host.  Synchronous.  info->n_in is set to n.  times (may be null): LIO_OGM_N_STAGES floats, filled with the stage times.
 int lio_ogm_device(const float4* d_pts, int n, const lio_ogm_config& cfg, int8_t* grid, size_t grid_cap, lio_ogm_info* info, hipStream_t s,
-                   LioOgmTimes* times);
-LioOgmTimes* lio_ogm_times_wanted(void);     // the calling thread's request (lio_ogm_debug_stage_ms), or null
+                   float* times);
+float* lio_ogm_times_wanted(void);           // the calling thread's request (lio_ogm_debug_stage_ms): where its times go, or null

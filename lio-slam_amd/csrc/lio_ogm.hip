@@ -20,6 +20,7 @@
 #include "lio_compact.h"
 #include "lio_kernels.h"
 #include "lio_pool.h"
+#include "lio_stageclock.h"
 #include "lio_wg.h"
 
 namespace {
@@ -125,94 +126,53 @@ __global__ __launch_bounds__(256) void k_ogm_occupied(const uint4* __restrict__ 
     if ((threadIdx.x & 63) == 0 && c) atomicAdd(&counts[1], c);
 }
 
-// stage boundaries as HIP events on the chain's stream, only when a caller asked for the times
-struct OgmClock {
-    enum { N = 8 };
-    hipEvent_t ev[N] = {};
-    bool on = false;
-    ~OgmClock() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
-    hipError_t start(bool want)
-    {
-        on = want;
-        for (int k = 0; on && k < N; ++k) {
-            const hipError_t e = hipEventCreate(&ev[k]);
-            if (e != hipSuccess) return e;
-        }
-        return hipSuccess;
-    }
-    void mark(int k, hipStream_t s) { if (on) (void)hipEventRecord(ev[k], s); }
-    float ms(int a, int b) const
-    {
-        float t = 0.0f;
-        return on && hipEventElapsedTime(&t, ev[a], ev[b]) == hipSuccess ? t : 0.0f;
-    }
-};
-
-// marks 1 (before the grid build), 2 (before the search), 3 (before the compaction), 4 (after it)
+// The chain's clock takes its marks in order: 0 before the slice (lio_ogm_device), here 1 (before the grid build), 2 (before
+// the search), 3 (before the compaction), 4 (after it), then 5 after the raster and 6 after the grid copy.
 int radius_device(const float4* d_pts, int n, float radius, int min_neighbors, LioTemp& out, int* n_out, int* d_count, hipStream_t s,
-                  OgmClock* clk)
+                  LioStageClock* clk)
 {
     *n_out = 0;
     int rc = lio_radius_check(radius, min_neighbors);
     if (rc != LIO_OK) return rc;
-    if (clk) clk->mark(1, s);
+    if (clk) clk->mark(s);
     if (n <= 0) {
         HIPCHK(out.alloc(16));
-        if (clk) { clk->mark(2, s); clk->mark(3, s); clk->mark(4, s); }
+        if (clk) { clk->mark(s); clk->mark(s); clk->mark(s); }
         return LIO_OK;
     }
-    // ---- the cloud as its own search target: SoA, box of the points that take part, grid, cell sort (as lio_sor_device)
-    LioTemp tx, ty, tz, t4, bbox, own;
-    HIPCHK(tx.alloc(sizeof(float) * (size_t)n)); HIPCHK(ty.alloc(sizeof(float) * (size_t)n)); HIPCHK(tz.alloc(sizeof(float) * (size_t)n));
-    HIPCHK(t4.alloc(sizeof(float4) * (size_t)n));
-    HIPCHK(bbox.alloc(6 * sizeof(unsigned)));
+    // ---- the cloud as its own search target (lio_cloud.h): the box of the points that take part, one empty cell at the origin
+    // without one, the grid from the radius alone, the cell sort
+    LioSearchTarget tg;
+    LioTemp own;
     const bool exact = d_count != nullptr;
     if (!exact) { HIPCHK(own.alloc(sizeof(int) * (size_t)n)); d_count = own.as<int>(); }
-    lio_launch_xyzi4_to_soa(d_pts, n, tx.as<float>(), ty.as<float>(), tz.as<float>(), t4.as<float4>(), s);
-    unsigned hb[6];
-    lio_ord_box_clear(hb);
-    HIPCHK(hipMemcpyAsync(bbox.p, hb, sizeof(hb), hipMemcpyHostToDevice, s));
-    lio_launch_map_bbox(tx.as<float>(), ty.as<float>(), tz.as<float>(), n, bbox.as<unsigned>(), s);
-    HIPCHK(hipMemcpyAsync(hb, bbox.p, sizeof(hb), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
     float mn[3], mx[3];
-    lio_ord_box_decode(hb, mn, mx);
-    bool any = true;
-    for (int a = 0; a < 3; ++a) any = any && hb[a] != LIO_ORD_NO_MIN && mn[a] <= mx[a];
-    if (!any) { mn[0] = mn[1] = mn[2] = 0.0f; mx[0] = mx[1] = mx[2] = 0.0f; }       // no such point: one empty cell
-    LioGrid g;
-    lio_ogm_choose_grid(mn, mx, radius, &g);
-    LioTemp cell_of, cell_count, cell_start, tiles, sorted;
-    HIPCHK(cell_of.alloc(sizeof(int) * (size_t)n));
-    HIPCHK(cell_count.alloc(sizeof(int) * (size_t)g.n_cells));
-    HIPCHK(cell_start.alloc(sizeof(int) * ((size_t)g.n_cells + 1)));
-    HIPCHK(tiles.alloc(sizeof(int) * ((size_t)lio_scan_tiles(g.n_cells) + 2)));
-    HIPCHK(sorted.alloc(sizeof(float4) * (size_t)n));
-    lio_launch_map_cell_sort(g, tx.as<float>(), ty.as<float>(), tz.as<float>(), n, cell_of.as<int>(), cell_count.as<int>(),
-                             cell_start.as<int>(), tiles.as<int>(), sorted.as<float4>(), s);
+    if ((rc = lio_search_target_box(d_pts, n, s, tg, mn, mx)) != LIO_OK) return rc;
+    if (!tg.any) { mn[0] = mn[1] = mn[2] = 0.0f; mx[0] = mx[1] = mx[2] = 0.0f; }
+    lio_ogm_choose_grid(mn, mx, radius, &tg.g);
+    if ((rc = lio_search_target_sort(n, s, tg)) != LIO_OK) return rc;
     HIPCHK(hipMemsetAsync(d_count, 0xff, sizeof(int) * (size_t)n, s));               // -1: takes no part
-    if (clk) clk->mark(2, s);
+    if (clk) clk->mark(s);
     OgmSearch P;
     memset(&P, 0, sizeof(P));
-    P.g = g; P.cell_start = cell_start.as<int>(); P.sorted = sorted.as<float4>();
+    P.g = tg.g; P.cell_start = tg.cell_start.as<int>(); P.sorted = tg.sorted.as<float4>();
     P.r2 = (float)((double)radius * (double)radius);
     P.stop_above = exact ? INT_MAX : min_neighbors;
     P.count = d_count;
     hipLaunchKernelGGL(k_ogm_search, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, P);
-    if (clk) clk->mark(3, s);
+    if (clk) clk->mark(s);
     OgmKeepPred pred;
     pred.src = d_pts; pred.count = d_count; pred.min_neighbors = min_neighbors;
     if ((rc = compact_device(pred, n, out, n_out, s)) != LIO_OK) return rc;
-    if (clk) clk->mark(4, s);
+    if (clk) clk->mark(s);
     return LIO_OK;
 }
 
-thread_local LioOgmTimes t_times;
-thread_local bool t_times_on = false;
+thread_local LioStageTimes<LIO_OGM_N_STAGES> t_times;
 
 }  // namespace
 
-LioOgmTimes* lio_ogm_times_wanted(void) { return t_times_on ? &t_times : nullptr; }
+float* lio_ogm_times_wanted(void) { return t_times.on ? t_times.ms : nullptr; }
 
 int lio_radius_check(float radius, int32_t min_neighbors)
 {
@@ -239,18 +199,17 @@ int lio_radius_device(const float4* d_pts, int n, float radius, int min_neighbor
 }
 
 int lio_ogm_device(const float4* d_pts, int n, const lio_ogm_config& cfg, int8_t* grid, size_t grid_cap, lio_ogm_info* info, hipStream_t s,
-                   LioOgmTimes* times)
+                   float* times)
 {
     memset(info, 0, sizeof(*info));
     info->n_in = n;
-    if (times) memset(times, 0, sizeof(*times));
+    if (times) memset(times, 0, sizeof(float) * LIO_OGM_N_STAGES);
     int rc = lio_ogm_check(&cfg);
     if (rc != LIO_OK) return rc;
     if (n <= 0) return LIO_OK;
-    OgmClock clk;
-    HIPCHK(clk.start(times != nullptr));
+    LioStageClock clk(times != nullptr);
     // ---- slice
-    clk.mark(0, s);
+    clk.mark(s);
     LioTemp sl, inl;
     OgmSlicePred slice;
     slice.src = d_pts; slice.lo = cfg.z_min; slice.hi = cfg.z_max; slice.negative = cfg.z_negative;
@@ -264,7 +223,7 @@ int lio_ogm_device(const float4* d_pts, int n, const lio_ogm_config& cfg, int8_t
         if ((rc = radius_device(cur, n_cur, cfg.radius, cfg.min_neighbors, inl, &n_inl, nullptr, s, &clk)) != LIO_OK) return rc;
         cur = inl.as<float4>(); n_cur = n_inl;
     } else {
-        for (int k = 1; k <= 4; ++k) clk.mark(k, s);
+        for (int k = 1; k <= 4; ++k) clk.mark(s);
     }
     info->n_inliers = n_cur;
     if (n_cur == 0) { HIPCHK(hipStreamSynchronize(s)); return LIO_OK; }
@@ -306,16 +265,14 @@ int lio_ogm_device(const float4* d_pts, int n, const lio_ogm_config& cfg, int8_t
     }
     int hc[2] = { 0, 0 };
     HIPCHK(hipMemcpyAsync(hc, counts.p, sizeof(hc), hipMemcpyDeviceToHost, s));
-    clk.mark(5, s);
+    clk.mark(s);
     if (grid) HIPCHK(hipMemcpyAsync(grid, d_grid.p, cells, hipMemcpyDeviceToHost, s));
-    clk.mark(6, s);
+    clk.mark(s);
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
     info->n_binned = hc[0]; info->n_occupied = hc[1];
-    if (times) {
-        times->slice = clk.ms(0, 1); times->grid_build = clk.ms(1, 2); times->search = clk.ms(2, 3); times->compact = clk.ms(3, 4);
-        times->raster = clk.ms(4, 5); times->copy = clk.ms(5, 6);
-    }
+    if (times)
+        for (int k = 0; k < LIO_OGM_N_STAGES; ++k) times[k] = clk.ms((size_t)k);
     return LIO_OK;
 }
 
@@ -335,12 +292,7 @@ extern "C" void lio_ogm_default_config(lio_ogm_config* cfg)
 // NULL) receives the last chain's slice, grid build, search, compaction, raster and grid copy, in ms.
 extern "C" int lio_ogm_debug_stage_ms(int32_t enable, float ms[6])
 try {
-    if (ms) {
-        const float v[6] = { t_times.slice, t_times.grid_build, t_times.search, t_times.compact, t_times.raster, t_times.copy };
-        memcpy(ms, v, sizeof(v));
-    }
-    t_times_on = enable != 0;
-    return LIO_OK;
+    return t_times.hook(enable, ms);
 } LIO_CATCH
 
 extern "C" int lio_radius_filter(int32_t device_id, const void* pts, size_t n, size_t stride, float radius, int32_t min_neighbors, void* out,

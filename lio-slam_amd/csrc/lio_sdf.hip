@@ -28,6 +28,7 @@
 #include "lio_cloud.h"
 #include "lio_planning.h"
 #include "lio_pool.h"
+#include "lio_stageclock.h"
 #include "lio_wg.h"
 
 #define SDF_CHUNK 32               // entries of a line staged per flush of k_sdf_cols; the rows a wave of k_sdf_rows owns
@@ -195,27 +196,7 @@ __global__ __launch_bounds__(256) void k_sdf_query(LioSdfLookup L, const float4*
 }
 
 // ---- the host side --------------------------------------------------------------------------------------------------------------
-struct SdfClock {                  // stage boundaries as HIP events on the build's stream, only when a caller asked for the times
-    std::vector<hipEvent_t> ev;
-    bool on = false;
-    ~SdfClock() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
-    void mark(hipStream_t s)
-    {
-        if (!on) return;
-        hipEvent_t e = nullptr;
-        if (hipEventCreate(&e) != hipSuccess) { on = false; return; }
-        ev.push_back(e);
-        (void)hipEventRecord(e, s);
-    }
-    float ms(size_t a) const
-    {
-        float t = 0.0f;
-        return on && a + 1 < ev.size() && hipEventElapsedTime(&t, ev[a], ev[a + 1]) == hipSuccess ? t : 0.0f;
-    }
-};
-
-thread_local float t_stage_ms[4] = { 0, 0, 0, 0 };
-thread_local bool t_stage_on = false;
+thread_local LioStageTimes<4> t_stage;                     // lio_sdf_build's four stages: the last complete measurement
 
 // the layers of a slab: as many as fit the workspace budget, at most a wave's worth of (layer, class) pairs
 int sdf_slab(size_t cells, int layers)
@@ -231,7 +212,7 @@ size_t sdf_stack_bounds(size_t cells, int slab) { return 2 * (size_t)slab * cell
 
 // Both sweeps of the layers [z0, z0 + slab) into dist (all layers) on stream s; nothing waits.
 template <bool OCC>
-void sdf_launch_slab(const SdfPass& P, const void* src, float* mid, float* dist, uint2* stack, hipStream_t s, SdfClock* clk)
+void sdf_launch_slab(const SdfPass& P, const void* src, float* mid, float* dist, uint2* stack, hipStream_t s, LioStageClock* clk)
 {
     const unsigned b1 = (unsigned)(((size_t)P.cols * 2 * (size_t)P.slab + 63) / 64);
     hipLaunchKernelGGL(k_sdf_cols<OCC>, dim3(b1), dim3(64), 0, s, P, src, mid, stack);
@@ -252,8 +233,7 @@ int lio_sdf_build_device(lio_sdf* sdf, const float* d_elev, int rows, int cols, 
     info->rows = rows; info->cols = cols; info->resolution = resolution;
     const size_t cells = (size_t)rows * (size_t)cols;
     if (2 * (long long)cells > LIO_SDF_MAX_NODES) return lio_fail(LIO_ERR_CAPACITY, "the field has more than LIO_SDF_NODE_LIMIT nodes (at least 2 layers)");
-    SdfClock clk;
-    clk.on = t_stage_on;
+    LioStageClock clk(t_stage.on);
     clk.mark(s);
     // ---- the layer's extremes: they size the field
     HIPCHK(sdf->d_stats.grow(4));
@@ -311,12 +291,12 @@ int lio_sdf_build_device(lio_sdf* sdf, const float* d_elev, int rows, int cols, 
     clk.mark(s);
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
-    if (clk.on && clk.ev.size() >= 4) {
-        t_stage_ms[0] = clk.ms(0);
-        t_stage_ms[1] = t_stage_ms[2] = 0.0f;
-        const size_t n_slabs = (clk.ev.size() - 4) / 2;         // marks: start, statistics read, buffers grown, two a slab, end
-        for (size_t k = 0; k < n_slabs; ++k) { t_stage_ms[1] += clk.ms(2 + 2 * k); t_stage_ms[2] += clk.ms(3 + 2 * k); }
-        t_stage_ms[3] = clk.ms(2 + 2 * n_slabs);
+    if (clk.count() >= 4) {
+        t_stage.ms[0] = clk.ms(0);
+        t_stage.ms[1] = t_stage.ms[2] = 0.0f;
+        const size_t n_slabs = (clk.count() - 4) / 2;           // marks: start, statistics read, buffers grown, two a slab, end
+        for (size_t k = 0; k < n_slabs; ++k) { t_stage.ms[1] += clk.ms(2 + 2 * k); t_stage.ms[2] += clk.ms(3 + 2 * k); }
+        t_stage.ms[3] = clk.ms(2 + 2 * n_slabs);
     }
     sdf->L = L;
     sdf->built = true;
@@ -501,7 +481,5 @@ try {
 
 extern "C" int lio_sdf_debug_stage_ms(int32_t enable, float ms[4])
 try {
-    if (ms) memcpy(ms, t_stage_ms, sizeof(t_stage_ms));
-    t_stage_on = enable != 0;
-    return LIO_OK;
+    return t_stage.hook(enable, ms);
 } LIO_CATCH

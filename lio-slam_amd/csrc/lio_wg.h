@@ -1,6 +1,6 @@
 // lio_wg.h -- the workgroup building blocks the feeder kernels share: the order-preserving float <-> uint mapping of the
-// bounding-box atomics, the exclusive scan over a workgroup (and the carry loop on top of it), and the min / max box of
-// three coordinates over a workgroup.  Device code besides the float-order pair.  Every reduction here has a FIXED shape
+// bounding-box atomics, the per-wave counter, the exclusive scan over a workgroup (and the carry loop on top of it), and
+// the min / max box of three coordinates over a workgroup.  Device code besides the float-order pair.  Every reduction here has a FIXED shape
 // (stated at each function); the results of the kernels that call them are pinned bit for bit by the tests, so keep it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -30,6 +30,15 @@ __host__ __device__ inline void lio_ord_box_clear(unsigned b[6])
 __host__ __device__ inline void lio_ord_box_decode(const unsigned b[6], float mn[3], float mx[3])
 {
     for (int a = 0; a < 3; ++a) { mn[a] = lio_ord2f(b[a]); mx[a] = lio_ord2f(b[3 + a]); }
+}
+
+// ---- counting --------------------------------------------------------------------------------------------------------
+// counters[which] += the lanes of the wave whose flag is set: one ballot, one atomic per wave (none where no lane has it).
+// Every lane of the wave must arrive.
+__device__ __forceinline__ void lio_wave_count(unsigned long long* counters, int which, bool flag)
+{
+    const unsigned long long m = __ballot(flag);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(&counters[which], (unsigned long long)__popcll(m));
 }
 
 // ---- exclusive scan -------------------------------------------------------------------------------------------------
