@@ -142,9 +142,9 @@ __global__ __launch_bounds__(256) void k_gc_occupancy(const int8_t* __restrict__
     bool unknown = false;
     if (i < n) {
         const unsigned w = lio_gc_occupancy_word(data[n - 1 - i]);
-        unknown = w == LIO_GC_QNAN;
+        unknown = w == LIO_QNAN_BITS;
         layer[i] = w;
-        for (int k = 0; k < F.n; ++k) F.p[k][i] = LIO_GC_QNAN;
+        for (int k = 0; k < F.n; ++k) F.p[k][i] = LIO_QNAN_BITS;
     }
     lio_wave_count(counters, GC_CNT_A, unknown);
 }
@@ -156,7 +156,7 @@ struct GcCloudPred {
 };
 struct GcCloudSink {
     LioGcCloud C;
-    LioTerrGeom G;
+    LioGridGeom G;
     unsigned* out;
     __device__ __forceinline__ void operator()(int at, const int& cell) const { lio_gc_cloud_record(C, G, cell, out + (size_t)at * (size_t)C.n_fields); }
 };
@@ -166,11 +166,11 @@ struct GcCellsPred {
     __device__ __forceinline__ bool operator()(int i, int& cell) const { cell = i; return lio_gc_cell_kept(layer[i], lower, upper); }
 };
 struct GcCellsSink {
-    LioTerrGeom G;
+    LioGridGeom G;
     double2* out;
     __device__ __forceinline__ void operator()(int at, const int& cell) const
     {
-        out[at] = make_double2(lio_terr_centre(G, 0, cell % G.rows), lio_terr_centre(G, 1, cell / G.rows));
+        out[at] = make_double2(lio_gm_centre(G, 0, cell % G.rows), lio_gm_centre(G, 1, cell / G.rows));
     }
 };
 struct GcSdfPred {
@@ -400,7 +400,7 @@ try {
     for (int a = 0; a < 2; ++a)                             // setGeometry's own size, GridMap.cpp:50
         if (round(length[a] / res) != (double)(a == 0 ? rows : cols)) return lio_fail(LIO_ERR_ARG, "round(length / resolution) is not the message's size");
     if (!g) return lio_fail(LIO_ERR_ARG, "null argument");
-    const LioTerrGeom& G = g->G;
+    const LioGridGeom& G = g->G;
     const bool replace = !g->mask || G.rows != rows || G.cols != cols || G.res != res || G.len[0] != length[0] || G.len[1] != length[1] ||
                          G.pos[0] != position[0] || G.pos[1] != position[1];
     if ((rc = lio_check_device(g->device_id)) != LIO_OK) return rc;
@@ -476,7 +476,7 @@ try {
         if ((basic_mask >> k) & 1u) C.basic[C.n_basic++] = (const unsigned*)g->d_layer[k].p;
     if (n_fields) *n_fields = C.n_fields;
     if ((rc = lio_check_device(g->device_id)) != LIO_OK) return rc;
-    const LioTerrGeom G = g->G;
+    const LioGridGeom G = g->G;
     return gc_compact_out<int>(pred, G.rows * G.cols, sizeof(float) * (size_t)C.n_fields, points, cap_points, n_out,
                                [&](void* p) { return GcCloudSink{ C, G, (unsigned*)p }; });
 } LIO_CATCH
@@ -490,7 +490,7 @@ try {
     if (!lio_grid_has_layer(g, layer)) return lio_fail(LIO_ERR_ARG, "the object holds no such layer");
     int rc = lio_check_device(g->device_id);
     if (rc != LIO_OK) return rc;
-    const LioTerrGeom G = g->G;
+    const LioGridGeom G = g->G;
     const GcCellsPred pred = { g->d_layer[layer].p, lower, upper };
     return gc_compact_out<int>(pred, G.rows * G.cols, sizeof(double2), cells, cap_cells, n_out, [&](void* p) { return GcCellsSink{ G, (double2*)p }; });
 } LIO_CATCH

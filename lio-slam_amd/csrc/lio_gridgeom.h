@@ -2,9 +2,8 @@
 // 282-330, 442-507, 554-627, 514-552; GMM = GridMapMath.cpp) behind the resident layer set (lio_gridgeom.hip): the geometry
 // each call decides on the host, and the per-cell work of the two gather kernels as __host__ __device__ functions, so that
 // the kernels and a host program (tools/grid_geom_host_check.cpp) run the same text.  Everything is fp64 in the order the
-// reference writes it and relies on -ffp-contract=off.  getPositionFromIndex is lio_terrain.h's lio_terr_centre,
-// getIndexFromPosition with checkIfPositionWithinMap lio_gridsample.h's lio_gs_index, boundPositionToRange with
-// getIndexFromPosition lio_terrain.h's lio_terr_index, setGeometry's size lio_gridtransform.h's lio_gt_size.  startIndex is
+// reference writes it and relies on -ffp-contract=off.  The geometry, its constructor and GridMapMath's index functions
+// (lio_gm_centre, lio_gm_index, lio_gm_bound_index, lio_gm_lookup, lio_gm_size) are lio_gridmath.h's.  startIndex is
 // always 0: every result is the reference's after convertToDefaultStartIndex (GM:677-707).  What runs on the device is
 // + - * /, compares and casts; fmod, round and copysign are in the host-only functions.  DESIGN.md section 4n lists the
 // conventions and the labelled deviations (parity unpinned).
@@ -14,62 +13,31 @@
 #include <math.h>
 #include <stdint.h>
 #include "../../include/liogpu.h"
-#include "lio_gridsample.h"
-#include "lio_gridtransform.h"
-#include "lio_terrain.h"
+#include "lio_gridmath.h"
 
-#define LIO_GG_HD __host__ __device__ __forceinline__
-#define LIO_GG_QNAN 0x7fc00000u
 #define LIO_GG_MAX_SHIFT 1073741824.0                        // 2^30: |position shift / resolution| stays below it
 
-// the members setGeometry leaves (GM:44-59) for a size already decided: length = size * resolution
-LIO_GG_HD LioTerrGeom lio_gg_geom(int rows, int cols, double res, double px, double py)
-{
-    LioTerrGeom G;
-    G.rows = rows; G.cols = cols; G.res = res;
-    G.pos[0] = px; G.pos[1] = py;
-    G.len[0] = (double)rows * res; G.len[1] = (double)cols * res;
-    for (int a = 0; a < 2; ++a) {
-        G.half[a] = 0.5 * G.len[a];                          // getVectorToOrigin
-        G.base[a] = G.pos[a] + (G.half[a] - 0.5 * res);      // mapPosition + getVectorToFirstCell
-    }
-    return G;
-}
-
-LIO_GG_HD bool lio_gg_word_finite(unsigned w) { return (w & 0x7f800000u) != 0x7f800000u; }       // isfinite on a float's bits
-
-// isInside then getIndex on G, as extendToInclude (GM:617-620) and addDataFrom (GM:539-542) call them: 0 the position is not
-// inside the map, 2 the index (*i, *j) is the cell's.  1: inside, but getIndex fails (a position within an ulp of the low
-// edge rounds to index n).  The reference ignores that verdict and reads past the buffer; the callers here skip the cell and
-// count it (the labelled deviation).  With no index out of range, what remains of lio_gs_index is checkIfPositionWithinMap.
-LIO_GG_HD int lio_gg_lookup(const LioTerrGeom& G, double px, double py, int* i, int* j)
-{
-    if (lio_gs_index(G, px, py, i, j)) return 2;
-    LioTerrGeom W = G;
-    W.rows = W.cols = 0x7fffffff;
-    int wi, wj;
-    return lio_gs_index(W, px, py, &wi, &wj) ? 1 : 0;
-}
+LIO_HD bool lio_gg_word_finite(unsigned w) { return (w & 0x7f800000u) != 0x7f800000u; }       // isfinite on a float's bits
 
 // ---- the geometry each call decides, on the host
 // getSubmapInformation (GMM:287-341), default start index.  halfTransform is -0.5 I: requested - halfTransform * length is
 // requested + 0.5 length bit for bit (the product's second term is -0.0 for a finite length >= 0), and likewise
 // - halfTransform * Constant(resolution) adds 0.5 resolution.  Both corners go through boundPositionToRange and
-// getIndexFromPosition (lio_terr_index).  A bounded corner whose index still fails there (a length whose last ulp swallows
-// the epsilon) is brought back to the last cell, where the reference returns false: lio_terr_index's labelled deviation.
+// getIndexFromPosition (lio_gm_bound_index).  A bounded corner whose index still fails there (a length whose last ulp swallows
+// the epsilon) is brought back to the last cell, where the reference returns false: lio_gm_bound_index's labelled deviation.
 struct LioGgSubmap {
     int ok;                        // getSubmapInformation's return value
     int top_left[2], size[2], requested[2];
     double length[2], position[2];
 };
 
-inline void lio_gg_submap_information(const LioTerrGeom& G, const double position[2], const double length[2], LioGgSubmap* S)
+inline void lio_gg_submap_information(const LioGridGeom& G, const double position[2], const double length[2], LioGgSubmap* S)
 {
     double corner[2];
     for (int a = 0; a < 2; ++a) {
-        S->top_left[a] = lio_terr_index(G, a, position[a] + 0.5 * length[a]);
-        const int bottom_right = lio_terr_index(G, a, position[a] - 0.5 * length[a]);
-        corner[a] = lio_terr_centre(G, a, S->top_left[a]) + 0.5 * G.res;
+        S->top_left[a] = lio_gm_bound_index(G, a, position[a] + 0.5 * length[a]);
+        const int bottom_right = lio_gm_bound_index(G, a, position[a] - 0.5 * length[a]);
+        corner[a] = lio_gm_centre(G, a, S->top_left[a]) + 0.5 * G.res;
         S->size[a] = bottom_right - S->top_left[a] + 1;
         S->length[a] = (double)S->size[a] * G.res;
         S->position[a] = corner[a] - 0.5 * S->length[a];
@@ -77,8 +45,8 @@ inline void lio_gg_submap_information(const LioTerrGeom& G, const double positio
     S->requested[0] = S->requested[1] = 0;
     S->ok = 0;
     if (S->size[0] < 1 || S->size[1] < 1) return;
-    const LioTerrGeom M = lio_gg_geom(S->size[0], S->size[1], G.res, S->position[0], S->position[1]);
-    S->ok = lio_gs_index(M, position[0], position[1], &S->requested[0], &S->requested[1]) ? 1 : 0;
+    const LioGridGeom M = lio_gm_geom(S->size[0], S->size[1], G.res, S->position[0], S->position[1]);
+    S->ok = lio_gm_index(M, position[0], position[1], &S->requested[0], &S->requested[1]) ? 1 : 0;
 }
 
 // getIndexShiftFromPositionShift (GMM:183-196), one component: (int)(v + 0.5 * (v > 0 ? 1 : -1)) with v = shift / resolution,
@@ -140,13 +108,13 @@ struct LioGgTable {
 // The integer-offset form (getSubmap's block copy; move followed by convertToDefaultStartIndex): destination cell (r, c) of a
 // grid of d_rows rows takes source cell (r + off0, c + off1) of the s_rows x s_cols grid where that exists, the quiet NaN
 // elsewhere.  Returns whether the cell was cleared.
-LIO_GG_HD bool lio_gg_offset_cell(const LioGgTable& T, int d_rows, int s_rows, int s_cols, int off0, int off1, int r, int c)
+LIO_HD bool lio_gg_offset_cell(const LioGgTable& T, int d_rows, int s_rows, int s_cols, int off0, int off1, int r, int c)
 {
     const long long sr = (long long)r + (long long)off0, sc = (long long)c + (long long)off1;
     const bool in = sr >= 0 && sr < (long long)s_rows && sc >= 0 && sc < (long long)s_cols;
     const size_t at = (size_t)c * (size_t)d_rows + (size_t)r;
     const size_t from = in ? (size_t)sc * (size_t)s_rows + (size_t)sr : 0;
-    for (int k = 0; k < T.n; ++k) T.dst[k][at] = in ? T.self[k][from] : LIO_GG_QNAN;
+    for (int k = 0; k < T.n; ++k) T.dst[k][at] = in ? T.self[k][from] : LIO_QNAN_BITS;
     return !in;
 }
 
@@ -169,18 +137,18 @@ struct LioGgCellCount {
 //   LIO_GG_ADD     the loop of addDataFrom (GM:532-549) on those values: valid = every basic slot finite (none: false);
 //                  skipped if valid and not LIO_GG_OVERWRITE; isInside and getIndex on X; each slot with an `other` layer takes
 //                  that cell's bits where they are finite.
-LIO_GG_HD void lio_gg_position_cell(const LioGgTable& T, const LioTerrGeom& N, const LioTerrGeom& O, const LioTerrGeom& X, int flags, int r, int c,
+LIO_HD void lio_gg_position_cell(const LioGgTable& T, const LioGridGeom& N, const LioGridGeom& O, const LioGridGeom& X, int flags, int r, int c,
                                     LioGgCellCount* n)
 {
     const size_t at = (size_t)c * (size_t)N.rows + (size_t)r;
-    const double cx = lio_terr_centre(N, 0, r), cy = lio_terr_centre(N, 1, c);
+    const double cx = lio_gm_centre(N, 0, r), cy = lio_gm_centre(N, 1, c);
     n->kept = n->skipped_valid = n->outside_other = n->index_outside_self = n->index_outside_other = false;
     n->copied = 0;
     bool have_self = true;
     size_t self_at = at;
     if (flags & LIO_GG_RESIZE) {
         int i, j;
-        const int st = lio_gg_lookup(O, cx, cy, &i, &j);
+        const int st = lio_gm_lookup(O, cx, cy, &i, &j);
         have_self = n->kept = st == 2;
         n->index_outside_self = st == 1;
         self_at = have_self ? (size_t)j * (size_t)O.rows + (size_t)i : 0;
@@ -195,7 +163,7 @@ LIO_GG_HD void lio_gg_position_cell(const LioGgTable& T, const LioTerrGeom& N, c
             n->skipped_valid = true;
         } else {
             int i, j;
-            const int st = lio_gg_lookup(X, cx, cy, &i, &j);
+            const int st = lio_gm_lookup(X, cx, cy, &i, &j);
             n->outside_other = st == 0;
             n->index_outside_other = st == 1;
             take = st == 2;
@@ -203,7 +171,7 @@ LIO_GG_HD void lio_gg_position_cell(const LioGgTable& T, const LioTerrGeom& N, c
         }
     }
     for (int k = 0; k < T.n; ++k) {
-        unsigned w = LIO_GG_QNAN;
+        unsigned w = LIO_QNAN_BITS;
         bool copied = false;
         if (take && T.other[k]) {
             const unsigned o = T.other[k][from];

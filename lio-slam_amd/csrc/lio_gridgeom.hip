@@ -21,6 +21,7 @@
 #include <string.h>
 
 #include "lio_gridgeom.h"
+#include "lio_gridsample.h"
 #include "lio_gridobj.h"
 #include "lio_cloud.h"
 #include "lio_pool.h"
@@ -39,7 +40,7 @@ __global__ __launch_bounds__(256) void k_gg_offset(LioGgTable T, int d_rows, int
     lio_wave_count(counters, GG_CNT_CLEARED, cleared);
 }
 
-__global__ __launch_bounds__(256) void k_gg_position(LioGgTable T, LioTerrGeom N, LioTerrGeom O, LioTerrGeom X, int flags, int n_cells,
+__global__ __launch_bounds__(256) void k_gg_position(LioGgTable T, LioGridGeom N, LioGridGeom O, LioGridGeom X, int flags, int n_cells,
                                                      unsigned long long* __restrict__ counters)
 {
     const int lin = (int)blockIdx.x * 256 + (int)threadIdx.x;
@@ -113,8 +114,8 @@ int gg_extend_add(lio_grid* g, lio_grid* other, bool extend, bool add, bool over
 {
     memset(out, 0, sizeof(*out));
     t_gg.clear();
-    const LioTerrGeom O = g->G, X = other->G;
-    LioTerrGeom N = O;
+    const LioGridGeom O = g->G, X = other->G;
+    LioGridGeom N = O;
     bool resized = false;
     if (extend) {
         double position[2], length[2];
@@ -125,7 +126,7 @@ int gg_extend_add(lio_grid* g, lio_grid* other, bool extend, bool add, bool over
         }
         if (resized) {
             for (int a = 0; a < 2; ++a) {
-                const double n = lio_gt_size(length[a], O.res);                // setGeometry, GM:50
+                const double n = lio_gm_size(length[a], O.res);                // setGeometry, GM:50
                 if (!std::isfinite(position[a]) || !std::isfinite(n) || !(n >= 1.0)) return lio_fail(LIO_ERR_ARG, "the extended map has no finite geometry");
                 if (n >= (double)LIO_GS_MAX_LINE) return lio_fail(LIO_ERR_CAPACITY, "the extended map has 2^24 or more cells along an axis");
                 size[a] = (int)n;
@@ -135,7 +136,7 @@ int gg_extend_add(lio_grid* g, lio_grid* other, bool extend, bool add, bool over
                 position[a] = lio_gg_align_axis(position[a], O.pos[a], O.res, size[a], a == 0 ? O.rows : O.cols);
                 if (!std::isfinite(position[a])) return lio_fail(LIO_ERR_ARG, "the extended map has no finite geometry");
             }
-            N = lio_gg_geom(size[0], size[1], O.res, position[0], position[1]);
+            N = lio_gm_geom(size[0], size[1], O.res, position[0], position[1]);
         }
     }
     out->resized = resized ? 1 : 0;
@@ -201,7 +202,7 @@ try {
     }
     int rc = gg_pair_check(src, dst, "src and dst are the same object", false);
     if (rc != LIO_OK) return rc;
-    const LioTerrGeom S = src->G;
+    const LioGridGeom S = src->G;
     LioGgSubmap M;
     lio_gg_submap_information(S, position, length, &M);
     if (!M.ok) {                                             // isSuccess = false: the reference returns a map without data
@@ -249,7 +250,7 @@ try {
     if (!std::isfinite(position[0]) || !std::isfinite(position[1])) return lio_fail(LIO_ERR_ARG, "position must be finite");
     if (!g) return lio_fail(LIO_ERR_ARG, "null argument");
     if (!g->mask) return lio_fail(LIO_ERR_ARG, "the object holds no layers (lio_grid_set_layers, lio_kf_store_planning_grid)");
-    const LioTerrGeom O = g->G;
+    const LioGridGeom O = g->G;
     int shift[2];
     double moved_to[2];
     for (int a = 0; a < 2; ++a) {
@@ -258,7 +259,7 @@ try {
         moved_to[a] = O.pos[a] + lio_gg_position_shift(shift[a], O.res);
         if (!std::isfinite(moved_to[a])) return lio_fail(LIO_ERR_ARG, "the moved map has no finite position");
     }
-    const LioTerrGeom N = lio_gg_geom(O.rows, O.cols, O.res, moved_to[0], moved_to[1]);
+    const LioGridGeom N = lio_gm_geom(O.rows, O.cols, O.res, moved_to[0], moved_to[1]);
     unsigned long long hc[GG_N_CNT] = { 0 };
     if (shift[0] != 0 || shift[1] != 0) {
         int rc = lio_check_device(g->device_id);

@@ -4,7 +4,7 @@
 #pragma once
 #include "lio_pool.h"
 #include "lio_stageclock.h"
-#include "lio_terrain.h"
+#include "lio_gridmath.h"
 
 enum {                             // the region calls' workspace (lio_gridregion.hip)
     LIO_RG_BUF_REGIONS = 0,        // the packed regions
@@ -20,7 +20,7 @@ enum {                             // the region calls' workspace (lio_gridregio
 struct lio_grid {
     int device_id = 0;
     unsigned mask = 0;             // bit k: layer k is present
-    LioTerrGeom G{};               // rows = cols = 0: no geometry yet
+    LioGridGeom G{};               // rows = cols = 0: no geometry yet
     LioDevBuf<float> d_layer[LIO_GRID_MAX_LAYERS];
     LioDevBytes d_region[LIO_RG_N_BUFS];
 };

@@ -3,7 +3,7 @@
 // of the resident layer set (lio_gridregion.hip): the cells of a region and the reduction over them as __host__ __device__
 // functions, so that the kernels and a host program (tools/grid_region_host_check.cpp) run the same text.  Everything is fp64
 // in the order the reference writes it, only + - * / sqrt, and everything here relies on -ffp-contract=off.  The geometry is
-// lio_terrain.h's; startIndex is always 0, so getIndexFromBufferIndex and its inverse are the identity and are left out.
+// lio_gridmath.h's; startIndex is always 0, so getIndexFromBufferIndex and its inverse are the identity and are left out.
 // DESIGN.md section 4l lists the conventions and the labelled deviations (parity unpinned).
 //
 // A region has two halves.  The plan (LioRgPlan) depends on the region alone: the window of an area kind (one axis per
@@ -16,11 +16,10 @@
 #include <math.h>
 #include <stdint.h>
 #include "../../include/liogpu.h"
-#include "lio_terrain.h"
-#include "lio_gridsample.h"
+#include "lio_gridmath.h"
+#include "lio_terrain.h"                                    // lio_terr_finite
 #include "lio_wg.h"
 
-#define LIO_RG_HD __host__ __device__ __forceinline__
 #define LIO_RG_LANES 64            // the partial sums of a region: fixed, whatever the launch shape
 
 // A region as the device reads it: lio_grid_region with the ellipse's sin and cos of the rotation (libm, on the host, as
@@ -50,10 +49,10 @@ inline void lio_rg_pack(const lio_grid_region& r, LioRgRegion* o)
     if (r.kind == LIO_REGION_ELLIPSE) { o->p[4] = sin(r.p[4]); o->p[5] = cos(r.p[4]); }
 }
 
-LIO_RG_HD bool lio_rg_finite(double v) { return fabs(v) <= DBL_MAX; }
+LIO_HD bool lio_rg_finite(double v) { return fabs(v) <= DBL_MAX; }
 
 // ---- INVALID: the causes the parameters alone show (a polygon's vertices are looked at by lio_rg_plan_half)
-LIO_RG_HD bool lio_rg_params_ok(const LioRgRegion& R)
+LIO_HD bool lio_rg_params_ok(const LioRgRegion& R)
 {
     const int np = R.kind == LIO_REGION_CIRCLE ? 3 : R.kind == LIO_REGION_ELLIPSE ? 6 : R.kind == LIO_REGION_LINE ? 4 : 0;
     for (int k = 0; k < np; ++k)
@@ -67,7 +66,7 @@ LIO_RG_HD bool lio_rg_params_ok(const LioRgRegion& R)
 // until GridMap::getIndex succeeds; direction is Eigen's normalized(): v / sqrt(v.v) when v.v > 0, else v.  Gives up (EMPTY:
 // the constructor throws) when what remains is shorter than a step.  The labelled deviation: LIO_REGION_MAX_WALK steps
 // without an answer are INVALID, where the reference would keep walking.
-LIO_RG_HD int lio_rg_walk(const LioTerrGeom& G, double sx, double sy, double ex, double ey, int* i, int* j)
+LIO_HD int lio_rg_walk(const LioGridGeom& G, double sx, double sy, double ex, double ey, int* i, int* j)
 {
     double vx = ex - sx, vy = ey - sy;
     const double z = vx * vx + vy * vy;
@@ -75,7 +74,7 @@ LIO_RG_HD int lio_rg_walk(const LioTerrGeom& G, double sx, double sy, double ex,
     const double step = G.res - DBL_EPSILON;
     double x = sx, y = sy;
     for (int k = 0; ; ++k) {
-        if (lio_gs_index(G, x, y, i, j)) return LIO_REGION_OK;
+        if (lio_gm_index(G, x, y, i, j)) return LIO_REGION_OK;
         if (k == LIO_REGION_MAX_WALK) return LIO_REGION_INVALID;
         x += step * vx;
         y += step * vy;
@@ -86,9 +85,9 @@ LIO_RG_HD int lio_rg_walk(const LioTerrGeom& G, double sx, double sy, double ex,
 
 // One half of a region's plan.  Area kinds: e is the axis, [*lo, *hi] the window along it -- findSubmapParameters of the
 // three iterators (CircleIterator.cpp:74-85, EllipseIterator.cpp:82-97, PolygonIterator.cpp:71-85): the corner positions
-// through boundPositionToRange and getIndexFromPosition (lio_terr_index).  Line: e is the endpoint, (*lo, *hi) its limited
+// through boundPositionToRange and getIndexFromPosition (lio_gm_bound_index).  Line: e is the endpoint, (*lo, *hi) its limited
 // cell.  verts: the flat (x, y) array the polygon's first_vertex counts in.  Returns the half's status.
-LIO_RG_HD int lio_rg_plan_half(const LioTerrGeom& G, const LioRgRegion& R, const double* verts, int e, int* lo, int* hi)
+LIO_HD int lio_rg_plan_half(const LioGridGeom& G, const LioRgRegion& R, const double* verts, int e, int* lo, int* hi)
 {
     *lo = 0; *hi = 0;
     if (!lio_rg_params_ok(R)) return LIO_REGION_INVALID;
@@ -115,14 +114,14 @@ LIO_RG_HD int lio_rg_plan_half(const LioTerrGeom& G, const LioRgRegion& R, const
         }
         if (!ok) return LIO_REGION_INVALID;
     }
-    *lo = lio_terr_index(G, e, top);
-    *hi = lio_terr_index(G, e, bottom);
+    *lo = lio_gm_bound_index(G, e, top);
+    *hi = lio_gm_bound_index(G, e, bottom);
     return LIO_REGION_OK;
 }
 
 // The two halves -> the plan.  The line's second walk does not run in the reference when the first fails: its verdict
 // then does not count.  initializeIterationParameters (IT/LineIterator.cpp:90-136).
-LIO_RG_HD void lio_rg_plan_join(const LioRgRegion& R, int s0, int lo0, int hi0, int s1, int lo1, int hi1, LioRgPlan* P)
+LIO_HD void lio_rg_plan_join(const LioRgRegion& R, int s0, int lo0, int hi0, int s1, int lo1, int hi1, LioRgPlan* P)
 {
     P->kind = R.kind;
     P->r0 = P->c0 = P->h = P->w = P->den = P->add = P->major = P->pad = 0;
@@ -148,12 +147,12 @@ LIO_RG_HD void lio_rg_plan_join(const LioRgRegion& R, int s0, int lo0, int hi0, 
 }
 
 // how many cells the plan numbers: the window's, the line's
-LIO_RG_HD int lio_rg_n_slots(const LioRgPlan& P) { return P.status == LIO_REGION_OK ? P.h * P.w : 0; }
+LIO_HD int lio_rg_n_slots(const LioRgPlan& P) { return P.status == LIO_REGION_OK ? P.h * P.w : 0; }
 
 // Cell k of the line.  LineIterator's ++ (IT/LineIterator.cpp:43-55) adds numeratorAdd and carries at most once a step
 // (numeratorAdd <= denominator), so after k steps the minor axis has moved (denominator / 2 + k numeratorAdd) / denominator
 // cells: the closed form the kernels use; tests/test_grid_region_cpu.py proves it against the serial loop.
-LIO_RG_HD void lio_rg_line_cell(const LioRgPlan& P, int k, int* r, int* c)
+LIO_HD void lio_rg_line_cell(const LioRgPlan& P, int k, int* r, int* c)
 {
     const int m = P.den > 0 ? (int)(((long long)(P.den / 2) + (long long)k * (long long)P.add) / (long long)P.den) : 0;
     *r = P.r0 + P.sr * (P.major == 0 ? k : m);
@@ -162,14 +161,14 @@ LIO_RG_HD void lio_rg_line_cell(const LioRgPlan& P, int k, int* r, int* c)
 
 // Slot t in the iterator's order: SubmapIterator (incrementIndexForSubmap, GMM:485-516) runs the column index inside the
 // row index; the line runs start to end.
-LIO_RG_HD void lio_rg_cell_by_order(const LioRgPlan& P, int t, int* r, int* c)
+LIO_HD void lio_rg_cell_by_order(const LioRgPlan& P, int t, int* r, int* c)
 {
     if (P.kind == LIO_REGION_LINE) { lio_rg_line_cell(P, t, r, c); return; }
     *r = P.r0 + t / P.w; *c = P.c0 + t % P.w;
 }
 
 // Slot `rank` in the order of the sum: the window column-major (the row fastest, as the layers lie in memory), the line by k.
-LIO_RG_HD void lio_rg_cell_by_rank(const LioRgPlan& P, int rank, int* r, int* c)
+LIO_HD void lio_rg_cell_by_rank(const LioRgPlan& P, int rank, int* r, int* c)
 {
     if (P.kind == LIO_REGION_LINE) { lio_rg_line_cell(P, rank, r, c); return; }
     *r = P.r0 + rank % P.h; *c = P.c0 + rank / P.h;
@@ -180,10 +179,10 @@ LIO_RG_HD void lio_rg_cell_by_rank(const LioRgPlan& P, int rank, int* r, int* c)
 //    the same iterator (the device is kept to + - * / sqrt; compilers fold pow(r, 2) to r * r themselves);
 //  - ellipse (EllipseIterator.cpp:17-28, :74-80): the transform (cos sin; sin -cos), squares over (0.5 length)^2;
 //  - polygon (PG:30-42): the even-odd crossing test, the division where the reference has it.
-LIO_RG_HD bool lio_rg_member(const LioTerrGeom& G, const LioRgRegion& R, const double* v, int r, int c)
+LIO_HD bool lio_rg_member(const LioGridGeom& G, const LioRgRegion& R, const double* v, int r, int c)
 {
     if (R.kind == LIO_REGION_LINE) return true;
-    const double px = lio_terr_centre(G, 0, r), py = lio_terr_centre(G, 1, c);
+    const double px = lio_gm_centre(G, 0, r), py = lio_gm_centre(G, 1, c);
     if (R.kind == LIO_REGION_CIRCLE) {
         const double dx = px - R.p[0], dy = py - R.p[1];
         return dx * dx + dy * dy <= R.p[2] * R.p[2];
@@ -209,12 +208,12 @@ struct LioRgAcc {
     int n_finite, n_below;
 };
 
-LIO_RG_HD void lio_rg_acc_clear(LioRgAcc* a)
+LIO_HD void lio_rg_acc_clear(LioRgAcc* a)
 {
     a->sum = 0.0; a->mn = LIO_ORD_NO_MIN; a->mx = LIO_ORD_NO_MAX; a->n_finite = 0; a->n_below = 0;
 }
 
-LIO_RG_HD void lio_rg_acc_add(LioRgAcc* a, float v, float threshold)
+LIO_HD void lio_rg_acc_add(LioRgAcc* a, float v, float threshold)
 {
     if (!lio_terr_finite(v)) return;
     a->sum = a->sum + (double)v;
@@ -226,7 +225,7 @@ LIO_RG_HD void lio_rg_acc_add(LioRgAcc* a, float v, float threshold)
 }
 
 // part[k] += part[k + s]: one level of the tree s = 32, 16, .. 1 that follows the partial sums
-LIO_RG_HD void lio_rg_acc_fold(LioRgAcc* a, const LioRgAcc& b)
+LIO_HD void lio_rg_acc_fold(LioRgAcc* a, const LioRgAcc& b)
 {
     a->sum = a->sum + b.sum;
     a->mn = b.mn < a->mn ? b.mn : a->mn;
@@ -235,11 +234,11 @@ LIO_RG_HD void lio_rg_acc_fold(LioRgAcc* a, const LioRgAcc& b)
     a->n_below += b.n_below;
 }
 
-LIO_RG_HD void lio_rg_acc_store(const LioRgAcc& a, lio_grid_region_stat* o)
+LIO_HD void lio_rg_acc_store(const LioRgAcc& a, lio_grid_region_stat* o)
 {
     o->sum = a.sum;
-    o->min = a.n_finite ? lio_ord2f(a.mn) : LIO_GS_QNAN;
-    o->max = a.n_finite ? lio_ord2f(a.mx) : LIO_GS_QNAN;
+    o->min = a.n_finite ? lio_ord2f(a.mn) : LIO_QNAN;
+    o->max = a.n_finite ? lio_ord2f(a.mx) : LIO_QNAN;
     o->n_finite = a.n_finite; o->n_below = a.n_below;
 }
 
@@ -247,7 +246,7 @@ LIO_RG_HD void lio_rg_acc_store(const LioRgAcc& a, lio_grid_region_stat* o)
 // rank = p (mod 64) in ascending rank, then the tree.  T::at(r, c): the layer.  Returns the member cells.  (The host's form;
 // k_rg_reduce holds one partial per lane.)
 template <class T>
-inline int lio_rg_reduce_serial(const LioTerrGeom& G, const LioRgRegion& R, const double* v, const LioRgPlan& P, const T& in, float threshold,
+inline int lio_rg_reduce_serial(const LioGridGeom& G, const LioRgRegion& R, const double* v, const LioRgPlan& P, const T& in, float threshold,
                                 lio_grid_region_stat* out)
 {
     LioRgAcc part[LIO_RG_LANES];

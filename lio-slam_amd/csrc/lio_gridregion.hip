@@ -39,7 +39,7 @@ struct RgLayers { const float* p[LIO_GRID_MAX_LAYERS]; };          // the reques
 
 enum { RG_CNT_OK = 0, RG_CNT_EMPTY, RG_CNT_INVALID, RG_CNT_CELLS, RG_N_CNT };
 
-__global__ __launch_bounds__(256) void k_rg_plan(LioTerrGeom G, const LioRgRegion* __restrict__ regions, const double* __restrict__ verts, int n,
+__global__ __launch_bounds__(256) void k_rg_plan(LioGridGeom G, const LioRgRegion* __restrict__ regions, const double* __restrict__ verts, int n,
                                                  LioRgPlan* __restrict__ plans)
 {
     const int gid = (int)blockIdx.x * 256 + (int)threadIdx.x;
@@ -99,7 +99,7 @@ __global__ __launch_bounds__(256) void k_rg_info(const unsigned char* __restrict
     }
 }
 
-__global__ __launch_bounds__(256) void k_rg_reduce(LioTerrGeom G, RgLayers L, int n_layers, float threshold, const LioRgRegion* __restrict__ regions,
+__global__ __launch_bounds__(256) void k_rg_reduce(LioGridGeom G, RgLayers L, int n_layers, float threshold, const LioRgRegion* __restrict__ regions,
                                                    const double* __restrict__ verts, const LioRgPlan* __restrict__ plans, int n,
                                                    lio_grid_region_stat* __restrict__ stats, int* __restrict__ n_cells, unsigned char* __restrict__ status)
 {
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(256) void k_rg_reduce(LioTerrGeom G, RgLayers L, in
 // WRITE false: counts[q] = the members, and the status.  WRITE true (after k_rg_info): the cells at offs[q], unless the call's
 // total does not fit `cap` (nothing is written then).
 template <bool WRITE>
-__global__ __launch_bounds__(256) void k_rg_cells(LioTerrGeom G, const LioRgRegion* __restrict__ regions, const double* __restrict__ verts,
+__global__ __launch_bounds__(256) void k_rg_cells(LioGridGeom G, const LioRgRegion* __restrict__ regions, const double* __restrict__ verts,
                                                   const LioRgPlan* __restrict__ plans, int n, int* __restrict__ counts, unsigned char* __restrict__ status,
                                                   const unsigned long long* __restrict__ counters, const int* __restrict__ offs, int* __restrict__ cells,
                                                   unsigned long long cap)

@@ -2,8 +2,9 @@
 // GMM = GridMapMath.cpp, CI = CubicInterpolation.cpp / .hpp) behind the resident layer set (lio_gridsample.hip): the query's
 // arithmetic as __host__ __device__ functions over a grid accessor, so that the kernel (device layers) and a host program
 // (a checked array) run the same text.  Everything is fp64 in the order the reference writes it, a tap is a float widened to
-// double, and everything here relies on -ffp-contract=off.  The geometry is lio_terrain.h's.  startIndex is always 0: the
-// library's grids are never circular buffers, so getIndexFromBufferIndex and its inverse are the identity and are left out.
+// double, and everything here relies on -ffp-contract=off.  The geometry and getIndexFromPosition (lio_gm_index) are
+// lio_gridmath.h's.  startIndex is always 0: the library's grids are never circular buffers, so getIndexFromBufferIndex and
+// its inverse are the identity and are left out.
 // DESIGN.md section 4k lists the conventions and the labelled deviations (parity unpinned).
 //
 // A query has two halves.  The geometry (LioGsQuery: the cell, the quadrant, every tap index, the normalised coordinates)
@@ -15,21 +16,19 @@
 #include <math.h>
 #include <stdint.h>
 #include "../../include/liogpu.h"
-#include "lio_terrain.h"
+#include "lio_gridmath.h"
 
-#define LIO_GS_HD __host__ __device__ __forceinline__
 #define LIO_GS_MAX_LINE (1 << 24)  // rows and cols stay below it
-#define LIO_GS_QNAN __builtin_bit_cast(float, 0x7fc00000u)
 
 // ---- the two constant matrices, CI.hpp:70-74 and :159-163, as the entries a product reads
-LIO_GS_HD double lio_gs_conv_m(int r, int c)
+LIO_HD double lio_gs_conv_m(int r, int c)
 {
     const int k = 4 * r + c;                               //  0  2  0  0 / -1  0  1  0 /  2 -5  4 -1 / -1  3 -3  1
     return k == 1 ? 2.0 : k == 4 ? -1.0 : k == 6 ? 1.0 : k == 8 ? 2.0 : k == 9 ? -5.0 : k == 10 ? 4.0 : k == 11 ? -1.0
          : k == 12 ? -1.0 : k == 13 ? 3.0 : k == 14 ? -3.0 : k == 15 ? 1.0 : 0.0;
 }
 
-LIO_GS_HD double lio_gs_bicubic_m(int r, int c)
+LIO_HD double lio_gs_bicubic_m(int r, int c)
 {
     const int k = 4 * r + c;                               //  1  0  0  0 /  0  0  1  0 / -3  3 -2 -1 /  2 -2  1  1
     return k == 0 ? 1.0 : k == 6 ? 1.0 : k == 8 ? -3.0 : k == 9 ? 3.0 : k == 10 ? -2.0 : k == 11 ? -1.0
@@ -39,14 +38,14 @@ LIO_GS_HD double lio_gs_bicubic_m(int r, int c)
 // A dot product of the two cubic methods: four terms, summed k = 0 .. 3, the terms of a zero matrix entry included (one
 // non-finite tap makes the result non-finite, and the sign of a zero is the dense product's).  Eigen's own order inside a
 // fixed-size product is not defined by the source: unpinned.
-LIO_GS_HD double lio_gs_dot4(double a0, double a1, double a2, double a3, double b0, double b1, double b2, double b3)
+LIO_HD double lio_gs_dot4(double a0, double a1, double a2, double a3, double b0, double b1, double b2, double b3)
 {
     return ((a0 * b0 + a1 * b1) + a2 * b2) + a3 * b3;
 }
 
 // bindIndexToRange (CI:15-21) on an index formed in int and read as unsigned: a negative index goes to the last row or
 // column, like one past the end.  border = 1 (the labelled extension): clamped into [0, n - 1].
-LIO_GS_HD int lio_gs_bind(int i, int n, int border)
+LIO_HD int lio_gs_bind(int i, int n, int border)
 {
     if (border) return i < 0 ? 0 : (i >= n ? n - 1 : i);
     return (unsigned)i >= (unsigned)n ? n - 1 : i;
@@ -75,36 +74,15 @@ struct LioGsQuery {
     LioGsBicubic bic;
 };
 
-// checkIfPositionWithinMap (GMM:162-172): -((p - position) - 0.5 length) in [0, length) on both axes -- the high edge is
-// inside, the low edge is not; a non-finite position fails every comparison.  Then getIndexFromPosition (:147-160):
-// (int)(-v) per component, v = ((p - 0.5 length) - position) / resolution, and checkIfIndexInRange on it (a position within
-// an ulp of the low edge can round to index n: outside as well, where the reference throws).
-LIO_GS_HD bool lio_gs_index(const LioTerrGeom& G, double px, double py, int* i, int* j)
-{
-    const double p[2] = { px, py };
-    int idx[2] = { 0, 0 };
-    bool in = true;
-    for (int a = 0; a < 2; ++a) {
-        const double t = -((p[a] - G.pos[a]) - G.half[a]);
-        if (!(t >= 0.0 && t < G.len[a])) { in = false; continue; }
-        const double v = ((p[a] - G.half[a]) - G.pos[a]) / G.res;
-        const int n = a == 0 ? G.rows : G.cols;
-        idx[a] = (int)(-v);                                // (|v| <= n + 1 here: the conversion is defined)
-        if (idx[a] < 0 || idx[a] >= n) in = false;
-    }
-    *i = idx[0]; *j = idx[1];
-    return in;
-}
-
 // atPositionLinearInterpolated's index work.  The neighbour row is chosen by position.x >= centre.x and the column likewise;
 // the taps are indices[idxShift[k]], and idxShift[k] = idxShift[0] ^ k in all four cases of GM:793-820.  border 0: each tap is
 // tested through its linear index col * rows + row alone, so (rows, c) reads (0, c + 1) and (-1, c) reads (rows - 1, c - 1);
 // a negative index fails as its size_t does, and so does rows * cols (the reference's `>` lets that one read past the
 // buffer: the labelled deviation).  The second getPosition (GM:839) leaves `point` alone when tap 0's own index is outside
 // the grid, so t is then measured from the cell's centre, as written.  border 1: every index clamped, nothing fails.
-LIO_GS_HD void lio_gs_linear_geom(const LioTerrGeom& G, int border, double px, double py, int i, int j, LioGsLinear* L)
+LIO_HD void lio_gs_linear_geom(const LioGridGeom& G, int border, double px, double py, int i, int j, LioGsLinear* L)
 {
-    const double cx = lio_terr_centre(G, 0, i), cy = lio_terr_centre(G, 1, j);
+    const double cx = lio_gm_centre(G, 0, i), cy = lio_gm_centre(G, 1, j);
     const bool up = px >= cx, right = py >= cy;
     int r[4], c[4];
     r[0] = i; c[0] = j;
@@ -124,25 +102,25 @@ LIO_GS_HD void lio_gs_linear_geom(const LioTerrGeom& G, int border, double px, d
     int r0 = r[s0], c0 = c[s0];
     if (border) { r0 = lio_gs_bind(r0, G.rows, 1); c0 = lio_gs_bind(c0, G.cols, 1); }
     const bool in_range = r0 >= 0 && r0 < G.rows && c0 >= 0 && c0 < G.cols;
-    const double ox = in_range ? lio_terr_centre(G, 0, r0) : cx, oy = in_range ? lio_terr_centre(G, 1, c0) : cy;
+    const double ox = in_range ? lio_gm_centre(G, 0, r0) : cx, oy = in_range ? lio_gm_centre(G, 1, c0) : cy;
     L->tx = (px - ox) / G.res; L->ty = (py - oy) / G.res;
     L->ux = 1.0 - L->tx; L->uy = 1.0 - L->ty;
 }
 
-LIO_GS_HD void lio_gs_conv_geom(const LioTerrGeom& G, int border, double px, double py, int i, int j, LioGsConv* V)
+LIO_HD void lio_gs_conv_geom(const LioGridGeom& G, int border, double px, double py, int i, int j, LioGsConv* V)
 {
     for (int k = 0; k < 4; ++k) {
         V->ri[k] = lio_gs_bind(i + 1 - k, G.rows, border);
         V->ci[k] = lio_gs_bind(j + 1 - k, G.cols, border);
     }
-    V->tx = (px - lio_terr_centre(G, 0, i)) / G.res;
-    V->ty = (py - lio_terr_centre(G, 1, j)) / G.res;
+    V->tx = (px - lio_gm_centre(G, 0, i)) / G.res;
+    V->ty = (py - lio_gm_centre(G, 1, j)) / G.res;
 }
 
 // getUnitSquareCornerIndices (CI:204-255) with its strict `>`, bindIndicesToRange, and the neighbours the derivatives read
-LIO_GS_HD void lio_gs_bicubic_geom(const LioTerrGeom& G, int border, double px, double py, int i, int j, LioGsBicubic* B)
+LIO_HD void lio_gs_bicubic_geom(const LioGridGeom& G, int border, double px, double py, int i, int j, LioGsBicubic* B)
 {
-    const bool xq = px > lio_terr_centre(G, 0, i), yq = py > lio_terr_centre(G, 1, j);
+    const bool xq = px > lio_gm_centre(G, 0, i), yq = py > lio_gm_centre(G, 1, j);
     B->r[0] = lio_gs_bind(xq ? i : i + 1, G.rows, border);           // topLeft / bottomLeft
     B->r[1] = lio_gs_bind(xq ? i - 1 : i, G.rows, border);           // topRight / bottomRight
     B->c[0] = lio_gs_bind(yq ? j : j + 1, G.cols, border);           // bottom
@@ -151,14 +129,14 @@ LIO_GS_HD void lio_gs_bicubic_geom(const LioTerrGeom& G, int border, double px, 
         B->rm[k] = lio_gs_bind(B->r[k] - 1, G.rows, border); B->rp[k] = lio_gs_bind(B->r[k] + 1, G.rows, border);
         B->cm[k] = lio_gs_bind(B->c[k] - 1, G.cols, border); B->cp[k] = lio_gs_bind(B->c[k] + 1, G.cols, border);
     }
-    B->tx = (px - lio_terr_centre(G, 0, B->r[0])) / G.res;
-    B->ty = (py - lio_terr_centre(G, 1, B->c[0])) / G.res;
+    B->tx = (px - lio_gm_centre(G, 0, B->r[0])) / G.res;
+    B->ty = (py - lio_gm_centre(G, 1, B->c[0])) / G.res;
 }
 
 // The geometry a query of `method` needs: its own and that of the methods it can fall back to.
-LIO_GS_HD void lio_gs_query(const LioTerrGeom& G, int method, int border, double px, double py, LioGsQuery* Q)
+LIO_HD void lio_gs_query(const LioGridGeom& G, int method, int border, double px, double py, LioGsQuery* Q)
 {
-    Q->outside = !lio_gs_index(G, px, py, &Q->i, &Q->j);
+    Q->outside = !lio_gm_index(G, px, py, &Q->i, &Q->j);
     if (Q->outside) return;
     if (method != LIO_GRID_NEAREST) lio_gs_linear_geom(G, border, px, py, Q->i, Q->j, &Q->lin);
     if (method == LIO_GRID_CUBIC_CONVOLUTION) lio_gs_conv_geom(G, border, px, py, Q->i, Q->j, &Q->conv);
@@ -169,7 +147,7 @@ LIO_GS_HD void lio_gs_query(const LioTerrGeom& G, int method, int border, double
 // layer at its column-major linear index k in [0, rows * cols), which is how the linear method reads (layerMat(indexLin)).
 // GM:843-844, left to right; there is no finiteness test
 template <class T>
-LIO_GS_HD float lio_gs_linear(const LioGsLinear& L, const T& in)
+LIO_HD float lio_gs_linear(const LioGsLinear& L, const T& in)
 {
     double f[4];
     for (int k = 0; k < 4; ++k) f[k] = (double)in.at_lin(L.tap[k]);
@@ -178,7 +156,7 @@ LIO_GS_HD float lio_gs_linear(const LioGsLinear& L, const T& in)
 }
 
 // convolve1D (CI:72-79): 0.5 * (tVector . (M * f))
-LIO_GS_HD double lio_gs_convolve(double t, double f0, double f1, double f2, double f3)
+LIO_HD double lio_gs_convolve(double t, double f0, double f1, double f2, double f3)
 {
     const double t2 = t * t, t3 = t2 * t;
     double tmp[4];
@@ -190,7 +168,7 @@ LIO_GS_HD double lio_gs_convolve(double t, double f0, double f1, double f2, doub
 // evaluateBicubicConvolutionInterpolation: row a of the function value matrix holds column j + 1 - a of the layer, taken at
 // rows i + 1, i, i - 1, i - 2 (CI:106-108)
 template <class T>
-LIO_GS_HD double lio_gs_conv(const LioGsConv& V, const T& in)
+LIO_HD double lio_gs_conv(const LioGsConv& V, const T& in)
 {
     double b[4];
     for (int a = 0; a < 4; ++a)
@@ -202,7 +180,7 @@ LIO_GS_HD double lio_gs_conv(const LioGsConv& V, const T& in)
 // evaluateBicubicInterpolation.  Corner (kr, kc): kr 0 left, 1 right; kc 0 bottom, 1 top.  The function value matrix of
 // CI:416-432 is F[2 a + kr][2 b + kc], (a, b) = (0, 0) f, (1, 0) dfx, (0, 1) dfy, (1, 1) ddfxy.
 template <class T>
-LIO_GS_HD double lio_gs_bicubic(const LioTerrGeom& G, const LioGsBicubic& B, const T& in)
+LIO_HD double lio_gs_bicubic(const LioGridGeom& G, const LioGsBicubic& B, const T& in)
 {
     const double res = G.res;
     double F[4][4];
@@ -239,15 +217,15 @@ LIO_GS_HD double lio_gs_bicubic(const LioTerrGeom& G, const LioGsBicubic& B, con
     return lio_gs_dot4(1.0, tx, tx2, tx3, v[0], v[1], v[2], v[3]);
 }
 
-LIO_GS_HD bool lio_gs_finite(double v) { return fabs(v) <= DBL_MAX; }          // std::isfinite
+LIO_HD bool lio_gs_finite(double v) { return fabs(v) <= DBL_MAX; }          // std::isfinite
 
 // atPosition (GM:161-204) on one layer: a cubic result that is not finite falls back to linear, linear whose taps fail to
 // nearest.  A finite double beyond float's range is rounded to +-inf, as written.  Outside the map nothing is read: the
 // quiet NaN 0x7fc00000 and LIO_GRID_OUTSIDE, where the reference throws (the labelled deviation).  Returns the method used.
 template <class T>
-LIO_GS_HD int lio_gs_eval(const LioTerrGeom& G, const LioGsQuery& Q, int method, const T& in, float* value)
+LIO_HD int lio_gs_eval(const LioGridGeom& G, const LioGsQuery& Q, int method, const T& in, float* value)
 {
-    if (Q.outside) { *value = LIO_GS_QNAN; return LIO_GRID_OUTSIDE; }
+    if (Q.outside) { *value = LIO_QNAN; return LIO_GRID_OUTSIDE; }
     if (method == LIO_GRID_CUBIC_CONVOLUTION) {
         const double v = lio_gs_conv(Q.conv, in);
         if (lio_gs_finite(v)) { *value = (float)v; return LIO_GRID_CUBIC_CONVOLUTION; }

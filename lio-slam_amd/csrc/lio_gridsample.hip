@@ -35,7 +35,7 @@ struct GsLayers { const float* p[LIO_GRID_MAX_LAYERS]; };          // the reques
 
 // counters[0..3] += pairs per method used, counters[4] += pairs outside
 template <int METHOD>
-__global__ __launch_bounds__(256) void k_grid_sample(LioTerrGeom G, GsLayers L, int n_layers, int border, const double2* __restrict__ pos, int n,
+__global__ __launch_bounds__(256) void k_grid_sample(LioGridGeom G, GsLayers L, int n_layers, int border, const double2* __restrict__ pos, int n,
                                                      float* __restrict__ values, unsigned char* __restrict__ method_used,
                                                      unsigned long long* __restrict__ counters)
 {
@@ -73,28 +73,14 @@ __global__ __launch_bounds__(256) void k_grid_sample(LioTerrGeom G, GsLayers L, 
 
 thread_local LioStageTimes<3> t_stage;                     // four marks around the three stages of lio_grid_sample
 
-void grid_apply_geometry(lio_grid* g, int rows, int cols, double resolution, const double* length, const double* position)
-{
-    LioTerrGeom& G = g->G;
-    G.rows = rows; G.cols = cols; G.res = resolution;
-    for (int a = 0; a < 2; ++a) {
-        G.len[a] = length[a]; G.pos[a] = position[a];
-        G.half[a] = 0.5 * length[a];                       // getVectorToOrigin
-        G.base[a] = position[a] + (G.half[a] - 0.5 * resolution);          // mapPosition + getVectorToFirstCell
-    }
-}
-
 }  // namespace
 
 int lio_grid_geometry_check(int rows, int cols, double resolution, const double* length, const double* position)
 {
     if (rows < 1 || cols < 1) return lio_fail(LIO_ERR_ARG, "rows and cols must be at least 1");
     if (rows >= LIO_GS_MAX_LINE || cols >= LIO_GS_MAX_LINE) return lio_fail(LIO_ERR_ARG, "rows and cols must be below 2^24");
-    if (!std::isfinite(resolution) || resolution < 1e-4) return lio_fail(LIO_ERR_ARG, "resolution must be finite and at least 1e-4");
-    for (int a = 0; a < 2; ++a) {
-        if (!std::isfinite(length[a]) || !std::isfinite(position[a])) return lio_fail(LIO_ERR_ARG, "length and position must be finite");
-        if (length[a] != (double)(a == 0 ? rows : cols) * resolution) return lio_fail(LIO_ERR_ARG, "length must be size * resolution (GridMap::setGeometry)");
-    }
+    if (const char* why = lio_gm_resolution_refusal(resolution)) return lio_fail(LIO_ERR_ARG, why);
+    if (const char* why = lio_gm_axes_refusal(rows, cols, resolution, length, position)) return lio_fail(LIO_ERR_ARG, why);
     if ((long long)rows * cols > 0x7fffffffLL - 1024) return lio_fail(LIO_ERR_CAPACITY, "a layer has more than 2^31 - 1024 cells");
     return LIO_OK;
 }
@@ -140,7 +126,7 @@ int lio_grid_set_geometry(lio_grid* g, int rows, int cols, double resolution, co
     lio_grid_clear(g);
     const int rc = lio_grid_geometry_check(rows, cols, resolution, length, position);
     if (rc != LIO_OK) return rc;
-    grid_apply_geometry(g, rows, cols, resolution, length, position);
+    g->G = lio_gm_geom(rows, cols, resolution, position[0], position[1]);
     return LIO_OK;
 }
 

@@ -20,6 +20,7 @@
 #include <string.h>
 
 #include "lio_gridtransform.h"
+#include "lio_gridsample.h"
 #include "lio_gridobj.h"
 #include "lio_cloud.h"
 #include "lio_pool.h"
@@ -46,7 +47,7 @@ __device__ __forceinline__ unsigned gt_wave_sum(unsigned v)
     return v;
 }
 
-__global__ __launch_bounds__(256) void k_gt_scatter(LioTerrGeom S, LioTerrGeom D, LioGtXf T, double sample_length, int n_samples,
+__global__ __launch_bounds__(256) void k_gt_scatter(LioGridGeom S, LioGridGeom D, LioGtXf T, double sample_length, int n_samples,
                                                     const float* __restrict__ height, int n_cells, unsigned long long* __restrict__ keys,
                                                     unsigned long long* __restrict__ counters)
 {
@@ -69,7 +70,7 @@ __global__ __launch_bounds__(256) void k_gt_scatter(LioTerrGeom S, LioTerrGeom D
 }
 
 // the words new cell `key` takes: w[k] for slot k; returns whether the cell received a value
-__device__ __forceinline__ bool gt_winner(const LioTerrGeom& S, const LioGtXf& T, double sample_length, const GtLayers& L, unsigned long long key,
+__device__ __forceinline__ bool gt_winner(const LioGridGeom& S, const LioGtXf& T, double sample_length, const GtLayers& L, unsigned long long key,
                                           int* lin, unsigned* height_word)
 {
     if (key == 0ull) { *lin = -1; *height_word = 0x7fc00000u; return false; }
@@ -80,7 +81,7 @@ __device__ __forceinline__ bool gt_winner(const LioTerrGeom& S, const LioGtXf& T
     return true;
 }
 
-__global__ __launch_bounds__(256) void k_gt_gather(LioTerrGeom S, LioGtXf T, double sample_length, GtLayers L, const unsigned long long* __restrict__ keys,
+__global__ __launch_bounds__(256) void k_gt_gather(LioGridGeom S, LioGtXf T, double sample_length, GtLayers L, const unsigned long long* __restrict__ keys,
                                                    long long n_new, unsigned long long* __restrict__ counters)
 {
     const long long q = (long long)blockIdx.x * 256 + (long long)threadIdx.x;
@@ -123,7 +124,7 @@ thread_local LioStageTimes<3> t_gt;                        // four marks around 
 
 // No transformed height may be NaN (the rule's premise): with every term of the z row bounded so that the sum of their
 // magnitudes stays far below DBL_MAX, no partial sum overflows, and a sum of finite terms that does not overflow is finite.
-bool gt_height_row_is_safe(const LioTerrGeom& S, const LioGtXf& T, double sample_length)
+bool gt_height_row_is_safe(const LioGridGeom& S, const LioGtXf& T, double sample_length)
 {
     const double x = (fabs(S.pos[0]) + S.half[0]) + fabs(sample_length), y = (fabs(S.pos[1]) + S.half[1]) + fabs(sample_length);
     const double bound = ((fabs(T.m[8]) * x + fabs(T.m[9]) * y) + fabs(T.m[10]) * (double)FLT_MAX) + fabs(T.m[11]);
@@ -148,7 +149,7 @@ try {
     if (src->device_id != dst->device_id) return lio_fail(LIO_ERR_ARG, "src and dst live on different devices");
     if (!src->mask) return lio_fail(LIO_ERR_ARG, "src holds no layers (lio_grid_set_layers, lio_kf_store_planning_grid)");
     if (!lio_grid_has_layer(src, height_layer)) return lio_fail(LIO_ERR_ARG, "height_layer names a layer src does not hold");
-    const LioTerrGeom S = src->G;
+    const LioGridGeom S = src->G;
     const double sample_length = S.res * sample_ratio;       // GM:344
     if (!gt_height_row_is_safe(S, T, sample_length)) return lio_fail(LIO_ERR_ARG, "the transform's z row could overflow a transformed height");
     // the new geometry, GM:347-382
@@ -156,7 +157,7 @@ try {
     int size[2];
     lio_gt_new_extent(S.len, S.pos, T, centre, new_length);
     for (int a = 0; a < 2; ++a) {
-        const double n = lio_gt_size(new_length[a], S.res);
+        const double n = lio_gm_size(new_length[a], S.res);
         if (!std::isfinite(centre[a]) || !(n >= 1.0) || !std::isfinite(n)) return lio_fail(LIO_ERR_ARG, "the new map has no cell along an axis (or no finite geometry)");
         if (n >= (double)LIO_GS_MAX_LINE) return lio_fail(LIO_ERR_CAPACITY, "the new map has 2^24 or more cells along an axis");
         size[a] = (int)n;
@@ -180,7 +181,7 @@ try {
         L.dst[L.n] = (unsigned*)d;
         ++L.n;
     }
-    const LioTerrGeom D = dst->G;
+    const LioGridGeom D = dst->G;
     hipStream_t s = nullptr;
     LioTemp keys;
     LioGridCounters counters;

@@ -2,13 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/liogpu.h"
+#include "lio_gridmath.h"
 #include "lio_pool.h"
-
-// grid_map's geometry after GridMap::setGeometry (GridMap.cpp:44-59): rows = size(0) along x, cols = size(1) along y
-struct LioHmGeom {
-    int rows, cols;
-    double length[2], position[2], resolution;
-};
 
 // R1 = Rx(-roll) * Ry(-pitch), R2 = Rx(roll) * Ry(pitch) (PointcloudProcessor.cpp:131-154), 3 x 3 row-major, formed in fp32
 // as helpers.cpp:107-139 forms them.  R2 is not R1's inverse.
@@ -20,17 +15,17 @@ void lio_hm_rotations(float roll, float pitch, float R1[9], float R2[9]);
 int lio_hm_level_ego(const float4* d_in, int n, const float R1[9], const float R2[9], int level, LioTemp& out, int* n_out, hipStream_t s);
 
 // GridMapPclLoader.cpp:97-108 + GridMap::setGeometry, on the host in fp64, from pcl::getMinMax3D of the cloud (K7's box pass)
-void lio_hm_geometry(const float mn[3], const float mx[3], double resolution, LioHmGeom* g);
+void lio_hm_geometry(const float mn[3], const float mx[3], double resolution, LioGridGeom* g);
 
 // pairs[i] = (cell of point i = row + col * rows, or rows * cols for a point outside the grid; i).  counters[0] += the
 // points inside.
-void lio_hm_launch_keys(const float4* d_pts, int n, const LioHmGeom& g, uint2* pairs, int* counters, hipStream_t s);
+void lio_hm_launch_keys(const float4* d_pts, int n, const LioGridGeom& g, uint2* pairs, int* counters, hipStream_t s);
 
 // From the pairs stably sorted by cell: the elevation layer, the hole filling, the grid copied to `grid` (host, column-major
 // rows x cols) and counters[0..2] = points binned, cells with an elevation, cells filled.  `counters`: the device words
 // lio_hm_launch_keys added to.  Synchronous.  `keep` (optional): receives the device grid instead of the pool, for a caller
 // that goes on from it (the terrain layers); `grid` may then be NULL, and nothing but the counters crosses.
-int lio_hm_grid(const float4* d_pts, const uint2* d_sorted, int n, const LioHmGeom& g, const lio_height_map_config* cfg, float* grid,
+int lio_hm_grid(const float4* d_pts, const uint2* d_sorted, int n, const LioGridGeom& g, const lio_height_map_config* cfg, float* grid,
                 int* counters, int h_counters[3], hipStream_t s, LioTemp* keep = nullptr);
 
 int lio_height_map_check(const lio_height_map_config* c);     // LIO_OK or LIO_ERR_ARG

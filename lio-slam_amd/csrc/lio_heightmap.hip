@@ -105,29 +105,24 @@ int lio_hm_level_ego(const float4* d_in, int n, const float R1[9], const float R
 }
 
 // ---- geometry (the box comes from K7's box pass, lio_cloud_box_launch) -----------------------------------------------
-void lio_hm_geometry(const float mn[3], const float mx[3], double resolution, LioHmGeom* g)
+void lio_hm_geometry(const float mn[3], const float mx[3], double resolution, LioGridGeom* g)
 {
-    g->resolution = resolution;
+    int sz[2];
+    double position[2];
     for (int a = 0; a < 2; ++a) {
         const float len = mx[a] - mn[a], sum = mx[a] + mn[a];             // pcl::PointXYZ members: float arithmetic
         const double size = std::round((double)len / resolution);        // GridMap.cpp:49-50
-        const int sz = size >= 2147483647.0 ? INT_MAX : (int)size;
-        (a == 0 ? g->rows : g->cols) = sz;
-        g->length[a] = (double)sz * resolution;
-        g->position[a] = (double)sum / 2.0;
+        sz[a] = size >= 2147483647.0 ? INT_MAX : (int)size;
+        position[a] = (double)sum / 2.0;
     }
+    *g = lio_gm_geom(sz[0], sz[1], resolution, position[0], position[1]);
 }
 
 // ---- binning ------------------------------------------------------------------------------------------------------------
-struct HmBin {
-    double half[2], pos[2], res;   // 0.5 * length_, position_, resolution_
-    int rows, cols;
-};
-
 // getIndexFromPosition: v = ((p - 0.5 length_) - position_) / resolution, index = (int)(-v).  An index equal to the size falls
 // into the reference's extra row or column, which nobody reads; a negative one cannot occur for finite input.  Both are
 // keyed behind the last cell.
-__global__ __launch_bounds__(256) void k_hm_keys(HmBin B, const float4* __restrict__ p, int n, uint2* __restrict__ pairs, int* __restrict__ counters)
+__global__ __launch_bounds__(256) void k_hm_keys(LioGridGeom B, const float4* __restrict__ p, int n, uint2* __restrict__ pairs, int* __restrict__ counters)
 {
     const int i = blockIdx.x * 256 + (int)threadIdx.x;
     bool in = false;
@@ -143,12 +138,9 @@ __global__ __launch_bounds__(256) void k_hm_keys(HmBin B, const float4* __restri
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(&counters[0], __popcll(m));
 }
 
-void lio_hm_launch_keys(const float4* d_pts, int n, const LioHmGeom& g, uint2* pairs, int* counters, hipStream_t s)
+void lio_hm_launch_keys(const float4* d_pts, int n, const LioGridGeom& g, uint2* pairs, int* counters, hipStream_t s)
 {
-    HmBin B;
-    for (int a = 0; a < 2; ++a) { B.half[a] = 0.5 * g.length[a]; B.pos[a] = g.position[a]; }
-    B.res = g.resolution; B.rows = g.rows; B.cols = g.cols;
-    hipLaunchKernelGGL(k_hm_keys, dim3((n + 255) / 256), dim3(256), 0, s, B, d_pts, n, pairs, counters);
+    hipLaunchKernelGGL(k_hm_keys, dim3((n + 255) / 256), dim3(256), 0, s, g, d_pts, n, pairs, counters);
 }
 
 // range[c] = [first, last + 1) of cell c in the sorted pairs ((0, 0), from the memset, for an empty cell); sorted_pts = the points
@@ -351,7 +343,7 @@ __global__ __launch_bounds__(256) void k_hm_fill(const float* __restrict__ pre, 
     }
 }
 
-int lio_hm_grid(const float4* d_pts, const uint2* d_sorted, int n, const LioHmGeom& g, const lio_height_map_config* cfg, float* grid,
+int lio_hm_grid(const float4* d_pts, const uint2* d_sorted, int n, const LioGridGeom& g, const lio_height_map_config* cfg, float* grid,
                 int* counters, int h_counters[3], hipStream_t s, LioTemp* keep)
 {
     const int n_cells = g.rows * g.cols;
@@ -455,10 +447,10 @@ int lio_height_map_device(const float4* d_in, int n, const lio_height_map_config
     if ((rc = lio_cloud_box_launch(cur, n_cur, bbox, s)) != LIO_OK) return rc;
     if ((rc = lio_cloud_box_wait(bbox, mn, mx, s)) != LIO_OK) return rc;
     HIPCHK(hipGetLastError());
-    LioHmGeom g;
+    LioGridGeom g;
     lio_hm_geometry(mn, mx, cfg->resolution, &g);
     info->rows = g.rows; info->cols = g.cols;
-    for (int a = 0; a < 2; ++a) { info->length[a] = g.length[a]; info->position[a] = g.position[a]; }
+    for (int a = 0; a < 2; ++a) { info->length[a] = g.len[a]; info->position[a] = g.pos[a]; }
     if (g.rows == 0 || g.cols == 0) return LIO_OK;         // (the reference asserts in GridMap::setGeometry)
     if ((long long)g.rows * g.cols > 0x7fffffffLL - 1024) return lio_fail(LIO_ERR_CAPACITY, "the grid has more than 2^31 cells");
     const size_t n_cells = (size_t)g.rows * (size_t)g.cols;

@@ -8,11 +8,11 @@
 #include <float.h>
 #include <math.h>
 #include "../../include/liogpu.h"
-#include "lio_terrain.h"
+#include "lio_gridmath.h"
+#include "lio_terrain.h"                                    // LIO_TERR_MAX_CELLS and the tile of the kernels
 #include "lio_wg.h"
 
 #define LIO_MF_MAX_ITERATIONS 15   // num_erode_dilation_iterations: the mask's halo 2 + max(N, 1) + N stays within LIO_TERR_MAX_CELLS
-#define LIO_MF_HD __host__ __device__ __forceinline__
 
 struct LioMfParams {
     int rows, cols;
@@ -29,11 +29,11 @@ struct LioMfCell {
     bool nan_in, masked, filled, filtered, nan_out;
 };
 
-LIO_MF_HD bool lio_mf_finite(float v) { return fabsf(v) <= FLT_MAX; }          // std::isfinite
+LIO_HD bool lio_mf_finite(float v) { return fabsf(v) <= FLT_MAX; }          // std::isfinite
 
 // [i - R, i + R] with both ends brought into [0, n - 1] (boundIndexToRange; for the morphology: cells outside the image take
 // no part, morphologyDefaultBorderValue)
-LIO_MF_HD void lio_mf_clip(int i, int R, int n, int& lo, int& hi)
+LIO_HD void lio_mf_clip(int i, int R, int n, int& lo, int& hi)
 {
     lo = i - R < 0 ? 0 : i - R;
     hi = i + R > n - 1 ? n - 1 : i + R;
@@ -44,7 +44,7 @@ LIO_MF_HD void lio_mf_clip(int i, int R, int n, int& lo, int& hi)
 // the 3 x 3 element under the default border are one (2k + 1)^2 box clipped to the grid, and a clipped box is the pass
 // along the rows followed by the pass along the columns (tests/test_median_fill_cpu.py proves both on random masks).
 template <class L>
-LIO_MF_HD unsigned lio_mf_line(const L& line, int lo, int hi, bool erode)
+LIO_HD unsigned lio_mf_line(const L& line, int lo, int hi, bool erode)
 {
     unsigned v = erode ? 1u : 0u;
     for (int k = lo; k <= hi; ++k) {
@@ -56,8 +56,8 @@ LIO_MF_HD unsigned lio_mf_line(const L& line, int lo, int hi, bool erode)
 
 // The four box operations of computeAndAddFillMask in order: cleanedMask's surviving erode + dilate (:220-221; the pair at
 // :218-219 is overwritten), then fillHoles' max(N, 1) dilations and N erosions.
-LIO_MF_HD int lio_mf_op_radius(const LioMfParams& P, int op) { return op < 2 ? 1 : (op == 2 ? P.n_dilate : P.n_iter); }
-LIO_MF_HD bool lio_mf_op_erodes(int op) { return op == 0 || op == 3; }
+LIO_HD int lio_mf_op_radius(const LioMfParams& P, int op) { return op < 2 ? 1 : (op == 2 ? P.n_dilate : P.n_iter); }
+LIO_HD bool lio_mf_op_erodes(int op) { return op == 0 || op == 3; }
 #define LIO_MF_N_OPS 4
 #define LIO_MF_OP_CLEANED 1        // the mask after this operation is the filter's debug layer
 
@@ -67,7 +67,7 @@ LIO_MF_HD bool lio_mf_op_erodes(int op) { return op == 0 || op == 3; }
 // open): one pass counts, then one pass per key bit, most significant first, fixes that bit of the answer by counting the
 // values that agree with the bits fixed so far and have a 0 there.  No per-lane array: the window stays where M keeps it.
 template <class M>
-LIO_MF_HD float lio_mf_median(const M& in, int r, int c, int R, int rows, int cols)
+LIO_HD float lio_mf_median(const M& in, int r, int c, int R, int rows, int cols)
 {
     int i0, i1, j0, j1;
     lio_mf_clip(r, R, rows, i0, i1);
@@ -92,7 +92,7 @@ LIO_MF_HD float lio_mf_median(const M& in, int r, int c, int R, int rows, int co
 
 // One cell of update() (:132-145).  mask: shouldFill at (r, c), non-zero = fill (a NaN compares non-zero, as there).
 template <class M>
-LIO_MF_HD void lio_mf_cell(const LioMfParams& P, const M& in, float mask, int r, int c, LioMfCell* o)
+LIO_HD void lio_mf_cell(const LioMfParams& P, const M& in, float mask, int r, int c, LioMfCell* o)
 {
     const float v = in.at(r, c);
     const bool fin = lio_mf_finite(v);

@@ -8,21 +8,21 @@
 #include <math.h>
 #include "../../include/liogpu.h"
 #include "lio_pool.h"
+#include "lio_gridmath.h"
 #include "lio_types.h"
 
-#define LIO_OGM_HD __host__ __device__ __forceinline__
 #define LIO_OGM_MAX_COORD 1.0e15f      // LIO_MAX_COORD: the bound of the cell sort
 #define LIO_OGM_MAX_CELLS (1LL << 22)  // the cap of the search grid
 
 // ---- the radius filter -------------------------------------------------------------------------------------------------
 // the points that take part: the ones the cell sort bins
-LIO_OGM_HD bool lio_ogm_takes_part(float x, float y, float z)
+LIO_HD bool lio_ogm_takes_part(float x, float y, float z)
 {
     return fabsf(x) <= LIO_OGM_MAX_COORD && fabsf(y) <= LIO_OGM_MAX_COORD && fabsf(z) <= LIO_OGM_MAX_COORD;
 }
 
 // lio_cell_coord (lio_s2m_device.h), the formula that bins the cloud: the same text, so the same cell
-LIO_OGM_HD int lio_ogm_cell_coord(float v, float origin, float inv_cell, int n)
+LIO_HD int lio_ogm_cell_coord(float v, float origin, float inv_cell, int n)
 {
     float c = floorf((v - origin) * inv_cell);
     c = fminf(fmaxf(c, -4.0f), (float)(n + 3));
@@ -30,7 +30,7 @@ LIO_OGM_HD int lio_ogm_cell_coord(float v, float origin, float inv_cell, int n)
 }
 
 // the cell of a point of the grid's box, clamped (a binned point is inside: the clamp never acts on one)
-LIO_OGM_HD void lio_ogm_cell(const LioGrid& g, float x, float y, float z, int& cx, int& cy, int& cz)
+LIO_HD void lio_ogm_cell(const LioGrid& g, float x, float y, float z, int& cx, int& cy, int& cz)
 {
     cx = lio_ogm_cell_coord(x, g.ox, g.inv_cell, g.nx); cx = cx < 0 ? 0 : (cx > g.nx - 1 ? g.nx - 1 : cx);
     cy = lio_ogm_cell_coord(y, g.oy, g.inv_cell, g.ny); cy = cy < 0 ? 0 : (cy > g.ny - 1 ? g.ny - 1 : cy);
@@ -62,7 +62,7 @@ inline float lio_ogm_choose_grid(const float mn[3], const float mx[3], float rad
 // clipped to the grid, as [beg, end) of the cell-sorted cloud.  false: the row is outside the grid.  A::at(i) =
 // cell_start[i], i in [0, n_cells].
 template <class A>
-LIO_OGM_HD bool lio_ogm_run(const LioGrid& g, const A& cell_start, int cx, int cy, int cz, int k, int& beg, int& end)
+LIO_HD bool lio_ogm_run(const LioGrid& g, const A& cell_start, int cx, int cy, int cz, int k, int& beg, int& end)
 {
     const int y = cy + k % 3 - 1, z = cz + k / 3 - 1;
     if (y < 0 || y >= g.ny || z < 0 || z >= g.nz) return false;
@@ -74,7 +74,7 @@ LIO_OGM_HD bool lio_ogm_run(const LioGrid& g, const A& cell_start, int cx, int c
 }
 
 // FLANN L2_Simple in fp32, and the strict test against r2 = (float)((double)radius * radius)
-LIO_OGM_HD bool lio_ogm_within(float qx, float qy, float qz, float mx, float my, float mz, float r2)
+LIO_HD bool lio_ogm_within(float qx, float qy, float qz, float mx, float my, float mz, float r2)
 {
     const float dx = qx - mx, dy = qy - my, dz = qz - mz;
     const float d2 = ((dx * dx) + dy * dy) + dz * dz;
@@ -84,7 +84,7 @@ LIO_OGM_HD bool lio_ogm_within(float qx, float qy, float qz, float mx, float my,
 // k_i of the point (qx, qy, qz) over the cell-sorted cloud; stops once the count exceeds `stop_above` (INT_MAX: never).
 // S::at(i) = sorted point i as float4 (x, y, z, -), i in [0, cell_start[n_cells]).
 template <class A, class S>
-LIO_OGM_HD int lio_ogm_count(const LioGrid& g, const A& cell_start, const S& sorted, float qx, float qy, float qz, float r2, int stop_above)
+LIO_HD int lio_ogm_count(const LioGrid& g, const A& cell_start, const S& sorted, float qx, float qy, float qz, float r2, int stop_above)
 {
     int cx, cy, cz;
     lio_ogm_cell(g, qx, qy, qz, cx, cy, cz);
@@ -110,7 +110,7 @@ struct LioOgmRaster {
 
 // (int)((v - v_min) / resolution) of the draft, toward zero; false where the conversion would leave int (such a point is
 // outside every grid that passed the 2^31 - 1 cell check)
-LIO_OGM_HD bool lio_ogm_axis_index(double v, double v_min, double res, int& idx)
+LIO_HD bool lio_ogm_axis_index(double v, double v_min, double res, int& idx)
 {
     const double d = (v - v_min) / res;
     if (!(d > -2147483648.0 && d < 2147483648.0)) return false;
@@ -119,7 +119,7 @@ LIO_OGM_HD bool lio_ogm_axis_index(double v, double v_min, double res, int& idx)
 }
 
 // the cell of a point, or -1 where the draft skips it: i < 0 || i >= width || j < 0 || j >= j_end
-LIO_OGM_HD long long lio_ogm_raster_cell(const LioOgmRaster& R, float x, float y)
+LIO_HD long long lio_ogm_raster_cell(const LioOgmRaster& R, float x, float y)
 {
     int i, j;
     if (!lio_ogm_axis_index((double)x, R.x_min, R.res, i) || i < 0 || i >= R.width) return -1;

@@ -25,8 +25,8 @@
 
 namespace {
 
-struct OgmInts { const int* p; LIO_OGM_HD int at(int i) const { return p[i]; } };
-struct OgmPts { const float4* p; LIO_OGM_HD float4 at(int i) const { return p[i]; } };
+struct OgmInts { const int* p; LIO_HD int at(int i) const { return p[i]; } };
+struct OgmPts { const float4* p; LIO_HD float4 at(int i) const { return p[i]; } };
 
 // ---- slice ------------------------------------------------------------------------------------------------------------
 struct OgmSlicePred {

@@ -9,8 +9,8 @@
 #include <math.h>
 #include <stdint.h>
 #include "../../include/liogpu.h"
+#include "lio_gridmath.h"
 
-#define LIO_SDF_HD __host__ __device__ __forceinline__
 #define LIO_SDF_INF (__builtin_huge_valf())          // Utils.hpp:18; it flows through the expressions below, never special-cased
 #define LIO_SDF_MAX_LINE (1 << 24)                   // a pixel index must be exact as a float (the float loop counters)
 #define LIO_SDF_MAX_NODES ((long long)LIO_SDF_NODE_LIMIT)   // 16 bytes each: 512 MiB of nodes, 128 MiB of distances
@@ -21,20 +21,20 @@ enum { LIO_SDF_MIXED = 0, LIO_SDF_ALL_OBSTACLE = 1, LIO_SDF_ALL_FREE = 2 };     
 enum { LIO_SDF_TO_OBSTACLE = 0, LIO_SDF_TO_FREE = 1 };                          // the two transforms of a layer
 
 // ---- PBD:26-101 -----------------------------------------------------------------------------------------------------------
-LIO_SDF_HD float lio_sdf_pbd(float i, float j)
+LIO_HD float lio_sdf_pbd(float i, float j)
 {
     const float a = fabsf(i - j) - 0.5f;
     return a < 0.0f ? 0.0f : a;                      // std::max(a, 0.0F)
 }
 
-LIO_SDF_HD float lio_sdf_sq_pbd(float i, float j, float f)
+LIO_HD float lio_sdf_sq_pbd(float i, float j, float f)
 {
     const float d = lio_sdf_pbd(i, j);
     return d * d + f;
 }
 
 // the point right of the origin that is as far from it as from pixel p > 0 carrying the offset fp: five solutions
-LIO_SDF_HD float lio_sdf_right_of_origin(float p, float fp)
+LIO_HD float lio_sdf_right_of_origin(float p, float fp)
 {
     const float pp = p * p;
     if (fp > pp) return (pp + p + fp) / (2.0f * p);
@@ -45,7 +45,7 @@ LIO_SDF_HD float lio_sdf_right_of_origin(float p, float fp)
     return (pp - p + fp) / (2.0f * p - 2.0f);
 }
 
-LIO_SDF_HD float lio_sdf_equidistance(float q, float fq, float p, float fp)
+LIO_HD float lio_sdf_equidistance(float q, float fq, float p, float fp)
 {
     if (fp == fq) return 0.5f * (p + q);
     const float df = fp - fq, dr = p - q;
@@ -59,7 +59,7 @@ LIO_SDF_HD float lio_sdf_equidistance(float q, float fq, float p, float fp)
 // The lower-bound stack keeps, per bound, the pixel index and z_rhs: z_lhs is the z_rhs of the bound below (-INF for the
 // first live bound) and f is In::at(index).  Stk: v(k), z(k), set(k, v, z), set_z(k, z), k in [0, n).
 template <class In>
-LIO_SDF_HD int lio_sdf_last_zero(const In& in, int n)
+LIO_HD int lio_sdf_last_zero(const In& in, int n)
 {
     for (int q = 0; q < n; ++q)
         if (in.at(q) > 0.0f) return q > 0 ? q - 1 : 0;
@@ -68,7 +68,7 @@ LIO_SDF_HD int lio_sdf_last_zero(const In& in, int n)
 
 // -> the first live bound; *top_out = the last one
 template <class In, class Stk>
-LIO_SDF_HD int lio_sdf_fill_bounds(const In& in, int n, int start, Stk& st, int* top_out)
+LIO_HD int lio_sdf_fill_bounds(const In& in, int n, int start, Stk& st, int* top_out)
 {
     const float nf = (float)n, sf = (float)start;
     int first = 0, top = 0;
@@ -111,7 +111,7 @@ struct LioSdfCursor {
     int start, it, top;
     float lastz;
     template <class In, class Stk>
-    LIO_SDF_HD void begin(const In& in, int n, Stk& st)
+    LIO_HD void begin(const In& in, int n, Stk& st)
     {
         start = lio_sdf_last_zero(in, n);
         it = top = 0;
@@ -122,7 +122,7 @@ struct LioSdfCursor {
         }
     }
     template <class In, class Stk>
-    LIO_SDF_HD float at(const In& in, const Stk& st, int q)
+    LIO_HD float at(const In& in, const Stk& st, int q)
     {
         const float x = in.at(q);
         if (q < start || !(x > 0.0f)) return x;                    // the leading zeros and every zero stay
@@ -139,7 +139,7 @@ struct LioSdfCursor {
 
 // ---- layers ---------------------------------------------------------------------------------------------------------------
 // SD2:190-213: the squared height distance in pixels, ((1 / res) * max(h - e, 0))^2 towards obstacles, min towards free space
-LIO_SDF_HD float lio_sdf_init(float e, float h, float inv_res, int cls)
+LIO_HD float lio_sdf_init(float e, float h, float inv_res, int cls)
 {
     const float d = h - e;
     const float m = cls == LIO_SDF_TO_OBSTACLE ? (d < 0.0f ? 0.0f : d) : (0.0f < d ? 0.0f : d);
@@ -148,13 +148,13 @@ LIO_SDF_HD float lio_sdf_init(float e, float h, float inv_res, int cls)
 }
 
 // SD2:229 / :234: an occupancy grid's offsets
-LIO_SDF_HD float lio_sdf_init_occupancy(bool occupied, int cls)
+LIO_HD float lio_sdf_init_occupancy(bool occupied, int cls)
 {
     return (cls == LIO_SDF_TO_OBSTACLE) == occupied ? 0.0f : LIO_SDF_INF;
 }
 
 // SDF:112-134: gridOriginZ, gridOriginZ + resolution, then gridOriginZ + (layerZ + 1) * resolution with layerZ + 1 = z
-LIO_SDF_HD float lio_sdf_layer_height(float origin_z, float res, int z)
+LIO_HD float lio_sdf_layer_height(float origin_z, float res, int z)
 {
     if (z == 0) return origin_z;
     if (z == 1) return origin_z + res;
@@ -162,20 +162,20 @@ LIO_SDF_HD float lio_sdf_layer_height(float origin_z, float res, int z)
 }
 
 // SD2:244-245 with SDF:83-84: decided by the elevation layer's own extremes
-LIO_SDF_HD int lio_sdf_layer_mode(float h, float e_min, float e_max)
+LIO_HD int lio_sdf_layer_mode(float h, float e_min, float e_max)
 {
     if (h < e_min) return LIO_SDF_ALL_OBSTACLE;
     if (h > e_max) return LIO_SDF_ALL_FREE;
     return LIO_SDF_MIXED;
 }
 
-LIO_SDF_HD bool lio_sdf_mode_uses(int mode, int cls)
+LIO_HD bool lio_sdf_mode_uses(int mode, int cls)
 {
     return mode == LIO_SDF_MIXED || (mode == LIO_SDF_ALL_OBSTACLE) == (cls == LIO_SDF_TO_FREE);
 }
 
 // SD2:250 / :254 / :259 (and :237)
-LIO_SDF_HD float lio_sdf_combine(int mode, float to_obstacle, float to_free, float res)
+LIO_HD float lio_sdf_combine(int mode, float to_obstacle, float to_free, float res)
 {
     if (mode == LIO_SDF_ALL_OBSTACLE) return to_free * -res;
     if (mode == LIO_SDF_ALL_FREE) return to_obstacle * res;
@@ -192,7 +192,7 @@ inline long long lio_sdf_num_layers(double min_h, double max_h, double res)
 // ---- DD:24-59 as SDF:120-161 applies them ---------------------------------------------------------------------------------
 // Differences of one axis: the one-sided factor 1 / step at the ends, 1 / (2 * step) between.  lo, mid, hi: the values at
 // i - 1, i, i + 1 (only the ones the position needs are read by the callers).
-LIO_SDF_HD float lio_sdf_diff(int i, int n, float lo, float mid, float hi, float step)
+LIO_HD float lio_sdf_diff(int i, int n, float lo, float mid, float hi, float step)
 {
     if (i == 0) return (1.0f / step) * (hi - mid);
     if (i == n - 1) return (1.0f / step) * (mid - lo);
@@ -202,7 +202,7 @@ LIO_SDF_HD float lio_sdf_diff(int i, int n, float lo, float mid, float hi, float
 // S::at(r, c, z): the distance layers.  {distance, dx, dy, dz}: dx along the rows and dy along the columns with -res (x and
 // y fall as the indices grow), dz along the layers with +res.  rows, cols, layers >= 2.
 template <class S>
-LIO_SDF_HD float4 lio_sdf_node(const S& sd, int r, int c, int z, int rows, int cols, int layers, float res)
+LIO_HD float4 lio_sdf_node(const S& sd, int r, int c, int z, int rows, int cols, int layers, float res)
 {
     const float d = sd.at(r, c, z);
     const float dx = lio_sdf_diff(r, rows, r > 0 ? sd.at(r - 1, c, z) : d, d, r + 1 < rows ? sd.at(r + 1, c, z) : d, -res);
@@ -218,14 +218,14 @@ struct LioSdfLookup {
 };
 
 // getNearestPositiveInteger: std::round, then std::min and std::max as written (a NaN ends at 0)
-LIO_SDF_HD int lio_sdf_nearest_index(double val, double mx)
+LIO_HD int lio_sdf_nearest_index(double val, double mx)
 {
     const double r = round(val);
     const double m = mx < r ? mx : r;
     return (int)(0.0 < m ? m : 0.0);
 }
 
-LIO_SDF_HD void lio_sdf_nearest_node(const LioSdfLookup& L, const double p[3], int idx[3])
+LIO_HD void lio_sdf_nearest_node(const LioSdfLookup& L, const double p[3], int idx[3])
 {
     const double inv = 1.0 / L.res;
     idx[0] = lio_sdf_nearest_index((L.origin[0] - p[0]) * inv, (double)(L.rows - 1));
@@ -233,7 +233,7 @@ LIO_SDF_HD void lio_sdf_nearest_node(const LioSdfLookup& L, const double p[3], i
     idx[2] = lio_sdf_nearest_index((p[2] - L.origin[2]) * inv, (double)(L.layers - 1));
 }
 
-LIO_SDF_HD size_t lio_sdf_linear_index(const LioSdfLookup& L, const int idx[3])
+LIO_HD size_t lio_sdf_linear_index(const LioSdfLookup& L, const int idx[3])
 {
     return ((size_t)idx[2] * (size_t)L.cols + (size_t)idx[1]) * (size_t)L.rows + (size_t)idx[0];
 }
@@ -241,7 +241,7 @@ LIO_SDF_HD size_t lio_sdf_linear_index(const LioSdfLookup& L, const int idx[3])
 // valueAndDerivative: distance + derivative . (position - nodePosition) in double, the dot summed x, y, z left to right
 // N::at(i): node i as float4
 template <class N>
-LIO_SDF_HD double lio_sdf_value(const LioSdfLookup& L, const N& nodes, const double p[3], double der[3])
+LIO_HD double lio_sdf_value(const LioSdfLookup& L, const N& nodes, const double p[3], double der[3])
 {
     int idx[3];
     lio_sdf_nearest_node(L, p, idx);

@@ -258,7 +258,7 @@ int lio_sdf_build_device(lio_sdf* sdf, const float* d_elev, int rows, int cols, 
     LioSdfLookup L;
     L.rows = rows; L.cols = cols; L.layers = (int)(layers < 0x7fffffffLL ? layers : 0x7fffffffLL);
     L.res = resolution;
-    for (int a = 0; a < 2; ++a) L.origin[a] = position[a] + (0.5 * length[a] - 0.5 * resolution);      // lio_terr_centre(G, a, 0)
+    for (int a = 0; a < 2; ++a) L.origin[a] = position[a] + (0.5 * length[a] - 0.5 * resolution);      // lio_gm_centre(G, a, 0)
     L.origin[2] = min_h;
     info->layers = L.layers;
     for (int a = 0; a < 3; ++a) info->origin[a] = L.origin[a];
@@ -326,11 +326,8 @@ int lio_sdf_check(const lio_sdf_config* cfg, int rows, int cols, double resoluti
     if (!length || !position) return lio_fail(LIO_ERR_ARG, "null argument");
     if (rows < 2 || cols < 2) return lio_fail(LIO_ERR_ARG, "rows and cols must be at least 2 (the finite differences)");
     if (rows >= LIO_SDF_MAX_LINE || cols >= LIO_SDF_MAX_LINE) return lio_fail(LIO_ERR_ARG, "rows and cols must be below 2^24");
-    if (!std::isfinite(resolution) || resolution < 1e-4) return lio_fail(LIO_ERR_ARG, "resolution must be finite and at least 1e-4");
-    for (int a = 0; a < 2; ++a) {
-        if (!std::isfinite(length[a]) || !std::isfinite(position[a])) return lio_fail(LIO_ERR_ARG, "length and position must be finite");
-        if (length[a] != (double)(a == 0 ? rows : cols) * resolution) return lio_fail(LIO_ERR_ARG, "length must be size * resolution (GridMap::setGeometry)");
-    }
+    if (const char* why = lio_gm_resolution_refusal(resolution)) return lio_fail(LIO_ERR_ARG, why);
+    if (const char* why = lio_gm_axes_refusal(rows, cols, resolution, length, position)) return lio_fail(LIO_ERR_ARG, why);
     return LIO_OK;
 }
 

@@ -7,17 +7,12 @@
 #include <float.h>
 #include <math.h>
 #include "../../include/liogpu.h"
+#include "lio_gridmath.h"
 
 #define LIO_TERR_MAX_CELLS 32      // the largest radius and half-window, in cells: bounds the halo of the LDS tile
 
-// grid_map's geometry as the iterators read it; base = position + (0.5 length - 0.5 resolution) (getVectorToFirstCell)
-struct LioTerrGeom {
-    double pos[2], len[2], half[2], base[2], res;
-    int rows, cols;
-};
-
 struct LioTerrParams {
-    LioTerrGeom G;
+    LioGridGeom G;
     double r_smooth, r_normal;
     int method, axis;              // method as used: 0 area, 1 raster
     int halo;                      // cells of input a tile needs around itself: the circles' windows and the raster stencil
@@ -31,42 +26,19 @@ struct LioTerrCell {
     bool valid, normal, few, degenerate;
 };
 
-#define LIO_TERR_NAN __builtin_nanf("")
-#define LIO_TERR_HD __host__ __device__ __forceinline__
-
-// getPositionFromIndex (GridMapMath.cpp:130-145), default start index, one component
-LIO_TERR_HD double lio_terr_centre(const LioTerrGeom& G, int a, int i) { return G.base[a] + G.res * (double)(-i); }
-
-// boundPositionToRange (GridMapMath.cpp:255-280) then getIndexFromPosition (:147-160), one component.  The reference
-// ignores getIndexFromPosition's verdict; an index outside the buffer (a length whose last ulp swallows the epsilon) would
-// read past it there and is brought back to the last cell here.
-LIO_TERR_HD int lio_terr_index(const LioTerrGeom& G, int a, double p)
-{
-    double eps = 10.0 * DBL_EPSILON;
-    if (fabs(p) > 1.0) eps *= fabs(p);
-    double sh = (p - G.pos[a]) + G.half[a];
-    if (sh <= 0.0) sh = eps;
-    else if (sh >= G.len[a]) sh = G.len[a] - eps;
-    const double q = (sh + G.pos[a]) - G.half[a];
-    const double v = ((q - G.half[a]) - G.pos[a]) / G.res;
-    const int n = a == 0 ? G.rows : G.cols;
-    const int idx = (int)(-v);
-    return idx < 0 ? 0 : (idx >= n ? n - 1 : idx);
-}
-
 // CircleIterator::findSubmapParameters: [lo, hi] of the candidates along one axis, additionally kept within `halo` cells
 // of the centre (never narrower than the reference's window: the halo is floor(radius / resolution + 0.5) + 1 at least)
-LIO_TERR_HD void lio_terr_window(const LioTerrGeom& G, int a, int i, double centre, double radius, int halo, int& lo, int& hi)
+LIO_HD void lio_terr_window(const LioGridGeom& G, int a, int i, double centre, double radius, int halo, int& lo, int& hi)
 {
-    lo = lio_terr_index(G, a, centre + radius);
-    hi = lio_terr_index(G, a, centre - radius);
+    lo = lio_gm_bound_index(G, a, centre + radius);
+    hi = lio_gm_bound_index(G, a, centre - radius);
     if (lo < i - halo) lo = i - halo;
     if (hi > i + halo) hi = i + halo;
 }
 
 struct LioTerrV3 { double x, y, z; };
 
-LIO_TERR_HD LioTerrV3 lio_terr_cross(const LioTerrV3& a, const LioTerrV3& b)
+LIO_HD LioTerrV3 lio_terr_cross(const LioTerrV3& a, const LioTerrV3& b)
 {
     LioTerrV3 c;
     c.x = a.y * b.z - a.z * b.y;
@@ -75,11 +47,11 @@ LIO_TERR_HD LioTerrV3 lio_terr_cross(const LioTerrV3& a, const LioTerrV3& b)
     return c;
 }
 
-LIO_TERR_HD double lio_terr_dot(const LioTerrV3& a, const LioTerrV3& b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+LIO_HD double lio_terr_dot(const LioTerrV3& a, const LioTerrV3& b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 
 // extract_kernel of Eigen's direct 3 x 3 solver on the symmetric matrix (a00 a10 a20; a10 a11 a21; a20 a21 a22): the column
 // of the largest |diagonal| (the first of equals) crossed with the two others, the longer product normalised
-LIO_TERR_HD void lio_terr_kernel_of(double a00, double a11, double a22, double a10, double a20, double a21, LioTerrV3& res, LioTerrV3& rep)
+LIO_HD void lio_terr_kernel_of(double a00, double a11, double a22, double a10, double a20, double a21, LioTerrV3& res, LioTerrV3& rep)
 {
     int i0 = 0;
     double m = fabs(a00);
@@ -98,7 +70,7 @@ LIO_TERR_HD void lio_terr_kernel_of(double a00, double a11, double a22, double a
 // q = (xx, yx, yy, zx, zy, zz): *v0 = eigenvectors().col(0); returns eigenvalues()(1).  Shift by trace / 3, scale by the
 // largest |coefficient|, the roots by the trigonometric closed form, the eigenvector of the better separated of the extreme
 // eigenvalues by extract_kernel, column 0 from it as the solver does.
-LIO_TERR_HD double lio_terr_eigen(int n, const double s[3], const double q[6], LioTerrV3* v0)
+LIO_HD double lio_terr_eigen(int n, const double s[3], const double q[6], LioTerrV3* v0)
 {
     const double dn = (double)n;
     const double m0 = s[0] / dn, m1 = s[1] / dn, m2 = s[2] / dn;
@@ -150,15 +122,15 @@ LIO_TERR_HD double lio_terr_eigen(int n, const double s[3], const double q[6], L
     return r1 * scale + shift;
 }
 
-LIO_TERR_HD bool lio_terr_finite(float v) { return fabsf(v) <= FLT_MAX; }
+LIO_HD bool lio_terr_finite(float v) { return fabsf(v) <= FLT_MAX; }
 
 // One cell of the first kernel: smooth, the normal, slope, roughness, traversability.  T::at(i, j) = the input layer at
 // row i, column j, for every (i, j) of the grid within P.halo cells of (r, c).
 template <class T>
-LIO_TERR_HD void lio_terr_cell(const LioTerrParams& P, const T& in, int r, int c, LioTerrCell* o)
+LIO_HD void lio_terr_cell(const LioTerrParams& P, const T& in, int r, int c, LioTerrCell* o)
 {
-    const LioTerrGeom& G = P.G;
-    const double cx = lio_terr_centre(G, 0, r), cy = lio_terr_centre(G, 1, c);
+    const LioGridGeom& G = P.G;
+    const double cx = lio_gm_centre(G, 0, r), cy = lio_gm_centre(G, 1, c);
     const float z = in.at(r, c);
     o->valid = lio_terr_finite(z);
     o->normal = o->few = o->degenerate = false;
@@ -171,9 +143,9 @@ LIO_TERR_HD void lio_terr_cell(const LioTerrParams& P, const T& in, int r, int c
         double sum = 0.0;
         int cnt = 0;
         for (int i = i0; i <= i1; ++i) {
-            const double dx = lio_terr_centre(G, 0, i) - cx, dx2 = dx * dx;
+            const double dx = lio_gm_centre(G, 0, i) - cx, dx2 = dx * dx;
             for (int j = j0; j <= j1; ++j) {
-                const double dy = lio_terr_centre(G, 1, j) - cy;
+                const double dy = lio_gm_centre(G, 1, j) - cy;
                 if (!(dx2 + dy * dy <= r2)) continue;
                 const float v = in.at(i, j);
                 if (!lio_terr_finite(v)) continue;
@@ -181,7 +153,7 @@ LIO_TERR_HD void lio_terr_cell(const LioTerrParams& P, const T& in, int r, int c
                 ++cnt;
             }
         }
-        o->smooth = cnt ? (float)(sum / (double)cnt) : LIO_TERR_NAN;
+        o->smooth = cnt ? (float)(sum / (double)cnt) : LIO_QNAN;
     }
     // ---- normal
     double n[3] = { 0.0, 0.0, 0.0 };
@@ -194,9 +166,9 @@ LIO_TERR_HD void lio_terr_cell(const LioTerrParams& P, const T& in, int r, int c
             double s[3] = { 0.0, 0.0, 0.0 }, q[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
             int cnt = 0;
             for (int i = i0; i <= i1; ++i) {
-                const double x = lio_terr_centre(G, 0, i), dx = x - cx, dx2 = dx * dx;
+                const double x = lio_gm_centre(G, 0, i), dx = x - cx, dx2 = dx * dx;
                 for (int j = j0; j <= j1; ++j) {
-                    const double y = lio_terr_centre(G, 1, j), dy = y - cy;
+                    const double y = lio_gm_centre(G, 1, j), dy = y - cy;
                     if (!(dx2 + dy * dy <= r2)) continue;
                     const float v = in.at(i, j);
                     if (!lio_terr_finite(v)) continue;
@@ -248,7 +220,7 @@ LIO_TERR_HD void lio_terr_cell(const LioTerrParams& P, const T& in, int r, int c
         if (along < 0.0) { n[0] = -n[0]; n[1] = -n[1]; n[2] = -n[2]; }
         o->nx = (float)n[0]; o->ny = (float)n[1]; o->nz = (float)n[2];
     } else {
-        o->nx = o->ny = o->nz = LIO_TERR_NAN;
+        o->nx = o->ny = o->nz = LIO_QNAN;
     }
     // ---- the MathExpressionFilters (EigenLab on MatrixXf: float) and the two ThresholdFilters (ThresholdFilter.cpp:79-90)
     o->slope = acosf(o->nz);
@@ -260,7 +232,7 @@ LIO_TERR_HD void lio_terr_cell(const LioTerrParams& P, const T& in, int r, int c
 }
 
 // scalar_sum_of_finites_op (FunctorsPlugin.hpp:3-12)
-LIO_TERR_HD float lio_terr_sum_of_finites(float a, float b)
+LIO_HD float lio_terr_sum_of_finites(float a, float b)
 {
     const bool fa = lio_terr_finite(a), fb = lio_terr_finite(b);
     if (fa && fb) return a + b;
@@ -273,7 +245,7 @@ LIO_TERR_HD float lio_terr_sum_of_finites(float a, float b)
 // cropped window (SlidingWindowIterator.cpp:59-73), reduced serially in the block's column-major order.  T::at as above
 // on the slope layer, within P.margin cells.
 template <class T>
-LIO_TERR_HD float lio_terr_edge(const LioTerrParams& P, const T& slope, int r, int c)
+LIO_HD float lio_terr_edge(const LioTerrParams& P, const T& slope, int r, int c)
 {
     const int i0 = r - P.margin < 0 ? 0 : r - P.margin, i1 = r + P.margin > P.G.rows - 1 ? P.G.rows - 1 : r + P.margin;
     const int j0 = c - P.margin < 0 ? 0 : c - P.margin, j1 = c + P.margin > P.G.cols - 1 ? P.G.cols - 1 : c + P.margin;
@@ -320,7 +292,7 @@ __device__ __forceinline__ TerrTile terr_stage(const float* __restrict__ src, in
     const int pitch = TERR_ROWS + 2 * h, n = pitch * (TERR_COLS + 2 * h);
     for (int k = (int)threadIdx.x; k < n; k += TERR_ROWS * TERR_COLS) {
         const int i = tr0 - h + k % pitch, j = tc0 - h + k / pitch;
-        tile[k] = (i >= 0 && i < rows && j >= 0 && j < cols) ? src[(size_t)i + (size_t)j * (size_t)rows] : LIO_TERR_NAN;
+        tile[k] = (i >= 0 && i < rows && j >= 0 && j < cols) ? src[(size_t)i + (size_t)j * (size_t)rows] : LIO_QNAN;
     }
     __syncthreads();
     r = tr0 + ((int)threadIdx.x % TERR_ROWS);

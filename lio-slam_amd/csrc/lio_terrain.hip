@@ -117,15 +117,8 @@ int lio_terrain_check(const lio_terrain_config* c, double resolution, LioTerrPla
 
 int lio_terrain_set_geometry(LioTerrPlan* plan, int rows, int cols, double resolution, const double length[2], const double position[2])
 {
-    LioTerrGeom& G = plan->P.G;
-    G.rows = rows; G.cols = cols; G.res = resolution;
-    for (int a = 0; a < 2; ++a) {
-        if (!std::isfinite(length[a]) || !std::isfinite(position[a])) return lio_fail(LIO_ERR_ARG, "length and position must be finite");
-        if (length[a] != (double)(a == 0 ? rows : cols) * resolution) return lio_fail(LIO_ERR_ARG, "length must be size * resolution (GridMap::setGeometry)");
-        G.len[a] = length[a]; G.pos[a] = position[a];
-        G.half[a] = 0.5 * length[a];                       // getVectorToOrigin
-        G.base[a] = position[a] + (G.half[a] - 0.5 * resolution);          // mapPosition + getVectorToFirstCell
-    }
+    if (const char* why = lio_gm_axes_refusal(rows, cols, resolution, length, position)) return lio_fail(LIO_ERR_ARG, why);
+    plan->P.G = lio_gm_geom(rows, cols, resolution, position[0], position[1]);
     return LIO_OK;
 }
 

@@ -11,7 +11,7 @@ What is not the reference's:
  - extendToInclude and addDataFrom ignore getIndex's verdict after isInside and would read past the buffer when it fails: such a
    cell is skipped and counted (n_index_outside);
  - submap_information(clamp=True), the library's form: a bounded corner whose getIndexFromPosition still fails is brought back
-   to the last cell (lio_terr_index), where the reference (clamp=False) returns false;
+   to the last cell (lio_gm_bound_index), where the reference (clamp=False) returns false;
  - index_shift raises ValueError where the reference's cast is undefined (|v| >= 2^30 or not finite).
 """
 import math

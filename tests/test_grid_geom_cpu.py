@@ -158,7 +158,7 @@ def test_index_shift_from_position_shift_literals():
 
 
 def test_clamped_corner_rule_agrees_on_every_window():
-    """the library's corner rule (lio_terr_index's clamp) against the reference's verdict over the windows the tests use"""
+    """the library's corner rule (lio_gm_bound_index's clamp) against the reference's verdict over the windows the tests use"""
     n = 0
     for rows, cols, _, res in K.shapes():
         g = K.geometry(rows, cols, res)

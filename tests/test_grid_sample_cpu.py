@@ -1,7 +1,8 @@
 """The layer sampling without a GPU: the numpy restatement of GridMap::atPosition (tests/grid_sample_restate.py) against the
 values the reference's own tests hold (GridMapTest.cpp:448-494), against the seven analytic surfaces of its cubic tests at
 their own bound of 1e-3, and, for the linear method, against scipy; then the header the kernel runs
-(lio-slam_amd/csrc/lio_gridsample.h, through tools/grid_sample_host_check.cpp) against the restatement, bit for bit."""
+(lio-slam_amd/csrc/lio_gridsample.h over the geometry of lio_gridmath.h, through tools/grid_sample_host_check.cpp) against the
+restatement, bit for bit."""
 import os
 import shutil
 import subprocess
@@ -130,7 +131,7 @@ def test_fall_back_chain_on_holes():
 
 
 def test_header_on_the_host_equals_the_restatement():
-    """tools/grid_sample_host_check.cpp runs csrc/lio_gridsample.h -- the text the kernel runs -- on the host: its own run
+    """tools/grid_sample_host_check.cpp runs csrc/lio_gridsample.h and lio_gridmath.h -- the text the kernel runs -- on the host: its own run
     counts no read outside a layer, and its `dump` mode equals the restatement on the border lattice, for every method and both
     border modes, values as words (NaN for NaN where a method computed it) and method bytes"""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"

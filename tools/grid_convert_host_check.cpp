@@ -28,7 +28,6 @@
 #include <vector>
 
 #include "../lio-slam_amd/csrc/lio_gridconvert.h"
-#include "../lio-slam_amd/csrc/lio_gridgeom.h"
 #include "../lio-slam_amd/csrc/lio_wg.h"
 
 typedef std::vector<unsigned char> Bytes;
@@ -285,14 +284,14 @@ int main(int argc, char** argv)
     }
     if ((mode == "cloud" && argc == 13) || (mode == "cells" && argc == 11)) {
         const int rows = atoi(argv[2]), cols = atoi(argv[3]);
-        const LioTerrGeom G = lio_gg_geom(rows, cols, strtod(argv[4], nullptr), strtod(argv[5], nullptr), strtod(argv[6], nullptr));
+        const LioGridGeom G = lio_gm_geom(rows, cols, strtod(argv[4], nullptr), strtod(argv[5], nullptr), strtod(argv[6], nullptr));
         const size_t cells = (size_t)rows * cols;
         if (mode == "cells") {
             const float lo = strtof(argv[7], nullptr), hi = strtof(argv[8], nullptr);
             const std::vector<float> layer = read_file<float>(argv[9], cells);
             std::vector<double> rec;
             for (size_t i = 0; i < cells; ++i)
-                if (lio_gc_cell_kept(layer.at(i), lo, hi)) { rec.push_back(lio_terr_centre(G, 0, (int)(i % rows))); rec.push_back(lio_terr_centre(G, 1, (int)(i / rows))); }
+                if (lio_gc_cell_kept(layer.at(i), lo, hi)) { rec.push_back(lio_gm_centre(G, 0, (int)(i % rows))); rec.push_back(lio_gm_centre(G, 1, (int)(i / rows))); }
             const int64_t n = (int64_t)rec.size() / 2;
             Out out(argv[10]);
             out.put(&n, 8); out.put(rec.data(), 8 * rec.size());

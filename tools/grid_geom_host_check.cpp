@@ -29,7 +29,7 @@
 static long long g_bad = 0;
 
 struct Map {                       // a map on the host: the layers of `mask` as words, column-major
-    LioTerrGeom G;
+    LioGridGeom G;
     unsigned mask = 0;
     std::vector<uint32_t> layer[LIO_GRID_MAX_LAYERS];
     size_t cells() const { return (size_t)G.rows * (size_t)G.cols; }
@@ -42,9 +42,9 @@ struct Result {
 
 static void make(Map& m, int rows, int cols, double res, double px, double py, unsigned mask)
 {
-    m.G = lio_gg_geom(rows, cols, res, px, py);
+    m.G = lio_gm_geom(rows, cols, res, px, py);
     m.mask = mask;
-    for (int k = 0; k < LIO_GRID_MAX_LAYERS; ++k) m.layer[k].assign(((mask >> k) & 1u) ? m.cells() : 0, LIO_GG_QNAN);
+    for (int k = 0; k < LIO_GRID_MAX_LAYERS; ++k) m.layer[k].assign(((mask >> k) & 1u) ? m.cells() : 0, LIO_QNAN_BITS);
 }
 
 static bool submap(const Map& src, const double q[2], const double len[2], Map& dst, Result& R)
@@ -83,15 +83,15 @@ static bool move(Map& m, const double q[2], Result& R)
         for (int c = 0; c < m.G.cols; ++c)
             for (int r = 0; r < m.G.rows; ++r) R.cleared += lio_gg_offset_cell(T, m.G.rows, m.G.rows, m.G.cols, shift[0], shift[1], r, c) ? 1 : 0;
     }
-    m.G = lio_gg_geom(m.G.rows, m.G.cols, m.G.res, to[0], to[1]);
+    m.G = lio_gm_geom(m.G.rows, m.G.cols, m.G.res, to[0], to[1]);
     return true;
 }
 
 // extendToInclude (add = false) and addDataFrom, as lio_gridgeom.hip's gg_extend_add decides them
 static bool extend_add(Map& g, const Map& other, bool extend, bool add, bool overwrite, unsigned listed, unsigned basic, Result& R)
 {
-    const LioTerrGeom O = g.G, X = other.G;
-    LioTerrGeom N = O;
+    const LioGridGeom O = g.G, X = other.G;
+    LioGridGeom N = O;
     bool resized = false;
     if (extend) {
         double position[2], length[2];
@@ -102,12 +102,12 @@ static bool extend_add(Map& g, const Map& other, bool extend, bool add, bool ove
         }
         if (resized) {
             for (int a = 0; a < 2; ++a) {
-                const double n = lio_gt_size(length[a], O.res);
+                const double n = lio_gm_size(length[a], O.res);
                 if (!(n >= 1.0) || !(n < 16777216.0)) return false;
                 size[a] = (int)n;
             }
             for (int a = 0; a < 2; ++a) position[a] = lio_gg_align_axis(position[a], O.pos[a], O.res, size[a], a == 0 ? O.rows : O.cols);
-            N = lio_gg_geom(size[0], size[1], O.res, position[0], position[1]);
+            N = lio_gm_geom(size[0], size[1], O.res, position[0], position[1]);
         }
     }
     R.flag = resized ? 1 : 0;
@@ -257,7 +257,7 @@ static int own_cases()
                             for (int r = 0; r < rows; ++r) {
                                 const int sr = r + s0[i], sc = c + s1[j];
                                 const bool in = sr >= 0 && sr < rows && sc >= 0 && sc < cols;
-                                const uint32_t want = in ? g.layer[k][(size_t)sc * rows + sr] : LIO_GG_QNAN;
+                                const uint32_t want = in ? g.layer[k][(size_t)sc * rows + sr] : LIO_QNAN_BITS;
                                 if (m.layer[k][(size_t)c * rows + r] != want) { expect(false, "moved word", r, c); r = rows; c = cols; }
                                 if (k == 0 && !in) ++cleared;
                             }

@@ -34,18 +34,6 @@ struct CheckedLayer {
     }
 };
 
-static void geometry(LioTerrGeom& G, int rows, int cols, double res, double px, double py)
-{
-    G.rows = rows; G.cols = cols; G.res = res;
-    const double pos[2] = { px, py };
-    for (int a = 0; a < 2; ++a) {
-        G.len[a] = (double)(a == 0 ? rows : cols) * res;
-        G.pos[a] = pos[a];
-        G.half[a] = 0.5 * G.len[a];
-        G.base[a] = pos[a] + (G.half[a] - 0.5 * res);
-    }
-}
-
 struct Result {
     std::vector<lio_grid_region_stat> stat;
     std::vector<int32_t> n_cells, cells;
@@ -55,7 +43,7 @@ struct Result {
 
 // both entry points' outputs for one layer, through the header alone: the plan's two halves, the cells by order, the
 // reduction by rank
-static void run(const LioTerrGeom& G, const std::vector<float>& layer, const std::vector<lio_grid_region>& regions, const std::vector<double>& verts,
+static void run(const LioGridGeom& G, const std::vector<float>& layer, const std::vector<lio_grid_region>& regions, const std::vector<double>& verts,
                 float threshold, Result& o)
 {
     const size_t n = regions.size();
@@ -143,7 +131,7 @@ static void polygon(std::vector<lio_grid_region>& regions, std::vector<double>& 
     regions.push_back(r);
 }
 
-static void lattice(const LioTerrGeom& G, std::vector<lio_grid_region>& regions, std::vector<double>& verts)
+static void lattice(const LioGridGeom& G, std::vector<lio_grid_region>& regions, std::vector<double>& verts)
 {
     std::vector<double> ax[2];
     for (int a = 0; a < 2; ++a) {
@@ -204,8 +192,7 @@ int main(int argc, char** argv)
         const float threshold = (float)atof(argv[7]);
         const size_t n = (size_t)atoll(argv[10]), nv = (size_t)atoll(argv[12]);
         if (rows < 1 || cols < 1 || !(res > 0.0)) { fprintf(stderr, "bad arguments\n"); return 2; }
-        LioTerrGeom G;
-        geometry(G, rows, cols, res, atof(argv[5]), atof(argv[6]));
+        const LioGridGeom G = lio_gm_geom(rows, cols, res, atof(argv[5]), atof(argv[6]));
         std::vector<float> layer((size_t)rows * (size_t)cols);
         std::vector<lio_grid_region> regions(n);
         std::vector<double> verts(2 * nv + 2);
@@ -232,8 +219,7 @@ int main(int argc, char** argv)
     const int shapes[][2] = { { 1, 1 }, { 3, 3 }, { 8, 5 }, { 5, 8 }, { 70, 50 } };
     for (const auto& s : shapes)
         for (int holes = 0; holes < 2; ++holes) {
-            LioTerrGeom G;
-            geometry(G, s[0], s[1], holes ? 0.2 : 1.0, holes ? 1e3 : 0.0, holes ? -3e3 : 0.0);
+            const LioGridGeom G = lio_gm_geom(s[0], s[1], holes ? 0.2 : 1.0, holes ? 1e3 : 0.0, holes ? -3e3 : 0.0);
             std::vector<float> layer((size_t)s[0] * (size_t)s[1]);
             for (size_t k = 0; k < layer.size(); ++k) layer[k] = 0.001f * (float)((k * 37) % 1000);
             if (holes)
@@ -254,8 +240,7 @@ int main(int argc, char** argv)
                    regions.size(), cnt[0], cnt[1], cnt[2], (long long)o.offsets.back(), (unsigned long long)checksum(o));
         }
     {                                                      // the single-thread cost of a region
-        LioTerrGeom G;
-        geometry(G, 550, 400, 0.2, 0.0, 0.0);
+        const LioGridGeom G = lio_gm_geom(550, 400, 0.2, 0.0, 0.0);
         std::vector<float> layer((size_t)550 * 400);
         for (size_t k = 0; k < layer.size(); ++k) layer[k] = 0.001f * (float)(k % 977);
         const char* names[] = { "line (40 cells)", "circle (r 1 m)", "ellipse (4 x 2 m)", "polygon (4 x 2 m)" };

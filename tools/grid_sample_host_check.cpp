@@ -37,19 +37,7 @@ struct CheckedLayer {
     }
 };
 
-static void geometry(LioTerrGeom& G, int rows, int cols, double res, double px, double py)
-{
-    G.rows = rows; G.cols = cols; G.res = res;
-    const double pos[2] = { px, py };
-    for (int a = 0; a < 2; ++a) {
-        G.len[a] = (double)(a == 0 ? rows : cols) * res;
-        G.pos[a] = pos[a];
-        G.half[a] = 0.5 * G.len[a];
-        G.base[a] = pos[a] + (G.half[a] - 0.5 * res);
-    }
-}
-
-static void run(const LioTerrGeom& G, const std::vector<float>& layer, const std::vector<double>& pos, int method, int border, std::vector<float>& val,
+static void run(const LioGridGeom& G, const std::vector<float>& layer, const std::vector<double>& pos, int method, int border, std::vector<float>& val,
                 std::vector<unsigned char>& used)
 {
     const size_t n = pos.size() / 2;
@@ -79,7 +67,7 @@ static uint64_t checksum(const std::vector<float>& val, const std::vector<unsign
 }
 
 // the lattice of tests/grid_sample_restate.py border_lattice
-static std::vector<double> lattice(const LioTerrGeom& G)
+static std::vector<double> lattice(const LioGridGeom& G)
 {
     std::vector<double> ax[2];
     for (int a = 0; a < 2; ++a) {
@@ -117,8 +105,7 @@ int main(int argc, char** argv)
         const double res = atof(argv[4]);
         const size_t n = (size_t)atoll(argv[11]);
         if (rows < 1 || cols < 1 || !(res > 0.0) || method < 0 || method > 3 || border < 0 || border > 1) { fprintf(stderr, "bad arguments\n"); return 2; }
-        LioTerrGeom G;
-        geometry(G, rows, cols, res, atof(argv[5]), atof(argv[6]));
+        const LioGridGeom G = lio_gm_geom(rows, cols, res, atof(argv[5]), atof(argv[6]));
         std::vector<float> layer((size_t)rows * (size_t)cols);
         std::vector<double> pos(2 * n);
         if (!read_file(argv[9], layer.data(), 4 * layer.size()) || !read_file(argv[10], pos.data(), 8 * pos.size())) { fprintf(stderr, "cannot read the inputs\n"); return 2; }
@@ -137,8 +124,7 @@ int main(int argc, char** argv)
     const char* names[] = { "nearest", "linear", "cubic convolution", "cubic" };
     for (const auto& s : shapes)
         for (int holes = 0; holes < 2; ++holes) {
-            LioTerrGeom G;
-            geometry(G, s[0], s[1], 0.2, holes ? 1e4 : 0.0, holes ? -3e4 : 0.0);
+            const LioGridGeom G = lio_gm_geom(s[0], s[1], 0.2, holes ? 1e4 : 0.0, holes ? -3e4 : 0.0);
             std::vector<float> layer((size_t)s[0] * (size_t)s[1]);
             for (size_t k = 0; k < layer.size(); ++k) layer[k] = 1.0f + 0.37f * (float)k + 0.01f * (float)(k * k % 7);
             if (holes && layer.size() > 4) {
@@ -168,8 +154,7 @@ int main(int argc, char** argv)
                 }
         }
     {                                                      // the single-thread cost of a query
-        LioTerrGeom G;
-        geometry(G, 550, 400, 0.2, 0.0, 0.0);
+        const LioGridGeom G = lio_gm_geom(550, 400, 0.2, 0.0, 0.0);
         std::vector<float> layer((size_t)550 * 400);
         for (size_t k = 0; k < layer.size(); ++k) layer[k] = 0.001f * (float)(k % 977);
         uint32_t seed = 12345u;

@@ -25,23 +25,11 @@
 
 static long long g_oob = 0, g_bad = 0;
 
-static void geometry(LioTerrGeom& G, int rows, int cols, double res, double px, double py)
-{
-    G.rows = rows; G.cols = cols; G.res = res;
-    const double pos[2] = { px, py };
-    for (int a = 0; a < 2; ++a) {
-        G.len[a] = (double)(a == 0 ? rows : cols) * res;
-        G.pos[a] = pos[a];
-        G.half[a] = 0.5 * G.len[a];
-        G.base[a] = pos[a] + (G.half[a] - 0.5 * res);
-    }
-}
-
 static uint32_t word(float f) { uint32_t w; memcpy(&w, &f, 4); return w; }
 static float from_word(uint32_t w) { float f; memcpy(&f, &w, 4); return f; }
 
 struct Map {                       // a map on the host: n layers of words, column-major
-    LioTerrGeom G;
+    LioGridGeom G;
     std::vector<std::vector<uint32_t>> layer;
     long long counts[3] = { 0, 0, 0 };                     // source cells, samples outside, cells written
     std::vector<int32_t> winner;   // per new cell: the visit whose values it holds, -1 none
@@ -54,11 +42,11 @@ static bool new_map(const Map& src, const LioGtXf& T, Map& dst)
     lio_gt_new_extent(src.G.len, src.G.pos, T, centre, new_length);
     int size[2];
     for (int a = 0; a < 2; ++a) {
-        const double n = lio_gt_size(new_length[a], src.G.res);
+        const double n = lio_gm_size(new_length[a], src.G.res);
         if (!(n >= 1.0) || !(n < 16777216.0)) return false;
         size[a] = (int)n;
     }
-    geometry(dst.G, size[0], size[1], src.G.res, centre[0], centre[1]);
+    dst.G = lio_gm_geom(size[0], size[1], src.G.res, centre[0], centre[1]);
     const size_t cells = (size_t)size[0] * (size_t)size[1];
     dst.layer.assign(src.layer.size(), std::vector<uint32_t>(cells, 0x7fc00000u));
     dst.winner.assign(cells, -1);
@@ -118,7 +106,7 @@ static bool as_written(const Map& src, const LioGtXf& T, int height, double samp
         const float value = from_word(src.layer[height][(size_t)col * rows + row]);
         if (!std::isfinite(value)) continue;
         ++newMap.counts[0];
-        const double center[3] = { lio_terr_centre(src.G, 0, row), lio_terr_centre(src.G, 1, col), (double)value };
+        const double center[3] = { lio_gm_centre(src.G, 0, row), lio_gm_centre(src.G, 1, col), (double)value };
         positionSamples.clear();
         if (sampleRatio > 0.0) {
             const double five[5][2] = { { center[0], center[1] }, { center[0] - sampleLength, center[1] }, { center[0] + sampleLength, center[1] },
@@ -132,7 +120,7 @@ static bool as_written(const Map& src, const LioGtXf& T, int height, double samp
             double transformedPosition[3];
             for (int i = 0; i < 3; ++i) transformedPosition[i] = ((T.m[4 * i] * x + T.m[4 * i + 1] * y) + T.m[4 * i + 2] * z) + T.m[4 * i + 3];
             int newIndex[2];
-            if (!lio_gs_index(newMap.G, transformedPosition[0], transformedPosition[1], &newIndex[0], &newIndex[1])) { ++newMap.counts[1]; continue; }
+            if (!lio_gm_index(newMap.G, transformedPosition[0], transformedPosition[1], &newIndex[0], &newIndex[1])) { ++newMap.counts[1]; continue; }
             const size_t at = (size_t)newIndex[1] * (size_t)newMap.G.rows + (size_t)newIndex[0];
             if (at >= newMap.winner.size()) { ++g_oob; continue; }
             const float newExistingValue = from_word(newMap.layer[height][at]);
@@ -202,7 +190,7 @@ int main(int argc, char** argv)
         const double res = atof(argv[4]), ratio = atof(argv[9]);
         if (rows < 1 || cols < 1 || !(res > 0.0) || n_layers < 1 || n_layers > LIO_GRID_MAX_LAYERS || height < 0 || height >= n_layers) { fprintf(stderr, "bad arguments\n"); return 2; }
         Map src, dst;
-        geometry(src.G, rows, cols, res, atof(argv[5]), atof(argv[6]));
+        src.G = lio_gm_geom(rows, cols, res, atof(argv[5]), atof(argv[6]));
         LioGtXf T;
         for (int k = 0; k < 12; ++k) T.m[k] = atof(argv[10 + k]);
         const size_t cells = (size_t)rows * (size_t)cols;
@@ -239,7 +227,7 @@ int main(int argc, char** argv)
     };
     for (const Case& c : cases) {
         Map src;
-        geometry(src.G, c.rows, c.cols, c.res, c.px, c.py);
+        src.G = lio_gm_geom(c.rows, c.cols, c.res, c.px, c.py);
         const size_t cells = (size_t)c.rows * (size_t)c.cols;
         src.layer.assign(3, std::vector<uint32_t>(cells));
         uint32_t seed = 12345u + (uint32_t)cells;
