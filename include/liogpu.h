@@ -1603,6 +1603,78 @@ int  lio_sdf_to_point_cloud(lio_sdf *sdf, int32_t decimation, float lower, float
  * launch their LDS-tiled kernels instead of the direct ones they run by default, for comparison (the same bytes). */
 int  lio_grid_convert_debug_stage_ms(int32_t enable, int32_t use_tiled, float ms[3]);
 
+/* ------------------------------------------------ resident planning layers filtered into new layers (grid_map_filters) */
+/* grid_map_filters' MinInRadiusFilter, MeanInRadiusFilter, SlidingWindowMathExpressionFilter, CurvatureFilter,
+ * ThresholdFilter, DuplicationFilter and DeletionFilter on a lio_grid: a layer derived from one the object holds, wherever
+ * that layer came from (the planning chain, lio_grid_add_data_from, lio_grid_move, an image, an occupancy grid), without it
+ * crossing PCIe.  DESIGN.md section 4p states the conventions and the labelled deviations; parity is against the restatement
+ * (tests/grid_filter_restate.py) with the reference's own test values on top (parity unpinned).  All arithmetic is IEEE basic
+ * operations in the reference's order; every word equals the serial loops'.
+ *
+ * Common to the four filters: out_layer is any id in 0 .. 15; the call replaces what that layer held (the reference's
+ * mapOut.add(output_layer) overwrites with NaN), so a cell the filter does not write is the quiet NaN 0x7fc00000.  info may be
+ * NULL: n_visited counts the cells the reference's loop evaluates, n_written the cells that receive a value, n_changed the cells
+ * the threshold sets.  Complete on return with one host wait.  A failure leaves the object's layer set as it was.  LIO_ERR_ARG,
+ * never a clamp, the arguments checked before the object is read: a null g, an object without layers, an absent input layer, a
+ * layer id outside 0 .. 15, an op, a mode or a flag out of range, a non-finite or negative radius or length, a radius or a
+ * half-window above 32 cells. */
+enum { LIO_GF_MIN = 0, LIO_GF_MEAN = 1 };                                               /* radius op */
+enum { LIO_GW_INSIDE = 0, LIO_GW_CROP = 1, LIO_GW_EMPTY = 2, LIO_GW_EDGE_MEAN = 3 };    /* SlidingWindowIterator::EdgeHandling, in its order */
+enum { LIO_GW_SUM = 0, LIO_GW_MEAN_OF_FINITES, LIO_GW_MIN_OF_FINITES, LIO_GW_MAX_OF_FINITES,
+       LIO_GW_NUMBER_OF_FINITES, LIO_GW_STDDEV, LIO_GW_WEIGHTED_SUM };                  /* window op */
+struct lio_grid_filter_info {
+    int32_t rows, cols;
+    int32_t window_size;          /* the window used, in cells (0: not a window filter)                          */
+    int32_t pad;
+    int64_t n_visited, n_written, n_changed;
+};
+typedef struct lio_grid_filter_info lio_grid_filter_info;
+/* MinInRadiusFilter (op LIO_GF_MIN) and MeanInRadiusFilter (LIO_GF_MEAN).  The circle is CircleIterator's around the cell's
+ * own centre: fp64 centres, member when dx dx + dy dy <= radius radius, the window of findSubmapParameters, SubmapIterator's
+ * order; a member counts when it is finite.  Mean: every cell; (float)(fp64 serial sum / count), written where the count is
+ * not 0 -- the arithmetic of LIO_TERRAIN_SMOOTH.  Min: where the centre is finite; the first finite member initialises, a
+ * later one replaces it only when it is smaller (of +0 and -0 the first seen stays).  radius = 0: the cell alone.
+ * out_layer == in_layer: LIO_ERR_ARG (a labelled deviation: the reference clears its own input there and returns NaN). */
+int  lio_grid_filter_radius(lio_grid *g, int32_t in_layer, int32_t out_layer, int32_t op, double radius, lio_grid_filter_info *info);
+/* SlidingWindowMathExpressionFilter with one of seven expressions over SlidingWindowIterator::getData().  window_size >= 1 is
+ * used as given (even: LIO_ERR_ARG, the reference throws); window_size == 0 derives it from window_length as setWindowLength
+ * does: (size_t)round(window_length / resolution), plus 1 when even.  The window matrix W is the block clipped to the map
+ * (INSIDE, CROP) or the full size x size matrix, pre-filled with NaN (EMPTY) or with the clipped block's meanOfFinites()
+ * (EDGE_MEAN).  Every reduction is serial, column-major over W, the first coefficient initialises (Eigen's default redux on a
+ * functor without a packet form):
+ *   SUM sumOfFinites(W); MEAN_OF_FINITES sumOfFinites / numberOfFinites in float; MIN_ / MAX_OF_FINITES the functors of
+ *   FunctorsPlugin.hpp as written; NUMBER_OF_FINITES counts x == x (an infinity counts), as a float;
+ *   STDDEV sqrt(sumOfFinites(square(W - meanOfFinites(W))) ./ numberOfFinites(W)) (with CROP: LIO_TERRAIN_EDGES);
+ *   WEIGHTED_SUM sumOfFinites(K .* W), weights = K, size x size floats, column-major, K(a, b) against W(a, b), each product
+ *   rounded to float.  weights must be NULL for every other op.  With CROP and a window above 1 the sizes disagree at the border
+ *   (EigenLab throws): LIO_ERR_ARG.
+ * CROP, EMPTY and EDGE_MEAN visit every cell.  INSIDE visits the cells whose whole window fits; with a size derived from the
+ * length it also reproduces the iterator's two setup() calls (the first with the filter's default size 3): a derived size of 1
+ * never visits column 0 and cell (0, 1), and a grid with fewer than 3 rows or columns is not visited at all.  The reference
+ * reads compute_empty_cells and never uses it: there is no such argument.  out_layer == in_layer is allowed and computes from
+ * the old values. */
+int  lio_grid_filter_window(lio_grid *g, int32_t in_layer, int32_t out_layer, int32_t op, int32_t edge_handling,
+                            int32_t window_size, double window_length, const float *weights, lio_grid_filter_info *info);
+/* CurvatureFilter.  L2 = (float)(resolution * resolution); per finite cell D = (float)(((double)(left + right) / 2.0 -
+ * (double)centre) / (double)L2) along the columns, E the same along the rows, the neighbour sum a float addition, a neighbour
+ * the map lacks replaced by the cell itself; a D or E that is not finite becomes 0; the value is (float)(-2.0 * (double)(D + E)).
+ * Cells that are not finite stay NaN.  out_layer == in_layer: LIO_ERR_ARG, as for the radius filters. */
+int  lio_grid_filter_curvature(lio_grid *g, int32_t in_layer, int32_t out_layer, lio_grid_filter_info *info);
+/* ThresholdFilter, in place on out_layer, which must exist and may be condition_layer: upper == 0 sets the cells where
+ * !((double)condition >= threshold), upper == 1 where !((double)condition <= threshold), to the bits of (float)set_to.  A NaN
+ * threshold or set_to is allowed, as there. */
+int  lio_grid_filter_threshold(lio_grid *g, int32_t condition_layer, int32_t out_layer, int32_t upper, double threshold,
+                               double set_to, lio_grid_filter_info *info);
+/* DuplicationFilter: out_layer becomes a copy of in_layer, device to device. */
+int  lio_grid_duplicate_layer(lio_grid *g, int32_t in_layer, int32_t out_layer);
+/* DeletionFilter: the listed layers leave the object (their memory stays with it).  LIO_ERR_ARG: n_layers outside 1 .. 16, an
+ * id outside 0 .. 15 or repeated, and (a labelled deviation: the reference logs it) a listed layer the object does not hold.
+ * An object left without a layer is as lio_grid_create left it. */
+int  lio_grid_delete_layers(lio_grid *g, const int32_t *layer_ids, int32_t n_layers);
+/* Measurement hook (tools/grid_filter_cost.py), as lio_grid_geom_debug_kernel_ms: the kernel of the calling thread's last call
+ * of the six, in milliseconds (0 where none was launched). */
+int  lio_grid_filter_debug_kernel_ms(int32_t enable, float *ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -502,6 +502,32 @@ public:
         if (rc != LIO_ERR_CAPACITY) check(rc, "lio_grid_to_grid_cells");
         return rc;
     }
+    // grid_map_filters on a layer the object holds; the result replaces out_layer.  MinInRadiusFilter / MeanInRadiusFilter
+    // (op LIO_GF_MIN / LIO_GF_MEAN):
+    void filterInRadius(int32_t in_layer, int32_t out_layer, int32_t op, double radius, lio_grid_filter_info* info = nullptr)
+    {
+        check(lio_grid_filter_radius(g_, in_layer, out_layer, op, radius, info), "lio_grid_filter_radius");
+    }
+    // SlidingWindowMathExpressionFilter: op LIO_GW_SUM .. LIO_GW_WEIGHTED_SUM, edge_handling LIO_GW_INSIDE .. LIO_GW_EDGE_MEAN;
+    // window_size 0: from window_length; weights (size x size, column-major) with LIO_GW_WEIGHTED_SUM only
+    void filterSlidingWindow(int32_t in_layer, int32_t out_layer, int32_t op, int32_t edge_handling, int32_t window_size, double window_length = 0.0,
+                             const float* weights = nullptr, lio_grid_filter_info* info = nullptr)
+    {
+        check(lio_grid_filter_window(g_, in_layer, out_layer, op, edge_handling, window_size, window_length, weights, info), "lio_grid_filter_window");
+    }
+    // CurvatureFilter
+    void filterCurvature(int32_t in_layer, int32_t out_layer, lio_grid_filter_info* info = nullptr)
+    {
+        check(lio_grid_filter_curvature(g_, in_layer, out_layer, info), "lio_grid_filter_curvature");
+    }
+    // ThresholdFilter, in place on out_layer: upper false is lower_threshold, true upper_threshold
+    void filterThreshold(int32_t condition_layer, int32_t out_layer, bool upper, double threshold, double set_to, lio_grid_filter_info* info = nullptr)
+    {
+        check(lio_grid_filter_threshold(g_, condition_layer, out_layer, upper ? 1 : 0, threshold, set_to, info), "lio_grid_filter_threshold");
+    }
+    // DuplicationFilter and DeletionFilter
+    void duplicateLayer(int32_t in_layer, int32_t out_layer) { check(lio_grid_duplicate_layer(g_, in_layer, out_layer), "lio_grid_duplicate_layer"); }
+    void deleteLayers(const int32_t* layer_ids, int32_t n_layers) { check(lio_grid_delete_layers(g_, layer_ids, n_layers), "lio_grid_delete_layers"); }
     void layer(int32_t k, float* out, size_t cap_floats) { check(lio_grid_get_layer(g_, k, out, cap_floats), "lio_grid_get_layer"); }
     lio_grid_desc info()
     {

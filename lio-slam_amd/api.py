@@ -318,6 +318,13 @@ GRID_FROM_IMAGE_INFO_DTYPE = np.dtype({"names": ["rows", "cols", "geometry_set",
 GRID_FROM_OCCUPANCY_INFO_DTYPE = np.dtype({"names": ["rows", "cols", "geometry_replaced", "pad", "length", "position", "n_unknown"],
                                            "formats": [np.int32, np.int32, np.int32, np.int32, (np.float64, 2), (np.float64, 2), np.int64],
                                            "offsets": [0, 4, 8, 12, 16, 32, 48], "itemsize": 56})
+# lio_grid_filter_info (tests/test_grid_filter_capi.py holds the layout to gcc's)
+GRID_FILTER_INFO_DTYPE = np.dtype({"names": ["rows", "cols", "window_size", "pad", "n_visited", "n_written", "n_changed"],
+                                   "formats": [np.int32, np.int32, np.int32, np.int32, np.int64, np.int64, np.int64], "offsets": [0, 4, 8, 12, 16, 24, 32],
+                                   "itemsize": 40})
+GF_MIN, GF_MEAN = 0, 1
+GW_INSIDE, GW_CROP, GW_EMPTY, GW_EDGE_MEAN = 0, 1, 2, 3
+GW_SUM, GW_MEAN_OF_FINITES, GW_MIN_OF_FINITES, GW_MAX_OF_FINITES, GW_NUMBER_OF_FINITES, GW_STDDEV, GW_WEIGHTED_SUM = range(7)
 IMAGE_8U, IMAGE_16U, IMAGE_32F = 0, 1, 2
 IMAGE_DTYPES = {IMAGE_8U: np.uint8, IMAGE_16U: np.uint16, IMAGE_32F: np.float32}
 REGION_LINE, REGION_CIRCLE, REGION_ELLIPSE, REGION_POLYGON = 0, 1, 2, 3
@@ -510,6 +517,13 @@ CAPI = {
     "lio_grid_to_grid_cells": [vp, i32, f32, f32, vp, sz, psz],
     "lio_sdf_to_point_cloud": [vp, i32, f32, f32, vp, sz, psz],
     "lio_grid_convert_debug_stage_ms": [i32, i32, pf],
+    "lio_grid_filter_radius": [vp, i32, i32, i32, f64, vp],
+    "lio_grid_filter_window": [vp, i32, i32, i32, i32, i32, f64, pf, vp],
+    "lio_grid_filter_curvature": [vp, i32, i32, vp],
+    "lio_grid_filter_threshold": [vp, i32, i32, i32, f64, f64, vp],
+    "lio_grid_duplicate_layer": [vp, i32, i32],
+    "lio_grid_delete_layers": [vp, pi, i32],
+    "lio_grid_filter_debug_kernel_ms": [i32, pf],
 }
 CAPI = {name: sig if isinstance(sig, tuple) else (C.c_int, sig) for name, sig in CAPI.items()}     # -> (restype, argtypes), all of them
 EXPORTS = list(CAPI)
@@ -1740,6 +1754,46 @@ class Grid(_Owner):
         def call(out, n):
             return self.lib.lio_grid_to_grid_cells(self.h, int(layer), float(lower), float(upper), out.ctypes.data if out.size else None, len(out), C.byref(n))
         return self._compacted("lio_grid_to_grid_cells", call, 2, np.float64, cap_cells)
+
+    def filter_radius(self, in_layer, out_layer, op, radius):
+        """grid_map_filters' MinInRadiusFilter (op GF_MIN) or MeanInRadiusFilter (GF_MEAN) of layer `in_layer` into `out_layer`,
+        which it replaces.  -> a GRID_FILTER_INFO_DTYPE record"""
+        info = np.zeros(1, GRID_FILTER_INFO_DTYPE)
+        _check(self.lib.lio_grid_filter_radius(self.h, int(in_layer), int(out_layer), int(op), float(radius), info.ctypes.data), "lio_grid_filter_radius")
+        return info[0]
+
+    def filter_window(self, in_layer, out_layer, op, edge_handling, window_size=0, window_length=0.0, weights=None):
+        """SlidingWindowMathExpressionFilter: op GW_SUM .. GW_WEIGHTED_SUM over the window of edge_handling GW_INSIDE ..
+        GW_EDGE_MEAN.  window_size 0: derived from window_length.  weights: [size, size] (K[a, b] against W[a, b]), with
+        GW_WEIGHTED_SUM only.  out_layer may be in_layer.  -> a GRID_FILTER_INFO_DTYPE record"""
+        k = None if weights is None else np.ascontiguousarray(np.asarray(weights, np.float32).ravel(order="F"))
+        info = np.zeros(1, GRID_FILTER_INFO_DTYPE)
+        _check(self.lib.lio_grid_filter_window(self.h, int(in_layer), int(out_layer), int(op), int(edge_handling), int(window_size), float(window_length),
+                                               None if k is None else _f32p(k), info.ctypes.data), "lio_grid_filter_window")
+        return info[0]
+
+    def filter_curvature(self, in_layer, out_layer):
+        """CurvatureFilter of layer `in_layer` into `out_layer`.  -> a GRID_FILTER_INFO_DTYPE record"""
+        info = np.zeros(1, GRID_FILTER_INFO_DTYPE)
+        _check(self.lib.lio_grid_filter_curvature(self.h, int(in_layer), int(out_layer), info.ctypes.data), "lio_grid_filter_curvature")
+        return info[0]
+
+    def filter_threshold(self, condition_layer, out_layer, upper, threshold, set_to):
+        """ThresholdFilter, in place on `out_layer`: upper False sets where !(condition >= threshold), True where
+        !(condition <= threshold).  -> a GRID_FILTER_INFO_DTYPE record (n_changed: the cells set)"""
+        info = np.zeros(1, GRID_FILTER_INFO_DTYPE)
+        _check(self.lib.lio_grid_filter_threshold(self.h, int(condition_layer), int(out_layer), int(bool(upper)), float(threshold), float(set_to),
+                                                  info.ctypes.data), "lio_grid_filter_threshold")
+        return info[0]
+
+    def duplicate_layer(self, in_layer, out_layer):
+        """DuplicationFilter: `out_layer` becomes a copy of `in_layer`, device to device"""
+        _check(self.lib.lio_grid_duplicate_layer(self.h, int(in_layer), int(out_layer)), "lio_grid_duplicate_layer")
+
+    def delete_layers(self, layer_ids):
+        """DeletionFilter: the listed layers leave the object"""
+        ids = np.ascontiguousarray(layer_ids, np.int32).reshape(-1)
+        _check(self.lib.lio_grid_delete_layers(self.h, ids.ctypes.data_as(C.POINTER(C.c_int32)) if len(ids) else None, len(ids)), "lio_grid_delete_layers")
 
     def memory(self):
         """-> bytes the object holds on the device"""
