@@ -16,7 +16,6 @@
 #define LIO_GC_PITCH (LIO_GC_TILE + 1)                      // words of a tile line in LDS: the odd pitch keeps a column walk on 32 banks
 #define LIO_GC_EMPTY 0xffffffffu                            // the tile word of a cell that leaves its pixel zero (no pixel value has it)
 
-LIO_HD bool lio_gc_finite(float v) { return fabsf(v) <= FLT_MAX; }
 LIO_HD int lio_gc_elem_bytes(int depth) { return depth == LIO_IMAGE_8U ? 1 : (depth == LIO_IMAGE_16U ? 2 : 4); }
 // imageMax / maxImageValue as a float (CV:87-95, :206-214)
 LIO_HD float lio_gc_image_max(int depth) { return depth == LIO_IMAGE_8U ? 255.0f : (depth == LIO_IMAGE_16U ? 65535.0f : 1.0f); }
@@ -33,7 +32,7 @@ enum { LIO_GC_IN_RANGE = 0, LIO_GC_CLAMPED_LOW, LIO_GC_CLAMPED_HIGH, LIO_GC_NONF
 LIO_HD unsigned lio_gc_pixel(float x, float lo, float hi, int depth, int* cls)
 {
     const float v = lio_gc_clamp(x, lo, hi);
-    if (!lio_gc_finite(v)) { *cls = LIO_GC_NONFINITE; return LIO_GC_EMPTY; }
+    if (!lio_gm_finite(v)) { *cls = LIO_GC_NONFINITE; return LIO_GC_EMPTY; }
     *cls = x < lo ? LIO_GC_CLAMPED_LOW : (x > hi ? LIO_GC_CLAMPED_HIGH : LIO_GC_IN_RANGE);
     const float s = ((v - lo) / (hi - lo)) * lio_gc_image_max(depth);
     if (depth == LIO_IMAGE_32F) return __builtin_bit_cast(unsigned, s);
@@ -145,7 +144,7 @@ LIO_HD unsigned lio_gc_word_from_pixel(const LioGcIngest& I, const unsigned char
 LIO_HD unsigned lio_gc_occupancy_word(int8_t v) { return v != -1 ? __builtin_bit_cast(unsigned, (float)v) : LIO_QNAN_BITS; }
 
 // toGridCells' test (RC:377-379)
-LIO_HD bool lio_gc_cell_kept(float v, float lower, float upper) { return lio_gc_finite(v) && v >= lower && v <= upper; }
+LIO_HD bool lio_gc_cell_kept(float v, float lower, float upper) { return lio_gm_finite(v) && v >= lower && v <= upper; }
 
 // toPointCloud's test (RC:184-195): L::word(k, i) is cell i of table entry k
 struct LioGcCloud {

@@ -51,7 +51,7 @@ __global__ __launch_bounds__(256) void k_gc_extremes(const float* __restrict__ l
     float mn[3] = { INFINITY, INFINITY, INFINITY }, mx[3] = { -INFINITY, -INFINITY, -INFINITY };
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         const float v = layer[i];
-        if (lio_gc_finite(v)) { mn[0] = fminf(mn[0], v); mx[0] = fmaxf(mx[0], v); }
+        if (lio_gm_finite(v)) { mn[0] = fminf(mn[0], v); mx[0] = fmaxf(mx[0], v); }
     }
     float lo = 0.0f, hi = 0.0f;
     lio_wg_box<4>(mn, mx, s_box, lo, hi);
@@ -295,7 +295,7 @@ try {
     if (!automatic) {
         if (lower != lower || upper != upper) return lio_fail(LIO_ERR_ARG, "lower and upper are both NaN (the layer's extremes) or both numbers");
         if (!(upper > lower)) return lio_fail(LIO_ERR_ARG, "upper must be greater than lower");
-        if (!lio_gc_finite(upper - lower)) return lio_fail(LIO_ERR_ARG, "upper - lower must be finite");
+        if (!lio_gm_finite(upper - lower)) return lio_fail(LIO_ERR_ARG, "upper - lower must be finite");
     }
     if (!g || !image) return lio_fail(LIO_ERR_ARG, "null argument");
     if (!lio_grid_has_layer(g, layer)) return lio_fail(LIO_ERR_ARG, "the object holds no such layer");
@@ -325,7 +325,7 @@ try {
         if (hs[0] == LIO_ORD_NO_MIN && hs[1] == LIO_ORD_NO_MAX) return lio_fail(LIO_ERR_ARG, "the layer has no finite cell: no automatic bounds");
         lower = lio_ord2f(hs[0]); upper = lio_ord2f(hs[1]);
         if (!(upper > lower)) return lio_fail(LIO_ERR_ARG, "the layer's finite extremes are equal: no automatic bounds");
-        if (!lio_gc_finite(upper - lower)) return lio_fail(LIO_ERR_ARG, "upper - lower must be finite");
+        if (!lio_gm_finite(upper - lower)) return lio_fail(LIO_ERR_ARG, "upper - lower must be finite");
     }
     clk.mark(s);
     if (!t_gc_tiled) {

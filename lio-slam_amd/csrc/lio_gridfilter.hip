@@ -1,8 +1,8 @@
 // lio_gridfilter.hip -- a new layer derived from one the resident object holds: grid_map_filters' MinInRadiusFilter,
 // MeanInRadiusFilter, SlidingWindowMathExpressionFilter (four edge modes, seven expressions), CurvatureFilter, ThresholdFilter,
 // DuplicationFilter and DeletionFilter.  The arithmetic is lio_gridfilter.h's; this file is the kernels and the entry points.
-//   k_gf_radius<op>         one lane per cell, the 32 x 8 tile of the terrain kernels with a halo of
-//                           floor(radius / resolution + 0.5) + 1 cells staged into LDS by terr_stage: a value is read by
+//   k_gf_radius<op>         one lane per cell, the 32 x 8 tile of lio_gridtile.h with a halo of
+//                           floor(radius / resolution + 0.5) + 1 cells staged into LDS by lio_tile_stage: a value is read by
 //                           every circle that holds it, once from memory.
 //   k_gf_window<op, edge>   the same tile with the half-window as halo.  EDGE_MEAN walks the clipped block first for its
 //                           fill, STDDEV walks the window twice; both passes read LDS.  The weights are a device buffer
@@ -29,7 +29,6 @@
 namespace {
 
 enum { GF_CNT_VISITED = 0, GF_CNT_WRITTEN, GF_CNT_CHANGED, GF_N_CNT };
-#define GF_LANES (TERR_ROWS * TERR_COLS)
 
 struct GfLayer {                   // a layer as it lies in memory: column-major, rows the contiguous axis
     const float* p;
@@ -47,12 +46,12 @@ __device__ __forceinline__ void gf_finish(const LioGfCell& o, bool in_grid, floa
 }
 
 template <int OP>
-__global__ __launch_bounds__(GF_LANES) void k_gf_radius(LioGfRadius P, const float* __restrict__ in, float* __restrict__ out,
+__global__ __launch_bounds__(LIO_TILE_LANES) void k_gf_radius(LioGfRadius P, const float* __restrict__ in, float* __restrict__ out,
                                                         unsigned long long* __restrict__ counters)
 {
     extern __shared__ __attribute__((aligned(16))) float s_tile[];
     int r, c;
-    const TerrTile T = terr_stage(in, P.G.rows, P.G.cols, P.halo, s_tile, r, c);
+    const LioTile T = lio_tile_stage(in, P.G.rows, P.G.cols, P.halo, s_tile, r, c);
     const bool in_grid = r < P.G.rows && c < P.G.cols;
     LioGfCell o;
     o.value = LIO_QNAN;
@@ -62,12 +61,12 @@ __global__ __launch_bounds__(GF_LANES) void k_gf_radius(LioGfRadius P, const flo
 }
 
 template <int OP, int EDGE>
-__global__ __launch_bounds__(GF_LANES) void k_gf_window(LioGfWindow P, const float* __restrict__ in, const float* __restrict__ weights,
+__global__ __launch_bounds__(LIO_TILE_LANES) void k_gf_window(LioGfWindow P, const float* __restrict__ in, const float* __restrict__ weights,
                                                         float* __restrict__ out, unsigned long long* __restrict__ counters)
 {
     extern __shared__ __attribute__((aligned(16))) float s_tile[];
     int r, c;
-    const TerrTile T = terr_stage(in, P.rows, P.cols, P.margin, s_tile, r, c);
+    const LioTile T = lio_tile_stage(in, P.rows, P.cols, P.margin, s_tile, r, c);
     const bool in_grid = r < P.rows && c < P.cols;
     LioGfCell o;
     o.value = LIO_QNAN;
@@ -169,9 +168,6 @@ void gf_fill_info(lio_grid_filter_info* info, const lio_grid* g, int window_size
     info->n_changed = (int64_t)hc[GF_CNT_CHANGED];
 }
 
-unsigned gf_tiles(int rows, int cols) { return (unsigned)((rows + TERR_ROWS - 1) / TERR_ROWS) * (unsigned)((cols + TERR_COLS - 1) / TERR_COLS); }
-size_t gf_lds(int halo) { return sizeof(float) * (size_t)(TERR_ROWS + 2 * halo) * (size_t)(TERR_COLS + 2 * halo); }
-
 typedef void (*GfWindowKernel)(LioGfWindow, const float*, const float*, float*, unsigned long long*);
 
 template <int OP>
@@ -222,9 +218,9 @@ try {
     hipStream_t s = nullptr;
     unsigned long long hc[GF_N_CNT];
     rc = gf_run(s, hc, [&](unsigned long long* d_cnt) {
-        const dim3 grid(gf_tiles(P.G.rows, P.G.cols)), block(GF_LANES);
-        if (op == LIO_GF_MIN) hipLaunchKernelGGL(k_gf_radius<LIO_GF_MIN>, grid, block, gf_lds(P.halo), s, P, d_in, out.d, d_cnt);
-        else hipLaunchKernelGGL(k_gf_radius<LIO_GF_MEAN>, grid, block, gf_lds(P.halo), s, P, d_in, out.d, d_cnt);
+        const dim3 grid(lio_tile_count(P.G.rows, P.G.cols)), block(LIO_TILE_LANES);
+        if (op == LIO_GF_MIN) hipLaunchKernelGGL(k_gf_radius<LIO_GF_MIN>, grid, block, lio_tile_lds_bytes(P.halo, sizeof(float)), s, P, d_in, out.d, d_cnt);
+        else hipLaunchKernelGGL(k_gf_radius<LIO_GF_MEAN>, grid, block, lio_tile_lds_bytes(P.halo, sizeof(float)), s, P, d_in, out.d, d_cnt);
     });
     if (rc != LIO_OK) return rc;
     undo.commit();
@@ -266,7 +262,7 @@ try {
     const float* d_in = g->d_layer[in_layer].p;
     unsigned long long hc[GF_N_CNT];
     rc = gf_run(s, hc, [&](unsigned long long* d_cnt) {
-        hipLaunchKernelGGL(gf_window_kernel(op, edge_handling), dim3(gf_tiles(P.rows, P.cols)), dim3(GF_LANES), gf_lds(P.margin), s, P, d_in,
+        hipLaunchKernelGGL(gf_window_kernel(op, edge_handling), dim3(lio_tile_count(P.rows, P.cols)), dim3(LIO_TILE_LANES), lio_tile_lds_bytes(P.margin, sizeof(float)), s, P, d_in,
                            (const float*)d_weights.as<float>(), out.d, d_cnt);
     });
     if (rc != LIO_OK) return rc;

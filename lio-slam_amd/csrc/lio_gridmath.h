@@ -1,7 +1,8 @@
 // lio_gridmath.h -- the library's GridMapMath: grid_map's geometry (GM = grid_map_core/src/GridMap.cpp, GMM =
 // GridMapMath.cpp) as every planning stage reads it.  The members setGeometry leaves, the one function that derives them,
 // getPositionFromIndex, getIndexFromPosition with checkIfPositionWithinMap, boundPositionToRange, and the rule by which an
-// entry point accepts a caller's geometry: each exists here and nowhere else.  startIndex is always 0 (the library's grids are
+// entry point accepts a caller's geometry, with the two questions every stage asks of a cell (is it finite, which cells of a
+// window lie in the grid): each exists here and nowhere else.  startIndex is always 0 (the library's grids are
 // never circular buffers).  Everything is fp64 in the order the reference writes it and relies on -ffp-contract=off.  The two
 // labelled deviations from the reference are lio_gm_bound_index's clamp and verdict 1 of lio_gm_lookup (DESIGN.md section 4,
 // "The grid geometry").
@@ -15,6 +16,16 @@
 #define LIO_HD __host__ __device__ __forceinline__
 #define LIO_QNAN_BITS 0x7fc00000u                            // NAN as the reference's layers hold it; __builtin_nanf("") is this word
 #define LIO_QNAN __builtin_bit_cast(float, LIO_QNAN_BITS)
+
+// std::isfinite of a cell, as isValid and every filter ask it
+LIO_HD bool lio_gm_finite(float v) { return fabsf(v) <= FLT_MAX; }
+
+// [i - R, i + R] with both ends brought into [0, n - 1]: boundIndexToRange on the two corners of a window of cells
+LIO_HD void lio_gm_clip(int i, int R, int n, int& lo, int& hi)
+{
+    lo = i - R < 0 ? 0 : i - R;
+    hi = i + R > n - 1 ? n - 1 : i + R;
+}
 
 // grid_map's geometry as the iterators read it; base = position + (0.5 length - 0.5 resolution) (getVectorToFirstCell).
 // rows = size(0) along x, cols = size(1) along y.  A kernel argument by value: the layout is part of the kernels' code.

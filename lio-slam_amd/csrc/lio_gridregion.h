@@ -17,7 +17,6 @@
 #include <stdint.h>
 #include "../../include/liogpu.h"
 #include "lio_gridmath.h"
-#include "lio_terrain.h"                                    // lio_terr_finite
 #include "lio_wg.h"
 
 #define LIO_RG_LANES 64            // the partial sums of a region: fixed, whatever the launch shape
@@ -215,7 +214,7 @@ LIO_HD void lio_rg_acc_clear(LioRgAcc* a)
 
 LIO_HD void lio_rg_acc_add(LioRgAcc* a, float v, float threshold)
 {
-    if (!lio_terr_finite(v)) return;
+    if (!lio_gm_finite(v)) return;
     a->sum = a->sum + (double)v;
     const unsigned o = lio_f2ord(v);
     a->mn = o < a->mn ? o : a->mn;

@@ -55,7 +55,7 @@ __global__ __launch_bounds__(256) void k_gt_scatter(LioGridGeom S, LioGridGeom D
     unsigned finite = 0u, outside = 0u;
     if (lin < n_cells) {
         const float h = height[lin];
-        if (fabsf(h) <= FLT_MAX) {                           // std::isfinite (getPosition3, GM:260-270)
+        if (lio_gm_finite(h)) {                              // std::isfinite (getPosition3, GM:260-270)
             GtKeySink sink = { keys };
             finite = 1u;
             outside = (unsigned)lio_gt_cell(S, D, T, sample_length, n_samples, lin, h, sink);

@@ -9,10 +9,10 @@
 #include <math.h>
 #include "../../include/liogpu.h"
 #include "lio_gridmath.h"
-#include "lio_terrain.h"                                    // LIO_TERR_MAX_CELLS and the tile of the kernels
+#include "lio_gridtile.h"                                   // LIO_TILE_MAX_REACH and the tile of the kernels
 #include "lio_wg.h"
 
-#define LIO_MF_MAX_ITERATIONS 15   // num_erode_dilation_iterations: the mask's halo 2 + max(N, 1) + N stays within LIO_TERR_MAX_CELLS
+#define LIO_MF_MAX_ITERATIONS 15   // num_erode_dilation_iterations: the mask's halo 2 + max(N, 1) + N stays within LIO_TILE_MAX_REACH
 
 struct LioMfParams {
     int rows, cols;
@@ -29,18 +29,9 @@ struct LioMfCell {
     bool nan_in, masked, filled, filtered, nan_out;
 };
 
-LIO_HD bool lio_mf_finite(float v) { return fabsf(v) <= FLT_MAX; }          // std::isfinite
-
-// [i - R, i + R] with both ends brought into [0, n - 1] (boundIndexToRange; for the morphology: cells outside the image take
-// no part, morphologyDefaultBorderValue)
-LIO_HD void lio_mf_clip(int i, int R, int n, int& lo, int& hi)
-{
-    lo = i - R < 0 ? 0 : i - R;
-    hi = i + R > n - 1 ? n - 1 : i + R;
-}
-
 // One pass of a box erosion (and) or dilation (or) along a line.  L::at(k): mask cell k of the line, 0 or 1, for
-// lo <= k <= hi; the caller has clipped [lo, hi] to the grid, so an empty range yields the pass's identity.  k iterations of
+// lo <= k <= hi; the caller has clipped [lo, hi] to the grid (lio_gm_clip: cells outside the image take no part,
+// morphologyDefaultBorderValue), so an empty range yields the pass's identity.  k iterations of
 // the 3 x 3 element under the default border are one (2k + 1)^2 box clipped to the grid, and a clipped box is the pass
 // along the rows followed by the pass along the columns (tests/test_median_fill_cpu.py proves both on random masks).
 template <class L>
@@ -70,11 +61,11 @@ template <class M>
 LIO_HD float lio_mf_median(const M& in, int r, int c, int R, int rows, int cols)
 {
     int i0, i1, j0, j1;
-    lio_mf_clip(r, R, rows, i0, i1);
-    lio_mf_clip(c, R, cols, j0, j1);
+    lio_gm_clip(r, R, rows, i0, i1);
+    lio_gm_clip(c, R, cols, j0, j1);
     unsigned n = 0;
     for (int j = j0; j <= j1; ++j)
-        for (int i = i0; i <= i1; ++i) n += lio_mf_finite(in.at(i, j)) ? 1u : 0u;
+        for (int i = i0; i <= i1; ++i) n += lio_gm_finite(in.at(i, j)) ? 1u : 0u;
     if (n == 0) return __builtin_bit_cast(float, 0x7fc00000u);
     unsigned k = n / 2, key = 0;
     for (int bit = 31; bit >= 0; --bit) {
@@ -83,7 +74,7 @@ LIO_HD float lio_mf_median(const M& in, int r, int c, int R, int rows, int cols)
         for (int j = j0; j <= j1; ++j)
             for (int i = i0; i <= i1; ++i) {
                 const float v = in.at(i, j);
-                zeros += (lio_mf_finite(v) && (lio_f2ord(v) & fixed) == key) ? 1u : 0u;
+                zeros += (lio_gm_finite(v) && (lio_f2ord(v) & fixed) == key) ? 1u : 0u;
             }
         if (k >= zeros) { k -= zeros; key |= 1u << bit; }
     }
@@ -95,7 +86,7 @@ template <class M>
 LIO_HD void lio_mf_cell(const LioMfParams& P, const M& in, float mask, int r, int c, LioMfCell* o)
 {
     const float v = in.at(r, c);
-    const bool fin = lio_mf_finite(v);
+    const bool fin = lio_gm_finite(v);
     o->masked = mask != 0.0f;
     o->nan_in = !fin;
     o->filtered = false;
@@ -106,7 +97,7 @@ LIO_HD void lio_mf_cell(const LioMfParams& P, const M& in, float mask, int r, in
         o->out = lio_mf_median(in, r, c, P.r_existing, P.rows, P.cols);
         o->filtered = true;
     }
-    o->nan_out = !lio_mf_finite(o->out);
+    o->nan_out = !lio_gm_finite(o->out);
     o->filled = !fin && !o->nan_out;
 }
 

@@ -5,7 +5,7 @@
 //               outside the image never takes part (morphologyDefaultBorderValue) and nothing has to be reset between an
 //               erosion and a dilation.  Every pass is computed for the whole staged region; what a pass cannot know (its
 //               window leaves the region) lies in the rim the next passes no longer read.
-//   k_mf_fill   update(): one lane per cell on the 32 x 8 tile of lio_terrain.h staged with the halo of the larger radius.
+//   k_mf_fill   update(): one lane per cell on the 32 x 8 tile of lio_gridtile.h staged with the halo of the larger radius.
 //               A lane that fills selects the median by counting over the LDS window (lio_mf_median): 33 (2R + 1)^2 reads,
 //               none for a lane that copies.  The five counts by ballot, one atomic per wave and counter.
 // The per-cell arithmetic is lio_medianfill.h's.  DESIGN.md section 4j: conventions, resources, what was measured.
@@ -19,7 +19,6 @@
 #include "lio_medianfill.h"
 #include "lio_cloud.h"
 #include "lio_pool.h"
-#include "lio_terrain.h"
 
 struct MfLine {                    // a line of a byte plane in LDS: entry k at p[k * stride]
     const unsigned char* p;
@@ -28,37 +27,38 @@ struct MfLine {                    // a line of a byte plane in LDS: entry k at 
 };
 
 // fill_mask, cleaned (may be NULL): rows x cols floats, 0.0f / 1.0f as cv2eigen leaves a Mat_<bool>
-__global__ __launch_bounds__(TERR_ROWS * TERR_COLS) void k_mf_mask(LioMfParams P, const float* __restrict__ in, float* __restrict__ fill_mask,
+__global__ __launch_bounds__(LIO_TILE_LANES) void k_mf_mask(LioMfParams P, const float* __restrict__ in, float* __restrict__ fill_mask,
                                                                     float* __restrict__ cleaned)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_planes[];
-    const int h = P.halo_mask, pitch = TERR_ROWS + 2 * h, width = TERR_COLS + 2 * h, n = pitch * width;
-    const int tiles_r = (P.rows + TERR_ROWS - 1) / TERR_ROWS;
-    const int r0 = ((int)blockIdx.x % tiles_r) * TERR_ROWS - h, c0 = ((int)blockIdx.x / tiles_r) * TERR_COLS - h;   // the region's first cell
+    const int h = P.halo_mask, pitch = LIO_TILE_ROWS + 2 * h, width = LIO_TILE_COLS + 2 * h, n = pitch * width;
+    int tr0, tc0;
+    lio_tile_origin(P.rows, tr0, tc0);
+    const int r0 = tr0 - h, c0 = tc0 - h;                  // the region's first cell
     unsigned char* a = s_planes;
     unsigned char* b = s_planes + n;
-    for (int k = (int)threadIdx.x; k < n; k += TERR_ROWS * TERR_COLS) {
+    for (int k = (int)threadIdx.x; k < n; k += LIO_TILE_LANES) {
         const int i = r0 + k % pitch, j = c0 + k / pitch;
-        a[k] = (i >= 0 && i < P.rows && j >= 0 && j < P.cols && lio_mf_finite(in[(size_t)i + (size_t)j * (size_t)P.rows])) ? 1 : 0;
+        a[k] = (i >= 0 && i < P.rows && j >= 0 && j < P.cols && lio_gm_finite(in[(size_t)i + (size_t)j * (size_t)P.rows])) ? 1 : 0;
     }
     __syncthreads();
     // the part of the region that lies in the grid, in the region's own indices
     const int i_min = r0 < 0 ? -r0 : 0, i_max = (P.rows - 1 - r0 < pitch - 1) ? P.rows - 1 - r0 : pitch - 1;
     const int j_min = c0 < 0 ? -c0 : 0, j_max = (P.cols - 1 - c0 < width - 1) ? P.cols - 1 - c0 : width - 1;
-    const int ti = h + ((int)threadIdx.x % TERR_ROWS), tj = h + ((int)threadIdx.x / TERR_ROWS);      // this lane's cell
+    const int ti = h + ((int)threadIdx.x % LIO_TILE_ROWS), tj = h + ((int)threadIdx.x / LIO_TILE_ROWS);      // this lane's cell
     const bool in_grid = r0 + ti < P.rows && c0 + tj < P.cols;
     const size_t at = (size_t)(r0 + ti) + (size_t)(c0 + tj) * (size_t)P.rows;
     for (int op = 0; op < LIO_MF_N_OPS; ++op) {
         const int R = lio_mf_op_radius(P, op);
         const bool erode = lio_mf_op_erodes(op);
         if (R > 0) {                                       // (N = 0: no erosion at all)
-            for (int k = (int)threadIdx.x; k < n; k += TERR_ROWS * TERR_COLS) {        // along the rows: a -> b
+            for (int k = (int)threadIdx.x; k < n; k += LIO_TILE_LANES) {        // along the rows: a -> b
                 const int i = k % pitch, j = k / pitch;
                 const MfLine line = { a + j * pitch, 1 };
                 b[k] = (unsigned char)lio_mf_line(line, i - R < i_min ? i_min : i - R, i + R > i_max ? i_max : i + R, erode);
             }
             __syncthreads();
-            for (int k = (int)threadIdx.x; k < n; k += TERR_ROWS * TERR_COLS) {        // along the columns: b -> a
+            for (int k = (int)threadIdx.x; k < n; k += LIO_TILE_LANES) {        // along the columns: b -> a
                 const int i = k % pitch, j = k / pitch;
                 const MfLine line = { b + i, pitch };
                 a[k] = (unsigned char)lio_mf_line(line, j - R < j_min ? j_min : j - R, j + R > j_max ? j_max : j + R, erode);
@@ -71,12 +71,12 @@ __global__ __launch_bounds__(TERR_ROWS * TERR_COLS) void k_mf_mask(LioMfParams P
 }
 
 // counters[0..4] += non-finite input cells, non-zero mask cells, cells filled, finite cells filtered, non-finite output cells
-__global__ __launch_bounds__(TERR_ROWS * TERR_COLS) void k_mf_fill(LioMfParams P, const float* __restrict__ in, const float* __restrict__ mask,
+__global__ __launch_bounds__(LIO_TILE_LANES) void k_mf_fill(LioMfParams P, const float* __restrict__ in, const float* __restrict__ mask,
                                                                     float* __restrict__ out, int* __restrict__ counters)
 {
     extern __shared__ __attribute__((aligned(16))) float s_tile[];
     int r, c;
-    const TerrTile T = terr_stage(in, P.rows, P.cols, P.halo_fill, s_tile, r, c);
+    const LioTile T = lio_tile_stage(in, P.rows, P.cols, P.halo_fill, s_tile, r, c);
     LioMfCell o;
     o.nan_in = o.masked = o.filled = o.filtered = o.nan_out = false;
     if (r < P.rows && c < P.cols) {
@@ -115,7 +115,7 @@ int lio_median_fill_check(const lio_median_fill_config* c, double resolution, Li
     for (int k = 0; k < 2; ++k) {
         if (!std::isfinite(radii[k]) || radii[k] < 0.0) return lio_fail(LIO_ERR_ARG, "radii must be finite and not negative");
         const double q = radii[k] / resolution;            // static_cast<size_t>(radius / resolution): truncated
-        if (!(q < (double)(LIO_TERR_MAX_CELLS + 1))) return lio_fail(LIO_ERR_ARG, "a radius reaches further than 32 cells");
+        if (!(q < (double)(LIO_TILE_MAX_REACH + 1))) return lio_fail(LIO_ERR_ARG, "a radius reaches further than 32 cells");
         cells[k] = (int)q;
     }
     if (c->filter_existing_values != 0 && c->filter_existing_values != 1) return lio_fail(LIO_ERR_ARG, "filter_existing_values is 0 or 1");
@@ -145,17 +145,15 @@ int lio_median_fill_device(const float* d_in, const LioMfParams& P, const float*
     HIPCHK(mask.alloc(sizeof(float) * n_cells));
     HIPCHK(counters.alloc(5 * sizeof(int)));
     HIPCHK(hipMemsetAsync(counters.p, 0, 5 * sizeof(int), s));
-    const unsigned tiles = (unsigned)((P.rows + TERR_ROWS - 1) / TERR_ROWS) * (unsigned)((P.cols + TERR_COLS - 1) / TERR_COLS);
+    const unsigned tiles = lio_tile_count(P.rows, P.cols);
     if (mask_in) {                                         // :119-125: the mask of a previous run, as it is
         HIPCHK(hipMemcpyAsync(mask.p, mask_in, sizeof(float) * n_cells, hipMemcpyHostToDevice, s));
     } else {
         if (cleaned_mask) HIPCHK(cleaned.alloc(sizeof(float) * n_cells));
-        const size_t lds = 2 * (size_t)(TERR_ROWS + 2 * P.halo_mask) * (size_t)(TERR_COLS + 2 * P.halo_mask);
-        hipLaunchKernelGGL(k_mf_mask, dim3(tiles), dim3(TERR_ROWS * TERR_COLS), lds, s, P, d_in, mask.as<float>(),
+        hipLaunchKernelGGL(k_mf_mask, dim3(tiles), dim3(LIO_TILE_LANES), lio_tile_lds_bytes(P.halo_mask, 2), s, P, d_in, mask.as<float>(),    // (two byte planes)
                            cleaned_mask ? cleaned.as<float>() : nullptr);
     }
-    const size_t lds_fill = sizeof(float) * (size_t)(TERR_ROWS + 2 * P.halo_fill) * (size_t)(TERR_COLS + 2 * P.halo_fill);
-    hipLaunchKernelGGL(k_mf_fill, dim3(tiles), dim3(TERR_ROWS * TERR_COLS), lds_fill, s, P, d_in, (const float*)mask.p, d_filled, counters.as<int>());
+    hipLaunchKernelGGL(k_mf_fill, dim3(tiles), dim3(LIO_TILE_LANES), lio_tile_lds_bytes(P.halo_fill, sizeof(float)), s, P, d_in, (const float*)mask.p, d_filled, counters.as<int>());
     if (filled) HIPCHK(hipMemcpyAsync(filled, d_filled, sizeof(float) * n_cells, hipMemcpyDeviceToHost, s));
     if (fill_mask) HIPCHK(hipMemcpyAsync(fill_mask, mask.p, sizeof(float) * n_cells, hipMemcpyDeviceToHost, s));
     if (cleaned_mask && !mask_in) HIPCHK(hipMemcpyAsync(cleaned_mask, cleaned.p, sizeof(float) * n_cells, hipMemcpyDeviceToHost, s));

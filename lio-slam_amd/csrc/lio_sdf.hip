@@ -52,7 +52,7 @@ struct SdfElevLine {               // a column of the elevation layer as the off
     __device__ __forceinline__ float at(int q) const
     {
         float e = col[q];
-        if (!(fabsf(e) <= FLT_MAX)) e = fill;                      // nan_policy 1 (policy 0 never gets here with such a cell)
+        if (!lio_gm_finite(e)) e = fill;                           // nan_policy 1 (policy 0 never gets here with such a cell)
         return lio_sdf_init(e, h, inv_res, cls);
     }
 };
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(256) void k_sdf_stats(const float* __restrict__ e, 
     int bad = 0;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
         const float v = e[i];
-        if (fabsf(v) <= FLT_MAX) { mn = fminf(mn, v); mx = fmaxf(mx, v); }
+        if (lio_gm_finite(v)) { mn = fminf(mn, v); mx = fmaxf(mx, v); }
         else ++bad;
     }
 #pragma unroll

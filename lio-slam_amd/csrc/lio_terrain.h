@@ -1,15 +1,16 @@
 // lio_terrain.h -- the terrain layers behind the planning height map (lio_terrain.hip): what the entry points need, and the
 // per-cell arithmetic of the chain as __host__ __device__ functions over a grid accessor, so that the kernels (an LDS tile)
-// and a host program (the grid itself) run the same text.  DESIGN.md section 4g lists the conventions (parity unpinned).
-// Everything here relies on -ffp-contract=off.
+// and a host program (the grid itself) run the same text.  A client of lio_gridfilter.h: smooth is its MEAN in a radius,
+// edges its STDDEV over a cropped window, the area normals read its circle window; the eigen solver, the raster stencil and
+// the float expressions are this header's own.  DESIGN.md section 4g lists the conventions (parity unpinned).  Everything here
+// relies on -ffp-contract=off.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <math.h>
 #include "../../include/liogpu.h"
 #include "lio_gridmath.h"
-
-#define LIO_TERR_MAX_CELLS 32      // the largest radius and half-window, in cells: bounds the halo of the LDS tile
+#include "lio_gridfilter.h"
 
 struct LioTerrParams {
     LioGridGeom G;
@@ -25,16 +26,6 @@ struct LioTerrCell {
     float smooth, nx, ny, nz, slope, rough, trav;
     bool valid, normal, few, degenerate;
 };
-
-// CircleIterator::findSubmapParameters: [lo, hi] of the candidates along one axis, additionally kept within `halo` cells
-// of the centre (never narrower than the reference's window: the halo is floor(radius / resolution + 0.5) + 1 at least)
-LIO_HD void lio_terr_window(const LioGridGeom& G, int a, int i, double centre, double radius, int halo, int& lo, int& hi)
-{
-    lo = lio_gm_bound_index(G, a, centre + radius);
-    hi = lio_gm_bound_index(G, a, centre - radius);
-    if (lo < i - halo) lo = i - halo;
-    if (hi > i + halo) hi = i + halo;
-}
 
 struct LioTerrV3 { double x, y, z; };
 
@@ -122,8 +113,6 @@ LIO_HD double lio_terr_eigen(int n, const double s[3], const double q[6], LioTer
     return r1 * scale + shift;
 }
 
-LIO_HD bool lio_terr_finite(float v) { return fabsf(v) <= FLT_MAX; }
-
 // One cell of the first kernel: smooth, the normal, slope, roughness, traversability.  T::at(i, j) = the input layer at
 // row i, column j, for every (i, j) of the grid within P.halo cells of (r, c).
 template <class T>
@@ -132,36 +121,18 @@ LIO_HD void lio_terr_cell(const LioTerrParams& P, const T& in, int r, int c, Lio
     const LioGridGeom& G = P.G;
     const double cx = lio_gm_centre(G, 0, r), cy = lio_gm_centre(G, 1, c);
     const float z = in.at(r, c);
-    o->valid = lio_terr_finite(z);
+    o->valid = lio_gm_finite(z);
     o->normal = o->few = o->degenerate = false;
-    // ---- smooth: MeanInRadiusFilter.cpp:59-79, every cell
-    {
-        int i0, i1, j0, j1;
-        lio_terr_window(G, 0, r, cx, P.r_smooth, P.halo, i0, i1);
-        lio_terr_window(G, 1, c, cy, P.r_smooth, P.halo, j0, j1);
-        const double r2 = P.r_smooth * P.r_smooth;
-        double sum = 0.0;
-        int cnt = 0;
-        for (int i = i0; i <= i1; ++i) {
-            const double dx = lio_gm_centre(G, 0, i) - cx, dx2 = dx * dx;
-            for (int j = j0; j <= j1; ++j) {
-                const double dy = lio_gm_centre(G, 1, j) - cy;
-                if (!(dx2 + dy * dy <= r2)) continue;
-                const float v = in.at(i, j);
-                if (!lio_terr_finite(v)) continue;
-                sum += (double)v;
-                ++cnt;
-            }
-        }
-        o->smooth = cnt ? (float)(sum / (double)cnt) : LIO_QNAN;
-    }
+    // ---- smooth: MeanInRadiusFilter.cpp:59-79, every cell.  Under the tile's halo, which is never narrower than the radius's own
+    const LioGfRadius S = { G, P.r_smooth, P.halo };
+    o->smooth = lio_gf_radius_cell<LIO_GF_MEAN>(S, in, r, c).value;
     // ---- normal
     double n[3] = { 0.0, 0.0, 0.0 };
     if (P.method == 0) {                                   // NormalVectorsFilter.cpp:195-251, where the centre is finite
         if (o->valid) {
             int i0, i1, j0, j1;
-            lio_terr_window(G, 0, r, cx, P.r_normal, P.halo, i0, i1);
-            lio_terr_window(G, 1, c, cy, P.r_normal, P.halo, j0, j1);
+            lio_gf_circle_window(G, 0, r, cx, P.r_normal, P.halo, i0, i1);
+            lio_gf_circle_window(G, 1, c, cy, P.r_normal, P.halo, j0, j1);
             const double r2 = P.r_normal * P.r_normal;
             double s[3] = { 0.0, 0.0, 0.0 }, q[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
             int cnt = 0;
@@ -171,7 +142,7 @@ LIO_HD void lio_terr_cell(const LioTerrParams& P, const T& in, int r, int c, Lio
                     const double y = lio_gm_centre(G, 1, j), dy = y - cy;
                     if (!(dx2 + dy * dy <= r2)) continue;
                     const float v = in.at(i, j);
-                    if (!lio_terr_finite(v)) continue;
+                    if (!lio_gm_finite(v)) continue;
                     const double w = (double)v;
                     s[0] += x; s[1] += y; s[2] += w;
                     q[0] += x * x; q[1] += y * x; q[2] += y * y; q[3] += w * x; q[4] += w * y; q[5] += w * w;
@@ -194,8 +165,8 @@ LIO_HD void lio_terr_cell(const LioTerrParams& P, const T& in, int r, int c, Lio
         const double centre = (double)z;
         double top = (double)ft, bottom = (double)fb, left = (double)fl, right = (double)fr;
         const int fc = o->valid ? 2 : 0;
-        const int kx = (lio_terr_finite(ft) ? 1 : 0) + fc + (lio_terr_finite(fb) ? 4 : 0);
-        const int ky = (lio_terr_finite(fl) ? 1 : 0) + fc + (lio_terr_finite(fr) ? 4 : 0);
+        const int kx = (lio_gm_finite(ft) ? 1 : 0) + fc + (lio_gm_finite(fb) ? 4 : 0);
+        const int ky = (lio_gm_finite(fl) ? 1 : 0) + fc + (lio_gm_finite(fr) ? 4 : 0);
         bool ok = true;
         double dX = 0.0, dY = 0.0;
         if (kx == 7 || kx == 5) dX = 2.0 * G.res;
@@ -231,75 +202,15 @@ LIO_HD void lio_terr_cell(const LioTerrParams& P, const T& in, int r, int c, Lio
     o->trav = t;
 }
 
-// scalar_sum_of_finites_op (FunctorsPlugin.hpp:3-12)
-LIO_HD float lio_terr_sum_of_finites(float a, float b)
+// The second kernel's cell is lio_gf_window_cell<LIO_GW_STDDEV, LIO_GW_CROP> on the slope layer over this window:
+// sqrt(sumOfFinites(square(slope - meanOfFinites(slope))) ./ numberOfFinites(slope)), SlidingWindowIterator.cpp:59-73.
+LIO_HD LioGfWindow lio_terr_edge_window(const LioTerrParams& P)
 {
-    const bool fa = lio_terr_finite(a), fb = lio_terr_finite(b);
-    if (fa && fb) return a + b;
-    if (fa) return a;
-    if (fb) return b;
-    return a + b;
-}
-
-// One cell of the second kernel: sqrt(sumOfFinites(square(slope - meanOfFinites(slope))) ./ numberOfFinites(slope)) over the
-// cropped window (SlidingWindowIterator.cpp:59-73), reduced serially in the block's column-major order.  T::at as above
-// on the slope layer, within P.margin cells.
-template <class T>
-LIO_HD float lio_terr_edge(const LioTerrParams& P, const T& slope, int r, int c)
-{
-    const int i0 = r - P.margin < 0 ? 0 : r - P.margin, i1 = r + P.margin > P.G.rows - 1 ? P.G.rows - 1 : r + P.margin;
-    const int j0 = c - P.margin < 0 ? 0 : c - P.margin, j1 = c + P.margin > P.G.cols - 1 ? P.G.cols - 1 : c + P.margin;
-    float sum = 0.0f;
-    int cnt = 0;
-    bool first = true;
-    for (int j = j0; j <= j1; ++j)
-        for (int i = i0; i <= i1; ++i) {
-            const float v = slope.at(i, j);
-            sum = first ? v : lio_terr_sum_of_finites(sum, v);
-            first = false;
-            cnt += v == v ? 1 : 0;
-        }
-    const float nf = (float)cnt;
-    const float mean = sum / nf;
-    float sq = 0.0f;
-    first = true;
-    for (int j = j0; j <= j1; ++j)
-        for (int i = i0; i <= i1; ++i) {
-            const float d = slope.at(i, j) - mean;
-            const float d2 = d * d;
-            sq = first ? d2 : lio_terr_sum_of_finites(sq, d2);
-            first = false;
-        }
-    return sqrtf(sq / nf);
-}
-
-// ---- the tile of the kernels that run one lane per cell (lio_terrain.hip, lio_medianfill.hip)
-#define TERR_ROWS 32               // the tile: rows are the contiguous axis of the column-major grid, a wave covers 32 x 2
-#define TERR_COLS 8
-
-struct TerrTile {                  // the LDS tile: rows [r0, r0 + pitch), columns from c0
-    const float* t;
-    int r0, c0, pitch;
-    __device__ __forceinline__ float at(int i, int j) const { return t[(i - r0) + (j - c0) * pitch]; }
-};
-
-// The workgroup's tile of `src` and h cells around it -> LDS (NaN outside the grid); the cell of this lane -> (r, c).
-// Ends with the barrier.
-__device__ __forceinline__ TerrTile terr_stage(const float* __restrict__ src, int rows, int cols, int h, float* tile, int& r, int& c)
-{
-    const int tiles_r = (rows + TERR_ROWS - 1) / TERR_ROWS;
-    const int tr0 = ((int)blockIdx.x % tiles_r) * TERR_ROWS, tc0 = ((int)blockIdx.x / tiles_r) * TERR_COLS;
-    const int pitch = TERR_ROWS + 2 * h, n = pitch * (TERR_COLS + 2 * h);
-    for (int k = (int)threadIdx.x; k < n; k += TERR_ROWS * TERR_COLS) {
-        const int i = tr0 - h + k % pitch, j = tc0 - h + k / pitch;
-        tile[k] = (i >= 0 && i < rows && j >= 0 && j < cols) ? src[(size_t)i + (size_t)j * (size_t)rows] : LIO_QNAN;
-    }
-    __syncthreads();
-    r = tr0 + ((int)threadIdx.x % TERR_ROWS);
-    c = tc0 + ((int)threadIdx.x / TERR_ROWS);
-    TerrTile T;
-    T.t = tile; T.r0 = tr0 - h; T.c0 = tc0 - h; T.pitch = pitch;
-    return T;
+    LioGfWindow W;
+    W.rows = P.G.rows; W.cols = P.G.cols;
+    W.size = 2 * P.margin + 1; W.margin = P.margin;
+    W.first_lin = 0;
+    return W;
 }
 
 // ---- the host side (lio_terrain.hip)

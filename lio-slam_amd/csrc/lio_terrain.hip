@@ -3,11 +3,12 @@
 //   main   smooth (MeanInRadiusFilter.cpp:59-79), the surface normal (NormalVectorsFilter.cpp: area :195-251, raster
 //          :304-394), slope = acos(normal_z), roughness = |input - smooth|, traversability and its two ThresholdFilters
 //   edges  the windowed standard deviation of slope (SlidingWindowMathExpressionFilter.cpp:74-92)
-// One lane per cell.  A workgroup owns a tile of TERR_ROWS x TERR_COLS cells and stages it with the halo of the largest
-// stencil into LDS: at a radius of 3 cells a value is read about 37 times by its neighbours' circles, once from memory.
-// `edges` needs the neighbours' slope, so it is a second kernel over the slope layer; everything else needs the input tile
-// only.  The per-cell arithmetic is in lio_terrain.h.  DESIGN.md section 4g lists the conventions (parity unpinned).
-// -ffp-contract=off.
+// One lane per cell.  A workgroup owns a tile of LIO_TILE_ROWS x LIO_TILE_COLS cells (lio_gridtile.h) and stages it with the
+// halo of the largest stencil into LDS: at a radius of 3 cells a value is read about 37 times by its neighbours' circles,
+// once from memory.  `edges` needs the neighbours' slope, so it is a second kernel over the slope layer; everything else
+// needs the input tile only.  The per-cell arithmetic is in lio_terrain.h; smooth and edges are the grid filters' own cells
+// (lio_gridfilter.h: MEAN in a radius, STDDEV over a cropped window), called from here without their counters.  DESIGN.md
+// section 4g lists the conventions (parity unpinned).  -ffp-contract=off.
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <math.h>
@@ -21,12 +22,12 @@
 
 // out: LIO_TERRAIN_N_LAYERS layers of rows x cols (this kernel writes all but LIO_TERRAIN_EDGES).  counters[0..3] += finite
 // input cells, normals written, circles of fewer than 3 points, degenerate covariances.
-__global__ __launch_bounds__(TERR_ROWS * TERR_COLS) void k_terr_main(LioTerrParams P, const float* __restrict__ in, float* __restrict__ out,
+__global__ __launch_bounds__(LIO_TILE_LANES) void k_terr_main(LioTerrParams P, const float* __restrict__ in, float* __restrict__ out,
                                                                       int* __restrict__ counters)
 {
     extern __shared__ __attribute__((aligned(16))) float s_tile[];
     int r, c;
-    const TerrTile T = terr_stage(in, P.G.rows, P.G.cols, P.halo, s_tile, r, c);
+    const LioTile T = lio_tile_stage(in, P.G.rows, P.G.cols, P.halo, s_tile, r, c);
     LioTerrCell o;
     o.valid = o.normal = o.few = o.degenerate = false;
     if (r < P.G.rows && c < P.G.cols) {
@@ -49,12 +50,13 @@ __global__ __launch_bounds__(TERR_ROWS * TERR_COLS) void k_terr_main(LioTerrPara
     }
 }
 
-__global__ __launch_bounds__(TERR_ROWS * TERR_COLS) void k_terr_edges(LioTerrParams P, const float* __restrict__ slope, float* __restrict__ edges)
+__global__ __launch_bounds__(LIO_TILE_LANES) void k_terr_edges(LioTerrParams P, const float* __restrict__ slope, float* __restrict__ edges)
 {
     extern __shared__ __attribute__((aligned(16))) float s_tile[];
     int r, c;
-    const TerrTile T = terr_stage(slope, P.G.rows, P.G.cols, P.margin, s_tile, r, c);
-    if (r < P.G.rows && c < P.G.cols) edges[(size_t)r + (size_t)c * (size_t)P.G.rows] = lio_terr_edge(P, T, r, c);
+    const LioTile T = lio_tile_stage(slope, P.G.rows, P.G.cols, P.margin, s_tile, r, c);
+    if (r < P.G.rows && c < P.G.cols)
+        edges[(size_t)r + (size_t)c * (size_t)P.G.rows] = lio_gf_window_cell<LIO_GW_STDDEV, LIO_GW_CROP>(lio_terr_edge_window(P), T, nullptr, r, c).value;
 }
 
 // ---- the host side ------------------------------------------------------------------------------------------------------
@@ -87,30 +89,25 @@ int lio_terrain_check(const lio_terrain_config* c, double resolution, LioTerrPla
         if (!std::isfinite(v) || v < 0.0f) return lio_fail(LIO_ERR_ARG, "criticals and weights must be finite and not negative");
     if (c->layers >> LIO_TERRAIN_N_LAYERS) return lio_fail(LIO_ERR_ARG, "layers has bits beyond LIO_TERRAIN_N_LAYERS");
     // the window: SlidingWindowIterator::setWindowLength (SlidingWindowIterator.cpp:35-42); an even explicit size throws there
-    long long window = c->edge_window_size;
-    if (window < 0 || (window != 0 && window % 2 == 0)) return lio_fail(LIO_ERR_ARG, "edge_window_size must be odd (0: from edge_window_length)");
-    if (window == 0) {
-        const double cells = std::round(c->edge_window_length / resolution);
-        if (cells > 2.0 * LIO_TERR_MAX_CELLS + 1.0) return lio_fail(LIO_ERR_ARG, "the edge window reaches further than 32 cells");
-        window = (long long)cells;
-        if (window % 2 != 1) ++window;
-    }
-    if ((window - 1) / 2 > LIO_TERR_MAX_CELLS) return lio_fail(LIO_ERR_ARG, "the edge window reaches further than 32 cells");
+    if (c->edge_window_size < 0 || (c->edge_window_size != 0 && c->edge_window_size % 2 == 0))
+        return lio_fail(LIO_ERR_ARG, "edge_window_size must be odd (0: from edge_window_length)");
+    LioGfWindow W;                                         // (its rows and columns come with the geometry: lio_terr_edge_window)
+    if (lio_gf_window_plan(0, 0, resolution, LIO_GW_CROP, c->edge_window_size, c->edge_window_length, &W))
+        return lio_fail(LIO_ERR_ARG, "the edge window reaches further than 32 cells");
     const bool fallback = c->normal_method == 0 && c->normal_radius <= 0.0;                // NormalVectorsFilter.cpp:39-51
     const int method = (c->normal_method == 1 || fallback) ? 1 : 0;
     double reach = c->smooth_radius / resolution;
     if (method == 0 && c->normal_radius / resolution > reach) reach = c->normal_radius / resolution;
-    if (reach > (double)LIO_TERR_MAX_CELLS) return lio_fail(LIO_ERR_ARG, "a radius reaches further than 32 cells");
+    if (reach > (double)LIO_TILE_MAX_REACH) return lio_fail(LIO_ERR_ARG, "a radius reaches further than 32 cells");
     LioTerrParams& P = plan->P;
     P.r_smooth = c->smooth_radius; P.r_normal = c->normal_radius;
     P.method = method; P.axis = c->normal_axis;
-    // a circle's window ends at trunc(i + 0.5 +- radius / resolution) up to the rounding of its corner: one cell of slack
-    P.halo = (int)std::floor(reach + 0.5) + 1;
-    P.margin = (int)((window - 1) / 2);
+    P.halo = lio_gf_halo(reach);
+    P.margin = W.margin;
     P.s_crit = c->slope_critical; P.r_crit = c->roughness_critical; P.w_s = c->slope_weight; P.w_r = c->roughness_weight;
     plan->mask = c->layers;
     plan->n_out = __builtin_popcount(c->layers);
-    plan->window = (int)window;
+    plan->window = W.size;
     plan->method_used = fallback ? 1 : 0;
     return LIO_OK;
 }
@@ -130,12 +127,11 @@ int lio_terrain_device(const float* d_grid, const LioTerrPlan& plan, float* laye
     HIPCHK(out.alloc(sizeof(float) * LIO_TERRAIN_N_LAYERS * n_cells));
     HIPCHK(counters.alloc(4 * sizeof(int)));
     HIPCHK(hipMemsetAsync(counters.p, 0, 4 * sizeof(int), s));
-    const unsigned tiles = (unsigned)((P.G.rows + TERR_ROWS - 1) / TERR_ROWS) * (unsigned)((P.G.cols + TERR_COLS - 1) / TERR_COLS);
-    const size_t lds_main = sizeof(float) * (size_t)(TERR_ROWS + 2 * P.halo) * (size_t)(TERR_COLS + 2 * P.halo);
-    const size_t lds_edges = sizeof(float) * (size_t)(TERR_ROWS + 2 * P.margin) * (size_t)(TERR_COLS + 2 * P.margin);
+    const unsigned tiles = lio_tile_count(P.G.rows, P.G.cols);
+    const size_t lds_main = lio_tile_lds_bytes(P.halo, sizeof(float)), lds_edges = lio_tile_lds_bytes(P.margin, sizeof(float));
     float* d_out = out.as<float>();
-    hipLaunchKernelGGL(k_terr_main, dim3(tiles), dim3(TERR_ROWS * TERR_COLS), lds_main, s, P, d_grid, d_out, counters.as<int>());
-    hipLaunchKernelGGL(k_terr_edges, dim3(tiles), dim3(TERR_ROWS * TERR_COLS), lds_edges, s, P, (const float*)(d_out + LIO_TERRAIN_SLOPE * n_cells),
+    hipLaunchKernelGGL(k_terr_main, dim3(tiles), dim3(LIO_TILE_LANES), lds_main, s, P, d_grid, d_out, counters.as<int>());
+    hipLaunchKernelGGL(k_terr_edges, dim3(tiles), dim3(LIO_TILE_LANES), lds_edges, s, P, (const float*)(d_out + LIO_TERRAIN_SLOPE * n_cells),
                        d_out + LIO_TERRAIN_EDGES * n_cells);
     if (layers) {                                          // the requested layers in enum order, neighbours in one copy
         size_t at = 0;

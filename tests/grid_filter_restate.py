@@ -21,7 +21,7 @@ QNAN_BITS = 0x7FC00000
 MIN, MEAN = 0, 1                                               # LIO_GF_*
 INSIDE, CROP, EMPTY, EDGE_MEAN = 0, 1, 2, 3                     # SlidingWindowIterator::EdgeHandling
 SUM, MEAN_OF_FINITES, MIN_OF_FINITES, MAX_OF_FINITES, NUMBER_OF_FINITES, STDDEV, WEIGHTED_SUM = range(7)
-MAX_CELLS = 32                                                 # LIO_TERR_MAX_CELLS
+MAX_CELLS = 32                                                 # LIO_TILE_MAX_REACH
 
 
 class Refused(ValueError):

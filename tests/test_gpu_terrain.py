@@ -28,7 +28,7 @@ AREA_MARGIN = 8.0
 # slope against float(arccos(double(normal_z))): no accuracy figure for acosf is in the ROCm installation's documents or
 # headers, so this is the project's existing derived 2 fp32 ulp bar, the restatement's rounding included
 ACOS_ULPS = 2
-TILE_ROWS, TILE_COLS = 32, 8                                   # TERR_ROWS x TERR_COLS of csrc/lio_terrain.hip
+TILE_ROWS, TILE_COLS = 32, 8                                   # LIO_TILE_ROWS x LIO_TILE_COLS of csrc/lio_gridtile.h
 
 
 def bits(a):
@@ -164,6 +164,32 @@ def test_tile_seams(pkg):
     d, info = check_stages(pkg, "seams", grid, res, pos, "seams raster", normal_method=1, **kw)
     assert info.edge_window_size == 7 and info.n_normal_cells == (rows - 2) * (cols - 2)
     check_stages(pkg, "seams", grid, res, pos, "seams area", **kw)
+
+
+@pytest.mark.parametrize("case, cfg", [
+    ("a smooth circle of 1 cell under the halo of area normals of 3 cells", dict(smooth_radius=0.25, normal_radius=0.75, edge_window_length=0.75)),
+    ("a smooth circle of 32 cells, raster normals: the largest tile", dict(smooth_radius=8.0, normal_method=1, edge_window_length=0.75)),
+    ("a window of 65: the largest margin", dict(smooth_radius=0.5, normal_method=1, edge_window_size=65)),
+])
+def test_smooth_and_edges_are_the_grid_filters_cells(pkg, case, cfg):
+    """33 x 9, one row and one column past a tile, with holes and a NaN border column: `smooth` is Grid.filter_radius(GF_MEAN)
+    and `edges` is Grid.filter_window(GW_STDDEV, GW_CROP) on the device's slope layer, every word with its NaN payload, and
+    every layer is the restatement's under the bars of check_stages"""
+    rows, cols, res, pos = TILE_ROWS + 1, TILE_COLS + 1, 0.25, (-7.3, 21.9)
+    rng = np.random.default_rng(33)
+    x, y = np.meshgrid(np.arange(rows) * res, np.arange(cols) * res, indexing="ij")
+    grid = (0.08 * x - 0.05 * y + rng.normal(0, 0.02, x.shape)).astype(f32)
+    grid[rng.uniform(size=grid.shape) < 0.1] = np.nan
+    grid[:, -1] = np.nan
+    d, info = check_stages(pkg, ("33 x 9", case), grid, res, pos, case, **cfg)
+    g = pkg.Grid()
+    g.set_layers(np.stack([grid, d["slope"]]), res, (rows * res, cols * res), pos)
+    g.filter_radius(0, 2, pkg.GF_MEAN, cfg["smooth_radius"])
+    assert np.array_equal(bits(g.layer(2)), bits(d["smooth"])), case
+    finfo = g.filter_window(1, 3, pkg.GW_STDDEV, pkg.GW_CROP, info.edge_window_size, 0.0)
+    assert finfo["window_size"] == info.edge_window_size == cfg.get("edge_window_size", 3)
+    assert np.array_equal(bits(g.layer(3)), bits(d["edges"])), case
+    g.close()
 
 
 def test_borders_and_holes(pkg):

@@ -148,7 +148,7 @@ static bool extremes(const std::vector<float>& layer, float* lo, float* hi)
 {
     unsigned mn = LIO_ORD_NO_MIN, mx = LIO_ORD_NO_MAX;
     for (float v : layer)
-        if (lio_gc_finite(v)) { const unsigned o = lio_f2ord(v); mn = o < mn ? o : mn; mx = o > mx ? o : mx; }
+        if (lio_gm_finite(v)) { const unsigned o = lio_f2ord(v); mn = o < mn ? o : mn; mx = o > mx ? o : mx; }
     *lo = lio_ord2f(mn); *hi = lio_ord2f(mx);
     return !(mn == LIO_ORD_NO_MIN && mx == LIO_ORD_NO_MAX);
 }
@@ -222,7 +222,7 @@ static int self_check()
                         for (size_t k = 0; k < la.size(); ++k) {
                             const float x = layer[(size_t)k], y = __builtin_bit_cast(float, la[k]);
                             const float want = lio_gc_clamp(x, -1.0f, 1.0f);
-                            if (lio_gc_finite(want) ? !(fabsf(y - want) <= 2.0f / 255.0f) : y == y) { bad("round trip", (long long)k); break; }
+                            if (lio_gm_finite(want) ? !(fabsf(y - want) <= 2.0f / 255.0f) : y == y) { bad("round trip", (long long)k); break; }
                         }
                     }
                 }
@@ -247,7 +247,7 @@ int main(int argc, char** argv)
         float lo = strtof(argv[6], nullptr), hi = strtof(argv[7], nullptr);
         const std::vector<float> layer = read_file<float>(argv[8], (size_t)rows * cols);
         if (lo != lo && hi != hi && !extremes(layer, &lo, &hi)) return 3;
-        if (!(hi > lo) || !lio_gc_finite(hi - lo)) return 3;
+        if (!(hi > lo) || !lio_gm_finite(hi - lo)) return 3;
         const size_t bytes = (size_t)rows * cols * ch * lio_gc_elem_bytes(depth);
         Bytes img(bytes, 0xa5);
         std::vector<unsigned char> written(bytes, 0);

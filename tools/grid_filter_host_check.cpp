@@ -11,7 +11,9 @@
 // holes and infinities -- and checks what can be said without a second implementation: no read outside the grid or the halo,
 // the counts against each other and against the sizes, a radius of 0 and a window of 1 against the layer itself, the number
 // of finites against a plain count.  It prints a checksum per case (FNV-1a over the layer's words) and "inconsistencies: 0"
-// at the end; the exit status is their number (capped).
+// at the end; the exit status is their number (capped).  Before that line it runs the terrain layers' cell (lio_terrain.h, both
+// normal methods) on a 33 x 9 grid with holes, the smooth radius below the normal radius, and prints how many cells it compared
+// and in how many `smooth` is not the MEAN filter's word or `edges` not STDDEV / CROP's on the same slope layer: 0.
 //   grid_filter_host_check filter KIND ROWS COLS RES PX PY OP EDGE SIZE P1 P2 IN OUT
 //       KIND 0 radius (P1 the radius), 1 window (P1 the length), 2 curvature, 3 threshold (OP = upper, P1 the threshold, P2
 //       set_to).  IN: the layer, column-major floats; for the threshold the layer to set follows; for LIO_GW_WEIGHTED_SUM the
@@ -26,6 +28,7 @@
 #include <vector>
 
 #include "../lio-slam_amd/csrc/lio_gridfilter.h"
+#include "../lio-slam_amd/csrc/lio_terrain.h"
 
 static long long g_bad = 0, g_outside = 0;
 
@@ -161,6 +164,51 @@ static void expect(bool ok, const char* what, const char* tag)
 
 static bool finite(float v) { return v - v == 0.0f; }
 
+// lio_terr_cell under the tile's halo against the filter under its own; the edge cell over the terrain plan's window against
+// the filter's plan.  Every read goes through the checked accessor.
+static void terrain_identity()
+{
+    const int rows = 33, cols = 9;
+    const double res = 0.25;
+    const std::vector<float> z = scene(rows, cols);
+    for (int method = 0; method < 2; ++method) {
+        LioTerrParams P;
+        memset(&P, 0, sizeof(P));
+        P.G = lio_gm_geom(rows, cols, res, 1e4, -3e4);
+        P.r_smooth = 1.5 * res; P.r_normal = 3.0 * res;
+        P.method = method; P.axis = 2;
+        P.halo = lio_gf_halo(method == 0 ? 3.0 : 1.5);
+        P.margin = 2;
+        P.s_crit = 0.6f; P.r_crit = 0.1f; P.w_s = 0.5f; P.w_r = 0.5f;
+        LioGfRadius S;
+        LioGfWindow W;
+        if (lio_gf_radius_plan(P.G, P.r_smooth, &S) || lio_gf_window_plan(rows, cols, res, LIO_GW_CROP, 2 * P.margin + 1, 0.0, &W)) { expect(false, "plans", "terrain"); return; }
+        std::vector<float> smooth(z.size()), slope(z.size());
+        long long compared = 0, differ = 0;
+        for (int c = 0; c < cols; ++c)
+            for (int r = 0; r < rows; ++r) {
+                const size_t at = (size_t)r + (size_t)c * rows;
+                const Checked tile = { z.data(), rows, cols, r, c, P.halo }, own = { z.data(), rows, cols, r, c, S.halo };
+                LioTerrCell o;
+                lio_terr_cell(P, tile, r, c, &o);
+                smooth[at] = o.smooth; slope[at] = o.slope;
+                const LioGfCell m = lio_gf_radius_cell<LIO_GF_MEAN>(S, own, r, c);
+                differ += word(o.smooth) != word(m.written ? m.value : LIO_QNAN);
+            }
+        for (int c = 0; c < cols; ++c)
+            for (int r = 0; r < rows; ++r) {
+                const Checked in = { slope.data(), rows, cols, r, c, P.margin };
+                const LioGfCell e = lio_gf_window_cell<LIO_GW_STDDEV, LIO_GW_CROP>(lio_terr_edge_window(P), in, nullptr, r, c);
+                const LioGfCell f = lio_gf_window_cell<LIO_GW_STDDEV, LIO_GW_CROP>(W, in, nullptr, r, c);
+                differ += word(e.value) != word(f.written ? f.value : LIO_QNAN);
+                ++compared;
+            }
+        expect(compared == (long long)rows * cols && differ == 0, "smooth is MEAN in the radius, edges is STDDEV over CROP", "terrain");
+        printf("terrain %dx%d method %d: smooth %08x slope %08x; cells compared %lld, words that differ %lld\n", rows, cols, method, checksum(smooth),
+               checksum(slope), compared, differ);
+    }
+}
+
 static int self_run()
 {
     const int shapes[][2] = { { 1, 1 }, { 1, 300 }, { 2, 2 }, { 8, 5 }, { 33, 9 }, { 69, 19 }, { 40, 9 } };
@@ -229,6 +277,7 @@ static int self_run()
                     }
             }
     }
+    terrain_identity();
     expect(g_outside == 0, "reads outside the grid or the halo", "all");
     printf("reads outside the grid or the halo: %lld\ninconsistencies: %lld\n", g_outside, g_bad);
     return (int)(g_bad > 100 ? 100 : g_bad);

@@ -75,7 +75,7 @@ static bool by_header(const Map& src, const LioGtXf& T, int height, double ratio
     for (int k = 0; k < n_src; ++k) {
         const int lin = reversed ? n_src - 1 - k : k;
         const float h = from_word(src.layer[height][lin]);
-        if (!(fabsf(h) <= FLT_MAX)) continue;
+        if (!lio_gm_finite(h)) continue;
         ++dst.counts[0];
         dst.counts[1] += lio_gt_cell(src.G, dst.G, T, sample_length, n_samples, lin, h, sink);
     }

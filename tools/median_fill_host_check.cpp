@@ -56,7 +56,7 @@ static void run_header(const std::vector<float>& g, const LioMfParams& P, const 
         R.mask.assign(mask_in, mask_in + n);
     } else {
         std::vector<unsigned char> a(n), b(n);
-        for (size_t k = 0; k < n; ++k) a[k] = lio_mf_finite(g[k]) ? 1 : 0;
+        for (size_t k = 0; k < n; ++k) a[k] = lio_gm_finite(g[k]) ? 1 : 0;
         for (int op = 0; op < LIO_MF_N_OPS; ++op) {
             const int rad = lio_mf_op_radius(P, op);
             const bool erode = lio_mf_op_erodes(op);
@@ -64,14 +64,14 @@ static void run_header(const std::vector<float>& g, const LioMfParams& P, const 
                 for (int j = 0; j < cols; ++j)
                     for (int i = 0; i < rows; ++i) {
                         int lo, hi;
-                        lio_mf_clip(i, rad, rows, lo, hi);
+                        lio_gm_clip(i, rad, rows, lo, hi);
                         const CheckedLine line = { a.data() + (size_t)j * (size_t)rows, 1, rows, i, rad };
                         b[(size_t)i + (size_t)j * (size_t)rows] = (unsigned char)lio_mf_line(line, lo, hi, erode);
                     }
                 for (int j = 0; j < cols; ++j)
                     for (int i = 0; i < rows; ++i) {
                         int lo, hi;
-                        lio_mf_clip(j, rad, cols, lo, hi);
+                        lio_gm_clip(j, rad, cols, lo, hi);
                         const CheckedLine line = { b.data() + (size_t)i, rows, cols, j, rad };
                         a[(size_t)i + (size_t)j * (size_t)rows] = (unsigned char)lio_mf_line(line, lo, hi, erode);
                     }
@@ -117,7 +117,7 @@ static float plain_median(const std::vector<float>& g, int rows, int cols, int r
     for (int j = std::max(c - R, 0); j <= std::min(c + R, cols - 1); ++j)
         for (int i = std::max(r - R, 0); i <= std::min(r + R, rows - 1); ++i) {
             const float v = g[(size_t)i + (size_t)j * (size_t)rows];
-            if (lio_mf_finite(v)) keys.push_back(lio_f2ord(v));
+            if (lio_gm_finite(v)) keys.push_back(lio_f2ord(v));
         }
     if (keys.empty()) return __builtin_bit_cast(float, 0x7fc00000u);
     std::sort(keys.begin(), keys.end());
@@ -129,7 +129,7 @@ static void run_plain(const std::vector<float>& g, const LioMfParams& P, const f
     const int rows = P.rows, cols = P.cols;
     const size_t n = (size_t)rows * (size_t)cols;
     std::vector<unsigned char> valid(n), m;
-    for (size_t k = 0; k < n; ++k) valid[k] = lio_mf_finite(g[k]) ? 1 : 0;
+    for (size_t k = 0; k < n; ++k) valid[k] = lio_gm_finite(g[k]) ? 1 : 0;
     m = morph3(morph3(valid, rows, cols, true), rows, cols, false);                     // :220-221
     R.cleaned.assign(n, 0.0f);
     for (size_t k = 0; k < n; ++k) R.cleaned[k] = m[k] ? 1.0f : 0.0f;
@@ -143,12 +143,12 @@ static void run_plain(const std::vector<float>& g, const LioMfParams& P, const f
     for (int c = 0; c < cols; ++c)
         for (int r = 0; r < rows; ++r) {
             const size_t at = (size_t)r + (size_t)c * (size_t)rows;
-            const bool fin = lio_mf_finite(g[at]), masked = R.mask[at] != 0.0f;
+            const bool fin = lio_gm_finite(g[at]), masked = R.mask[at] != 0.0f;
             float out = g[at];
             if (!fin && masked) out = plain_median(g, rows, cols, r, c, P.r_fill);
             else if (P.filter_existing && masked) { out = plain_median(g, rows, cols, r, c, P.r_existing); ++R.counts[3]; }
             memcpy(&R.filled[at], &out, 4);
-            R.counts[0] += !fin; R.counts[1] += masked; R.counts[2] += !fin && lio_mf_finite(out); R.counts[4] += !lio_mf_finite(out);
+            R.counts[0] += !fin; R.counts[1] += masked; R.counts[2] += !fin && lio_gm_finite(out); R.counts[4] += !lio_gm_finite(out);
         }
 }
 
@@ -167,7 +167,7 @@ static uint64_t checksum(const Result& R)
 static bool plan(LioMfParams& P, int rows, int cols, int r_fill, int r_existing, int filter, int n_iter)
 {
     memset(&P, 0, sizeof(P));
-    if (n_iter < 0 || n_iter > LIO_MF_MAX_ITERATIONS || r_fill < 0 || r_fill > LIO_TERR_MAX_CELLS || r_existing < 0 || r_existing > LIO_TERR_MAX_CELLS) return false;
+    if (n_iter < 0 || n_iter > LIO_MF_MAX_ITERATIONS || r_fill < 0 || r_fill > LIO_TILE_MAX_REACH || r_existing < 0 || r_existing > LIO_TILE_MAX_REACH) return false;
     P.rows = rows; P.cols = cols; P.r_fill = r_fill; P.r_existing = r_existing; P.filter_existing = filter;
     P.n_iter = n_iter; P.n_dilate = n_iter > 1 ? n_iter : 1;
     P.halo_mask = 2 + P.n_dilate + P.n_iter;

@@ -39,7 +39,7 @@ struct ElevLine {                  // a column of the elevation layer as the off
     float at(int q) const
     {
         float e = col.at(q);
-        if (!(fabsf(e) <= FLT_MAX)) e = fill;
+        if (!lio_gm_finite(e)) e = fill;
         return lio_sdf_init(e, h, inv_res, cls);
     }
 };
@@ -120,7 +120,7 @@ static bool build_field(const std::vector<float>& elev, int rows, int cols, doub
     float mn = INFINITY, mx = -INFINITY;
     F.n_nan = 0;
     for (float v : elev) {
-        if (fabsf(v) <= FLT_MAX) { mn = fminf(mn, v); mx = fmaxf(mx, v); } else ++F.n_nan;
+        if (lio_gm_finite(v)) { mn = fminf(mn, v); mx = fmaxf(mx, v); } else ++F.n_nan;
     }
     if (!(mn <= mx) || (F.n_nan && policy == 0)) return false;
     F.e_min = mn; F.e_max = mx;
@@ -171,7 +171,7 @@ static void check_field(const char* name, const std::vector<float>& elev, int ro
     Field F;
     if (!build_field(elev, rows, cols, res, min_h, max_h, policy, F)) { printf("field %-16s %3d x %3d: refused (%d non-finite)\n", name, rows, cols, F.n_nan); return; }
     std::vector<float> clean = elev;
-    for (float& v : clean) if (!(fabsf(v) <= FLT_MAX)) v = F.e_min;
+    for (float& v : clean) if (!lio_gm_finite(v)) v = F.e_min;
     double worst = 0.0;
     long long bad = 0;
     for (int z = 0; n2 && z < F.L.layers; ++z)
