@@ -1675,6 +1675,56 @@ int  lio_grid_delete_layers(lio_grid *g, const int32_t *layer_ids, int32_t n_lay
  * of the six, in milliseconds (0 where none was launched). */
 int  lio_grid_filter_debug_kernel_ms(int32_t enable, float *ms);
 
+/* ------------------------------------------------ a layer from several by an expression (grid_map_filters' MathExpressionFilter) */
+/* An EigenLab expression (Parser<Eigen::MatrixXf>) over the layers of a lio_grid, stored as a layer of the same object.  The
+ * text is compiled on the host by a port of the parser's chunk passes (split into chunks, negations, powers, products, sums,
+ * functions -- in that order, each left to right) into a postfix program, which the device interprets one lane per cell;
+ * DESIGN.md section 4q states the conventions and the labelled deviations, parity is against the restatement
+ * (tests/grid_expression_restate.py; parity unpinned).  A value is a full layer or a scalar.
+ *   + - .+ .-            layer with layer, layer with scalar, scalar with layer
+ *   * / .* ./            with a scalar on either side; .* ./ also layer with layer
+ *   ^ .^                 with a scalar on either side; .^ also layer with layer
+ *   -x                   x * -1, before powers: -a^2 is (-a)^2
+ *   abs sqrt square      float; square is x * x
+ *   cwiseMin(a, b)       b < a ? b : a;  cwiseMax(a, b): a < b ? b : a, also on a NaN (Eigen's scalar path)
+ *   acos                 acosf, the call behind LIO_TERRAIN_SLOPE
+ *   exp log sin cos tan asin, and pow: the fp64 function on the widened argument, narrowed once; log10 is that log times
+ *                        (float)(1.0 / log(10)), a float product
+ *   sumOfFinites meanOfFinites minOfFinites maxOfFinites numberOfFinites
+ *                        of a layer-valued argument: one scalar for the whole map, serial in memory order (column-major), the
+ *                        first coefficient initialises, FunctorsPlugin.hpp's functors; numberOfFinites counts x == x.  Of a
+ *                        scalar argument: the value, x == x ? 1 : 0, their quotient.
+ * names[k] is the variable that stands for layer layer_ids[k]: at most 16 names of [A-Za-z0-9_], not empty, not starting with a
+ * digit, each once; ids in 0 .. 15.  A name that is also a function's is the layer.  A listed layer that the object lacks is
+ * refused only when the expression reads it.  out_layer may be a layer the expression reads: the result is computed from the old
+ * values.  A failure leaves the object's layer set as it was.
+ * LIO_ERR_ARG, decided before the object or a device is touched, lio_last_error naming the construct: matrix literals [..],
+ * ranges with ':', index groups name(..), assignment, * / ^ between two layers, trace norm size transpose conjugate adjoint zeros
+ * ones eye prod, sum mean min max absmax (their order is the Eigen build's), a second (dimension) argument, an unknown name, a
+ * function without '(', a missing bracket, an empty expression, what does not reduce to one value (a leading '+'), a scalar
+ * result.  LIO_ERR_CAPACITY: an expression above 1024 bytes, 128 ops, a stack of 16 or 8 map-wide reductions. */
+struct lio_grid_expression_info {
+    int32_t  rows, cols;
+    int32_t  n_ops, n_passes;     /* ops over all passes; passes = reductions + 1 */
+    uint32_t layers_read;         /* bit k: layer k is read                        */
+    int32_t  stack_depth;
+    int64_t  n_finite;            /* finite cells of the result (0 from _check)    */
+};
+typedef struct lio_grid_expression_info lio_grid_expression_info;
+/* compile only: no grid, no device (rows = cols = 0) */
+int  lio_grid_expression_check(const char *expression, const char *const *names, const int32_t *layer_ids,
+                               int32_t n_names, lio_grid_expression_info *info);
+int  lio_grid_filter_expression(lio_grid *g, const char *expression, const char *const *names,
+                                const int32_t *layer_ids, int32_t n_names, int32_t out_layer,
+                                lio_grid_expression_info *info);
+/* The same program through the same header text on the host, serially.  layers: n_names layers of rows x cols, column-major,
+ * in the order of names; out: rows x cols. */
+int  lio_debug_grid_expression_host(const char *expression, const char *const *names, int32_t n_names,
+                                    const float *layers, int32_t rows, int32_t cols, float *out);
+/* Measurement hook (tools/grid_expression_cost.py): the reduction passes and the storing pass of the calling thread's last
+ * lio_grid_filter_expression, in milliseconds. */
+int  lio_grid_expression_debug_kernel_ms(int32_t enable, float ms[2]);
+
 #ifdef __cplusplus
 }
 #endif

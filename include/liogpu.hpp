@@ -528,6 +528,12 @@ public:
     // DuplicationFilter and DeletionFilter
     void duplicateLayer(int32_t in_layer, int32_t out_layer) { check(lio_grid_duplicate_layer(g_, in_layer, out_layer), "lio_grid_duplicate_layer"); }
     void deleteLayers(const int32_t* layer_ids, int32_t n_layers) { check(lio_grid_delete_layers(g_, layer_ids, n_layers), "lio_grid_delete_layers"); }
+    // MathExpressionFilter: an EigenLab expression over the layers names[k] -> layer_ids[k], stored as out_layer (which it may read)
+    void filterMathExpression(const char* expression, const char* const* names, const int32_t* layer_ids, int32_t n_names, int32_t out_layer,
+                              lio_grid_expression_info* info = nullptr)
+    {
+        check(lio_grid_filter_expression(g_, expression, names, layer_ids, n_names, out_layer, info), "lio_grid_filter_expression");
+    }
     void layer(int32_t k, float* out, size_t cap_floats) { check(lio_grid_get_layer(g_, k, out, cap_floats), "lio_grid_get_layer"); }
     lio_grid_desc info()
     {

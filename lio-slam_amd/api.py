@@ -322,6 +322,10 @@ GRID_FROM_OCCUPANCY_INFO_DTYPE = np.dtype({"names": ["rows", "cols", "geometry_r
 GRID_FILTER_INFO_DTYPE = np.dtype({"names": ["rows", "cols", "window_size", "pad", "n_visited", "n_written", "n_changed"],
                                    "formats": [np.int32, np.int32, np.int32, np.int32, np.int64, np.int64, np.int64], "offsets": [0, 4, 8, 12, 16, 24, 32],
                                    "itemsize": 40})
+# lio_grid_expression_info (tests/test_grid_expression_capi.py holds the layout to gcc's)
+GRID_EXPRESSION_INFO_DTYPE = np.dtype({"names": ["rows", "cols", "n_ops", "n_passes", "layers_read", "stack_depth", "n_finite"],
+                                       "formats": [np.int32, np.int32, np.int32, np.int32, np.uint32, np.int32, np.int64],
+                                       "offsets": [0, 4, 8, 12, 16, 20, 24], "itemsize": 32})
 GF_MIN, GF_MEAN = 0, 1
 GW_INSIDE, GW_CROP, GW_EMPTY, GW_EDGE_MEAN = 0, 1, 2, 3
 GW_SUM, GW_MEAN_OF_FINITES, GW_MIN_OF_FINITES, GW_MAX_OF_FINITES, GW_NUMBER_OF_FINITES, GW_STDDEV, GW_WEIGHTED_SUM = range(7)
@@ -524,6 +528,10 @@ CAPI = {
     "lio_grid_duplicate_layer": [vp, i32, i32],
     "lio_grid_delete_layers": [vp, pi, i32],
     "lio_grid_filter_debug_kernel_ms": [i32, pf],
+    "lio_grid_expression_check": [C.c_char_p, P(C.c_char_p), pi, i32, vp],
+    "lio_grid_filter_expression": [vp, C.c_char_p, P(C.c_char_p), pi, i32, i32, vp],
+    "lio_debug_grid_expression_host": [C.c_char_p, P(C.c_char_p), i32, pf, i32, i32, pf],
+    "lio_grid_expression_debug_kernel_ms": [i32, pf],
 }
 CAPI = {name: sig if isinstance(sig, tuple) else (C.c_int, sig) for name, sig in CAPI.items()}     # -> (restype, argtypes), all of them
 EXPORTS = list(CAPI)
@@ -1524,6 +1532,33 @@ def footprint_polygons(poses, length, width):
     return rec, verts.reshape(-1, 2)
 
 
+def _expression_names(names):
+    """{variable: layer id} -> the names, the ids and their number as lio_grid_filter_expression takes them"""
+    keys = [str(k).encode() for k in names]
+    ids = [int(v) for v in names.values()]
+    return (C.c_char_p * len(keys))(*keys), (C.c_int32 * len(ids))(*ids), len(keys)
+
+
+def grid_expression_check(expression, names):
+    """Compiles `expression` over `names` ({variable: layer id}) without a grid or a device; LioError names what is refused.
+    -> a GRID_EXPRESSION_INFO_DTYPE record (n_ops, n_passes, layers_read, stack_depth)"""
+    info = np.zeros(1, GRID_EXPRESSION_INFO_DTYPE)
+    _check(load_library().lio_grid_expression_check(expression.encode(), *_expression_names(names), info.ctypes.data), "lio_grid_expression_check")
+    return info[0]
+
+
+def grid_expression_host(expression, names, layers):
+    """The program of `expression` run serially on the host over layers [n, rows, cols] float32, names[k] standing for
+    layers[k] (the text the kernels run).  -> [rows, cols] float32"""
+    a = np.asarray(layers, np.float32)
+    flat = np.ascontiguousarray(np.stack([l.ravel(order="F") for l in a]))
+    out = np.empty(a.shape[1:], np.float32, order="F")
+    keys = [str(k).encode() for k in names]
+    _check(load_library().lio_debug_grid_expression_host(expression.encode(), (C.c_char_p * len(keys))(*keys), len(keys), _f32p(flat), a.shape[1], a.shape[2],
+                                                         _f32p(out)), "lio_debug_grid_expression_host")
+    return out
+
+
 class Grid(_Owner):
     """A set of up to GRID_MAX_LAYERS [rows, cols] float32 layers resident on the device: upload them (or let
     KeyframeStore.planning_grid leave its grids here), then sample them at positions."""
@@ -1794,6 +1829,14 @@ class Grid(_Owner):
         """DeletionFilter: the listed layers leave the object"""
         ids = np.ascontiguousarray(layer_ids, np.int32).reshape(-1)
         _check(self.lib.lio_grid_delete_layers(self.h, ids.ctypes.data_as(C.POINTER(C.c_int32)) if len(ids) else None, len(ids)), "lio_grid_delete_layers")
+
+    def filter_expression(self, expression, names, out_layer):
+        """MathExpressionFilter: the EigenLab `expression` over the layers that `names` ({variable: layer id}) lists, stored as
+        `out_layer`, which may be a layer it reads.  -> a GRID_EXPRESSION_INFO_DTYPE record"""
+        info = np.zeros(1, GRID_EXPRESSION_INFO_DTYPE)
+        _check(self.lib.lio_grid_filter_expression(self.h, expression.encode(), *_expression_names(names), int(out_layer), info.ctypes.data),
+               "lio_grid_filter_expression")
+        return info[0]
 
     def memory(self):
         """-> bytes the object holds on the device"""
